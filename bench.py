@@ -7,7 +7,7 @@ H_A / Y_A / Y priors, backward into the adjacency, Adam + projection, and the
 per-step monitoring forward (:290-296).  Inputs are resident in HBM before the
 timed region.  Prints ONE JSON line (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synthetic-10k-hsic|cora-shape-hsic|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synthetic-10k-hsic|cora-shape-hsic|...] [--dump-outputs DIR]
 
 N > 1 runs ONE attack, row-block sharded over N ranks, one per GPU (every N x N pass split by
 rows, collectives over RCCL inside the timed region); `value` is the steps of that attack per second ("scaling":
@@ -366,6 +366,35 @@ def timed_region(step_fn, steps, warmup, sync, world, dist=None, device=None, to
     return dt
 
 
+DUMP_MAX_ENTRIES = 1 << 23      # adj_changes entries --dump-outputs writes at most (32 MB of float32)
+
+
+def dump_outputs(out_dir, eng, victim_logp, torch):
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy in float32 -- `adj_changes`,
+    the learnable adjacency after the step's Adam pass and projection (packed lower triangle, torch.tril_indices(n, n, -1)
+    order), and `victim_logp`, the monitoring forward's log-probabilities (n x nclass; absent under --no-monitor).  A
+    packed adjacency longer than DUMP_MAX_ENTRIES is written as `adj_changes_sample`: one entry in each of
+    DUMP_MAX_ENTRIES equal strides, at offsets drawn from a fixed seed -- the same positions on every run of a workload."""
+    os.makedirs(out_dir, exist_ok=True)
+    packed = eng.get_adj_changes()
+    m = packed.numel()
+    outs = {}
+    if m > DUMP_MAX_ENTRIES:
+        stride = m // DUMP_MAX_ENTRIES
+        idx = np.arange(DUMP_MAX_ENTRIES, dtype=np.int64) * stride + np.random.RandomState(0).randint(0, stride, DUMP_MAX_ENTRIES)
+        outs["adj_changes_sample"] = packed[torch.as_tensor(idx, device=packed.device)]
+    else:
+        outs["adj_changes"] = packed
+    if victim_logp is not None:
+        outs["victim_logp"] = victim_logp
+    shapes = {}
+    for name, t in outs.items():
+        arr = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return {"dir": os.path.abspath(out_dir), "arrays": shapes, "adj_changes_entries": m}
+
+
 def aggregate_value(world, steps, dt):
     """Whole-job throughput of N independent replicas (weak scaling): every rank ran `steps` attack steps."""
     return world * steps / dt
@@ -626,7 +655,12 @@ def main(argv=None):
                     help="run the two --pmc child passes even with --no-split-probe (the fused MSELoss / KL workloads: roofline.traffic per step)")
     ap.add_argument("--no-split-probe", action="store_true",
                     help="skip the extra runs at N = 1 (other evaluation of the N x N x N product, Cora-shape workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB: "
+                         "dump_outputs); N = 1 only")
     a = ap.parse_args(argv)
+    if a.dump_outputs and max(a.gpus or 1, int(os.environ.get("WORLD_SIZE", 1))) > 1:
+        raise SystemExit("bench.py: --dump-outputs is for the 1-GPU run (N = 1)")
 
     if "WORLD_SIZE" not in os.environ:
         if (a.gpus or 1) > 1:
@@ -685,11 +719,14 @@ def main(argv=None):
                 stepper.monitor(last=last)
     else:
         eng, inp, adj_dev = build_engine(pkg, torch, dev, a.workload, a.seed)
+        last_logp = [None]          # the last monitoring forward's output (--dump-outputs)
 
         def one_step(last=False):
             eng.step()
             if monitor:
-                eng.monitor()
+                logp, _ = eng.monitor()
+                if a.dump_outputs:
+                    last_logp[0] = logp
 
     # (a row-block rank's monitoring forward forks the NEXT step's product: the last warm-up step and the last timed step say
     # `last`, so the timed region holds exactly K steps' worth of products -- none started in front of it, none left behind it)
@@ -714,6 +751,7 @@ def main(argv=None):
     eng_path = dict(eng.path_stats(), fused_steps=eng.fused_steps(), gram_split_steps=eng.gram_split_steps(),
                     masked_fused_steps=eng.masked_fused_steps(), cut_product_steps=eng.cut_product_steps())
     stepper_exchanges = ((stepper.exchanges - ex0) / a.steps) if stepper is not None else None      # of the timed steps
+    dumped = dump_outputs(a.dump_outputs, eng, last_logp[0], torch) if a.dump_outputs else None      # untimed
 
     # the same N x N x N product alone on the chip (no side-stream company), for the roofline's "alone" figure
     alone_ms = None
@@ -1019,6 +1057,8 @@ def main(argv=None):
                                                "note": "launch- and VALU-bound kernels included: ~75 node-level launches per step"}
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -144,6 +144,47 @@ def test_bench_gpus_flag_starts_ranks_and_refuses_a_mismatch(monkeypatch, capsys
         bench.main(["--gpus", "4", "--no-cpu-baseline"])
 
 
+def test_dump_outputs_writes_the_last_step_within_64_mb(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: the packed adj_changes the engine holds after the timed steps and the last monitoring
+    forward's output, as float32 .npy files; a packed adjacency above DUMP_MAX_ENTRIES as a sample whose positions do not
+    change from run to run (DUMP_MAX_ENTRIES itself keeps the largest workload's files under 64 MB); refused at N > 1."""
+    import numpy as np
+    import bench
+
+    class FakeEngine:
+        def __init__(self, packed):
+            self.packed = packed
+
+        def get_adj_changes(self):
+            return self.packed
+
+    n_max = max(v[0] for v in bench.WORKLOADS.values())
+    nclass_max = max(v[2] for v in bench.WORKLOADS.values())
+    assert 4 * (min(bench.DUMP_MAX_ENTRIES, n_max * (n_max - 1) // 2) + n_max * nclass_max) <= 64 << 20
+    packed = torch.arange(1000, dtype=torch.float32) * 0.5
+    logp = torch.randn(45, 3)
+    d = tmp_path / "full"
+    r = bench.dump_outputs(str(d), FakeEngine(packed), logp, torch)
+    assert r["arrays"] == {"adj_changes": [1000], "victim_logp": [45, 3]}
+    a, lp = np.load(d / "adj_changes.npy"), np.load(d / "victim_logp.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, packed.numpy()) and np.array_equal(lp, logp.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 64)
+    samples = []
+    for k in range(2):
+        d = tmp_path / f"sample{k}"
+        r = bench.dump_outputs(str(d), FakeEngine(packed), None, torch)
+        assert r["arrays"] == {"adj_changes_sample": [64]} and r["adj_changes_entries"] == 1000
+        assert sorted(os.listdir(d)) == ["adj_changes_sample.npy"]
+        samples.append(np.load(d / "adj_changes_sample.npy"))
+    pos = (samples[0] * 2).astype(np.int64)                     # entry i holds i / 2: the sample's positions
+    assert np.array_equal(samples[0], samples[1]) and np.all(np.diff(pos) > 0) and pos[-1] < 1000
+    assert np.array_equal(pos // (1000 // 64), np.arange(64))   # one entry in each stride
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    with pytest.raises(SystemExit, match="dump-outputs"):
+        bench.main(["--gpus", "2", "--dump-outputs", str(tmp_path / "x")])
+
+
 def test_live_traffic_accounting(monkeypatch):
     """bench.live_traffic: the two `rocprofv3 --pmc` child passes (FETCH_SIZE, WRITE_SIZE; --kernel-trace only beside them) and
     the accounting of their CSVs -- 2 x FETCH_SIZE + WRITE_SIZE per kernel, the product's main grid per launch, everything
