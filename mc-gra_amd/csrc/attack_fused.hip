@@ -543,8 +543,10 @@ static int fused_step_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* ex) 
   const double k1 = w1 * 1000 * AP_C1, k2 = w2 * 100 * AP_C2, k6 = w6 * 100 * AP_C6, k7 = w7 * AP_C7;
   const double k9 = w9 * AP_C9, k10 = w10 * AP_C10, n2 = (double)n * n;
   const bool use1 = !mse && w1 != 0, use2 = !mse && w2 != 0;
-  const float kmse1 = kl ? (float)(k1 / n) : mse ? (float)(k1 * 2.0 / n2) : 0.f;      // k_loss_elem's multipliers; KL: k / batch (batchmean over rows)
-  const float kmse2 = kl ? (float)(k2 / n) : mse ? (float)(k2 * 2.0 / n2) : 0.f;
+  // (TEST-ONLY mutation 3 drops the measure's per-pair terms c1 / c2 from the decode and the tail: both multipliers zero)
+  const bool no_calc = h->test_mutate == 3;
+  const float kmse1 = no_calc ? 0.f : kl ? (float)(k1 / n) : mse ? (float)(k1 * 2.0 / n2) : 0.f;      // k_loss_elem's multipliers; KL: k / batch (batchmean over rows)
+  const float kmse2 = no_calc ? 0.f : kl ? (float)(k2 / n) : mse ? (float)(k2 * 2.0 / n2) : 0.f;
   const float* em = h->Hu + h->off[Le - 1];
   const int he = h->wdt[Le - 1];
   const float a1 = use1 ? 2.f * (float)(sg * k1) : 0.f, a2 = use2 ? 2.f * (float)(sg * k2) : 0.f;
@@ -673,6 +675,10 @@ static int fused_step_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* ex) 
         // calc_kl's row statistics (logsumexp of adj_norm's and of modified_adj1's rows) from M, r and Zn: the decode backward and
         // the tail need those of EVERY row (d c2 / d A1_ij + d c2 / d A1_ji), so a row-block rank gathers its peers' first
         (void)fl_decode_stats(st, n, R0, R1, he, h->Zn, h->hmax, h->Zpair, h->M, ld, h->r, h->klpart, h->klA, h->kl1);
+        if (h->test_mutate == 4) {      // TEST-ONLY mutation: the row statistics wiped before the decode and the tail read them
+          MCGRA_HIP(hipMemsetAsync(h->klA, 0, sizeof(float) * (size_t)n, st));
+          MCGRA_HIP(hipMemsetAsync(h->kl1, 0, sizeof(float) * (size_t)n, st));
+        }
         if (h->sharded) rows_to_stage2(h, st, narrow_stage(h), 1, h->klA, 1, 0, 1, h->kl1, 1, 1);
       }
       if (kl) { FS_XCHG(h->fs_state, 12, X_SG(h)) }
@@ -1127,7 +1133,7 @@ int mcgra_attack_shard_scalars(mcgra_attack_t* h, void* stream, double* out) {
 }
 
 int mcgra_attack_test_mutate(mcgra_attack_t* h, int what) {
-  if (!h || what < 0 || what > 2) { set_error("test_mutate: what = %d", what); return MCGRA_EINVAL; }
+  if (!h || what < 0 || what > 4) { set_error("test_mutate: what = %d", what); return MCGRA_EINVAL; }
   if (what && !h->testing) {
     set_error("mcgra_attack_test_mutate: refused -- this engine was not created under MCGRA_TESTING=1 (a defect injector for the "
               "parity suite's mutation guards, never part of a real run)");
@@ -1136,7 +1142,10 @@ int mcgra_attack_test_mutate(mcgra_attack_t* h, int what) {
   h->test_mutate = what;
   if (what)
     fprintf(stderr, "[mcgra] TEST MUTATION ARMED on engine %p: the fused step now %s -- its gradients are WRONG on purpose\n", (void*)h,
-            what == 1 ? "wipes the N x N x N product's result" : "drops the rank-k terms of its tail");
+            what == 1   ? "wipes the N x N x N product's result"
+            : what == 2 ? "drops the rank-k terms of its tail"
+            : what == 3 ? "drops the measure's per-pair terms (MSELoss / KL c1, c2)"
+                        : "wipes the KL row statistics");
   return 0;
 }
 

@@ -411,8 +411,9 @@ class AttackEngine:
         return ms.value
 
     def test_mutate(self, what):
-        """TEST ONLY (mcgra_attack_test_mutate): 'p1' wipes the product's result, 'rk' drops the tail's rank-k terms, None disarms."""
-        check(lib.mcgra_attack_test_mutate(self._h, {None: 0, "p1": 1, "rk": 2}[what]))
+        """TEST ONLY (mcgra_attack_test_mutate): 'p1' wipes the product's result, 'rk' drops the tail's rank-k terms, 'calc' drops
+        the MSELoss / KL per-pair terms c1 / c2, 'klstats' wipes the KL row statistics, None disarms."""
+        check(lib.mcgra_attack_test_mutate(self._h, {None: 0, "p1": 1, "rk": 2, "calc": 3, "klstats": 4}[what]))
 
     def profile(self, enable=True):
         check(lib.mcgra_attack_profile(self._h, int(enable)))

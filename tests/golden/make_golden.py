@@ -3,7 +3,8 @@
 
 Runs only in the build container (needs /root/reference); the fixtures it
 writes under tests/golden/ are data (inputs + the reference's outputs) and are
-what travels to the GPU box.  Usage:  python tests/golden/make_golden.py [--only small|ops|cw|cora|cora_sparse|mid|bench10k|citeseer]
+what travels to the GPU box.  Usage:  python tests/golden/make_golden.py [--only small|ops|cw|cora|cora_sparse|mid|bench10k|citeseer|
+                      bench10k_mse|bench10k_kl|bench10k_mse_ref64|bench10k_kl_ref64]
 
 Environment shims applied before importing the reference (none of them is on
 the computed path):
@@ -1082,5 +1083,10 @@ if __name__ == "__main__":
             gen_bench(tmp)
         if a.only in ("bench10k_ref64",):   # the reference's own code in float64 on the bench's starts: ~45 GB, ~30 min
             gen_bench_ref64(tmp)
+        for m in ("mse", "kl"):             # the fused MSELoss / KL workloads at the bench's N = 10 000: not part of "all"
+            if a.only == f"bench10k_{m}":
+                gen_bench(tmp, workload=f"synthetic-10k-{m}", tag=f"bench10k_{m}")
+            if a.only == f"bench10k_{m}_ref64":          # needs bench10k_<m>_fp64.npz (make_truth64.py bench10k_<m>)
+                gen_bench_ref64(tmp, workload=f"synthetic-10k-{m}", tag=f"bench10k_{m}")
         if a.only in ("check_ref64",):
             check_ref64(tmp)

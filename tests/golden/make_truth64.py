@@ -5,10 +5,12 @@ own float32 run is from the exact gradient at N = 10 000 (its Gram evaluation of
 O(1) Gram entries in fp32), which bounds what "equal to the reference" can mean per entry at that size.
 
     python tests/golden/make_truth64.py          (~10 min and ~30 GB per start on 8 cores)
+    python tests/golden/make_truth64.py bench10k_mse | bench10k_kl   (the same for bench.py's synthetic-10k-mse / -kl:
+                                                 needs make_golden.py --only bench10k_mse / bench10k_kl first)
     python tests/golden/make_truth64.py mid      (the n = 1200 fixture, seconds)
     python tests/golden/make_truth64.py readme   (the README-line fixtures, ~10 min; `readme+`: only the ones the file lacks)
 
-Writes tests/golden/bench10k_hsic_fp64.npz: for each start of the fixture (`run`, `one0`, ...) `<name>_g64` = the
+Writes tests/golden/bench10k_<measure>_fp64.npz: for each start of the fixture (`run`, `one0`, ...) `<name>_g64` = the
 mirrored packed gradient of its first step at `packed_pos`, plus its largest magnitude over the whole vector."""
 import os
 import sys
@@ -141,5 +143,9 @@ if __name__ == "__main__":
         mid()
     elif len(sys.argv) > 1 and sys.argv[1] in ("readme", "readme+"):
         readme(only_missing=sys.argv[1] == "readme+")
+    elif len(sys.argv) > 1 and sys.argv[1] in ("bench10k_mse", "bench10k_kl"):
+        main(workload="synthetic-10k-" + sys.argv[1].split("_")[1], tag=sys.argv[1])
+    elif len(sys.argv) > 1 and sys.argv[1] != "bench10k_hsic":
+        sys.exit(f"make_truth64.py: unknown fixture {sys.argv[1]!r}")
     else:
         main()

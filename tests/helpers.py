@@ -153,6 +153,28 @@ def tril_pos(p):
     return i, p - i * (i - 1) // 2
 
 
+def decode_slices(n, rows=None):
+    """Column slices of the fused MSELoss / KL step's per-pair passes (k_decode_stats, k_decode_fly<.., 1|2>) over `rows` rows of
+    an n-node graph (None: all of them, the monolithic engine): a mirror of fl_decode_slabs(n, rows, alone=true) and of the
+    slice width of fl_decode_fly / fl_decode_stats (mc-gra_amd/csrc/fused_lowrank.hip), rounded up to a multiple of 4 for the
+    16-byte loads of M.  Returns (js, jper, [(j0, j1) per slice]); a slice with j0 >= n is empty."""
+    rows = n if rows is None else rows
+    nb = (rows + 255) // 256
+    js = max(1, min((1024 + nb - 1) // nb, 64, n // 64))
+    jper = ((n + js - 1) // js + 3) & ~3
+    return js, jper, [(s * jper, min(n, s * jper + jper)) for s in range(js)]
+
+
+def empty_decode_slices(n, rows=None):
+    return sum(j0 >= n for j0, _ in decode_slices(n, rows)[2])
+
+
+# n of the fused MSELoss / KL oracle cases that are there for a property of the decode's slicing (tests/test_gpu_parity.py):
+# each must keep it (tests/test_cabi_symbols.py::test_fused_decode_edge_cases_keep_their_property)
+DECODE_EDGE_N = {1155: "odd n, padded ld, empty last decode slice",
+                 4200: "n >= 4096 (small-operand terms on their own stream), empty last decode slice, also on world-3 row blocks"}
+
+
 def cora_feature_adj(feats):
     """main.dot_product_decode for cora (main.py:44-48)."""
     Z = feats @ feats.T

@@ -86,3 +86,33 @@ def test_decode_mode_mapping(pkg):
 def test_adj_changes_property_before_attack(pkg):
     m = pkg.PGDAttack(model=None, embedding=None, nnodes=7, device="cpu")
     assert m.adj_changes.shape == (21,) and float(m.adj_changes.abs().sum()) == 0.0
+
+
+def test_fused_decode_edge_cases_keep_their_property(pkg):
+    """The fused MSELoss / KL oracle cases of tests/test_gpu_parity.py at n = 1155 and 4200 are there for the decode's column
+    slicing: k_decode_stats / k_decode_fly cut the columns into fl_decode_slabs(n, rows, true) slices rounded up to a multiple of
+    4, so that for many n the last slice starts at or past n and is empty (it must contribute zero partials to the row sums
+    k_kl_stats_fin takes the log of).  tests/helpers.py:decode_slices mirrors that rule; it is checked here against the library's
+    own fl_decode_slabs, so that a change of the rule cannot quietly leave these cases without the edge they pin."""
+    from mc_gra_amd.sharded import RowBlockPlan
+    from tests import helpers as H
+    slabs = getattr(ctypes.CDLL(LIB), "_ZN5mcgra15fl_decode_slabsEiib")      # mcgra::fl_decode_slabs(int, int, bool): host code
+    slabs.restype, slabs.argtypes = ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_bool]
+    rng = np.random.RandomState(0)
+    ns = sorted(set(H.DECODE_EDGE_N) | {256, 1100, 2050, 4095, 4096, 10000} | set(rng.randint(256, 40000, 200).tolist()))
+    for n in ns:
+        for rows in {n, n // 3, (n + 2) // 3, 256, 1536, n - 256 if n > 512 else n}:
+            assert slabs(n, rows, True) == H.decode_slices(n, rows)[0], (n, rows)
+    n = 1155
+    assert n % 2 == 1 and (n + 31) // 32 * 32 != n                  # odd n; the engine's ld = round_up(n, 32) pads the rows
+    assert H.empty_decode_slices(n) >= 1
+    n = 4200
+    assert n >= 4096 and H.empty_decode_slices(n) >= 1              # (attack_fused.hip: the small-operand terms' stream)
+    # test_sharded_mse_ranks_match_monolithic_step at world 3: the row-range form cuts other slices, and each rank has empty ones
+    plans = [RowBlockPlan(n, 3, r) for r in range(3)]
+    assert all(p.has_rows for p in plans)
+    for p in plans:
+        rows = p.row_end - p.row_begin
+        assert H.decode_slices(n, rows)[0] != H.decode_slices(n)[0] and H.empty_decode_slices(n, rows) >= 1, (p.rank, rows)
+    # the bench's N = 10 000 (tests/test_gpu_fullsize.py: the MSELoss / KL reference tests) runs 26 slices, none of them empty
+    assert H.decode_slices(10000)[0] == 26 and H.empty_decode_slices(10000) == 0

@@ -5,7 +5,8 @@ PGDAttack.attack (topology_attack.py:161-324, torch CPU) produced on exactly the
 (tests/golden/make_golden.py --only bench10k: bench.make_inputs + bench.make_a0 handed to the reference classes);
 test_bench_workload_matches_reference_at_10k drives the engine the way bench.py does (default fp16-split product on
 the side stream, fused tail, monitor forward adopted by the next step) and holds per-step gradients, states and the
-recovered-adjacency AUC against it.  The oracle cannot run at this size in seconds, so the other tests carry
+recovered-adjacency AUC against it; test_fused_elementwise_workload_matches_reference_at_10k does the same for the
+MSELoss and KL workloads (bench10k_mse.npz, bench10k_kl.npz).  The oracle cannot run at this size in seconds, so the other tests carry
 size-independent properties -- state invariants, bit-determinism, agreement of the two independent evaluations of
 linear_HSIC (low-rank vs Gram), bit-identity of the row-block sharded phases, gradient linearity."""
 import os
@@ -20,6 +21,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 WL = "synthetic-10k-hsic"
+# (workload, mutation, start) of the MSELoss / KL mutation guards: each defect on the starts where it misses the first-step
+# bar by 30 times or more (test_mutations_turn_the_fused_10k_reference_tests_red says by how much on every start)
+MUTATION_CASES = [("synthetic-10k-mse", "calc", "run"), ("synthetic-10k-mse", "calc", "one0"), ("synthetic-10k-mse", "rk", "run"),
+                  ("synthetic-10k-mse", "rk", "one1"), ("synthetic-10k-kl", "calc", "one0"), ("synthetic-10k-kl", "rk", "run"),
+                  ("synthetic-10k-kl", "rk", "one1"), ("synthetic-10k-kl", "klstats", "run"), ("synthetic-10k-kl", "klstats", "one1")]
 
 
 @pytest.fixture(scope="module")
@@ -48,26 +54,28 @@ def test_tril_pos_helper():
     assert np.array_equal(i, ii) and np.array_equal(j, jj)
 
 
-def _reference_run_errors(ctx, z, z64, name, steps=None, check=True, mutate=None):
-    """Drive the engine the way bench.py does from the start `name` of the fixture; returns the per-step gradient errors
-    against the reference (and, step 0, against the float64 evaluation), asserting the bars when `check`."""
+def _reference_run_errors(ctx, z, z64, name, steps=None, check=True, mutate=None, wl=WL):
+    """Drive the engine the way bench.py does from the start `name` of the fixture of workload `wl`; returns the per-step
+    gradient errors against the reference (and, step 0, against the float64 evaluation), asserting the bars when `check`."""
     pkg, torch, bench, dev = ctx
     seed, lr = int(z["seed"]), float(z["lr"])
-    n = bench.WORKLOADS[WL][0]
-    assert lr == bench.workload_lr(WL, n) and float(z["start_scale"]) == bench.start_scale(WL, n), "fixture is of another bench start"
+    n = bench.WORKLOADS[wl][0]
+    assert str(z["workload"]) == wl, (str(z["workload"]), wl)
+    assert lr == bench.workload_lr(wl, n) and float(z["start_scale"]) == bench.start_scale(wl, n), "fixture is of another bench start"
     pi, pj = _tril_pos(z["packed_pos"])
     ti, tj = torch.as_tensor(pi, device=dev), torch.as_tensor(pj, device=dev)
     sd, sc = int(z[f"{name}_a0_seed"]), float(z[f"{name}_a0_scale"])
     if mutate:          # the defect injector is accepted only by an engine created under MCGRA_TESTING=1
         os.environ["MCGRA_TESTING"] = "1"
     try:
-        eng, inp, adj_dev = bench.build_engine(pkg, torch, dev, WL, seed)
+        eng, inp, adj_dev = bench.build_engine(pkg, torch, dev, wl, seed)
     finally:
         os.environ.pop("MCGRA_TESTING", None)
-    assert eng.product_mode() == 3, "the default product of this size is the 2-plane fp16 split"
+    if bench.WORKLOADS[wl][5] == "HSIC":
+        assert eng.product_mode() == 3, "the default product of this size is the 2-plane fp16 split"
     if mutate:
         eng.test_mutate(mutate)
-    if (sd, sc) != (seed, bench.start_scale(WL, n)):
+    if (sd, sc) != (seed, bench.start_scale(wl, n)):
         eng.set_adj_changes(torch.as_tensor(bench.make_a0(n, sd, sc), device=dev))
     G, A = z[f"{name}_g"], z[f"{name}_a"]
     errs = []
@@ -148,18 +156,27 @@ def test_bench_workload_matches_reference_at_10k(ctx):
     hold against the reference -- to the reference within the reference's own distance from the exact gradient plus
     3e-4, and its first Adam step to the reference's within the reference's own sign flips plus 0.2 %; free-running
     steps, which have no float64 truth, to 2e-3."""
+    _check_against_reference_at_10k(ctx, WL)
+
+
+def _check_against_reference_at_10k(ctx, wl):
+    """The reference test of workload `wl` (bench.WORKLOADS) against tests/golden/bench10k_<measure>{,_ref64,_fp64}.npz."""
     pkg, torch, bench, dev = ctx
-    z = np.load(os.path.join(ROOT, "tests", "golden", "bench10k_hsic.npz"))
-    z64 = np.load(os.path.join(ROOT, "tests", "golden", "bench10k_hsic_ref64.npz"))
-    assert str(z["workload"]) == WL and np.array_equal(z["packed_pos"], z64["packed_pos"])
-    # (the numpy oracle in float64, make_truth64.py, agrees with the reference in float64 to 2e-10 of gmax: two independent
-    # float64 evaluations of topology_attack.py:161-283)
-    zo = np.load(os.path.join(ROOT, "tests", "golden", "bench10k_hsic_fp64.npz"))
-    for nm in ("run", "one0", "one1"):
+    tag = "bench10k_" + wl.rsplit("-", 1)[1]
+    z = np.load(os.path.join(ROOT, "tests", "golden", f"{tag}.npz"))
+    z64 = np.load(os.path.join(ROOT, "tests", "golden", f"{tag}_ref64.npz"))
+    assert str(z["workload"]) == wl and str(z64["workload"]) == wl and np.array_equal(z["packed_pos"], z64["packed_pos"])
+    # (the numpy oracle in float64, make_truth64.py, agrees with the reference in float64 to 2e-10 of gmax for HSIC, 2e-15 for
+    # MSELoss / KL: two independent float64 evaluations of topology_attack.py:161-283)
+    zo = np.load(os.path.join(ROOT, "tests", "golden", f"{tag}_fp64.npz"))
+    starts = ["run"] + sorted({k[:4] for k in z.files if k.startswith("one")})
+    assert len(starts) >= 3
+    for nm in starts:
         assert np.abs(zo[f"{nm}_g64"] - z64[f"{nm}_g64ref"]).max() <= 1e-8 * float(z64[f"{nm}_g64ref_absmax"])
     sp = z["sample_pos"]
-    for name in ["run"] + sorted({k[:4] for k in z.files if k.startswith("one")}):
-        eng, inp, adj_dev, errs = _reference_run_errors(ctx, z, z64, name)
+    for name in starts:
+        eng, inp, adj_dev, errs = _reference_run_errors(ctx, z, z64, name, wl=wl)
+        assert len(errs) == z[f"{name}_g"].shape[0]
         assert eng.path_stats()["general_steps"] == 0 and eng.fused_steps() == len(errs)
         lab = torch.as_tensor(inp["labels"], device=dev)
         final = eng.finalize(0, eng.buffer("HA"), eng.buffer("YA"), (lab[:, None] == lab[None, :]).float())
@@ -190,6 +207,52 @@ def test_mutations_turn_the_10k_reference_test_red(ctx, monkeypatch, mutation, n
     err_ref, err_true, _ = errs[0]
     assert eng.fused_steps() == 1
     assert err_true > 30 * 3e-4, (mutation, name, err_ref, err_true)
+    del eng
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("wl", ["synthetic-10k-mse", "synthetic-10k-kl"])
+def test_fused_elementwise_workload_matches_reference_at_10k(ctx, wl):
+    """bench.py's synthetic-10k-mse / synthetic-10k-kl (calc = MSELoss / calc_kl: the fused elementwise steps of
+    attack_fused.hip -- k_decode_stats, k_decode_fly<H, V7, 1|2>, k_kl_stats_fin / k_kl_v_fin, k_tail_reduce<V, 1|2> -- at
+    the size the bench quotes them: 26 column slices of the decode, 157 x 157 tail tiles, the small-operand terms on their
+    own stream) against the reference, the same way and with the same bars as the HSIC test above: fixtures
+    tests/golden/bench10k_{mse,kl}.npz (make_golden.py --only bench10k_mse / bench10k_kl: the reference's 4-step run from
+    the bench's own start and single steps from two other seeded starts), bench10k_{mse,kl}_ref64.npz (the first
+    gradients of the reference's own code in float64) and bench10k_{mse,kl}_fp64.npz (the numpy oracle in float64).
+    Every step is a fused one; no general step.
+
+    Measured (MI355X; max |g - g64| / gmax of the first step at the sampled positions, run / one0 / one1): the reference's own
+    fp32 gradient sits 7.2e-7 / 7.9e-7 / 3.6e-7 from its float64 gradient for MSELoss (rms 1.5e-7 / 1.8e-7 / 9.3e-8) and
+    1.1e-5 / 4.7e-7 / 3.2e-6 for KL (rms 6.4e-7 / 1.2e-7 / 1.2e-7) -- no N x N x N product and no Gram cancellation here, unlike
+    HSIC's 1.2e-2.  The engine: 8.1e-7 / 7.4e-7 / 3.5e-7 (MSELoss) and 8.5e-6 / 3.9e-7 / 2.2e-6 (KL), i.e. at or below the
+    reference's own rounding and 35x (KL) to 370x (MSELoss) under the 3e-4 bar; free-running steps of `run` to the reference: <= 1.3e-6 (MSELoss), 3.2e-5 (KL).
+    AUC: within 6e-9 of the reference's on every start.  The bars stay the HSIC test's: a kernel defect that matters misses
+    them by far more (test_mutations_turn_the_fused_10k_reference_tests_red)."""
+    _check_against_reference_at_10k(ctx, wl)
+
+
+@pytest.mark.parametrize("wl,mutation,name", MUTATION_CASES)
+def test_mutations_turn_the_fused_10k_reference_tests_red(ctx, wl, mutation, name):
+    """Mutation guard of the MSELoss / KL reference tests above: 'calc' drops the measure's per-pair terms c1 / c2 (the
+    multipliers kmse1 = kmse2 = 0 of the decode and of the tail's first pass), 'klstats' wipes the KL row statistics
+    (lseA / lse1 after k_decode_stats), 'rk' drops the tail's rank-k terms.  Each must miss the first-step bar against the
+    exact gradient (3e-4 of gmax) by 30 times or more -- on the start named here.
+
+    Measured first-step error against the float64 gradient, in units of the bar (run / one0 / one1): 'calc' MSELoss 67 / 53 /
+    14, KL 8.5 / 46 / 1.6; 'rk' 2 400 ... 2 700 on every start of both; 'klstats' 2e8 / 1e9 / 3e7.  The per-pair terms carry
+    the gradient where the small-operand terms c9 / c10 leave them room: scripts/nxn_share.py at N = 10 000 (the numpy oracle,
+    one term at a time) gives c2 3.2e-2 / 2.4e-2 / 6.3e-3 of the gradient's largest magnitude for MSELoss and 2.0e-3 / 1.1e-2 /
+    3.8e-4 for KL (c1 at most 3.3e-3) at the starts' scales -- so 'calc' is held on the starts where c2 is in charge: run
+    and one0 (MSELoss), one0 (KL, the half-scale start)."""
+    pkg, torch, bench, dev = ctx
+    tag = "bench10k_" + wl.rsplit("-", 1)[1]
+    z = np.load(os.path.join(ROOT, "tests", "golden", f"{tag}.npz"))
+    z64 = np.load(os.path.join(ROOT, "tests", "golden", f"{tag}_ref64.npz"))
+    eng, _, _, errs = _reference_run_errors(ctx, z, z64, name, steps=1, check=False, mutate=mutation, wl=wl)
+    err_ref, err_true, _ = errs[0]
+    assert eng.fused_steps() == 1 and eng.path_stats()["general_steps"] == 0
+    assert err_true > 30 * 3e-4, (wl, mutation, name, err_ref, err_true)
     del eng
     torch.cuda.empty_cache()
 

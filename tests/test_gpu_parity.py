@@ -1818,14 +1818,20 @@ def test_gram_products_beside_the_step_are_bit_identical(pkg, monkeypatch, wp):
 @pytest.mark.parametrize("measure", ["MSELoss", "KL"])
 @pytest.mark.parametrize("n,widths,wp", [
     (1100, (16, 16), None), (300, (16, 16), NXN_ONLY), (515, (8, 8), (0, 0.01, 0, 0, 0, 10, 10, 0, 10, 1000)),
-    (1030, (16, 16, 16), None), (700, (16, 32), (0.01, 0, 0, 0, 0, 0, 10, 0, 10, 0))])
+    (1030, (16, 16, 16), None), (700, (16, 32), (0.01, 0, 0, 0, 0, 0, 10, 0, 10, 0)),
+    (1155, (16, 16), None), (4200, (16, 16), None)])
 def test_fused_mse_step_matches_general_path_and_oracle(pkg, n, widths, wp, measure, monkeypatch):
     """measure = MSELoss through attack_fused.hip (adj_norm, modified_adj1 and the gradients w.r.t. them are never stored: the
     decode carries d / d modified_adj1, the tail's first pass d / d adj_norm with feature_adj in the place of the HSIC product
     and S = Zn Zn^T as a third rank-k group) against the general step (MCGRA_NO_FUSED_LR=1) and the oracle, teacher-forced,
     with the monitoring forward adopted in between: mirrored gradient, every loss term, the updated adjacency.
     measure = KL: the same through the fused KL step (softmax(feature_adj) in feature_adj's place, the row statistics of
-    adj_norm and modified_adj1 from one more per-pair pass, an asymmetric per-pair term symmetrised in the decode and the tail)."""
+    adj_norm and modified_adj1 from one more per-pair pass, an asymmetric per-pair term symmetrised in the decode and the tail).
+    n = 1155 and 4200 (tests/helpers.py:DECODE_EDGE_N) put the last column slice of k_decode_stats / k_decode_fly past n (an
+    empty slice whose zero partials enter every row's sums); 1155 is odd with a padded ld, 4200 is past n = 4096, where the
+    MSELoss step's small-operand terms leave the caller's stream for a third one."""
+    if n in H.DECODE_EDGE_N:      # (the slicing rule itself is checked against the library: test_cabi_symbols.py)
+        assert H.empty_decode_slices(n) >= 1, (n, H.decode_slices(n)[:2])
     kw = {} if wp is None else {"weight_param": wp}
     z = _synthetic_case(n, 11, widths, 4, seed=n, measure=measure, **kw)
     fused = H.engine_from(pkg, z)
@@ -1939,6 +1945,18 @@ def test_sharded_mse_ranks_match_monolithic_step(pkg, n, widths, world, wp, meas
     """The fused MSELoss (KL) step as `world` row-block ranks in lockstep: no N x N exchange at all (all-gathers of node arrays with
     the partial scalars in their lane only; KL: one more gather, of the rows' softmax statistics) -- the union of the ranks' rows
     equals the monolithic fused step, mirrored entries bit for bit across the ranks, loss terms identical on every rank."""
+    _check_sharded_mse_ranks(pkg, n, widths, world, wp, measure)
+
+
+def test_sharded_kl_ranks_match_monolithic_step_past_4096(pkg):
+    """The same for calc_kl at n = 4200 on 3 ranks: each rank's row range (1536, 1536, 1128 rows) gets 64 column slices of the
+    row statistics and the decode from the row-range form of fl_decode_slabs, the monolithic step 61; both leave the last
+    slices empty (tests/test_cabi_symbols.py::test_fused_decode_edge_cases_keep_their_property)."""
+    assert H.empty_decode_slices(4200) >= 1
+    _check_sharded_mse_ranks(pkg, 4200, (16, 16), 3, None, "KL")
+
+
+def _check_sharded_mse_ranks(pkg, n, widths, world, wp, measure):
     from mc_gra_amd import sharded as S
     import torch
     kw = {} if wp is None else {"weight_param": wp}
