@@ -19,7 +19,6 @@
 #include <string.h>
 
 #include <string>
-#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -88,34 +87,20 @@ int eg(mcgra_attack* h, hipStream_t st, bool ta, bool tb, int M, int N, int K, f
   MCGRA_HIP(sgemm(st, ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, h->ws, h->ws_bytes, keep));
   return timer_end(h, st, big, 2.0 * M * N * K);
 }
-// C = A A^T (A is [n x k]); sym: lower tile storage only.  (A2, C2): second Gram in the same launch.
-int eg_syrk(mcgra_attack* h, hipStream_t st, bool sym, int n, int k, const float* A, int lda, float* C, int ldc,
-                   const float* A2 = nullptr, float* C2 = nullptr, int t0 = 0, int trows = -1) {
-  if (!sym) {
-    CHK(eg(h, st, false, true, n, n, k, 1.f, A, lda, A, lda, 0.f, C, ldc));
-    if (C2) CHK(eg(h, st, false, true, n, n, k, 1.f, A2, lda, A2, lda, 0.f, C2, ldc));
-    return 0;
-  }
-  const bool big = h->profile;
-  CHK(timer_begin(h, st, big));
-  MCGRA_HIP(ssyrk_lower(st, n, k, 1.f, A, lda, 0.f, C, ldc, A2, C2, t0, trows));
-  const double ta = t0, tb = trows >= 0 ? t0 + trows : (n + SYM_TILE - 1) / SYM_TILE;
-  return timer_end(h, st, big, (C2 ? 2.0 : 1.0) * 2.0 * (tb * (tb + 1) / 2 - ta * (ta + 1) / 2) * SYM_TILE * SYM_TILE * k);
+// C = A A^T (A is [n x k]) on lower tile storage.  (A2, C2): second Gram in the same launch.
+static int eg_syrk(mcgra_attack* h, hipStream_t st, int n, int k, const float* A, int lda, float* C, int ldc,
+                   const float* A2 = nullptr, float* C2 = nullptr) {
+  CHK(timer_begin(h, st, h->profile));
+  MCGRA_HIP(ssyrk_lower(st, n, k, 1.f, A, lda, 0.f, C, ldc, A2, C2));
+  const double tb = (n + SYM_TILE - 1) / SYM_TILE;      // tile rows: tb (tb + 1) / 2 lower tiles
+  return timer_end(h, st, h->profile, (C2 ? 2.0 : 1.0) * 2.0 * (tb * (tb + 1) / 2) * SYM_TILE * SYM_TILE * k);
 }
-// C = S B + beta C (S symmetric [n x n], B [n x m]); sym: S is in lower tile storage
-int eg_symm(mcgra_attack* h, hipStream_t st, bool sym, int n, int m, const float* S, int lds_, const float* B,
-                   int ldb, float beta, float* C, int ldc, const float* S2 = nullptr, const float* B2 = nullptr,
-                   float* C2 = nullptr, int t0 = 0, int trows = -1) {
-  if (!sym) {
-    CHK(eg(h, st, false, false, n, m, n, 1.f, S, lds_, B, ldb, beta, C, ldc));
-    if (C2) CHK(eg(h, st, false, false, n, m, n, 1.f, S2, lds_, B2, ldb, beta, C2, ldc));
-    return 0;
-  }
-  const bool big = h->profile;
-  CHK(timer_begin(h, st, big));
-  MCGRA_HIP(ssymm_lower(st, n, m, 1.f, S, lds_, B, ldb, beta, C, ldc, S2, B2, C2, t0, trows));
-  const double rows = trows >= 0 ? fmin((double)trows * SYM_TILE, (double)n - (double)t0 * SYM_TILE) : n;
-  return timer_end(h, st, big, (C2 ? 2.0 : 1.0) * 2.0 * rows * (double)m * n);
+// C = S B + beta C (S symmetric [n x n] in lower tile storage, B [n x m]).  (S2, B2, C2): second product in the same launch.
+static int eg_symm(mcgra_attack* h, hipStream_t st, int n, int m, const float* S, int lds_, const float* B, int ldb, float beta,
+                   float* C, int ldc, const float* S2 = nullptr, const float* B2 = nullptr, float* C2 = nullptr) {
+  CHK(timer_begin(h, st, h->profile));
+  MCGRA_HIP(ssymm_lower(st, n, m, 1.f, S, lds_, B, ldb, beta, C, ldc, S2, B2, C2));
+  return timer_end(h, st, h->profile, (C2 ? 2.0 : 1.0) * 2.0 * n * (double)m * n);
 }
 
 // x = relu(adj @ (x W_l) + b_l) for `depth` layers (models/gcn.py:71-76,164-172).
@@ -403,7 +388,7 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
         set_error("stream / event creation failed"); rc = MCGRA_EHIP;
       }
       if (h->mask_host) { h->mask_host[0] = 0u; h->mask_host[1] = 0u; }
-      // Gram evaluation: its four products on the side stream, beside the HBM-bound rest of the step (step_impl).
+      // Gram evaluation: its four products on the side stream, beside the HBM-bound rest of the step (gram_eval).
       // MCGRA_GRAM_OVERLAP=0: everything on the caller's stream, same launches in the same order (bit-identical: A/B test)
       { const char* eg2 = ab_env("MCGRA_GRAM_OVERLAP"); h->gram_ovl = h->gram_split && !rc && !(eg2 && eg2[0] == '0'); }
       // ... and the first of them forked by the monitoring forward (configurations without a low-rank form; MCGRA_GRAM_KX_EARLY=0: by the step)
@@ -914,6 +899,59 @@ int collect_scalars(mcgra_attack* h, hipStream_t st, double* scalars_out, bool h
   return 0;
 }
 
+// ---- the general step: every configuration the fused steps do not cover.  Its stages, in program order on the caller's stream:
+//   step_forward   forward and decode; Xc = H adj_norm with the start of Kx (Gram evaluation) or the fork of P1 (low-rank step)
+//   *_terms        the N x N loss terms of the measure; HSIC decides between the low-rank forms and the Grams
+//   gram_eval      the Grams and their gradient products on the split kernel, on the Gram stream beside the rest of the step
+//   gram_fp32      ... or on the fp32 SYRK / SYMM
+//   step_backward  small-operand terms, victim chain, decode and modified_adj chain backward
+//   step_tail      normalisation backward, Adam, projection, scalars
+struct GeneralStep {
+  mcgra_attack* h;
+  hipStream_t st, gst;             // the caller's stream; the Gram evaluation's (st2 beside the rest of the step: gram_ovl)
+  const float *noise, *A, *em;     // A: modified_adj (M itself when ori == 0, eps == 0); em: the embedding the decode reads
+  const unsigned char* gate;
+  int he;                          // width of em
+  double sg, k1, k2, k6, k7, k9, k10, n2;
+  bool cka, hsic, use1, use2, use9, use10;
+  bool gen;                        // modified_adj = clamp(M + ori + eps noise) with its gate
+  bool want_xc;                    // HSIC / CKA with c1 or c2: centred operands and Grams (or their low-rank forms)
+  bool gs_path;                    // ... the Grams on the split kernel, unless the low-rank form takes the step
+  bool gs_only;                    // ... with no low-rank form at all: the step IS a Gram evaluation
+  bool adopt;                      // forward of this iteration already done by the last monitor call
+  bool kx_adopt;                   // ... and Kx of its adj_norm forked by it (gram_pack_fork_kx)
+  bool p1_deferred;                // P1's fork waits for this step's masked-pair count
+  bool ky_early;                   // Ky started in front of the entropy pass
+  bool small_side;                 // small-operand terms on the third stream (ev_fork3 recorded behind the forward chains)
+  bool gram_eval;                  // known after the loss terms: this step evaluates the Grams on the split kernel
+};
+
+// One N x N x N product of the Gram evaluation on the split kernel (2-plane fp16 operands, MCGRA_SPLIT_BF16=1: single-plane), timed
+// when profiling, on the Gram stream gst: it picks up behind everything enqueued on the caller's stream st so far, and records
+// `done` (if any) behind the product.  Split-K slabs in the small graph's slab when there is one, else in `slab`, an N x N buffer
+// idle meanwhile.
+// (the (A, B) operand magnitudes of a product are read where they are: split3_symm takes B's through its own pointer.  Rounds
+//  2 - 5 paired them up in amax[8 ..] with two 4-byte device-to-device copies per product -- eight launches of ~5 us per step on
+//  the caller's queue.  No slot is rewritten between a product's fork and its join: amax[1] / [2] come out of the centring
+//  passes of this step, [3] / [4] out of hsic_gram_scales / the CKA combine, all in front of the products that read them.)
+static int gram_product(mcgra_attack* h, hipStream_t st, hipStream_t gst, const void* Ap, const void* Bp, float* C, float* slab,
+                        const float* amax_a, const float* amax_b, int flags, hipEvent_t done) {
+  const int n = h->n, ld = h->ld;
+  if (gst != st) { MCGRA_HIP(hipEventRecord(h->ev_fork, st)); MCGRA_HIP(hipStreamWaitEvent(gst, h->ev_fork, 0)); }
+  CHK(timer_begin(h, gst, h->profile));
+  MCGRA_HIP(split3_symm(gst, n, Ap, Bp, C, ld, 0, -1, h->small_slab ? h->small_slab : slab,
+                        h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, 2, amax_a, 0, -1,
+                        flags | (h->split_single ? SPLIT_SINGLE : 0), 0, nullptr, 0, nullptr, amax_b));
+  CHK(timer_end(h, gst, h->profile, 2.0 * (double)n * n * n));
+  if (gst != st && done) MCGRA_HIP(hipEventRecord(done, gst));
+  return 0;
+}
+// Kx = Xc Xc^T from the planes of Xc's rows in Gp0, forked onto the Gram stream: lower tiles, mirrored by the epilogue (full,
+// bitwise symmetric matrix); split-K slabs in G_A, idle until the tail
+static int fork_kx(mcgra_attack* h, hipStream_t st) {
+  hipStream_t gst = (h->gram_ovl && h->st2) ? h->st2 : st;
+  return gram_product(h, st, gst, h->Gp0, h->Gp0, h->KX, h->G_A, h->amax + 1, h->amax + 1, SPLIT_TRI, nullptr);
+}
 // Gram-evaluation configurations without a low-rank form (GAT / GraphSAGE victims, CKA, widths > 32, MCGRA_NO_LOWRANK): both packed
 // orientations of Xc = H adj_norm in one pass over `adjn` (rows of Xc: both operands of Kx = Xc Xc^T; rows of Xc^T: the B operand of
 // G_adjn += LY Xc), diag(Kx) from the same pass, and Kx on the side stream.  Called by the step -- or, one forward earlier, by the
@@ -921,27 +959,528 @@ int collect_scalars(mcgra_attack* h, hipStream_t st, double* scalars_out, bool h
 // sums of adjn.
 static int gram_pack_fork_kx(mcgra_attack* h, hipStream_t st, const float* adjn) {
   const int n = h->n, ld = h->ld;
-  hipStream_t sg = (h->gram_ovl && h->st2) ? h->st2 : st;
   launch_colmean_f32(st, n, ld, h->rowsx, h->cmean);
   pack_center_both(st, n, ld, adjn, h->cmean, h->r, 0.f, h->Gp0, h->Bpack, h->amax + 1, h->gram_diag, reinterpret_cast<double*>(h->XC));
-  if (sg != st) { MCGRA_HIP(hipEventRecord(h->ev_fork, st)); MCGRA_HIP(hipStreamWaitEvent(sg, h->ev_fork, 0)); }
-  CHK(timer_begin(h, sg, h->profile));
-  MCGRA_HIP(split3_symm(sg, n, h->Gp0, h->Gp0, h->KX, ld, 0, -1, h->small_slab ? h->small_slab : h->G_A,
-                        h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, 2, h->amax + 1, 0, -1, 2 | (h->split_single ? 8 : 0), 0, nullptr,
-                        0, nullptr, h->amax + 1));
-  CHK(timer_end(h, sg, h->profile, 2.0 * (double)n * n * n));
+  return fork_kx(h, st);
+}
+// Ky = Yc Yc^T behind Kx on the Gram stream (ev_first: Kx done, ev_join: Ky done), from the planes the centring pass of
+// modified_adj1 just packed
+static int launch_ky(GeneralStep& s) {
+  mcgra_attack* h = s.h;
+  if (s.gst != s.st) MCGRA_HIP(hipEventRecord(h->ev_first, s.gst));    // Kx done
+  if (s.use2) CHK(gram_product(h, s.st, s.gst, h->Gp1, h->Gp1, h->KY, h->G_A, h->amax + 2, h->amax + 2, SPLIT_TRI, h->ev_join));
   return 0;
 }
 
-// Phases of one step (bit k of `phases`), for row-block sharding over ranks:
-//   0  replicated: forward, losses, centred operands Xc / Yc (every measure other than HSIC / CKA finishes its
-//      N x N terms here)
-//   1  sharded:    centred Grams, tile rows [row_begin, row_end) only           -> exchange KX, KY row blocks
-//   2  sharded:    combine (replicated, cheap) + gradient products, rows [row_begin, row_end) only
-//                                                                              -> exchange G_adjn, G_A1 row blocks
-//   3  replicated: small-operand terms, backward chains, normalisation backward, Adam, projection
-static int step_impl(mcgra_attack_t* h, void* stream, const float* noise, double* scalars_out, int phases) {
-#define PH(k) ((phases >> (k)) & 1)
+// P1 = (H Kf H) Xc: value and gradient of c1 in the low-rank path; the only N x N x N product of such a step.  Forked onto st2 (it
+// needs nothing else of the step), joined in front of its only consumer in the tail.
+static int fork_p1(GeneralStep& s) {
+  mcgra_attack* h = s.h; const int n = h->n, ld = h->ld;
+  hipStream_t sp = h->overlap ? h->st2 : s.st;
+  if (h->overlap) { MCGRA_HIP(hipEventRecord(h->ev_fork, s.st)); MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0)); }
+  if (h->split_on && !s.gen) {
+    // planes of Xc^T from the rows of the (symmetric) adj_norm (packed by center_xc), then the plane-reusing kernel
+    // (split_symm_bf16.hip); split-K slabs of the ragged last round go to KY, idle on a low-rank step
+    CHK(timer_begin(h, sp, h->profile));
+    MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, 0, -1, h->small_slab ? h->small_slab : h->KY,
+                          h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->split_planes, h->amax, 0, -1,
+                          h->split_single ? SPLIT_SINGLE : 0));
+    CHK(timer_end(h, sp, h->profile, 2.0 * (double)n * n * n));
+    ++h->split_steps;
+  } else
+  CHK(eg_symm(h, sp, n, n, h->KFC, ld, h->XC, ld, 0.f, h->KX, ld));
+  if (h->overlap) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
+  h->p1_inflight = true;
+  return 0;
+}
+
+// Xc = H adj_norm (and, for the low-rank path, |xc_i|^2 = diag(Kx) from the same pass): the packed operands and the start of Kx
+// of a Gram evaluation, or the operands and the fork of P1 of a low-rank step
+static int center_xc(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  if (s.gen) {                               // possibly asymmetric: true column sums
+    if (!h->colpart_d) CHK(dalloc(h, &h->colpart_d, (size_t)h->nstrips * ld));
+    launch_colsum(st, n, ld, h->ADJN, h->colpart_d, h->nstrips, h->rowsx);
+  }
+  if (s.gs_only) {
+    // This step IS a Gram evaluation: the fp32 Xc is never stored, Kx starts now, beside the forward chains and the decode.
+    // (kx_adopt: the monitor call of the previous iteration did exactly this on the adj_norm this step adopted)
+    if (!s.kx_adopt) CHK(gram_pack_fork_kx(h, st, h->ADJN));
+  } else {
+    // (gram_diag: |xc_i|^2 = diag(Kx) for the scale bound of the combined Grams -- only when the low-rank path does not want it)
+    const bool want_lrrs = h->lr_ok && !s.cka && s.use2;
+    launch_center_cols(st, n, ld, h->ADJN, h->rowsx, h->cmean, h->XC, want_lrrs ? h->lrRs : (s.gs_path ? h->gram_diag : nullptr),
+                       ((h->split_mode == 2 && h->split_planes == 2) || h->gram_split) ? h->amax + 1 : nullptr);
+    // Gram evaluation through the split kernel: planes of Xc^T now (cmean is reused by Yc's centring), unless the
+    // low-rank product below packs them anyway
+    if (h->gram_split && !s.gen && !(h->lr_ok && !s.cka && s.use1 && h->split_on))
+      split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, 2, h->amax + 1);
+  }
+  if (h->lr_ok && !s.cka && s.use1) {
+    // bf16 planes of Xc^T (opt-in split path) on the caller's stream, ahead of the fork: cmean is reused later
+    if (h->split_on && !s.gen)
+      split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr);
+    // (in a run whose decode keeps masking pairs the product would be thrown away: it then waits for this step's own
+    // masked-pair count, hsic_terms)
+    if (!(h->skip_fused && s.use2)) CHK(fork_p1(s));
+    else s.p1_deferred = true;
+  }
+  return 0;
+}
+
+// ---- forward: adjacency, normalisation (:164-166), victim and embedding chains (:167-185), dot_product_decode +
+// get_modified_adj_after (:187-188)
+static int step_forward(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, L = h->L, Le = h->Le, C = h->C, he = s.he;
+  // (S_SQ, S_SUM are the first two slots: written by forward_common, kept when its results are adopted)
+  MCGRA_HIP(hipMemsetAsync(h->scal + (s.adopt ? 2 : 0), 0, sizeof(double) * (S_COUNT - (s.adopt ? 2 : 0)), st));
+  const float* noise_ld = nullptr;
+  if (s.noise) {  // caller layout is [n][n]; the kernels use leading dimension ld.  G_A is free at this point.
+    MCGRA_HIP(hipMemcpy2DAsync(h->G_A, (size_t)ld * 4, s.noise, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
+    noise_ld = h->G_A;
+  }
+  // adj_norm is symmetric when eps == 0 (ori == 0): its column means are its row sums / n, which k_adjn emits
+  if (s.adopt) { float* t = h->ADJN; h->ADJN = h->ADJN_next; h->ADJN_next = t; }
+  else CHK(forward_common(h, st, h->ADJN, noise_ld, (s.want_xc && !s.gen) ? h->rowsx : nullptr));
+  h->p1_inflight = false;
+  if (s.want_xc) CHK(center_xc(s));
+  // ---- victim(features, adj_norm) (:167) and the CE loss (:172)
+  if (!s.adopt) {
+    CHK(chain_forward(h, st, h->ADJN, ld, L, h->Tv, h->Pv, h->Hv, h->Sv));
+    CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->sm));
+  }
+  launch_nll_grad(st, n, C, h->logp, h->sm, C, h->labels, h->cnt, (float)(h->cfg.weight_sup / h->na), h->GZ, h->rowvals + 6 * (size_t)ld);
+  launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, n, 1, h->scal + S_NLL);
+  // ---- embedding(features, modified_adj - ori_adj) (:185) == first Le layers of victim(features, modified_adj) (:259)
+  CHK(chain_forward(h, st, s.A, ld, L, h->Tu, h->Pu, h->Hu, h->Su));
+  CHK(head_forward(h, st, h->Hu, h->Z2, nullptr, h->sm2));
+  if (h->has_ori) {      // embedding(features, modified_adj - ori_adj) (:185) no longer shares the chain of output2 (:259)
+    launch_axpby2d(st, n, s.A, ld, 1.f, h->ORI, ld, -1.f, h->Bbuf, ld);
+    CHK(chain_forward(h, st, h->Bbuf, ld, Le, h->Te, h->Pe, h->He, h->Se));
+  }
+  if (h->small_side_on && h->st3 && h->st3 != st && (s.use9 || s.use10)) {
+    MCGRA_HIP(hipEventRecord(h->ev_fork3, st));      // (em and softmax(output2) stand: what the small-operand terms need)
+    s.small_side = true;
+  }
+  // ---- dot_product_decode + get_modified_adj_after (:187-188)
+  launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->hmax, h->nrm, 2.f);
+  CHK(eg(h, st, false, true, n, n, he, 1.f, h->Zn, h->hmax, h->Zn, h->hmax, 0.f, h->A1, ld));
+  // (the count of relu-masked pairs is read by the low-rank decision only: HSIC with c2 on a configuration that has the
+  // low-rank forms -- every other step skips the counting)
+  const bool count_masked = h->cfg.measure == MCGRA_MEASURE_HSIC && h->lr_ok && h->cfg.w[1] != 0;
+  if (count_masked) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, sizeof(unsigned int), st));
+  h->nmask_zero = false;
+  launch_decode_post(st, n, ld, h->A1, h->has_ori ? h->ORI : nullptr, count_masked ? h->nmask : nullptr);
+  h->lr_step = false;
+  return 0;
+}
+
+// ---- N x N loss terms (:212-236), one function per measure family
+// the elementwise pass: entropy terms c6, c7 (and MSELoss' c1, c2: kmse1, kmse2); y_side = false leaves modified_adj1's to the
+// low-rank decode backward
+static void elem_terms(GeneralStep& s, float kmse1, float kmse2, bool y_side = true) {
+  mcgra_attack* h = s.h;
+  launch_loss_elem(s.st, h->n, h->ld, h->ADJN, y_side ? h->A1 : nullptr, h->FADJ, kmse1, kmse2, (float)(s.k6 / s.n2),
+                   (float)(s.k7 / s.n2), h->G_ADJN, y_side ? h->G_A1 : nullptr, h->rowvals);
+  launch_reduce_rows(s.st, h->rowvals, h->n, 4, h->scal + S_V1);
+}
+// dot_product(X, Y) = |Y^T X|_F (:480-481); d/dY = X P^T / |P|, d/dX = Y P / |P| with P = Y^T X
+static int dp_terms(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  elem_terms(s, 0.f, 0.f);
+  if (s.use1) {   // c1 = k1 dot_product(feature_adj, adj_norm): P = adj_norm^T Fadj
+    CHK(eg(h, st, true, false, n, n, n, 1.f, h->ADJN, ld, h->FADJ, ld, 0.f, h->KX, ld));
+    launch_rowsumsq(st, n, ld, h->KX, h->rowsx);
+    launch_reduce_rows(st, h->rowsx, n, 1, h->scal + S_H1);
+    CHK(eg(h, st, false, true, n, n, n, 1.f, h->FADJ, ld, h->KX, ld, 0.f, h->XC, ld));
+    launch_axpy_invnorm(st, n, ld, h->XC, h->scal + S_H1, (float)s.k1, h->G_ADJN);
+  }
+  if (s.use2) {   // c2 = k2 dot_product(adj_norm, A1): P = A1^T adj_norm
+    CHK(eg(h, st, true, false, n, n, n, 1.f, h->A1, ld, h->ADJN, ld, 0.f, h->KY, ld));
+    launch_rowsumsq(st, n, ld, h->KY, h->rowsy);
+    launch_reduce_rows(st, h->rowsy, n, 1, h->scal + S_H2);
+    CHK(eg(h, st, false, false, n, n, n, 1.f, h->A1, ld, h->KY, ld, 0.f, h->XC, ld));          // d/dX = Y P
+    launch_axpy_invnorm(st, n, ld, h->XC, h->scal + S_H2, (float)s.k2, h->G_ADJN);
+    CHK(eg(h, st, false, true, n, n, n, 1.f, h->ADJN, ld, h->KY, ld, 0.f, h->XC, ld));         // d/dY = X P^T
+    launch_axpy_invnorm(st, n, ld, h->XC, h->scal + S_H2, (float)s.k2, h->G_A1);
+  }
+  return 0;
+}
+// calc = MutualInformation(sigma=0.4, num_bins=N) (:199-201): c1 = k1 calc(feature_adj, adj_norm)[0] (:213-216),
+// c2 = k2 calc(adj_norm, modified_adj1)[0] (:222-225).  Entry (i, j) of an operand meets bin j only and bins j >= 7 are
+// out of reach of values <= 2 in float32 (kde_kernels.hip): the terms live on the first KDE_NXN_COLS columns.
+static int kde_terms(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  elem_terms(s, 0.f, 0.f);      // only the entropy slots are non-zero
+  const int kc = n < h->kde_cols ? n : h->kde_cols;      // (set_graph: 8, or as far as feature_adj's values reach)
+  if (s.use1) launch_kde_term(st, n, kc, n, h->FADJ, ld, h->ADJN, ld, s.k1, nullptr, 0, false, h->G_ADJN, ld, true, h->scal + S_H1, h->kde);
+  if (s.use2) launch_kde_term(st, n, kc, n, h->ADJN, ld, h->A1, ld, s.k2, h->G_ADJN, ld, true, h->G_A1, ld, true, h->scal + S_H2, h->kde);
+  return 0;
+}
+// calc_kl (:483-487) against softmax(feature_adj) (XC, set_graph)
+static int kl_terms(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  elem_terms(s, 0.f, 0.f);      // only the entropy slots are non-zero
+  if (s.use1 || s.use2) {
+    launch_kl_rows(st, n, ld, h->ADJN, h->A1, h->XC, s.use1 ? (float)s.k1 : 0.f, s.use2 ? (float)s.k2 : 0.f, h->G_ADJN,
+                   h->G_A1, h->rowvals + 4 * (size_t)ld);
+    launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 2, h->scal + S_H1);
+  }
+  return 0;
+}
+// MSELoss: elementwise, values and gradients of c1, c2 and the entropy terms in one pass
+static int mse_terms(GeneralStep& s) {
+  elem_terms(s, (float)(s.k1 * 2.0 / s.n2), (float)(s.k2 * 2.0 / s.n2));
+  return 0;
+}
+
+// Yc = H modified_adj1 for the Grams (and, on the split kernel, its planes and diag(Ky))
+static void center_yc(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  launch_rowsum(st, n, ld, h->A1, h->rowsy);
+  const bool gs = h->gram_split && !s.gen;
+  if (gs && !h->lr_ok) {
+    // rows of Yc (both operands of Ky = Yc Yc^T) and of Yc^T (B operand of G_A1 += LX Yc) in one pass over the symmetric
+    // modified_adj1 (entries in [0, 1]), diag(Ky) from the same pass
+    launch_colmean_f32(st, n, ld, h->rowsy, h->cmean);
+    pack_center_both(st, n, ld, h->A1, h->cmean, nullptr, 1.0002f, h->Gp1, h->Gp2, h->amax + 2, h->gram_diag + ld,
+                     reinterpret_cast<double*>(h->YC));
+  } else {
+    launch_center_cols(st, n, ld, h->A1, h->rowsy, h->cmean, h->YC, gs ? h->gram_diag + ld : nullptr, gs ? h->amax + 2 : nullptr);
+    if (gs) {
+      split3_pack(st, n, ld, h->A1, h->cmean, false, h->Gp2, 2, h->amax + 2);      // Yc^T (A1 is symmetric)
+      split3_pack(st, n, ld, h->YC, nullptr, false, h->Gp1, 2, h->amax + 2);       // Yc: both operands of Ky = Yc Yc^T
+    }
+  }
+}
+
+// linear_HSIC / linear_CKA (utils.py:1085-1096): the entropy terms, the low-rank decision, and the operands of whichever
+// evaluation the step takes -- the factors of the low-rank forms, or Yc centred (and packed) for the Grams
+static int hsic_terms(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, he = s.he;
+  if (s.want_xc && h->lr_ok && !s.cka) {
+    // Low-rank path for c2 needs every off-diagonal pair active in the decode's relu (relu'(0) = 0 would
+    // mask a pair in the backward); that is data dependent, so the count is read back once per step.
+    unsigned int masked = 0;
+    if (s.use2) {
+      MCGRA_HIP(hipMemcpyAsync(&masked, h->nmask, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+      MCGRA_HIP(hipStreamSynchronize(st));
+    }
+    h->lr_step = (masked == 0);
+    if (s.use2) h->skip_fused = masked != 0;
+    if (h->lr_step && s.p1_deferred) CHK(fork_p1(s));
+  }
+  // on a low-rank step with c2 the modified_adj1 side (c7 value and gradient) is folded into k_lr_decode_bwd
+  const bool y_fused = h->lr_step && s.use2 && lr_decode_supported(he);
+  // A step that IS a Gram evaluation centres and packs modified_adj1 and starts Ky FIRST: the side stream is idle from the end of
+  // Kx until this point, and the N x N entropy pass and its reduction (40 us at n = 3312) need none of it
+  s.ky_early = s.gs_only && s.use2 && !h->lr_step && s.gst != st;
+  if (s.ky_early) { center_yc(s); CHK(launch_ky(s)); }
+  elem_terms(s, 0.f, 0.f, !y_fused);
+  if (!s.want_xc) return 0;
+  if (h->lr_step) {
+    ++h->lr_steps;
+    if (s.use2) {
+      launch_lr_colstats(st, n, he, h->Zn, h->hmax, h->lrStats);
+      launch_lr_prep(st, n, he, h->Zn, h->hmax, h->lrStats, h->lrL, h->lrV, h->lr_ldv, h->lrDelta);
+      // T = Xc^T [U | D Z | delta^2]: W, W2 and t3 from one pass over Xc
+      CHK(eg(h, st, true, false, n, h->lr_ldv, n, 1.f, h->XC, ld, h->lrV, h->lr_ldv, 0.f, h->lrT, h->lr_ldv));
+      h->t3_zero = false;
+      launch_lr_post(st, n, he, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
+    }
+    return 0;
+  }
+  ++h->general_steps;
+  if (s.use2 && !s.ky_early) center_yc(s);
+  return 0;
+}
+
+// The part of the backward that needs the forward only: small-operand terms c9 (:237-258) and c10 (:259-272), and the
+// victim(adj_norm) chain's backward down to G_P of every layer.  (A Gram-evaluation step runs it beside its Grams.)
+// (the small-operand terms need em and softmax(output2) only and feed the backward of the modified_adj chain, the last part of the
+//  step: ~20 launches of a few microseconds each -- a sixth of a Citeseer-sized step's critical path -- that run on the third stream
+//  beside the decode, the N x N loss passes and the Grams; their products use their own split-K workspace: small_term)
+// The fork EVENT is recorded right behind the forward chains; the launches themselves are enqueued later in program order
+// (early_bwd: beside the Grams, or at the top of the backward) -- the host needs ~5 us per launch, and enqueued in front of the
+// decode they left the caller's queue empty for that long (213 us idle under the profiler, a third of the gain).
+static int small_terms(GeneralStep& s, hipStream_t q) {
+  mcgra_attack* h = s.h;
+  MCGRA_HIP(hipMemsetAsync(h->Gem, 0, sizeof(float) * (size_t)h->n * h->hmax, q));
+  if (s.use9) CHK(small_term(h, q, s.he, s.em, h->hsum, h->HAg, h->HAc, s.sg * s.k9, h->Gem, h->hmax, S_C9));
+  if (s.use10) {
+    MCGRA_HIP(hipMemsetAsync(h->Gsm, 0, sizeof(float) * (size_t)h->n * h->C, q));
+    CHK(small_term(h, q, h->C, h->sm2, h->C, h->YAg, h->YAc, s.sg * s.k10, h->Gsm, h->C, S_C10));
+    launch_softmax_bwd(q, h->n, h->C, h->sm2, h->Gsm, h->C, h->GZ2);
+  }
+  return 0;
+}
+static int early_bwd(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, L = h->L, C = h->C, hs = h->hsum;
+  if (!s.small_side) CHK(small_terms(s, st));
+  // ---- backward: victim(adj_norm) chain -> G_adjn
+  if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z, h->GZ);     // through elu(out_att(x)) (gat.py:206)
+  launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                     h->Pv + h->off[L - 1], hs, h->act, nullptr, 0, h->GPv + h->off[L - 1], hs);
+  CHK(chain_backward(h, st, h->ADJN, h->ld, L - 1, h->Pv, h->GPv, -1, nullptr, 0));
+  if (s.small_side) {      // (behind the victim chain's launches in program order: the caller's queue is fed first)
+    MCGRA_HIP(hipStreamWaitEvent(h->st3, h->ev_fork3, 0));
+    CHK(small_terms(s, h->st3));
+    MCGRA_HIP(hipEventRecord(h->ev_join3, h->st3));
+  }
+  return 0;
+}
+
+// G_adjn += sum_l G_P_l T_l^T (+ the low-rank 2 s2 (U M1^T - D Z W^T) of a low-rank step, in the same pass)
+static int victim_rankk(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, he = s.he;
+  const bool lr2 = s.hsic && h->lr_step && s.use2;
+  if (lr2 && rankk_nt_supported(n, n, hs, 2 * he)) {
+    MCGRA_HIP(rankk_nt(st, n, n, hs, 1.f, h->GPv, hs, h->Tv, hs, 2 * he, 2.f * (float)(s.sg * s.k2), h->lrL, 2 * he, h->lrR,
+                       2 * he, 1.f, h->G_ADJN, ld));
+    return 0;
+  }
+  if (lr2) CHK(eg(h, st, false, true, n, n, 2 * he, 2.f * (float)(s.sg * s.k2), h->lrL, 2 * he, h->lrR, 2 * he, 1.f, h->G_ADJN, ld));
+  return eg(h, st, false, true, n, n, hs, 1.f, h->GPv, hs, h->Tv, hs, 1.f, h->G_ADJN, ld);   // sum_l G_P_l T_l^T
+}
+
+// linear_CKA's value sums and the left factors of its gradient products (L1 -> KY, L2 -> KX) from the Grams (lower: in lower
+// tile storage); amax_l2 / amax_l1: their magnitudes, for the split kernel's packs
+static void cka_factors(GeneralStep& s, bool lower, float* amax_l2 = nullptr, float* amax_l1 = nullptr) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  launch_cka_sums(st, n, ld, h->KX, h->KY, h->KFC, s.use1, s.use2, h->rowvals + 4 * (size_t)ld, lower);
+  launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 4, h->scal + S_CK0);
+  launch_cka_coef(st, h->scal + S_CK0, h->cst + 0, s.use1 ? (float)s.k1 : 0.f, s.use2 ? (float)s.k2 : 0.f, h->coef);
+  launch_cka_lincomb(st, n, ld, h->KX, h->KY, h->KFC, h->coef, s.use1, s.use2, lower, amax_l2, amax_l1);
+}
+
+// ---- Gram evaluation on the split kernel (steps the low-rank forms do not cover): four N x N x N products.  They run on
+// the Gram stream (gram_ovl) beside the HBM-bound rest of the step:
+//   Kx = Xc Xc^T   beside the forward chains, the decode, the entropy pass and Yc's centring / packs
+//   Ky = Yc Yc^T   beside the small-operand terms and the victim chain's backward
+//   G_A1 += LX Yc  beside the victim chain's rank-k update of G_adjn
+//   G_adjn += LY Xc  beside the decode backward and the modified_adj chain's backward
+// Full Kx and Ky from the fp16 planes of Xc and Yc (split_symm_bf16.hip): tiles on or below the diagonal, mirrored by the
+// epilogue; split-K slabs in G_A, idle until the tail.  G_A1 += LX Yc needs Kx only (LX = 2 s2 Kxc is packed beside Ky),
+// G_adjn += LY Xc (LY = 2 (s1 Kfc + s2 Kyc) is combined and packed beside the third), its slabs in KX (dead: combined and
+// packed).  linear_CKA's factors need both Grams: it combines first.
+static int gram_eval(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st, gst = s.gst; const int n = h->n, ld = h->ld;
+  const float s1 = (float)(s.sg * s.k1), s2 = (float)(s.sg * s.k2);
+  if (!s.gs_only) {      // (a low-rank configuration whose decode found a dead row: Xc was centred, not packed)
+    split3_pack(st, n, ld, h->XC, nullptr, false, h->Gp0, 2, h->amax + 1);
+    CHK(fork_kx(h, st));
+  }
+  if (!s.ky_early) CHK(launch_ky(s));      // (hsic_terms started it in front of the entropy pass when it could)
+  ++h->gram_split_steps;
+  const void* LY = h->Gp1;
+  if (!s.cka) {
+    // operand scales of LY / LX from the diagonals of the centred Grams (known since the centring passes)
+    hsic_gram_scales(st, n, (h->lr_ok && s.use2) ? h->lrRs : h->gram_diag, h->gram_diag + ld, s.use1 ? s1 : 0.f, s.use2 ? s2 : 0.f,
+                     h->amax);
+    if (gst != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
+    if (s.use2) {
+      // LX = 2 s2 Kxc into the planes Xc's rows held (Kx is done with them); G_A1 += LX Yc right behind Ky (ev_second: complete)
+      split3_pack(st, n, ld, h->KX, nullptr, false, h->Gp0, 2, h->amax + 4, 2.f * s2);
+      CHK(gram_product(h, st, gst, h->Gp0, h->Gp2, h->G_A1, h->G_A, h->amax + 4, h->amax + 2, SPLIT_BETA, h->ev_second));
+    }
+    // beside the Grams: everything of the backward that needs the forward only -- enqueued BEHIND the fork of G_A1 += LX Yc, whose
+    // operand pack needs Kx and the diagonals only: the ~20 small-operand launches cost the host ~70 us, and in front of the
+    // pack they held the third product back by that long (r06 timeline: 27 us between Ky's reduction and the product)
+    CHK(early_bwd(s));
+    if (s.use2 && gst != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));      // the combine reads Ky
+    // LY straight into its packed planes (the planes Yc's rows held: Ky is done with them), the two value sums from the same
+    // pass (partials in YC, dead once packed) -- beside G_A1 += LX Yc
+    hsic_combine_pack(st, n, ld, h->KX, h->KY, h->KFC, s.use1 ? s1 : 0.f, s.use2 ? s2 : 0.f, h->amax, h->Gp1, nullptr,
+                      reinterpret_cast<double*>(h->YC), h->rowvals + 4 * (size_t)ld);
+    launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 2, h->scal + S_H1);
+  } else {
+    CHK(early_bwd(s));
+    if (gst != st) MCGRA_HIP(hipStreamWaitEvent(st, s.use2 ? h->ev_join : h->ev_first, 0));
+    // linear_CKA (:486): the same two gradient products with left factors L1 -> KY, L2 -> KX
+    MCGRA_HIP(hipMemsetAsync(h->amax + 3, 0, 2 * sizeof(float), st));
+    cka_factors(s, false, h->amax + 4, h->amax + 3);
+    split3_pack(st, n, ld, h->KY, nullptr, false, h->Gp0, 2, h->amax + 3);
+    LY = h->Gp0;
+    if (s.use2) {
+      split3_pack(st, n, ld, h->KX, nullptr, false, h->Gp1, 2, h->amax + 4);
+      CHK(gram_product(h, st, gst, h->Gp1, h->Gp2, h->G_A1, h->G_A, h->amax + 4, h->amax + 2, SPLIT_BETA, h->ev_second));
+    }
+  }
+  // G_adjn += LY Xc behind the victim chain's rank-k update of G_adjn
+  CHK(victim_rankk(s));
+  CHK(gram_product(h, st, gst, LY, h->Bpack, h->G_ADJN, h->KX, h->amax + 3, h->amax + 1, SPLIT_BETA, h->ev_join));
+  MCGRA_KERNEL_CHECK();
+  return 0;
+}
+
+// ---- the same on the fp32 MFMA GEMM: Grams are symmetric, only the 128x128 tiles on or below the diagonal are computed (lower
+// tile storage), and the gradient products read the mirrored half transposed (SYMM): 3 n^3 MACs per step instead of 4
+static int gram_fp32(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  CHK(eg_syrk(h, st, n, n, h->XC, ld, h->KX, ld, s.use2 ? h->YC : nullptr, s.use2 ? h->KY : nullptr));   // H Kx H (and H Ky H)
+  if (s.cka) cka_factors(s, true);
+  else {
+    const float s1 = (float)(s.sg * s.k1), s2 = (float)(s.sg * s.k2);
+    launch_hsic_combine(st, n, ld, h->KX, h->KY, h->KFC, s.use1 ? s1 : 0.f, s.use2 ? s2 : 0.f, h->rowvals + 4 * (size_t)ld, true);
+    launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 2, h->scal + S_H1);
+  }
+  // G_adjn += 2 (s1 Kfc + s2 Kyc) @ Xc ;  G_A1 += 2 s2 Kxc @ Yc   (K 1 = 0, so Xc may replace X)
+  if (s.use2) CHK(eg_symm(h, st, n, n, h->KY, ld, h->XC, ld, 1.f, h->G_ADJN, ld, h->KX, h->YC, h->G_A1));
+  else CHK(eg_symm(h, st, n, n, h->KY, ld, h->XC, ld, 1.f, h->G_ADJN, ld));
+  MCGRA_KERNEL_CHECK();
+  return 0;
+}
+
+// ---- backward: the low-rank step's decode factors, the forward-only part (unless the Gram evaluation ran it beside its
+// products), the decode, and the modified_adj chain (embedding + output2) down to G_P
+static int step_backward(GeneralStep& s) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, L = h->L, Le = h->Le, C = h->C, he = s.he;
+  const bool lr2 = s.hsic && h->lr_step && s.use2;
+  if (lr2) {
+    CHK(eg(h, st, false, false, n, 2 * he, n, 1.f, h->XC, ld, h->lrT, h->lr_ldv, 0.f, h->lrQ, 2 * he));         // [Q | Q2] = Xc [W | W2]
+    if (!lr_decode_supported(he))     // widths without a fused decode backward: d c2 / d A1 += 2 s2 Q Z^T, materialised
+      CHK(eg(h, st, false, true, n, n, he, 2.f * (float)(s.sg * s.k2), h->lrQ, 2 * he, h->Zn, h->hmax, 1.f, h->G_A1, ld));
+    MCGRA_KERNEL_CHECK();
+  }
+  if (!s.gram_eval) { CHK(early_bwd(s)); CHK(victim_rankk(s)); }      // (a Gram-evaluation step ran both beside its products)
+  // the decode backward reads G_A1: behind G_A1 += LX Yc on the Gram stream
+  if (s.gram_eval && s.use2 && s.gst != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_second, 0));
+
+  // ---- backward: decode (S = Zn Zn^T, A1 = offdiag relu(S))
+  if (lr2 && lr_decode_supported(he)) {
+    // ((G + G^T) o [S > 0]) Zn for G = ie'(A1) + 2 s2 Q Z^T, without materialising G (c7 value from the same pass)
+    const int np = launch_lr_decode_bwd(st, n, ld, he, h->A1, h->Zn, h->hmax, h->lrQ, (float)(s.k7 / s.n2), h->ws,
+                                        h->rowvals + 6 * (size_t)ld, h->GZn, h->hmax, h->lrQtZ);
+    if (np > 0) launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, np, 1, h->scal + S_V7);
+  } else {
+    launch_sym_mask(st, n, ld, h->G_A1, h->A1, h->has_ori ? h->ORI : nullptr, h->G_A);    // G_A used as scratch for (G + G^T) * [S > 0]
+    CHK(eg(h, st, false, false, n, he, n, 1.f, h->G_A, ld, h->Zn, h->hmax, 0.f, h->GZn, h->hmax));
+  }
+  if (lr2) {   // the -2 s2 KX D part of d c2 / d A1, applied to Zn directly
+    const bool fused = lr_decode_supported(he);
+    launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrDelta, h->lrRs, -2.f * (float)(s.sg * s.k2), h->GZn, h->hmax,
+                    h->rowvals + 7 * (size_t)ld, h->rowvals + 5 * (size_t)ld, fused ? h->lrStats + 2 * he : nullptr,
+                    fused ? h->lrQtZ : nullptr, 2.f * (float)(s.sg * s.k2));
+    launch_reduce_rows(st, h->rowvals + 5 * (size_t)ld, n, 1, h->scal + S_H2);
+  }
+  if (s.small_side) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join3, 0));      // c9 / c10: Gem, GZ2 and their scalars
+  launch_row_normalize_bwd(st, n, he, h->GZn, h->Zn, h->hmax, h->nrm, h->Gem, h->hmax);
+
+  // ---- backward: modified_adj chain (embedding + output2) -> G_A
+  if (h->has_ori) {
+    // two chains: output2 on modified_adj (only c10 reaches it) and the embedding on modified_adj - ori (em)
+    MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
+    MCGRA_HIP(hipMemsetAsync(h->GPe, 0, sizeof(float) * (size_t)n * hs, st));
+    if (s.use10) {
+      if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
+      launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                         h->Pu + h->off[L - 1], hs, h->act, nullptr, 0, h->GPu + h->off[L - 1], hs);
+      CHK(chain_backward(h, st, s.A, ld, L - 1, h->Pu, h->GPu, -1, nullptr, 0));
+    }
+    launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pe + h->off[Le - 1], hs, h->act, h->Gem, h->hmax, h->GPe + h->off[Le - 1], hs);
+    CHK(chain_backward(h, st, h->Bbuf, ld, Le - 1, h->Pe, h->GPe, -1, nullptr, 0));
+    return 0;
+  }
+  int ltop;
+  if (s.use10) {
+    ltop = L - 1;
+    if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
+    launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pu + h->off[L - 1], hs, h->act, (L - 1 == Le - 1) ? h->Gem : nullptr, h->hmax,
+                       h->GPu + h->off[L - 1], hs);
+  } else {
+    ltop = Le - 1;
+    if (L > Le) MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
+    launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pu + h->off[Le - 1], hs, h->act, h->Gem, h->hmax, h->GPu + h->off[Le - 1], hs);
+  }
+  CHK(chain_backward(h, st, s.A, ld, ltop, h->Pu, h->GPu, Le - 1, h->Gem, h->hmax));
+  return 0;
+}
+
+// ---- tail: the low-rank step's last contribution to G_adjn, normalisation backward, packed-gradient mirror + Adam + projection
+// + clamp (:274-283), scalars
+static int step_tail(GeneralStep& s, double* scalars_out) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const mcgra_attack_config_t& c = h->cfg;
+  const int n = h->n, ld = h->ld, hs = h->hsum;
+  // the normalisation backward reads G_adjn: behind G_adjn += LY Xc on the Gram stream
+  if (s.gram_eval && s.gst != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+  bool normbwd_parts = false;
+  float* nb_colpart = h->colpart;       // column partials of the normalisation backward: [nb_strips][n]
+  int nb_strips = h->nstrips;
+  if (s.hsic && h->lr_step && (s.use1 || s.use2)) {
+    // Last contribution to G_adjn, and the only consumer of P1: everything above ran beside the forked product.
+    // G_adjn += 2 s1 P1 + 2 s2 (D^2 Xc + 1 c^T);  v1 = sum P1 o Xc
+    if (h->p1_inflight) {
+      if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+      h->p1_inflight = false;
+    }
+    // ... fused with the two N x N reductions of the normalisation backward that follows (one pass instead of three);
+    // its partial sums live in KY, idle on a low-rank step (the product that used it as split-K slab has been joined)
+    if (lr_elem_normbwd_scratch_floats(n) <= (size_t)n * ld) {
+      double* v1part = nullptr;
+      int v1count = 0;
+      launch_lr_elem_normbwd(st, n, ld, h->XC, s.use1 ? h->KX : nullptr, s.use2 ? h->lrDelta : nullptr, s.use2 ? h->lrC : nullptr,
+                             2.f * (float)(s.sg * s.k1), 2.f * (float)(s.sg * s.k2), h->G_ADJN, s.A, h->r, h->KY, h->rowpart,
+                             &nb_colpart, &nb_strips, &v1part, &v1count);
+      launch_reduce_rows(st, v1part, v1count, 1, h->scal + S_H1);
+      normbwd_parts = true;
+    } else {
+      launch_lr_elem(st, n, ld, h->XC, s.use1 ? h->KX : nullptr, s.use2 ? h->lrDelta : nullptr, s.use2 ? h->lrC : nullptr,
+                     2.f * (float)(s.sg * s.k1), 2.f * (float)(s.sg * s.k2), h->G_ADJN, h->rowvals + 4 * (size_t)ld);
+      launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 1, h->scal + S_H1);
+    }
+  }
+  // Adam's scalars first: the fused tail below consumes them
+  h->t += 1;
+  const double b1 = 0.9, b2 = 0.999;
+  const double bc1 = 1.0 - pow(b1, (double)h->t), bc2 = 1.0 - pow(b2, (double)h->t);
+  hipLaunchKernelGGL(k_cn, dim3(1), dim3(1), 0, st, h->scal, (float)(c.weight_sup * 0.001), h->mm + 2);
+  // clamp(a,0,1).sum() <= n(n-1)/2, so a larger budget can never trigger the bisection (:339)
+  const bool may_project = c.num_edges < 0.5 * s.n2;
+  bool adam_done = false;
+  // normalisation backward writes G_A (beta = 0), then the chain's outer products accumulate
+  if (h->fuse_tail && rankk_apply_adam_supported(n, ld, hs) && !h->has_ori) {
+    // one pass over the lower tile pairs: apply step + rank-k update + gradient mirror + Adam, no G_A in between
+    launch_normbwd(st, n, ld, h->G_ADJN, s.A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
+    // (its row sums of the new M go to G_A, which this path leaves unused; not with a projection still to come)
+    const size_t cnt = (size_t)n * rankk_apply_adam_tiles(n);
+    const bool emit = !may_project && !s.gen && 3 * cnt + 4 <= (size_t)n * ld;
+    MCGRA_HIP(rankk_apply_adam(st, n, ld, hs, h->GPu, hs, h->Tu, hs, h->G_ADJN, h->r, h->gd, s.gate, h->M, h->am, h->av, h->mm + 2,
+                               (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
+                               h->keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
+                               emit ? reinterpret_cast<double*>(h->G_A + ((cnt + 1) & ~(size_t)1)) : nullptr));
+    h->prep_valid = emit;
+    adam_done = true;
+  } else if (rankk_nt_supported(n, n, hs, 0) && !h->has_ori) {
+    // one pass: G_A = GPu Tu^T + (G_adjn_ij r_i r_j + gd_i), the apply step of the normalisation backward as the
+    // epilogue of the rank-k update
+    launch_normbwd(st, n, ld, h->G_ADJN, s.A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
+    MCGRA_HIP(rankk_nt(st, n, n, hs, 1.f, h->GPu, hs, h->Tu, hs, 0, 0.f, nullptr, 0, nullptr, 0, 0.f, h->G_A, ld, h->G_ADJN, ld,
+                       h->r, h->gd));
+  } else {
+    launch_normbwd(st, n, ld, h->G_ADJN, s.A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, h->G_A, normbwd_parts);
+    CHK(eg(h, st, false, true, n, n, hs, 1.f, h->GPu, hs, h->Tu, hs, 1.f, h->G_A, ld));
+    if (h->has_ori) CHK(eg(h, st, false, true, n, n, hs, 1.f, h->GPe, hs, h->Te, hs, 1.f, h->G_A, ld));   // d / d (modified_adj - ori)
+  }
+
+  // ---- packed-gradient mirror + Adam + projection + clamp (:274-283)
+  if (!adam_done) {
+    h->prep_valid = false;
+    launch_adam_sym(st, n, ld, h->G_A, s.gate, h->M, h->am, h->av, h->mm + 2, (float)(1.0 - b1), (float)b2,
+                    (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f, h->keep_gsym ? h->GSYM : nullptr,
+                    may_project ? 0 : 1);
+  }
+  MCGRA_KERNEL_CHECK();
+  h->have_step = true;
+  if (may_project) { CHK(project(h, st)); h->prep_valid = false; }
+
+  if (scalars_out) CHK(collect_scalars(h, st, scalars_out));
+  return 0;
+}
+
+int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* scalars_out) {
   if (!h) { set_error("null handle"); return MCGRA_EINVAL; }
   if (!h->graph_set) { set_error("mcgra_attack_set_graph must be called first"); return MCGRA_EINVAL; }
   if ((h->cfg.eps != 0.f) != (noise != nullptr)) {
@@ -955,7 +1494,7 @@ static int step_impl(mcgra_attack_t* h, void* stream, const float* noise, double
   }
   // (after a step whose decode masked a pair the general path goes first: it reads the masked-pair count itself, and
   // only once that is zero again is the fused step worth enqueueing -- a masked run otherwise pays for both every step)
-  if (phases == 0xF && !noise && !h->sharded && fused_step_possible(h) && !h->skip_fused) {
+  if (!noise && !h->sharded && fused_step_possible(h) && !h->skip_fused) {
     const int rc = fused_step(h, st, scalars_out);      // 1: a relu-masked pair in the decode, the general path redoes the step
     if (rc <= 0) return rc;
   }
@@ -963,592 +1502,49 @@ static int step_impl(mcgra_attack_t* h, void* stream, const float* noise, double
   h->fused_fwd_valid = false;
   if (h->early_pack) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0)); h->early_pack = false; }      // (the general step packs its own operands)
   // Kx of this step's adj_norm, forked by the monitor call whose forward the step adopts: taken over (anything else is dropped)
-  const bool kx_adopt = h->kx_early && h->fwd_cached && !noise && !h->has_ori && phases == 0xF;
+  const bool kx_adopt = h->kx_early && h->fwd_cached && !noise && !h->has_ori;
   if (kx_adopt) h->kx_early = false;
   CHK(drop_early_p1(h, st));
+
   const mcgra_attack_config_t& c = h->cfg;
-  const int n = h->n, ld = h->ld, hs = h->hsum, L = h->L, Le = h->Le, C = h->C;
-  const double sg = sign_of(h);
+  GeneralStep s{};
+  s.h = h; s.st = st; s.noise = noise; s.he = h->wdt[h->Le - 1]; s.sg = sign_of(h); s.n2 = (double)h->n * h->n;
   const double w1 = c.w[0], w2 = c.w[1], w6 = c.w[5], w7 = c.w[6], w9 = c.w[8], w10 = c.w[9];
-  const double k1 = w1 * 1000 * AP_C1, k2 = w2 * 100 * AP_C2, k6 = w6 * 100 * AP_C6, k7 = w7 * AP_C7;
-  const double k9 = w9 * AP_C9, k10 = w10 * AP_C10;
-  const double n2 = (double)n * n;
-  const bool cka = c.measure == MCGRA_MEASURE_CKA;
-  const bool hsic = c.measure == MCGRA_MEASURE_HSIC || cka;      // both run the centred-Gram path
-  const bool gen = noise != nullptr || h->has_ori;      // modified_adj = clamp(M + ori + eps noise) with its gate
-  const float* A = gen ? h->Abuf : h->M;     // modified_adj == M when ori == 0, eps == 0
-  const unsigned char* gate = gen ? h->gate : nullptr;
-  const float* em = (h->has_ori ? h->He : h->Hu) + h->off[Le - 1];
-  const int he = h->wdt[Le - 1];
-  const bool use1 = (w1 != 0), use2 = (w2 != 0);
-  const bool sym = true;      // SYRK / SYMM on lower tile storage for the linear_HSIC Grams
-  // tile rows of this rank (single GPU: all of them)
-  const int t_all = (n + SYM_TILE - 1) / SYM_TILE;
-  // (a trailing rank of a padded plan may own no tile rows at all: t0 == t1 == t_all)
-  const int t0 = 0, t1 = t_all;          // (row-block ranks run the fused step: attack_fused.hip)
-  const bool sharded = false;
-  const int sflag = h->split_single ? 8 : 0;      // MCGRA_SPLIT_BF16=1: the Gram evaluation's four products as single-plane products too
-
-  // The part of the backward that needs the forward only: small-operand terms c9 (:237-258) and c10 (:259-272), and the
-  // victim(adj_norm) chain's backward down to G_P of every layer.  (A Gram-evaluation step runs it beside its Grams.)
-  // (the small-operand terms need em and softmax(output2) only and feed the backward of the modified_adj chain, the last part of the
-  //  step: ~20 launches of a few microseconds each -- a sixth of a Citeseer-sized step's critical path -- that run on the third stream
-  //  beside the decode, the N x N loss passes and the Grams; their products use their own split-K workspace: small_term)
-  // The fork EVENT is recorded right behind the forward chains; the launches themselves are enqueued later in program order
-  // (early_bwd: beside the Grams, or at the top of the backward) -- the host needs ~5 us per launch, and enqueued in front of the
-  // decode they left the caller's queue empty for that long (213 us idle under the profiler, a third of the gain).
-  bool small_forked = false, small_fork_armed = false;
-  auto small_terms = [&](hipStream_t s) -> int {
-    MCGRA_HIP(hipMemsetAsync(h->Gem, 0, sizeof(float) * (size_t)n * h->hmax, s));
-    if (w9 != 0) CHK(small_term(h, s, he, em, hs, h->HAg, h->HAc, sg * k9, h->Gem, h->hmax, S_C9));
-    if (w10 != 0) {
-      MCGRA_HIP(hipMemsetAsync(h->Gsm, 0, sizeof(float) * (size_t)n * C, s));
-      CHK(small_term(h, s, C, h->sm2, C, h->YAg, h->YAc, sg * k10, h->Gsm, C, S_C10));
-      launch_softmax_bwd(s, n, C, h->sm2, h->Gsm, C, h->GZ2);
-    }
-    return 0;
-  };
-  auto early_bwd = [&]() -> int {
-    if (!small_fork_armed) CHK(small_terms(st));
-    // ---- backward: victim(adj_norm) chain -> G_adjn
-    if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z, h->GZ);     // through elu(out_att(x)) (gat.py:206)
-    launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pv + h->off[L - 1], hs, h->act, nullptr, 0, h->GPv + h->off[L - 1], hs);
-    CHK(chain_backward(h, st, h->ADJN, ld, L - 1, h->Pv, h->GPv, -1, nullptr, 0));
-    if (small_fork_armed) {      // (behind the victim chain's launches in program order: the caller's queue is fed first)
-      MCGRA_HIP(hipStreamWaitEvent(h->st3, h->ev_fork3, 0));
-      CHK(small_terms(h->st3));
-      MCGRA_HIP(hipEventRecord(h->ev_join3, h->st3));
-      small_forked = true;
-    }
-    return 0;
-  };
-  // G_adjn += sum_l G_P_l T_l^T (+ the low-rank 2 s2 (U M1^T - D Z W^T) of a low-rank step, in the same pass)
-  auto victim_rankk = [&]() -> int {
-    if (hsic && h->lr_step && use2 && rankk_nt_supported(n, n, hs, 2 * he)) {
-      MCGRA_HIP(rankk_nt(st, n, n, hs, 1.f, h->GPv, hs, h->Tv, hs, 2 * he, 2.f * (float)(sg * k2), h->lrL, 2 * he, h->lrR,
-                         2 * he, 1.f, h->G_ADJN, ld));
-    } else {
-      if (hsic && h->lr_step && use2)
-        CHK(eg(h, st, false, true, n, n, 2 * he, 2.f * (float)(sg * k2), h->lrL, 2 * he, h->lrR, 2 * he, 1.f, h->G_ADJN, ld));
-      CHK(eg(h, st, false, true, n, n, hs, 1.f, h->GPv, hs, h->Tv, hs, 1.f, h->G_ADJN, ld));   // sum_l G_P_l T_l^T
-    }
-    return 0;
-  };
-  bool gs_path = false, kx_started = false, ky_started = false, gs_early_bwd = false, gs_p4 = false, gs_p3 = false, gs_rankk_done = false;
-  hipStream_t sg_ = st;
-  std::function<int()> gs_fork, launch_ky;
-  std::function<int(bool)> launch_kx;
-  if (PH(0)) {
-  const bool adopt = h->fwd_cached && !gen;         // forward of this iteration already done by the last monitor call
+  s.k1 = w1 * 1000 * AP_C1; s.k2 = w2 * 100 * AP_C2; s.k6 = w6 * 100 * AP_C6; s.k7 = w7 * AP_C7; s.k9 = w9 * AP_C9; s.k10 = w10 * AP_C10;
+  s.use1 = w1 != 0; s.use2 = w2 != 0; s.use9 = w9 != 0; s.use10 = w10 != 0;
+  s.cka = c.measure == MCGRA_MEASURE_CKA;
+  s.hsic = c.measure == MCGRA_MEASURE_HSIC || s.cka;      // both run the centred-Gram path
+  s.gen = noise != nullptr || h->has_ori;
+  s.A = s.gen ? h->Abuf : h->M; s.gate = s.gen ? h->gate : nullptr; s.em = (h->has_ori ? h->He : h->Hu) + h->off[h->Le - 1];
+  s.want_xc = s.hsic && (s.use1 || s.use2);
+  s.gs_path = h->gram_split && !s.gen && s.want_xc;
+  s.gs_only = s.gs_path && !h->lr_ok;
+  s.gst = (s.gs_path && h->gram_ovl && h->st2) ? h->st2 : st;
+  s.adopt = h->fwd_cached && !s.gen; s.kx_adopt = kx_adopt;      // (kx_adopt implies adopt)
   h->fwd_cached = false;
-  // (S_SQ, S_SUM are the first two slots: written by forward_common, kept when its results are adopted)
-  MCGRA_HIP(hipMemsetAsync(h->scal + (adopt ? 2 : 0), 0, sizeof(double) * (S_COUNT - (adopt ? 2 : 0)), st));
-  // ---- forward: adjacency, normalisation (:164-166)
-  const float* noise_ld = nullptr;
-  if (noise) {  // caller layout is [n][n]; the kernels use leading dimension ld.  G_A is free at this point.
-    MCGRA_HIP(hipMemcpy2DAsync(h->G_A, (size_t)ld * 4, noise, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
-    noise_ld = h->G_A;
-  }
-  const bool want_xc = hsic && (use1 || use2);
-  // adj_norm is symmetric when eps == 0 (ori == 0): its column means are its row sums / n, which k_adjn emits
-  if (adopt) { float* t = h->ADJN; h->ADJN = h->ADJN_next; h->ADJN_next = t; }
-  else CHK(forward_common(h, st, h->ADJN, noise_ld, (want_xc && !gen) ? h->rowsx : nullptr));
-  h->p1_inflight = false;
-  std::function<int()> fork_p1;       // the forked product of a low-rank step, when its launch is deferred
-  // ---- Gram evaluation on the split kernel (steps the low-rank forms do not cover): four N x N x N products.  They run on
-  // the side stream (gram_ovl) beside the HBM-bound rest of the step:
-  //   Kx = Xc Xc^T   beside the forward chains, the decode, the entropy pass and Yc's centring / packs
-  //   Ky = Yc Yc^T   beside the small-operand terms and the victim chain's backward
-  //   G_A1 += LX Yc  beside the victim chain's rank-k update of G_adjn
-  //   G_adjn += LY Xc  beside the decode backward and the modified_adj chain's backward
-  // split-K slabs: G_A (Kx, Ky: idle until the tail), KY / KX (the two gradient products: dead once combined and packed)
-  gs_path = h->gram_split && !gen && want_xc;
-  const bool gs_only = gs_path && !h->lr_ok;      // known now that the step evaluates the Grams
-  sg_ = (gs_path && h->gram_ovl && h->st2) ? h->st2 : st;
-  gs_fork = [=]() -> int {      // the side stream picks up behind everything enqueued on the caller's so far
-    if (sg_ != st) { MCGRA_HIP(hipEventRecord(h->ev_fork, st)); MCGRA_HIP(hipStreamWaitEvent(sg_, h->ev_fork, 0)); }
-    return 0;
-  };
-  // (the (A, B) operand magnitudes of a product are read where they are: split3_symm takes B's through its own pointer.  Rounds
-  //  2 - 5 paired them up in amax[8 ..] with two 4-byte device-to-device copies per product -- eight launches of ~5 us per step on
-  //  the caller's queue.  No slot is rewritten between a product's fork and its join: amax[1] / [2] come out of the centring
-  //  passes of this step, [3] / [4] out of hsic_gram_scales / the CKA combine, all in front of the products that read them.)
-  launch_kx = [=](bool packed) -> int {      // Kx: lower tiles, mirrored by the epilogue (full, bitwise symmetric matrix)
-    if (!packed) split3_pack(st, n, ld, h->XC, nullptr, false, h->Gp0, 2, h->amax + 1);
-    CHK(gs_fork());
-    CHK(timer_begin(h, sg_, h->profile));
-    MCGRA_HIP(split3_symm(sg_, n, h->Gp0, h->Gp0, h->KX, ld, 0, -1, h->small_slab ? h->small_slab : h->G_A,
-                          h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, 2, h->amax + 1, 0, -1, 2 | sflag, 0, nullptr, 0, nullptr,
-                          h->amax + 1));
-    CHK(timer_end(h, sg_, h->profile, 2.0 * (double)n * n * n));
-    return 0;
-  };
-  // Ky = Yc Yc^T behind Kx on the side stream (ev_first: Kx done, ev_join: Ky done), from the planes the centring pass of
-  // modified_adj1 just packed
-  launch_ky = [=, &ky_started]() -> int {
-    if (sg_ != st) MCGRA_HIP(hipEventRecord(h->ev_first, sg_));    // Kx done
-    if (use2) {
-      const size_t slab = sizeof(float) * (size_t)n * ld;
-      CHK(gs_fork());
-      CHK(timer_begin(h, sg_, h->profile));
-      MCGRA_HIP(split3_symm(sg_, n, h->Gp1, h->Gp1, h->KY, ld, 0, -1, h->small_slab ? h->small_slab : h->G_A, h->small_slab ? h->small_slab_bytes : slab, 2, h->amax + 2, 0, -1, 2 | sflag, 0, nullptr, 0, nullptr, h->amax + 2));
-      CHK(timer_end(h, sg_, h->profile, 2.0 * (double)n * n * n));
-      if (sg_ != st) MCGRA_HIP(hipEventRecord(h->ev_join, sg_));   // Ky done
-    }
-    ky_started = true;
-    return 0;
-  };
-  if (want_xc) {
-    // Xc = H adj_norm (and, for the low-rank path, |xc_i|^2 = diag(Kx) from the same pass)
-    if (gen) {                               // possibly asymmetric: true column sums
-      if (!h->colpart_d) CHK(dalloc(h, &h->colpart_d, (size_t)h->nstrips * ld));
-      launch_colsum(st, n, ld, h->ADJN, h->colpart_d, h->nstrips, h->rowsx);
-    }
-    if (gs_only) {
-      // This step IS a Gram evaluation (no low-rank form: GAT / GraphSAGE victims, CKA, widths > 32, MCGRA_NO_LOWRANK): both
-      // packed orientations of Xc in ONE pass over adj_norm -- rows of Xc (the operands of Kx = Xc Xc^T) and rows of Xc^T (the B
-      // operand of G_adjn += LY Xc) -- with diag(Kx) from the same pass; the fp32 Xc is never stored.  Kx starts now, beside
-      // the forward chains and the decode.
-      // (kx_adopt: the monitor call of the previous iteration did exactly this on the adj_norm this step adopted)
-      if (!(kx_adopt && adopt)) CHK(gram_pack_fork_kx(h, st, h->ADJN));
-      kx_started = true;
-    } else {
-    // (gram_diag: |xc_i|^2 = diag(Kx) for the scale bound of the combined Grams -- only when the low-rank path does not want it)
-    const bool want_lrrs = h->lr_ok && !cka && use2;
-    launch_center_cols(st, n, ld, h->ADJN, h->rowsx, h->cmean, h->XC, want_lrrs ? h->lrRs : (gs_path ? h->gram_diag : nullptr),
-                       ((h->split_mode == 2 && h->split_planes == 2) || h->gram_split) ? h->amax + 1 : nullptr);
-    // Gram evaluation through the split kernel: planes of Xc^T now (cmean is reused by Yc's centring), unless the
-    // low-rank product below packs them anyway
-    if (h->gram_split && !gen && !(h->lr_ok && !cka && use1 && h->split_on))
-      split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, 2, h->amax + 1);
-    }
-    if (h->lr_ok && !cka && use1) {
-      // P1 = (H Kf H) Xc: value and gradient of c1 in the low-rank path; the only N x N x N product of such a
-      // step.  Forked onto st2 now (it needs nothing else of the step), joined in phase 1.
-      hipStream_t sp = h->overlap ? h->st2 : st;
-      // bf16 planes of Xc^T (opt-in split path) on the caller's stream, ahead of the fork: cmean is reused later
-      // (row blocks of a sharded step must start on a 256-row panel for the split kernel; otherwise fp32 SYMM)
-      const bool split_now = h->split_on && !gen;
-      if (split_now)
-        split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr);
-      fork_p1 = [=]() -> int {
-        if (h->overlap) {
-          MCGRA_HIP(hipEventRecord(h->ev_fork, st));
-          MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
-        }
-        if (split_now) {
-          // planes of Xc^T from the rows of the (symmetric) adj_norm, then the plane-reusing kernel (split_symm_bf16.hip)
-          const int row0 = t0 * SYM_TILE, row1 = t1 * SYM_TILE < n ? t1 * SYM_TILE : n;
-          const bool big = h->profile;
-          CHK(timer_begin(h, sp, big));
-          const int P = split3_panel(), p0 = row0 / P, p1 = (row1 + P - 1) / P;
-          // (split-K slabs of the ragged last round go to KY, idle on a low-rank step)
-          MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, p0, p1 - p0, h->small_slab ? h->small_slab : h->KY,
-                                h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->split_planes, h->amax, 0, -1,
-                                h->split_single ? 8 : 0));
-          CHK(timer_end(h, sp, big, 2.0 * (row1 > row0 ? row1 - row0 : 0) * (double)n * n));
-          ++h->split_steps;
-        } else
-        CHK(eg_symm(h, sp, true, n, n, h->KFC, ld, h->XC, ld, 0.f, h->KX, ld, nullptr, nullptr, nullptr, t0, t1 - t0));
-        if (h->overlap) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
-        h->p1_inflight = true;
-        return 0;
-      };
-      // (in a run whose decode keeps masking pairs the product would be thrown away: it then waits for this step's own
-      // masked-pair count, below)
-      if (!(h->skip_fused && use2)) { CHK(fork_p1()); fork_p1 = nullptr; }
-    }
-  }
-  // ---- victim(features, adj_norm) (:167) and the CE loss (:172)
-  if (!adopt) {
-    CHK(chain_forward(h, st, h->ADJN, ld, L, h->Tv, h->Pv, h->Hv, h->Sv));
-    CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->sm));
-  }
-  launch_nll_grad(st, n, C, h->logp, h->sm, C, h->labels, h->cnt, (float)(c.weight_sup / h->na), h->GZ, h->rowvals + 6 * (size_t)ld);
-  launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, n, 1, h->scal + S_NLL);
-  // ---- embedding(features, modified_adj - ori_adj) (:185) == first Le layers of victim(features, modified_adj) (:259)
-  CHK(chain_forward(h, st, A, ld, L, h->Tu, h->Pu, h->Hu, h->Su));
-  CHK(head_forward(h, st, h->Hu, h->Z2, nullptr, h->sm2));
-  if (h->has_ori) {      // embedding(features, modified_adj - ori_adj) (:185) no longer shares the chain of output2 (:259)
-    launch_axpby2d(st, n, A, ld, 1.f, h->ORI, ld, -1.f, h->Bbuf, ld);
-    CHK(chain_forward(h, st, h->Bbuf, ld, Le, h->Te, h->Pe, h->He, h->Se));
-  }
-  if (phases == 0xF && h->small_side_on && h->st3 && h->st3 != st && (w9 != 0 || w10 != 0)) {
-    MCGRA_HIP(hipEventRecord(h->ev_fork3, st));      // (em and softmax(output2) stand: what the small-operand terms need)
-    small_fork_armed = true;
-  }
-  // ---- dot_product_decode + get_modified_adj_after (:187-188)
-  launch_row_normalize(st, n, he, em, hs, h->Zn, h->hmax, h->nrm, 2.f);
-  CHK(eg(h, st, false, true, n, n, he, 1.f, h->Zn, h->hmax, h->Zn, h->hmax, 0.f, h->A1, ld));
-  // (the count of relu-masked pairs is read by the low-rank decision below only: HSIC with c2 on a configuration that has the
-  // low-rank forms -- every other step skips the counting)
-  const bool count_masked = c.measure == MCGRA_MEASURE_HSIC && h->lr_ok && c.w[1] != 0;
-  if (count_masked) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, sizeof(unsigned int), st));
-  h->nmask_zero = false;
-  launch_decode_post(st, n, ld, h->A1, h->has_ori ? h->ORI : nullptr, count_masked ? h->nmask : nullptr);
-  h->lr_step = false;
 
-  // ---- N x N loss terms (:212-236)
-  if (c.measure == MCGRA_MEASURE_DP) {
-    // dot_product(X, Y) = |Y^T X|_F (:480-481); d/dY = X P^T / |P|, d/dX = Y P / |P| with P = Y^T X
-    launch_loss_elem(st, n, ld, h->ADJN, h->A1, h->FADJ, 0.f, 0.f, (float)(k6 / n2), (float)(k7 / n2), h->G_ADJN,
-                     h->G_A1, h->rowvals);
-    launch_reduce_rows(st, h->rowvals, n, 4, h->scal + S_V1);
-    if (use1) {   // c1 = k1 dot_product(feature_adj, adj_norm): P = adj_norm^T Fadj
-      CHK(eg(h, st, true, false, n, n, n, 1.f, h->ADJN, ld, h->FADJ, ld, 0.f, h->KX, ld));
-      launch_rowsumsq(st, n, ld, h->KX, h->rowsx);
-      launch_reduce_rows(st, h->rowsx, n, 1, h->scal + S_H1);
-      CHK(eg(h, st, false, true, n, n, n, 1.f, h->FADJ, ld, h->KX, ld, 0.f, h->XC, ld));
-      launch_axpy_invnorm(st, n, ld, h->XC, h->scal + S_H1, (float)k1, h->G_ADJN);
-    }
-    if (use2) {   // c2 = k2 dot_product(adj_norm, A1): P = A1^T adj_norm
-      CHK(eg(h, st, true, false, n, n, n, 1.f, h->A1, ld, h->ADJN, ld, 0.f, h->KY, ld));
-      launch_rowsumsq(st, n, ld, h->KY, h->rowsy);
-      launch_reduce_rows(st, h->rowsy, n, 1, h->scal + S_H2);
-      CHK(eg(h, st, false, false, n, n, n, 1.f, h->A1, ld, h->KY, ld, 0.f, h->XC, ld));          // d/dX = Y P
-      launch_axpy_invnorm(st, n, ld, h->XC, h->scal + S_H2, (float)k2, h->G_ADJN);
-      CHK(eg(h, st, false, true, n, n, n, 1.f, h->ADJN, ld, h->KY, ld, 0.f, h->XC, ld));         // d/dY = X P^T
-      launch_axpy_invnorm(st, n, ld, h->XC, h->scal + S_H2, (float)k2, h->G_A1);
-    }
-  } else if (c.measure == MCGRA_MEASURE_KDE) {
-    // calc = MutualInformation(sigma=0.4, num_bins=N) (:199-201): c1 = k1 calc(feature_adj, adj_norm)[0] (:213-216),
-    // c2 = k2 calc(adj_norm, modified_adj1)[0] (:222-225).  Entry (i, j) of an operand meets bin j only and bins j >= 7 are
-    // out of reach of values <= 2 in float32 (kde_kernels.hip): the terms live on the first KDE_NXN_COLS columns.
-    launch_loss_elem(st, n, ld, h->ADJN, h->A1, h->FADJ, 0.f, 0.f, (float)(k6 / n2), (float)(k7 / n2), h->G_ADJN,
-                     h->G_A1, h->rowvals);
-    launch_reduce_rows(st, h->rowvals, n, 4, h->scal + S_V1);      // only the entropy slots are non-zero
-    const int kc = n < h->kde_cols ? n : h->kde_cols;      // (set_graph: 8, or as far as feature_adj's values reach)
-    if (use1) launch_kde_term(st, n, kc, n, h->FADJ, ld, h->ADJN, ld, k1, nullptr, 0, false, h->G_ADJN, ld, true, h->scal + S_H1, h->kde);
-    if (use2) launch_kde_term(st, n, kc, n, h->ADJN, ld, h->A1, ld, k2, h->G_ADJN, ld, true, h->G_A1, ld, true, h->scal + S_H2, h->kde);
-  } else if (c.measure == MCGRA_MEASURE_KL) {
-    launch_loss_elem(st, n, ld, h->ADJN, h->A1, h->FADJ, 0.f, 0.f, (float)(k6 / n2), (float)(k7 / n2), h->G_ADJN,
-                     h->G_A1, h->rowvals);
-    launch_reduce_rows(st, h->rowvals, n, 4, h->scal + S_V1);      // only the entropy slots are non-zero
-    if (use1 || use2) {
-      launch_kl_rows(st, n, ld, h->ADJN, h->A1, h->XC, use1 ? (float)k1 : 0.f, use2 ? (float)k2 : 0.f, h->G_ADJN,
-                     h->G_A1, h->rowvals + 4 * (size_t)ld);
-      launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 2, h->scal + S_H1);
-    }
-  } else if (!hsic) {
-    launch_loss_elem(st, n, ld, h->ADJN, h->A1, h->FADJ, (float)(k1 * 2.0 / n2), (float)(k2 * 2.0 / n2),
-                     (float)(k6 / n2), (float)(k7 / n2), h->G_ADJN, h->G_A1, h->rowvals);
-    launch_reduce_rows(st, h->rowvals, n, 4, h->scal + S_V1);
-  } else {
-    if ((use1 || use2) && h->lr_ok && !cka) {
-      // Low-rank path for c2 needs every off-diagonal pair active in the decode's relu (relu'(0) = 0 would
-      // mask a pair in the backward); that is data dependent, so the count is read back once per step.
-      unsigned int masked = 0;
-      if (use2) {
-        MCGRA_HIP(hipMemcpyAsync(&masked, h->nmask, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        MCGRA_HIP(hipStreamSynchronize(st));
-      }
-      h->lr_step = (masked == 0);
-      if (use2) h->skip_fused = masked != 0;
-      if (h->lr_step && fork_p1) CHK(fork_p1());
-    }
-    // on a low-rank step with c2 the modified_adj1 side (c7 value and gradient) is folded into k_lr_decode_bwd
-    const bool y_fused = h->lr_step && use2 && lr_decode_supported(he);
-    // A step that IS a Gram evaluation centres and packs modified_adj1 and starts Ky FIRST: the side stream is idle from the end of
-    // Kx until this point, and the N x N entropy pass and its reduction (40 us at n = 3312) need none of it
-    const bool ky_early = gs_only && use2 && !h->lr_step && phases == 0xF && sg_ != st && kx_started;
-    if (ky_early) {
-      launch_rowsum(st, n, ld, h->A1, h->rowsy);
-      launch_colmean_f32(st, n, ld, h->rowsy, h->cmean);
-      pack_center_both(st, n, ld, h->A1, h->cmean, nullptr, 1.0002f, h->Gp1, h->Gp2, h->amax + 2, h->gram_diag + ld,
-                       reinterpret_cast<double*>(h->YC));
-      CHK(launch_ky());
-    }
-    launch_loss_elem(st, n, ld, h->ADJN, y_fused ? nullptr : h->A1, h->FADJ, 0.f, 0.f, (float)(k6 / n2), (float)(k7 / n2),
-                     h->G_ADJN, y_fused ? nullptr : h->G_A1, h->rowvals);
-    launch_reduce_rows(st, h->rowvals, n, 4, h->scal + S_V1);
-    if (use1 || use2) {
-      if (h->lr_step) {
-        ++h->lr_steps;
-        if (use2) {
-          launch_lr_colstats(st, n, he, h->Zn, h->hmax, h->lrStats);
-          launch_lr_prep(st, n, he, h->Zn, h->hmax, h->lrStats, h->lrL, h->lrV, h->lr_ldv, h->lrDelta);
-          // T = Xc^T [U | D Z | delta^2]: W, W2 and t3 from one pass over Xc
-          CHK(eg(h, st, true, false, n, h->lr_ldv, n, 1.f, h->XC, ld, h->lrV, h->lr_ldv, 0.f, h->lrT, h->lr_ldv));
-          h->t3_zero = false;
-          launch_lr_post(st, n, he, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
-        }
-      } else {
-        ++h->general_steps;
-        if (use2 && !ky_early) {
-          launch_rowsum(st, n, ld, h->A1, h->rowsy);
-          const bool gs = h->gram_split && !gen;
-          if (gs && !h->lr_ok) {
-            // rows of Yc (both operands of Ky = Yc Yc^T) and of Yc^T (B operand of G_A1 += LX Yc) in one pass over the symmetric
-            // modified_adj1 (entries in [0, 1]), diag(Ky) from the same pass
-            launch_colmean_f32(st, n, ld, h->rowsy, h->cmean);
-            pack_center_both(st, n, ld, h->A1, h->cmean, nullptr, 1.0002f, h->Gp1, h->Gp2, h->amax + 2, h->gram_diag + ld,
-                             reinterpret_cast<double*>(h->YC));
-          } else {
-          launch_center_cols(st, n, ld, h->A1, h->rowsy, h->cmean, h->YC, gs ? h->gram_diag + ld : nullptr, gs ? h->amax + 2 : nullptr);
-          if (gs) {
-            split3_pack(st, n, ld, h->A1, h->cmean, false, h->Gp2, 2, h->amax + 2);      // Yc^T (A1 is symmetric)
-            split3_pack(st, n, ld, h->YC, nullptr, false, h->Gp1, 2, h->amax + 2);       // Yc: both operands of Ky = Yc Yc^T
-          }
-          }
-        }
-      }
-    }
-  }
+  CHK(step_forward(s));
+  const int m = c.measure;
+  CHK(m == MCGRA_MEASURE_DP ? dp_terms(s) : m == MCGRA_MEASURE_KDE ? kde_terms(s) : m == MCGRA_MEASURE_KL ? kl_terms(s)
+      : s.hsic ? hsic_terms(s) : mse_terms(s));
   MCGRA_KERNEL_CHECK();
-  }  // phase 0
-
-  if (PH(1) && hsic && (use1 || use2)) {
-    // Grams are symmetric: only the 128x128 tiles on or below the diagonal are computed (lower tile
-    // storage), and the gradient products read the mirrored half transposed (SYMM): 3 n^3 MACs per
-    // step instead of 4.  Sharded: tile rows [t0, t1) of this rank.
-    if (sharded && !sym) { set_error("row-block sharding needs the symmetric GEMM path"); return MCGRA_EINVAL; }
-    // Join the forked P1 product: always before the Gram path may overwrite KX; on a low-rank step only when
-    // the caller runs phases separately (the KX rows are exchanged after this phase).  A monolithic low-rank
-    // step joins as late as possible (phase 3, in front of the only consumer).
-    if (h->p1_inflight && (!h->lr_step || phases != 0xF)) {
+  s.gram_eval = s.gs_path && !h->lr_step;
+  if (s.want_xc) {
+    // Join the forked P1 product before the Grams may overwrite KX; a low-rank step joins it as late as possible, in front of
+    // its only consumer (step_tail)
+    if (h->p1_inflight && !h->lr_step) {
       if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
       h->p1_inflight = false;
     }
-    if (h->lr_step) {
-    } else if (gs_path) {
-      // full Kx and Ky from the fp16 planes of Xc and Yc (split_symm_bf16.hip): tiles on or below the diagonal, mirrored by
-      // the epilogue; split-K slabs in G_A, idle until the tail.  The four products of the step run back to back on the
-      // side stream: Kx, Ky, G_A1 += LX Yc (needs Kx only: LX = 2 s2 Kxc is packed beside Ky), G_adjn += LY Xc (LY = 2 (s1
-      // Kfc + s2 Kyc) is combined and packed beside the third).  linear_CKA's factors need both Grams: it combines first.
-      const size_t slab = sizeof(float) * (size_t)n * ld;
-      const float s1 = (float)(sg * k1), s2 = (float)(sg * k2);
-      if (!kx_started) { CHK(launch_kx(false)); kx_started = true; }      // (a low-rank configuration whose decode found a dead row)
-      if (!ky_started) CHK(launch_ky());      // (phase 0 started it in front of the entropy pass when it could)
-      ++h->gram_split_steps;
-      // beside the Grams: everything of the backward that needs the forward only -- enqueued BEHIND the fork of G_A1 += LX Yc, whose
-      // operand pack needs Kx and the diagonals only: the ~20 small-operand launches cost the host ~70 us, and in front of the
-      // pack they held the third product back by that long (r06 timeline: 27 us between Ky's reduction and the product)
-      if (cka) { CHK(early_bwd()); gs_early_bwd = true; }
-      if (!cka) {
-        // operand scales of LY / LX from the diagonals of the centred Grams (known since the centring passes)
-        hsic_gram_scales(st, n, (h->lr_ok && use2) ? h->lrRs : h->gram_diag, h->gram_diag + ld, use1 ? s1 : 0.f, use2 ? s2 : 0.f, h->amax);
-        if (sg_ != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
-        if (use2) {
-          // LX = 2 s2 Kxc into the planes Xc's rows held (Kx is done with them); G_A1 += LX Yc right behind Ky, slabs in G_A
-          split3_pack(st, n, ld, h->KX, nullptr, false, h->Gp0, 2, h->amax + 4, 2.f * s2);
-          CHK(gs_fork());
-          CHK(timer_begin(h, sg_, h->profile));
-          MCGRA_HIP(split3_symm(sg_, n, h->Gp0, h->Gp2, h->G_A1, ld, 0, -1, h->small_slab ? h->small_slab : h->G_A, h->small_slab ? h->small_slab_bytes : slab, 2, h->amax + 4, 0, -1, 1 | sflag, 0, nullptr, 0, nullptr, h->amax + 2));
-          CHK(timer_end(h, sg_, h->profile, 2.0 * (double)n * n * n));
-          if (sg_ != st) MCGRA_HIP(hipEventRecord(h->ev_second, sg_));   // G_A1 complete
-          gs_p4 = true;
-        }
-        CHK(early_bwd()); gs_early_bwd = true;
-        if (use2 && sg_ != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));      // the combine reads Ky
-        // LY straight into its packed planes (the planes Yc's rows held: Ky is done with them), the two value sums from the same
-        // pass (partials in YC, dead once packed) -- beside G_A1 += LX Yc
-        hsic_combine_pack(st, n, ld, h->KX, h->KY, h->KFC, use1 ? s1 : 0.f, use2 ? s2 : 0.f, h->amax, h->Gp1, nullptr,
-                          reinterpret_cast<double*>(h->YC), h->rowvals + 4 * (size_t)ld);
-        launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 2, h->scal + S_H1);
-      } else if (sg_ != st) {
-        MCGRA_HIP(hipStreamWaitEvent(st, use2 ? h->ev_join : h->ev_first, 0));
-      }
-    } else
-    if (use2) CHK(eg_syrk(h, st, sym, n, n, h->XC, ld, h->KX, ld, h->YC, h->KY, t0, t1 - t0));   // H Kx H and H Ky H
-    else CHK(eg_syrk(h, st, sym, n, n, h->XC, ld, h->KX, ld, nullptr, nullptr, t0, t1 - t0));    // H Kx H
+    if (s.gram_eval) CHK(gram_eval(s));
+    else if (!h->lr_step) CHK(gram_fp32(s));
   }
-
-  if (PH(2) && hsic && (use1 || use2) && !h->lr_step && gs_path) {
-    const size_t slab = sizeof(float) * (size_t)n * ld;
-    const bool big = h->profile;
-    const void* LY = h->Gp1;
-    if (cka) {      // linear_CKA (:486): the same two gradient products with left factors L1 -> KY, L2 -> KX
-      MCGRA_HIP(hipMemsetAsync(h->amax + 3, 0, 2 * sizeof(float), st));
-      launch_cka_sums(st, n, ld, h->KX, h->KY, h->KFC, use1, use2, h->rowvals + 4 * (size_t)ld, false);
-      launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 4, h->scal + S_CK0);
-      launch_cka_coef(st, h->scal + S_CK0, h->cst + 0, use1 ? (float)k1 : 0.f, use2 ? (float)k2 : 0.f, h->coef);
-      launch_cka_lincomb(st, n, ld, h->KX, h->KY, h->KFC, h->coef, use1, use2, false, h->amax + 4, h->amax + 3);
-      split3_pack(st, n, ld, h->KY, nullptr, false, h->Gp0, 2, h->amax + 3);
-      LY = h->Gp0;
-      if (use2) {
-        split3_pack(st, n, ld, h->KX, nullptr, false, h->Gp1, 2, h->amax + 4);
-        CHK(gs_fork());
-        CHK(timer_begin(h, sg_, big));
-        MCGRA_HIP(split3_symm(sg_, n, h->Gp1, h->Gp2, h->G_A1, ld, 0, -1, h->small_slab ? h->small_slab : h->G_A, h->small_slab ? h->small_slab_bytes : slab, 2, h->amax + 4, 0, -1, 1 | sflag, 0, nullptr, 0, nullptr, h->amax + 2));
-        CHK(timer_end(h, sg_, big, 2.0 * (double)n * n * n));
-        if (sg_ != st) MCGRA_HIP(hipEventRecord(h->ev_second, sg_));
-        gs_p4 = true;
-      }
-    }
-    // G_adjn += LY Xc behind the victim chain's rank-k update of G_adjn; slabs in KX (dead: combined and packed)
-    CHK(victim_rankk()); gs_rankk_done = true;
-    CHK(gs_fork());
-    CHK(timer_begin(h, sg_, big));
-    MCGRA_HIP(split3_symm(sg_, n, LY, h->Bpack, h->G_ADJN, ld, 0, -1, h->small_slab ? h->small_slab : h->KX, h->small_slab ? h->small_slab_bytes : slab, 2, h->amax + 3, 0, -1, 1 | sflag, 0, nullptr, 0, nullptr, h->amax + 1));
-    CHK(timer_end(h, sg_, big, 2.0 * (double)n * n * n));
-    if (sg_ != st) MCGRA_HIP(hipEventRecord(h->ev_join, sg_));
-    gs_p3 = true;
-    MCGRA_KERNEL_CHECK();
-  } else
-  if (PH(2) && hsic && (use1 || use2) && !h->lr_step) {
-    const float s1 = (float)(sg * k1), s2 = (float)(sg * k2);
-    if (cka) {
-      launch_cka_sums(st, n, ld, h->KX, h->KY, h->KFC, use1, use2, h->rowvals + 4 * (size_t)ld, sym);
-      launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 4, h->scal + S_CK0);
-      launch_cka_coef(st, h->scal + S_CK0, h->cst + 0, use1 ? (float)k1 : 0.f, use2 ? (float)k2 : 0.f, h->coef);
-      launch_cka_lincomb(st, n, ld, h->KX, h->KY, h->KFC, h->coef, use1, use2, sym);
-    } else {
-      launch_hsic_combine(st, n, ld, h->KX, h->KY, h->KFC, use1 ? s1 : 0.f, use2 ? s2 : 0.f,
-                          h->rowvals + 4 * (size_t)ld, sym);
-      launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 2, h->scal + S_H1);
-    }
-    // G_adjn += 2 (s1 Kfc + s2 Kyc) @ Xc ;  G_A1 += 2 s2 Kxc @ Yc   (K 1 = 0, so Xc may replace X)
-    if (use2) CHK(eg_symm(h, st, sym, n, n, h->KY, ld, h->XC, ld, 1.f, h->G_ADJN, ld, h->KX, h->YC, h->G_A1, t0, t1 - t0));
-    else CHK(eg_symm(h, st, sym, n, n, h->KY, ld, h->XC, ld, 1.f, h->G_ADJN, ld, nullptr, nullptr, nullptr, t0, t1 - t0));
-    MCGRA_KERNEL_CHECK();
-  }
-
-  if (PH(3)) {
-  if (hsic && h->lr_step && use2) {
-    CHK(eg(h, st, false, false, n, 2 * he, n, 1.f, h->XC, ld, h->lrT, h->lr_ldv, 0.f, h->lrQ, 2 * he));         // [Q | Q2] = Xc [W | W2]
-    if (!lr_decode_supported(he))     // widths without a fused decode backward: d c2 / d A1 += 2 s2 Q Z^T, materialised
-      CHK(eg(h, st, false, true, n, n, he, 2.f * (float)(sg * k2), h->lrQ, 2 * he, h->Zn, h->hmax, 1.f, h->G_A1, ld));
-    MCGRA_KERNEL_CHECK();
-  }
-  if (!gs_early_bwd) CHK(early_bwd());           // (a Gram-evaluation step ran them beside its Grams, phase 1)
-  if (!gs_rankk_done) CHK(victim_rankk());       // (... and this one in front of G_adjn += LY Xc, phase 2)
-  // the decode backward reads G_A1: behind G_A1 += LX Yc on the side stream
-  if (gs_p4 && sg_ != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_second, 0));
-
-  // ---- backward: decode (S = Zn Zn^T, A1 = offdiag relu(S))
-  if (hsic && h->lr_step && use2 && lr_decode_supported(he)) {
-    // ((G + G^T) o [S > 0]) Zn for G = ie'(A1) + 2 s2 Q Z^T, without materialising G (c7 value from the same pass)
-    const int np = launch_lr_decode_bwd(st, n, ld, he, h->A1, h->Zn, h->hmax, h->lrQ, (float)(k7 / n2), h->ws,
-                                        h->rowvals + 6 * (size_t)ld, h->GZn, h->hmax, h->lrQtZ);
-    if (np > 0) launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, np, 1, h->scal + S_V7);
-  } else {
-    launch_sym_mask(st, n, ld, h->G_A1, h->A1, h->has_ori ? h->ORI : nullptr, h->G_A);    // G_A used as scratch for (G + G^T) * [S > 0]
-    CHK(eg(h, st, false, false, n, he, n, 1.f, h->G_A, ld, h->Zn, h->hmax, 0.f, h->GZn, h->hmax));
-  }
-  if (hsic && h->lr_step && use2) {   // the -2 s2 KX D part of d c2 / d A1, applied to Zn directly
-    const bool fused = lr_decode_supported(he);
-    launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrDelta, h->lrRs, -2.f * (float)(sg * k2), h->GZn, h->hmax,
-                    h->rowvals + 7 * (size_t)ld, h->rowvals + 5 * (size_t)ld, fused ? h->lrStats + 2 * he : nullptr,
-                    fused ? h->lrQtZ : nullptr, 2.f * (float)(sg * k2));
-    launch_reduce_rows(st, h->rowvals + 5 * (size_t)ld, n, 1, h->scal + S_H2);
-  }
-  if (small_forked) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join3, 0));      // c9 / c10: Gem, GZ2 and their scalars
-  launch_row_normalize_bwd(st, n, he, h->GZn, h->Zn, h->hmax, h->nrm, h->Gem, h->hmax);
-
-  // ---- backward: modified_adj chain (embedding + output2) -> G_A
-  int ltop;
-  if (h->has_ori) {
-    // two chains: output2 on modified_adj (only c10 reaches it) and the embedding on modified_adj - ori (em)
-    MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
-    MCGRA_HIP(hipMemsetAsync(h->GPe, 0, sizeof(float) * (size_t)n * hs, st));
-    if (w10 != 0) {
-      if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
-      launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                         h->Pu + h->off[L - 1], hs, h->act, nullptr, 0, h->GPu + h->off[L - 1], hs);
-      CHK(chain_backward(h, st, A, ld, L - 1, h->Pu, h->GPu, -1, nullptr, 0));
-    }
-    launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pe + h->off[Le - 1], hs, h->act, h->Gem, h->hmax, h->GPe + h->off[Le - 1], hs);
-    CHK(chain_backward(h, st, h->Bbuf, ld, Le - 1, h->Pe, h->GPe, -1, nullptr, 0));
-    ltop = L - 1;
-  } else {
-  if (w10 != 0) {
-    ltop = L - 1;
-    if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
-    launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pu + h->off[L - 1], hs, h->act, (L - 1 == Le - 1) ? h->Gem : nullptr, h->hmax,
-                       h->GPu + h->off[L - 1], hs);
-  } else {
-    ltop = Le - 1;
-    if (L > Le) MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
-    launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pu + h->off[Le - 1], hs, h->act, h->Gem, h->hmax, h->GPu + h->off[Le - 1], hs);
-  }
-  CHK(chain_backward(h, st, A, ld, ltop, h->Pu, h->GPu, Le - 1, h->Gem, h->hmax));
-  }
-  // the normalisation backward reads G_adjn: behind G_adjn += LY Xc on the side stream
-  if (gs_p3 && sg_ != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-  bool normbwd_parts = false;
-  float* nb_colpart = h->colpart;       // column partials of the normalisation backward: [nb_strips][n]
-  int nb_strips = h->nstrips;
-  if (hsic && h->lr_step && (use1 || use2)) {
-    // Last contribution to G_adjn, and the only consumer of P1: everything above ran beside the forked product.
-    // G_adjn += 2 s1 P1 + 2 s2 (D^2 Xc + 1 c^T);  v1 = sum P1 o Xc
-    if (h->p1_inflight) {
-      if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-      h->p1_inflight = false;
-    }
-    // ... fused with the two N x N reductions of the normalisation backward that follows (one pass instead of three);
-    // its partial sums live in KY, idle on a low-rank step (the product that used it as split-K slab has been joined)
-    if (lr_elem_normbwd_scratch_floats(n) <= (size_t)n * ld) {
-      double* v1part = nullptr;
-      int v1count = 0;
-      launch_lr_elem_normbwd(st, n, ld, h->XC, use1 ? h->KX : nullptr, use2 ? h->lrDelta : nullptr, use2 ? h->lrC : nullptr,
-                             2.f * (float)(sg * k1), 2.f * (float)(sg * k2), h->G_ADJN, A, h->r, h->KY, h->rowpart, &nb_colpart,
-                             &nb_strips, &v1part, &v1count);
-      launch_reduce_rows(st, v1part, v1count, 1, h->scal + S_H1);
-      normbwd_parts = true;
-    } else {
-      launch_lr_elem(st, n, ld, h->XC, use1 ? h->KX : nullptr, use2 ? h->lrDelta : nullptr, use2 ? h->lrC : nullptr,
-                     2.f * (float)(sg * k1), 2.f * (float)(sg * k2), h->G_ADJN, h->rowvals + 4 * (size_t)ld);
-      launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 1, h->scal + S_H1);
-    }
-  }
-  // Adam's scalars first: the fused tail below consumes them
-  h->t += 1;
-  const double b1 = 0.9, b2 = 0.999;
-  const double bc1 = 1.0 - pow(b1, (double)h->t), bc2 = 1.0 - pow(b2, (double)h->t);
-  hipLaunchKernelGGL(k_cn, dim3(1), dim3(1), 0, st, h->scal, (float)(c.weight_sup * 0.001), h->mm + 2);
-  // clamp(a,0,1).sum() <= n(n-1)/2, so a larger budget can never trigger the bisection (:339)
-  const bool may_project = c.num_edges < 0.5 * n2;
-  bool adam_done = false;
-  // normalisation backward writes G_A (beta = 0), then the chain's outer products accumulate
-  if (h->fuse_tail && rankk_apply_adam_supported(n, ld, hs) && !h->has_ori) {
-    // one pass over the lower tile pairs: apply step + rank-k update + gradient mirror + Adam, no G_A in between
-    launch_normbwd(st, n, ld, h->G_ADJN, A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
-    // (its row sums of the new M go to G_A, which this path leaves unused; not with a projection still to come)
-    const size_t cnt = (size_t)n * rankk_apply_adam_tiles(n);
-    const bool emit = !may_project && !gen && 3 * cnt + 4 <= (size_t)n * ld;
-    MCGRA_HIP(rankk_apply_adam(st, n, ld, hs, h->GPu, hs, h->Tu, hs, h->G_ADJN, h->r, h->gd, gate, h->M, h->am, h->av, h->mm + 2,
-                               (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
-                               h->keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
-                               emit ? reinterpret_cast<double*>(h->G_A + ((cnt + 1) & ~(size_t)1)) : nullptr));
-    h->prep_valid = emit;
-    adam_done = true;
-  } else if (rankk_nt_supported(n, n, hs, 0) && !h->has_ori) {
-    // one pass: G_A = GPu Tu^T + (G_adjn_ij r_i r_j + gd_i), the apply step of the normalisation backward as the
-    // epilogue of the rank-k update
-    launch_normbwd(st, n, ld, h->G_ADJN, A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
-    MCGRA_HIP(rankk_nt(st, n, n, hs, 1.f, h->GPu, hs, h->Tu, hs, 0, 0.f, nullptr, 0, nullptr, 0, 0.f, h->G_A, ld, h->G_ADJN, ld,
-                       h->r, h->gd));
-  } else {
-    launch_normbwd(st, n, ld, h->G_ADJN, A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, h->G_A, normbwd_parts);
-    CHK(eg(h, st, false, true, n, n, hs, 1.f, h->GPu, hs, h->Tu, hs, 1.f, h->G_A, ld));
-    if (h->has_ori) CHK(eg(h, st, false, true, n, n, hs, 1.f, h->GPe, hs, h->Te, hs, 1.f, h->G_A, ld));   // d / d (modified_adj - ori)
-  }
-
-  // ---- packed-gradient mirror + Adam + projection + clamp (:274-283)
-  if (!adam_done) h->prep_valid = false;
-  if (!adam_done)
-    launch_adam_sym(st, n, ld, h->G_A, gate, h->M, h->am, h->av, h->mm + 2, (float)(1.0 - b1), (float)b2,
-                    (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f, h->keep_gsym ? h->GSYM : nullptr,
-                    may_project ? 0 : 1);
-  MCGRA_KERNEL_CHECK();
-  h->have_step = true;
-  if (may_project) { CHK(project(h, st)); h->prep_valid = false; }
-
-  if (scalars_out) CHK(collect_scalars(h, st, scalars_out));
-  }  // phase 3
-  return 0;
-#undef PH
+  CHK(step_backward(s));
+  return step_tail(s, scalars_out);
 }
 
 int mcgra_attack_step(mcgra_attack_t* h, void* stream, const float* noise, double* scalars_out) {
-  return step_impl(h, stream, noise, scalars_out, 0xF);
-}
-int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* scalars_out) {
-  return step_impl(h, stream, noise, scalars_out, 0xF);
+  return step_general(h, stream, noise, scalars_out);
 }
 
 long long mcgra_attack_masked_fused_steps(mcgra_attack_t* h) { return h ? (long long)h->masked_fused_steps : 0; }

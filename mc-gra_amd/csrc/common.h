@@ -96,10 +96,18 @@ int split3_pack_rsq_parts(int n, int planes);
 int split3_chunks(int n, int planes);   // 16-k chunks per panel of a packed operand
 void split3_pack_from_m(hipStream_t st, int n, int ld, const float* M, const float* rvec, const float* mean, void* out, int planes,
                         const float* amax, int panel_off, int panel_rows, float* rsq_part, float* rsum_part = nullptr);
+// launch flags of split3_symm
+constexpr int SPLIT_BETA = 1;      // C += product (instead of C = product)
+constexpr int SPLIT_TRI = 2;       // A == B (Gram product): only tiles on or below the diagonal are computed; tiles below it
+                                   // are stored twice, as computed and mirrored, so that C is the full, bitwise symmetric matrix
+constexpr int SPLIT_SINGLE = 8;    // 2-plane fp16 operands, ONE plane product x0 y0 (split2_m16_kernel<true>): the low planes are neither staged nor
+                                   // read nor multiplied -- fp16 accuracy (2^-11 per operand), a third of the matrix-core work.  MCGRA_SPLIT_BF16=1 only.
+constexpr int SPLIT_WRAP = 4;      // the launch covers ALL row panels starting at panel_off and wrapping around: a row-block rank
+                                   // computes the row panels of its peers first and its own last (split3_symm: first_tiles)
 hipError_t split3_symm(hipStream_t st, int n, const void* Apack, const void* Bpack, float* C, int ldc, int panel_off,
                        int panel_rows, float* slab, size_t slab_bytes, int planes = 3, const float* amax = nullptr,
-                       int npanel_off = 0, int npanel_cols = -1, int flags = 0,      // flags: 1 = C += product; 2 = Gram product (A == B): lower tiles computed, mirrored into the upper half;
-                       int first_tiles = 0, hipEvent_t ev_first = nullptr,             // 4 = all row panels from panel_off, wrapping; 8 = (planes == 2) the single-plane product x0 y0, low planes compiled out; first_tiles: cut of the linear tile range, ev_first recorded behind the first part
+                       int npanel_off = 0, int npanel_cols = -1, int flags = 0,      // flags: SPLIT_* above
+                       int first_tiles = 0, hipEvent_t ev_first = nullptr,             // first_tiles: cut of the linear tile range, ev_first recorded behind the first part
                        int second_tiles = 0, hipEvent_t ev_second = nullptr,           // a second cut behind the first
                        const float* amax_b = nullptr);      // planes == 2: B's packed-with magnitude when it does not sit at amax[1] (no 4-byte copies to pair the two up)
 int split3_panel();

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void k_pack(int n, int ld, const float* __rest
   }
 }
 
-// Gram evaluation of linear_HSIC (attack.hip, phases 1 - 2): the elementwise combine of the centred Grams and the packs of its
+// Gram evaluation of linear_HSIC (attack.hip: gram_eval): the elementwise combine of the centred Grams and the packs of its
 // two results in ONE pass.  With KX = Xc Xc^T, KY = Yc Yc^T and the constant KFC the gradient products need
 //   LY = 2 (s1 KFC + s2 KY)   (G_adjn += LY Xc)      and      LX = 2 s2 KX   (G_A1 += LX Yc)
 // as A operands of the split kernel: both are written straight into the packed fp16 planes (outY, outX) -- the fp32 forms are
@@ -377,14 +377,6 @@ __device__ __forceinline__ f32x16 plane_mma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-// launch flags of the split kernels
-constexpr int SPLIT_BETA = 1;      // C += product (instead of C = product)
-constexpr int SPLIT_TRI = 2;       // A == B (Gram product): only tiles on or below the diagonal are computed; tiles below it
-                                   // are stored twice, as computed and mirrored, so that C is the full, bitwise symmetric matrix
-constexpr int SPLIT_SINGLE = 8;    // 2-plane fp16 operands, ONE plane product x0 y0 (split2_m16_kernel<true>): the low planes are neither staged nor
-                                   // read nor multiplied -- fp16 accuracy (2^-11 per operand), a third of the matrix-core work.  MCGRA_SPLIT_BF16=1 only.
-constexpr int SPLIT_WRAP = 4;      // the launch covers ALL row panels starting at panel_off and wrapping around: a row-block rank
-                                   // computes the row panels of its peers first and its own last (split3_symm: first_tiles)
 // linear tile index -> (tile_m, tile_n): 4-panel groups over the tile grid (gemm_f32.hip), or the lower triangle row by row
 __device__ __forceinline__ void split_tile_of(int lin, int tiles_m, int tiles_n, int panel_off, int npanel_off, int flags,
                                               int& tile_m, int& tile_n) {
