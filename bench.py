@@ -7,18 +7,23 @@ H_A / Y_A / Y priors, backward into the adjacency, Adam + projection, and the
 per-step monitoring forward (:290-296).  Inputs are resident in HBM before the
 timed region.  Prints ONE JSON line (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synthetic-10k-hsic|cora-shape-hsic|...] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synthetic-10k-hsic|cora-shape-hsic|...] [--dump-outputs DIR] [--full]
 
 N > 1 runs ONE attack, row-block sharded over N ranks, one per GPU (every N x N pass split by
 rows, collectives over RCCL inside the timed region); `value` is the steps of that attack per second ("scaling":
 "strong").  Under torch.distributed.run (RANK / WORLD_SIZE set) this process is one of the ranks and --gpus must equal
 WORLD_SIZE; a plain `python bench.py --gpus N` starts the N ranks itself (launch_ranks) and prints rank 0's line.
-Independent replicas, one per GPU, are the side figure `replica_probe`.
 
-At N = 1 two things happen BEFORE this process touches the GPU (child processes): the CPU baseline (whole oracle steps of the
-same workload on the host cores, `cpu_baseline`) and two runs of this script under `rocprofv3 --pmc FETCH_SIZE` /
-`--pmc WRITE_SIZE` that measure the build's memory-side traffic on this box (`live_traffic` -> `roofline.traffic`,
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line (`roofline` from the timed steps' own HIP events, no run of its own).  Everything else runs behind the timed
+steps only with --full: the recovered-adjacency `auc`, the other evaluations of the product (`split_bf16_probe` /
+`fp32_mfma_probe`, `gram_path_probe`, `roofline.alone`, `step_outside_product`), `other_workloads`, and at N > 1 the
+`multi_rank` diagnostics and independent replicas, one per GPU (`replica_probe`).  Also with --full, at N = 1 two things
+happen BEFORE this process touches the GPU (child processes): the CPU baseline (whole oracle steps of the same workload on
+the host cores, `cpu_baseline`) and two runs of this script under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` that
+measure the build's memory-side traffic on this box (`live_traffic` -> `roofline.traffic`,
 `step_outside_product.bytes_per_step`; without rocprofv3 the committed passes of profiles/ stand in, and the line says which).
+The --no-* switches below drop single parts of a --full run.
 Defaults: 200 timed steps behind 20 untimed ones (the clock settles over the first ~30 steps of a run).
 
 Workloads carry their own start and learning rate (WORKLOADS below): adj_changes starts at start_kappa / N x U[0, 1)
@@ -287,7 +292,7 @@ def live_traffic(workload, seed, steps=6, timeout_s=120.0):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, ctr)
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", d, "--", py, os.path.abspath(__file__),
-                   "--steps", str(steps), "--warmup", "1", "--workload", workload, "--seed", str(seed), "--no-cpu-baseline",
+                   "--steps", str(steps), "--warmup", "1", "--workload", workload, "--seed", str(seed), "--full", "--no-cpu-baseline",
                    "--no-split-probe", "--no-live-traffic"]
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL,
@@ -643,18 +648,21 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="synthetic-10k-hsic", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (CPU baseline, live traffic, AUC, product "
+                         "probes, other workloads; N > 1: multi-rank diagnostics, replica probe); the --no-* switches drop parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-monitor", action="store_true", help="skip the per-step monitoring forward (:290-296)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-shard-probe", action="store_true",
-                    help="N > 1: skip the extra (untimed-for-value) run of independent replicas, one attack per rank")
+                    help="N > 1, --full: skip the extra (untimed-for-value) run of independent replicas, one attack per rank")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the two rocprofv3 --pmc child passes that measure the memory-side traffic of this build on this box "
+                    help="--full: do not run the two rocprofv3 --pmc child passes that measure the memory-side traffic of this build on this box "
                          "(N = 1; implied by --no-split-probe)")
     ap.add_argument("--live-traffic", action="store_true",
-                    help="run the two --pmc child passes even with --no-split-probe (the fused MSELoss / KL workloads: roofline.traffic per step)")
+                    help="--full: run the two --pmc child passes even with --no-split-probe (the fused MSELoss / KL workloads: roofline.traffic per step)")
     ap.add_argument("--no-split-probe", action="store_true",
-                    help="skip the extra runs at N = 1 (other evaluation of the N x N x N product, Cora-shape workload)")
+                    help="--full: skip the extra runs at N = 1 (other evaluation of the N x N x N product, Cora-shape workload)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB: "
                          "dump_outputs); N = 1 only")
@@ -674,12 +682,13 @@ def main(argv=None):
     # MCGRA_BENCH_SHARED_GPU=1 (tests on a 1-GPU box): every rank on cuda:0, the collectives over gloo with host-staged
     # arena slices (RCCL refuses two ranks on one device); same engine, protocol and timing contract, never a reported number
     shared_gpu = world > 1 and "1" in (os.environ.get("MCGRA_BENCH_SHARED_GPU"), os.environ.get("MCGRA_SHARED_GPU"))
-    # CPU baseline first (N = 1 only): its child process is forked before anything here touches the GPU, and it is over
+    # CPU baseline first (--full, N = 1 only): its child process is forked before anything here touches the GPU, and it is over
     # before the timed region starts, so the host cores are idle while the GPU is timed
-    cpu = cpu_baseline(a.workload, a.seed) if (world == 1 and not a.no_cpu_baseline) else None
+    cpu = cpu_baseline(a.workload, a.seed) if (a.full and world == 1 and not a.no_cpu_baseline) else None
     # ... and so are the two PMC passes that measure this build's memory-side traffic on this box (children under rocprofv3)
     live, live_error = None, None
-    if world == 1 and not a.no_live_traffic and (not a.no_split_probe or a.live_traffic) and WORKLOADS[a.workload][5] in ("HSIC", "MSELoss", "KL"):
+    if a.full and world == 1 and not a.no_live_traffic and (not a.no_split_probe or a.live_traffic) \
+            and WORKLOADS[a.workload][5] in ("HSIC", "MSELoss", "KL"):
         try:
             live = live_traffic(a.workload, a.seed)
         except Exception as e:
@@ -753,9 +762,11 @@ def main(argv=None):
     stepper_exchanges = ((stepper.exchanges - ex0) / a.steps) if stepper is not None else None      # of the timed steps
     dumped = dump_outputs(a.dump_outputs, eng, last_logp[0], torch) if a.dump_outputs else None      # untimed
 
+    # from here to the result line: --full only (untimed figures and checks that need runs of their own)
+
     # the same N x N x N product alone on the chip (no side-stream company), for the roofline's "alone" figure
     alone_ms = None
-    if world == 1 and st["launches"] and eng_path["lowrank_steps"] > 0 and measure == "HSIC" and eng.product_mode() == 0:
+    if a.full and world == 1 and st["launches"] and eng_path["lowrank_steps"] > 0 and measure == "HSIC" and eng.product_mode() == 0:
         from mc_gra_amd import engine as E
         KFC, Bop = eng.buffer("KFC"), eng.buffer("adj_norm")
         out_s = torch.empty_like(Bop)
@@ -771,23 +782,25 @@ def main(argv=None):
         del out_s
 
     # recovered-adjacency AUC of the run (post-loop ensemble, topology_attack.py:300-324), untimed
-    lab = torch.as_tensor(inp["labels"], device=dev)
-    label_adj = (lab[:, None] == lab[None, :]).float()
-    H_A = eng.buffer("HA"); Y_A = eng.buffer("YA")
-    final = eng.finalize(0, H_A, Y_A, label_adj)
-    auc = gpu_auc(adj_dev, final, torch)
+    auc = None
+    if a.full:
+        lab = torch.as_tensor(inp["labels"], device=dev)
+        label_adj = (lab[:, None] == lab[None, :]).float()
+        final = eng.finalize(0, eng.buffer("HA"), eng.buffer("YA"), label_adj)
+        auc = gpu_auc(adj_dev, final, torch)
+        del final, label_adj
 
     # N > 1: what makes the first multi-GPU line explain itself -- the collectives' time by kind, every rank's product time, the
     # same steps with nothing exchanged (compute only), and the sharded attack's result against the 1-rank attack's
     multi = None
-    if world > 1:
+    if a.full and world > 1:
         multi = multi_rank_diagnostics(pkg, torch, dist, dev, rank, world, a, eng, stepper, plan, comm, st, auc, dt, monitor, shared_gpu)
 
     # the other evaluation of the N x N x N product beside the headline: pure fp32 MFMA when the default (bf16 split,
     # fp32-level error) ran, the split when MCGRA_SPLIT_BF16=0 was given
     pmode = eng.product_mode()
     split = None
-    if world == 1 and measure == "HSIC" and not a.no_split_probe:
+    if a.full and world == 1 and measure == "HSIC" and not a.no_split_probe:
         try:
             split = product_probe(pkg, torch, dev, a.workload, a.seed + rank, min(a.steps, 20), min(a.warmup, 3), monitor, 0 if pmode else 2)
             split["headline_auc"] = auc
@@ -798,7 +811,8 @@ def main(argv=None):
     # the split product by itself: the timed engine's own last product replayed back to back with nothing beside it
     replay_ms = None
     # (not under --no-split-probe: the rocprofv3 passes of profiles/ then hold the step's own launches only)
-    if world == 1 and measure == "HSIC" and pmode in (2, 3) and eng_path["fused_steps"] > 0 and wp[0] != 0 and not a.no_split_probe:
+    if a.full and world == 1 and measure == "HSIC" and pmode in (2, 3) and eng_path["fused_steps"] > 0 and wp[0] != 0 \
+            and not a.no_split_probe:
         try:
             eng.product_replay(3)
             replay_ms = eng.product_replay(20)
@@ -807,7 +821,7 @@ def main(argv=None):
     # ... and the step without the side stream (same engine configuration with MCGRA_OVERLAP=0): what the fork is worth
     alone = None
     side_stream = (ab_switch("MCGRA_OVERLAP") or ("1" if pmode == 3 else "0")) == "1"
-    if world == 1 and measure == "HSIC" and pmode in (2, 3) and side_stream and not a.no_split_probe:
+    if a.full and world == 1 and measure == "HSIC" and pmode in (2, 3) and side_stream and not a.no_split_probe:
         try:
             alone = product_probe(pkg, torch, dev, a.workload, a.seed + rank, min(a.steps, 40), min(a.warmup, 10), monitor, pmode, overlap=0)
         except Exception as e:
@@ -816,7 +830,7 @@ def main(argv=None):
     # the same workload when the fused low-rank step does not apply (a dead embedding row, a GAT / GraphSAGE victim, CKA, a
     # hidden width > 32): the reference's own formulation, four N x N x N products per step on the same split kernel
     gram = None
-    if world == 1 and measure == "HSIC" and pmode in (2, 3) and not a.no_split_probe:
+    if a.full and world == 1 and measure == "HSIC" and pmode in (2, 3) and not a.no_split_probe:
         try:
             g = product_probe(pkg, torch, dev, a.workload, a.seed, min(a.steps, 5), 1, monitor, pmode, extra_env={"MCGRA_NO_LOWRANK": "1"})
             gram = {"value": g["value"], "unit": "attack-steps/s", "ms_per_step": g["ms_per_step"], "steps": g["steps"], "auc": g["auc"],
@@ -828,7 +842,7 @@ def main(argv=None):
 
     # BASELINE.json configs[1] (Cora-sized dense GCN + HSIC, fp32) beside the 10k headline: same engine, same timing
     extra = None
-    if world == 1 and a.workload == "synthetic-10k-hsic" and not a.no_split_probe:
+    if a.full and world == 1 and a.workload == "synthetic-10k-hsic" and not a.no_split_probe:
         try:
             e2, _, _ = build_engine(pkg, torch, dev, "cora-shape-hsic", a.seed)
 
@@ -878,8 +892,8 @@ def main(argv=None):
             extra = dict(extra or {}, error=f"{type(e).__name__}: {e}"[:300])
 
     replicas = None
-    if world > 1 and not a.no_shard_probe:
-        del eng, final, H_A, Y_A, label_adj, stepper
+    if a.full and world > 1 and not a.no_shard_probe:
+        del eng, stepper
         torch.cuda.empty_cache()
         try:
             replicas = replica_probe(pkg, torch, dist, dev, rank, world, a.workload, a.seed, min(a.steps, 10), 2, monitor, red_dev)
@@ -916,8 +930,9 @@ def main(argv=None):
                                        + ("(gloo, host-staged: the ranks share ONE GPU -- a test mode, not a measurement)"
                                           if shared_gpu else "(RCCL)")
                                        if world > 1 else "single")},
-            "auc": auc,
         }
+        if auc is not None:
+            out["auc"] = auc
         if replicas is not None:
             out["replica_probe"] = replicas
         if multi is not None:

@@ -7,11 +7,11 @@ for l in sys.stdin:
     d=json.loads(l); print('echo 10k world', d['world'], round(d['per_rank_compute_ms'],3), 'product', round(d['product_ms_per_step'],3), 'fused', d['fused_steps'], d['general_steps'])
 "
 python3 scripts/shard_emulate.py --echo --workload synthetic-30k-hsic-3layer --worlds 8 --steps 4 2>&1 | grep '^{"world"' | cut -c1-200
-for wl in cora-shape-hsic synthetic-4k-hsic; do python3 bench.py --workload $wl --steps 200 --warmup 30 --no-cpu-baseline --no-split-probe 2>/dev/null | python3 -c "
+for wl in cora-shape-hsic synthetic-4k-hsic; do python3 bench.py --workload $wl --steps 200 --warmup 30 --full --no-cpu-baseline --no-split-probe 2>/dev/null | python3 -c "
 import sys, json
 d=json.loads(sys.stdin.read()); print(d['config']['workload'], d['value'], d['ms_per_step'], d['auc'])
 "; done
-python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-split-probe 2>/dev/null | python3 -c "
+python3 bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-split-probe 2>/dev/null | python3 -c "
 import sys, json
 d=json.loads(sys.stdin.read()); print(d['config']['workload'], d['value'], d['ms_per_step'], d['auc'])
 "

@@ -10,7 +10,7 @@ mkdir -p $OUT
 export MCGRA_AB=1 MCGRA_EARLY_TAIL=0
 for pass in 1 2; do
   for g in 4 1 2 8 16; do
-    MCGRA_SPLIT_GROUP_M=$g timeout 400 python bench.py --steps 40 --warmup 10 --no-cpu-baseline > $OUT/g${g}_p${pass}.json 2> $OUT/g${g}_p${pass}.err
+    MCGRA_SPLIT_GROUP_M=$g timeout 400 python bench.py --steps 40 --warmup 10 --full --no-cpu-baseline > $OUT/g${g}_p${pass}.json 2> $OUT/g${g}_p${pass}.err
     python - <<PY
 import json
 d = json.load(open("$OUT/g${g}_p${pass}.json"))

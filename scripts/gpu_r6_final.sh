@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 python -m pytest tests -m gpu -q --tb=short --maxfail=30 -p no:cacheprovider > $O/pytest.log 2>&1
 tail -4 $O/pytest.log
 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' 2>&1 | tail -1
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 j=json.loads(open('gpurun_out/r06f/bench.json').read().strip().splitlines()[-1])
@@ -24,7 +24,7 @@ python -c "
 import json; l=json.loads(open('$O/bench_20_5.json').read().strip().splitlines()[-1]); print('20/5', l['value'], l['ms_per_step'])"
 for wl in synthetic-10k-kl cora-shape-kl synthetic-10k-mse cora-shape-mse cora-shape-hsic synthetic-4k-hsic citeseer-shape-gat-hsic synthetic-10k-hsic-masked; do
   LT=""; case $wl in *-kl|*-mse) LT="--live-traffic";; esac      # (the fused MSELoss / KL steps: roofline.traffic per step from two --pmc child passes)
-  python bench.py --workload $wl --no-cpu-baseline --no-split-probe $LT --steps 100 --warmup 20 > $O/o_bench_$wl.json 2>/dev/null
+  python bench.py --workload $wl --full --no-cpu-baseline --no-split-probe $LT --steps 100 --warmup 20 > $O/o_bench_$wl.json 2>/dev/null
   python -c "
 import json; l=json.loads(open('$O/o_bench_$wl.json').read().strip().splitlines()[-1]); print('$wl', round(l['value'],1), round(l['ms_per_step'],4), l['config'].get('fused_steps'), l['config'].get('general_steps'), (l.get('roofline') or {}).get('frac'))"
 done

@@ -185,6 +185,34 @@ def test_dump_outputs_writes_the_last_step_within_64_mb(monkeypatch, tmp_path):
         bench.main(["--gpus", "2", "--dump-outputs", str(tmp_path / "x")])
 
 
+def test_only_a_full_bench_runs_children_before_the_gpu(monkeypatch):
+    """A plain bench run goes straight to the GPU; --full first runs the CPU baseline and the live-traffic passes (both child
+    processes started before this process touches the GPU), and its --no-* switches still drop them one by one."""
+    import torch
+    import bench
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    calls = []
+
+    class GpuReached(Exception):
+        pass
+
+    def at_gpu(*args, **kw):
+        raise GpuReached()
+
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *args, **kw: calls.append("cpu_baseline"))
+    monkeypatch.setattr(bench, "live_traffic", lambda *args, **kw: calls.append("live_traffic"))
+    monkeypatch.setattr(torch.cuda, "set_device", at_gpu)
+    for argv, want in ((["--gpus", "1", "--steps", "3", "--warmup", "1"], []),
+                       (["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"], ["cpu_baseline", "live_traffic"]),
+                       (["--full", "--no-cpu-baseline"], ["live_traffic"]),
+                       (["--full", "--no-split-probe"], ["cpu_baseline"])):
+        calls.clear()
+        with pytest.raises(GpuReached):
+            bench.main(argv)
+        assert calls == want, (argv, calls)
+
+
 def test_live_traffic_accounting(monkeypatch):
     """bench.live_traffic: the two `rocprofv3 --pmc` child passes (FETCH_SIZE, WRITE_SIZE; --kernel-trace only beside them) and
     the accounting of their CSVs -- 2 x FETCH_SIZE + WRITE_SIZE per kernel, the product's main grid per launch, everything

@@ -160,7 +160,7 @@ def test_bench_world2_branch_on_a_shared_gpu(tmp_path):
     by two processes for 2 timed steps; MCGRA_BENCH_SHARED_GPU=1 selects gloo + host staging on cuda:0.  The recovered-
     adjacency AUC of the 2-rank attack equals the 1-rank attack's on the same workload, start and step count."""
     out = str(tmp_path / "bench2")
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--no-shard-probe"]
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--full", "--no-shard-probe"]
     _run_ranks(W.run_bench_rank, 2, (argv,), out, timeout=900)
     line = json.load(open(out + ".json"))
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["scaling"] == "strong"
@@ -189,7 +189,7 @@ def test_bench_world2_branch_with_the_fused_mseloss_step(tmp_path, workload, nco
     row-block MSELoss / KL steps exchange no N x N data -- six / seven all-gathers per step + monitor, no all-to-all, no product --
     and the 2-rank attack's AUC is the 1-rank attack's (rank 0's replay behind the timed region says so too)."""
     out = str(tmp_path / "bench2mse")
-    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--no-shard-probe"]
+    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--full", "--no-shard-probe"]
     _run_ranks(W.run_bench_rank, 2, (argv,), out, timeout=900)
     line = json.load(open(out + ".json"))
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["scaling"] == "strong"
@@ -205,11 +205,11 @@ def test_bench_world2_branch_with_the_fused_mseloss_step(tmp_path, workload, nco
 
 @needs_two_gpus
 def test_bench_gpus2_over_rccl_on_two_devices(tmp_path):
-    """`python bench.py --gpus 2 --steps 5` as the driver's multi-GPU tier runs it, on a box with two devices: no MCGRA_SHARED_GPU,
+    """`python bench.py --gpus 2 --steps 5 --full` on a box with two devices: no MCGRA_SHARED_GPU,
     backend nccl (RCCL over xGMI), rank k on cuda:k.  The line explains itself (collective time by kind, the all-to-all of the
     product's tile blocks among them) and rank 0's replay of the attack on one rank agrees with the two-rank state."""
     out = str(tmp_path / "rccl2")
-    argv = ["--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", "synthetic-4k-hsic", "--no-shard-probe"]
+    argv = ["--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", "synthetic-4k-hsic", "--full", "--no-shard-probe"]
     ctx = mp.get_context("forkserver")
     p = ctx.Process(target=W.run_bench_plain, args=(argv, out, {"OMP_NUM_THREADS": "2"}))
     p.start()
@@ -236,7 +236,7 @@ def test_plain_bench_gpus2_starts_its_own_ranks(tmp_path):
     not touched the GPU), prints rank 0's line as the only stdout line, and that line says n_gpus == 2.  The caller here is a
     fork-server child (this pytest process has initialised the GPU and must not fork + exec)."""
     out = str(tmp_path / "plain2")
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--no-shard-probe"]
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--full", "--no-shard-probe"]
     ctx = mp.get_context("forkserver")
     p = ctx.Process(target=W.run_bench_plain, args=(argv, out, {"MCGRA_BENCH_SHARED_GPU": "1", "OMP_NUM_THREADS": "2"}))
     p.start()
@@ -307,13 +307,13 @@ def test_row_block_processes_at_the_headline_size(pkg, tmp_path):
 
 
 def test_plain_bench_measures_its_traffic_live(tmp_path):
-    """`python bench.py` as the driver runs it at N = 1 (here: the 4k workload, 5 steps): before it touches the GPU the process
+    """`python bench.py --full` at N = 1 (here: the 4k workload, 5 steps): before it touches the GPU the process
     runs two children of itself under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` and reports the product's memory-side
     bytes per launch and the rest of the step's per step from THEM (the line quoted committed profiles) --
     `traffic_source` says so.  The caller is a fork-server child: this pytest process has initialised the GPU."""
     import shutil
     out = str(tmp_path / "live")
-    argv = ["--steps", "5", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--no-cpu-baseline"]
+    argv = ["--steps", "5", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--full", "--no-cpu-baseline"]
     ctx = mp.get_context("forkserver")
     p = ctx.Process(target=W.run_bench_plain, args=(argv, out, {"OMP_NUM_THREADS": "2"}))
     p.start()
@@ -338,6 +338,36 @@ def test_plain_bench_measures_its_traffic_live(tmp_path):
         assert compulsory <= r["traffic"] <= 12 * compulsory, (r["traffic"], compulsory)
         so = line["step_outside_product"]
         assert so["bytes_source"].startswith("rocprofv3 --pmc") and 8 * n * n * 4 <= so["bytes_per_step"] <= 40 * n * n * 4
+
+
+def test_plain_bench_runs_only_the_headline(tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- no child process, no AUC,
+    no probe, no other workload; `roofline` comes from the timed steps' own events (no run of its own)."""
+    out = str(tmp_path / "lean")
+    dump = tmp_path / "dump"
+    argv = ["--gpus", "1", "--steps", "5", "--warmup", "1", "--workload", "synthetic-4k-hsic", "--dump-outputs", str(dump)]
+    ctx = mp.get_context("forkserver")
+    p = ctx.Process(target=W.run_bench_plain, args=(argv, out, {"OMP_NUM_THREADS": "2"}))
+    p.start()
+    p.join(900)
+    if p.is_alive():
+        p.kill()
+        pytest.fail("timeout")
+    err = out + ".rank0.err"
+    assert p.exitcode == 0, open(err).read() if os.path.exists(err) else f"exit code {p.exitcode}"
+    lines = [ln for ln in open(out + ".stdout").read().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["metric"] == "attack-steps/sec" and line["unit"] == "attack-steps/s" and line["higher_is_better"] is True
+    assert line["n_gpus"] == 1 and line["steps"] == 5 and line["config"]["fused_steps"] == 6
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3 and line["dtype"].startswith("f32")
+    for k in ("auc", "cpu_baseline", "split_bf16_probe", "fp32_mfma_probe", "gram_path_probe", "other_workloads",
+              "step_outside_product", "multi_rank", "replica_probe"):
+        assert k not in line, k
+    r = line["roofline"]
+    assert r["bound"] == "mfma" and r["avg_launch_ms"] > 0 and "alone" not in r and "live_traffic_error" not in r
+    assert sorted(line["dumped_outputs"]["arrays"]) == ["adj_changes", "victim_logp"]
+    assert np.load(dump / "adj_changes.npy").shape == (4096 * 4095 // 2,)
 
 
 # ---- the sharded step behind the class surface and main.py (north_star: "keep the PGDAttack / BaseAttack class surface and
