@@ -169,6 +169,22 @@ int mcgra_mmd_pxpy_pxy(void* stream, int m, int dx, int dy, const float* X, cons
 /* torch.nn.MSELoss()(X, Y) over `count` elements, *out device scalar. */
 int mcgra_mse(void* stream, int64_t count, const float* X, const float* Y, float* out);
 
+/* main.metric_pool (main.py:66-75): roc_curve + auc of labels[idx][:, idx] (the true adjacency) against
+ * scores[idx][:, idx] (the inference adjacency), without gathering the submatrix.  labels, scores: n x n fp32 with
+ * leading dimensions ld_labels, ld_scores >= n; idx: n_idx device int64 node ids (repeats allowed: the gathered matrix
+ * holds repeated rows and columns), or NULL for all n nodes once.  *out (host memory) = U / (P N), 2U = the sum over
+ * positives of 2 #negatives with a lower score + #negatives with an equal score; synchronises `stream`.
+ *   - ties are float32 equality (-0.0 == +0.0; subnormals and negative scores are ordinary values);
+ *   - exact: P, N and 2U are 64-bit integers, the one rounding is the final division (nearest double), and the result
+ *     is the same bits on every call;
+ *   - a selected score that is NaN or +-inf, or a selected label other than 0 or 1: MCGRA_EINVAL (sklearn raises
+ *     ValueError); an id outside [0, n): MCGRA_EINVAL;
+ *   - P == 0 or N == 0: *out = NaN (what roc_curve + auc return);
+ *   - n_idx (n when idx is NULL) up to 65 535, the largest for which 2 P N fits 64 bits; MCGRA_ENOSUP beyond.
+ * Device scratch: two 4-byte keys per selected entry plus about 3 MB. */
+int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                  const int64_t* idx, int64_t n_idx, double* out);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

@@ -188,6 +188,33 @@ def mse(X, Y):
 
 
 @_on_operand_device
+def roc_auc(real, pred, idx=None):
+    """main.metric_pool (main.py:66-75): roc_curve + auc of real[idx][:, idx] against pred[idx][:, idx], exactly, without
+    gathering the submatrix (mcgra_roc_auc).  real, pred: n x n on the device; idx: node ids (tensor, array or list,
+    repeats allowed) or None for all nodes.  NaN when one class is absent; McgraError for a NaN / inf score or a label
+    other than 0 / 1."""
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+
+    def rows(t):
+        t = t.detach()
+        if t.device != dev or t.dtype != torch.float32 or t.stride(1) != 1:
+            t = t.to(device=dev, dtype=torch.float32).contiguous()
+        return t
+
+    real, pred = rows(real), rows(pred)
+    ix = None
+    if idx is not None:
+        ix = idx.detach() if isinstance(idx, torch.Tensor) else torch.as_tensor(np.asarray(idx, dtype=np.int64))
+        ix = ix.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    out = C.c_double()
+    check(lib.mcgra_roc_auc(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
+                            ix.numel() if ix is not None else n, C.byref(out)))
+    return out.value
+
+
+@_on_operand_device
 def gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=0):
     """GCN.forward (eval) and, when emb_nlayer > 0, embedding_GCN.forward."""
     n, nfeat = X.shape

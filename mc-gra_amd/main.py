@@ -28,14 +28,14 @@ if __package__ in (None, ""):          # run as a script: load the hyphenated di
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import mcgra_loader
     mcgra_loader.load()
-    from mc_gra_amd import utils
+    from mc_gra_amd import engine, utils
     from mc_gra_amd.dataset import Dataset
     from mc_gra_amd.models.gcn import GCN, embedding_GCN
     from mc_gra_amd.models.gat import GAT, embedding_gat
     from mc_gra_amd.models.graphsage import graphsage, embedding_graphsage
     from mc_gra_amd.topology_attack import PGDAttack
 else:
-    from . import utils
+    from . import engine, utils
     from .dataset import Dataset
     from .models.gcn import GCN, embedding_GCN
     from .models.gat import GAT, embedding_gat
@@ -44,7 +44,6 @@ else:
 
 import torch
 import torch.nn.functional as F
-from sklearn.metrics import auc, roc_curve
 
 
 def build_parser():
@@ -98,11 +97,9 @@ def dot_product_decode(Z, dataset):
 
 
 def metric_pool(ori_adj, inference_adj, idx):
-    """main.metric_pool (main.py:66-75)."""
-    real = ori_adj[idx, :][:, idx].reshape(-1).cpu()
-    pred = inference_adj[idx, :][:, idx].reshape(-1).cpu()
-    fpr, tpr, _ = roc_curve(real, pred)
-    return auc(fpr, tpr)
+    """main.metric_pool (main.py:66-75): roc_curve + auc of ori_adj[idx][:, idx] against inference_adj[idx][:, idx], on the
+    device that holds inference_adj (engine.roc_auc: exact, no gathered submatrix, no host copy).  idx None: every node."""
+    return engine.roc_auc(ori_adj.to(inference_adj.device), inference_adj, idx)
 
 
 def label_adjacency(labels):
@@ -244,10 +241,10 @@ def _run(args, rank, world):
     model.attack(args, None, lr, 0, args.weight_sup, weight_param, feature_adj, 0, 0, 0, idx_train, idx_val,
                  idx_test, adj, features, init_adj, labels, idx_attack, num_edges, 0, epochs=args.epochs,
                  label_adj=label_adj)
-    inference_adj = model.modified_adj.cpu()
-    res = {"auc_attack": float(metric_pool(adj, inference_adj, idx_attack)),
-           "auc_train": float(metric_pool(adj, inference_adj, idx_train)),
-           "auc_all": float(metric_pool(adj, inference_adj, np.arange(adj.shape[0]))),
+    inference_adj = model.modified_adj                     # stays on the device: the three AUCs run there (main.py:247-250)
+    res = {"auc_attack": float(metric_pool(ad, inference_adj, idx_attack)),
+           "auc_train": float(metric_pool(ad, inference_adj, idx_train)),
+           "auc_all": float(metric_pool(ad, inference_adj, None)),
            "density": float(inference_adj.mean())}
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
