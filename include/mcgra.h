@@ -93,6 +93,10 @@ int mcgra_ssymm_split_bf16(void* stream, int n, const float* S, int lds, const f
  * matrix-core work of the 3-plane form; fp32-level error for elements within 2^18 of their operand's maximum. */
 int mcgra_ssymm_split_f16(void* stream, int n, const float* S, int lds, const float* X, int ldx, const float* rowsub,
                           float* C, int ldc);
+/* Y[n x nc] = M[n x n] V[n x nc] (nc <= 48; ldm >= n a multiple of 4, M 16-byte aligned) on the kernel the fused step's
+ * forward runs beside the N x N x N product: both operands split exactly into three bf16 planes, the six plane products
+ * with i + j <= 2 in the fp32 accumulator of the bf16 MFMA (fp32-level error, fp32 exponent range).  Synchronous. */
+int mcgra_sgemm_skinny_x3(void* stream, int n, const float* M, int ldm, const float* V, int ldv, int nc, float* Y, int ldy);
 
 /* ------------------------------------------------------- standalone ops --
  * Each mirrors one reference function on its own inputs; the attack engine

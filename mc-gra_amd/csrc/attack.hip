@@ -445,6 +445,20 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
       h->planes_mm_on = h->late_mean && h->split_planes == 2 && planes_mm_supported((int)n, 32) && want_pm;
       if (h->planes_mm_on) { A_(pm_scratch, planes_mm_scratch_bytes((int)n)); }
     }
+    {
+      // The forward of a step whose planes the early pack makes on the product's stream (attack_fused.hip) needs nothing the
+      // product reads or writes, so the product is forked behind the pack and the forward runs beside it -- on skinny_x3.hip,
+      // whose blocks fit beside a product block, not on gemm_f32, whose blocks do not.  Default from n = 8192, where the
+      // product is long enough to hide the forward; MCGRA_FWD_X3 / MCGRA_P1_BEHIND_PACK = 0 / 1 force each part (A/B).
+      const bool can = h->late_mean && h->overlap && h->early_pack_on && h->split_planes == 2;
+      const char* ex = ab_env("MCGRA_FWD_X3");
+      const char* eb = ab_env("MCGRA_P1_BEHIND_PACK");
+      int wf = 0;      // (the forward's widest product: [r o Tv_l | Tu_l])
+      for (int l = 0; l < h->L; ++l) wf = 2 * h->wdt[l] > wf ? 2 * h->wdt[l] : wf;
+      h->fwd_x3 = can && ((ex && ex[0]) ? ex[0] == '1' : n >= 8192) && skinny_x3_supported((int)n, wf, (int)ld);
+      h->p1_behind_pack_on = can && ((eb && eb[0]) ? eb[0] == '1' : h->fwd_x3);
+      if (h->fwd_x3) { A_(sx_scratch, skinny_x3_scratch_bytes((int)n)); }
+    }
     if (cfg->shard_world > 0) {
       // row-block rank: only the fused step is sharded, and the host-driven bisection of the projection is not
       if (!h->fused_ok || cfg->num_edges < 0.5 * (double)n * (double)n) {

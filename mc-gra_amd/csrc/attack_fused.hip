@@ -216,8 +216,9 @@ int64_t fused_exchange_bytes(const mcgra_attack* h) {
 }
 
 // Y rows [row0, row1) = M[rows, :] V      (V = FV [n x ncol]).  A row-block rank needs the result in FY (it is exchanged);
-// a monolithic engine leaves a split-K product as its slabs and hands its consumers a view of them (h->fy).
-static int mm_rows(mcgra_attack* h, hipStream_t st, int ncol) {
+// a monolithic engine leaves a split-K product as its slabs and hands its consumers a view of them (h->fy).  fwd: one of the
+// forward's products, which run beside the N x N x N product when it is forked behind the early pack (fwd_x3).
+static int mm_rows(mcgra_attack* h, hipStream_t st, int ncol, bool fwd = false) {
   const int rows = h->row1 - h->row0;
   h->fy = YView{h->FY, h->sharded ? h->fyw : h->fcols, 1, 0};
   if (rows <= 0) return 0;
@@ -227,6 +228,10 @@ static int mm_rows(mcgra_attack* h, hipStream_t st, int ncol) {
   if (h->planes_valid && planes_mm_supported(h->n, ncol)) {      // beside the N x N x N product: from its own operand planes
     MCGRA_HIP(planes_mm(st, h->n, h->Bpack, split3_chunks(h->n, 2), h->amax + 1, h->FV, h->fcols, ncol, h->r, h->ws, h->ws_bytes, &h->fy,
                         h->pm_scratch));
+    return 0;
+  }
+  if (fwd && h->fwd_x3 && h->late_mean) {      // (a configuration decision, not a run-time one: monitor and step adoption stay bit-identical)
+    MCGRA_HIP(skinny_x3(st, h->n, h->M, h->ld, h->FV, h->fcols, ncol, h->ws, h->ws_bytes, &h->fy, h->sx_scratch));
     return 0;
   }
   MCGRA_HIP(sgemm(st, false, false, rows, ncol, h->n, 1.f, h->M, h->ld, h->FV, h->fcols, 0.f, h->FY, h->fcols, h->ws, h->ws_bytes,
@@ -271,7 +276,9 @@ static int fused_forward_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* e
         // Early pack: the planes of the N x N x N product's operand need r only, and the pack is a pure streaming pass
         // (read M, write planes) while the forward's two skinny products keep the fp32 matrix pipe busy at 3 - 4 TB/s: the
         // pack runs on the product's stream beside them instead of behind them (0.16 ms off the path in front of the product).
-        // The product still waits for the forward (ev_fork): a forward beside the product itself was measured a wash.
+        // The product is forked behind the pack on that stream (p1_behind_pack_on) when the forward's products run on
+        // skinny_x3.hip, whose blocks fit beside a product block; beside a gemm_f32 forward it was measured a wash, and the
+        // product then waits for the forward (ev_fork).
         h->early_pack = false;
         if (h->late_mean && h->overlap && h->st2 && h->early_pack_on) {
           const int np = split3_pack_rsq_parts(n, h->split_planes);
@@ -282,11 +289,14 @@ static int fused_forward_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* e
           split3_pack_from_m(h->st2, n, ld, h->M, h->r, nullptr, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr, 0, -1,
                              h->cfg.w[1] != 0 ? h->A1 : nullptr, psum);
           // (|adj_changes|^2 and sum(modified_adj): nothing of the forward needs them -- off the caller's stream too)
-          launch_reduce_rows(h->st2, h->rowsq, n, 2, h->scal + S_SQ);
+          if (!h->p1_behind_pack_on) launch_reduce_rows(h->st2, h->rowsq, n, 2, h->scal + S_SQ);
           MCGRA_HIP(hipEventRecord(h->ev_pack, h->st2));
           h->early_pack = true;
+          // With the product behind the pack, the pack is on the path: it streams M alone and the product follows it directly;
+          // the forward (and the sums above) follow it on the caller's stream, beside the product.
+          if (h->p1_behind_pack_on) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
         }
-        if (!h->early_pack) launch_reduce_rows(st, h->rowsq, n, 2, h->scal + S_SQ);      // rowsq | rowsum are adjacent, and so are S_SQ | S_SUM
+        if (!h->early_pack || h->p1_behind_pack_on) launch_reduce_rows(st, h->rowsq, n, 2, h->scal + S_SQ);      // rowsq | rowsum are adjacent, and so are S_SQ | S_SUM
       } else {
         // own rows of r and d, and this rank's share of |adj_changes|^2 and sum(modified_adj) in the scalar lane: ONE gather
         const Stage sg = narrow_stage(h);
@@ -314,7 +324,7 @@ static int fused_forward_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* e
           // [r o Tv | Tu (| r)] -- already in FV when the previous layer's post pass wrote it (fl_layer_post_next)
           if (!(l >= 1 && fused_post && fl_layer_post_fused_supported(h->wdt[l - 1], w)))
             fl_cat_segs(st, n, with_r ? 3 : 2, Xs, lds, rs, ws, h->FV, fc);
-          CHK(mm_rows(h, st, 2 * w + (with_r ? 1 : 0)));
+          CHK(mm_rows(h, st, 2 * w + (with_r ? 1 : 0), true));
         }
         FS_XCHG(h->fw_state, 3, X_FY(h))
         {
@@ -435,7 +445,10 @@ static int tail_reduce_call(mcgra_attack* h, hipStream_t st, int phase, bool pai
 
 // The N x N x N product P1 = KFC Xc^T[:, own rows] (c1) on the side stream -- forked here: the caller's stream is recorded, the side
 // stream waits for it, ev_join marks the product's end (ev_first / ev_second the cuts).  Sets p1_inflight (and p1_first / tail_rows).
-static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals) {
+// behind_pack: the planes were packed on the side stream by this M's early pack, and nothing else on the caller's stream feeds
+// the product (Apack: the graph's; Bpack, amax[1]: the pack's; KX, KY, small_slab: last read by the previous step's tail, which
+// precedes the pack's ev_r) -- the product goes straight behind the pack, beside the forward and whatever follows it.
+static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_pack = false) {
   const int n = h->n, ld = h->ld, R0 = h->row0, R1 = h->row1;
   const int P = split3_panel(), p_off = R0 / P, p_cnt = R1 > R0 ? (R1 - R0 + P - 1) / P : 0;
   const bool ovl = h->overlap;
@@ -443,7 +456,7 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals) {
   h->p1_inflight = false;
   if (p_cnt <= 0) return 0;
   hipStream_t sp = ovl ? h->st2 : st;
-  if (ovl) {
+  if (ovl && !behind_pack) {
     MCGRA_HIP(hipEventRecord(h->ev_fork, st));
     MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
   }
@@ -572,6 +585,7 @@ static int fused_step_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* ex) 
     return 0;
   };
   int rc;
+  bool behind_pack = false;      // (the product forked behind the early pack: fork_p1)
 
   if (h->fs_state == 0) {
     if (h->fs_open) CHK(fused_resync(h, st));
@@ -599,6 +613,7 @@ static int fused_step_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* ex) 
           // reads the planes or the pack's row partials (k_mean_fin, planes_mm) waits for it here
           MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
           h->early_pack = false;
+          behind_pack = h->p1_behind_pack_on;
         } else {
           const int np = split3_pack_rsq_parts(n, h->split_planes);
           float* psum = h->A1 + (((size_t)n * np + 3) & ~(size_t)3);
@@ -626,7 +641,7 @@ static int fused_step_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* ex) 
                              h->A1, h->A1 + (((size_t)n * split3_pack_rsq_parts(n, h->split_planes) + 3) & ~(size_t)3), h->cmean, h->lrRs);
       } else {
         h->p1_inflight = false;
-        if (p_cnt > 0 && use1) CHK(fork_p1(h, st, want_vals));
+        if (p_cnt > 0 && use1) CHK(fork_p1(h, st, want_vals, behind_pack));
       }
 
       // (behind the fork: nothing in front of the product needs them)

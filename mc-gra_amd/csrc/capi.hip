@@ -186,6 +186,23 @@ int mcgra_ssymm_split_f16(void* stream, int n, const float* S, int lds_, const f
   return ssymm_split(stream, 2, n, S, lds_, X, ldx, rowsub, C, ldc);
 }
 
+int mcgra_sgemm_skinny_x3(void* stream, int n, const float* M, int ldm, const float* V, int ldv, int nc, float* Y, int ldy) {
+  if (n < 1 || !M || !V || !Y || ldv < nc || ldy < nc || !skinny_x3_supported(n, nc, ldm) || ((uintptr_t)M & 15) != 0) {
+    set_error("bad skinny_x3 argument (n >= 1, 1 <= nc <= 48, ldm >= n a multiple of 4, M 16-byte aligned)");
+    return MCGRA_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  Scratch s;
+  const size_t ws_bytes = (size_t)64 * n * 48 * sizeof(float);
+  float* ws = s.get<float>(ws_bytes / sizeof(float)); NEED(ws);
+  unsigned char* vp = s.get<unsigned char>(skinny_x3_scratch_bytes(n)); NEED(vp);
+  YView v{nullptr, 0, 1, 0};
+  MCGRA_HIP(skinny_x3(st, n, M, ldm, V, ldv, nc, ws, ws_bytes, &v, vp));
+  skinny_x3_sum(st, n, nc, v, Y, ldy);
+  MCGRA_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
 int mcgra_get_modified_adj(void* stream, int n, const float* adj_changes, const float* ori_adj, float* out) {
   if (n < 1 || !adj_changes || !out) { set_error("bad argument"); return MCGRA_EINVAL; }
   launch_unpack_sym((hipStream_t)stream, n, n, adj_changes, ori_adj, n, out);

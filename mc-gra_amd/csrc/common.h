@@ -58,6 +58,14 @@ bool planes_mm_supported(int n, int nc);
 hipError_t planes_mm(hipStream_t st, int n, const void* Ap, int nchunks, const float* amaxA, const float* W, int ldw, int nc,
                      const float* r, float* ws, size_t ws_bytes, YView* out, void* scratch);
 
+// skinny_x3.hip: Y = M V (skinny, fp32 M) on the bf16 matrix cores, three exact planes per operand, as split-K slabs described
+// by *out; one block of four waves per CU, no LDS, <= 128 VGPRs: it fits beside the N x N x N product's blocks
+size_t skinny_x3_scratch_bytes(int n);
+bool skinny_x3_supported(int n, int nc, int ldm);
+hipError_t skinny_x3(hipStream_t st, int n, const float* M, int ldm, const float* V, int ldv, int nc, float* ws, size_t ws_bytes,
+                     YView* out, void* scratch);
+void skinny_x3_sum(hipStream_t st, int n, int nc, const YView& v, float* Y, int ldy);
+
 // rankk_f32.hip: C = beta C + alpha1 A1 B1^T (+ alpha2 A2 B2^T), K1, K2 <= 64 (HBM-bound rank-k updates)
 bool rankk_nt_supported(int M, int N, int K1, int K2);
 hipError_t rankk_nt(hipStream_t st, int M, int N, int K1, float alpha1, const float* A1, int lda1, const float* B1,

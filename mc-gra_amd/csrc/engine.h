@@ -192,6 +192,11 @@ struct mcgra_attack {
   bool planes_mm_on = false, planes_valid = false;
   bool fused_post = true;          // forward: post pass + next layer's T / heads in one launch (MCGRA_NO_FUSED_POST=1: separate kernels)
   char* pm_scratch = nullptr;
+  // Monolithic fused step with the early pack: the forward's two skinny products on the bf16x3 kernel whose blocks fit beside a
+  // product block (skinny_x3.hip; MCGRA_FWD_X3=0 / 1: gemm_f32 / forced on), and the product forked behind the pack on its own
+  // stream instead of behind the forward (MCGRA_P1_BEHIND_PACK=0 / 1; A/B).  Both default on from n = 8192.
+  bool fwd_x3 = false, p1_behind_pack_on = false;
+  char* sx_scratch = nullptr;      // packed right-hand side of skinny_x3
   float* Zpair = nullptr;          // pair-interleaved copy of Zn for the decode's scalar loads (fused_lowrank.hip: k_decode_fly_s)
   int64_t fused_steps = 0;
   // row-block sharding (mcgra_attack_shard_*): this rank owns rows [row0, row1) of M / am / av

@@ -95,6 +95,18 @@ def ssymm_split_bf16(S, X, rowsub=None, out=None):
 
 
 @_on_operand_device
+def sgemm_skinny_x3(M, V, out=None):
+    """M @ V (M [n x n], V [n x nc], nc <= 48) on the three-plane bf16 kernel of the fused step's forward
+    (mcgra_sgemm_skinny_x3); M's rows must be 16-byte aligned (stride a multiple of 4)."""
+    n, nc = M.shape[0], V.shape[1]
+    assert M.shape[1] == n and V.shape[0] == n and M.stride(1) == 1 and V.stride(1) == 1
+    if out is None:
+        out = torch.empty(n, nc, device=M.device, dtype=torch.float32)
+    check(lib.mcgra_sgemm_skinny_x3(_stream(), n, _p(M), M.stride(0), _p(V), V.stride(0), nc, _p(out), out.stride(0)))
+    return out
+
+
+@_on_operand_device
 def ssymm_split_f16(S, X, rowsub=None, out=None):
     """The same product through the 2-plane fp16 split kernel (mcgra_ssymm_split_f16); S symmetric."""
     n = S.shape[0]
