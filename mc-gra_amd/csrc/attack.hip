@@ -298,6 +298,7 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
   { const char* e = ab_env("MCGRA_NO_FUSED_TAIL"); h->fuse_tail = !(e && e[0] == '1'); }
   if (h->fwd_reuse) { A_(ADJN_next, nn); }
   A_(cm_part, (size_t)64 * 256);      // column-sum partials of launch_colmean_center (small-operand terms)
+  if (cfg->measure == MCGRA_MEASURE_HSIC) { A_(Yg8, am_); }
   A_(Q, (size_t)h->hmax * h->hmax); A_(Q2, (size_t)h->hmax * h->hmax); A_(Gg2, am_); A_(coef, 16); A_(cst, 8);
   {
     const char* e = ab_env("MCGRA_NO_LOWRANK");
@@ -716,7 +717,8 @@ int small_term(mcgra_attack* h, hipStream_t st, int width, const float* Ysrc, in
     MCGRA_KERNEL_CHECK();
     return 0;
   }
-  launch_gather_rows(st, na, width, Ysrc, ldy, h->idx, h->Yg, hm);
+  const bool y8 = h->cfg.measure == MCGRA_MEASURE_HSIC && Ysrc == h->sm2;      // c10: centred from the logits in float64, below
+  if (!y8) launch_gather_rows(st, na, width, Ysrc, ldy, h->idx, h->Yg, hm);
   if (h->cfg.measure == MCGRA_MEASURE_CKA) {
     // linear_CKA(X, Y) (utils.py:1091-1096): value hxy / (sqrt(hxx) sqrt(hyy)); Q = Xc^T Yc, R = Yc^T Yc,
     // d/dY = (2/den) Xc Q - (2 hxy / (den hyy)) Yc R.  hxx is the constant in cst[cst_slot].
@@ -750,7 +752,11 @@ int small_term(mcgra_attack* h, hipStream_t st, int width, const float* Ysrc, in
   } else {  // HSIC: value |Xc^T Yc|_F^2, gradient 2 Xc (Xc^T Yc)   (utils.py:1085-1089)
     // Y is centred explicitly: Xc^T Y == Xc^T Yc only in exact arithmetic, and with identical rows of Y
     // (adj_changes == 0) the fp32 residue of Xc's column sums would otherwise be the whole "gradient"
-    launch_colmean_center(st, na, width, h->Yg, hm, h->cm_part);
+    // (c10: Y = softmax(output2) is nearly the same row on every node, so the STORED float32 softmax has lost most of what the
+    //  centring keeps -- 4.8e-5 of the term's gradient on a 3-layer victim at n = 80, against 8e-6 with the rows recomputed from
+    //  the logits in float64 and rounded after the centring: node_kernels.hip, k_softmax8_gather)
+    if (y8) launch_softmax8_centered(st, na, width, h->Z2, h->C, h->idx, h->head_act, h->Yg8, h->Yg, hm, h->cm_part);
+    else launch_colmean_center(st, na, width, h->Yg, hm, h->cm_part);
     // one Q per term (c9: Q, c10: Q2): each is only ever written on its term's width x width block, so its pad columns
     // keep the zeros of the allocation and no fill is needed per step
     float* Qb = slot == S_C10 ? h->Q2 : h->Q;

@@ -79,6 +79,7 @@ struct mcgra_attack {
   unsigned char* gate = 0;         // clamp pass-through mask of adding_noise's torch.clamp
   double* colpart_d = 0;
   double* cm_part = 0;             // scratch of launch_colmean_center
+  double* Yg8 = 0;                 // softmax(output2)[idx] in float64 (linear_HSIC's c10: launch_softmax8_centered)
   double* kde = 0;                 // measure KDE: tables + per-block partials of one term (kde_kernels.hip: kde_scratch_doubles)
   int kde_cols = mcgra::KDE_NXN_COLS;   // ... columns of the N x N operands whose kernel values can be non-zero in float32 (set_graph: from max |feature_adj|)
   double* cst = 0;                 // constants of the CKA terms: [0] hsic(Fadj,Fadj), [1] hsic(HA,HA), [2] hsic(YA,YA)

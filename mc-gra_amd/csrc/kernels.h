@@ -91,6 +91,9 @@ void launch_cka_small_coef(hipStream_t st, const double* hxx, const double* hxy,
                            double* val);
 void launch_scatter_add2_rows(hipStream_t st, int m, int h, const float* S1, const float* S2, int lds_, const int* idx,
                               const float* ab, float* dst, int ldd);
+// Yc = H softmax(Z[idx]) (elu(Z) when head_act) with the softmax and the column means in float64 (Y8: m x ld doubles of scratch)
+void launch_softmax8_centered(hipStream_t st, int m, int c, const float* Z, int ldz, const int* idx, int head_act, double* Y8,
+                              float* Yc, int ld, double* part);
 void launch_colmean_center(hipStream_t st, int m, int h, float* X, int ld, double* part = nullptr);      // part: 64 x h doubles of scratch (without: one block per column)
 void launch_sumsq(hipStream_t st, size_t count, const float* X, double* out);
 void launch_mse_small_fused(hipStream_t st, int m, int h, const float* X, int ldx, const float* Ysrc, int ldy, const int* idx, float k,

@@ -338,7 +338,8 @@ __global__ void k_scatter_add2_rows(int m, int h, const float* __restrict__ S1, 
 // then every block of the second launch adds the partials in block order and subtracts.  (Round 4: one block of 256 threads per
 // COLUMN striding through the rows -- 58 us for 10 000 x 16, on the chain of small-operand launches a short step waits for.)
 constexpr int CM_PARTS = 64;
-__global__ __launch_bounds__(256) void k_colsum_small(int m, int h, const float* __restrict__ X, int ld, double* __restrict__ part) {
+template <typename T>
+__global__ __launch_bounds__(256) void k_colsum_small(int m, int h, const T* __restrict__ X, int ld, double* __restrict__ part) {
   __shared__ double sh[256];
   const int lanes = 256 / ld, r = threadIdx.x / ld, c = threadIdx.x % ld;
   const int per = (m + CM_PARTS - 1) / CM_PARTS, i0 = blockIdx.x * per, i1 = min(m, i0 + per);
@@ -363,6 +364,51 @@ __global__ __launch_bounds__(256) void k_center_small(int m, int h, float* __res
   const int lanes = 256 / ld, r = threadIdx.x / ld, c = threadIdx.x % ld;
   const int per = (m + gridDim.x - 1) / gridDim.x, i0 = blockIdx.x * per, i1 = min(m, i0 + per);
   if (r < lanes && c < h) { const float v = mu[c]; for (int i = i0 + r; i < i1; i += lanes) X[(size_t)i * ld + c] -= v; }
+}
+
+// softmax(output2)[idx] for linear_HSIC's small-operand term c10, centred: Yc = H softmax(Z[idx]).  output2 comes from the
+// unnormalised adjacency, so its softmax is nearly the same row on every node (to 1e-2 ... 2e-3 of its magnitude) and the
+// centring removes all but that: the float32 rounding of the STORED softmax (6e-8 of the row) is 1e-5 ... 5e-5 of what is
+// left, and Xc^T Yc sums it.  So the rows are recomputed from the logits in float64 (elu first for a GAT head), the column
+// means are taken in float64 and only the centred value is rounded to float32.
+__global__ void k_softmax8_gather(int m, int c, const float* __restrict__ Z, int ldz, const int* __restrict__ idx, int head_act,
+                                  double* __restrict__ Y8, int ld8) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const float* z = Z + (size_t)idx[i] * ldz;
+  double* y = Y8 + (size_t)i * ld8;
+  double mx = -INFINITY;
+  for (int k = 0; k < c; ++k) {
+    double v = (double)z[k];
+    if (head_act && v <= 0.0) v = expm1(v);
+    y[k] = v;
+    mx = fmax(mx, v);
+  }
+  double s = 0.0;
+  for (int k = 0; k < c; ++k) { const double e = exp(y[k] - mx); y[k] = e; s += e; }
+  for (int k = 0; k < c; ++k) y[k] /= s;
+}
+__global__ __launch_bounds__(256) void k_center_small8(int m, int h, const double* __restrict__ Y8, int ld, const double* __restrict__ part,
+                                                       float* __restrict__ out) {
+  __shared__ double mu[256];
+  if (threadIdx.x < h) {
+    double t = 0;
+    for (int b = 0; b < CM_PARTS; ++b) t += part[(size_t)b * h + threadIdx.x];
+    mu[threadIdx.x] = t / m;
+  }
+  __syncthreads();
+  const int lanes = 256 / ld, r = threadIdx.x / ld, c = threadIdx.x % ld;
+  const int per = (m + gridDim.x - 1) / gridDim.x, i0 = blockIdx.x * per, i1 = min(m, i0 + per);
+  if (r < lanes && c < h) { const double v = mu[c]; for (int i = i0 + r; i < i1; i += lanes) out[(size_t)i * ld + c] = (float)(Y8[(size_t)i * ld + c] - v); }
+}
+__global__ void k_colmean_center_col8(int m, int h, const double* __restrict__ Y8, int ld, float* __restrict__ out) {
+  __shared__ double shd[16];
+  const int c = blockIdx.x;
+  double s = 0;
+  for (int i = threadIdx.x; i < m; i += blockDim.x) s += Y8[(size_t)i * ld + c];
+  s = block_sum_d(s, shd);
+  const double mu = s / m;
+  for (int i = threadIdx.x; i < m; i += blockDim.x) out[(size_t)i * ld + c] = (float)(Y8[(size_t)i * ld + c] - mu);
 }
 
 // (wider matrices: one block per column)
@@ -561,9 +607,17 @@ void launch_scatter_add2_rows(hipStream_t st, int m, int h, const float* S1, con
 }
 void launch_colmean_center(hipStream_t st, int m, int h, float* X, int ld, double* part) {
   if (ld <= 256 && part) {
-    LAUNCH(k_colsum_small, dim3(CM_PARTS), dim3(256), st, m, h, X, ld, part);
+    LAUNCH(k_colsum_small<float>, dim3(CM_PARTS), dim3(256), st, m, h, X, ld, part);
     LAUNCH(k_center_small, dim3(CM_PARTS), dim3(256), st, m, h, X, ld, part);
   } else LAUNCH(k_colmean_center_col, dim3(h), dim3(256), st, m, h, X, ld);
+}
+void launch_softmax8_centered(hipStream_t st, int m, int c, const float* Z, int ldz, const int* idx, int head_act, double* Y8,
+                              float* Yc, int ld, double* part) {
+  LAUNCH(k_softmax8_gather, g1(m), dim3(256), st, m, c, Z, ldz, idx, head_act, Y8, ld);
+  if (ld <= 256 && part) {
+    LAUNCH(k_colsum_small<double>, dim3(CM_PARTS), dim3(256), st, m, c, Y8, ld, part);
+    LAUNCH(k_center_small8, dim3(CM_PARTS), dim3(256), st, m, c, Y8, ld, part, Yc);
+  } else LAUNCH(k_colmean_center_col8, dim3(c), dim3(256), st, m, c, Y8, ld, Yc);
 }
 void launch_sumsq(hipStream_t st, size_t count, const float* X, double* out) {
   LAUNCH(k_sumsq, dim3(1), dim3(1024), st, count, X, out);

@@ -714,19 +714,32 @@ __global__ __launch_bounds__(ROW_THREADS) void k_kl_rows(int n, int ld, const fl
   ma = block_max4(ma, shf);
   if (k2 != 0.f) mb = block_max4(mb, shf);
   float sa = 0.f, sb = 0.f;
-  for (int j = threadIdx.x; j < n; j += ROW_THREADS) { sa += expf(A[base + j] - ma); if (k2 != 0.f) sb += expf(B[base + j] - mb); }
+  double sa8 = 0, sb8 = 0;
+  for (int j = threadIdx.x; j < n; j += ROW_THREADS) {
+    const float ea = expf(A[base + j] - ma);
+    sa += ea; sa8 += (double)ea;
+    if (k2 != 0.f) { const float eb = expf(B[base + j] - mb); sb += eb; sb8 += (double)eb; }
+  }
   sa = block_sum(sa, shf);
   if (k2 != 0.f) sb = block_sum(sb, shf);
   const float lsa = ma + logf(sa), lsb = (k2 != 0.f) ? mb + logf(sb) : 0.f;
+  // The VALUES take the rows' log-sum-exps in float64: a value is a difference of log-sum-exps of ~ log n that agree to three
+  // digits, and the rows of adj_norm are so alike that every row's float32 log-sum-exp rounds the same way -- a bias of 3e-5 (c1)
+  // and 2e-4 (c2) of the value at n = 700, ten times the float32 reference's (tests/test_gpu_terms.py).  The gradients keep
+  // the float32 ones (their bits are unchanged).
+  sa8 = block_sum_d(sa8, shd);
+  if (k2 != 0.f) sb8 = block_sum_d(sb8, shd);
+  const double lsa8 = (double)ma + log(sa8), lsb8 = (k2 != 0.f) ? (double)mb + log(sb8) : 0.0;
   // <g, xs> of the c2 term and the two values
   double v1 = 0, v2 = 0;
   float dot = 0.f;
   for (int j = threadIdx.x; j < n; j += ROW_THREADS) {
     const float la = A[base + j] - lsa;
-    if (k1 != 0.f) { const float f = FS[base + j]; if (f > 0.f) v1 += (double)f * (logf(f) - la); }
+    const double la8 = (double)A[base + j] - lsa8;
+    if (k1 != 0.f) { const float f = FS[base + j]; if (f > 0.f) v1 += (double)f * ((double)logf(f) - la8); }
     if (k2 != 0.f) {
       const float lb = B[base + j] - lsb, xs = expf(la);
-      if (xs > 0.f) v2 += (double)xs * (la - lb);
+      if (xs > 0.f) v2 += (double)xs * (la8 - ((double)B[base + j] - lsb8));
       dot += (la + 1.f - lb) * invn * xs;
     }
   }

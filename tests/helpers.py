@@ -1,4 +1,6 @@
 """Shared test helpers: load golden fixtures, build oracle objects from them."""
+import contextlib
+import functools
 import glob
 import os
 
@@ -43,7 +45,10 @@ def init_adj_changes(n, seed, scale):
 
 def a0_of(z):
     if "a0_seed" in z:
-        return init_adj_changes(z["adj"].shape[0], z["a0_seed"], z["a0_scale"])
+        a = init_adj_changes(z["adj"].shape[0], z["a0_seed"], z["a0_scale"])
+        if "a0_keep" in z:      # a sparse start: that fraction of the entries, the rest zero (synthetic_case)
+            a = a * (np.random.RandomState(int(z["a0_seed"]) + 1).rand(a.size) < float(z["a0_keep"])).astype(np.float32)
+        return a
     return None
 
 
@@ -182,18 +187,26 @@ def cora_feature_adj(feats):
     return (1.0 / (1.0 + np.exp(-Z.astype(np.float64)))).astype(np.float32)
 
 
-def synthetic_case(n, nfeat, widths, nclass, seed, measure="HSIC", weight_param=(0.01, 0.01, 0, 0, 0, 10, 10, 0, 10, 1000)):
+def synthetic_case(n, nfeat, widths, nclass, seed, measure="HSIC", weight_param=(0.01, 0.01, 0, 0, 0, 10, 10, 0, 10, 1000),
+                   emb_nlayer=None, gain=1.0, a0_keep=None, a0_scale=0.05, lr=0.01):
+    """A seeded random problem.  emb_nlayer: depth of the embedding (default min(2, layers), as main.py leaves it); gain scales
+    every W_l and Wlin (the biases stay): at 1.0 the priors Y_A / output2, which come from the UNNORMALISED adjacency, saturate
+    their softmax on deep or narrow victims and the c10 / c9 gradient is exactly zero (tests/test_term_cases_cpu.py).  The
+    random draws do not depend on either, so the defaults keep every earlier case's bits.  a0_keep: the seeded start keeps that
+    fraction of its entries and zeroes the rest (a0_of); a0_scale, lr: the start's scale and Adam's step (SPARSE_START)."""
     rng = np.random.RandomState(seed)
     dims = [nfeat] + list(widths)
     z = {"measure": np.array(measure), "weight_sup": np.array(1.0), "weight_param": np.array(weight_param, np.float64),
-         "lr": np.array(0.01), "num_edges": np.array(1e30), "nlayer": np.array(len(widths)),
-         "emb_nlayer": np.array(min(2, len(widths))), "a0_seed": np.array(7), "a0_scale": np.array(0.05)}
+         "lr": np.array(float(lr)), "num_edges": np.array(1e30), "nlayer": np.array(len(widths)),
+         "emb_nlayer": np.array(min(2, len(widths)) if emb_nlayer is None else int(emb_nlayer)),
+         "a0_seed": np.array(7), "a0_scale": np.array(float(a0_scale))}
+    g = np.float32(gain)
     for l in range(len(widths)):
         s = 1.0 / np.sqrt(dims[l + 1])
-        z[f"W{l}"] = rng.uniform(-s, s, (dims[l], dims[l + 1])).astype(np.float32)
+        z[f"W{l}"] = rng.uniform(-s, s, (dims[l], dims[l + 1])).astype(np.float32) * g
         z[f"b{l}"] = rng.uniform(0, s, dims[l + 1]).astype(np.float32)
     s = 1.0 / np.sqrt(widths[-1])
-    z["Wlin"] = rng.uniform(-s, s, (nclass, widths[-1])).astype(np.float32)
+    z["Wlin"] = rng.uniform(-s, s, (nclass, widths[-1])).astype(np.float32) * g
     z["blin"] = rng.uniform(-s, s, nclass).astype(np.float32)
     z["features"] = (rng.rand(n, nfeat) < 0.3).astype(np.float32)
     a = (rng.rand(n, n) < 0.08).astype(np.float32)
@@ -201,6 +214,8 @@ def synthetic_case(n, nfeat, widths, nclass, seed, measure="HSIC", weight_param=
     z["feature_adj"] = cora_feature_adj(z["features"])
     z["labels"] = rng.randint(0, nclass, n)
     z["idx_attack"] = rng.permutation(n)[: n - 5]
+    if a0_keep is not None:
+        z["a0_keep"] = np.array(float(a0_keep))
     return z
 
 
@@ -214,6 +229,273 @@ def masked_weights(z):
     w.b = [b.copy() for b in w.b]
     w.b[le] = (w.b[le] - np.quantile(probe.last["em"], 0.5, axis=0)).astype(np.float32)
     return w
+
+
+# ---------------------------------------------------------------- one loss term at a time, against the float64 oracle
+@contextlib.contextmanager
+def oracle_precision(dtype):
+    """The numpy oracle evaluates in the module global O.F32: switch it for the block only (construction and every step() of
+    a float64 oracle), so the float32 oracle tests of the same process never see it."""
+    old = O.F32
+    O.F32 = dtype
+    try:
+        yield
+    finally:
+        O.F32 = old
+
+
+class Oracle64:
+    """PGDAttackOracle evaluated in float64 on a case's own (float32) inputs, as tests/golden/make_truth64.py runs it.  Between
+    steps its state is rounded to float32: that is the state an engine (and the float32 oracle) can be handed exactly."""
+
+    def __init__(self, z, weight_sup=None, weight_param=None):
+        f8 = lambda x: np.asarray(x).astype(np.float64)
+        w0 = weights_from(z)
+        w = O.GCNWeights([f8(x) for x in w0.W], [f8(x) for x in w0.b], f8(w0.Wlin), f8(w0.blin),
+                         None if w0.Ws is None else [f8(x) for x in w0.Ws], w0.act, w0.head_act)
+        cfg = cfg_from(z)
+        if weight_sup is not None:
+            cfg.weight_sup = float(weight_sup)
+        if weight_param is not None:
+            cfg.weight_param = tuple(float(x) for x in weight_param)
+        n = z["adj"].shape[0]
+        with oracle_precision(np.float64):
+            ori = f8(z["ori_adj"]) if "ori_adj" in z else np.zeros((n, n))
+            self.orc = O.PGDAttackOracle(w, f8(z["features"]), f8(z["adj"]), ori, f8(z["feature_adj"]), z["labels"],
+                                         z["idx_attack"], cfg)
+            self.orc.w = w
+            if a0_of(z) is not None:
+                self.orc.set_adj_changes(f8(a0_of(z)))
+        assert self.orc.HA.dtype == np.float64 and self.orc.M.dtype == np.float64
+
+    def step(self, noise=None):
+        with oracle_precision(np.float64):
+            out = self.orc.step(noise=None if noise is None else np.asarray(noise, np.float64))
+            assert self.orc.last["G_sym"].dtype == np.float64
+            self.orc.M = self.orc.M.astype(np.float32).astype(np.float64)
+        return out
+
+    @property
+    def last(self):
+        return self.orc.last
+
+    @property
+    def adj_changes(self):
+        """packed state, float32 (exact: step() rounds the state)"""
+        r, c = O.tril_indices(self.orc.n)
+        return np.ascontiguousarray(self.orc.M[r, c]).astype(np.float32)
+
+
+def oracle64_from(z, weight_sup=None, weight_param=None):
+    return Oracle64(z, weight_sup, weight_param)
+
+
+ALL_TERMS = (0.01, 0.01, 0, 0, 0, 10, 10, 0, 10, 1000)       # synthetic_case's default weight_param
+_SLOT = {"c1": 0, "c2": 1, "c6": 5, "c7": 6, "c9": 8, "c10": 9}
+
+
+def _only(term):
+    return tuple(ALL_TERMS[i] if i == _SLOT[term] else 0.0 for i in range(10))
+
+
+# (weight_sup, weight_param) with one term switched on; "all" is the default set of every synthetic case
+TERM_SETS = {"nll": (1.0, (0.0,) * 10), **{t: (0.0, _only(t)) for t in _SLOT}}
+TERMS = ("nll", "c1", "c2", "c6", "c7", "c9", "c10")
+FLOOR = 3e-5                                                  # the suite's path-to-path allowance
+CAPS = {"HSIC": 3e-4, "CKA": 3e-4, "DP": 3e-4, "KDE": 3e-4, "MSELoss": 1e-4, "KL": 1e-4}      # the suite's oracle bounds
+
+
+def term_weights(term, tiny=0.0, factor=1.0):
+    """(weight_sup, weight_param) of a term set.  tiny: w1 = w2 of the sets that have no N x N HSIC term of their own (the
+    fused HSIC step exists only with one: attack.hip `fused_ok`); factor scales the term's OWN weights and not `tiny` (the
+    resolving-power guard hands the engine factor = 1 + 4 bound)."""
+    if term == "all":
+        return factor, tuple(x * factor for x in ALL_TERMS)
+    ws, wp = TERM_SETS[term]
+    wp = [x * factor for x in wp]
+    if term not in ("c1", "c2") and tiny:
+        wp[0] = wp[1] = float(tiny)
+    return ws * factor, tuple(wp)
+
+
+def term_bound(yardstick, measure):
+    """bound = min(cap, max(float32-oracle distance, floor)): every number is the suite's own or the reference's behaviour."""
+    return min(CAPS[measure], max(float(yardstick), FLOOR))
+
+
+def _values(orc):
+    return {"nll": float(orc.last["nll"]), **{k: float(orc.last["terms"].get(k, 0.0)) for k in _SLOT}}
+
+
+def _near_clamp(o):
+    """How many entries sit within 1e-6 (relative to the bound) of one of Info_entropy's clamp bounds: adj_norm (c6), and the
+    off-diagonal entries of modified_adj1 (c7).  The terms' gradients jump there, so float32 and float64 may disagree on a whole
+    entry's share -- one such pair of 490 000 costs 4e-5 of the c7 gradient at n = 700."""
+    def near(v):
+        return int(sum((np.abs(v - b) <= 1e-6 * b).sum() for b in (1e-4, 1 - 1e-4)))
+    A1 = o.last["A1"]
+    return near(o.last["adj_norm"]), near(A1[~np.eye(A1.shape[0], dtype=bool)])
+
+
+def oracle_trajectory(z, weight_sup, weight_param, steps=2):
+    """`steps` teacher-forced steps of the float64 oracle and, from the same state, of the float32 oracle.  Per step:
+    a (the packed float32 state the step starts from), G64 (mirrored gradient, float64), gmax = max|G64|, d32 = max|G32 - G64| /
+    gmax (0 when gmax is 0), v64 / v32 (nll and the terms' values), dead (embedding rows that are all zero) and masked
+    (off-diagonal pairs the decode's relu masks: S_ij <= 0), near6 / near7 (_near_clamp), all from the float64 run."""
+    o64 = Oracle64(z, weight_sup, weight_param)
+    z32 = dict(z)
+    z32["weight_sup"], z32["weight_param"] = np.array(float(weight_sup)), np.array(weight_param, np.float64)
+    o32 = oracle_from(z32)
+    out = []
+    for t in range(steps):
+        a = o64.adj_changes
+        o32.set_adj_changes(a)
+        o64.step(); o32.step()
+        G64, G32 = o64.last["G_sym"], o32.last["G_sym"]
+        gmax = float(np.abs(G64).max())
+        em, S = o64.last["em"], o64.last["S"]
+        off = ~np.eye(S.shape[0], dtype=bool)
+        near6, near7 = _near_clamp(o64)
+        out.append(dict(near6=near6, near7=near7, a=a, G64=G64, gmax=gmax, d32=float(np.abs(G32 - G64).max() / gmax) if gmax > 0 else 0.0,
+                        finite=bool(np.isfinite(G64).all() and np.isfinite(G32).all()),
+                        v64=_values(o64), v32=_values(o32), dead=int((np.abs(em).sum(1) == 0).sum()),
+                        masked=int(((S <= 0) & off).sum()) // 2))
+    return out
+
+
+@functools.lru_cache(maxsize=64)
+def _nxn_unit_gmax(spec, unit):
+    """max|G_64| of the first step with w1 = w2 = unit and nothing else on (linear in unit)."""
+    o = Oracle64(case_from(spec), 0.0, (unit, unit) + (0.0,) * 8)
+    o.step()
+    return float(np.abs(o.last["G_sym"]).max())
+
+
+def is_degenerate(spec, term):
+    """The (case, term) pairs whose reference gradient is exactly zero on purpose: c10 on a victim with ONE class (its softmax is
+    the constant 1).  They assert exact zeros / finiteness instead of a relative error."""
+    return spec[0] == "syn" and spec[4] == 1 and term == "c10"
+
+
+def term_conditions(spec, term, with_tiny, unit=1e-12):
+    """The conditions a term case must meet, from the float64 oracle's first step alone:
+      g_term  max|G_64| with ONLY the term on: non-zero and finite, exactly zero on is_degenerate pairs          (a)
+      T       w1 = w2 of the sets without an N x N term of their own when with_tiny (the fused HSIC step exists only with one:
+              attack.hip `fused_ok`): the largest of 1e-12, 1e-15, ... whose N x N contribution g_tiny is at most 1e-2 of g_term.
+              The oracle carries the same T, so only the engine's ERROR on that contribution (<= 3e-4 of it) reaches a comparison:
+              a tenth of the floor                                                                                   (b)
+      dead, masked   embedding rows that are all zero, off-diagonal pairs the decode's relu masks (S_ij <= 0)              (c)
+      near6, near7   entries of adj_norm / modified_adj1 on one of Info_entropy's clamp bounds (_near_clamp): none where c6 / c7
+              is the term                                                                                                (e)"""
+    z = case_from(spec)
+    o = Oracle64(z, *term_weights(term))
+    o.step()
+    G = o.last["G_sym"]
+    em, S = o.last["em"], o.last["S"]
+    off = ~np.eye(S.shape[0], dtype=bool)
+    c = dict(g_term=float(np.abs(G).max()), finite=bool(np.isfinite(G).all()), dead=int((np.abs(em).sum(1) == 0).sum()),
+             masked=int(((S <= 0) & off).sum()) // 2, T=0.0, g_tiny=0.0)
+    c["near6"], c["near7"] = _near_clamp(o)
+    if with_tiny and term not in ("c1", "c2", "all"):
+        g_unit = _nxn_unit_gmax(spec, unit) / unit
+        T = unit
+        while c["g_term"] > 0 and T * g_unit > 1e-2 * c["g_term"] and T > 1e-30:
+            T *= 1e-3
+        c["T"], c["g_tiny"] = T, T * g_unit
+    return c
+
+
+def assert_term_conditions(spec, term, c, fused_subject):
+    assert c["finite"], (spec, term)
+    if is_degenerate(spec, term):
+        assert c["g_term"] == 0.0, (spec, term, c)
+    else:
+        assert c["g_term"] > 0.0, ("the isolated term's reference gradient is zero: the case checks nothing", spec, term)
+        assert c["g_tiny"] <= 1e-2 * c["g_term"], (spec, term, c)
+    if spec[0] == "syn":
+        assert c["dead"] == 0, (spec, term, c)
+        if fused_subject:
+            assert c["masked"] == 0, (spec, term, c)
+    assert_clear_of_the_clamp(term, c)
+
+
+def assert_clear_of_the_clamp(term, c):
+    if term in ("c6", "c7"):
+        assert c["near" + term[1]] == 0, ("an entry sits on Info_entropy's clamp bound: the term's gradient jumps there", term, c["near" + term[1]])
+
+
+# the victim-shape matrix: (nfeat, widths, nclass, emb_nlayer) and what each row crosses
+def victim_shapes():
+    return [
+        ((11, (13, 16), 5, 2), "odd first width, padded leading dimensions"),
+        ((1, (5, 8), 2, 2), "nfeat = 1, narrowest decode"),
+        ((1, (5, 8), 1, 2), "one class: zero supervised and c10 gradients, nothing non-finite"),
+        ((7, (31, 16), 32, 2), "HSIC fc = 63 -> 64, the last fused width; C = 32, the last fused head"),
+        ((7, (32, 16), 33, 2), "HSIC fc = 65: leaves the fused step; MSELoss / KL fc = 64, FP_ROWS * w = 256; C = 33: separate head kernels"),
+        ((11, (16, 32), 3, 2), "he = 32"),
+        ((11, (24, 8), 6, 2), "he = 8"),
+        ((11, (16, 16, 16, 16), 4, 2), "summed width 64 = kmax, four backward levels"),
+        ((11, (16, 16, 16, 16, 8), 4, 2), "summed width 72: not fused; general tail in three rounds of 32 columns"),
+        ((11, (16, 24), 4, 1), "embedding = first layer"),
+        ((11, (8, 8, 16), 4, 3), "embedding = last of three layers"),
+    ]
+
+
+# the general step's rank-k tail: widths rounded up to 4 and summed give 32 / 36 / 64 / 68 / 128 / 132 columns
+GENERAL_WIDTHS = [(16, 16), (17, 16), (32, 32), (33, 32), (64, 64), (65, 64)]
+TERM_GAIN = 0.25       # synthetic_case(gain=...) of the term cases: keeps nll, c9 and c10 alive on every shape (test_term_cases_cpu.py)
+
+
+# The start of the cases of c2 and c7, the terms that go through the decode (modified_adj1 = relu(Zn Zn^T)).  From the dense start
+# of the other cases every embedding row is within 1e-4 of parallel to every other (smallest off-diagonal modified_adj1 0.99997
+# at n = 700, 0.999995 at n = 1100, whatever the seed or the weight scale): all of modified_adj1 sits above Info_entropy's clamp
+# at 1 - 1e-4, so c7 has NO gradient, and the decode backward of c2 projects out all but 1e-3 of what it is handed (the float32
+# oracle itself is 5e-4 of the term away under MSELoss).  1 % of the entries at ten times the scale spreads modified_adj1 over
+# [0.58, 0.9998], clear of the clamp's bounds (a pair that crosses one between float32 and float64 flips its whole share of a
+# gradient that is not continuous there), and Adam's step of 1e-4 keeps the second step's state clear of them too.
+SPARSE_START = dict(a0_keep=0.01, a0_scale=0.5, lr=1e-4)
+
+
+def syn_spec(n, shape, measure, gain=TERM_GAIN, start=None):
+    """Hashable description of a synthetic term case: shape = (nfeat, widths, nclass, emb_nlayer), seed = n; start "sparse":
+    SPARSE_START."""
+    nfeat, widths, nclass, emb = shape
+    assert start in (None, "sparse")
+    return ("syn", int(n), int(nfeat), tuple(widths), int(nclass), int(emb), str(measure), float(gain), start)
+
+
+def golden_spec(name, term):
+    return ("golden", name, "sparse" if term in ("c2", "c7") else None)
+
+
+def case_from(spec):
+    """Inputs of a term case: ("syn", ...) from syn_spec, or ("golden", name, start) from golden_spec: the inputs of a committed
+    attack fixture (the general-only victims: elu / GAT head, GraphSAGE self weights, three layers below n = 256)."""
+    if spec[0] == "golden":
+        z = load_case(spec[1])
+        if "a0_seed" not in z:      # a fixture that starts at the origin (adj_norm = I: the entropy terms sit on their clamp): a seeded start
+            z["a0_seed"], z["a0_scale"] = np.array(7), np.array(0.05)
+        if spec[2] == "sparse":     # (48 and 80 nodes: 30 % of the entries)
+            z["a0_keep"], z["a0_scale"], z["lr"] = np.array(0.3), np.array(SPARSE_START["a0_scale"]), np.array(SPARSE_START["lr"])
+        return z
+    _, n, nfeat, widths, nclass, emb, measure, gain, start = spec
+    return synthetic_case(n, nfeat, widths, nclass, seed=n, measure=measure, emb_nlayer=emb, gain=gain,
+                          **(SPARSE_START if start == "sparse" else {}))
+
+
+def step_case(measure, n, term):
+    """The case of the step-implementation tests: synthetic_case as the other oracle tests use it (11 features, widths (16, 16),
+    4 classes, weight scale 1); c2 and c7, the terms that go through the decode, from SPARSE_START."""
+    return syn_spec(n, (11, (16, 16), 4, 2), measure, gain=1.0, start="sparse" if term in ("c2", "c7") else None)
+
+
+@functools.lru_cache(maxsize=4)
+def term_case(spec, term, with_tiny, steps=2):
+    """(z, conditions, (weight_sup, weight_param), trajectory) of one term set on one case (term_conditions, oracle_trajectory).
+    Cached: the paths of one (case, term) share the oracle's work."""
+    c = term_conditions(spec, term, with_tiny)
+    ws, wp = term_weights(term, c["T"])
+    return case_from(spec), c, (ws, wp), oracle_trajectory(case_from(spec), ws, wp, steps)
 
 
 # ---------------------------------------------------------------- GPU-side helpers
