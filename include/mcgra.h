@@ -189,6 +189,22 @@ int mcgra_mse(void* stream, int64_t count, const float* X, const float* Y, float
 int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                   const int64_t* idx, int64_t n_idx, double* out);
 
+/* The same AUC for scores that are never stored: s_ij = dot_product_decode2(Z)_ij of the thin factor Z [n x d] (leading
+ * dimension ldz >= d), computed pair by pair over idx x idx (main.py:412-437, notrain_test: how much of the graph a prior
+ * leaks on its own).  labels, idx, n_idx, *out, exactness, NaN and error codes as mcgra_roc_auc.
+ *   - mode 0, 1, 2, 4 of the table above (main.dot_product_decode, main.py:44-55, is modes 0 and 4); 3, 5, 6: MCGRA_ENOSUP;
+ *   - d <= 128; wider: MCGRA_ENOSUP (mcgra_decode_scores + mcgra_roc_auc take any width);
+ *   - modes 1, 4: rows normalised once, z / max(|z|_2, 1e-12), into an n x d scratch;
+ *   - s_ij = <z_i, z_j> accumulated k ascending in fp32 (one fma per k), - 1 where i == j, relu, sigmoid for modes 0, 1:
+ *     s_ij and s_ji are the same bits, and the result is bit for bit mcgra_roc_auc on what mcgra_decode_scores writes;
+ *   - an entry of Z (any row) that is NaN or +-inf, or a selected score that is: MCGRA_EINVAL.
+ * Device scratch: two 4-byte keys per selected pair, the normalised copy, about 3 MB. */
+int mcgra_decode_auc(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels, int ld_labels,
+                     const int64_t* idx, int64_t n_idx, double* out);
+/* out [n x n] (leading dimension ld_out >= n) = the same s_ij, materialised; any d.  Not the bits of
+ * mcgra_dot_product_decode2, whose product runs on the MFMA GEMM.  Synchronises. */
+int mcgra_decode_scores(void* stream, int n, int d, const float* Z, int ldz, int mode, float* out, int ld_out);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

@@ -38,7 +38,7 @@ SYMBOLS = [
     "mcgra_attack_test_mutate",
     "mcgra_attack_masked_fused_steps",
     "mcgra_attack_cut_product_steps",
-    "mcgra_roc_auc",
+    "mcgra_roc_auc", "mcgra_decode_auc", "mcgra_decode_scores",
 ]
 
 
@@ -98,6 +98,8 @@ def _load():
         "mcgra_mmd_pxpy_pxy": [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_float, C.c_float, fp],
         "mcgra_mse": [vp, C.c_int64, fp, fp, fp],
         "mcgra_roc_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_double)],
+        "mcgra_decode_auc": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_double)],
+        "mcgra_decode_scores": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

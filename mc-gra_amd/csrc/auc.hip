@@ -13,6 +13,11 @@
 //                      count, one scan of the (digit, block) counts and a stable scatter
 //   k_auc_pairs        each key of the smaller class looks up its lower and upper bound in the sorted larger class;
 //                      the sum of the two is that key's share of 2U
+// mcgra_decode_auc ranks scores that are never stored, s_ij = dot_product_decode2(Z)_ij of a thin factor Z [n x d]:
+//   k_dec_rows         every row of Z: NaN / inf check, the L2-normalised copy of modes 1 and 4
+//   k_dec_classify     k_auc_classify on the scores dec_for_each decodes, a block owning 64 x 64 tiles of idx x idx
+//   k_dec_emit         k_auc_emit on the same scores; the sort and k_auc_pairs follow unchanged
+//   k_dec_scores       the same scores written out (mcgra_decode_scores: the materialised route)
 // Counts and 2U are 64-bit integers merged with global integer atomics, so the result does not depend on the order in
 // which blocks run; the one rounding is the final division (host, exact integer long division, nearest even).
 #include <hip/hip_runtime.h>
@@ -33,7 +38,13 @@ constexpr int AUC_SORT_TILE = 1024;        // keys staged per step of a sort blo
 constexpr int AUC_SORT_BLOCKS = 1024;      // at most this many tiles of keys per sort pass
 constexpr int64_t AUC_MAX_NIDX = 65535;    // 2 P N <= 2 (n_idx^2 / 2)^2 < 2^63
 
-enum { AUC_BAD_SCORE = 1, AUC_BAD_LABEL = 2, AUC_BAD_INDEX = 4, AUC_REPEAT = 8 };
+enum { AUC_BAD_SCORE = 1, AUC_BAD_LABEL = 2, AUC_BAD_INDEX = 4, AUC_REPEAT = 8, AUC_BAD_FACTOR = 16 };
+
+// scores decoded pair by pair from a thin factor Z (mcgra_decode_auc, mcgra_decode_scores)
+constexpr int DEC_TILE = 64;               // a block's tile: 64 x 64 selected pairs, 4 x 4 per lane
+constexpr int DEC_KC = 32;                 // columns of Z staged per step
+constexpr int DEC_MAX_D = 128;             // widest factor mcgra_decode_auc takes
+constexpr int DEC_SCORE_BLOCKS = 4096;     // blocks of k_dec_scores (grid-stride over the tiles)
 
 // float32 -> unsigned key with the same order; -0.0 and +0.0 are one value.  Bit tests throughout, so that no
 // floating-point mode (denormal flushing) can merge a subnormal with zero.
@@ -266,6 +277,156 @@ __global__ __launch_bounds__(AUC_THREADS) void k_auc_pairs(const uint32_t* __res
   if (threadIdx.x == 0 && tot) atomicAdd(acc, (unsigned long long)tot);
 }
 
+// ---- scores decoded from a thin factor: s_ij = dot_product_decode2(Z)_ij, modes 0, 1, 2, 4, pair by pair ----
+namespace {
+struct DecShared {
+  float a[DEC_TILE][DEC_KC + 1];           // the row panel and the column panel of Z, one step of DEC_KC columns
+  float b[DEC_TILE][DEC_KC + 1];
+  int64_t ia[DEC_TILE], ib[DEC_TILE];      // their node ids; -1 past the selection
+};
+
+// THE score of a pair: f(i, j, s_ij, L_ij) for every selected pair (i, j) of the tiles this block owns (tile t = blockIdx.x,
+// + gridDim.x, ... of the ts x ts tiles of idx x idx; idx == NULL: all nodes).  s_ij = <z_i, z_j> accumulated k ascending
+// in fp32 (one fma per k), - 1 where i == j, relu, sigmoid when sig.  The products commute, so s_ij and s_ji are the same
+// bits, and every kernel below takes its scores from here.
+template <class F>
+__device__ __forceinline__ void dec_for_each(int rows, int d, const float* __restrict__ Z, int64_t ldz, bool sig,
+                                             const float* __restrict__ L, int64_t ldl, const int64_t* __restrict__ idx,
+                                             DecShared& sh, F&& f) {
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  const int ts = (rows + DEC_TILE - 1) / DEC_TILE;
+  for (int64_t tile = blockIdx.x; tile < (int64_t)ts * ts; tile += gridDim.x) {
+    const int a0 = (int)(tile / ts) * DEC_TILE, b0 = (int)(tile % ts) * DEC_TILE;
+    __syncthreads();                                  // the previous tile's epilogue has read ia / ib
+    if (t < 2 * DEC_TILE) {
+      const int r = t % DEC_TILE, q = (t < DEC_TILE ? a0 : b0) + r;
+      (t < DEC_TILE ? sh.ia : sh.ib)[r] = q < rows ? (idx ? idx[q] : (int64_t)q) : -1;
+    }
+    __syncthreads();
+    // the pairs' labels (L != NULL) are asked for first: their latency runs beside the panels' loads and the products
+    float lab[4][4] = {};
+    if (L) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int64_t i = sh.ia[ty + 16 * r], j = sh.ib[tx + 16 * c];
+          if (i >= 0 && j >= 0) lab[r][c] = L[i * ldl + j];
+        }
+    }
+    float acc[4][4] = {};
+    for (int k0 = 0; k0 < d; k0 += DEC_KC) {
+      if (k0) __syncthreads();
+      for (int e = t; e < DEC_TILE * DEC_KC; e += AUC_THREADS) {
+        const int r = e / DEC_KC, k = k0 + e % DEC_KC;
+        const int64_t i = sh.ia[r], j = sh.ib[r];
+        sh.a[r][e % DEC_KC] = (i >= 0 && k < d) ? Z[i * ldz + k] : 0.f;
+        sh.b[r][e % DEC_KC] = (j >= 0 && k < d) ? Z[j * ldz + k] : 0.f;
+      }
+      __syncthreads();
+      const int kn = min(DEC_KC, d - k0);
+      for (int k = 0; k < kn; ++k) {
+        float a[4], b[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { a[q] = sh.a[ty + 16 * q][k]; b[q] = sh.b[tx + 16 * q][k]; }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(a[r], b[c], acc[r][c]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int64_t i = sh.ia[ty + 16 * r], j = sh.ib[tx + 16 * c];
+        if (i < 0 || j < 0) continue;
+        float s = acc[r][c];
+        if (i == j) s -= 1.f;
+        s = s <= 0.f ? 0.f : s;                       // relu; a NaN stays one (torch.relu)
+        if (sig) s = 1.f / (1.f + expf(-s));
+        f(i, j, s, lab[r][c]);
+      }
+  }
+}
+}  // namespace
+
+// One wave per row of Z: flags |= AUC_BAD_FACTOR for a NaN / inf entry; Zn != NULL: Zn[row] = z / max(|z|_2, 1e-12)
+// (F.normalize(Z, p=2, dim=1)), leading dimension d.
+__global__ __launch_bounds__(AUC_THREADS) void k_dec_rows(int n, int d, const float* __restrict__ Z, int64_t ldz,
+                                                          float* __restrict__ Zn, int* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  bool bad = false;
+  for (int row = blockIdx.x * (AUC_THREADS / 64) + (threadIdx.x >> 6); row < n; row += gridDim.x * (AUC_THREADS / 64)) {
+    const float* z = Z + row * ldz;
+    float ss = 0.f;
+    for (int k = lane; k < d; k += 64) {
+      const float v = z[k];
+      bad |= !auc_finite(v);
+      ss = fmaf(v, v, ss);
+    }
+    if (!Zn) continue;
+    const float den = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+    for (int k = lane; k < d; k += 64) Zn[(int64_t)row * d + k] = z[k] / den;
+  }
+  if (bad) atomicOr(flags, AUC_BAD_FACTOR);
+}
+
+// k_auc_classify / k_auc_emit with the scores of dec_for_each
+__global__ __launch_bounds__(AUC_THREADS) void k_dec_classify(int rows, int d, const float* __restrict__ Z, int64_t ldz, int sig,
+                                                              const float* __restrict__ L, int64_t ldl,
+                                                              const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
+                                                              int* __restrict__ flags) {
+  __shared__ DecShared sh;
+  __shared__ uint64_t red[AUC_THREADS / 64];
+  uint32_t pos = 0, tot = 0;
+  int f = 0;
+  dec_for_each(rows, d, Z, ldz, sig != 0, L, ldl, idx, sh, [&](int64_t, int64_t, float s, float l) {
+    if (!auc_finite(s)) f |= AUC_BAD_SCORE;
+    if (auc_pos(l)) ++pos;
+    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;
+    ++tot;
+  });
+  if (f) atomicOr(flags, f);
+  const uint64_t p = block_sum_u64(pos, red);
+  __syncthreads();
+  const uint64_t n = block_sum_u64(tot, red);
+  if (threadIdx.x == 0) { counts[2 * blockIdx.x] = p; counts[2 * blockIdx.x + 1] = n - p; }
+}
+
+__global__ __launch_bounds__(AUC_THREADS) void k_dec_emit(int rows, int d, const float* __restrict__ Z, int64_t ldz, int sig,
+                                                          const float* __restrict__ L, int64_t ldl,
+                                                          const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
+                                                          uint32_t* __restrict__ keys) {
+  __shared__ DecShared sh;
+  __shared__ uint32_t cur[2];
+  if (threadIdx.x < 2) cur[threadIdx.x] = 0;
+  const uint64_t o_pos = offs[2 * blockIdx.x], o_neg = offs[2 * blockIdx.x + 1];
+  const int lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1ull;
+  dec_for_each(rows, d, Z, ldz, sig != 0, L, ldl, idx, sh, [&](int64_t, int64_t, float s, float l) {
+    const bool p = auc_pos(l);
+    const uint64_t act = __ballot(1), mp = __ballot(p);
+    const int leader = __ffsll((unsigned long long)act) - 1;
+    uint32_t bp = 0, bn = 0;
+    if (lane == leader) {
+      bp = atomicAdd(&cur[0], (uint32_t)__popcll(mp));
+      bn = atomicAdd(&cur[1], (uint32_t)__popcll(act & ~mp));
+    }
+    bp = __shfl(bp, leader, 64);
+    bn = __shfl(bn, leader, 64);
+    const uint64_t at = p ? o_pos + bp + __popcll(mp & below) : o_neg + bn + __popcll(act & ~mp & below);
+    keys[at] = auc_key(s);
+  });
+}
+
+// out[i][j] = s_ij for all nodes: the materialised route
+__global__ __launch_bounds__(AUC_THREADS) void k_dec_scores(int n, int d, const float* __restrict__ Z, int64_t ldz, int sig,
+                                                            float* __restrict__ out, int64_t ldo) {
+  __shared__ DecShared sh;
+  dec_for_each(n, d, Z, ldz, sig != 0, nullptr, 0, nullptr, sh, [&](int64_t i, int64_t j, float s, float) { out[i * ldo + j] = s; });
+}
+
 namespace {
 struct AucBufs {
   std::vector<void*> p;
@@ -312,6 +473,92 @@ double auc_divide(uint64_t num, uint64_t den) {
   if (half && (rest || (q & 1u))) ++q;
   return ldexp((double)q, 1 - sh);
 }
+
+// What mcgra_roc_auc and mcgra_decode_auc share around their two passes over the selected pairs.
+struct AucRun {
+  const char* who;
+  hipStream_t st;
+  AucBufs b;
+  int* flags = nullptr;
+  uint64_t* counts = nullptr;
+  unsigned long long* acc = nullptr;
+  int h_flags = 0;
+
+  int begin() {
+    flags = b.get<int>(1);
+    counts = b.get<uint64_t>(2 * AUC_ROW_BLOCKS);
+    acc = b.get<unsigned long long>(1);
+    if (!flags || !counts || !acc) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
+    MCGRA_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
+    MCGRA_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long), st));
+    return 0;
+  }
+  // idx != NULL: range check and repeats; a permutation of all nodes becomes idx = NULL (the same multiset)
+  int select(int n, const int64_t*& idx, int64_t n_idx) {
+    if (!idx) return 0;
+    uint32_t* seen = b.get<uint32_t>(n);
+    if (!seen) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
+    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
+    const int g = (int)std::min<int64_t>(1024, (n_idx + AUC_THREADS - 1) / AUC_THREADS);
+    k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, n_idx, idx, seen, flags);
+    MCGRA_KERNEL_CHECK();
+    MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipStreamSynchronize(st));
+    if (h_flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
+    if (!(h_flags & AUC_REPEAT) && n_idx == n) idx = nullptr;
+    return 0;
+  }
+  // Behind the classify pass of g blocks: its counts and flags, the per-block offsets, the emit pass (emit(offs, keys)
+  // launches it), the two sorts, the pair count and the division.
+  template <class Emit>
+  int finish(int g, Emit&& emit, double* out) {
+    std::vector<uint64_t> h(2 * (size_t)g);
+    MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipStreamSynchronize(st));
+    if (h_flags & AUC_BAD_FACTOR) {
+      set_error("%s: an entry of Z is NaN or infinite", who);
+      return MCGRA_EINVAL;
+    }
+    if (h_flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
+      set_error("%s: %s%s", who, (h_flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite (sklearn: ValueError) " : "",
+                (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1 (sklearn: ValueError)" : "");
+      return MCGRA_EINVAL;
+    }
+    uint64_t P = 0, N = 0;
+    for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
+    if (P == 0 || N == 0) { *out = NAN; return 0; }     // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
+    // positives at [0, P), negatives at [nbase, nbase + N): each region starts on a 16-byte boundary
+    const uint64_t nbase = (P + 3) / 4 * 4;
+    for (uint64_t op = 0, on = nbase, i = 0; i < (uint64_t)g; ++i) {
+      const uint64_t p = h[2 * i], q = h[2 * i + 1];
+      h[2 * i] = op; h[2 * i + 1] = on;
+      op += p; on += q;
+    }
+    uint32_t* keys = b.get<uint32_t>(nbase + N);
+    uint32_t* tmp = b.get<uint32_t>(nbase + N);
+    uint32_t* cnt = b.get<uint32_t>(256 * AUC_SORT_BLOCKS);
+    uint64_t* off = b.get<uint64_t>(256 * AUC_SORT_BLOCKS);
+    if (!keys || !tmp || !cnt || !off) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
+    MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
+    emit(counts, keys);
+    MCGRA_KERNEL_CHECK();
+    if (int rc = auc_sort(st, keys, tmp, P, cnt, off)) return rc;
+    if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, cnt, off)) return rc;
+    const bool a_pos = P <= N;                        // look the smaller class up in the larger one
+    const uint32_t* A = a_pos ? keys : keys + nbase;
+    const uint32_t* B = a_pos ? keys + nbase : keys;
+    const uint64_t na = a_pos ? P : N, nbk = a_pos ? N : P;
+    const int gp = (int)std::min<uint64_t>(4096, (na + AUC_THREADS - 1) / AUC_THREADS);
+    k_auc_pairs<<<gp, AUC_THREADS, 0, st>>>(A, na, B, nbk, a_pos ? 1 : 0, acc);
+    MCGRA_KERNEL_CHECK();
+    unsigned long long u2 = 0;
+    MCGRA_HIP(hipMemcpyAsync(&u2, acc, sizeof(u2), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipStreamSynchronize(st));
+    *out = auc_divide((uint64_t)u2, 2 * P * N);
+    return 0;
+  }
+};
 }  // namespace
 
 }  // namespace mcgra
@@ -330,70 +577,83 @@ extern "C" int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_la
               (long long)AUC_MAX_NIDX);
     return MCGRA_ENOSUP;
   }
-  hipStream_t st = (hipStream_t)stream;
-  AucBufs b;
-  int* flags = b.get<int>(1);
-  uint64_t* counts = b.get<uint64_t>(2 * AUC_ROW_BLOCKS);
-  unsigned long long* acc = b.get<unsigned long long>(1);
-  if (!flags || !counts || !acc) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
-  MCGRA_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
-  MCGRA_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long), st));
-  int h_flags = 0;
-  if (idx) {
-    uint32_t* seen = b.get<uint32_t>(n);
-    if (!seen) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-    const int g = (int)std::min<int64_t>(1024, (n_idx + AUC_THREADS - 1) / AUC_THREADS);
-    k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, n_idx, idx, seen, flags);
-    MCGRA_KERNEL_CHECK();
-    MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (h_flags & AUC_BAD_INDEX) { set_error("roc_auc: a node id outside [0, %d)", n); return MCGRA_EINVAL; }
-    if (!(h_flags & AUC_REPEAT) && n_idx == n) idx = nullptr;      // a permutation of all nodes: the same multiset
-  }
+  AucRun run{"roc_auc", (hipStream_t)stream};
+  hipStream_t st = run.st;
+  if (int rc = run.begin()) return rc;
+  if (int rc = run.select(n, idx, n_idx)) return rc;
   const int rows = (int)n_idx;
   const int g = std::min(rows, AUC_ROW_BLOCKS);
-  k_auc_classify<<<g, AUC_THREADS, 0, st>>>(rows, scores, ld_scores, labels, ld_labels, idx, counts, flags);
+  k_auc_classify<<<g, AUC_THREADS, 0, st>>>(rows, scores, ld_scores, labels, ld_labels, idx, run.counts, run.flags);
   MCGRA_KERNEL_CHECK();
-  std::vector<uint64_t> h(2 * (size_t)g);
-  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipStreamSynchronize(st));
-  if (h_flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-    set_error("roc_auc: %s%s", (h_flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite (sklearn: ValueError) " : "",
-              (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1 (sklearn: ValueError)" : "");
+  return run.finish(g, [&](const uint64_t* offs, uint32_t* keys) {
+    k_auc_emit<<<g, AUC_THREADS, 0, st>>>(rows, scores, ld_scores, labels, ld_labels, idx, offs, keys);
+  }, out);
+}
+
+namespace mcgra {
+namespace {
+// argument checks of the two decode entries; the factor the tile kernels read: Z, or (modes 1, 4) its normalised copy
+int dec_prepare(const char* who, AucRun& run, int n, int d, const float*& Z, int& ldz, int mode) {
+  if (mode < 0 || mode > 6) { set_error("%s: decode_mode %d", who, mode); return MCGRA_EINVAL; }
+  if (mode == 3 || mode > 4) {
+    set_error("%s: decode_mode %d is not a function of <z_i, z_j> alone (modes 0, 1, 2, 4)", who, mode);
+    return MCGRA_ENOSUP;
+  }
+  if (int rc = run.begin()) return rc;
+  float* Zn = nullptr;
+  if (mode == 1 || mode == 4) {
+    Zn = run.b.get<float>((size_t)n * d);
+    if (!Zn) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
+  }
+  k_dec_rows<<<std::min((n + 3) / 4, 1024), AUC_THREADS, 0, run.st>>>(n, d, Z, ldz, Zn, run.flags);
+  MCGRA_KERNEL_CHECK();
+  if (Zn) { Z = Zn; ldz = d; }
+  return 0;
+}
+}  // namespace
+}  // namespace mcgra
+
+extern "C" int mcgra_decode_auc(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
+                                int ld_labels, const int64_t* idx, int64_t n_idx, double* out) {
+  if (n < 1 || d < 1 || !Z || ldz < d || !labels || !out || ld_labels < n || (idx && n_idx < 1)) {
+    set_error("decode_auc: bad argument");
     return MCGRA_EINVAL;
   }
-  uint64_t P = 0, N = 0;
-  for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
-  if (P == 0 || N == 0) { *out = NAN; return 0; }     // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
-  // positives at [0, P), negatives at [nbase, nbase + N): each region starts on a 16-byte boundary
-  const uint64_t nbase = (P + 3) / 4 * 4;
-  for (uint64_t op = 0, on = nbase, i = 0; i < (uint64_t)g; ++i) {
-    const uint64_t p = h[2 * i], q = h[2 * i + 1];
-    h[2 * i] = op; h[2 * i + 1] = on;
-    op += p; on += q;
+  if (!idx) n_idx = n;
+  if (n_idx > AUC_MAX_NIDX) {
+    set_error("decode_auc: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", (long long)n_idx,
+              (long long)AUC_MAX_NIDX);
+    return MCGRA_ENOSUP;
   }
-  uint32_t* keys = b.get<uint32_t>(nbase + N);
-  uint32_t* tmp = b.get<uint32_t>(nbase + N);
-  uint32_t* cnt = b.get<uint32_t>(256 * AUC_SORT_BLOCKS);
-  uint64_t* off = b.get<uint64_t>(256 * AUC_SORT_BLOCKS);
-  if (!keys || !tmp || !cnt || !off) { set_error("roc_auc: hipMalloc of 2 x %llu keys failed", (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
-  MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-  k_auc_emit<<<g, AUC_THREADS, 0, st>>>(rows, scores, ld_scores, labels, ld_labels, idx, counts, keys);
+  if (d > DEC_MAX_D) {
+    set_error("decode_auc: a factor of %d columns (at most %d; mcgra_decode_scores + mcgra_roc_auc take any width)", d, DEC_MAX_D);
+    return MCGRA_ENOSUP;
+  }
+  AucRun run{"decode_auc", (hipStream_t)stream};
+  hipStream_t st = run.st;
+  if (int rc = dec_prepare(run.who, run, n, d, Z, ldz, mode)) return rc;
+  if (int rc = run.select(n, idx, n_idx)) return rc;
+  const int rows = (int)n_idx, sig = mode < 2;
+  const int ts = (rows + DEC_TILE - 1) / DEC_TILE;
+  const int g = (int)std::min<int64_t>((int64_t)ts * ts, AUC_ROW_BLOCKS);
+  k_dec_classify<<<g, AUC_THREADS, 0, st>>>(rows, d, Z, ldz, sig, labels, ld_labels, idx, run.counts, run.flags);
   MCGRA_KERNEL_CHECK();
-  if (int rc = auc_sort(st, keys, tmp, P, cnt, off)) return rc;
-  if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, cnt, off)) return rc;
-  const bool a_pos = P <= N;                        // look the smaller class up in the larger one
-  const uint32_t* A = a_pos ? keys : keys + nbase;
-  const uint32_t* B = a_pos ? keys + nbase : keys;
-  const uint64_t na = a_pos ? P : N, nbk = a_pos ? N : P;
-  const int gp = (int)std::min<uint64_t>(4096, (na + AUC_THREADS - 1) / AUC_THREADS);
-  k_auc_pairs<<<gp, AUC_THREADS, 0, st>>>(A, na, B, nbk, a_pos ? 1 : 0, acc);
+  return run.finish(g, [&](const uint64_t* offs, uint32_t* keys) {
+    k_dec_emit<<<g, AUC_THREADS, 0, st>>>(rows, d, Z, ldz, sig, labels, ld_labels, idx, offs, keys);
+  }, out);
+}
+
+extern "C" int mcgra_decode_scores(void* stream, int n, int d, const float* Z, int ldz, int mode, float* out, int ld_out) {
+  if (n < 1 || d < 1 || !Z || ldz < d || !out || ld_out < n) { set_error("decode_scores: bad argument"); return MCGRA_EINVAL; }
+  AucRun run{"decode_scores", (hipStream_t)stream};
+  hipStream_t st = run.st;
+  if (int rc = dec_prepare(run.who, run, n, d, Z, ldz, mode)) return rc;
+  const int ts = (n + DEC_TILE - 1) / DEC_TILE;
+  const int g = (int)std::min<int64_t>((int64_t)ts * ts, DEC_SCORE_BLOCKS);
+  k_dec_scores<<<g, AUC_THREADS, 0, st>>>(n, d, Z, ldz, mode < 2, out, ld_out);
   MCGRA_KERNEL_CHECK();
-  unsigned long long u2 = 0;
-  MCGRA_HIP(hipMemcpyAsync(&u2, acc, sizeof(u2), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipStreamSynchronize(st));
-  *out = auc_divide((uint64_t)u2, 2 * P * N);
+  MCGRA_HIP(hipMemcpyAsync(&run.h_flags, run.flags, sizeof(int), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));     // also: the normalised copy is freed on return
+  if (run.h_flags & AUC_BAD_FACTOR) { set_error("decode_scores: an entry of Z is NaN or infinite"); return MCGRA_EINVAL; }
   return 0;
 }

@@ -199,6 +199,21 @@ def mse(X, Y):
     return out[0]
 
 
+def _rows_f32(t, dev):
+    """t as float32 rows on dev (unit stride inside a row; a padded leading dimension is kept)."""
+    t = t.detach()
+    if t.device != dev or t.dtype != torch.float32 or t.stride(1) != 1:
+        t = t.to(device=dev, dtype=torch.float32).contiguous()
+    return t
+
+
+def _node_ids(idx, dev):
+    if idx is None:
+        return None
+    ix = idx.detach() if isinstance(idx, torch.Tensor) else torch.as_tensor(np.asarray(idx, dtype=np.int64))
+    return ix.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+
+
 @_on_operand_device
 def roc_auc(real, pred, idx=None):
     """main.metric_pool (main.py:66-75): roc_curve + auc of real[idx][:, idx] against pred[idx][:, idx], exactly, without
@@ -208,22 +223,38 @@ def roc_auc(real, pred, idx=None):
     dev = real.device
     n = real.shape[0]
     assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-
-    def rows(t):
-        t = t.detach()
-        if t.device != dev or t.dtype != torch.float32 or t.stride(1) != 1:
-            t = t.to(device=dev, dtype=torch.float32).contiguous()
-        return t
-
-    real, pred = rows(real), rows(pred)
-    ix = None
-    if idx is not None:
-        ix = idx.detach() if isinstance(idx, torch.Tensor) else torch.as_tensor(np.asarray(idx, dtype=np.int64))
-        ix = ix.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
     out = C.c_double()
     check(lib.mcgra_roc_auc(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
                             ix.numel() if ix is not None else n, C.byref(out)))
     return out.value
+
+
+@_on_operand_device
+def decode_auc(real, Z, mode, idx=None):
+    """roc_auc(real, decode_scores(Z, mode), idx), bit for bit, without the n x n score matrix (mcgra_decode_auc): the AUC
+    of a prior's decode, main.py:412-437.  Z: n x d, d <= 128; mode 0, 1, 2 or 4 (McgraNotSupported otherwise)."""
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and Z.dim() == 2 and Z.shape[0] == n, (real.shape, Z.shape)
+    real, Z = _rows_f32(real, dev), _rows_f32(Z, dev)
+    ix = _node_ids(idx, dev)
+    out = C.c_double()
+    check(lib.mcgra_decode_auc(_stream(), n, Z.shape[1], _p(Z), Z.stride(0), int(mode), _p(real), real.stride(0), _p(ix),
+                               ix.numel() if ix is not None else n, C.byref(out)))
+    return out.value
+
+
+@_on_operand_device
+def decode_scores(Z, mode):
+    """The n x n scores decode_auc ranks, materialised (mcgra_decode_scores): dot_product_decode2 modes 0, 1, 2, 4 from one
+    fp32 dot product per pair, bitwise symmetric; any width."""
+    Z = _rows_f32(Z, Z.device)
+    n, d = Z.shape
+    out = torch.empty(n, n, device=Z.device, dtype=torch.float32)
+    check(lib.mcgra_decode_scores(_stream(), n, d, _p(Z), Z.stride(0), int(mode), _p(out), n))
+    return out
 
 
 @_on_operand_device

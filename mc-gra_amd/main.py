@@ -6,8 +6,11 @@ H_A / Y_A, run PGDAttack on the MI355X hot path, report the recovered-adjacency 
         --useH_A --useY_A --useY --measure MSELoss            (after mcgra_loader.load())
     python mc-gra_amd/main.py ...                             (stand-alone; bootstraps the loader itself)
 
---arch gcn | sage | gat select the victim family as main.py:175-231 does.  Not provided (each exits with a message
-naming the reference line): --mode search/baseline/gaussian/gcn_attack.
+--arch gcn | sage | gat select the victim family as main.py:175-231 does.  Also provided: --mode prepare (main.py:440-450,
+writes the label adjacency under --saved_data) and --mode notrain_test (main.py:412-437: no attack; the AUC of each prior's
+own decode -- features, H_A1, H_A2, Y_A, label adjacency -- against the true graph, the three thin priors pair by pair on
+the GPU without an n x n score matrix).  Not provided (each exits with a message naming the reference line): --mode
+search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 mc-gra_amd/main.py --dataset ... --measure HSIC ...
@@ -96,6 +99,12 @@ def dot_product_decode(Z, dataset):
     return torch.relu(Z - torch.eye(Z.shape[0], device=Z.device))
 
 
+def decode_branch(dataset):
+    """The branch of dot_product_decode above as a decode mode of mcgra.h: 0 sigmoid(relu(Z Z^T - I)) for cora / citeseer /
+    AIDS, 4 relu(Zn Zn^T - I) on L2-normalised rows otherwise."""
+    return 0 if dataset in ('cora', 'citeseer', 'AIDS') else 4
+
+
 def metric_pool(ori_adj, inference_adj, idx):
     """main.metric_pool (main.py:66-75): roc_curve + auc of ori_adj[idx][:, idx] against inference_adj[idx][:, idx], on the
     device that holds inference_adj (engine.roc_auc: exact, no gathered submatrix, no host copy).  idx None: every node."""
@@ -106,6 +115,26 @@ def label_adjacency(labels):
     """main.prepare (main.py:440-450): label_adj[i][j] = (labels[i] == labels[j])."""
     lab = np.asarray(labels)
     return (lab[:, None] == lab[None, :]).astype(np.float32)
+
+
+def prior_aucs(adj, feature_adj, H_A1, H_A2, Y_A, label_adj, dataset):
+    """main.notrain_test (main.py:412-437): metric_pool over all nodes of what each prior gives away on its own.  The two
+    n x n matrices go through engine.roc_auc; H_A1, H_A2, Y_A are decoded pair by pair inside engine.decode_auc (no n x n
+    score matrix), a prior wider than 128 columns through engine.decode_scores + engine.roc_auc (the same scores)."""
+    dev, mode = H_A2.device, decode_branch(dataset)
+    adj = adj.to(dev)
+
+    def matrix(S):
+        return engine.roc_auc(adj, torch.as_tensor(S).to(dev))
+
+    def thin(Z):
+        Z = Z.detach().to(dev)
+        if Z.shape[1] > 128:
+            return engine.roc_auc(adj, engine.decode_scores(Z, mode))
+        return engine.decode_auc(adj, Z, mode)
+
+    return {"feature": float(matrix(feature_adj)), "layer1": float(thin(H_A1)), "layer2": float(thin(H_A2)),
+            "out": float(thin(Y_A)), "label": float(matrix(label_adj))}
 
 
 def victim_tensors(m):
@@ -222,7 +251,7 @@ def _run(args, rank, world):
         embedding(fd, ad)                                                                  # H_A     main.py:235
         Y_A = victim_model(fd, ad)                                                         # main.py:236
         embedding.set_layers(1)
-        embedding(fd, ad)                                                                  # H_A1    main.py:238-239
+        H_A1 = embedding(fd, ad)                                                           # main.py:238-239
         embedding.set_layers(2)
         H_A2 = embedding(fd, ad)                                                           # main.py:240-241
         out = victim_model(fd, utils.normalize_adj_tensor(ad))
@@ -230,10 +259,18 @@ def _run(args, rank, world):
     idx_attack = np.array(random.sample(range(adj.shape[0]), int(adj.shape[0] * args.nlabel)))   # main.py:244
     num_edges = int(0.5 * args.density * adj.sum() / adj.shape[0] ** 2 * len(idx_attack) ** 2)
 
-    lr = 10 ** args.lr                                                                     # objective(): main.py:282-283
-    weight_param = tuple(getattr(args, f"w{i}") for i in range(1, 11))
     lab_path = os.path.join(args.saved_data, args.dataset + ".npy")
     label_adj = np.load(lab_path) if os.path.exists(lab_path) else label_adjacency(labels)
+    if args.mode == "notrain_test":                                                        # main.py:412-437: no attack
+        res = prior_aucs(ad, feature_adj, H_A1, H_A2, Y_A, label_adj, args.dataset)
+        if rank == 0:
+            print("feautre adj=", res["feature"])
+            print("layer1 adj=", res["layer1"])
+            print("layer2 adj=", res["layer2"])
+            print("out adj=", res["out"])
+        return res
+    lr = 10 ** args.lr                                                                     # objective(): main.py:282-283
+    weight_param = tuple(getattr(args, f"w{i}") for i in range(1, 11))
     model = PGDAttack(model=victim_model, embedding=embedding, H_A=H_A2, Y_A=Y_A, nnodes=adj.shape[0],
                       loss_type='CE', device=device)
     if getattr(args, "adj_changes_init", None) is not None:      # (tests: a seeded start; adj_changes is a public attribute, :77)
