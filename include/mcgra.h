@@ -189,6 +189,25 @@ int mcgra_mse(void* stream, int64_t count, const float* X, const float* Y, float
 int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                   const int64_t* idx, int64_t n_idx, double* out);
 
+/* The AUC above and the average precision of the same ranking,
+ * sklearn.metrics.average_precision_score(labels[idx][:, idx].reshape(-1), scores[idx][:, idx].reshape(-1)), from one
+ * classify, one emit and one sort of the selected entries.  auc, ap: host doubles; either may be NULL (not computed), not
+ * both (MCGRA_EINVAL).  Arguments, checks, error codes and the n_idx limit as mcgra_roc_auc; *auc is bit for bit what
+ * mcgra_roc_auc returns.
+ *   AP = (1 / P) sum over selected positives i of TP(s_i) / (TP(s_i) + FP(s_i)),
+ *   TP(s) = #selected positives with score >= s, FP(s) = #selected negatives with score >= s
+ *   - ties as above (float32 equality, -0.0 == +0.0): all positives of one score share one term;
+ *   - TP + FP < 2^33, so each term is one correctly rounded float64 division; the terms are added in a fixed order (no
+ *     floating-point atomics; per lane in index order, a fixed tree over lanes, waves and blocks, the grid a function of
+ *     P alone), so *ap is the same bits on every call and under any permutation of a repeat-free idx.  With T =
+ *     ceil(P / 2^20) terms per lane the relative error is at most (T + 32) 2^-53: 3.7e-15 up to P = 2^20, 4.6e-13 at
+ *     the n_idx limit;
+ *   - N == 0: *ap = 1.0 exactly (every term is 1; sklearn gives the same), *auc = NaN;
+ *   - P == 0: *ap = NaN, a mean over no positives, as *auc is NaN for an absent class.  (sklearn 1.7 returns 0.0 here
+ *     and warns "No positive class found"; older versions return NaN.) */
+int mcgra_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                       const int64_t* idx, int64_t n_idx, double* auc, double* ap);
+
 /* The same AUC for scores that are never stored: s_ij = dot_product_decode2(Z)_ij of the thin factor Z [n x d] (leading
  * dimension ldz >= d), computed pair by pair over idx x idx (main.py:412-437, notrain_test: how much of the graph a prior
  * leaks on its own).  labels, idx, n_idx, *out, exactness, NaN and error codes as mcgra_roc_auc.
@@ -201,6 +220,11 @@ int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const
  * Device scratch: two 4-byte keys per selected pair, the normalised copy, about 3 MB. */
 int mcgra_decode_auc(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels, int ld_labels,
                      const int64_t* idx, int64_t n_idx, double* out);
+/* mcgra_rank_metrics on the scores mcgra_decode_auc ranks: mode and width rules, checks and error codes as
+ * mcgra_decode_auc, auc / ap as mcgra_rank_metrics; *auc is bit for bit mcgra_decode_auc's, and both are bit for bit
+ * mcgra_rank_metrics on what mcgra_decode_scores writes. */
+int mcgra_decode_rank_metrics(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
+                              int ld_labels, const int64_t* idx, int64_t n_idx, double* auc, double* ap);
 /* out [n x n] (leading dimension ld_out >= n) = the same s_ij, materialised; any d.  Not the bits of
  * mcgra_dot_product_decode2, whose product runs on the MFMA GEMM.  Synchronises. */
 int mcgra_decode_scores(void* stream, int n, int d, const float* Z, int ldz, int mode, float* out, int ld_out);

@@ -39,6 +39,7 @@ SYMBOLS = [
     "mcgra_attack_masked_fused_steps",
     "mcgra_attack_cut_product_steps",
     "mcgra_roc_auc", "mcgra_decode_auc", "mcgra_decode_scores",
+    "mcgra_rank_metrics", "mcgra_decode_rank_metrics",
 ]
 
 
@@ -100,6 +101,10 @@ def _load():
         "mcgra_roc_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_double)],
         "mcgra_decode_auc": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_double)],
         "mcgra_decode_scores": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int],
+        "mcgra_rank_metrics": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)],
+        "mcgra_decode_rank_metrics": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, ip, C.c_int64,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

@@ -13,6 +13,9 @@
 //                      count, one scan of the (digit, block) counts and a stable scatter
 //   k_auc_pairs        each key of the smaller class looks up its lower and upper bound in the sorted larger class;
 //                      the sum of the two is that key's share of 2U
+//   k_ap_terms         (average precision, mcgra_rank_metrics) each positive key x: its lower bound in the sorted
+//                      positives and in the sorted negatives give TP = #positives >= x, FP = #negatives >= x and the term
+//                      TP / (TP + FP); one float64 partial per block.  k_ap_sum adds the partials and divides by P
 // mcgra_decode_auc ranks scores that are never stored, s_ij = dot_product_decode2(Z)_ij of a thin factor Z [n x d]:
 //   k_dec_rows         every row of Z: NaN / inf check, the L2-normalised copy of modes 1 and 4
 //   k_dec_classify     k_auc_classify on the scores dec_for_each decodes, a block owning 64 x 64 tiles of idx x idx
@@ -20,6 +23,19 @@
 //   k_dec_scores       the same scores written out (mcgra_decode_scores: the materialised route)
 // Counts and 2U are 64-bit integers merged with global integer atomics, so the result does not depend on the order in
 // which blocks run; the one rounding is the final division (host, exact integer long division, nearest even).
+//
+// Average precision, AP = (1 / P) sum over selected positives of TP / (TP + FP) at that positive's score (ties included:
+// sklearn.metrics.average_precision_score), is a sum of float64 terms, so its summation order is fixed instead: no
+// floating-point atomics, a grid that is a function of P alone (min(4096, ceil(P / 256)) blocks of 256 lanes), each lane adds
+// its strided terms in index order, the 64 lanes of a wave are added in a fixed xor-shuffle tree (6 levels), the four waves
+// as (w0 + w1) + (w2 + w3) through LDS, and one block adds the per-block partials the same way (at most 16 per lane, then
+// the same 8 levels).  The sorted regions do not depend on the order of a repeat-free idx, so neither do the bits of AP.
+// Rounding: TP + FP < 2^33 is exact in float64, so a term is one correctly rounded division; with T = ceil(P / (256 x blocks))
+// serial terms per lane the result passes through at most 1 + (T - 1) + 8 + 15 + 8 + 1 = T + 32 roundings, and all terms are
+// positive, so the relative error is at most (T + 32) 2^-53 (1 + o(1)): 3.7e-15 up to P = 2^20, and with n_idx <= 65 535
+// (P < 2^32, T <= 4096) at most 4128 * 2^-53 = 4.6e-13.
+// P = 0: AP is a mean over no positives, NaN as the AUC of an absent class is (sklearn 1.7 returns 0.0 with a "No positive
+// class found" warning, older versions NaN).  N = 0: every term is 1 and AP is exactly 1.0, as sklearn's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -37,6 +53,8 @@ constexpr int AUC_ROW_BLOCKS = 1024;       // blocks of the two passes over the 
 constexpr int AUC_SORT_TILE = 1024;        // keys staged per step of a sort block (256 lanes x one 16-byte load)
 constexpr int AUC_SORT_BLOCKS = 1024;      // at most this many tiles of keys per sort pass
 constexpr int64_t AUC_MAX_NIDX = 65535;    // 2 P N <= 2 (n_idx^2 / 2)^2 < 2^63
+constexpr int AP_BLOCKS = 4096;            // at most this many blocks (and float64 partials) of k_ap_terms
+static_assert(AUC_THREADS == 256, "block_sum_f64 adds four waves as (w0 + w1) + (w2 + w3)");
 
 enum { AUC_BAD_SCORE = 1, AUC_BAD_LABEL = 2, AUC_BAD_INDEX = 4, AUC_REPEAT = 8, AUC_BAD_FACTOR = 16 };
 
@@ -103,6 +121,15 @@ __device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* sh) {
   if (threadIdx.x == 0)
     for (int w = 0; w < AUC_THREADS / 64; ++w) t += sh[w];
   return t;
+}
+// float64 sum over the block in one fixed tree: xor butterfly over the 64 lanes of a wave (a + b == b + a, so every lane
+// holds the same bits), then (w0 + w1) + (w2 + w3); valid in every thread
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 }  // namespace
 
@@ -275,6 +302,38 @@ __global__ __launch_bounds__(AUC_THREADS) void k_auc_pairs(const uint32_t* __res
   }
   const uint64_t tot = block_sum_u64(s, sh);
   if (threadIdx.x == 0 && tot) atomicAdd(acc, (unsigned long long)tot);
+}
+
+// part[b] = block b's sum of TP / (TP + FP) over the sorted positives Pk[0, np) it owns (index i = global lane, + lanes of
+// the grid, ...; a lane adds its terms in that order), TP = np - lower_bound(Pk, x), FP = nn - lower_bound(Nk, x).  Always
+// walks the positives; the grid is a function of np alone (header comment).
+__global__ __launch_bounds__(AUC_THREADS) void k_ap_terms(const uint32_t* __restrict__ Pk, uint64_t np,
+                                                          const uint32_t* __restrict__ Nk, uint64_t nn,
+                                                          double* __restrict__ part) {
+  __shared__ double sh[AUC_THREADS / 64];
+  double s = 0.0;
+  for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < np; i += (uint64_t)gridDim.x * AUC_THREADS) {
+    const uint32_t x = Pk[i];
+    uint64_t lo = 0, hi = i;                        // first positive >= x: Pk[i] == x, so it is at or before i
+    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (Pk[m] < x) lo = m + 1; else hi = m; }
+    const uint64_t tp = np - lo;
+    lo = 0; hi = nn;                                // first negative >= x
+    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (Nk[m] < x) lo = m + 1; else hi = m; }
+    const uint64_t fp = nn - lo;
+    s += (double)tp / (double)(tp + fp);            // tp + fp < 2^33: both conversions exact, one rounding
+  }
+  const double tot = block_sum_f64(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// one block: *out = (part[0] + ... + part[nb - 1]) / np, lane t adding part[t], part[t + 256], ... then the same tree
+__global__ __launch_bounds__(AUC_THREADS) void k_ap_sum(const double* __restrict__ part, int nb, uint64_t np,
+                                                        double* __restrict__ out) {
+  __shared__ double sh[AUC_THREADS / 64];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += AUC_THREADS) s += part[i];
+  const double tot = block_sum_f64(s, sh);
+  if (threadIdx.x == 0) *out = tot / (double)np;
 }
 
 // ---- scores decoded from a thin factor: s_ij = dot_product_decode2(Z)_ij, modes 0, 1, 2, 4, pair by pair ----
@@ -474,7 +533,8 @@ double auc_divide(uint64_t num, uint64_t den) {
   return ldexp((double)q, 1 - sh);
 }
 
-// What mcgra_roc_auc and mcgra_decode_auc share around their two passes over the selected pairs.
+// What mcgra_roc_auc / mcgra_rank_metrics and mcgra_decode_auc / mcgra_decode_rank_metrics share around their two passes
+// over the selected pairs.
 struct AucRun {
   const char* who;
   hipStream_t st;
@@ -509,9 +569,10 @@ struct AucRun {
     return 0;
   }
   // Behind the classify pass of g blocks: its counts and flags, the per-block offsets, the emit pass (emit(offs, keys)
-  // launches it), the two sorts, the pair count and the division.
+  // launches it), the two sorts, then what was asked for: auc != NULL the pair count and the division, ap != NULL the
+  // average-precision terms and their sum (both read the same sorted regions).
   template <class Emit>
-  int finish(int g, Emit&& emit, double* out) {
+  int finish(int g, Emit&& emit, double* auc, double* ap) {
     std::vector<uint64_t> h(2 * (size_t)g);
     MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -527,7 +588,11 @@ struct AucRun {
     }
     uint64_t P = 0, N = 0;
     for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
-    if (P == 0 || N == 0) { *out = NAN; return 0; }     // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
+    if (P == 0 || N == 0) {
+      if (auc) *auc = NAN;                              // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
+      if (ap) *ap = P == 0 ? NAN : 1.0;                 // a mean over no positives; no negatives: every term is TP / TP
+      return 0;
+    }
     // positives at [0, P), negatives at [nbase, nbase + N): each region starts on a 16-byte boundary
     const uint64_t nbase = (P + 3) / 4 * 4;
     for (uint64_t op = 0, on = nbase, i = 0; i < (uint64_t)g; ++i) {
@@ -539,23 +604,35 @@ struct AucRun {
     uint32_t* tmp = b.get<uint32_t>(nbase + N);
     uint32_t* cnt = b.get<uint32_t>(256 * AUC_SORT_BLOCKS);
     uint64_t* off = b.get<uint64_t>(256 * AUC_SORT_BLOCKS);
-    if (!keys || !tmp || !cnt || !off) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
+    double* part = ap ? b.get<double>(AP_BLOCKS + 1) : nullptr;      // the per-block partials, then the result
+    if (!keys || !tmp || !cnt || !off || (ap && !part)) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
     MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
     emit(counts, keys);
     MCGRA_KERNEL_CHECK();
     if (int rc = auc_sort(st, keys, tmp, P, cnt, off)) return rc;
     if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, cnt, off)) return rc;
-    const bool a_pos = P <= N;                        // look the smaller class up in the larger one
-    const uint32_t* A = a_pos ? keys : keys + nbase;
-    const uint32_t* B = a_pos ? keys + nbase : keys;
-    const uint64_t na = a_pos ? P : N, nbk = a_pos ? N : P;
-    const int gp = (int)std::min<uint64_t>(4096, (na + AUC_THREADS - 1) / AUC_THREADS);
-    k_auc_pairs<<<gp, AUC_THREADS, 0, st>>>(A, na, B, nbk, a_pos ? 1 : 0, acc);
-    MCGRA_KERNEL_CHECK();
     unsigned long long u2 = 0;
-    MCGRA_HIP(hipMemcpyAsync(&u2, acc, sizeof(u2), hipMemcpyDeviceToHost, st));
+    if (auc) {
+      const bool a_pos = P <= N;                      // look the smaller class up in the larger one
+      const uint32_t* A = a_pos ? keys : keys + nbase;
+      const uint32_t* B = a_pos ? keys + nbase : keys;
+      const uint64_t na = a_pos ? P : N, nbk = a_pos ? N : P;
+      const int gp = (int)std::min<uint64_t>(4096, (na + AUC_THREADS - 1) / AUC_THREADS);
+      k_auc_pairs<<<gp, AUC_THREADS, 0, st>>>(A, na, B, nbk, a_pos ? 1 : 0, acc);
+      MCGRA_KERNEL_CHECK();
+      MCGRA_HIP(hipMemcpyAsync(&u2, acc, sizeof(u2), hipMemcpyDeviceToHost, st));
+    }
+    double h_ap = 0.0;
+    if (ap) {
+      const int ga = (int)std::min<uint64_t>(AP_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
+      k_ap_terms<<<ga, AUC_THREADS, 0, st>>>(keys, P, keys + nbase, N, part);
+      k_ap_sum<<<1, AUC_THREADS, 0, st>>>(part, ga, P, part + AP_BLOCKS);
+      MCGRA_KERNEL_CHECK();
+      MCGRA_HIP(hipMemcpyAsync(&h_ap, part + AP_BLOCKS, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
     MCGRA_HIP(hipStreamSynchronize(st));
-    *out = auc_divide((uint64_t)u2, 2 * P * N);
+    if (auc) *auc = auc_divide((uint64_t)u2, 2 * P * N);
+    if (ap) *ap = h_ap;
     return 0;
   }
 };
@@ -565,19 +642,22 @@ struct AucRun {
 
 using namespace mcgra;
 
-extern "C" int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
-                             const int64_t* idx, int64_t n_idx, double* out) {
-  if (n < 1 || !labels || !scores || !out || ld_labels < n || ld_scores < n || (idx && n_idx < 1)) {
-    set_error("roc_auc: bad argument");
+namespace mcgra {
+namespace {
+// mcgra_roc_auc (ap == NULL) and mcgra_rank_metrics: one classify, one emit and the two sorts for whatever is asked for
+int rank_matrix(const char* who, void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
+  if (n < 1 || !labels || !scores || (!auc && !ap) || ld_labels < n || ld_scores < n || (idx && n_idx < 1)) {
+    set_error("%s: bad argument", who);
     return MCGRA_EINVAL;
   }
   if (!idx) n_idx = n;
   if (n_idx > AUC_MAX_NIDX) {
-    set_error("roc_auc: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", (long long)n_idx,
+    set_error("%s: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", who, (long long)n_idx,
               (long long)AUC_MAX_NIDX);
     return MCGRA_ENOSUP;
   }
-  AucRun run{"roc_auc", (hipStream_t)stream};
+  AucRun run{who, (hipStream_t)stream};
   hipStream_t st = run.st;
   if (int rc = run.begin()) return rc;
   if (int rc = run.select(n, idx, n_idx)) return rc;
@@ -587,7 +667,19 @@ extern "C" int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_la
   MCGRA_KERNEL_CHECK();
   return run.finish(g, [&](const uint64_t* offs, uint32_t* keys) {
     k_auc_emit<<<g, AUC_THREADS, 0, st>>>(rows, scores, ld_scores, labels, ld_labels, idx, offs, keys);
-  }, out);
+  }, auc, ap);
+}
+}  // namespace
+}  // namespace mcgra
+
+extern "C" int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                             const int64_t* idx, int64_t n_idx, double* out) {
+  return rank_matrix("roc_auc", stream, n, labels, ld_labels, scores, ld_scores, idx, n_idx, out, nullptr);
+}
+
+extern "C" int mcgra_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                                  const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
+  return rank_matrix("rank_metrics", stream, n, labels, ld_labels, scores, ld_scores, idx, n_idx, auc, ap);
 }
 
 namespace mcgra {
@@ -613,23 +705,27 @@ int dec_prepare(const char* who, AucRun& run, int n, int d, const float*& Z, int
 }  // namespace
 }  // namespace mcgra
 
-extern "C" int mcgra_decode_auc(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
-                                int ld_labels, const int64_t* idx, int64_t n_idx, double* out) {
-  if (n < 1 || d < 1 || !Z || ldz < d || !labels || !out || ld_labels < n || (idx && n_idx < 1)) {
-    set_error("decode_auc: bad argument");
+namespace mcgra {
+namespace {
+// mcgra_decode_auc (ap == NULL) and mcgra_decode_rank_metrics
+int rank_decoded(const char* who, void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
+                 int ld_labels, const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
+  if (n < 1 || d < 1 || !Z || ldz < d || !labels || (!auc && !ap) || ld_labels < n || (idx && n_idx < 1)) {
+    set_error("%s: bad argument", who);
     return MCGRA_EINVAL;
   }
   if (!idx) n_idx = n;
   if (n_idx > AUC_MAX_NIDX) {
-    set_error("decode_auc: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", (long long)n_idx,
+    set_error("%s: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", who, (long long)n_idx,
               (long long)AUC_MAX_NIDX);
     return MCGRA_ENOSUP;
   }
   if (d > DEC_MAX_D) {
-    set_error("decode_auc: a factor of %d columns (at most %d; mcgra_decode_scores + mcgra_roc_auc take any width)", d, DEC_MAX_D);
+    set_error("%s: a factor of %d columns (at most %d; mcgra_decode_scores + mcgra_roc_auc / mcgra_rank_metrics take any width)",
+              who, d, DEC_MAX_D);
     return MCGRA_ENOSUP;
   }
-  AucRun run{"decode_auc", (hipStream_t)stream};
+  AucRun run{who, (hipStream_t)stream};
   hipStream_t st = run.st;
   if (int rc = dec_prepare(run.who, run, n, d, Z, ldz, mode)) return rc;
   if (int rc = run.select(n, idx, n_idx)) return rc;
@@ -640,7 +736,19 @@ extern "C" int mcgra_decode_auc(void* stream, int n, int d, const float* Z, int 
   MCGRA_KERNEL_CHECK();
   return run.finish(g, [&](const uint64_t* offs, uint32_t* keys) {
     k_dec_emit<<<g, AUC_THREADS, 0, st>>>(rows, d, Z, ldz, sig, labels, ld_labels, idx, offs, keys);
-  }, out);
+  }, auc, ap);
+}
+}  // namespace
+}  // namespace mcgra
+
+extern "C" int mcgra_decode_auc(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
+                                int ld_labels, const int64_t* idx, int64_t n_idx, double* out) {
+  return rank_decoded("decode_auc", stream, n, d, Z, ldz, mode, labels, ld_labels, idx, n_idx, out, nullptr);
+}
+
+extern "C" int mcgra_decode_rank_metrics(void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
+                                         int ld_labels, const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
+  return rank_decoded("decode_rank_metrics", stream, n, d, Z, ldz, mode, labels, ld_labels, idx, n_idx, auc, ap);
 }
 
 extern "C" int mcgra_decode_scores(void* stream, int n, int d, const float* Z, int ldz, int mode, float* out, int ld_out) {

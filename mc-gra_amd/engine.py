@@ -246,6 +246,61 @@ def decode_auc(real, Z, mode, idx=None):
     return out.value
 
 
+def _rank_metrics(real, pred, idx, want_auc, want_ap):
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
+    auc, ap = C.c_double(), C.c_double()
+    check(lib.mcgra_rank_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
+                                 ix.numel() if ix is not None else n, C.byref(auc) if want_auc else None,
+                                 C.byref(ap) if want_ap else None))
+    return auc.value, ap.value
+
+
+@_on_operand_device
+def rank_metrics(real, pred, idx=None):
+    """(roc_auc(real, pred, idx), average precision of the same ranking) from one sort of the selected entries
+    (mcgra_rank_metrics).  The AUC is bit for bit roc_auc's; the average precision is
+    sklearn.metrics.average_precision_score(real[idx][:, idx].reshape(-1), pred[idx][:, idx].reshape(-1)): ties share one
+    term, summed in a fixed order (the same bits on every call).  Arguments and refusals as roc_auc.  No selected
+    positive: (NaN, NaN); no selected negative: (NaN, 1.0)."""
+    return _rank_metrics(real, pred, idx, True, True)
+
+
+@_on_operand_device
+def average_precision(real, pred, idx=None):
+    """The second value of rank_metrics alone (the pair count of the AUC is not run)."""
+    return _rank_metrics(real, pred, idx, False, True)[1]
+
+
+def _decode_rank_metrics(real, Z, mode, idx, want_auc, want_ap):
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and Z.dim() == 2 and Z.shape[0] == n, (real.shape, Z.shape)
+    real, Z = _rows_f32(real, dev), _rows_f32(Z, dev)
+    ix = _node_ids(idx, dev)
+    auc, ap = C.c_double(), C.c_double()
+    check(lib.mcgra_decode_rank_metrics(_stream(), n, Z.shape[1], _p(Z), Z.stride(0), int(mode), _p(real), real.stride(0),
+                                        _p(ix), ix.numel() if ix is not None else n, C.byref(auc) if want_auc else None,
+                                        C.byref(ap) if want_ap else None))
+    return auc.value, ap.value
+
+
+@_on_operand_device
+def decode_rank_metrics(real, Z, mode, idx=None):
+    """rank_metrics(real, decode_scores(Z, mode), idx), bit for bit, without the n x n score matrix
+    (mcgra_decode_rank_metrics).  Z, mode and refusals as decode_auc."""
+    return _decode_rank_metrics(real, Z, mode, idx, True, True)
+
+
+@_on_operand_device
+def decode_average_precision(real, Z, mode, idx=None):
+    """The second value of decode_rank_metrics alone."""
+    return _decode_rank_metrics(real, Z, mode, idx, False, True)[1]
+
+
 @_on_operand_device
 def decode_scores(Z, mode):
     """The n x n scores decode_auc ranks, materialised (mcgra_decode_scores): dot_product_decode2 modes 0, 1, 2, 4 from one

@@ -9,7 +9,8 @@ H_A / Y_A, run PGDAttack on the MI355X hot path, report the recovered-adjacency 
 --arch gcn | sage | gat select the victim family as main.py:175-231 does.  Also provided: --mode prepare (main.py:440-450,
 writes the label adjacency under --saved_data) and --mode notrain_test (main.py:412-437: no attack; the AUC of each prior's
 own decode -- features, H_A1, H_A2, Y_A, label adjacency -- against the true graph, the three thin priors pair by pair on
-the GPU without an n x n score matrix).  Not provided (each exits with a message naming the reference line): --mode
+the GPU without an n x n score matrix).  --ap (not in the reference; off by default, and then nothing changes) adds the
+average precision of every ranking that is scored beside its AUC, from the same sort (engine.rank_metrics).  Not provided (each exits with a message naming the reference line): --mode
 search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -86,6 +87,7 @@ def build_parser():
     p.add_argument('--dataset_root', type=str, default='./dataset')
     p.add_argument('--saved_data', type=str, default='./saved_data')
     p.add_argument('--device', type=str, default='cuda:0')
+    p.add_argument('--ap', action='store_true')     # also report average precision (engine.rank_metrics)
     return p
 
 
@@ -135,6 +137,27 @@ def prior_aucs(adj, feature_adj, H_A1, H_A2, Y_A, label_adj, dataset):
 
     return {"feature": float(matrix(feature_adj)), "layer1": float(thin(H_A1)), "layer2": float(thin(H_A2)),
             "out": float(thin(Y_A)), "label": float(matrix(label_adj))}
+
+
+def prior_rank_metrics(adj, feature_adj, H_A1, H_A2, Y_A, label_adj, dataset):
+    """prior_aucs with the average precision of each ranking beside its AUC (--ap): (aucs, aps), two dicts with prior_aucs'
+    keys.  Each pair comes from one sort: engine.rank_metrics for the matrices, engine.decode_rank_metrics for the thin
+    priors, engine.decode_scores + engine.rank_metrics past 128 columns.  The AUCs are prior_aucs' bit for bit."""
+    dev, mode = H_A2.device, decode_branch(dataset)
+    adj = adj.to(dev)
+
+    def matrix(S):
+        return engine.rank_metrics(adj, torch.as_tensor(S).to(dev))
+
+    def thin(Z):
+        Z = Z.detach().to(dev)
+        if Z.shape[1] > 128:
+            return engine.rank_metrics(adj, engine.decode_scores(Z, mode))
+        return engine.decode_rank_metrics(adj, Z, mode)
+
+    both = {"feature": matrix(feature_adj), "layer1": thin(H_A1), "layer2": thin(H_A2), "out": thin(Y_A),
+            "label": matrix(label_adj)}
+    return {k: float(v[0]) for k, v in both.items()}, {k: float(v[1]) for k, v in both.items()}
 
 
 def victim_tensors(m):
@@ -262,12 +285,20 @@ def _run(args, rank, world):
     lab_path = os.path.join(args.saved_data, args.dataset + ".npy")
     label_adj = np.load(lab_path) if os.path.exists(lab_path) else label_adjacency(labels)
     if args.mode == "notrain_test":                                                        # main.py:412-437: no attack
-        res = prior_aucs(ad, feature_adj, H_A1, H_A2, Y_A, label_adj, args.dataset)
+        want_ap = getattr(args, "ap", False)
+        if want_ap:
+            res, aps = prior_rank_metrics(ad, feature_adj, H_A1, H_A2, Y_A, label_adj, args.dataset)
+            res["ap"] = aps
+        else:
+            res = prior_aucs(ad, feature_adj, H_A1, H_A2, Y_A, label_adj, args.dataset)
         if rank == 0:
             print("feautre adj=", res["feature"])
             print("layer1 adj=", res["layer1"])
             print("layer2 adj=", res["layer2"])
             print("out adj=", res["out"])
+            if want_ap:
+                for k in ("feature", "layer1", "layer2", "out", "label"):
+                    print(f"{k} ap=", res["ap"][k])
         return res
     lr = 10 ** args.lr                                                                     # objective(): main.py:282-283
     weight_param = tuple(getattr(args, f"w{i}") for i in range(1, 11))
@@ -279,19 +310,34 @@ def _run(args, rank, world):
                  idx_test, adj, features, init_adj, labels, idx_attack, num_edges, 0, epochs=args.epochs,
                  label_adj=label_adj)
     inference_adj = model.modified_adj                     # stays on the device: the three AUCs run there (main.py:247-250)
-    res = {"auc_attack": float(metric_pool(ad, inference_adj, idx_attack)),
-           "auc_train": float(metric_pool(ad, inference_adj, idx_train)),
-           "auc_all": float(metric_pool(ad, inference_adj, None)),
-           "density": float(inference_adj.mean())}
+    want_ap = getattr(args, "ap", False)
+    if want_ap:             # AUC and average precision from one sort per index set; the AUCs are metric_pool's bit for bit
+        sets = {"attack": idx_attack, "train": idx_train, "all": None}
+        both = {k: engine.rank_metrics(ad.to(inference_adj.device), inference_adj, ix) for k, ix in sets.items()}
+        res = {f"auc_{k}": float(both[k][0]) for k in sets}
+        res["density"] = float(inference_adj.mean())
+        res.update({f"ap_{k}": float(both[k][1]) for k in sets})
+    else:
+        res = {"auc_attack": float(metric_pool(ad, inference_adj, idx_attack)),
+               "auc_train": float(metric_pool(ad, inference_adj, idx_train)),
+               "auc_all": float(metric_pool(ad, inference_adj, None)),
+               "density": float(inference_adj.mean())}
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
     print(f"current auc={res['auc_all']}")
+    if want_ap:
+        print(f"current ap={res['ap_all']}")
     os.makedirs("./results/", exist_ok=True)
+    # the parameter line names --ap only when it is set: without it the log is what it was before the flag existed
+    shown = args if want_ap else argparse.Namespace(**{k: v for k, v in vars(args).items() if k != "ap"})
     with open(os.path.join("./results", args.log_name), "a") as f:                         # main.py:314-323
-        f.write(f"current parameter: {args}\n")
+        f.write(f"current parameter: {shown}\n")
         f.write(f"In attack graph: AUC={res['auc_attack']}\tIn train graph: AUC={res['auc_train']}\t"
                 f"In Whole Graph: AUC={res['auc_all']}\n")
+        if want_ap:
+            f.write(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
+                    f"In Whole Graph: AP={res['ap_all']}\n")
         f.write(f"current density: {res['density']}\n")
     return res
 
