@@ -498,6 +498,98 @@ def term_case(spec, term, with_tiny, steps=2):
     return case_from(spec), c, (ws, wp), oracle_trajectory(case_from(spec), ws, wp, steps)
 
 
+# ---------------------------------------------------------------- the edge-budget projection against its exact root
+def exact_projection_root(a_packed, num_edges):
+    """(miu*, K): the float64 root of f(x) = sum(clip(a - x, 0, 1)) = num_edges and K, the number of entries with
+    0 < a - miu* < 1 (f's slope at the root is -K).  f is piecewise linear and non-increasing: float64 bisection to 1e-15 finds the
+    linear piece, the piece's own equation  sum_{active} a - K x + #{a - x >= 1} = num_edges  gives the root.  The budget must
+    bind (f(0) > num_edges > 0): PGDAttack.projection does not search otherwise."""
+    a = np.asarray(a_packed, np.float64).ravel()
+    ne = float(num_edges)
+    f = lambda x: float(np.clip(a - x, 0.0, 1.0).sum())
+    assert 0.0 < ne < f(0.0), ("the budget does not bind", ne, f(0.0))
+    lo, hi = float(a.min()) - 1.0, float(a.max())          # f(lo) = a.size > ne, f(hi) = 0 < ne
+    while hi - lo > 1e-15:
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:                        # (the bracket is down to neighbouring doubles)
+            break
+        if f(mid) > ne:
+            lo = mid
+        else:
+            hi = mid
+    x = 0.5 * (lo + hi)
+    act = (a - x > 0.0) & (a - x < 1.0)
+    K = int(act.sum())
+    if K == 0:                                            # a flat piece: every point of it is a root
+        return x, 0
+    miu = (float(a[act].sum()) + float((a - x >= 1.0).sum()) - ne) / K
+    assert abs(miu - x) <= 1e-12 and abs(f(miu) - ne) <= 1e-9 * max(1.0, ne), (miu, x, f(miu), ne)
+    return miu, int(((a - miu > 0.0) & (a - miu < 1.0)).sum())
+
+
+def pre_projection_state(M_before, adam_m, adam_v, t, lr):
+    """What Adam's step t left of the state BEFORE projection and clamp: p - step_size * (m / denom) in float32, operation by
+    operation as oracle.AdamState.step ends, from the moments AFTER that step (an engine's buffer("adam_m") / buffer("adam_v")).
+    M_before is the state the step started from; t counts from 1.  Every argument is packed (strict lower triangle, O.pack_tril):
+    the fused step does not write the mirrored halves of the moments (fl_tail_adam: mirror_moments = 0), so only that triangle
+    is Adam's state.  Returns float32."""
+    f4 = np.float32
+    p, m, v = (np.asarray(x, f4) for x in (M_before, adam_m, adam_v))
+    assert p.ndim == m.ndim == v.ndim == 1 and p.shape == m.shape == v.shape
+    bc1 = 1 - 0.9 ** int(t)
+    bc2 = 1 - 0.999 ** int(t)
+    step_size = float(lr) / bc1
+    denom = (np.sqrt(v) / f4(np.sqrt(bc2)) + f4(1e-8)).astype(f4)
+    return (p - f4(step_size) * (m / denom)).astype(f4)
+
+
+# The projection cases (tests/test_gpu_projection.py; their properties: tests/test_projection_cases_cpu.py).  The start is
+# uniform on [0, 1.05): about 4 % of the entries sit above 1 + lr and are above 1 after any Adam step, so a premature clamp in an
+# Adam kernel -- clip(clip(a, 0, 1) - miu, 0, 1) in place of clip(a - miu, 0, 1) -- moves them by up to 0.05.
+PROJ_A0_SCALE = 1.05
+PROJ_BUDGETS = {"tight": 0.4, "loose": 0.95}              # num_edges = factor * sum(clip(a0, 0, 1)), float64
+
+
+def projection_case(n, measure, ori=False):
+    """synthetic_case as the other oracle tests use it (11 features, widths (16, 16), 4 classes, seed = n) from the start above;
+    ori: ori_adj = adj, the graph itself, so that the step runs clamp(M + ori) with its gradient gate."""
+    z = synthetic_case(n, 11, (16, 16), 4, seed=n, measure=measure, a0_scale=PROJ_A0_SCALE)
+    if ori:
+        z["ori_adj"] = z["adj"].copy()
+    return z
+
+
+def projection_budget(z, which):
+    return PROJ_BUDGETS[which] * float(np.clip(a0_of(z).astype(np.float64), 0.0, 1.0).sum())
+
+
+# id -> (n, measure, ori_adj = adj, switches): one case per Adam kernel that can run in front of the projection, at the smallest
+# n that takes it (HSIC: the fused step from n = 1024, where the split product starts; 515: a ragged last 64-tile)
+PROJ_CASES = {
+    "fused_mse_300": (300, "MSELoss", False, {}),
+    "fused_kl_300": (300, "KL", False, {}),
+    "fused_hsic_1100": (1100, "HSIC", False, {}),
+    "rankk_adam_hsic_300": (300, "HSIC", False, {"MCGRA_NO_FUSED_LR": "1"}),
+    "rankk_adam_mse_515": (515, "MSELoss", False, {"MCGRA_NO_FUSED_LR": "1"}),
+    "rankk_nt_adam_sym_300": (300, "HSIC", False, {"MCGRA_NO_FUSED_LR": "1", "MCGRA_NO_FUSED_TAIL": "1"}),
+    # (below n = 256.  Not the smallest ragged size, 97: its 4656 pairs hold about 4656 * lr / 1.05 = 44 entries within lr of 0, so
+    #  no step can leave the 100 entries below 0 that test_projection_cases_cpu.py asks of every MSELoss case; 161 = 2 * 64 + 33 can)
+    "adam_sym_161": (161, "MSELoss", False, {}),
+    "adam_sym_gate_161": (161, "MSELoss", True, {}),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def projection_oracle_pre(n, measure, ori):
+    """(a0, a_pre) of a projection case on the numpy oracle: the packed start and the packed state its first Adam step leaves
+    before projection and clamp (which no budget changes)."""
+    z = projection_case(n, measure, ori)
+    orc = oracle_from(z)
+    orc.step()
+    a0 = a0_of(z)
+    return a0, pre_projection_state(a0, O.pack_tril(orc.adam.m), O.pack_tril(orc.adam.v), 1, float(z["lr"]))
+
+
 # ---------------------------------------------------------------- GPU-side helpers
 def engine_from(pkg, z, device="cuda:0", measure=None, weight_param=None, **kw):
     """AttackEngine (C-ABI handle) set up from a golden attack case."""
