@@ -229,6 +229,45 @@ int mcgra_decode_rank_metrics(void* stream, int n, int d, const float* Z, int ld
  * mcgra_dot_product_decode2, whose product runs on the MFMA GEMM.  Synchronises. */
 int mcgra_decode_scores(void* stream, int n, int d, const float* Z, int ldz, int mode, float* out, int ld_out);
 
+/* The recovered graph: the k best-scored node pairs of `scores` within idx, and how many of them are edges of `labels`.
+ *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL
+ *     for all n nodes in order.  The candidates are the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b; pair
+ *     (a, b) is nodes u = idx[a], v = idx[b], its score scores[u][v] and its label labels[u][v]: the strict lower triangle
+ *     of the gathered submatrix -- for an asymmetric matrix that entry, not [v][u], is the one read.  Its packed position
+ *     is p = a (a - 1) / 2 + b (torch.tril_indices(offset=-1); adj_changes).  Unlike mcgra_roc_auc / mcgra_rank_metrics,
+ *     which range over all ordered entries of idx x idx, diagonal included, this ranges over unordered off-diagonal pairs;
+ *   - the ranking: score descending as float32 values (-0.0 == +0.0; subnormals and negative scores are ordinary values),
+ *     ties by ascending packed position; the k best are its first k: np.argsort(-s, kind="stable")[:k] over the scores in
+ *     packed order;
+ *   - counts (host int64[4]) = {k used, P, TP, m}: P the candidates with label 1, TP those among the k best.  precision =
+ *     TP / k, recall = TP / P, F1 = 2 TP / (k + P) are left to the caller (exact integers);
+ *   - k == 0 means k = P, the true graph's own edge count in the selection (then precision = recall = F1); with P == 0
+ *     counts = {0, 0, 0, m} and *threshold is not written.  k < 0 or k > m: MCGRA_EINVAL;
+ *   - *threshold (host, may be NULL) = the score of the k-th pair of the ranking, its bits as stored;
+ *   - a selected score that is NaN or +-inf, or a selected label other than 0 or 1: MCGRA_EINVAL; entries outside the
+ *     selected lower triangle are not looked at;
+ *   - n_idx (n when idx is NULL) from 2 (MCGRA_EINVAL below) up to 65 535, so that p fits 32 bits; MCGRA_ENOSUP beyond;
+ *   - exact and the same bits on every call: a radix select on order-preserving keys (no sort of the m candidates),
+ *     integer counts, and threshold ties ranked in packed order whatever order the blocks run in.
+ * Argument checks that need no device run before any HIP call.  Synchronises `stream`.
+ * Device scratch: 5 bytes per candidate pair (a 4-byte key and the label) plus about 3 MB. */
+int mcgra_topk_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                       const int64_t* idx, int64_t n_idx, int64_t k, int64_t* counts /* host[4]: k used, P, TP, m */,
+                       float* threshold /* host, score of the k-th pair; may be NULL */);
+
+/* The same k best pairs as an edge list in RANKING ORDER (best first, ties by ascending packed position), so that the
+ * first k' <= k rows are the answer for k'.  Selection, ranking, checks, limits and error codes as mcgra_topk_metrics;
+ * 1 <= k <= m.  pairs (device int64 [k x 2]) = the node ids u = idx[a], v = idx[b] (a > b) of each pair; pair_scores
+ * (device [k], may be NULL) = scores[u][v], the bits as stored; hits (device uint8 [k], may be NULL; needs labels) = 1
+ * where labels[u][v] is 1.  labels may be NULL (then nothing is said about edges; given, every selected label is checked).
+ * Synchronises `stream`.
+ * Device scratch: 4 bytes per candidate pair, 16 bytes per returned pair (the records and the second buffer of their
+ * stable radix sort by descending key), about 3 MB. */
+int mcgra_top_pairs(void* stream, int n, const float* scores, int ld_scores, const int64_t* idx, int64_t n_idx, int64_t k,
+                    const float* labels /* may be NULL */, int ld_labels,
+                    int64_t* pairs /* device [k x 2]: u, v */, float* pair_scores /* device [k], may be NULL */,
+                    uint8_t* hits /* device [k], may be NULL; needs labels */);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

@@ -1,0 +1,377 @@
+// The recovered graph: the k best-scored unordered node pairs of a scored square matrix restricted to idx, as counts
+// (mcgra_topk_metrics: TP among the k best, P among all candidates) and as an edge list in ranking order (mcgra_top_pairs).
+//
+// Candidates: the m = n_idx (n_idx - 1) / 2 pairs of positions a > b of idx (idx == NULL: all n nodes in order); pair (a, b)
+// is nodes u = idx[a], v = idx[b], its score scores[u][v], its label labels[u][v] (the strict lower triangle of the gathered
+// submatrix: for an asymmetric matrix that entry, not [v][u], is read), its packed position p = a (a - 1) / 2 + b (the order
+// of torch.tril_indices(offset=-1) and of adj_changes).  The AUC and AP entries of auc.hip range over all ordered entries,
+// diagonal included; these range over unordered off-diagonal pairs.
+// Ranking: score descending as float32 values (-0.0 == +0.0, subnormals and negatives ordinary values), ties by ascending p:
+// np.argsort(-s, kind="stable")[:k] over the scores in packed order.
+//
+// Passes:
+//   k_auc_index        idx only: range check, repeats (rank_common.h)
+//   k_topk_emit        the one read of the selected lower triangle: argument checks, P (64-bit integer atomics), each
+//                      pair's order-preserving key to keys[p] and, for the metrics, its label to lab[p]
+//   k_topk_hist/_pick  MSB-first radix select, 4 passes of 8 bits: a 256-bin histogram (LDS, merged with integer atomics) of
+//                      the keys that match the prefix found so far, then one block walks the bins from 255 down.  Result:
+//                      the threshold key T, g = #keys above T, r = k - g >= 1 keys equal to T to take.  No sort of the m keys
+//   k_topk_count       per block of a contiguous packed range: #keys above T, #keys equal to T; k_auc_digit_scan scans both
+//   k_topk_take        every block ranks the threshold ties of its range in index order (ballots; wave counts through LDS;
+//                      the scan gives the ties before the block) and takes those of rank < r: TP is counted (metrics), or
+//                      the chosen (key, p) records are compacted in packed order (edge list); the pair of tie rank r - 1 is
+//                      the k-th of the ranking and its score is the threshold reported
+//   auc_sort           edge list: a stable LSD radix sort of the k records by descending key with p as payload; they enter
+//                      in ascending p, so ties leave in ascending p
+//   k_topk_write       each record's pair (u, v), and its score and label read back from the matrices (copied bits)
+// All of it is integers and copied float32 bits; per-block counts are over fixed contiguous ranges and merged by a scan or by
+// integer atomics, so no result depends on the order in which blocks run and every call returns the same bits.
+// Device scratch: 4 bytes per candidate (the keys), + 1 byte per candidate (mcgra_topk_metrics: the labels), + 16 bytes per
+// returned pair (mcgra_top_pairs: the records and the sort's second buffer), + about 3 MB.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/mcgra.h"
+#include "common.h"
+#include "rank_common.h"
+
+namespace mcgra {
+namespace {
+constexpr int TOPK_ROW_BLOCKS = 1024;      // blocks of the pass over the matrix (grid-stride over selected rows)
+constexpr int TOPK_BLOCKS = 1024;          // at most this many contiguous packed ranges (and blocks) per pass over the keys
+constexpr int TOPK_HIST_STEP = 4 * AUC_THREADS;   // keys per step of a histogram block (one 16-byte load per lane)
+
+struct TopkState {
+  unsigned long long hist[256];            // the current pass's bins; k_topk_pick clears them
+  unsigned long long P;                    // candidates with label 1
+  unsigned long long tp;                   // of the k best
+  unsigned long long remaining;            // keys still to take among those that match the prefix
+  uint32_t prefix;                         // the threshold key's digits found so far
+  uint32_t thr_bits;                       // the k-th pair's score
+  int flags;
+};
+
+// pair (a, b), a > b >= 0, of packed position p = a (a - 1) / 2 + b
+__device__ __forceinline__ void topk_unpack(uint32_t p, uint32_t& a, uint32_t& b) {
+  uint32_t x = (uint32_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
+  while ((uint64_t)x * (x - 1) / 2 > p) --x;
+  while ((uint64_t)x * (x + 1) / 2 <= p) ++x;
+  a = x;
+  b = p - (uint32_t)((uint64_t)x * (x - 1) / 2);
+}
+
+// keys[p] = key of pair p, lab[p] = its label (lab != NULL); st->P += labels that are 1; st->flags |= argument errors.
+// A block owns rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection.
+__global__ __launch_bounds__(AUC_THREADS) void k_topk_emit(int rows, const float* __restrict__ S, int64_t lds,
+                                                           const float* __restrict__ L, int64_t ldl,
+                                                           const int64_t* __restrict__ idx, uint32_t* __restrict__ keys,
+                                                           uint8_t* __restrict__ lab, TopkState* __restrict__ st) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  uint64_t pos = 0;
+  int f = 0;
+  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
+    const int64_t u = idx ? idx[a] : a;
+    const float* srow = S + u * lds;
+    const float* lrow = L ? L + u * ldl : nullptr;
+    const uint64_t base = (uint64_t)a * (a - 1) / 2;
+    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
+      const int64_t v = idx ? idx[b] : b;
+      const float s = srow[v];
+      if (!auc_finite(s)) f |= AUC_BAD_SCORE;
+      keys[base + b] = auc_key(s);
+      if (lrow) {
+        const float l = lrow[v];
+        const bool p = auc_pos(l);
+        if (p) ++pos;
+        else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+        if (lab) lab[base + b] = p ? 1 : 0;
+      }
+    }
+  }
+  if (f) atomicOr(&st->flags, f);
+  const uint64_t tot = block_sum_u64(pos, sh);
+  if (threadIdx.x == 0 && tot) atomicAdd(&st->P, (unsigned long long)tot);
+}
+
+// st->hist[d] += keys whose digits above `shift + 8` are the prefix's and whose digit (key >> shift) & 255 is d
+__global__ __launch_bounds__(AUC_THREADS) void k_topk_hist(const uint32_t* __restrict__ keys, uint64_t count, int shift,
+                                                           TopkState* __restrict__ st) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t prefix = st->prefix;
+  const int hi = shift + 8;                                    // 32 on the first pass: every key matches
+  auto add = [&](uint32_t k) {
+    if ((uint32_t)((uint64_t)(k ^ prefix) >> hi) == 0u) atomicAdd(&h[(k >> shift) & 255u], 1u);
+  };
+  // a block adds at most ceil(2^31 / (TOPK_BLOCKS * TOPK_HIST_STEP)) * TOPK_HIST_STEP < 2^32 keys: the bins do not wrap
+  for (uint64_t e = ((uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x) * 4; e < count; e += (uint64_t)gridDim.x * TOPK_HIST_STEP) {
+    if (e + 4 <= count) {
+      const uint4 k = *(const uint4*)(keys + e);                // keys is a hipMalloc'ed base: 16-byte aligned
+      add(k.x); add(k.y); add(k.z); add(k.w);
+    } else {
+      for (uint64_t q = e; q < count; ++q) add(keys[q]);
+    }
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&st->hist[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// one block: the digit d at which the bins, walked from 255 down, reach st->remaining; prefix |= d << shift, remaining -= the
+// keys in the bins above d; the bins are cleared for the next pass
+__global__ __launch_bounds__(256) void k_topk_pick(int shift, TopkState* __restrict__ st) {
+  __shared__ unsigned long long h[256];
+  h[threadIdx.x] = st->hist[threadIdx.x];
+  __syncthreads();
+  st->hist[threadIdx.x] = 0;
+  if (threadIdx.x != 0) return;
+  const unsigned long long want = st->remaining;
+  unsigned long long above = 0;
+  int d = 255;
+  while (d > 0 && above + h[d] < want) { above += h[d]; --d; }
+  st->prefix |= (uint32_t)d << shift;
+  st->remaining = want - above;
+}
+
+// block b's contiguous range [b tile, (b + 1) tile): cnt[b] = #keys above T, cnt[nb + b] = #keys equal to T
+__global__ __launch_bounds__(AUC_THREADS) void k_topk_count(const uint32_t* __restrict__ keys, uint64_t count, uint64_t tile,
+                                                            uint32_t T, int nb, uint32_t* __restrict__ cnt) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  const uint64_t beg = blockIdx.x * tile, end = min(count, beg + tile);
+  uint64_t gt = 0, eq = 0;
+  for (uint64_t e = beg + threadIdx.x; e < end; e += AUC_THREADS) {
+    const uint32_t k = keys[e];
+    gt += k > T;
+    eq += k == T;
+  }
+  const uint64_t g = block_sum_u64(gt, sh);
+  __syncthreads();
+  const uint64_t q = block_sum_u64(eq, sh);
+  if (threadIdx.x == 0) { cnt[blockIdx.x] = (uint32_t)g; cnt[nb + blockIdx.x] = (uint32_t)q; }
+}
+
+// The k best of block b's range, in index order, 256 keys a step: a key above T, or a key equal to T whose rank among ALL
+// keys equal to T (off[nb + b] - g before this block, then the earlier steps, the earlier waves, the lower lanes) is below
+// r.  EMIT: the chosen (~key, p) go to rk / rp at their rank among the chosen, off[b] + min(ties before the block, r) before
+// this block (packed order).  Otherwise st->tp += the chosen with label 1.  The tie of rank r - 1 is the k-th pair: its
+// score goes to st->thr_bits.
+template <bool EMIT>
+__global__ __launch_bounds__(AUC_THREADS) void k_topk_take(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab,
+                                                           uint64_t count, uint64_t tile, uint32_t T, uint64_t g, uint64_t r,
+                                                           int nb, const uint64_t* __restrict__ off,
+                                                           const float* __restrict__ S, int64_t lds,
+                                                           const int64_t* __restrict__ idx, uint32_t* __restrict__ rk,
+                                                           uint32_t* __restrict__ rp, TopkState* __restrict__ st) {
+  __shared__ uint32_t weq[2][AUC_THREADS / 64], wch[2][AUC_THREADS / 64];
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const uint64_t beg = blockIdx.x * tile, end = min(count, beg + tile);
+  uint64_t run_eq = off[nb + blockIdx.x] - g;                  // ties before this block
+  uint64_t run_ch = off[blockIdx.x] + min(run_eq, r);          // chosen before this block
+  uint64_t tp = 0;
+  int par = 0;
+  for (uint64_t base = beg; base < end; base += AUC_THREADS, par ^= 1) {
+    const uint64_t e = base + t;
+    const bool valid = e < end;
+    const uint32_t k = valid ? keys[e] : 0u;
+    const bool eq = valid && k == T;
+    const uint64_t meq = __ballot(eq);
+    if (lane == 0) weq[par][w] = (uint32_t)__popcll(meq);
+    __syncthreads();
+    uint64_t rank = run_eq + __popcll(meq & below), all_eq = 0;
+    for (int q = 0; q < AUC_THREADS / 64; ++q) {
+      if (q < w) rank += weq[par][q];
+      all_eq += weq[par][q];
+    }
+    const bool chosen = valid && (k > T || (eq && rank < r));
+    if (eq && rank == r - 1) {
+      uint32_t a, b;
+      topk_unpack((uint32_t)e, a, b);
+      const int64_t u = idx ? idx[a] : a, v = idx ? idx[b] : b;
+      st->thr_bits = __float_as_uint(S[u * lds + v]);
+    }
+    run_eq += all_eq;
+    if (EMIT) {
+      const uint64_t mch = __ballot(chosen);
+      if (lane == 0) wch[par][w] = (uint32_t)__popcll(mch);
+      __syncthreads();
+      uint64_t at = run_ch + __popcll(mch & below), all_ch = 0;
+      for (int q = 0; q < AUC_THREADS / 64; ++q) {
+        if (q < w) at += wch[par][q];
+        all_ch += wch[par][q];
+      }
+      if (chosen) { rk[at] = ~k; rp[at] = (uint32_t)e; }
+      run_ch += all_ch;
+    } else if (chosen && lab[e]) {
+      ++tp;
+    }
+  }
+  if (!EMIT) {
+    const uint64_t tot = block_sum_u64(tp, sh);
+    if (t == 0 && tot) atomicAdd(&st->tp, (unsigned long long)tot);
+  }
+}
+
+// row i of the answer: the pair of record i, its score and its label read back from the matrices
+__global__ __launch_bounds__(AUC_THREADS) void k_topk_write(uint64_t k, const uint32_t* __restrict__ rp,
+                                                            const float* __restrict__ S, int64_t lds,
+                                                            const float* __restrict__ L, int64_t ldl,
+                                                            const int64_t* __restrict__ idx, int64_t* __restrict__ pairs,
+                                                            float* __restrict__ pair_scores, uint8_t* __restrict__ hits) {
+  for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < k; i += (uint64_t)gridDim.x * AUC_THREADS) {
+    uint32_t a, b;
+    topk_unpack(rp[i], a, b);
+    const int64_t u = idx ? idx[a] : a, v = idx ? idx[b] : b;
+    pairs[2 * i] = u;
+    pairs[2 * i + 1] = v;
+    if (pair_scores) pair_scores[i] = S[u * lds + v];
+    if (hits) hits[i] = auc_pos(L[u * ldl + v]) ? 1 : 0;
+  }
+}
+
+// What the two entries share: the argument pass, the keys and the select.
+struct TopkRun {
+  const char* who;
+  hipStream_t st;
+  AucBufs b;
+  TopkState* state = nullptr;
+  TopkState h{};                          // the host's copy, after emit() and after select()
+  uint32_t* keys = nullptr;
+  uint8_t* lab = nullptr;
+  uint32_t* cnt = nullptr;
+  uint64_t* off = nullptr;
+  uint64_t m = 0, tile = 0;
+  int nb = 0;
+
+  int fetch() {
+    MCGRA_HIP(hipMemcpyAsync(&h, state, sizeof(TopkState), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipStreamSynchronize(st));
+    return 0;
+  }
+  // idx check, then the one read of the selected lower triangle; on return h.P is P
+  int emit(int n, const float* S, int lds, const float* L, int ldl, const int64_t* idx, int rows, bool want_lab) {
+    m = (uint64_t)rows * (rows - 1) / 2;
+    state = b.get<TopkState>(1);
+    keys = b.get<uint32_t>(m);
+    lab = want_lab ? b.get<uint8_t>(m) : nullptr;
+    cnt = b.get<uint32_t>(256 * AUC_SORT_BLOCKS);
+    off = b.get<uint64_t>(256 * AUC_SORT_BLOCKS);
+    if (!state || !keys || (want_lab && !lab) || !cnt || !off) {
+      set_error("%s: hipMalloc of the scratch of %llu pairs failed", who, (unsigned long long)m);
+      return MCGRA_ENOMEM;
+    }
+    MCGRA_HIP(hipMemsetAsync(state, 0, sizeof(TopkState), st));
+    if (idx) {
+      uint32_t* seen = b.get<uint32_t>(n);
+      if (!seen) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
+      MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
+      const int g = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
+      k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, rows, idx, seen, &state->flags);
+      MCGRA_KERNEL_CHECK();
+      if (int rc = fetch()) return rc;
+      if (h.flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
+      if (h.flags & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
+    }
+    k_topk_emit<<<std::min(rows - 1, TOPK_ROW_BLOCKS), AUC_THREADS, 0, st>>>(rows, S, lds, L, ldl, idx, keys, lab, state);
+    MCGRA_KERNEL_CHECK();
+    if (int rc = fetch()) return rc;
+    if (h.flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
+      set_error("%s: %s%s", who, (h.flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
+                (h.flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
+      return MCGRA_EINVAL;
+    }
+    tile = (m + TOPK_BLOCKS - 1) / TOPK_BLOCKS;
+    tile = (tile + AUC_THREADS - 1) / AUC_THREADS * AUC_THREADS;
+    nb = (int)((m + tile - 1) / tile);
+    return 0;
+  }
+  // the threshold of the k best, 1 <= k <= m: h.prefix = T, h.remaining = r; then the per-range counts and their scan
+  int select(uint64_t k) {
+    MCGRA_HIP(hipMemcpyAsync(&state->remaining, &k, sizeof(k), hipMemcpyHostToDevice, st));
+    const int g = (int)std::min<uint64_t>(TOPK_BLOCKS, (m + TOPK_HIST_STEP - 1) / TOPK_HIST_STEP);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      k_topk_hist<<<g, AUC_THREADS, 0, st>>>(keys, m, shift, state);
+      k_topk_pick<<<1, 256, 0, st>>>(shift, state);
+    }
+    MCGRA_KERNEL_CHECK();
+    if (int rc = fetch()) return rc;      // (also: &k was read)
+    k_topk_count<<<nb, AUC_THREADS, 0, st>>>(keys, m, tile, h.prefix, nb, cnt);
+    k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt, 2 * nb, off);
+    MCGRA_KERNEL_CHECK();
+    return 0;
+  }
+};
+
+int topk_check(const char* who, int n, const float* scores, int ld_scores, const float* labels, int ld_labels,
+               const int64_t* idx, int64_t& n_idx, int64_t k, int64_t k_min) {
+  if (!idx) n_idx = n;
+  if (n < 1 || !scores || ld_scores < n || (labels && ld_labels < n) || n_idx < 2 || k < k_min) {
+    set_error("%s: bad argument", who);
+    return MCGRA_EINVAL;
+  }
+  if (n_idx > AUC_MAX_NIDX) {
+    set_error("%s: %lld selected nodes; a packed pair position of more than %lld does not fit 32 bits", who, (long long)n_idx,
+              (long long)AUC_MAX_NIDX);
+    return MCGRA_ENOSUP;
+  }
+  const int64_t m = n_idx * (n_idx - 1) / 2;
+  if (k > m) { set_error("%s: k = %lld of %lld pairs", who, (long long)k, (long long)m); return MCGRA_EINVAL; }
+  return 0;
+}
+}  // namespace
+}  // namespace mcgra
+
+using namespace mcgra;
+
+extern "C" int mcgra_topk_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                                  const int64_t* idx, int64_t n_idx, int64_t k, int64_t* counts, float* threshold) {
+  if (!labels || !counts) { set_error("topk_metrics: bad argument"); return MCGRA_EINVAL; }
+  if (int rc = topk_check("topk_metrics", n, scores, ld_scores, labels, ld_labels, idx, n_idx, k, 0)) return rc;
+  TopkRun run{"topk_metrics", (hipStream_t)stream};
+  hipStream_t st = run.st;
+  if (int rc = run.emit(n, scores, ld_scores, labels, ld_labels, idx, (int)n_idx, true)) return rc;
+  const uint64_t P = run.h.P;
+  const uint64_t kk = k ? (uint64_t)k : P;                  // k == 0: the true graph's own edge count in the selection
+  counts[0] = (int64_t)kk; counts[1] = (int64_t)P; counts[2] = 0; counts[3] = (int64_t)run.m;
+  if (kk == 0) return 0;
+  if (int rc = run.select(kk)) return rc;
+  const uint64_t r = run.h.remaining, g = kk - r;
+  k_topk_take<false><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, run.lab, run.m, run.tile, run.h.prefix, g, r, run.nb, run.off,
+                                                     scores, ld_scores, idx, nullptr, nullptr, run.state);
+  MCGRA_KERNEL_CHECK();
+  if (int rc = run.fetch()) return rc;
+  counts[2] = (int64_t)run.h.tp;
+  if (threshold) memcpy(threshold, &run.h.thr_bits, sizeof(float));
+  return 0;
+}
+
+extern "C" int mcgra_top_pairs(void* stream, int n, const float* scores, int ld_scores, const int64_t* idx, int64_t n_idx,
+                               int64_t k, const float* labels, int ld_labels, int64_t* pairs, float* pair_scores,
+                               uint8_t* hits) {
+  if (!pairs || (hits && !labels)) { set_error("top_pairs: bad argument"); return MCGRA_EINVAL; }
+  if (int rc = topk_check("top_pairs", n, scores, ld_scores, labels, ld_labels, idx, n_idx, k, 1)) return rc;
+  TopkRun run{"top_pairs", (hipStream_t)stream};
+  hipStream_t st = run.st;
+  if (int rc = run.emit(n, scores, ld_scores, labels, ld_labels, idx, (int)n_idx, false)) return rc;
+  const uint64_t kk = (uint64_t)k;
+  uint32_t* rk = run.b.get<uint32_t>(kk);
+  uint32_t* rp = run.b.get<uint32_t>(kk);
+  uint32_t* tk = run.b.get<uint32_t>(kk);
+  uint32_t* tp = run.b.get<uint32_t>(kk);
+  if (!rk || !rp || !tk || !tp) { set_error("top_pairs: hipMalloc of %llu records failed", (unsigned long long)kk); return MCGRA_ENOMEM; }
+  if (int rc = run.select(kk)) return rc;
+  const uint64_t r = run.h.remaining, g = kk - r;
+  k_topk_take<true><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, nullptr, run.m, run.tile, run.h.prefix, g, r, run.nb, run.off,
+                                                    scores, ld_scores, idx, rk, rp, run.state);
+  MCGRA_KERNEL_CHECK();
+  if (int rc = auc_sort(st, rk, tk, kk, run.cnt, run.off, rp, tp)) return rc;
+  const int gw = (int)std::min<uint64_t>(2048, (kk + AUC_THREADS - 1) / AUC_THREADS);
+  k_topk_write<<<gw, AUC_THREADS, 0, st>>>(kk, rp, scores, ld_scores, labels, ld_labels, idx, pairs, pair_scores, hits);
+  MCGRA_KERNEL_CHECK();
+  MCGRA_HIP(hipStreamSynchronize(st));      // the scratch is freed on return
+  return 0;
+}

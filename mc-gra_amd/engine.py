@@ -275,6 +275,56 @@ def average_precision(real, pred, idx=None):
     return _rank_metrics(real, pred, idx, False, True)[1]
 
 
+def _ratio(num, den):
+    return num / den if den else float("nan")
+
+
+@_on_operand_device
+def topk_metrics(real, pred, k=None, idx=None):
+    """The recovered graph in numbers (mcgra_topk_metrics): of the k best-scored unordered node pairs of pred within idx, how
+    many are edges of real.  The candidates are the pairs of positions a > b of idx (REPEAT-FREE node ids; None: all nodes in
+    order) with score pred[idx[a], idx[b]] and label real[idx[a], idx[b]] -- the strict lower triangle of the gathered
+    submatrix, also for an asymmetric pred -- ranked by score descending (float32 values, -0.0 == +0.0), ties by ascending
+    packed position a (a - 1) / 2 + b.  k None or 0: the true edge count among the candidates (then precision = recall = f1).
+    Returns {"k", "positives" (P), "hits" (TP), "pairs" (m), "precision" TP / k, "recall" TP / P, "f1" 2 TP / (k + P),
+    "threshold" (the k-th pair's score)}: exact integers, one float64 division each, NaN for a zero denominator (and for
+    the threshold when k = 0).  McgraError for k > m, a repeated or out-of-range id, a selected NaN / inf score or a selected
+    label other than 0 / 1."""
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
+    counts, thr = (C.c_int64 * 4)(), C.c_float(float("nan"))
+    check(lib.mcgra_topk_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
+                                 ix.numel() if ix is not None else n, int(k or 0), counts, C.byref(thr)))
+    kk, P, tp, m = (int(c) for c in counts)
+    return {"k": kk, "positives": P, "hits": tp, "pairs": m, "precision": _ratio(tp, kk), "recall": _ratio(tp, P),
+            "f1": _ratio(2 * tp, kk + P), "threshold": thr.value}
+
+
+@_on_operand_device
+def top_pairs(pred, k, idx=None, real=None):
+    """The recovered graph as an edge list (mcgra_top_pairs): (pairs [k, 2] int64, scores [k] float32), and hits [k] bool when
+    real is given -- the k best pairs of topk_metrics' ranking, best first (ties by ascending packed position), so the first
+    k' rows are the answer for k'.  pairs[i] = (idx[a], idx[b]), a > b; scores[i] = pred[pairs[i, 0], pairs[i, 1]], the bits as
+    stored; hits[i] = (real[pairs[i, 0], pairs[i, 1]] == 1).  Device tensors.  1 <= k <= m; refusals as topk_metrics."""
+    dev = pred.device
+    n = pred.shape[0]
+    assert pred.dim() == 2 and tuple(pred.shape) == (n, n), pred.shape
+    assert real is None or tuple(real.shape) == (n, n), (real.shape, pred.shape)
+    pred = _rows_f32(pred, dev)
+    real = None if real is None else _rows_f32(real, dev)
+    ix = _node_ids(idx, dev)
+    k = int(k)
+    pairs = torch.empty(max(k, 0), 2, device=dev, dtype=torch.int64)
+    scores = torch.empty(max(k, 0), device=dev, dtype=torch.float32)
+    hits = None if real is None else torch.empty(max(k, 0), device=dev, dtype=torch.uint8)
+    check(lib.mcgra_top_pairs(_stream(), n, _p(pred), pred.stride(0), _p(ix), ix.numel() if ix is not None else n, k,
+                              _p(real), real.stride(0) if real is not None else 0, _p(pairs), _p(scores), _p(hits)))
+    return (pairs, scores) if real is None else (pairs, scores, hits.view(torch.bool))
+
+
 def _decode_rank_metrics(real, Z, mode, idx, want_auc, want_ap):
     dev = real.device
     n = real.shape[0]

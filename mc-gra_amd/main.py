@@ -10,7 +10,13 @@ H_A / Y_A, run PGDAttack on the MI355X hot path, report the recovered-adjacency 
 writes the label adjacency under --saved_data) and --mode notrain_test (main.py:412-437: no attack; the AUC of each prior's
 own decode -- features, H_A1, H_A2, Y_A, label adjacency -- against the true graph, the three thin priors pair by pair on
 the GPU without an n x n score matrix).  --ap (not in the reference; off by default, and then nothing changes) adds the
-average precision of every ranking that is scored beside its AUC, from the same sort (engine.rank_metrics).  Not provided (each exits with a message naming the reference line): --mode
+average precision of every ranking that is scored beside its AUC, from the same sort (engine.rank_metrics).
+--topk K (not in the reference; --mode evaluate only; absent by default, and then nothing changes) reports the recovered
+graph itself: of the K best-scored unordered node pairs of modified_adj within each index set (attack, train, all), how many
+are true edges -- precision, recall and F1 at K (engine.topk_metrics; ties by packed position, so the answer is defined).
+K = 0 takes each set's own true edge count; a K above a set's pair count is clamped to it, and the printed k says so.
+--save_edges PATH (needs --topk) writes the whole-graph selection as an .npz of pairs, scores and hits in ranking order
+(engine.top_pairs).  Not provided (each exits with a message naming the reference line): --mode
 search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -50,9 +56,27 @@ import torch
 import torch.nn.functional as F
 
 
+def check_topk_args(args, fail):
+    """--topk / --save_edges against the rest of the command line; fail(message) does not return."""
+    topk, edges = getattr(args, "topk", None), getattr(args, "save_edges", None)
+    if edges and topk is None:
+        fail("--save_edges needs --topk")
+    if topk is not None and topk < 0:
+        fail("--topk takes K >= 0 (0: each index set's own true edge count)")
+    if topk is not None and args.mode != "evaluate":
+        fail(f"--topk scores the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, *a, **k):
+        args = super().parse_args(*a, **k)
+        check_topk_args(args, self.error)
+        return args
+
+
 def build_parser():
     """Same flags and defaults as main.py:78-137 (+ --dataset_root, --saved_data for file locations)."""
-    p = argparse.ArgumentParser()
+    p = _Parser()
     p.add_argument('--seed', type=int, default=15)
     p.add_argument('--epochs', type=int, default=100)
     p.add_argument('--lr', type=float, default=0.01)
@@ -88,6 +112,8 @@ def build_parser():
     p.add_argument('--saved_data', type=str, default='./saved_data')
     p.add_argument('--device', type=str, default='cuda:0')
     p.add_argument('--ap', action='store_true')     # also report average precision (engine.rank_metrics)
+    p.add_argument('--topk', type=int, default=None)        # also report the K best pairs' precision / recall / F1
+    p.add_argument('--save_edges', type=str, default=None)  # with --topk: the whole-graph edge list as an .npz
     return p
 
 
@@ -160,6 +186,27 @@ def prior_rank_metrics(adj, feature_adj, H_A1, H_A2, Y_A, label_adj, dataset):
     return {k: float(v[0]) for k, v in both.items()}, {k: float(v[1]) for k, v in both.items()}
 
 
+def topk_report(ori_adj, inference_adj, sets, K):
+    """--topk K: engine.topk_metrics of each index set of `sets` (name -> node ids, None: every node), K clamped to the
+    set's pair count (K = 0: the set's own true edge count).  Returns {"topk_<name>": dict}."""
+    real = ori_adj.to(inference_adj.device)
+    out = {}
+    for name, ix in sets.items():
+        rows = inference_adj.shape[0] if ix is None else len(ix)
+        out[f"topk_{name}"] = engine.topk_metrics(real, inference_adj, min(K, rows * (rows - 1) // 2), ix)
+    return out
+
+
+def save_edges(path, ori_adj, inference_adj, k):
+    """--save_edges: the k best pairs of the whole graph in ranking order (engine.top_pairs) as an .npz at exactly `path`."""
+    if k > 0:
+        pairs, scores, hits = (t.cpu().numpy() for t in engine.top_pairs(inference_adj, k, None, ori_adj.to(inference_adj.device)))
+    else:
+        pairs, scores, hits = np.zeros((0, 2), np.int64), np.zeros(0, np.float32), np.zeros(0, bool)
+    with open(path, "wb") as f:
+        np.savez(f, pairs=pairs, scores=scores, hits=hits)
+
+
 def victim_tensors(m):
     """Every parameter of a victim: the registered ones and those of the layers it keeps in plain lists (models/gcn.py:44,
     graphsage.py:50, gat.py:47 -- as the reference's classes do)."""
@@ -209,7 +256,12 @@ def run(args):
                 dist.destroy_process_group()
 
 
+def _exit(message):
+    raise SystemExit(message)
+
+
 def _run(args, rank, world):
+    check_topk_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -322,15 +374,24 @@ def _run(args, rank, world):
                "auc_train": float(metric_pool(ad, inference_adj, idx_train)),
                "auc_all": float(metric_pool(ad, inference_adj, None)),
                "density": float(inference_adj.mean())}
+    want_topk = getattr(args, "topk", None) is not None
+    if want_topk:           # every rank computes (as the AUCs); the keys exist only with the flag
+        res.update(topk_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, args.topk))
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
     print(f"current auc={res['auc_all']}")
     if want_ap:
         print(f"current ap={res['ap_all']}")
+    if want_topk:
+        print(f"current f1={res['topk_all']['f1']} (k={res['topk_all']['k']})")
+        if getattr(args, "save_edges", None):
+            save_edges(args.save_edges, ad, inference_adj, res["topk_all"]["k"])
     os.makedirs("./results/", exist_ok=True)
-    # the parameter line names --ap only when it is set: without it the log is what it was before the flag existed
-    shown = args if want_ap else argparse.Namespace(**{k: v for k, v in vars(args).items() if k != "ap"})
+    # the parameter line names --ap, --topk and --save_edges only when they are set: without them the log is what it was
+    # before the flags existed
+    hidden = (set() if want_ap else {"ap"}) | (set() if want_topk else {"topk", "save_edges"})
+    shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
     with open(os.path.join("./results", args.log_name), "a") as f:                         # main.py:314-323
         f.write(f"current parameter: {shown}\n")
         f.write(f"In attack graph: AUC={res['auc_attack']}\tIn train graph: AUC={res['auc_train']}\t"
@@ -338,6 +399,10 @@ def _run(args, rank, world):
         if want_ap:
             f.write(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
                     f"In Whole Graph: AP={res['ap_all']}\n")
+        if want_topk:
+            f.write("\t".join(f"In {name}: k={d['k']} P={d['precision']} R={d['recall']} F1={d['f1']}" for name, d in
+                              (("attack graph", res["topk_attack"]), ("train graph", res["topk_train"]),
+                               ("Whole Graph", res["topk_all"]))) + "\n")
         f.write(f"current density: {res['density']}\n")
     return res
 
