@@ -414,12 +414,24 @@ int mcgra_attack_product_mode(mcgra_attack_t* h);
 int mcgra_attack_path_stats(mcgra_attack_t* h, long long* lowrank_steps, long long* general_steps);
 /* How many of the low-rank steps ran as the fused step that evaluates every N x N quantity from the learnable
  * adjacency and n-vectors (attack_fused.hip: adj_norm, its centred copy, modified_adj1 and d loss / d adj_norm are
- * never stored).  Conditions: measure HSIC, ReLU GCN victim, eps == 0, the split product (n >= 1024 or
- * MCGRA_SPLIT_BF16=1/2/3), n >= 256, embedding width 8 / 16 / 32, summed layer widths <= 64; MCGRA_NO_FUSED_LR=1 (beside MCGRA_AB=1)
- * disables it.  Counted as well: the fused MSELoss step (calc = MSELoss: elementwise in the same per-pair quantities, no product) and
- * the fused KL step (calc = calc_kl, topology_attack.py:483-487: + per-row softmax statistics from one more per-pair pass) -- same
- * conditions on the victim, any n >= 256; they do not count as low-rank steps in mcgra_attack_path_stats. */
+ * never stored), the fused MSELoss step (calc = MSELoss: elementwise in the same per-pair quantities, no product) and the fused KL
+ * step (calc = calc_kl, topology_attack.py:483-487: + per-row softmax statistics from one more per-pair pass) included; those two do
+ * not count as low-rank steps in mcgra_attack_path_stats.  Which configurations take a fused step: mcgra_attack_plan, below. */
 long long mcgra_attack_fused_steps(mcgra_attack_t* h);
+/* What mcgra_attack_create decides for a configuration, from the configuration and the environment alone: no device is touched
+ * and none is needed (the rule itself: csrc/attack_plan.hip: plan_attack, which create runs first).  fused .. product_mode and
+ * text describe cfg as given; shardable / why answer whether a row-block rank (shard_world > 0) may run it, whatever
+ * shard_world / row_begin / row_end of cfg say.  Returns what mcgra_attack_create would return for the same cfg (the reason in
+ * mcgra_last_error), except that the refusal of a row-block rank shows in shardable / why only. */
+typedef struct mcgra_attack_plan {
+  int32_t fused;        /* 0 none, 1 the fused HSIC step, 2 MSELoss, 3 KL (mcgra_attack_fused_steps) */
+  int32_t lowrank;      /* the unfused low-rank step is available (mcgra_attack_path_stats) */
+  int32_t product_mode; /* as mcgra_attack_product_mode */
+  int32_t shardable;    /* create with shard_world > 0 would accept this configuration */
+  char why[256];        /* shardable == 0: the first term of the rule that fails */
+  char text[1024];      /* diagnostic: every create-time flag, one "name=value" per line */
+} mcgra_attack_plan_t;
+int mcgra_attack_plan(const mcgra_attack_config_t* cfg, mcgra_attack_plan_t* out);
 /* Fused steps whose decode relu-masked pairs (S_ij <= 0 off the diagonal) while every embedding row was alive: they stand.
  * With a ReLU embedding zn >= 0, so a masked pair has S_ij == 0 exactly: the value of modified_adj1 is still Z Z^T - D, and
  * what relu'(0) = 0 takes out of the decode backward is a multiple of zn_j on row i -- coordinates on which em_i is zero,

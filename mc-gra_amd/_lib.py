@@ -27,7 +27,7 @@ SYMBOLS = [
     "mcgra_dot_product_decode", "mcgra_dot_product_decode2", "mcgra_linear_hsic", "mcgra_hsic_regular", "mcgra_hsic_normalized", "mcgra_hsic_regular2", "mcgra_hsic_normalized_cca", "mcgra_distmat", "mcgra_mmd",
     "mcgra_mmd_pxpy_pxy", "mcgra_mse", "mcgra_mutual_information",
     "mcgra_gcn_forward",
-    "mcgra_attack_create", "mcgra_attack_destroy", "mcgra_attack_set_model", "mcgra_attack_set_graph",
+    "mcgra_attack_plan", "mcgra_attack_create", "mcgra_attack_destroy", "mcgra_attack_set_model", "mcgra_attack_set_graph",
     "mcgra_attack_set_adj_changes", "mcgra_attack_get_adj_changes", "mcgra_attack_step",
     "mcgra_attack_exchange_bytes", "mcgra_attack_bind_exchange", "mcgra_attack_shard_begin", "mcgra_attack_shard_next",
     "mcgra_attack_shard_scalars", "mcgra_attack_get_rows", "mcgra_attack_path_stats", "mcgra_attack_fused_steps", "mcgra_attack_gram_split_steps", "mcgra_attack_product_mode", "mcgra_ssymm_split_bf16", "mcgra_ssymm_split_f16", "mcgra_sgemm_skinny_x3",
@@ -53,6 +53,17 @@ class AttackConfig(C.Structure):
         ("act", C.c_int32), ("head_act", C.c_int32), ("has_self", C.c_int32), ("fin_layers", C.c_int32 * 2),
         ("shard_world", C.c_int32), ("shard_rows", C.c_int32),
     ]
+
+
+class AttackPlan(C.Structure):
+    """mcgra_attack_plan_t"""
+    _fields_ = [("fused", C.c_int32), ("lowrank", C.c_int32), ("product_mode", C.c_int32), ("shardable", C.c_int32),
+                ("why", C.c_char * 256), ("text", C.c_char * 1024)]
+
+    def flags(self):
+        """`text` as a dict: every create-time flag as an int (off, wdt: lists of ints)."""
+        kv = dict(line.split("=") for line in self.text.decode().splitlines())
+        return {k: [int(x) for x in v.split(",")] if k in ("off", "wdt") else int(v) for k, v in kv.items()}
 
 
 class Exchange(C.Structure):
@@ -112,6 +123,7 @@ def _load():
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],
+        "mcgra_attack_plan": [C.POINTER(AttackConfig), C.POINTER(AttackPlan)],
         "mcgra_attack_create": [C.POINTER(C.c_void_p), C.POINTER(AttackConfig)],
         "mcgra_attack_destroy": [vp],
         "mcgra_attack_set_model": [vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), fp, fp, C.POINTER(C.c_void_p)],

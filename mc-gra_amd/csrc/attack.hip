@@ -183,92 +183,60 @@ int mcgra_device_count(void) {
   return c;
 }
 
-// The A/B switches of the parity suite and of the measurements under profiles/  are honoured only when
-// MCGRA_AB=1 is set beside them: a variable left in the environment of a real run changes nothing -- and says so once.
-static const char* ab_env(const char* name) {
-  const char* v = getenv(name);
-  if (!v) return nullptr;
-  const char* on = getenv("MCGRA_AB");
-  if (on && on[0] == '1') return v;
-  // (said once per variable and process, not once per engine)
-  static std::mutex mu;
-  static std::vector<std::string> said;
-  std::lock_guard<std::mutex> lock(mu);
-  for (const std::string& s : said) if (s == name) return nullptr;
-  said.emplace_back(name);
-  fprintf(stderr, "[mcgra] %s=%s is ignored: A/B switches are honoured only under MCGRA_AB=1\n", name, v);
-  return nullptr;
+// The handle's working copies of what create planned.  A non-zero ori_adj takes the general path only: the fused / low-rank
+// forms assume modified_adj == M and modified_adj1 == offdiag relu(Zn Zn^T), and the monitoring forward (:290-293) runs on
+// the UNclamped M + ori, so there is nothing for the next step to adopt; a later graph without one has the planned paths again.
+static void apply_plan(mcgra_attack* h, bool has_ori) {
+  const AttackPlan& p = h->plan;
+  h->act = h->cfg.act; h->head_act = h->cfg.head_act; h->has_self = h->cfg.has_self;
+  h->fin0 = p.fin0; h->fin1 = p.fin1;
+  h->n = h->cfg.n; h->ld = p.ld; h->L = p.L; h->Le = p.Le; h->C = p.C; h->na = p.na; h->hsum = p.hsum; h->hmax = p.hmax;
+  for (int l = 0; l <= MCGRA_MAX_LAYERS; ++l) { h->off[l] = p.off[l]; h->wdt[l] = p.wdt[l]; }
+  h->keep_gsym = p.keep_gsym; h->testing = p.testing; h->fuse_tail = p.fuse_tail;
+  h->lr_ldv = p.lr_ldv;
+  h->split_on = p.split_on; h->split_planes = p.split_planes; h->split_single = p.split_single; h->split_mode = p.split_mode;
+  h->overlap = p.overlap; h->gram_ovl = p.gram_ovl; h->kx_early_on = p.kx_early_on; h->small_side_on = p.small_side_on;
+  h->fused_mse = p.fused == FUSED_MSE || p.fused == FUSED_KL;      // ("an elementwise measure": every branch of the MSELoss step that is not MSELoss' own arithmetic)
+  h->fused_kl = p.fused == FUSED_KL;
+  h->fcols = p.fcols;
+  h->fused_post = p.fused_post; h->early_pack_on = p.early_pack_on; h->early_p1_on = p.early_p1_on; h->early_tail_on = p.early_tail_on;
+  h->mse_decode_side = p.mse_decode_side; h->mse_small_inline = p.mse_small_inline;
+  h->fwd_x3 = p.fwd_x3; h->p1_behind_pack_on = p.p1_behind_pack_on;
+  h->sharded = p.sharded; h->world = p.world; h->rank = p.rank; h->rpr = p.rpr; h->npad = p.npad; h->row0 = p.row0; h->row1 = p.row1;
+  h->sgw = p.sgw; h->fyw = p.fyw; h->a2a_overlap = p.a2a_overlap;
+  h->has_ori = has_ori;
+  h->lr_ok = p.lr_ok && !has_ori;
+  h->fused_ok = p.fused != FUSED_NONE && !has_ori;
+  h->gram_split = p.gram_split && !has_ori;
+  h->late_mean = p.late_mean && !has_ori;
+  h->planes_mm_on = p.planes_mm_on && !has_ori;
+  h->fwd_reuse = p.fwd_reuse && !has_ori;
 }
 
+// the engine's own events (all without timing)
+static hipEvent_t mcgra_attack::* const ENGINE_EVENTS[] = {
+    &mcgra_attack::ev_fork4, &mcgra_attack::ev_join4, &mcgra_attack::ev_fork,  &mcgra_attack::ev_join,  &mcgra_attack::ev_first,
+    &mcgra_attack::ev_second, &mcgra_attack::ev_r,    &mcgra_attack::ev_pack,  &mcgra_attack::ev_fork3, &mcgra_attack::ev_join3};
+
+// plan (attack_plan.hip: every decision, no device), then allocate what the plan asks for, then streams and events
 int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) {
   if (!out || !cfg) { set_error("null argument"); return MCGRA_EINVAL; }
-  if (cfg->n < 2 || cfg->nlayer < 2 || cfg->nlayer > MCGRA_MAX_LAYERS || cfg->emb_nlayer < 1 ||
-      cfg->emb_nlayer > cfg->nlayer || cfg->nclass < 1 || cfg->n_attack < 1) {
-    set_error("bad config: n=%d nlayer=%d emb_nlayer=%d nclass=%d n_attack=%d", cfg->n, cfg->nlayer, cfg->emb_nlayer,
-              cfg->nclass, cfg->n_attack);
-    return MCGRA_EINVAL;
-  }
-  if (cfg->measure < MCGRA_MEASURE_HSIC || cfg->measure > MCGRA_MEASURE_KDE) {
-    set_error("measure %d: HSIC, MSELoss, KL, CKA, DP, KDE (topology_attack.py:194-208)", cfg->measure);
-    return MCGRA_ENOSUP;
-  }
-  if (cfg->measure == MCGRA_MEASURE_KDE && (cfg->dims[cfg->emb_nlayer] > KDE_MAXC || cfg->nclass > KDE_MAXC)) {
-    set_error("measure KDE: embedding width %d / %d classes; the c x c joint of utils.MutualInformation is built for widths <= %d",
-              cfg->dims[cfg->emb_nlayer], cfg->nclass, KDE_MAXC);
-    return MCGRA_ENOSUP;
-  }
-  if (cfg->shard_world < 0 || (cfg->shard_world == 0 && (cfg->row_begin != 0 || (cfg->row_end != 0 && cfg->row_end < cfg->n)))) {
-    set_error("row block [%d, %d) without shard_world", cfg->row_begin, cfg->row_end);
-    return MCGRA_EINVAL;
-  }
-  if (cfg->shard_world > 0) {
-    const int rpr = cfg->shard_rows;
-    if (rpr < 256 || rpr % 256 != 0 || (long long)rpr * cfg->shard_world < cfg->n || cfg->row_begin % rpr != 0 ||
-        cfg->row_begin / rpr >= cfg->shard_world ||
-        cfg->row_end != (cfg->row_begin + rpr < cfg->n ? cfg->row_begin + rpr : (cfg->row_begin < cfg->n ? cfg->n : cfg->row_begin))) {
-      set_error("row block [%d, %d) is not rank %d's block of %d x %d rows (shard_rows: a multiple of 256 with shard_rows * "
-                "shard_world >= n)", cfg->row_begin, cfg->row_end, rpr > 0 ? cfg->row_begin / rpr : -1, cfg->shard_world, rpr);
-      return MCGRA_EINVAL;
-    }
-  }
+  AttackPlan plan;
+  CHK(plan_attack(*cfg, read_plan_env(), &plan));
   mcgra_attack* h = new mcgra_attack();
   h->cfg = *cfg;
-  h->act = cfg->act; h->head_act = cfg->head_act; h->has_self = cfg->has_self;
-  h->fin0 = cfg->fin_layers[0] > 0 ? cfg->fin_layers[0] : 1;
-  h->fin1 = cfg->fin_layers[1] > 0 ? cfg->fin_layers[1] : 2;
-  if (h->fin0 > cfg->nlayer || h->fin1 > cfg->nlayer || cfg->act < 0 || cfg->act > 1) {
-    delete h; set_error("bad act / fin_layers"); return MCGRA_EINVAL;
-  }
-  h->n = cfg->n;
-  // rows of the N x N buffers start on 128-byte lines (ld a multiple of 32 floats; round 3: of 4): the 64- and 128-column
-  // tile rows of the tail, the pack and the skinny products are then whole lines (+1 ... 2 % steps/s at N = 10 000, where
-  // ld = 10 016; profiles/r04_ab_edge_tiles_ld_align.txt).
-  h->ld = (cfg->n + 31) & ~31;
-  h->L = cfg->nlayer;
-  h->Le = cfg->emb_nlayer;
-  h->C = cfg->nclass;
-  h->na = cfg->n_attack;
-  int o = 0, hm = cfg->nclass;
-  for (int l = 0; l < h->L; ++l) {
-    h->off[l] = o;
-    h->wdt[l] = cfg->dims[l + 1];
-    if (h->wdt[l] < 1) { delete h; set_error("bad dims[%d]", l + 1); return MCGRA_EINVAL; }
-    o += (h->wdt[l] + 3) & ~3;
-    if (h->wdt[l] > hm) hm = h->wdt[l];
-  }
-  h->hsum = o;
-  h->hmax = (hm + 3) & ~3;
+  h->plan = plan;
+  apply_plan(h, false);
+  const AttackPlan& p = h->plan;
   const size_t n = h->n, ld = h->ld, nn = n * ld;
+  const int he = h->wdt[h->Le - 1];
+  const bool hsic = cfg->measure == MCGRA_MEASURE_HSIC, cka = cfg->measure == MCGRA_MEASURE_CKA;
   int rc = 0;
-#define A_(p, cnt) if (!rc) rc = dalloc(h, &h->p, (cnt))
+#define A_(f, cnt) if (!rc) rc = dalloc(h, &h->f, (cnt))
   A_(M, nn); A_(am, nn); A_(av, nn); A_(ADJN, nn); A_(A1, nn); A_(G_ADJN, nn); A_(G_A1, nn); A_(G_A, nn);
   A_(KX, nn); A_(FADJ, nn);
-  { const char* e = ab_env("MCGRA_KEEP_GSYM"); h->keep_gsym = e && e[0] == '1'; }
-  { const char* e = getenv("MCGRA_TESTING"); h->testing = e && e[0] == '1'; }
-  if (h->keep_gsym) { A_(GSYM, nn); }
-  if (cfg->measure == MCGRA_MEASURE_HSIC || cfg->measure == MCGRA_MEASURE_CKA) {
-    A_(KY, nn); A_(KFC, nn); A_(XC, nn); A_(YC, nn);
-  }
+  if (p.keep_gsym) { A_(GSYM, nn); }
+  if (hsic || cka) { A_(KY, nn); A_(KFC, nn); A_(XC, nn); A_(YC, nn); }
   if (cfg->measure == MCGRA_MEASURE_KL) { A_(XC, nn); }      // XC holds softmax(feature_adj) rows
   if (cfg->measure == MCGRA_MEASURE_DP) { A_(KY, nn); A_(XC, nn); }
   if (cfg->measure == MCGRA_MEASURE_KDE) { A_(kde, kde_scratch_doubles((int)n)); }
@@ -294,214 +262,39 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
   const size_t am_ = (size_t)h->na * h->hmax;
   A_(HA, nm); A_(YA, nc); A_(HAg, am_); A_(HAc, am_); A_(YAg, am_); A_(YAc, am_); A_(Yg, am_); A_(Gg, am_);
   if (cfg->eps != 0.f) { A_(Abuf, nn); A_(gate, nn); A_(colpart_d, (size_t)h->nstrips * ld); }
-  { const char* e = ab_env("MCGRA_NO_FWD_REUSE"); h->fwd_reuse = cfg->eps == 0.f && !(e && e[0] == '1'); }
-  { const char* e = ab_env("MCGRA_NO_FUSED_TAIL"); h->fuse_tail = !(e && e[0] == '1'); }
-  if (h->fwd_reuse) { A_(ADJN_next, nn); }
+  if (p.fwd_reuse) { A_(ADJN_next, nn); }
   A_(cm_part, (size_t)64 * 256);      // column-sum partials of launch_colmean_center (small-operand terms)
-  if (cfg->measure == MCGRA_MEASURE_HSIC) { A_(Yg8, am_); }
+  if (hsic) { A_(Yg8, am_); }
   A_(Q, (size_t)h->hmax * h->hmax); A_(Q2, (size_t)h->hmax * h->hmax); A_(Gg2, am_); A_(coef, 16); A_(cst, 8);
-  {
-    const char* e = ab_env("MCGRA_NO_LOWRANK");
-    const int he = h->wdt[h->Le - 1];
-    h->lr_ok = cfg->measure == MCGRA_MEASURE_HSIC && h->act == 0 && he <= 32 && !(e && e[0] == '1');
-    if (h->lr_ok) {
-      h->lr_ldv = (2 * he + 1 + 3) & ~3;
-      A_(lrL, n * 2 * he); A_(lrR, n * 2 * he); A_(lrQ, n * 2 * he); A_(lrV, n * (size_t)h->lr_ldv);
-      A_(lrT, n * (size_t)h->lr_ldv); A_(lrDelta, ld); A_(lrC, ld); A_(lrStats, lr_stats_doubles(he)); A_(lrRs, ld); A_(lrQtZ, lr_qtz_doubles(he));
-    }
-    A_(nmask, 4);
-    // The one N x N x N product of a low-rank step.  Default for n >= 1024: the 2-plane fp16 split on the 16-bit matrix
-    // cores (split_symm_bf16.hip: fp32-level error, three plane products).  MCGRA_SPLIT_BF16=0: fp32 MFMA SYMM;
-    // =2: the 3-plane bf16 split kernel (six products, fp32 exponent range) at any size; =3: the 2-plane fp16
-    // kernel at any size.
-    const char* es = getenv("MCGRA_SPLIT_BF16");
-    const char auto_mode[2] = {n >= 1024 ? '3' : '0', 0};
-    if (!es || !es[0]) es = auto_mode;
-    h->split_single = es[0] == '1';      // (by name only: also the Gram evaluation's four products, below)
-    // =1: the fp16 x 2 operands, ONE plane product (fp16 accuracy: 2^-11 per operand; a third of the matrix-core work) -- what "bf16 MFMA"
-    // in BASELINE.json's configs[2] / [4] means taken literally.  Never a default: the reference's CPU path is fp32.
-    if (!rc && h->lr_ok && cfg->eps == 0.f && es && (es[0] == '1' || es[0] == '2' || es[0] == '3')) {
-      h->split_planes = es[0] == '2' ? 3 : 2;
-      h->split_single = es[0] == '1';
-      A_(Apack, split3_pack_bytes((int)n, h->split_planes)); A_(Bpack, split3_pack_bytes((int)n, h->split_planes));
-      A_(amax, 16);
-      h->split_on = (rc == 0);
-      h->split_mode = 2;
-    }
-    // The Gram evaluation of HSIC (steps the low-rank forms do not cover: a masked decode, GAT / SAGE chains,
-    // MCGRA_NO_LOWRANK) through the 2-plane fp16 kernel as well: Kx = Xc Xc^T and Ky = Yc Yc^T as full matrices, then
-    // G_adjn += Ky' Xc and G_A1 += Kx' Yc -- four products of 2 n^3 instead of 3 n^3 MACs of fp32 SYMM at a third of
-    // their rate.  MCGRA_GRAM_SPLIT=0: fp32 path.
-    const char* eg_ = ab_env("MCGRA_GRAM_SPLIT");
-    const bool gram_auto = (es[0] == '3' || es[0] == '1') && !(eg_ && eg_[0] == '0');      // (the Gram evaluation's products stay 3-product splits under =1)
-    if (!rc && (cfg->measure == MCGRA_MEASURE_HSIC || cfg->measure == MCGRA_MEASURE_CKA) && cfg->eps == 0.f && gram_auto) {
-      if (!h->split_on) { h->split_planes = 2; A_(Bpack, split3_pack_bytes((int)n, 2)); A_(amax, 16); }
-      if (h->split_planes == 2) {
-        const size_t pb = split3_pack_bytes((int)n, 2);
-        A_(Gp0, pb); A_(Gp1, pb); A_(Gp2, pb);
-        h->gram_split = (rc == 0);
-      }
-    }
-    // The product on the engine's own stream, beside the HBM-bound kernels of the step that do not need it.  On by
-    // default with the 2-plane fp16 kernel (64 KB of LDS and 212 VGPRs per CU leave room for them: 9.1 vs 9.4 ms per
-    // step at N = 10 000 although the product itself slows from 4.8 to 5.6 ms); the fp32 SYMM and the 3-plane kernel
-    // hold every CU's LDS and registers, so what runs beside them crawls and slows them by about as much as it hides
-    // (measured: 21.2-21.5 ms with the side stream, 21.6 without).  MCGRA_OVERLAP=0 / 1 overrides.
-    const char* eo = ab_env("MCGRA_OVERLAP");
-    h->overlap = (eo && eo[0]) ? eo[0] == '1' : (h->split_mode == 2 && h->split_planes == 2);
-    if (h->gram_split) { A_(gram_diag, 2 * ld); }
-    // (the fused MSELoss step -- attack_fused.hip -- uses the side streams of the small-operand terms and of the decode too)
-    const bool mse_fusable = (cfg->measure == MCGRA_MEASURE_MSE || cfg->measure == MCGRA_MEASURE_KL) && cfg->eps == 0.f && !h->has_self &&
-                             h->act == 0 && h->head_act == 0;      // (and the fused KL step)
-    if (!rc && (h->lr_ok || h->gram_split || mse_fusable)) {
-      int pr_least = 0, pr_greatest = 0;
-      (void)hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
-      // The two side streams are shared by all engines of a device in this process: a process has few hardware queues
-      // (four by default), and engines beyond the first would otherwise multiplex their side streams onto the ones in
-      // use (measured: a second live engine's Cora-size step went from 0.63 to 2.4 ms).  Engines of one process run
-      // one after another, so sharing only adds ordering that is there anyway.
-      static hipStream_t side2[64] = {nullptr}, side3[64] = {nullptr}, side4[64] = {nullptr};
-      static std::mutex side_mu;                        // creation from several host threads (include/mcgra.h: "Threads")
-      std::lock_guard<std::mutex> side_lock(side_mu);
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      if (dev < 0 || dev >= 64) dev = 0;
-      // the product's stream: normal priority (A/B at N = 10 000, same box: low 153.8, normal 154.8, high 154.4 steps/s;
-      // round 1's fp32 SYMM, which left no room beside itself, wanted the lowest)
-      const int pr2 = (pr_least + pr_greatest) / 2;
-      if (!side2[dev] && hipStreamCreateWithPriority(&side2[dev], hipStreamNonBlocking, pr2) != hipSuccess) side2[dev] = nullptr;
-      if (!side3[dev] && hipStreamCreateWithFlags(&side3[dev], hipStreamNonBlocking) != hipSuccess) side3[dev] = nullptr;
-      if (!side4[dev] && hipStreamCreateWithFlags(&side4[dev], hipStreamNonBlocking) != hipSuccess) side4[dev] = nullptr;
-      h->st2 = side2[dev]; h->st3 = side3[dev]; h->st4 = side4[dev];
-      if (!h->st2 || !h->st3 || !h->st4 ||
-          hipEventCreateWithFlags(&h->ev_fork4, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_join4, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_first, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_second, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_r, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_pack, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_fork3, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming) != hipSuccess ||
-          hipHostMalloc((void**)&h->mask_host, 8, hipHostMallocMapped) != hipSuccess ||
-          hipHostGetDevicePointer((void**)&h->mask_host_dev, (void*)h->mask_host, 0) != hipSuccess) {
-        set_error("stream / event creation failed"); rc = MCGRA_EHIP;
-      }
-      if (h->mask_host) { h->mask_host[0] = 0u; h->mask_host[1] = 0u; }
-      // Gram evaluation: its four products on the side stream, beside the HBM-bound rest of the step (gram_eval).
-      // MCGRA_GRAM_OVERLAP=0: everything on the caller's stream, same launches in the same order (bit-identical: A/B test)
-      { const char* eg2 = ab_env("MCGRA_GRAM_OVERLAP"); h->gram_ovl = h->gram_split && !rc && !(eg2 && eg2[0] == '0'); }
-      // ... and the first of them forked by the monitoring forward (configurations without a low-rank form; MCGRA_GRAM_KX_EARLY=0: by the step)
-      { const char* ek = ab_env("MCGRA_GRAM_KX_EARLY"); h->kx_early_on = h->gram_ovl && !h->lr_ok && h->fwd_reuse && !(ek && ek[0] == '0'); }
-      // (KDE: its small-operand terms share one scratch table with the N x N terms -- they stay on the caller's stream)
-      { const char* es3 = ab_env("MCGRA_SMALL_SIDE"); h->small_side_on = !rc && cfg->measure != MCGRA_MEASURE_KDE && !(es3 && es3[0] == '0'); }
-    }
+  if (p.lr_ok) {
+    A_(lrL, n * 2 * he); A_(lrR, n * 2 * he); A_(lrQ, n * 2 * he); A_(lrV, n * (size_t)h->lr_ldv);
+    A_(lrT, n * (size_t)h->lr_ldv); A_(lrDelta, ld); A_(lrC, ld); A_(lrStats, lr_stats_doubles(he)); A_(lrRs, ld); A_(lrQtZ, lr_qtz_doubles(he));
   }
-  {
-    // The fused low-rank step (attack_fused.hip): HSIC with a ReLU GCN embedding, eps == 0, the split product, widths
-    // that fit the 64-column skinny products and the rank-k panels of the tail.  MCGRA_NO_FUSED_LR=1: general path only.
-    const char* e = ab_env("MCGRA_NO_FUSED_LR");
-    const int he = h->wdt[h->Le - 1];
-    int fc = 2 * he + 1 + h->wdt[h->L - 1];
-    for (int l = 0; l < h->L; ++l) fc = (2 * h->wdt[l] + 1) > fc ? 2 * h->wdt[l] + 1 : fc;
-    if (cfg->measure == MCGRA_MEASURE_MSE || cfg->measure == MCGRA_MEASURE_KL) {      // the fused MSELoss / KL step: no means column, no low-rank factors -- [r o Tv | Tu] only
-      fc = 0;
-      for (int l = 0; l < h->L; ++l) fc = 2 * h->wdt[l] > fc ? 2 * h->wdt[l] : fc;
-    }
-    fc = (fc + 3) & ~3;
-    const int kmax = h->hsum > 2 * he ? h->hsum : 2 * he;
-    h->fused_ok = !rc && !(e && e[0] == '1') && cfg->measure == MCGRA_MEASURE_HSIC && h->lr_ok && cfg->eps == 0.f &&
-                  !h->has_self && h->act == 0 && h->head_act == 0 && h->split_on && h->split_mode == 2 &&
-                  lr_decode_supported(he) && fl_tail_supported((int)n, (int)ld, kmax) && fc <= 64 &&
-                  (cfg->w[0] != 0.f || cfg->w[1] != 0.f);
-    // The fused MSELoss step (round 5): calc = MSELoss is elementwise in (M, feature_adj, r, Zn), so the same two tail passes
-    // over tile pairs serve it with no N x N x N product and no N x N intermediate (adj_norm, modified_adj1, the gradients
-    // w.r.t. them are never stored) -- and a row-block rank needs no N x N exchange at all.  Any n >= 256.
-    h->fused_mse = !rc && !(e && e[0] == '1') && cfg->measure == MCGRA_MEASURE_MSE && cfg->eps == 0.f && !h->has_self &&
-                   h->act == 0 && h->head_act == 0 && lr_decode_supported(he) && fl_tail_supported((int)n, (int)ld, kmax) && fc <= 64 &&
-                   h->st3 != nullptr;
-    if (h->fused_mse) h->fused_ok = true;
-    // The fused KL step (round 6): calc = calc_kl (:197-198, :483-487) is elementwise in the same quantities plus per-row softmax
-    // statistics of adj_norm and modified_adj1 -- the MSELoss step's data flow with one more per-pair pass for the statistics
-    // (attack_fused.hip).  softmax(feature_adj) (XC, constant per graph) takes feature_adj's place in the tail.
-    h->fused_kl = !rc && !(e && e[0] == '1') && cfg->measure == MCGRA_MEASURE_KL && cfg->eps == 0.f && !h->has_self &&
-                  h->act == 0 && h->head_act == 0 && lr_decode_supported(he) && fl_tail_supported((int)n, (int)ld, kmax) && fc <= 64 &&
-                  h->st3 != nullptr;
-    if (h->fused_kl) { h->fused_ok = true; h->fused_mse = true; }      // (fused_mse: "an elementwise measure" -- every branch of the MSELoss step that is not MSELoss' own arithmetic)
-    h->row0 = 0; h->row1 = (int)n;
-    { const char* ef = ab_env("MCGRA_NO_FUSED_POST"); h->fused_post = !(ef && ef[0] == '1'); }
-    { const char* ee = ab_env("MCGRA_EARLY_PACK"); h->early_pack_on = !(ee && ee[0] == '0'); }
-    { const char* ee = ab_env("MCGRA_EARLY_P1"); h->early_p1_on = cfg->shard_world > 0 && !(ee && ee[0] == '0'); }
-    { const char* ee = ab_env("MCGRA_EARLY_TAIL"); h->early_tail_on = !(ee && ee[0] == '0'); }
-    { const char* ee = ab_env("MCGRA_MSE_DECODE_SIDE"); h->mse_decode_side = ee && ee[0] == '1'; }
-    { const char* ee = ab_env("MCGRA_MSE_SMALL_INLINE"); h->mse_small_inline = !(ee && ee[0] == '0'); }
-    h->late_mean = h->fused_ok && !h->fused_mse && cfg->shard_world == 0;
-    {
-      const char* ep = ab_env("MCGRA_PLANES_MM");
-      // default from n = 8192: on smaller graphs the step is bound by its chain of launches, and the two extra launches per
-      // product (magnitude + pack of the right-hand side) cost more than the matrix-pipe time they free (Cora-shape step
-      // 0.51 -> 0.56 ms, N = 4096 0.86 -> 0.92 ms with it); MCGRA_PLANES_MM=1 forces it on (tests), =0 off
-      const bool want_pm = (ep && ep[0]) ? ep[0] == '1' : n >= 8192;
-      h->planes_mm_on = h->late_mean && h->split_planes == 2 && planes_mm_supported((int)n, 32) && want_pm;
-      if (h->planes_mm_on) { A_(pm_scratch, planes_mm_scratch_bytes((int)n)); }
-    }
-    {
-      // The forward of a step whose planes the early pack makes on the product's stream (attack_fused.hip) needs nothing the
-      // product reads or writes, so the product is forked behind the pack and the forward runs beside it -- on skinny_x3.hip,
-      // whose blocks fit beside a product block, not on gemm_f32, whose blocks do not.  Default from n = 8192, where the
-      // product is long enough to hide the forward; MCGRA_FWD_X3 / MCGRA_P1_BEHIND_PACK = 0 / 1 force each part (A/B).
-      const bool can = h->late_mean && h->overlap && h->early_pack_on && h->split_planes == 2;
-      const char* ex = ab_env("MCGRA_FWD_X3");
-      const char* eb = ab_env("MCGRA_P1_BEHIND_PACK");
-      int wf = 0;      // (the forward's widest product: [r o Tv_l | Tu_l])
-      for (int l = 0; l < h->L; ++l) wf = 2 * h->wdt[l] > wf ? 2 * h->wdt[l] : wf;
-      h->fwd_x3 = can && ((ex && ex[0]) ? ex[0] == '1' : n >= 8192) && skinny_x3_supported((int)n, wf, (int)ld);
-      h->p1_behind_pack_on = can && ((eb && eb[0]) ? eb[0] == '1' : h->fwd_x3);
-      if (h->fwd_x3) { A_(sx_scratch, skinny_x3_scratch_bytes((int)n)); }
-    }
-    if (cfg->shard_world > 0) {
-      // row-block rank: only the fused step is sharded, and the host-driven bisection of the projection is not
-      if (!h->fused_ok || cfg->num_edges < 0.5 * (double)n * (double)n) {
-        if (!rc) {
-          set_error("shard_world > 0 needs a configuration a fused step covers (HSIC: ReLU GCN victim, eps == 0, n >= 1024 or "
-                    "MCGRA_SPLIT_BF16=2/3, widths <= 32; MSELoss, KL: ReLU GCN victim, eps == 0, n >= 256, widths <= 32) and a projection "
-                    "budget that cannot bind");
-          rc = MCGRA_ENOSUP;
-        }
-      } else {
-        h->sharded = true;
-        h->world = cfg->shard_world; h->rpr = cfg->shard_rows; h->rank = cfg->row_begin / cfg->shard_rows;
-        h->npad = h->rpr * h->world;
-        h->row0 = cfg->row_begin; h->row1 = cfg->row_end;
-        // exchanged node arrays (attack_fused.hip: wide_stage / narrow_stage): n-vector columns (decode backward | |xc_i|^2 as
-        // two words) + a two-column scalar lane; the wide one carries a product's fcols columns in front of them
-        h->sgw = ((he + 2 + 3) & ~3) + 2;
-        h->fyw = fc + h->sgw;
-        // the all-to-all of P1 beside the own row panels of the product (attack_fused.hip): free when a whole round of the chip
-        // ends behind the peers' tiles, worth a second ragged round while world <= 4 (world 8 at N = 10 000: 200 tiles on 256
-        // CUs, nothing to run beside)
-        { const char* ee = ab_env("MCGRA_A2A_OVERLAP"); h->a2a_overlap = ee ? (ee[0] == '1' ? 2 : 0) : (h->world >= 2 ? 1 : 0); }
-      }
-    }
-    if (h->fused_ok && !rc) {
-      h->fcols = fc;
-      A_(FV, n * (size_t)fc); A_(em_last, nm); A_(fstat, 256 + fl_wcolsum_scratch_doubles());
-      if (!h->sharded) { A_(FY, n * (size_t)fc); }      // a row-block rank keeps FY in the exchange arena
-      A_(rkbuf, fl_tail_pack_bytes((int)n));           // packed fp16 planes of the tail's rank-k panels
-      A_(Zpair, (n + 2) * (size_t)h->hmax);
-      // (a row-block rank cuts the columns of its rows' decode into up to 64 slices: fused_lowrank.hip: fl_decode_slabs)
-      A_(ws_dec, (size_t)((h->sharded || h->fused_mse) ? 64 : lr_decode_slabs((int)n)) * n * he);      // (MSELoss: up to 64 slices too, nothing runs beside its decode)
-      if (h->fused_kl) { A_(klA, ld); A_(kl1, ld); A_(klv, ld); A_(klvsum, ld); A_(klpart, (size_t)64 * n * 2); }
-      h->fused_ok = (rc == 0);
-    }
+  A_(nmask, 4);
+  // packed planes of the split products: the low-rank step's (Apack: H Kf H, per graph; Bpack: Xc) and the Gram evaluation's
+  if (p.split_on) { A_(Apack, split3_pack_bytes((int)n, p.split_planes)); }
+  if (p.split_on || p.gram_split) { A_(Bpack, split3_pack_bytes((int)n, p.split_planes)); A_(amax, 16); }
+  if (p.gram_split) {
+    const size_t pb = split3_pack_bytes((int)n, 2);
+    A_(Gp0, pb); A_(Gp1, pb); A_(Gp2, pb); A_(gram_diag, 2 * ld);
   }
-  if (!rc && (h->split_on || h->gram_split)) {      // a small graph's split products: room to cut them along K (its N x N buffers are too small)
+  if (p.planes_mm_on) { A_(pm_scratch, planes_mm_scratch_bytes((int)n)); }
+  if (p.fwd_x3) { A_(sx_scratch, skinny_x3_scratch_bytes((int)n)); }
+  if (p.fused) {
+    const size_t fc = (size_t)p.fcols;
+    A_(FV, n * fc); A_(em_last, nm); A_(fstat, 256 + fl_wcolsum_scratch_doubles());
+    if (!p.sharded) { A_(FY, n * fc); }      // a row-block rank keeps FY in the exchange arena
+    A_(rkbuf, fl_tail_pack_bytes((int)n));           // packed fp16 planes of the tail's rank-k panels
+    A_(Zpair, (n + 2) * (size_t)h->hmax);
+    // (a row-block rank cuts the columns of its rows' decode into up to 64 slices: fused_lowrank.hip: fl_decode_slabs)
+    A_(ws_dec, (size_t)((p.sharded || p.fused != FUSED_HSIC) ? 64 : lr_decode_slabs((int)n)) * n * he);      // (MSELoss, KL: up to 64 slices too, nothing runs beside their decode)
+    if (p.fused == FUSED_KL) { A_(klA, ld); A_(kl1, ld); A_(klv, ld); A_(klvsum, ld); A_(klpart, (size_t)64 * n * 2); }
+  }
+  if (p.split_on || p.gram_split) {      // a small graph's split products: room to cut them along K (its N x N buffers are too small)
     const size_t want = split3_small_slab_bytes((int)n);
-    if (want > sizeof(float) * (size_t)n * h->ld) {
-      h->small_slab_bytes = want;
+    if (want > sizeof(float) * nn) {
       A_(small_slab, want / sizeof(float));
-      if (rc) { h->small_slab = nullptr; h->small_slab_bytes = 0; }
+      if (!rc) h->small_slab_bytes = want;
     }
   }
   h->ws_bytes = (size_t)64 * n * 64 * sizeof(float);
@@ -509,6 +302,35 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
   h->ws_small_bytes = (size_t)64 * (h->na > h->hmax ? h->na : h->hmax) * h->hmax * sizeof(float);
   A_(ws_small, h->ws_small_bytes / sizeof(float));
 #undef A_
+  if (!rc && p.side_streams) {
+    int pr_least = 0, pr_greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
+    // The side streams are shared by all engines of a device in this process: a process has few hardware queues
+    // (four by default), and engines beyond the first would otherwise multiplex their side streams onto the ones in
+    // use (measured: a second live engine's Cora-size step went from 0.63 to 2.4 ms).  Engines of one process run
+    // one after another, so sharing only adds ordering that is there anyway.
+    static hipStream_t side2[64] = {nullptr}, side3[64] = {nullptr}, side4[64] = {nullptr};
+    static std::mutex side_mu;                        // creation from several host threads (include/mcgra.h: "Threads")
+    std::lock_guard<std::mutex> side_lock(side_mu);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64) dev = 0;
+    // the product's stream: normal priority (A/B at N = 10 000, same box: low 153.8, normal 154.8, high 154.4 steps/s;
+    // round 1's fp32 SYMM, which left no room beside itself, wanted the lowest)
+    const int pr2 = (pr_least + pr_greatest) / 2;
+    if (!side2[dev] && hipStreamCreateWithPriority(&side2[dev], hipStreamNonBlocking, pr2) != hipSuccess) side2[dev] = nullptr;
+    if (!side3[dev] && hipStreamCreateWithFlags(&side3[dev], hipStreamNonBlocking) != hipSuccess) side3[dev] = nullptr;
+    if (!side4[dev] && hipStreamCreateWithFlags(&side4[dev], hipStreamNonBlocking) != hipSuccess) side4[dev] = nullptr;
+    h->st2 = side2[dev]; h->st3 = side3[dev]; h->st4 = side4[dev];
+    bool ok = h->st2 && h->st3 && h->st4;
+    for (auto ev : ENGINE_EVENTS) ok = ok && hipEventCreateWithFlags(&(h->*ev), hipEventDisableTiming) == hipSuccess;
+    // (the fused step's masked-pair count is posted to mapped host memory: engine.h: mask_host)
+    if (!ok || hipHostMalloc((void**)&h->mask_host, 8, hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&h->mask_host_dev, (void*)h->mask_host, 0) != hipSuccess) {
+      set_error("stream / event creation failed"); rc = MCGRA_EHIP;
+    }
+    if (h->mask_host) { h->mask_host[0] = 0u; h->mask_host[1] = 0u; }
+  }
   // the zero fills of dalloc ran on the null stream: order them in front of whatever stream the caller uses next
   if (!rc && hipDeviceSynchronize() != hipSuccess) { set_error("hipDeviceSynchronize failed after allocation"); rc = MCGRA_EHIP; }
   if (rc) { mcgra_attack_destroy(h); return rc; }
@@ -520,19 +342,8 @@ int mcgra_attack_destroy(mcgra_attack_t* h) {
   if (!h) return 0;
   for (void* p : h->allocs) (void)hipFree(p);
   for (hipEvent_t e : h->timer.ev) (void)hipEventDestroy(e);
-  if (h->st2) (void)hipStreamSynchronize(h->st2);      // (shared side streams: drained, not destroyed)
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->ev_first) (void)hipEventDestroy(h->ev_first);
-  if (h->ev_second) (void)hipEventDestroy(h->ev_second);
-  if (h->st3) (void)hipStreamSynchronize(h->st3);
-  if (h->st4) (void)hipStreamSynchronize(h->st4);
-  if (h->ev_fork4) (void)hipEventDestroy(h->ev_fork4);
-  if (h->ev_join4) (void)hipEventDestroy(h->ev_join4);
-  if (h->ev_r) (void)hipEventDestroy(h->ev_r);
-  if (h->ev_pack) (void)hipEventDestroy(h->ev_pack);
-  if (h->ev_fork3) (void)hipEventDestroy(h->ev_fork3);
-  if (h->ev_join3) (void)hipEventDestroy(h->ev_join3);
+  for (hipStream_t st : {h->st2, h->st3, h->st4}) if (st) (void)hipStreamSynchronize(st);      // (shared side streams: drained, not destroyed)
+  for (auto ev : ENGINE_EVENTS) if (h->*ev) (void)hipEventDestroy(h->*ev);
   if (h->mask_host) (void)hipHostFree((void*)h->mask_host);
   delete h;
   return 0;
@@ -566,7 +377,7 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
   CHK(drop_early_p1(h, st));
   const int n = h->n, ld = h->ld, hs = h->hsum;
   if (ori_adj) {
-    // general path only: the fused / low-rank forms assume modified_adj == M and modified_adj1 == offdiag relu(Zn Zn^T)
+    // (general path only: apply_plan)
     if (h->sharded) { set_error("a non-zero ori_adj is not supported on a row-block rank"); return MCGRA_ENOSUP; }
     const size_t nn = (size_t)n * ld, nh = (size_t)n * hs;
     int rc = 0;
@@ -576,21 +387,8 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
 #undef A1_
     if (rc) return rc;
     MCGRA_HIP(hipMemcpy2DAsync(h->ORI, (size_t)ld * 4, ori_adj, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
-    if (!h->has_ori) {             // what create decided, for a later set_graph without ori_adj
-      h->lr_ok0 = h->lr_ok; h->fused_ok0 = h->fused_ok; h->gram_split0 = h->gram_split; h->fwd_reuse0 = h->fwd_reuse;
-      h->late_mean0 = h->late_mean; h->planes_mm_on0 = h->planes_mm_on;
-    }
-    h->has_ori = true;
-    h->lr_ok = h->fused_ok = h->gram_split = false;
-    h->late_mean = h->planes_mm_on = false;
-    h->fwd_reuse = false;          // the monitoring forward (:290-293) runs on the UNclamped M + ori: nothing to adopt
-  } else {
-    if (h->has_ori) {              // back to a zero ori_adj on the same handle: the create-time paths again
-      h->lr_ok = h->lr_ok0; h->fused_ok = h->fused_ok0; h->gram_split = h->gram_split0; h->fwd_reuse = h->fwd_reuse0;
-      h->late_mean = h->late_mean0; h->planes_mm_on = h->planes_mm_on0;
-    }
-    h->has_ori = false;
   }
+  apply_plan(h, ori_adj != nullptr);
   h->fused_fwd_valid = h->fwd_cached = h->prep_valid = h->planes_valid = false;      // (a new graph: nothing of the old one to adopt)
   MCGRA_HIP(hipMemcpy2DAsync(h->FADJ, (size_t)ld * 4, feature_adj, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipMemcpyAsync(h->labels, labels, sizeof(int) * n, hipMemcpyDeviceToDevice, st));

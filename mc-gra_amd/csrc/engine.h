@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mcgra.h"
+#include "attack_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -28,6 +29,7 @@ struct GemmTimer {
 
 struct mcgra_attack {
   mcgra_attack_config_t cfg;
+  mcgra::AttackPlan plan;          // what create decided (attack_plan.h), never written again; apply_plan copies it into the fields below
   int n = 0, ld = 0, L = 0, Le = 0, C = 0, na = 0, hsum = 0, hmax = 0;
   int off[MCGRA_MAX_LAYERS + 1];   // column offset of layer l inside the concatenated node buffers
   int wdt[MCGRA_MAX_LAYERS + 1];   // width of layer l output (dims[l+1])
@@ -174,8 +176,6 @@ struct mcgra_attack {
   bool fused_kl = false;           // ... as the fused KL step (calc = calc_kl: the MSELoss step's data flow + per-row softmax statistics)
   float *klA = 0, *kl1 = 0, *klv = 0;      // fused KL step: logsumexp of adj_norm's rows, of modified_adj1's rows, v_i = the row's share of c2
   double *klpart = 0, *klvsum = 0;         // ... per-(column slice, row) partials of the two passes [64][n][2]; v_i in fp64 [ld]
-  // create-time values of the path switches a non-zero ori_adj turns off (set_graph restores them when ori_adj goes away)
-  bool lr_ok0 = false, fused_ok0 = false, gram_split0 = false, fwd_reuse0 = false, late_mean0 = false, planes_mm_on0 = false;
   bool fused_fwd_valid = false;    // both chains, heads, d / r / mean of the CURRENT M are in place (left by the monitor call)
   bool fused_last = false;         // the last step ran fused: adj_norm of that iteration was never stored (see em_last)
   int fcols = 0;                   // leading dimension of FV / FY

@@ -379,6 +379,42 @@ def gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=0):
 
 
 # ---------------------------------------------------------------- the engine
+def attack_config(n, dims, nclass, emb_nlayer, measure, weight_sup, weight_param, lr, num_edges, n_attack, eps=0.0,
+                  act="relu", head_act="none", has_self=False, fin_layers=(1, 2), plan=None):
+    """mcgra_attack_config_t of these arguments (AttackEngine's, without the device)."""
+    dims = [int(d) for d in dims]
+    cfg = AttackConfig()
+    cfg.n, cfg.nfeat, cfg.nclass = int(n), dims[0], int(nclass)
+    cfg.nlayer, cfg.emb_nlayer = len(dims) - 1, int(emb_nlayer)
+    for i, d in enumerate(dims):
+        cfg.dims[i] = d
+    if measure not in _lib.MEASURES:
+        raise ValueError(f"measure {measure!r}: topology_attack.py:194-208 knows {sorted(_lib.MEASURES)}")
+    cfg.measure = _lib.MEASURES[measure]
+    cfg.n_attack = int(n_attack)
+    cfg.weight_sup = float(weight_sup)
+    for i in range(10):
+        cfg.w[i] = float(weight_param[i])
+    cfg.lr, cfg.eps = float(lr), float(eps)
+    cfg.num_edges = float(min(num_edges, 1e300))
+    # plan: a sharded.RowBlockPlan makes this engine one of plan.world row-block ranks (include/mcgra.h)
+    cfg.row_begin, cfg.row_end = (0, cfg.n) if plan is None else (int(plan.row_begin), int(plan.row_end))
+    cfg.shard_world, cfg.shard_rows = (0, 0) if plan is None else (int(plan.world), int(plan.rows_per_rank))
+    cfg.act = {"relu": 0, "elu": 1}[act]
+    cfg.head_act = {"none": 0, "elu": 1}[head_act]
+    cfg.has_self = int(bool(has_self))
+    cfg.fin_layers[0], cfg.fin_layers[1] = int(fin_layers[0]), int(fin_layers[1])
+    return cfg
+
+
+def attack_plan(cfg):
+    """What mcgra_attack_create would decide for this AttackConfig in this environment (mcgra_attack_plan): needs no device.
+    Returns the _lib.AttackPlan (.flags(): its diagnostic text as a dict)."""
+    out = _lib.AttackPlan()
+    check(lib.mcgra_attack_plan(C.byref(cfg), C.byref(out)))
+    return out
+
+
 class AttackEngine:
     """One mcgra_attack_t.  Mirrors the state PGDAttack keeps across the loop of
     topology_attack.py:161-298 (adj_changes + Adam moments) in HBM."""
@@ -389,27 +425,8 @@ class AttackEngine:
         _lib.require_device()
         self.device = torch.device(device)
         self.n, self.nclass, self.dims = int(n), int(nclass), list(int(d) for d in dims)
-        cfg = AttackConfig()
-        cfg.n, cfg.nfeat, cfg.nclass = self.n, self.dims[0], self.nclass
-        cfg.nlayer, cfg.emb_nlayer = len(self.dims) - 1, int(emb_nlayer)
-        for i, d in enumerate(self.dims):
-            cfg.dims[i] = d
-        if measure not in _lib.MEASURES:
-            raise ValueError(f"measure {measure!r}: topology_attack.py:194-208 knows {sorted(_lib.MEASURES)}")
-        cfg.measure = _lib.MEASURES[measure]
-        cfg.n_attack = int(n_attack)
-        cfg.weight_sup = float(weight_sup)
-        for i in range(10):
-            cfg.w[i] = float(weight_param[i])
-        cfg.lr, cfg.eps = float(lr), float(eps)
-        cfg.num_edges = float(min(num_edges, 1e300))
-        # plan: a sharded.RowBlockPlan makes this engine one of plan.world row-block ranks (include/mcgra.h)
-        cfg.row_begin, cfg.row_end = (0, self.n) if plan is None else (int(plan.row_begin), int(plan.row_end))
-        cfg.shard_world, cfg.shard_rows = (0, 0) if plan is None else (int(plan.world), int(plan.rows_per_rank))
-        cfg.act = {"relu": 0, "elu": 1}[act]
-        cfg.head_act = {"none": 0, "elu": 1}[head_act]
-        cfg.has_self = int(bool(has_self))
-        cfg.fin_layers[0], cfg.fin_layers[1] = int(fin_layers[0]), int(fin_layers[1])
+        cfg = attack_config(n, dims, nclass, emb_nlayer, measure, weight_sup, weight_param, lr, num_edges, n_attack, eps, act,
+                            head_act, has_self, fin_layers, plan)
         self._h = C.c_void_p(0)
         with torch.cuda.device(self.device):
             check(lib.mcgra_attack_create(C.byref(self._h), C.byref(cfg)))

@@ -14,11 +14,10 @@ from victim_model.gc).
 
 Several GPUs: when ``torch.distributed`` is initialised with more than one rank (``torchrun ... main.py``: one process
 per GPU, backend "nccl" = RCCL), ``attack`` runs ONE attack row-block sharded over the ranks (mc-gra_amd/sharded.py,
-DESIGN.md section 6) whenever the configuration is one a fused step covers (measure HSIC -- n >= 1024, w1 or w2 non-zero -- or
-MSELoss -- n >= 256 --, ReLU GCN victim, eps == 0, ori_adj == 0, hidden widths <= 32, a projection budget that cannot bind); every
-rank returns the same ``modified_adj``.  Any other configuration says on stderr that it runs replicated.
+DESIGN.md section 6) whenever the configuration is one the engine accepts on a row-block rank (``mcgra_attack_plan``: a fused HSIC,
+MSELoss or KL step and a projection budget that cannot bind) with loss_type 'CE' and ori_adj == 0; every rank returns the same
+``modified_adj``.  Any other configuration says on stderr that it runs replicated, and why.
 """
-import os
 import sys
 
 import numpy as np
@@ -27,7 +26,7 @@ import torch
 
 from .base_attack import BaseAttack
 from ._lib import McgraNotSupported
-from .engine import AttackEngine
+from .engine import AttackEngine, attack_config, attack_plan
 
 # dot_product_decode2 branch -> mcgra_attack_finalize decode_mode (topology_attack.py:421-467)
 def _decode_mode(args):
@@ -174,48 +173,20 @@ class PGDAttack(BaseAttack):
     @staticmethod
     def _replicated_reason(measure, eps, ori_np, Ws, act, head_act, loss_type, n, dims, w1, w2, num_edges, emb_nlayer=None):
         """None when the row-block sharded fused step covers this configuration (include/mcgra.h: mcgra_attack_shard_*),
-        else why it does not.  Mirrors the create-time rule of csrc/attack.hip (`fused_ok` / `fused_mse` / `fused_kl` under
-        shard_world > 0) term by term: a configuration this accepts and mcgra_attack_create refuses would fail on every rank
-        instead of running replicated (attack() also catches that refusal, should the two ever drift apart)."""
-        if measure not in ("HSIC", "MSELoss", "KL"):
-            return f"measure {measure} (the fused HSIC, MSELoss and KL steps are the sharded ones)"
+        else why it does not: the engine's own create-time rule (mcgra_attack_plan: no device needed), and the two terms
+        that are not part of an engine's configuration."""
         if loss_type != "CE":
             return "loss_type 'CW' takes no step"
-        if eps != 0:
-            return "eps != 0 (adding_noise makes modified_adj asymmetric: general step)"
         if ori_np is not None:
             return "a non-zero ori_adj (general step)"
-        if Ws is not None or act != "relu" or head_act != "none":
-            return "a GAT / GraphSAGE victim (Gram evaluation of linear_HSIC)"
-        split = os.environ.get("MCGRA_SPLIT_BF16", "")
-        if measure == "HSIC" and split == "0":
-            return "MCGRA_SPLIT_BF16=0 (the product runs on the fp32 kernel: nothing to shard)"
-        if measure == "HSIC" and n < 1024 and split not in ("2", "3"):
-            return f"n = {n} < 1024 (the product runs on the fp32 kernel: nothing to shard)"
-        if n < 256:
-            return f"n = {n} < 256"
-        widths = [int(w) for w in dims[1:]]
-        le = min(2, len(widths)) if emb_nlayer is None else int(emb_nlayer)
-        he = widths[le - 1]
-        if max(widths) > 32:
-            return f"hidden width {max(widths)} > 32"
-        if he not in (8, 16, 32):                                  # lr_decode_supported: the per-pair decode's register tiles
-            return f"embedding width {he} (the per-pair decode is built for widths 8, 16 and 32)"
-        hsum = sum((w + 3) & ~3 for w in widths)                   # the concatenated node buffers: rank-k depth of the tail
-        if max(hsum, 2 * he) > 64:                                 # fl_tail_supported: kmax <= 64
-            return (f"summed layer widths {hsum} / twice the embedding width {2 * he} > 64 (rank-k depth of the tail's "
-                    f"panels: e.g. more than four 16-wide layers)")
-        if measure == "HSIC":
-            fc = max([2 * he + 1 + widths[-1]] + [2 * w + 1 for w in widths])
-        else:
-            fc = max(2 * w for w in widths)
-        if ((fc + 3) & ~3) > 64:
-            return f"skinny products of {fc} columns > 64"
-        if measure == "HSIC" and w1 == 0 and w2 == 0:
-            return "w1 == w2 == 0 (no N x N HSIC term)"
-        if num_edges < 0.5 * float(n) * float(n):
-            return "a projection budget that can bind (host-driven bisection)"
-        return None
+        le = min(2, len(dims) - 1) if emb_nlayer is None else int(emb_nlayer)
+        cfg = attack_config(n, dims, 1, le, measure, 0.0, (w1, w2) + (0,) * 8, 0.0, num_edges, 1, eps=eps, act=act,
+                            head_act=head_act, has_self=Ws is not None)
+        try:
+            plan = attack_plan(cfg)
+        except McgraNotSupported as e:                              # (what create refuses outright)
+            return str(e)
+        return None if plan.shardable else plan.why.decode()
 
     def test(self, idx_attack, idx_val, idx_test, adj, features, labels, victim_model):
         """topology_attack.py:83-93 through mcgra_gcn_forward / mcgra_normalize_adj."""
@@ -329,7 +300,8 @@ class PGDAttack(BaseAttack):
         try:
             eng = mk(plan)
         except McgraNotSupported as e:
-            # the create-time rule decides the same way on every rank (configuration only): all of them fall back together
+            # (the rule was asked above; a refusal for a reason outside the configuration is the same on every rank: all of them
+            #  fall back together)
             if plan is None:
                 raise
             if rank == 0:

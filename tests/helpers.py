@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 os.environ.setdefault("MCGRA_KEEP_GSYM", "1")     # the parity tests read each step's mirrored gradient ("G_sym")
-os.environ.setdefault("MCGRA_AB", "1")            # ... and the engine honours such switches only beside MCGRA_AB=1 (attack.hip: ab_env)
+os.environ.setdefault("MCGRA_AB", "1")            # ... and the engine honours such switches only beside MCGRA_AB=1 (attack_plan.hip: ab_env)
 
 from oracle import mcgra_oracle as O
 
@@ -588,6 +588,53 @@ def projection_oracle_pre(n, measure, ori):
     orc.step()
     a0 = a0_of(z)
     return a0, pre_projection_state(a0, O.pack_tril(orc.adam.m), O.pack_tril(orc.adam.v), 1, float(z["lr"]))
+
+
+# ---------------------------------------------------------------- the sharding rule, stated independently of the engine
+def shard_rule(measure, eps, ori_np, Ws, act, head_act, loss_type, n, dims, w1, w2, num_edges, emb_nlayer=None, projection=True):
+    """None when a row-block rank may run this configuration (include/mcgra.h: mcgra_attack_shard_*: a fused step covers it and
+    the projection budget cannot bind), else why not.  The suite's own statement of the engine's documented create-time rule
+    (csrc/attack_plan.hip: plan_attack decides; PGDAttack._replicated_reason asks it): the two are compared, never derived from
+    one another.  projection=False: the rule of the fused step alone."""
+    if measure not in ("HSIC", "MSELoss", "KL"):
+        return f"measure {measure} (the fused HSIC, MSELoss and KL steps are the sharded ones)"
+    if loss_type != "CE":
+        return "loss_type 'CW' takes no step"
+    if eps != 0:
+        return "eps != 0 (adding_noise makes modified_adj asymmetric: general step)"
+    if ori_np is not None:
+        return "a non-zero ori_adj (general step)"
+    if Ws is not None or act != "relu" or head_act != "none":
+        return "a GAT / GraphSAGE victim (Gram evaluation of linear_HSIC)"
+    split = os.environ.get("MCGRA_SPLIT_BF16", "")[:1]            # (the first character decides; 1, 2 and 3 are the split modes)
+    if measure == "HSIC" and split not in ("", "1", "2", "3"):
+        return f"MCGRA_SPLIT_BF16={split} (the product runs on the fp32 kernel: nothing to shard)"
+    if measure == "HSIC" and n < 1024 and split == "":
+        return f"n = {n} < 1024 (the product runs on the fp32 kernel: nothing to shard)"
+    if n < 256:
+        return f"n = {n} < 256"
+    widths = [int(w) for w in dims[1:]]
+    le = min(2, len(widths)) if emb_nlayer is None else int(emb_nlayer)
+    he = widths[le - 1]
+    if max(widths) > 32:
+        return f"hidden width {max(widths)} > 32"
+    if he not in (8, 16, 32):                                  # lr_decode_supported: the per-pair decode's register tiles
+        return f"embedding width {he} (the per-pair decode is built for widths 8, 16 and 32)"
+    hsum = sum((w + 3) & ~3 for w in widths)                   # the concatenated node buffers: rank-k depth of the tail
+    if max(hsum, 2 * he) > 64:                                 # fl_tail_supported: kmax <= 64
+        return (f"summed layer widths {hsum} / twice the embedding width {2 * he} > 64 (rank-k depth of the tail's "
+                f"panels: e.g. more than four 16-wide layers)")
+    if measure == "HSIC":
+        fc = max([2 * he + 1 + widths[-1]] + [2 * w + 1 for w in widths])
+    else:
+        fc = max(2 * w for w in widths)
+    if ((fc + 3) & ~3) > 64:
+        return f"skinny products of {fc} columns > 64"
+    if measure == "HSIC" and w1 == 0 and w2 == 0:
+        return "w1 == w2 == 0 (no N x N HSIC term)"
+    if projection and num_edges < 0.5 * float(n) * float(n):
+        return "a projection budget that can bind (host-driven bisection)"
+    return None
 
 
 # ---------------------------------------------------------------- GPU-side helpers

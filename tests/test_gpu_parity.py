@@ -886,7 +886,7 @@ def test_row_block_forward_forks_the_next_products_and_a_product_nobody_takes_is
 
 def test_ab_switches_are_ignored_without_MCGRA_AB(pkg, monkeypatch, capfd):
     """A variable left in the environment of a real run changes nothing: the engine reads its A/B switches only beside
-    MCGRA_AB=1 (attack.hip: ab_env) and says on stderr what it ignored.  MCGRA_NO_FUSED_LR=1 would send every step through the
+    MCGRA_AB=1 (attack_plan.hip: ab_env) and says on stderr what it ignored.  MCGRA_NO_FUSED_LR=1 would send every step through the
     general path, MCGRA_KEEP_GSYM=1 would keep the mirrored gradient."""
     z = _synthetic_case(1100, 11, (16, 16), 4, seed=3)
     monkeypatch.delenv("MCGRA_AB", raising=False)

@@ -141,19 +141,17 @@ def grad_bound(st, measure, term):
 
 
 def expected_path(z, path, n_steps):
-    """What fused_steps() / path_stats() / product_mode() must say, from PGDAttack._replicated_reason (the Python mirror of the
-    engine's create-time rule) and the conditions documented at mcgra_attack_fused_steps / mcgra_attack_product_mode
-    (include/mcgra.h): a fused step when the mirror accepts the configuration; else, for HSIC with an N x N term, the unfused
-    low-rank step on a ReLU chain whose embedding is at most 32 wide and the Gram evaluation otherwise; the fused MSELoss / KL
-    steps are no low-rank steps."""
-    from mc_gra_amd import topology_attack as TA
+    """What fused_steps() / path_stats() / product_mode() must say, from helpers.shard_rule (the suite's own statement of the
+    engine's create-time rule; not PGDAttack._replicated_reason, which asks the engine) and the conditions documented at
+    mcgra_attack_path_stats / mcgra_attack_product_mode (include/mcgra.h): a fused step when the rule accepts the configuration;
+    else, for HSIC with an N x N term, the unfused low-rank step on a ReLU chain whose embedding is at most 32 wide and the Gram
+    evaluation otherwise; the fused MSELoss / KL steps are no low-rank steps."""
     cfg, w = H.cfg_from(z), H.weights_from(z)
     n = z["adj"].shape[0]
     dims = [w.W[0].shape[0]] + [x.shape[1] for x in w.W]
     ori = z["ori_adj"] if "ori_adj" in z and np.any(z["ori_adj"]) else None
     w1, w2 = cfg.weight_param[0], cfg.weight_param[1]
-    why = TA.PGDAttack._replicated_reason(cfg.measure, cfg.eps, ori, w.Ws, w.act, w.head_act, "CE", n, dims, w1, w2,
-                                          cfg.num_edges, cfg.emb_nlayer)
+    why = H.shard_rule(cfg.measure, cfg.eps, ori, w.Ws, w.act, w.head_act, "CE", n, dims, w1, w2, cfg.num_edges, cfg.emb_nlayer)
     fused = why is None and path in ("fused", "ranks2")
     he = dims[cfg.emb_nlayer]
     lowrank = general = 0
@@ -282,7 +280,7 @@ def test_victim_shapes_match_the_float64_oracle(pkg, monkeypatch, spec, term, pa
     the create-time switches of the node kernels that carry the small terms -- odd widths, nfeat = 1, one class, 32 / 33 classes,
     fc = 64 / 65, he = 8 / 32, summed widths 64 / 72, emb_nlayer = 1 and 3, and the 32-column rounds of the general tail's rank-k
     update (32 / 36 / 64 / 68 / 128 / 132 columns).  path "fused" is the engine's default: the step the create-time rule picks,
-    which expected_path() takes from PGDAttack._replicated_reason and asserts with fused_steps() / path_stats() / product_mode();
+    which expected_path() takes from helpers.shard_rule and asserts with fused_steps() / path_stats() / product_mode();
     "general" is MCGRA_NO_FUSED_LR=1.  One class makes the c10 gradient exactly zero: asserted as exact zeros (under HSIC the
     gradient is then the tiny N x N contribution alone, compared as usual)."""
     check_term(pkg, monkeypatch, spec, term, path)
