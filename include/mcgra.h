@@ -371,8 +371,9 @@ int mcgra_attack_step(mcgra_attack_t* h, void* stream, const float* noise,
  *   The elementwise measures have no product and no low-rank factors: measure MSELoss exchanges 2 L + 2 all-gathers per step and
  *   no N x N data; measure KL (round 6) 2 L + 3 -- one more gather, of the rows' softmax statistics [logsumexp(adj_norm_i) |
  *   logsumexp(modified_adj1_i)], which the decode backward and the tail need of EVERY row.
- * The engine runs until the next exchange point and describes the collective; the host layer (mc-gra_amd/sharded.py)
- * executes it with torch.distributed (backend "nccl" = RCCL) on views of ONE caller-owned device arena:
+ * The step is an ordered table of stages (csrc/attack_fused.hip: FS_STAGES, its forward FW_STAGES); a stage that ends at an
+ * exchange describes the collective, mcgra_attack_shard_next returns there and the next call goes on with the next stage.  The
+ * host layer (mc-gra_amd/sharded.py) executes it with torch.distributed (backend "nccl" = RCCL) on views of ONE caller-owned device arena:
  *     mcgra_attack_bind_exchange(h, arena, mcgra_attack_exchange_bytes(h));
  *     mcgra_attack_shard_begin(h, stream, MCGRA_SHARD_STEP, want_scalars);
  *     while (mcgra_attack_shard_next(h, stream, &ex) == 0 && ex.kind != MCGRA_XCHG_DONE)  run_collective(ex);

@@ -575,8 +575,7 @@ int forward_common(mcgra_attack* h, hipStream_t st, float* adjn_out, const float
   if (!general && h->prep_valid) {
     // d, r and the norm / sparsity sums from the row sums the Adam pass left behind: no pass over M
     const size_t cnt = (size_t)n * rankk_apply_adam_tiles(n);
-    prep_from_partials(st, n, h->G_A, reinterpret_cast<const double*>(h->G_A + ((cnt + 1) & ~(size_t)1)), h->d, h->r, h->rowsq,
-                       h->rowsum);
+    prep_from_partials(st, n, h->G_A, adam_row_sums(h, cnt), h->d, h->r, h->rowsq, h->rowsum);
   } else
   launch_prep(st, general, n, ld, h->M, h->has_ori ? h->ORI : nullptr, noise, h->cfg.eps, h->Abuf, h->gate, h->d, h->r, h->rowsq, h->rowsum);
   launch_reduce_rows(st, h->rowsq, n, 1, h->scal + S_SQ);
@@ -1264,11 +1263,11 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
     launch_normbwd(st, n, ld, h->G_ADJN, s.A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
     // (its row sums of the new M go to G_A, which this path leaves unused; not with a projection still to come)
     const size_t cnt = (size_t)n * rankk_apply_adam_tiles(n);
-    const bool emit = !may_project && !s.gen && 3 * cnt + 4 <= (size_t)n * ld;
+    const bool emit = !s.gen && adam_emits_partials(h, may_project, cnt);
     MCGRA_HIP(rankk_apply_adam(st, n, ld, hs, h->GPu, hs, h->Tu, hs, h->G_ADJN, h->r, h->gd, s.gate, h->M, h->am, h->av, h->mm + 2,
                                (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
                                h->keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
-                               emit ? reinterpret_cast<double*>(h->G_A + ((cnt + 1) & ~(size_t)1)) : nullptr));
+                               emit ? adam_row_sums(h, cnt) : nullptr));
     h->prep_valid = emit;
     adam_done = true;
   } else if (rankk_nt_supported(n, n, hs, 0) && !h->has_ori) {

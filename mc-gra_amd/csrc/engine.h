@@ -209,12 +209,33 @@ struct mcgra_attack {
   float *SG = 0, *A2S = 0, *A2R = 0, *NXS = 0;   // views into the arena: n-vector stage [npad][sgw], all-to-all send / recv, N x N stage
   double* SC = 0;                  // 16 scalars summed over the ranks (from the stages' scalar lanes)
   int sgw = 0, fyw = 0;            // row widths (floats, even) of the narrow / wide exchanged node arrays
-  // resumable step (protothread state: the step runs to the next exchange point and returns)
-  int fs_state = 0, fw_state = 0, fs_l = 0, fs_l2 = 0, fs_what = 0, fs_want = 0, fs_np = 0, fs_nblk = 0;
-  bool fs_active = false, fs_adopted = false, fs_dec_forked = false;
+  // The fused step as a table of stages (attack_fused.hip: FS_STAGES, and FW_STAGES for its forward): a row-block rank runs it
+  // to the next exchange point and returns.  The step's constants are rebuilt on every entry (FusedStep); only these cross an
+  // exchange:
+  int fs_state = 0, fw_state = 0;  // index of the next stage of the step / of the forward (0: from the top)
+  int fs_what = 0, fs_want = 0;    // what mcgra_attack_shard_begin asked for: MCGRA_SHARD_*; scalars (2: already collected)
+  bool fs_active = false;          // between shard_begin and the last shard_next
   bool fs_open = false;            // a fused step was started and has not reached a regular exit (see fused_resync)
+  // ... and the stages' own counters and flags:
+  bool fs_adopted = false;         // fs_begin: the step took the forward a monitor call left (fs_forward then passes)
+  int fs_l = 0;                    // fw_layer_product / fw_layer_post: the forward's layer; fs_decode_bwd, fs_bwd_product / fs_bwd_post:
+  int fs_l2 = 0;                   //   the backward levels still to do, victim chain | modified_adj chain; fs_gather_*: the gather (fs_l)
+  int fs_np = 0;                   // fs_decode: row partials of the decode's entropy term
+  int fs_nblk = 0;                 // fs_tail_reduce: blocks of the tail's first pass (partials of the loss terms' values)
+  bool fs_dec_forked = false;      // fs_decode: the decode runs on the fourth stream; its first reader joins it (fs_small_terms, fs_decode_bwd)
   double fs_scalars[10] = {0};
 };
+
+// ---- scratch layouts the fused and the general step share
+// The operand pack's per-block row partials in A1: sums of squares [n][np], and behind them (16-byte aligned) the row sums [n][np]
+static inline float* pack_row_sums(const mcgra_attack* h, int np) { return h->A1 + (((size_t)h->n * np + 3) & ~(size_t)3); }
+// The row partials of the new M an Adam pass leaves in G_A for the next forward (prep_from_partials): cnt = n * tiles floats,
+// and behind them (8-byte aligned) as many fp64 row sums ...
+static inline double* adam_row_sums(const mcgra_attack* h, size_t cnt) { return reinterpret_cast<double*>(h->G_A + ((cnt + 1) & ~(size_t)1)); }
+// ... which it emits when no projection follows and they fit into G_A.  prep_valid says the same: ONE predicate for both.
+static inline bool adam_emits_partials(const mcgra_attack* h, bool may_project, size_t cnt) {
+  return !may_project && 3 * cnt + 4 <= (size_t)h->n * h->ld;
+}
 
 // attack_fused.hip
 bool fused_step_possible(const mcgra_attack* h);

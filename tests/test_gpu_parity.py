@@ -829,6 +829,99 @@ def test_sharded_ranks_hand_masked_steps_to_the_general_path(pkg, monkeypatch):
     assert torch.equal(_gather_rows(bks), mono.buffer("M"))
 
 
+def _record_exchanges(bks, he=16):
+    """Wraps every backend's next() so that each exchange is noted as the NAME of the arena region it moves, by the layout of
+    mcgra_attack_bind_exchange: [FY npad x fyw | SG npad x sgw | SC 16 doubles | A2A send | A2A receive | NXN npad x ld], every
+    region rounded up to 256 bytes.  sgw comes from the embedding width he (attack_plan.hip); the wide array's width is not
+    visible from here, so SG's offset is what the other regions leave of exchange_bytes().  Returns the shared log."""
+    from mc_gra_amd import sharded as S
+    up = lambda x: (x + 255) // 256 * 256
+    p = bks[0].plan
+    n, w, rpr, npad = p.n, p.world, p.rows_per_rank, p.n_pad
+    ld = (n + 31) & ~31          # the engine's leading dimension of M (attack_plan.hip)
+    sgw = ((he + 2 + 3) & ~3) + 2
+    a2a, nxn = up(w * rpr * rpr * 4), up(npad * ld * 4)
+    sg = bks[0].eng.exchange_bytes() - up(npad * sgw * 4) - up(16 * 8) - 2 * a2a - nxn
+    a2s = sg + up(npad * sgw * 4) + up(16 * 8)
+    assert sg > 0 and sg % 256 == 0
+    names = {(S.XCHG_ALLGATHER, 0): "FY", (S.XCHG_ALLGATHER, sg): "SG", (S.XCHG_ALLTOALL, a2s): "A2A",
+             (S.XCHG_ALLGATHER, a2s + 2 * a2a): "NXN"}
+    chunks = {"SG": rpr * sgw * 4, "A2A": rpr * rpr * 4, "NXN": rpr * ld * 4}
+    log = [[] for _ in bks]
+    for b, mine in zip(bks, log):
+        def next_(inner=b.next, mine=mine):
+            ex = inner()
+            kind, count, off, off2, chunk = ex
+            if kind != S.XCHG_DONE:
+                name = names[(kind, off)]
+                assert chunk == chunks.get(name, chunk) and (off2 == a2s + a2a if name == "A2A" else off2 == 0), ex
+                mine.append(name)
+            return ex
+        b.next = next_
+    return log
+
+
+def _exchanges_of(log):
+    assert all(l == log[0] for l in log), log
+    out = list(log[0])
+    for l in log:
+        del l[:]
+    return out
+
+
+# The exchanges of a row-block rank's step at L = 2 GCN layers, read off the step as it stood BEFORE it became a table of stages
+# (attack_fused.hip at 4af8849: the FS_XCHG points of fused_forward_pt | fused_step_pt in program order, with their guards):
+#   forward   [r | d] -> SG; one product per layer -> FY, FY
+#   HSIC      (use2) the product for T with the decode's rows -> FY; the product for Q -> FY; L - 1 backward levels -> FY;
+#             (use1) P1's tile blocks -> A2A; gd -> SG
+#   MSELoss   (!use2) the decode's rows -> SG; backward level -> FY; gd -> SG
+#   KL        the rows' softmax statistics -> SG, then as MSELoss
+_FORWARD = ["SG", "FY", "FY"]
+_STEP = {"HSIC": ["FY", "FY", "FY", "A2A", "SG"], "MSELoss": ["SG", "FY", "SG"], "KL": ["SG", "SG", "FY", "SG"]}
+
+
+@pytest.mark.parametrize("measure", ["HSIC", "MSELoss", "KL"])
+def test_sharded_step_asks_for_its_exchanges_in_order(pkg, measure):
+    """The exchange sequence of two row-block ranks as data: which region of the arena each collective of a step moves, in
+    order.  A bare step runs its own forward (8, 6, 7 collectives: the counts tests/test_gpu_multiproc.py asserts, and the
+    2 * 8 + 3 + 1 of the one-rank stepper); a step behind a monitor call adopts that forward and drops its three; want_scalars
+    appends the gather of the clamp sum."""
+    from mc_gra_amd import sharded as S
+    z = _synthetic_case(1100, 11, (16, 16), 4, seed=1100, **({} if measure == "HSIC" else {"measure": measure}))
+    _, bks = _shard_engines(pkg, z, 2)
+    log = _record_exchanges(bks)
+    S.run_lockstep(bks, S.SHARD_STEP)
+    assert _exchanges_of(log) == _FORWARD + _STEP[measure]
+    assert len(_FORWARD + _STEP[measure]) == {"HSIC": 8, "MSELoss": 6, "KL": 7}[measure]
+    S.run_lockstep(bks, S.SHARD_MONITOR)
+    assert _exchanges_of(log) == _FORWARD
+    S.run_lockstep(bks, S.SHARD_STEP)
+    assert _exchanges_of(log) == _STEP[measure]
+    S.run_lockstep(bks, S.SHARD_STEP, want_scalars=True)
+    assert _exchanges_of(log) == _FORWARD + _STEP[measure] + ["SG"]
+    S.run_lockstep(bks, S.SHARD_MONITOR)
+    S.run_lockstep(bks, S.SHARD_STEP, want_scalars=True)
+    assert _exchanges_of(log)[3:] == _STEP[measure] + ["SG"]
+    assert all(b.eng.fused_steps() == 4 for b in bks)
+
+
+def test_sharded_masked_step_gathers_the_state_in_front_of_the_redo(pkg, monkeypatch):
+    """... and a step whose decode masks a dead row (the construction of
+    test_sharded_ranks_hand_masked_steps_to_the_general_path): the whole fused sequence, then three gathers through the
+    N x N region -- M and the two Adam moments -- in front of the replicated redo, which exchanges nothing."""
+    from mc_gra_amd import sharded as S
+    z = _synthetic_case(600, 11, (16, 16), 4, seed=9, weight_param=(0.01, 0.01, 0, 0, 0, 10, 10, 0, 10, 0))
+    monkeypatch.setenv("MCGRA_SPLIT_BF16", "3")
+    w = H.masked_weights(z)
+    _, bks = _shard_engines(pkg, z, 2)
+    for b in bks:
+        b.eng.set_model(w.W, w.b, w.Wlin, w.blin, w.Ws)
+    log = _record_exchanges(bks)
+    S.run_lockstep(bks, S.SHARD_STEP)
+    assert _exchanges_of(log) == _FORWARD + _STEP["HSIC"] + ["NXN"] * 3
+    assert all(b.eng.path_stats()["general_steps"] == 1 for b in bks)
+
+
 def test_row_block_forward_forks_the_next_products_and_a_product_nobody_takes_is_dropped(pkg, monkeypatch):
     """A row-block rank's forward (the monitor call's, adopted by the next step) forks the NEXT step's pack and N x N x N product as
     soon as the degree vector is complete (attack_fused.hip: fork_p1_early).  (1) Against the same ranks with MCGRA_EARLY_P1=0
