@@ -571,8 +571,10 @@ int mcgra_mse(void* stream, int64_t count, const float* X, const float* Y, float
 int mcgra_gcn_forward(void* stream, int n, int nfeat, int nlayer, const int32_t* dims, const float* X,
                       const float* adj, const float* const* W, const float* const* b, const float* Wlin,
                       const float* blin, int nclass, int emb_nlayer, float* emb_out, float* out) {
-  if (n < 1 || nlayer < 1 || nlayer > MCGRA_MAX_LAYERS || !dims || !X || !adj || !W || !b || !Wlin || !blin || !out ||
-      dims[0] != nfeat) { set_error("bad argument"); return MCGRA_EINVAL; }
+  if (n < 1 || nfeat < 1 || nclass < 1 || nlayer < 1 || nlayer > MCGRA_MAX_LAYERS || !dims || !X || !adj || !W || !b || !Wlin ||
+      !blin || !out || dims[0] != nfeat) { set_error("bad argument"); return MCGRA_EINVAL; }
+  for (int l = 1; l <= nlayer; ++l)
+    if (dims[l] < 1) { set_error("gcn_forward: layer %d has width %d", l - 1, dims[l]); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   int hm = nclass;
   for (int l = 0; l < nlayer; ++l) hm = dims[l + 1] > hm ? dims[l + 1] : hm;

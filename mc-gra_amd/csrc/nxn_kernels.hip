@@ -909,7 +909,9 @@ __global__ __launch_bounds__(ROW_THREADS) void k_gauss_kernel(int m, int ld, flo
   const int mc = sq2 ? m2 : m;
   double s = 0;
   for (int j = threadIdx.x; j < mc; j += ROW_THREADS) {
-    const float d = ri - 2.f * A[base + j] + sc[j];
+    // (r_i + r_j) first: the sum commutes, so D_ij and D_ji -- and K with them -- are the same bits for the symmetric Gram of the
+    // square form.  k_hsic_gauss_rows and mcgra_mmd_pxpy_pxy read K's row means as its column means.  (r_i - 2 a) + r_j is not.
+    const float d = (ri + sc[j]) - 2.f * A[base + j];
     const float k = inv2s2 != 0.f ? expf(-d * inv2s2) : d;
     A[base + j] = k;
     s += k;

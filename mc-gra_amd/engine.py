@@ -19,14 +19,54 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _on_operand_device(fn):
+def _tensors(args):
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            yield a
+        elif isinstance(a, (list, tuple)):
+            yield from _tensors(a)
+
+
+def _need_device(op, *args):
+    """ValueError for a tensor that is not in device memory: the C ABI would follow its data_ptr() on the GPU."""
+    for t in _tensors(args):
+        if not t.is_cuda:
+            raise ValueError(f"{op}: a {t.device.type} tensor of shape {tuple(t.shape)}; the standalone ops take device tensors")
+
+
+def _on_operand_device(fn, every=False):
     """Standalone ops launch on the device (and its current stream) of their first tensor argument, not on
-    whatever device happens to be current."""
+    whatever device happens to be current.  A first argument that is not on a device is refused before anything is called."""
     @functools.wraps(fn)
     def run(first, *a, **k):
+        _need_device(fn.__name__, first, *((*a, *k.values()) if every else ()))
         with torch.cuda.device(first.device):
             return fn(first, *a, **k)
     return run
+
+
+def _device_operands(fn):
+    """_on_operand_device for the wrappers that hand data_ptr() of EVERY tensor argument to the C ABI (the metrics move theirs
+    to the first operand's device instead): any of them on the host is refused."""
+    return _on_operand_device(fn, every=True)
+
+
+def _f32(x):
+    """An operand as the C ABI reads it: float32, contiguous, no autograd history (the reference's functions take any float
+    tensor).  A float32 contiguous tensor is passed through as it is."""
+    return None if x is None else x.detach().to(dtype=torch.float32).contiguous()
+
+
+def _strided_f32(op, *ts):
+    """The GEMM family passes strides on and may write into `out`: nothing is converted (a copy would break out= aliasing),
+    so anything the kernels cannot read as float32 rows is refused."""
+    for t in ts:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise ValueError(f"{op}: {t.dtype} operand; the GEMM family takes float32")
+        if t.stride(-1) != 1:
+            raise ValueError(f"{op}: operand of shape {tuple(t.shape)} with strides {tuple(t.stride())}; the inner stride must be 1")
 
 
 def _p(t):
@@ -48,9 +88,10 @@ def _dev_i32(x, device):
 
 
 # ------------------------------------------------------------- standalone ops
-@_on_operand_device
+@_device_operands
 def sgemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None):
     """torch.mm on the fp32 MFMA kernel (mcgra_sgemm)."""
+    _strided_f32("sgemm", A, B, out)
     m = A.shape[1] if ta else A.shape[0]
     k = A.shape[0] if ta else A.shape[1]
     n = B.shape[0] if tb else B.shape[1]
@@ -62,10 +103,11 @@ def sgemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None):
     return out
 
 
-@_on_operand_device
+@_device_operands
 def ssyrk_lower(A, out=None):
     """C = A A^T on the lower tile storage (128 x 128 tiles on or below the diagonal); the rest of
     `out` is left untouched (mcgra_ssyrk_lower)."""
+    _strided_f32("ssyrk_lower", A, out)
     n, k = A.shape
     if out is None:
         out = torch.zeros(n, n, device=A.device, dtype=torch.float32)
@@ -73,9 +115,10 @@ def ssyrk_lower(A, out=None):
     return out
 
 
-@_on_operand_device
+@_device_operands
 def ssymm_lower(S, B, beta=0.0, out=None):
     """C = S B with symmetric S read from its lower tile storage only (mcgra_ssymm_lower)."""
+    _strided_f32("ssymm_lower", S, B, out)
     n, m = S.shape[0], B.shape[1]
     if out is None:
         out = torch.zeros(n, m, device=S.device, dtype=torch.float32)
@@ -84,9 +127,10 @@ def ssymm_lower(S, B, beta=0.0, out=None):
     return out
 
 
-@_on_operand_device
+@_device_operands
 def ssymm_split_bf16(S, X, rowsub=None, out=None):
     """C = S (X - rowsub 1^T)^T through the 3-plane bf16 split kernel (mcgra_ssymm_split_bf16); S symmetric."""
+    _strided_f32("ssymm_split_bf16", S, X, rowsub, out)
     n = S.shape[0]
     if out is None:
         out = torch.empty(n, n, device=S.device, dtype=torch.float32)
@@ -94,21 +138,23 @@ def ssymm_split_bf16(S, X, rowsub=None, out=None):
     return out
 
 
-@_on_operand_device
+@_device_operands
 def sgemm_skinny_x3(M, V, out=None):
     """M @ V (M [n x n], V [n x nc], nc <= 48) on the three-plane bf16 kernel of the fused step's forward
     (mcgra_sgemm_skinny_x3); M's rows must be 16-byte aligned (stride a multiple of 4)."""
+    _strided_f32("sgemm_skinny_x3", M, V, out)
     n, nc = M.shape[0], V.shape[1]
-    assert M.shape[1] == n and V.shape[0] == n and M.stride(1) == 1 and V.stride(1) == 1
+    assert M.shape[1] == n and V.shape[0] == n
     if out is None:
         out = torch.empty(n, nc, device=M.device, dtype=torch.float32)
     check(lib.mcgra_sgemm_skinny_x3(_stream(), n, _p(M), M.stride(0), _p(V), V.stride(0), nc, _p(out), out.stride(0)))
     return out
 
 
-@_on_operand_device
+@_device_operands
 def ssymm_split_f16(S, X, rowsub=None, out=None):
     """The same product through the 2-plane fp16 split kernel (mcgra_ssymm_split_f16); S symmetric."""
+    _strided_f32("ssymm_split_f16", S, X, rowsub, out)
     n = S.shape[0]
     if out is None:
         out = torch.empty(n, n, device=S.device, dtype=torch.float32)
@@ -116,53 +162,69 @@ def ssymm_split_f16(S, X, rowsub=None, out=None):
     return out
 
 
-@_on_operand_device
+@_device_operands
 def normalize_adj_tensor(adj):
     """utils.normalize_adj_tensor, dense branch (utils.py:211-230)."""
+    adj = _f32(adj)
     out = torch.empty_like(adj)
     check(lib.mcgra_normalize_adj(_stream(), adj.shape[0], _p(adj), _p(out)))
     return out
 
 
-@_on_operand_device
+@_device_operands
 def get_modified_adj(adj_changes, ori_adj, n):
+    adj_changes, ori_adj = _f32(adj_changes), _f32(ori_adj)
     out = torch.empty(n, n, device=adj_changes.device, dtype=torch.float32)
     check(lib.mcgra_get_modified_adj(_stream(), n, _p(adj_changes), _p(ori_adj), _p(out)))
     return out
 
 
-@_on_operand_device
+@_device_operands
+def pack_tril(M):
+    """M[tril_indices(n, n, -1)]: the inverse data movement of get_modified_adj (mcgra_pack_tril)."""
+    M = _f32(M)
+    n = M.shape[0]
+    out = torch.empty(n * (n - 1) // 2, device=M.device, dtype=torch.float32)
+    check(lib.mcgra_pack_tril(_stream(), n, _p(M), M.stride(0), _p(out)))
+    return out
+
+
+@_device_operands
 def info_entropy(prob):
+    prob = _f32(prob)
     out = torch.zeros(1, device=prob.device, dtype=torch.float32)
     check(lib.mcgra_info_entropy(_stream(), prob.shape[0], _p(prob), _p(out)))
     return out[0]
 
 
-@_on_operand_device
+@_device_operands
 def dot_product_decode(Z):
+    Z = _f32(Z)
     n, d = Z.shape
     out = torch.empty(n * (n - 1) // 2, device=Z.device, dtype=torch.float32)
     check(lib.mcgra_dot_product_decode(_stream(), n, d, _p(Z), _p(out)))
     return out
 
 
-@_on_operand_device
+@_device_operands
 def dot_product_decode2(Z, mode):
     """PGDAttack.dot_product_decode2 (topology_attack.py:421-467); `mode` as topology_attack._decode_mode gives it."""
+    Z = _f32(Z)
     n, d = Z.shape
     out = torch.empty(n, n, device=Z.device, dtype=torch.float32)
     check(lib.mcgra_dot_product_decode2(_stream(), n, d, _p(Z), int(mode), _p(out)))
     return out
 
 
-@_on_operand_device
+@_device_operands
 def linear_hsic(X, Y):
+    X, Y = _f32(X), _f32(Y)
     out = torch.zeros(1, device=X.device, dtype=torch.float32)
     check(lib.mcgra_linear_hsic(_stream(), X.shape[0], X.shape[1], Y.shape[1], _p(X), _p(Y), _p(out)))
     return out[0]
 
 
-@_on_operand_device
+@_device_operands
 def mutual_information(X, Y, want_grad=False):
     """utils.MutualInformation(sigma=0.4, num_bins=X.shape[1], normalize=True)(X, Y)[0] (utils.py:980-1049); want_grad: also
     its gradients w.r.t. X and Y (mcgra_mutual_information)."""
@@ -176,24 +238,58 @@ def mutual_information(X, Y, want_grad=False):
     return (out[0], gX, gY) if want_grad else out[0]
 
 
-@_on_operand_device
+@_device_operands
 def hsic_regular(x, y, sigma):
     """hsic.hsic_regular (hsic.py:117-124) with a given sigma."""
+    x, y = _f32(x), _f32(y)
     out = torch.zeros(1, device=x.device, dtype=torch.float32)
     check(lib.mcgra_hsic_regular(_stream(), x.shape[0], x.shape[1], y.shape[1], _p(x), _p(y), float(sigma), _p(out)))
     return out[0]
 
 
-@_on_operand_device
+@_device_operands
 def hsic_normalized(x, y, sigma):
     """hsic.hsic_normalized (hsic.py:127-135) with a given sigma."""
+    x, y = _f32(x), _f32(y)
     out = torch.zeros(1, device=x.device, dtype=torch.float32)
     check(lib.mcgra_hsic_normalized(_stream(), x.shape[0], x.shape[1], y.shape[1], _p(x), _p(y), float(sigma), _p(out)))
     return out[0]
 
 
-@_on_operand_device
+@_device_operands
+def hsic_regular2(x, y, sigma_x, sigma_y, normalized=False):
+    """hsic.hsic_regular / hsic_normalized with one bandwidth per operand, as kernelmat takes them for sigma=None
+    (hsic.py:39-41; mcgra_hsic_regular2)."""
+    x, y = _f32(x), _f32(y)
+    out = torch.zeros(1, device=x.device, dtype=torch.float32)
+    check(lib.mcgra_hsic_regular2(_stream(), x.shape[0], x.shape[1], y.shape[1], _p(x), _p(y), float(sigma_x), float(sigma_y),
+                                  int(bool(normalized)), _p(out)))
+    return out[0]
+
+
+@_device_operands
+def mmd(x, y, sigma_x, sigma_y, sigma_xy):
+    """hsic.mmd (hsic.py:68-89) with its three bandwidths given (mcgra_mmd); x [mx x d], y [my x d]."""
+    x, y = _f32(x), _f32(y)
+    out = torch.zeros(1, device=x.device, dtype=torch.float32)
+    check(lib.mcgra_mmd(_stream(), x.shape[0], y.shape[0], x.shape[1], _p(x), _p(y), float(sigma_x), float(sigma_y),
+                        float(sigma_xy), _p(out)))
+    return out[0]
+
+
+@_device_operands
+def mmd_pxpy_pxy(x, y, sigma_x, sigma_y):
+    """hsic.mmd_pxpy_pxy (hsic.py:92-114) with its two bandwidths given (mcgra_mmd_pxpy_pxy)."""
+    x, y = _f32(x), _f32(y)
+    out = torch.zeros(1, device=x.device, dtype=torch.float32)
+    check(lib.mcgra_mmd_pxpy_pxy(_stream(), x.shape[0], x.shape[1], y.shape[1], _p(x), _p(y), float(sigma_x), float(sigma_y),
+                                 _p(out)))
+    return out[0]
+
+
+@_device_operands
 def mse(X, Y):
+    X, Y = _f32(X), _f32(Y)
     out = torch.zeros(1, device=X.device, dtype=torch.float32)
     check(lib.mcgra_mse(_stream(), X.numel(), _p(X), _p(Y), _p(out)))
     return out[0]
@@ -362,9 +458,11 @@ def decode_scores(Z, mode):
     return out
 
 
-@_on_operand_device
+@_device_operands
 def gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=0):
     """GCN.forward (eval) and, when emb_nlayer > 0, embedding_GCN.forward."""
+    X, adj, Wlin, blin = _f32(X), _f32(adj), _f32(Wlin), _f32(blin)
+    W, b = [_f32(w) for w in W], [_f32(x) for x in b]
     n, nfeat = X.shape
     L = len(W)
     dims = (C.c_int32 * (L + 1))(*([nfeat] + [w.shape[1] for w in W]))

@@ -13,14 +13,11 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .engine import _on_operand_device, _p, _stream
+from . import engine
+from .engine import _device_operands, _f32, _need_device, _p, _stream
 
 
-def _f32(x):
-    return x.detach().to(dtype=torch.float32).contiguous()
-
-
-@_on_operand_device
+@_device_operands
 def distmat(X):
     """hsic.distmat (:20-27)."""
     X = _f32(X)
@@ -31,6 +28,7 @@ def distmat(X):
 
 def sigma_estimation(X, Y):
     """hsic.sigma_estimation (:5-17): median of the pairwise squared distances of cat([X, Y]) (lower triangle)."""
+    _need_device("sigma_estimation", X, Y)
     D = distmat(torch.cat([_f32(X), _f32(Y)])).cpu().numpy()
     tri = D[np.tril_indices(D.shape[0], -1)]
     med = np.median(tri)
@@ -43,6 +41,7 @@ def sigma_estimation(X, Y):
 
 def distcorr(X, sigma=1.0):
     """hsic.distcorr (:50-53): mean(exp(-distmat(X) / (2 sigma^2)))."""
+    _need_device("distcorr", X)
     return _gauss_mean(_f32(X), float(sigma))
 
 
@@ -56,42 +55,33 @@ def _gauss_mean(X, sigma):
     return out[0] + 1.0
 
 
-@_on_operand_device
 def mmd(x, y, sigma=None, use_cuda=True, to_numpy=False):
     """hsic.mmd (:68-89)."""
-    x, y = _f32(x), _f32(y)
+    _need_device("mmd", x, y)
     if sigma:
         sx = sy = sxy = float(sigma)
     else:
         sx, sy, sxy = sigma_estimation(x, x), sigma_estimation(y, y), sigma_estimation(x, y)
-    out = torch.zeros(1, device=x.device, dtype=torch.float32)
-    check(lib.mcgra_mmd(_stream(), x.shape[0], y.shape[0], x.shape[1], _p(x), _p(y), sx, sy, sxy, _p(out)))
-    return out[0]
+    return engine.mmd(x, y, sx, sy, sxy)
 
 
-@_on_operand_device
 def mmd_pxpy_pxy(x, y, sigma=None, use_cuda=True, to_numpy=False):
     """hsic.mmd_pxpy_pxy (:92-114)."""
-    x, y = _f32(x), _f32(y)
+    _need_device("mmd_pxpy_pxy", x, y)
     if sigma:
         sx = sy = float(sigma)
     else:
         sx, sy = sigma_estimation(x, x), sigma_estimation(y, y)
-    out = torch.zeros(1, device=x.device, dtype=torch.float32)
-    check(lib.mcgra_mmd_pxpy_pxy(_stream(), x.shape[0], x.shape[1], y.shape[1], _p(x), _p(y), sx, sy, _p(out)))
-    return out[0]
+    return engine.mmd_pxpy_pxy(x, y, sx, sy)
 
 
 def _hsic(x, y, sigma, normalized):
-    x, y = _f32(x), _f32(y)
+    _need_device("hsic_normalized" if normalized else "hsic_regular", x, y)
     if sigma:
         sx = sy = float(sigma)
     else:                     # kernelmat (:39-41): one estimate per operand
         sx, sy = sigma_estimation(x, x), sigma_estimation(y, y)
-    out = torch.zeros(1, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        check(lib.mcgra_hsic_regular2(_stream(), x.shape[0], x.shape[1], y.shape[1], _p(x), _p(y), sx, sy, int(normalized), _p(out)))
-    return out[0]
+    return engine.hsic_regular2(x, y, sx, sy, normalized)
 
 
 def hsic_regular(x, y, sigma=None, use_cuda=True, to_numpy=False):
@@ -104,7 +94,7 @@ def hsic_normalized(x, y, sigma=None, use_cuda=True, to_numpy=True):
     return _hsic(x, y, sigma, True)
 
 
-@_on_operand_device
+@_device_operands
 def hsic_normalized_cca(x, y, sigma=None, use_cuda=True, to_numpy=True):
     """hsic.hsic_normalized_cca (:138-151); utils.hsic_normalized_cca (utils.py:732-743) is this with sigma=5.0."""
     x, y = _f32(x), _f32(y)
