@@ -208,6 +208,42 @@ int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_labels, const
 int mcgra_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                        const int64_t* idx, int64_t n_idx, double* auc, double* ap);
 
+/* The curves behind those two numbers: what sklearn.metrics.roc_curve(..., drop_intermediate=) and
+ * precision_recall_curve(..., drop_intermediate=) return for labels[idx][:, idx].reshape(-1) against
+ * scores[idx][:, idx].reshape(-1), as exact integer counts per kept threshold.  Selection, ties, checks, error codes and the
+ * n_idx limit as mcgra_roc_auc (repeats allowed; NaN / +-inf scores and labels other than 0 / 1: MCGRA_EINVAL).
+ *   - a LEVEL is a distinct selected score; levels are numbered by descending score.  Level l carries tps[l] = #selected
+ *     positives with score >= its value, fps[l] = the same for negatives, and its threshold (the score; -0.0 is reported
+ *     as +0.0): sklearn's _binary_clf_curve;
+ *   - ROC points (roc_tps, roc_fps, roc_thr: device [cap], all three or none): point 0 is (0, 0, +inf), then the levels
+ *     roc_curve keeps, in descending-threshold order: all of them when drop_intermediate == 0 or levels <= 2, otherwise the
+ *     first, the last and every interior l with fps[l-1] - 2 fps[l] + fps[l+1] != 0 or the same expression in tps != 0.
+ *     fpr = roc_fps / N and tpr = roc_tps / P are left to the caller;
+ *   - PR points (pr_tps, pr_fps, pr_thr: device [cap], all three or none), in descending-threshold order (the caller
+ *     reverses and appends sklearn's (1, 0)): all levels when drop_intermediate == 0 or levels <= 2, otherwise the first, the
+ *     last and every interior l with tps[l] != tps[l-1] or tps[l+1] != tps[l];
+ *   - counts (host int64[5]) = {P, N, levels, ROC points (len(fpr) of sklearn), PR points (len(thresholds) of sklearn)},
+ *     written whenever the checks pass;
+ *   - best (host int64[3], may be NULL) = {tp, fp, level index} of the level that maximises F1 = 2 tp / (tp + fp + P) over
+ *     ALL levels, compared exactly (128-bit cross-multiplication), ties to the higher threshold; *best_thr (host, may be
+ *     NULL) its threshold.  P == 0: neither is written;
+ *   - capacity: the point counts depend on the data (no bound below levels + 1 holds a priori).  A requested curve with more
+ *     points than cap: nothing is written to the six buffers, the call returns MCGRA_ENOMEM, counts holds what is needed
+ *     and mcgra_last_error() names it;
+ *   - counts NULL, cap < 0, a curve with some but not all of its three buffers, or nothing asked for (all six buffers and
+ *     best NULL): MCGRA_EINVAL, decided before any HIP call;
+ *   - P == 0 or N == 0 still gives the integer curves (the NaN rates of sklearn are the caller's business).
+ * Every result is an integer count or the copied bits of a score: no floating-point arithmetic, per-tile counts merged by
+ * scans, so the same bits on every call.  Synchronises `stream`.
+ * Device scratch: 8 bytes per selected entry (the sort's two key buffers) + 12 bytes per level + about 6 MB. */
+int mcgra_rank_curves(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                      const int64_t* idx, int64_t n_idx, int drop_intermediate, int64_t cap,
+                      int64_t* roc_tps, int64_t* roc_fps, float* roc_thr,   /* device [cap]; all three NULL: no ROC */
+                      int64_t* pr_tps, int64_t* pr_fps, float* pr_thr,      /* device [cap]; all three NULL: no PR  */
+                      int64_t* counts   /* host[5]: P, N, levels, ROC points, PR points */,
+                      int64_t* best     /* host[3]: tp, fp, level index of the best-F1 level; may be NULL */,
+                      float* best_thr   /* host; may be NULL */);
+
 /* The same AUC for scores that are never stored: s_ij = dot_product_decode2(Z)_ij of the thin factor Z [n x d] (leading
  * dimension ldz >= d), computed pair by pair over idx x idx (main.py:412-437, notrain_test: how much of the graph a prior
  * leaks on its own).  labels, idx, n_idx, *out, exactness, NaN and error codes as mcgra_roc_auc.

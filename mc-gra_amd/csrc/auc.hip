@@ -16,6 +16,8 @@
 //   k_ap_terms         (average precision, mcgra_rank_metrics) each positive key x: its lower bound in the sorted
 //                      positives and in the sorted negatives give TP = #positives >= x, FP = #negatives >= x and the term
 //                      TP / (TP + FP); one float64 partial per block.  k_ap_sum adds the partials and divides by P
+//   rank_curves_sorted (mcgra_rank_curves: the ROC and precision-recall curves) the third consumer of the two sorted regions;
+//                      its passes are in curves.hip
 // mcgra_decode_auc ranks scores that are never stored, s_ij = dot_product_decode2(Z)_ij of a thin factor Z [n x d]:
 //   k_dec_rows         every row of Z: NaN / inf check, the L2-normalised copy of modes 1 and 4
 //   k_dec_classify     k_auc_classify on the scores dec_for_each decodes, a block owning 64 x 64 tiles of idx x idx
@@ -45,6 +47,7 @@
 #include "../../include/mcgra.h"
 #include "common.h"
 #include "rank_common.h"      // the keys, the idx check, the block sums and the radix sort (shared with topk.hip)
+#include "curves.h"           // the third consumer of the sorted regions (curves.hip: mcgra_rank_curves)
 
 namespace mcgra {
 
@@ -407,9 +410,10 @@ struct AucRun {
   }
   // Behind the classify pass of g blocks: its counts and flags, the per-block offsets, the emit pass (emit(offs, keys)
   // launches it), the two sorts, then what was asked for: auc != NULL the pair count and the division, ap != NULL the
-  // average-precision terms and their sum (both read the same sorted regions).
+  // average-precision terms and their sum (both read the same sorted regions); cv != NULL (then auc == ap == NULL) the
+  // curves of curves.hip, which also take a single-class selection.
   template <class Emit>
-  int finish(int g, Emit&& emit, double* auc, double* ap) {
+  int finish(int g, Emit&& emit, double* auc, double* ap, const CurveRequest* cv = nullptr) {
     std::vector<uint64_t> h(2 * (size_t)g);
     MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -425,7 +429,7 @@ struct AucRun {
     }
     uint64_t P = 0, N = 0;
     for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
-    if (P == 0 || N == 0) {
+    if ((P == 0 || N == 0) && !cv) {
       if (auc) *auc = NAN;                              // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
       if (ap) *ap = P == 0 ? NAN : 1.0;                 // a mean over no positives; no negatives: every term is TP / TP
       return 0;
@@ -448,6 +452,7 @@ struct AucRun {
     MCGRA_KERNEL_CHECK();
     if (int rc = auc_sort(st, keys, tmp, P, cnt, off)) return rc;
     if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, cnt, off)) return rc;
+    if (cv) return rank_curves_sorted(who, st, keys, tmp, P, nbase, N, *cv);
     unsigned long long u2 = 0;
     if (auc) {
       const bool a_pos = P <= N;                      // look the smaller class up in the larger one
@@ -481,10 +486,11 @@ using namespace mcgra;
 
 namespace mcgra {
 namespace {
-// mcgra_roc_auc (ap == NULL) and mcgra_rank_metrics: one classify, one emit and the two sorts for whatever is asked for
+// mcgra_roc_auc (ap == NULL), mcgra_rank_metrics and mcgra_rank_curves (cv != NULL): one classify, one emit and the two sorts
+// for whatever is asked for
 int rank_matrix(const char* who, void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
-                const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
-  if (n < 1 || !labels || !scores || (!auc && !ap) || ld_labels < n || ld_scores < n || (idx && n_idx < 1)) {
+                const int64_t* idx, int64_t n_idx, double* auc, double* ap, const CurveRequest* cv = nullptr) {
+  if (n < 1 || !labels || !scores || (!auc && !ap && !cv) || ld_labels < n || ld_scores < n || (idx && n_idx < 1)) {
     set_error("%s: bad argument", who);
     return MCGRA_EINVAL;
   }
@@ -504,7 +510,7 @@ int rank_matrix(const char* who, void* stream, int n, const float* labels, int l
   MCGRA_KERNEL_CHECK();
   return run.finish(g, [&](const uint64_t* offs, uint32_t* keys) {
     k_auc_emit<<<g, AUC_THREADS, 0, st>>>(rows, scores, ld_scores, labels, ld_labels, idx, offs, keys);
-  }, auc, ap);
+  }, auc, ap, cv);
 }
 }  // namespace
 }  // namespace mcgra
@@ -517,6 +523,20 @@ extern "C" int mcgra_roc_auc(void* stream, int n, const float* labels, int ld_la
 extern "C" int mcgra_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                                   const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
   return rank_matrix("rank_metrics", stream, n, labels, ld_labels, scores, ld_scores, idx, n_idx, auc, ap);
+}
+
+extern "C" int mcgra_rank_curves(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                                 const int64_t* idx, int64_t n_idx, int drop_intermediate, int64_t cap, int64_t* roc_tps,
+                                 int64_t* roc_fps, float* roc_thr, int64_t* pr_tps, int64_t* pr_fps, float* pr_thr,
+                                 int64_t* counts, int64_t* best, float* best_thr) {
+  const int roc = (roc_tps != nullptr) + (roc_fps != nullptr) + (roc_thr != nullptr);
+  const int pr = (pr_tps != nullptr) + (pr_fps != nullptr) + (pr_thr != nullptr);
+  if (!counts || cap < 0 || roc % 3 || pr % 3 || (!roc && !pr && !best)) {
+    set_error("rank_curves: bad argument (counts, cap >= 0, each curve's three buffers together, something to compute)");
+    return MCGRA_EINVAL;
+  }
+  const CurveRequest rq{drop_intermediate, cap, roc_tps, roc_fps, roc_thr, pr_tps, pr_fps, pr_thr, counts, best, best_thr};
+  return rank_matrix("rank_curves", stream, n, labels, ld_labels, scores, ld_scores, idx, n_idx, nullptr, nullptr, &rq);
 }
 
 namespace mcgra {

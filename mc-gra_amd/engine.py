@@ -421,6 +421,114 @@ def top_pairs(pred, k, idx=None, real=None):
     return (pairs, scores) if real is None else (pairs, scores, hits.view(torch.bool))
 
 
+def _curve_first_cap(entries, drop_intermediate):
+    """The first attempt's capacity: levels + 1 <= entries + 1 always suffices, and without drop_intermediate little less
+    does; with it a curve keeps the corners only, so an eighth of the entries (at least 2^20 points) is tried first and
+    mcgra_rank_curves says what is needed when that is too small (measured, DESIGN.md 3d: a modified_adj at n = 2 708 keeps
+    679 000 ROC points of 7.3 million entries, one at N = 10 000 1.1 million of 10^8)."""
+    return entries + 1 if not drop_intermediate else min(entries + 1, max(1 << 20, entries // 8))
+
+
+def _rank_curves(real, pred, idx, drop_intermediate, want_roc, want_pr, want_best, first_cap=None):
+    """One mcgra_rank_curves call (a second one, sized from its counts, when the first capacity is too small; never a
+    third).  Returns (counts, roc, pr, best): counts = (P, N, levels, ROC points, PR points); roc / pr = (tps, fps, thresholds)
+    device tensors of exactly that many points (int64, int64, float32) or None; best = (tp, fp, level, threshold) or None."""
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
+    rows = ix.numel() if ix is not None else n
+    cap = max(1, int(first_cap) if first_cap is not None else _curve_first_cap(rows * rows, drop_intermediate))
+    counts, best, thr = (C.c_int64 * 5)(), (C.c_int64 * 3)(), C.c_float(float("nan"))
+    for attempt in range(2):
+        def bufs(want):
+            if not want:
+                return None, None, None
+            return (torch.empty(cap, device=dev, dtype=torch.int64), torch.empty(cap, device=dev, dtype=torch.int64),
+                    torch.empty(cap, device=dev, dtype=torch.float32))
+        roc, pr = bufs(want_roc), bufs(want_pr)
+        rc = lib.mcgra_rank_curves(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows,
+                                   1 if drop_intermediate else 0, cap, _p(roc[0]), _p(roc[1]), _p(roc[2]), _p(pr[0]),
+                                   _p(pr[1]), _p(pr[2]), counts, best if want_best else None,
+                                   C.byref(thr) if want_best else None)
+        if rc == -4 and counts[2] > 0 and attempt == 0:       # MCGRA_ENOMEM with counts written: cap was too small
+            cap = max(counts[3] if want_roc else 0, counts[4] if want_pr else 0)
+            continue
+        check(rc)
+        break
+    P, N, levels, n_roc, n_pr = (int(c) for c in counts)
+    roc = tuple(t[:n_roc] for t in roc) if want_roc else None
+    pr = tuple(t[:n_pr] for t in pr) if want_pr else None
+    got_best = (int(best[0]), int(best[1]), int(best[2]), thr.value) if want_best and P > 0 else None
+    return (P, N, levels, n_roc, n_pr), roc, pr, got_best
+
+
+def _roc_rates(counts, roc):
+    """(fpr, tpr, thresholds) of roc_curve from the integer ROC points: fps / fps[-1] (= N) and tps / tps[-1] (= P), one
+    float64 division each (by a device tensor: a host scalar would be turned into a multiplication by its reciprocal, a
+    second rounding); NaN for an absent class."""
+    P, N = counts[0], counts[1]
+    tps, fps, thr = (roc[0].to(torch.float64), roc[1].to(torch.float64), roc[2])
+    nan = torch.full((tps.numel(),), float("nan"), device=tps.device, dtype=torch.float64)
+    fpr = fps / fps[-1] if N > 0 else nan
+    tpr = tps / tps[-1] if P > 0 else nan.clone()
+    return fpr, tpr, thr
+
+
+def _pr_rates(counts, pr):
+    """(precision, recall, thresholds) of precision_recall_curve from the integer PR points (descending thresholds): reversed,
+    with sklearn's last point (1, 0) appended; precision 0 where tp + fp == 0, recall 1 everywhere when P == 0."""
+    P = counts[0]
+    tps, fps, thr = (t.flip(0) for t in pr)
+    ps = (tps + fps).to(torch.float64)
+    t64 = tps.to(torch.float64)
+    precision = torch.where(ps != 0, t64 / torch.where(ps != 0, ps, torch.ones_like(ps)), torch.zeros_like(ps))
+    recall = t64 / t64[0] if P > 0 else torch.ones_like(t64)      # t64[0]: the last level's tp = P (a device tensor)
+    one, zero = torch.ones(1, device=t64.device, dtype=torch.float64), torch.zeros(1, device=t64.device, dtype=torch.float64)
+    return torch.cat((precision, one)), torch.cat((recall, zero)), thr
+
+
+def _best_f1(counts, best):
+    if best is None:
+        nan = float("nan")
+        return {"f1": nan, "threshold": nan, "tp": 0, "fp": 0, "precision": nan, "recall": nan}
+    tp, fp, _, thr = best
+    return {"f1": _ratio(2 * tp, tp + fp + counts[0]), "threshold": thr, "tp": tp, "fp": fp,
+            "precision": _ratio(tp, tp + fp), "recall": _ratio(tp, counts[0])}
+
+
+@_on_operand_device
+def roc_curve(real, pred, idx=None, drop_intermediate=True):
+    """sklearn.metrics.roc_curve(real[idx][:, idx].reshape(-1), pred[idx][:, idx].reshape(-1), drop_intermediate=) without
+    gathering the submatrix or leaving the device (mcgra_rank_curves): (fpr, tpr, thresholds), float64, float64, float32
+    device tensors, thresholds[0] = +inf.  The counts behind the rates are exact integers; a rate is one float64 division.
+    fpr is NaN when no selected label is 0, tpr when none is 1 (sklearn's warnings are not reproduced).  Arguments and
+    refusals as roc_auc."""
+    counts, roc, _, _ = _rank_curves(real, pred, idx, drop_intermediate, True, False, False)
+    return _roc_rates(counts, roc)
+
+
+@_on_operand_device
+def precision_recall_curve(real, pred, idx=None, drop_intermediate=False):
+    """sklearn.metrics.precision_recall_curve of the same selection (mcgra_rank_curves): (precision, recall, thresholds),
+    thresholds ascending, the last precision 1 and the last recall 0.  recall is 1 everywhere when no selected label is 1."""
+    counts, _, pr, _ = _rank_curves(real, pred, idx, drop_intermediate, False, True, False)
+    return _pr_rates(counts, pr)
+
+
+@_on_operand_device
+def rank_curves(real, pred, idx=None, drop_intermediate=True, _first_cap=None):
+    """Both curves and the best F1 from one classify, one emit and one sort (mcgra_rank_curves).  Returns a dict: "roc" =
+    roc_curve's triple, "pr" = precision_recall_curve's (with this drop_intermediate), "positives", "negatives", "levels"
+    (distinct selected scores), "roc_points", "pr_points", and "best_f1" = {"f1", "threshold", "tp", "fp", "precision",
+    "recall"} of the threshold that maximises F1 = 2 tp / (tp + fp + P) over ALL distinct scores (exact comparison, ties to the
+    higher threshold; NaN when no selected label is 1)."""
+    counts, roc, pr, best = _rank_curves(real, pred, idx, drop_intermediate, True, True, True, _first_cap)
+    return {"roc": _roc_rates(counts, roc), "pr": _pr_rates(counts, pr), "positives": counts[0], "negatives": counts[1],
+            "levels": counts[2], "roc_points": counts[3], "pr_points": counts[4], "best_f1": _best_f1(counts, best)}
+
+
 def _decode_rank_metrics(real, Z, mode, idx, want_auc, want_ap):
     dev = real.device
     n = real.shape[0]

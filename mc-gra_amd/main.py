@@ -16,8 +16,13 @@ graph itself: of the K best-scored unordered node pairs of modified_adj within e
 are true edges -- precision, recall and F1 at K (engine.topk_metrics; ties by packed position, so the answer is defined).
 K = 0 takes each set's own true edge count; a K above a set's pair count is clamped to it, and the printed k says so.
 --save_edges PATH (needs --topk) writes the whole-graph selection as an .npz of pairs, scores and hits in ranking order
-(engine.top_pairs).  Not provided (each exits with a message naming the reference line): --mode
-search/baseline/gaussian/gcn_attack.
+(engine.top_pairs).
+--curves PATH (not in the reference; --mode evaluate only; absent by default, and then nothing changes) writes what the
+reference's roc_curve call returns, and the precision-recall curve beside it, for each of the three index sets as an .npz at
+PATH (roc_fpr_<set>, roc_tpr_<set>, roc_thresholds_<set>, pr_precision_<set>, pr_recall_<set>, pr_thresholds_<set>; sklearn's
+conventions and defaults: drop_intermediate on for the ROC curve, off for the PR curve), computed on the GPU
+(engine.rank_curves, engine.precision_recall_curve), and reports the best F1 over all thresholds.
+Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 mc-gra_amd/main.py --dataset ... --measure HSIC ...
@@ -67,10 +72,17 @@ def check_topk_args(args, fail):
         fail(f"--topk scores the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
 
 
+def check_curves_args(args, fail):
+    """--curves against the rest of the command line; fail(message) does not return."""
+    if getattr(args, "curves", None) and args.mode != "evaluate":
+        fail(f"--curves draws the curves of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
         check_topk_args(args, self.error)
+        check_curves_args(args, self.error)
         return args
 
 
@@ -114,6 +126,7 @@ def build_parser():
     p.add_argument('--ap', action='store_true')     # also report average precision (engine.rank_metrics)
     p.add_argument('--topk', type=int, default=None)        # also report the K best pairs' precision / recall / F1
     p.add_argument('--save_edges', type=str, default=None)  # with --topk: the whole-graph edge list as an .npz
+    p.add_argument('--curves', type=str, default=None)      # also write the ROC and precision-recall curves as an .npz
     return p
 
 
@@ -207,6 +220,27 @@ def save_edges(path, ori_adj, inference_adj, k):
         np.savez(f, pairs=pairs, scores=scores, hits=hits)
 
 
+def curves_report(path, ori_adj, inference_adj, sets):
+    """--curves PATH: the ROC curve (drop_intermediate on, as the reference's roc_curve call) and the precision-recall curve
+    (drop_intermediate off, sklearn's default) of each index set of `sets` (name -> node ids, None: every node), written as
+    one .npz at exactly `path` when it is given.  Returns {"curves_<name>": dict} with the point counts and the best F1."""
+    real = ori_adj.to(inference_adj.device)
+    out, arrays = {}, {}
+    for name, ix in sets.items():
+        c = engine.rank_curves(real, inference_adj, ix)
+        pr = engine.precision_recall_curve(real, inference_adj, ix)
+        for k, t in zip(("fpr", "tpr", "thresholds"), c["roc"]):
+            arrays[f"roc_{k}_{name}"] = t.cpu().numpy()
+        for k, t in zip(("precision", "recall", "thresholds"), pr):
+            arrays[f"pr_{k}_{name}"] = t.cpu().numpy()
+        out[f"curves_{name}"] = {"roc_points": c["roc_points"], "pr_points": int(pr[2].numel()), "levels": c["levels"],
+                                 "best_f1": c["best_f1"]["f1"], "best_threshold": c["best_f1"]["threshold"]}
+    if path:
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+    return out
+
+
 def victim_tensors(m):
     """Every parameter of a victim: the registered ones and those of the layers it keeps in plain lists (models/gcn.py:44,
     graphsage.py:50, gat.py:47 -- as the reference's classes do)."""
@@ -262,6 +296,7 @@ def _exit(message):
 
 def _run(args, rank, world):
     check_topk_args(args, _exit)
+    check_curves_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -377,6 +412,10 @@ def _run(args, rank, world):
     want_topk = getattr(args, "topk", None) is not None
     if want_topk:           # every rank computes (as the AUCs); the keys exist only with the flag
         res.update(topk_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, args.topk))
+    want_curves = bool(getattr(args, "curves", None))
+    if want_curves:         # every rank computes; rank 0 writes the file
+        res.update(curves_report(args.curves if rank == 0 else None, ad, inference_adj,
+                                 {"attack": idx_attack, "train": idx_train, "all": None}))
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
@@ -387,10 +426,13 @@ def _run(args, rank, world):
         print(f"current f1={res['topk_all']['f1']} (k={res['topk_all']['k']})")
         if getattr(args, "save_edges", None):
             save_edges(args.save_edges, ad, inference_adj, res["topk_all"]["k"])
+    if want_curves:
+        print(f"current best_f1={res['curves_all']['best_f1']} (threshold={res['curves_all']['best_threshold']})")
     os.makedirs("./results/", exist_ok=True)
-    # the parameter line names --ap, --topk and --save_edges only when they are set: without them the log is what it was
-    # before the flags existed
-    hidden = (set() if want_ap else {"ap"}) | (set() if want_topk else {"topk", "save_edges"})
+    # the parameter line names --ap, --topk, --save_edges and --curves only when they are set: without them the log is what
+    # it was before the flags existed
+    hidden = (set() if want_ap else {"ap"}) | (set() if want_topk else {"topk", "save_edges"}) | \
+        (set() if want_curves else {"curves"})
     shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
     with open(os.path.join("./results", args.log_name), "a") as f:                         # main.py:314-323
         f.write(f"current parameter: {shown}\n")
@@ -403,6 +445,11 @@ def _run(args, rank, world):
             f.write("\t".join(f"In {name}: k={d['k']} P={d['precision']} R={d['recall']} F1={d['f1']}" for name, d in
                               (("attack graph", res["topk_attack"]), ("train graph", res["topk_train"]),
                                ("Whole Graph", res["topk_all"]))) + "\n")
+        if want_curves:
+            f.write("\t".join(f"In {name}: ROC points={d['roc_points']} PR points={d['pr_points']} levels={d['levels']} "
+                              f"best F1={d['best_f1']} at {d['best_threshold']}" for name, d in
+                              (("attack graph", res["curves_attack"]), ("train graph", res["curves_train"]),
+                               ("Whole Graph", res["curves_all"]))) + "\n")
         f.write(f"current density: {res['density']}\n")
     return res
 
