@@ -513,10 +513,14 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode,
  * tests ("adj_norm", "A1", "em", "G_adjn", "G_A1", "G_A", "G_sym", "M", "d",
  * "r", "logp", "sm2", "HA", "YA", "T0", "KFC").  ld receives the leading dimension.  "G_sym" (the mirrored packed
  * gradient of the last step) is kept only when MCGRA_KEEP_GSYM=1 was set at create; on a low-rank step "G_A1" does not
- * hold d loss / d modified_adj1 (it is never materialised there). */
+ * hold d loss / d modified_adj1 (it is never materialised there).
+ * The call takes no stream and orders nothing: a monitor call may have left work running on a side stream that writes the scratch
+ * buffers ("A1", "G_A", ...).  Read the pointer through mcgra_attack_copy_buffer, or on a stream behind the wait that
+ * mcgra_attack_copy_buffer enqueues there. */
 int mcgra_attack_buffer(mcgra_attack_t* h, const char* name, float** ptr,
                         int* rows, int* cols, int* ld);
-/* copy of the same intermediate into a caller buffer dst [rows x cols], leading dimension dst_ld */
+/* copy of the same intermediate into a caller buffer dst [rows x cols], leading dimension dst_ld; `stream` first waits for
+ * whatever the last call left running on a side stream (no flag of the engine changes) */
 int mcgra_attack_copy_buffer(mcgra_attack_t* h, void* stream, const char* name, float* dst, int dst_ld);
 
 /* Timing of the dominant kernel: the engine brackets every launch of the fp32

@@ -351,7 +351,7 @@ int mcgra_attack_destroy(mcgra_attack_t* h) {
 
 int mcgra_attack_set_model(mcgra_attack_t* h, void* stream, const float* const* W, const float* const* b,
                            const float* Wlin, const float* blin, const float* const* Ws) {
-  if (h) h->fwd_cached = h->prep_valid = h->fused_fwd_valid = h->skip_fused = false;      // whatever the last step / monitor call left is stale now
+  if (h) carry_forget(h);      // Rule: forget.  Nothing in flight reads the model.
   if (!h || !W || !b || !Wlin || !blin) { set_error("null argument"); return MCGRA_EINVAL; }
   if ((h->has_self != 0) != (Ws != nullptr)) { set_error("Ws must be given exactly when has_self is set"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
@@ -369,12 +369,11 @@ int mcgra_attack_set_model(mcgra_attack_t* h, void* stream, const float* const* 
 int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* features, const float* adj,
                            const float* ori_adj, const float* feature_adj, const int32_t* labels,
                            const int32_t* idx_attack) {
-  if (h) h->fwd_cached = h->prep_valid = h->fused_fwd_valid = false;      // whatever the last step / monitor call left is stale now
+  if (h) carry_forget(h, true);      // Rule: drop (below, once the arguments stand) + forget.  skip_fused is kept: it only says which path goes first
   if (!h || !features || !adj || !feature_adj || !labels || !idx_attack) { set_error("null argument"); return MCGRA_EINVAL; }
   if (!h->model_set) { set_error("mcgra_attack_set_model must be called first"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  if (h->early_pack) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0)); h->early_pack = false; }
-  CHK(drop_early_p1(h, st));
+  CHK(carry_drop(h, st));
   const int n = h->n, ld = h->ld, hs = h->hsum;
   if (ori_adj) {
     // (general path only: apply_plan)
@@ -389,7 +388,6 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
     MCGRA_HIP(hipMemcpy2DAsync(h->ORI, (size_t)ld * 4, ori_adj, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
   }
   apply_plan(h, ori_adj != nullptr);
-  h->fused_fwd_valid = h->fwd_cached = h->prep_valid = h->planes_valid = false;      // (a new graph: nothing of the old one to adopt)
   MCGRA_HIP(hipMemcpy2DAsync(h->FADJ, (size_t)ld * 4, feature_adj, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipMemcpyAsync(h->labels, labels, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipMemcpyAsync(h->idx, idx_attack, sizeof(int) * h->na, hipMemcpyDeviceToDevice, st));
@@ -453,7 +451,7 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
   // (small_term's HSIC branch relies on zero pad columns in Q / Q2: see there)
   MCGRA_HIP(hipMemsetAsync(h->Q, 0, sizeof(float) * (size_t)h->hmax * h->hmax, st));
   MCGRA_HIP(hipMemsetAsync(h->Q2, 0, sizeof(float) * (size_t)h->hmax * h->hmax, st));
-  h->t3_zero = false;
+  h->step.t3_zero = false;
   MCGRA_KERNEL_CHECK();
   // feature_adj.max() != feature_adj.min() (topology_attack.py:212) is evaluated by the host layer
   MCGRA_HIP(hipStreamSynchronize(st));
@@ -479,19 +477,15 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
 }
 
 int mcgra_attack_set_adj_changes(mcgra_attack_t* h, void* stream, const float* packed) {
-  if (h) h->fwd_cached = h->prep_valid = h->fused_fwd_valid = h->skip_fused = false;      // whatever the last step / monitor call left is stale now
+  if (h) carry_forget(h);      // Rule: drop + forget.  A pack or product of the old M may still be reading it on the side stream.
   if (!h || !packed) { set_error("null argument"); return MCGRA_EINVAL; }
-  if (h->early_pack) {      // a pack of the old M may still be reading it on the side stream
-    MCGRA_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_pack, 0));
-    h->early_pack = false;
-  }
-  CHK(drop_early_p1(h, (hipStream_t)stream));      // (likewise the product a row-block rank's forward forked)
+  CHK(carry_drop(h, (hipStream_t)stream));
   launch_unpack_sym((hipStream_t)stream, h->n, h->ld, packed, nullptr, 0, h->M);
   MCGRA_KERNEL_CHECK();
   h->m_is_full = true;
   return 0;
 }
-int mcgra_attack_get_adj_changes(mcgra_attack_t* h, void* stream, float* packed) {
+int mcgra_attack_get_adj_changes(mcgra_attack_t* h, void* stream, float* packed) {      // Rule: none.  It reads M, which whatever is in flight also only reads.
   if (!h || !packed) { set_error("null argument"); return MCGRA_EINVAL; }
   if (h->sharded && !h->m_is_full) { set_error("row-block rank: only rows [row_begin, row_end) are kept between a step and mcgra_attack_finalize (mcgra_attack_get_rows)"); return MCGRA_EINVAL; }
   launch_pack_tril((hipStream_t)stream, h->n, h->ld, h->M, packed, false);
@@ -572,7 +566,7 @@ int forward_common(mcgra_attack* h, hipStream_t st, float* adjn_out, const float
                           double* adjn_rowsum = nullptr) {
   const int n = h->n, ld = h->ld;
   const bool general = noise != nullptr || h->has_ori;      // (ori != 0: clamp(M + ori) even without noise, :474-478)
-  if (!general && h->prep_valid) {
+  if (!general && h->carry.prep_valid) {
     // d, r and the norm / sparsity sums from the row sums the Adam pass left behind: no pass over M
     const size_t cnt = (size_t)n * rankk_apply_adam_tiles(n);
     prep_from_partials(st, n, h->G_A, adam_row_sums(h, cnt), h->d, h->r, h->rowsq, h->rowsum);
@@ -807,7 +801,7 @@ static int fork_p1(GeneralStep& s) {
   } else
   CHK(eg_symm(h, sp, n, n, h->KFC, ld, h->XC, ld, 0.f, h->KX, ld));
   if (h->overlap) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
-  h->p1_inflight = true;
+  h->step.p1_inflight = true;
   return 0;
 }
 
@@ -839,7 +833,7 @@ static int center_xc(GeneralStep& s) {
       split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr);
     // (in a run whose decode keeps masking pairs the product would be thrown away: it then waits for this step's own
     // masked-pair count, hsic_terms)
-    if (!(h->skip_fused && s.use2)) CHK(fork_p1(s));
+    if (!(h->carry.skip_fused && s.use2)) CHK(fork_p1(s));
     else s.p1_deferred = true;
   }
   return 0;
@@ -859,7 +853,7 @@ static int step_forward(GeneralStep& s) {
   // adj_norm is symmetric when eps == 0 (ori == 0): its column means are its row sums / n, which k_adjn emits
   if (s.adopt) { float* t = h->ADJN; h->ADJN = h->ADJN_next; h->ADJN_next = t; }
   else CHK(forward_common(h, st, h->ADJN, noise_ld, (s.want_xc && !s.gen) ? h->rowsx : nullptr));
-  h->p1_inflight = false;
+  h->step.p1_inflight = false;
   if (s.want_xc) CHK(center_xc(s));
   // ---- victim(features, adj_norm) (:167) and the CE loss (:172)
   if (!s.adopt) {
@@ -886,9 +880,9 @@ static int step_forward(GeneralStep& s) {
   // low-rank forms -- every other step skips the counting)
   const bool count_masked = h->cfg.measure == MCGRA_MEASURE_HSIC && h->lr_ok && h->cfg.w[1] != 0;
   if (count_masked) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, sizeof(unsigned int), st));
-  h->nmask_zero = false;
+  h->step.nmask_zero = false;
   launch_decode_post(st, n, ld, h->A1, h->has_ori ? h->ORI : nullptr, count_masked ? h->nmask : nullptr);
-  h->lr_step = false;
+  h->step.lr_step = false;
   return 0;
 }
 
@@ -983,26 +977,26 @@ static int hsic_terms(GeneralStep& s) {
       MCGRA_HIP(hipMemcpyAsync(&masked, h->nmask, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
       MCGRA_HIP(hipStreamSynchronize(st));
     }
-    h->lr_step = (masked == 0);
-    if (s.use2) h->skip_fused = masked != 0;
-    if (h->lr_step && s.p1_deferred) CHK(fork_p1(s));
+    h->step.lr_step = (masked == 0);
+    if (s.use2) h->carry.skip_fused = masked != 0;
+    if (h->step.lr_step && s.p1_deferred) CHK(fork_p1(s));
   }
   // on a low-rank step with c2 the modified_adj1 side (c7 value and gradient) is folded into k_lr_decode_bwd
-  const bool y_fused = h->lr_step && s.use2 && lr_decode_supported(he);
+  const bool y_fused = h->step.lr_step && s.use2 && lr_decode_supported(he);
   // A step that IS a Gram evaluation centres and packs modified_adj1 and starts Ky FIRST: the side stream is idle from the end of
   // Kx until this point, and the N x N entropy pass and its reduction (40 us at n = 3312) need none of it
-  s.ky_early = s.gs_only && s.use2 && !h->lr_step && s.gst != st;
+  s.ky_early = s.gs_only && s.use2 && !h->step.lr_step && s.gst != st;
   if (s.ky_early) { center_yc(s); CHK(launch_ky(s)); }
   elem_terms(s, 0.f, 0.f, !y_fused);
   if (!s.want_xc) return 0;
-  if (h->lr_step) {
+  if (h->step.lr_step) {
     ++h->lr_steps;
     if (s.use2) {
       launch_lr_colstats(st, n, he, h->Zn, h->hmax, h->lrStats);
       launch_lr_prep(st, n, he, h->Zn, h->hmax, h->lrStats, h->lrL, h->lrV, h->lr_ldv, h->lrDelta);
       // T = Xc^T [U | D Z | delta^2]: W, W2 and t3 from one pass over Xc
       CHK(eg(h, st, true, false, n, h->lr_ldv, n, 1.f, h->XC, ld, h->lrV, h->lr_ldv, 0.f, h->lrT, h->lr_ldv));
-      h->t3_zero = false;
+      h->step.t3_zero = false;
       launch_lr_post(st, n, he, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
     }
     return 0;
@@ -1050,7 +1044,7 @@ static int early_bwd(GeneralStep& s) {
 // G_adjn += sum_l G_P_l T_l^T (+ the low-rank 2 s2 (U M1^T - D Z W^T) of a low-rank step, in the same pass)
 static int victim_rankk(GeneralStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, he = s.he;
-  const bool lr2 = s.hsic && h->lr_step && s.use2;
+  const bool lr2 = s.hsic && h->step.lr_step && s.use2;
   if (lr2 && rankk_nt_supported(n, n, hs, 2 * he)) {
     MCGRA_HIP(rankk_nt(st, n, n, hs, 1.f, h->GPv, hs, h->Tv, hs, 2 * he, 2.f * (float)(s.sg * s.k2), h->lrL, 2 * he, h->lrR,
                        2 * he, 1.f, h->G_ADJN, ld));
@@ -1152,7 +1146,7 @@ static int gram_fp32(GeneralStep& s) {
 // products), the decode, and the modified_adj chain (embedding + output2) down to G_P
 static int step_backward(GeneralStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, L = h->L, Le = h->Le, C = h->C, he = s.he;
-  const bool lr2 = s.hsic && h->lr_step && s.use2;
+  const bool lr2 = s.hsic && h->step.lr_step && s.use2;
   if (lr2) {
     CHK(eg(h, st, false, false, n, 2 * he, n, 1.f, h->XC, ld, h->lrT, h->lr_ldv, 0.f, h->lrQ, 2 * he));         // [Q | Q2] = Xc [W | W2]
     if (!lr_decode_supported(he))     // widths without a fused decode backward: d c2 / d A1 += 2 s2 Q Z^T, materialised
@@ -1226,12 +1220,12 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
   bool normbwd_parts = false;
   float* nb_colpart = h->colpart;       // column partials of the normalisation backward: [nb_strips][n]
   int nb_strips = h->nstrips;
-  if (s.hsic && h->lr_step && (s.use1 || s.use2)) {
+  if (s.hsic && h->step.lr_step && (s.use1 || s.use2)) {
     // Last contribution to G_adjn, and the only consumer of P1: everything above ran beside the forked product.
     // G_adjn += 2 s1 P1 + 2 s2 (D^2 Xc + 1 c^T);  v1 = sum P1 o Xc
-    if (h->p1_inflight) {
+    if (h->step.p1_inflight) {
       if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-      h->p1_inflight = false;
+      h->step.p1_inflight = false;
     }
     // ... fused with the two N x N reductions of the normalisation backward that follows (one pass instead of three);
     // its partial sums live in KY, idle on a low-rank step (the product that used it as split-K slab has been joined)
@@ -1268,7 +1262,7 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
                                (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
                                h->keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
                                emit ? adam_row_sums(h, cnt) : nullptr));
-    h->prep_valid = emit;
+    h->carry.prep_valid = emit;
     adam_done = true;
   } else if (rankk_nt_supported(n, n, hs, 0) && !h->has_ori) {
     // one pass: G_A = GPu Tu^T + (G_adjn_ij r_i r_j + gd_i), the apply step of the normalisation backward as the
@@ -1284,14 +1278,14 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
 
   // ---- packed-gradient mirror + Adam + projection + clamp (:274-283)
   if (!adam_done) {
-    h->prep_valid = false;
+    h->carry.prep_valid = false;
     launch_adam_sym(st, n, ld, h->G_A, s.gate, h->M, h->am, h->av, h->mm + 2, (float)(1.0 - b1), (float)b2,
                     (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f, h->keep_gsym ? h->GSYM : nullptr,
                     may_project ? 0 : 1);
   }
   MCGRA_KERNEL_CHECK();
   h->have_step = true;
-  if (may_project) { CHK(project(h, st)); h->prep_valid = false; }
+  if (may_project) { CHK(project(h, st)); h->carry.prep_valid = false; }
 
   if (scalars_out) CHK(collect_scalars(h, st, scalars_out));
   return 0;
@@ -1309,19 +1303,19 @@ int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* sc
     set_error("this engine is a row-block rank: drive it with mcgra_attack_shard_begin / mcgra_attack_shard_next");
     return MCGRA_EINVAL;
   }
+  // Rule: the fused step goes first and takes what it adopts (fs_begin, fs_pack_fork); the general step takes Kx and drops the rest, below.
   // (after a step whose decode masked a pair the general path goes first: it reads the masked-pair count itself, and
   // only once that is zero again is the fused step worth enqueueing -- a masked run otherwise pays for both every step)
-  if (!noise && !h->sharded && fused_step_possible(h) && !h->skip_fused) {
+  if (!noise && !h->sharded && fused_step_possible(h) && !h->carry.skip_fused) {
     const int rc = fused_step(h, st, scalars_out);      // 1: a relu-masked pair in the decode, the general path redoes the step
     if (rc <= 0) return rc;
   }
-  h->fused_last = false;
-  h->fused_fwd_valid = false;
-  if (h->early_pack) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0)); h->early_pack = false; }      // (the general step packs its own operands)
-  // Kx of this step's adj_norm, forked by the monitor call whose forward the step adopts: taken over (anything else is dropped)
-  const bool kx_adopt = h->kx_early && h->fwd_cached && !noise && !h->has_ori;
-  if (kx_adopt) h->kx_early = false;
-  CHK(drop_early_p1(h, st));
+  // Rule: take, then drop.  Kx of this step's adj_norm, forked by the monitor call whose forward the step adopts, is taken over;
+  // anything else in flight is dropped (the general step packs its own operands), and so is a forward the fused step would have adopted.
+  const bool kx_adopt = h->carry.kx_early && h->carry.fwd_cached && !noise && !h->has_ori;
+  if (kx_adopt) h->carry.kx_early = false;
+  CHK(carry_drop(h, st));
+  h->carry.fused_last = h->carry.fused_fwd_valid = false;
 
   const mcgra_attack_config_t& c = h->cfg;
   GeneralStep s{};
@@ -1337,24 +1331,24 @@ int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* sc
   s.gs_path = h->gram_split && !s.gen && s.want_xc;
   s.gs_only = s.gs_path && !h->lr_ok;
   s.gst = (s.gs_path && h->gram_ovl && h->st2) ? h->st2 : st;
-  s.adopt = h->fwd_cached && !s.gen; s.kx_adopt = kx_adopt;      // (kx_adopt implies adopt)
-  h->fwd_cached = false;
+  s.adopt = h->carry.fwd_cached && !s.gen; s.kx_adopt = kx_adopt;      // (kx_adopt implies adopt)
+  h->carry.fwd_cached = false;
 
   CHK(step_forward(s));
   const int m = c.measure;
   CHK(m == MCGRA_MEASURE_DP ? dp_terms(s) : m == MCGRA_MEASURE_KDE ? kde_terms(s) : m == MCGRA_MEASURE_KL ? kl_terms(s)
       : s.hsic ? hsic_terms(s) : mse_terms(s));
   MCGRA_KERNEL_CHECK();
-  s.gram_eval = s.gs_path && !h->lr_step;
+  s.gram_eval = s.gs_path && !h->step.lr_step;
   if (s.want_xc) {
     // Join the forked P1 product before the Grams may overwrite KX; a low-rank step joins it as late as possible, in front of
     // its only consumer (step_tail)
-    if (h->p1_inflight && !h->lr_step) {
+    if (h->step.p1_inflight && !h->step.lr_step) {
       if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-      h->p1_inflight = false;
+      h->step.p1_inflight = false;
     }
     if (s.gram_eval) CHK(gram_eval(s));
-    else if (!h->lr_step) CHK(gram_fp32(s));
+    else if (!h->step.lr_step) CHK(gram_fp32(s));
   }
   CHK(step_backward(s));
   return step_tail(s, scalars_out);
@@ -1368,8 +1362,7 @@ long long mcgra_attack_masked_fused_steps(mcgra_attack_t* h) { return h ? (long 
 long long mcgra_attack_cut_product_steps(mcgra_attack_t* h) { return h ? (long long)h->cut_product_steps : 0; }
 int mcgra_attack_product_mode(mcgra_attack_t* h) {
   if (!h) return 0;
-  if (h->split_single && (h->gram_split || (h->split_mode == 2 && h->split_planes == 2))) return 1;
-  return h->split_mode == 2 && h->split_planes == 2 ? 3 : h->split_mode;
+  return plan_product_mode(h->split_single, h->gram_split, h->split_mode, h->split_planes);
 }
 
 int mcgra_attack_path_stats(mcgra_attack_t* h, long long* lowrank_steps, long long* general_steps) {
@@ -1386,23 +1379,25 @@ int mcgra_attack_monitor(mcgra_attack_t* h, void* stream, float* out_logp, doubl
   if (!h || !h->graph_set) { set_error("engine not set up"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   if (h->sharded) { set_error("row-block rank: use mcgra_attack_shard_begin(MCGRA_SHARD_MONITOR)"); return MCGRA_EINVAL; }
-  if (fused_step_possible(h) && h->fused_last && h->cfg.eps == 0.f) {
+  // Rule: none.  A monitor call adds to what is in flight; forking an item again replaces it (the pack on its own side stream:
+  // fw_prep; Kx behind a drop, below).  It leaves ONE forward: the fused one or the general one.
+  if (fused_step_possible(h) && h->carry.fused_last && h->cfg.eps == 0.f) {
     // the monitoring forward IS the next iteration's forward (eps == 0): both chains from M, adopted by fused_step
     CHK(fused_forward(h, st));
-    h->fused_fwd_valid = true;
-    h->fwd_cached = false;
+    h->carry.fused_fwd_valid = true;
+    h->carry.fwd_cached = false;
     if (out_logp)
       MCGRA_HIP(hipMemcpyAsync(out_logp, h->logp, sizeof(float) * (size_t)h->n * h->C, hipMemcpyDeviceToDevice, st));
     if (sparsity) {
       double s;
-      if (h->early_pack) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));      // (the sum rides on the pack's stream)
+      if (h->carry.early_pack) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));      // (the sum rides on the pack's stream)
       MCGRA_HIP(hipMemcpyAsync(&s, h->scal + S_SUM, sizeof(double), hipMemcpyDeviceToHost, st));
       MCGRA_HIP(hipStreamSynchronize(st));
       *sparsity = s / ((double)h->n * h->n);
     }
     return 0;
   }
-  h->fused_fwd_valid = false;
+  h->carry.fused_fwd_valid = false;
   // adj_norm2 must not overwrite ADJN, which has to survive for the post-loop decode (:300): it goes to ADJN_next
   // (adopted by the next step, see fwd_cached) or, without reuse, to the A1 buffer.
   const bool want_xc = (h->cfg.measure == MCGRA_MEASURE_HSIC || h->cfg.measure == MCGRA_MEASURE_CKA) &&
@@ -1415,15 +1410,15 @@ int mcgra_attack_monitor(mcgra_attack_t* h, void* stream, float* out_logp, doubl
     // the next step of this configuration is a Gram evaluation whose first product needs this adj_norm only: packed and forked now,
     // it runs beside the chains below and beside the next step's own forward part instead of behind them (the row partials in G_A
     // that forward_common just consumed make room for the product's split-K slabs)
-    CHK(drop_early_p1(h, st));      // (two monitor calls in a row)
+    CHK(carry_drop(h, st));      // (two monitor calls in a row: the first one's Kx)
     CHK(gram_pack_fork_kx(h, st, dst));
     if (h->gram_ovl && h->st2) MCGRA_HIP(hipEventRecord(h->ev_first, h->st2));
-    h->kx_early = true;
-    if (!h->small_slab) h->prep_valid = false;      // (the product's split-K slabs went into G_A, over the row partials forward_common just consumed)
+    h->carry.kx_early = true;
+    if (!h->small_slab) h->carry.prep_valid = false;      // (the product's split-K slabs went into G_A, over the row partials forward_common just consumed)
   }
   CHK(chain_forward(h, st, dst, h->ld, h->L, h->Tv, h->Pv, h->Hv, h->Sv));
   CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->fwd_reuse ? h->sm : nullptr));
-  h->fwd_cached = h->fwd_reuse;
+  h->carry.fwd_cached = h->fwd_reuse;
   if (out_logp)
     MCGRA_HIP(hipMemcpyAsync(out_logp, h->logp, sizeof(float) * (size_t)h->n * h->C, hipMemcpyDeviceToDevice, st));
   if (sparsity) {
@@ -1458,18 +1453,16 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, cons
   if (decode_mode < 0 || decode_mode > 6) { set_error("decode_mode %d", decode_mode); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   const int n = h->n, ld = h->ld, hs = h->hsum, Le = h->Le, L = h->L;
-  // (a pack a monitor call forked for a step that never came: it reads M, which is overwritten below, and writes scratch)
-  if (h->early_pack) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0)); h->early_pack = false; }
-  CHK(drop_early_p1(h, st));
+  // Rule: drop + forget.  What a monitor call forked for a step that never came reads M, which is overwritten below (:301), and writes
+  // scratch; the forward it left and the row sums the Adam pass left describe the old M.  (skip_fused is kept: a step may follow.)
+  CHK(carry_drop(h, st));
+  carry_forget(h, true);
   if (!h->have_step) {               // epochs == 0: adj_norm of :142
     if (h->has_ori) CHK(forward_ori_unclamped(h, st, h->ADJN));
     else CHK(forward_common(h, st, h->ADJN, nullptr));
   }
-  // M is overwritten below (:301): the forward a monitor call left for the next step and the row sums the Adam pass
-  // left for the next normalisation describe the old M
-  h->fwd_cached = h->prep_valid = h->fused_fwd_valid = false;
   // em = embedding(features, adj_norm) ; adj_changes <- dot_product_decode(em) (:300-301)
-  if (h->fused_last && h->have_step) {
+  if (h->carry.fused_last && h->have_step) {
     // the fused step never stores adj_norm; embedding(features, adj_norm) of the last iteration is its victim-chain
     // activation of layer emb_nlayer (shared weights), saved by fused_step
     launch_row_normalize(st, n, h->wdt[Le - 1], h->em_last, h->hmax, h->Zn, h->hmax, h->nrm, 2.f);
@@ -1537,9 +1530,7 @@ int mcgra_attack_copy_buffer(mcgra_attack_t* h, void* stream, const char* name, 
   int r = 0, c = 0, l = 0;
   CHK(mcgra_attack_buffer(h, name, &p, &r, &c, &l));
   if (!dst || dst_ld < c) { set_error("bad destination"); return MCGRA_EINVAL; }
-  if (h->early_pack) MCGRA_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_pack, 0));      // (scratch buffers under a forked pack)
-  if (h->p1_early) MCGRA_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_join, 0));      // (... or under a forked product)
-  if (h->kx_early && h->gram_ovl && h->st2) MCGRA_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_first, 0));
+  CHK(carry_wait(h, (hipStream_t)stream));      // Rule: wait.  Scratch buffers under a forked pack, product or Kx.
   MCGRA_HIP(hipMemcpy2DAsync(dst, (size_t)dst_ld * 4, p, (size_t)l * 4, (size_t)c * 4, r, hipMemcpyDeviceToDevice,
                              (hipStream_t)stream));
   return 0;

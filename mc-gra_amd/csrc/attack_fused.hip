@@ -116,7 +116,7 @@ static int mm_rows(mcgra_attack* h, hipStream_t st, int ncol, bool fwd = false) 
   if (h->sharded)      // into the product columns of the wide exchange stage
     return eg(h, st, false, false, rows, ncol, h->n, 1.f, h->M + (size_t)h->row0 * h->ld, h->ld, h->FV, h->fcols, 0.f,
               h->FY + (size_t)h->row0 * h->fyw, h->fyw);
-  if (h->planes_valid && planes_mm_supported(h->n, ncol)) {      // beside the N x N x N product: from its own operand planes
+  if (h->step.planes_valid && planes_mm_supported(h->n, ncol)) {      // beside the N x N x N product: from its own operand planes
     MCGRA_HIP(planes_mm(st, h->n, h->Bpack, split3_chunks(h->n, 2), h->amax + 1, h->FV, h->fcols, ncol, h->r, h->ws, h->ws_bytes, &h->fy,
                         h->pm_scratch));
     return 0;
@@ -131,17 +131,29 @@ static int mm_rows(mcgra_attack* h, hipStream_t st, int ncol, bool fwd = false) 
 }
 
 static int fork_p1_early(const FusedStep& s);
-// A product forked by a forward whose step never came (or comes by another path): ordered in front of whatever the caller's
-// stream does next, its result dropped.
-int drop_early_p1(mcgra_attack* h, hipStream_t st) {
-  if (h->kx_early) {      // (likewise the Gram product Kx a monitor call forked for a step that never came: attack.hip, gram_kx_early)
-    if (h->gram_ovl && h->st2) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
-    h->kx_early = false;
-  }
-  if (!h->p1_early) return 0;
-  MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-  h->p1_early = h->p1_inflight = h->p1_first = false;
+// ---- the transitions of Carry (engine.h).  Nothing in flight: no HIP call.
+// Everything a forward forked and left running is ordered in front of whatever the caller's stream does next.  (Kx and a rank's
+// product never coexist: one is a monolithic engine's, the other a row-block rank's.)
+int carry_wait(mcgra_attack* h, hipStream_t st) {
+  const Carry& c = h->carry;
+  if (c.early_pack) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
+  if (c.kx_early && h->gram_ovl && h->st2) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
+  if (c.p1_early) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
   return 0;
+}
+// ... and its results dropped: forked by a forward whose step never came, or comes by another path
+int carry_drop(mcgra_attack* h, hipStream_t st) {
+  CHK(carry_wait(h, st));
+  Carry& c = h->carry;
+  c.early_pack = c.kx_early = c.p1_early = c.p1_first = false;
+  c.p1_early_cut = c.p1_early_split = 0;
+  h->step.p1_inflight = false;      // (the exception of StepScratch: it stands for the same product as p1_early)
+  return 0;
+}
+void carry_forget(mcgra_attack* h, bool keep_skip_fused) {
+  Carry& c = h->carry;
+  c.fwd_cached = c.fused_fwd_valid = c.prep_valid = false;
+  if (!keep_skip_fused) c.skip_fused = false;
 }
 
 // The operand pack on the product's stream, forked behind r (ev_r) and marked by ev_pack: the planes of panels [p_off, p_off +
@@ -166,7 +178,7 @@ enum { FW_PREP, FW_R_DONE, FW_LAYER_PRODUCT, FW_LAYER_POST, FW_HEADS, FW_COUNT }
 static int fw_prep(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, ld = s.ld, R0 = s.R0, R1 = s.R1;
-  if (h->prep_valid) {
+  if (h->carry.prep_valid) {
     prep_from_partials(st, n, h->G_A, adam_row_sums(h, (size_t)n * fl_tail_tiles(n)), h->d, h->r, h->rowsq, h->rowsum, R0, R1);
   } else {
     launch_prep(st, false, n, ld, h->M, nullptr, nullptr, 0.f, nullptr, nullptr, h->d, h->r, h->rowsq, h->rowsum, R0, R1);
@@ -178,16 +190,16 @@ static int fw_prep(FusedStep& s) {
     // The product is forked behind the pack on that stream (p1_behind_pack_on) when the forward's products run on
     // skinny_x3.hip, whose blocks fit beside a product block; beside a gemm_f32 forward it was measured a wash, and the
     // product then waits for the forward (ev_fork).
-    h->early_pack = false;
+    h->carry.early_pack = false;
     if (h->late_mean && h->overlap && h->st2 && h->early_pack_on) {
       CHK(pack_on_side_stream(h, st, 0, -1, h->cfg.w[1] != 0 ? h->A1 : nullptr,
                               pack_row_sums(h, split3_pack_rsq_parts(n, h->split_planes)), !h->p1_behind_pack_on));
-      h->early_pack = true;
+      h->carry.early_pack = true;
       // With the product behind the pack, the pack is on the path: it streams M alone and the product follows it directly;
       // the forward (and the sums above) follow it on the caller's stream, beside the product.
       if (h->p1_behind_pack_on) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
     }
-    if (!h->early_pack || h->p1_behind_pack_on) launch_reduce_rows(st, h->rowsq, n, 2, h->scal + S_SQ);      // rowsq | rowsum are adjacent, and so are S_SQ | S_SUM
+    if (!h->carry.early_pack || h->p1_behind_pack_on) launch_reduce_rows(st, h->rowsq, n, 2, h->scal + S_SQ);      // rowsq | rowsum are adjacent, and so are S_SQ | S_SUM
   } else {
     // own rows of r and d, and this rank's share of |adj_changes|^2 and sum(modified_adj) in the scalar lane: ONE gather
     const Stage sg = narrow_stage(h);
@@ -209,7 +221,7 @@ static int fw_r_done(FusedStep& s) {
     // r is complete: the N x N x N product needs nothing else of this forward (uncentred planes: KFC 1 = 0)
     if (h->early_p1_on && s.R1 > s.R0 && !(h->fs_active && h->fs_what == MCGRA_SHARD_MONITOR && h->fs_last)) CHK(fork_p1_early(s));
   }
-  h->fs_l = 0;
+  h->step.fs_l = 0;
   return GO;
 }
 // layer fs_l: the product Y = M [r o Tv | Tu (| r)]; its post pass loops back until the last layer is done
@@ -217,7 +229,7 @@ static int fw_layer_product(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, fc = s.fc;
   const bool fused_post = h->fused_post;
-  const int l = h->fs_l, w = h->wdt[l];
+  const int l = h->step.fs_l, w = h->wdt[l];
   const float* Xs[3] = {h->Tv + h->off[l], h->Tu + h->off[l], h->r};
   const float* rs[3] = {h->r, nullptr, nullptr};
   const int lds[3] = {hs, hs, 1}, ws[3] = {w, w, 1};
@@ -232,7 +244,7 @@ static int fw_layer_post(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, L = s.L, C = s.C, fc = s.fc;
   const bool fused_post = h->fused_post;
-  const int l = h->fs_l, w = h->wdt[l];
+  const int l = h->step.fs_l, w = h->wdt[l];
   const bool wr = l == 0 && !h->late_mean && !h->fused_mse;
   // the post pass and what follows it on the same rows in ONE launch where the widths allow (<= 32): the next
   // layer's T of both chains + the next product's right-hand side, or -- last layer -- both linear heads with their
@@ -253,7 +265,7 @@ static int fw_layer_post(FusedStep& s) {
       launch_rowmat(st, n, w, h->wdt[l + 1], h->Hu + h->off[l], hs, h->W[l + 1], h->wdt[l + 1], 1, nullptr, h->Tu + h->off[l + 1], hs);
     }
   }
-  if (++h->fs_l < L) h->fw_state = FW_LAYER_PRODUCT;
+  if (++h->step.fs_l < L) h->fw_state = FW_LAYER_PRODUCT;
   return GO;
 }
 // heads (where the last post pass did not take them), the operand-scale bound and the mean's statistics
@@ -264,9 +276,9 @@ static int fw_heads(FusedStep& s) {
     CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->sm));
     CHK(head_forward(h, st, h->Hu, h->Z2, nullptr, h->sm2));
   }
-  if (h->late_mean) { if (h->amax && !h->early_pack) hipLaunchKernelGGL(k_rmax2, dim3(1), dim3(1024), 0, st, n, h->r, h->amax + 1); }
+  if (h->late_mean) { if (h->amax && !h->carry.early_pack) hipLaunchKernelGGL(k_rmax2, dim3(1), dim3(1024), 0, st, n, h->r, h->amax + 1); }
   else if (!h->fused_mse)      // (p1_early: the operand-scale bound is k_rmax2's, and the product in flight reads it)
-    fl_mean_stats(st, n, h->cmean, h->r, h->fstat + 192, (h->amax && !h->p1_early) ? h->amax + 1 : h->mm + 3);
+    fl_mean_stats(st, n, h->cmean, h->r, h->fstat + 192, (h->amax && !h->carry.p1_early) ? h->amax + 1 : h->mm + 3);
   MCGRA_KERNEL_CHECK();
   return GO;
 }
@@ -285,21 +297,22 @@ static int fused_forward_pt(mcgra_attack* h, hipStream_t st, mcgra_exchange_t* e
 
 int fused_forward(mcgra_attack* h, hipStream_t st) {      // monolithic engines only
   h->fw_state = 0;
+  h->step.planes_valid = false;      // (mm_rows reads it; a step sets it behind its own pack only)
   return fused_forward_pt(h, st, nullptr);
 }
 
 // host-side bookkeeping of a fused step that went through (the Adam pass is enqueued)
 static void fused_commit(mcgra_attack* h) {
   const int n = h->n;
-  h->planes_valid = false;          // the Adam pass is enqueued: Bpack no longer describes M
+  h->step.planes_valid = false;          // the Adam pass is enqueued: Bpack no longer describes M
   const bool may_project = h->cfg.num_edges < 0.5 * (double)n * (double)n;
-  h->lr_step = !h->fused_mse;
+  h->step.lr_step = !h->fused_mse;
   if (!h->fused_mse) ++h->lr_steps;      // (the fused MSELoss step has no low-rank form: it counts as a fused step only)
   ++h->fused_steps;
   h->t += 1;
-  h->prep_valid = adam_emits_partials(h, may_project, (size_t)n * fl_tail_tiles(n));
+  h->carry.prep_valid = adam_emits_partials(h, may_project, (size_t)n * fl_tail_tiles(n));
   h->have_step = true;
-  h->fused_last = true;
+  h->carry.fused_last = true;
 }
 
 // A fused step that did not reach one of its regular exits (a HIP error, or a row-block step the caller abandoned after a
@@ -315,15 +328,11 @@ static int fused_resync(mcgra_attack* h, hipStream_t st) {
   unsigned int seq = 0;
   MCGRA_HIP(hipMemcpy(&seq, h->mask_seq_dev, sizeof(seq), hipMemcpyDeviceToHost));
   h->mask_seq = h->mask_want = seq;
-  h->p1_inflight = h->fs_dec_forked = false;
-  h->p1_first = h->p1_early = false;
-  h->tail_rows = 0;
-  // (the streams were drained above, but st2 is non-blocking and shared with other engines: a pack forked for the abandoned
-  // step is ordered in front of this stream's next launches explicitly, as at every other site that drops the flag)
-  if (h->early_pack) (void)hipStreamWaitEvent(st, h->ev_pack, 0);
-  h->early_pack = false;
-  h->nmask_zero = h->t3_zero = false;
-  h->fused_fwd_valid = h->fwd_cached = h->prep_valid = false;
+  // (the streams were drained above, but st2 is non-blocking and shared with other engines: what was forked for the abandoned
+  // step is ordered in front of this stream's next launches explicitly, as at every other site that drops it)
+  CHK(carry_drop(h, st));
+  carry_forget(h, true);      // (skip_fused stands: the abandoned step wrote scratch only, M and the model are the ones it was counted on)
+  h->step = StepScratch{};
   h->fs_open = false;
   return 0;
 }
@@ -377,7 +386,7 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
   const int P = split3_panel(), p_off = R0 / P, p_cnt = R1 > R0 ? (R1 - R0 + P - 1) / P : 0;
   const bool ovl = h->overlap;
   const int sflag = h->split_single ? 8 : 0;      // MCGRA_SPLIT_BF16=1: the single-plane product of the same operands (split_symm_bf16.hip)
-  h->p1_inflight = false;
+  h->step.p1_inflight = false;
   if (p_cnt <= 0) return 0;
   hipStream_t sp = ovl ? h->st2 : st;
   if (ovl && !behind_pack) {
@@ -385,7 +394,7 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
     MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
   }
   CHK(timer_begin(h, sp, h->profile));
-  h->p1_first = false;
+  h->carry.p1_first = false;
   if (h->sharded && h->a2a_overlap && ovl && h->world > 1 && h->test_mutate != 1) {
     // Row panels of the peers first (rotated start: the panel behind the own ones, wrapping), own panels last, the launch
     // cut behind the peers' tiles: the all-to-all that hands them over waits for ev_first only and runs beside the rest.
@@ -400,12 +409,12 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
     if (first > 0 && first < total) {
       MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, rot, -1, h->KY, sizeof(float) * (size_t)n * ld, h->split_planes,
                             h->amax, p_off, p_cnt, 4 | sflag, first, h->ev_first));
-      h->p1_first = true;
+      h->carry.p1_first = true;
       ++h->cut_product_steps;
     }
   }
-  h->tail_rows = h->tail_rows2 = 0;
-  if (!h->p1_first && !h->sharded && ovl && h->early_tail_on && n >= 8192 && !want_vals && h->test_mutate != 1) {
+  h->step.tail_rows = h->step.tail_rows2 = 0;
+  if (!h->carry.p1_first && !h->sharded && ovl && h->early_tail_on && n >= 8192 && !want_vals && h->test_mutate != 1) {
     // The tail's first pass needs P1_ij and P1_ji: the rows the product has finished in BOTH orientations.  Its tiles run
     // in groups of four row panels, so behind a cut on whole rounds of the chip at ~0.8 of the launch the first
     // `tail_rows` rows are complete, and the pass over them runs beside the product's last rounds (N = 10 000: the cut
@@ -420,18 +429,18 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
     if (cut >= slots && cut < total && rows >= n / 2) {
       MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, 0, -1, h->KY, sizeof(float) * ((size_t)n * ld - tail_ps_floats(h)),
                             h->split_planes, h->amax, p_off, p_cnt, sflag, cut, h->ev_first, cut2, cut2 ? h->ev_second : nullptr));
-      h->tail_rows = rows;
-      h->tail_rows2 = rows2;
+      h->step.tail_rows = rows;
+      h->step.tail_rows2 = rows2;
       ++h->cut_product_steps;
     }
   }
-  if (!h->p1_first && h->tail_rows == 0)
+  if (!h->carry.p1_first && h->step.tail_rows == 0)
   MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, 0, -1, h->small_slab ? h->small_slab : h->KY,
                         h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->split_planes, h->amax, p_off, p_cnt, sflag));
   CHK(timer_end(h, sp, h->profile, 2.0 * (double)n * n * (double)(R1 - R0)));
   ++h->split_steps;
   if (ovl) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
-  h->p1_inflight = true;
+  h->step.p1_inflight = true;
   return 0;
 }
 
@@ -440,19 +449,19 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
 // world 8, a quarter of the rank's product -- and nothing in it feeds the product: the planes are packed UNCENTRED (the product
 // does not see the centring vector: KFC 1 = 0; the monolithic step packs the same way), their scale bound is max r^2, and the
 // rows' |xc_i|^2 come from the pack's partials once the forward has the means (k_rsq_fin_unc).  The step finds p1_early set.
-// A forward whose step never comes (the last monitor call of a run) leaves a product nobody reads: drop_early_p1.
+// A forward whose step never comes (the last monitor call of a run) leaves a product nobody reads: carry_drop.
 static int fork_p1_early(const FusedStep& s) {      // (called with R1 > R0: p_cnt > 0)
   mcgra_attack* h = s.h; hipStream_t st = s.st;
-  CHK(drop_early_p1(h, st));      // (two forwards in a row)
+  CHK(carry_drop(h, st));      // (two forwards in a row)
   if (!s.use1 || !h->overlap || !h->st2 || h->test_mutate == 1) return 0;
   CHK(pack_on_side_stream(h, st, s.p_off, s.p_cnt, s.use2 ? h->A1 : nullptr,
                           s.use2 ? pack_row_sums(h, split3_pack_rsq_parts(s.n, h->split_planes)) : nullptr, false));
   const auto cut0 = h->cut_product_steps, split0 = h->split_steps;
   CHK(fork_p1(h, st, true));
-  h->p1_early = h->p1_inflight;
+  h->carry.p1_early = h->step.p1_inflight;
   // (the counters move with the step that takes the product, not with a forward whose step may never come)
-  h->p1_early_cut = (int)(h->cut_product_steps - cut0); h->cut_product_steps = cut0;
-  h->p1_early_split = (int)(h->split_steps - split0); h->split_steps = split0;
+  h->carry.p1_early_cut = (int)(h->cut_product_steps - cut0); h->cut_product_steps = cut0;
+  h->carry.p1_early_split = (int)(h->split_steps - split0); h->split_steps = split0;
   return 0;
 }
 
@@ -462,9 +471,9 @@ enum {
   FS_BWD_PRODUCT, FS_BWD_POST, FS_TAIL_FRONT, FS_TAIL_REDUCE, FS_DECIDE, FS_GATHER_SEND, FS_GATHER_RECV, FS_ADAM, FS_SCALARS, FS_COUNT
 };
 static int join_p1(const FusedStep& s) {      // the forked product, in front of its first reader on the caller's stream
-  if (s.h->p1_inflight) {
+  if (s.h->step.p1_inflight) {
     if (s.ovl) MCGRA_HIP(hipStreamWaitEvent(s.st, s.h->ev_join, 0));
-    s.h->p1_inflight = false;
+    s.h->step.p1_inflight = false;
   }
   return 0;
 }
@@ -474,16 +483,16 @@ static int fs_begin(FusedStep& s) {
   mcgra_attack* h = s.h;
   if (h->fs_open) CHK(fused_resync(h, s.st));
   h->fs_open = true;
-  h->planes_valid = false;
-  h->fs_adopted = h->fused_fwd_valid;
-  h->fused_fwd_valid = false;
-  h->fwd_cached = false;
+  h->step.planes_valid = false;
+  h->step.fs_adopted = h->carry.fused_fwd_valid;
+  h->carry.fused_fwd_valid = false;
+  h->carry.fwd_cached = false;
   h->fw_state = 0;
   return GO;
 }
 // the step's own forward: this stage is the next one until FW_STAGES has run through
 static int fs_forward(FusedStep& s) {
-  if (s.h->fs_adopted) return GO;
+  if (s.h->step.fs_adopted) return GO;
   const int rc = forward_stages(s);
   if (rc == AT_XCHG) s.h->fs_state = FS_FORWARD;
   return rc;
@@ -499,18 +508,18 @@ static int fs_pack_fork(FusedStep& s) {
   if (h->late_mean) {
     // uncentred planes ((H Kf H) 1 = 0: the product does not see the centring vector), row sums and sums of squares of
     // adj_norm from the same pass -> the column means (adj_norm is symmetric) and |xc_i|^2
-    if (h->early_pack) {
+    if (h->carry.early_pack) {
       // packed on the product's stream beside this M's forward (fused_forward_pt): everything on the caller's stream that
       // reads the planes or the pack's row partials (k_mean_fin, planes_mm) waits for it here
       MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
-      h->early_pack = false;
+      h->carry.early_pack = false;
       behind_pack = h->p1_behind_pack_on;
     } else
       split3_pack_from_m(st, n, ld, h->M, h->r, nullptr, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr, 0, -1,
                          use2 ? h->A1 : nullptr, pack_row_sums(h, np));
-    h->planes_valid = h->planes_mm_on;          // (the means themselves: behind the fork, below)
+    h->step.planes_valid = h->planes_mm_on;          // (the means themselves: behind the fork, below)
   } else
-  if (p_cnt > 0 && !mse && !h->p1_early) {
+  if (p_cnt > 0 && !mse && !h->carry.p1_early) {
     split3_pack_from_m(st, n, ld, h->M, h->r, h->cmean, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr, p_off, p_cnt,
                        use2 ? h->A1 : nullptr);
     if (use2)
@@ -518,16 +527,16 @@ static int fs_pack_fork(FusedStep& s) {
   }
 
   // ---- P1 (column block of the own rows: Xc^T rows = adj_norm rows by symmetry) forked onto the side stream
-  if (h->p1_early) {
+  if (h->carry.p1_early) {
     // a row-block rank's forward forked pack and product as soon as r was complete (fork_p1_early): in flight since then.
     // The pack's row partials (|xc_i|^2 below) are ready at ev_pack.
     MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
-    h->p1_early = false;
-    h->cut_product_steps += h->p1_early_cut; h->split_steps += h->p1_early_split;
+    h->carry.p1_early = false;
+    h->cut_product_steps += h->carry.p1_early_cut; h->split_steps += h->carry.p1_early_split;
     if (use2)
       hipLaunchKernelGGL(k_rsq_fin_unc, dim3((R1 - R0 + 3) / 4), dim3(256), 0, st, R0, R1, n, np, h->A1, pack_row_sums(h, np), h->cmean, h->lrRs);
   } else {
-    h->p1_inflight = false;
+    h->step.p1_inflight = false;
     if (p_cnt > 0 && use1) CHK(fork_p1(h, st, want_vals, behind_pack));
   }
 
@@ -581,7 +590,7 @@ static int fs_decode_stats(FusedStep& s) {
   {
     const ZeroFill zf{h->Gem, (size_t)n * h->hmax, s.use10 ? h->Gsm : nullptr, s.use10 ? (size_t)n * C : 0, h->nmask, 2};
     launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->hmax, h->nrm, 2.f, h->Zpair, zero_inline ? &zf : nullptr);
-    if (zero_inline) h->nmask_zero = true;
+    if (zero_inline) h->step.nmask_zero = true;
   }
   if (s.kl) {
     // calc_kl's row statistics (logsumexp of adj_norm's and of modified_adj1's rows) from M, r and Zn: the decode backward and
@@ -605,8 +614,8 @@ static int decode_fly(const FusedStep& s, hipStream_t s4, bool forked, bool zero
     MCGRA_HIP(hipStreamWaitEvent(s4, h->ev_fork4, 0));
   }
   if (zero) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, 2 * sizeof(unsigned int), s4));
-  h->nmask_zero = false;
-  h->fs_np = fl_decode_fly(s4, s.n, s.R0, s.R1, s.he, h->Zn, h->hmax, (float)(s.k7 / s.n2), slabs, rowvals, h->GZn, h->hmax, h->nmask, h->Zpair,
+  h->step.nmask_zero = false;
+  h->step.fs_np = fl_decode_fly(s4, s.n, s.R0, s.R1, s.he, h->Zn, h->hmax, (float)(s.k7 / s.n2), slabs, rowvals, h->GZn, h->hmax, h->nmask, h->Zpair,
                            want_vals, mse ? h->M : nullptr, s.ld, h->r, s.kmse2, kl ? h->klA : nullptr, kl ? h->kl1 : nullptr,
                            kl ? h->klpart : nullptr);
   return 0;
@@ -614,7 +623,7 @@ static int decode_fly(const FusedStep& s, hipStream_t s4, bool forked, bool zero
 // ... and its end on s4, behind whatever the variant put there: fs_dec_forked asks the first reader of its results to join
 static int decode_end(const FusedStep& s, hipStream_t s4, bool forked) {
   if (forked) MCGRA_HIP(hipEventRecord(s.h->ev_join4, s4));
-  s.h->fs_dec_forked = forked;
+  s.h->step.fs_dec_forked = forked;
   return 0;
 }
 // monolithic: the results go to scal, the masked-pair count is posted from the decode's stream
@@ -632,8 +641,8 @@ static int decode_monolithic(FusedStep& s) {
   //  MSELoss 0.248 -> 0.214 ms, KL 0.307 -> 0.271; A/B MCGRA_MSE_DECODE_SIDE=1)
   hipStream_t s4 = (h->st3 != st && n < 4096 && (!mse || h->mse_decode_side)) ? h->st4 : st;
   // (with c2, k_post_mask leaves the counter at zero for the next fused step; the general path does not)
-  CHK(decode_fly(s, s4, s4 != st, !h->nmask_zero, h->ws_dec, h->rowvals, want_vals));
-  if (want_vals) launch_reduce_rows(s4, h->rowvals, h->fs_np, 1, h->scal + S_V7);
+  CHK(decode_fly(s, s4, s4 != st, !h->step.nmask_zero, h->ws_dec, h->rowvals, want_vals));
+  if (want_vals) launch_reduce_rows(s4, h->rowvals, h->step.fs_np, 1, h->scal + S_V7);
   if (kl) {      // v_i for the tail; their sum / n is the value of c2 (k_kl_rows' slot)
     fl_kl_v_fin(s4, n, R0, R1, h->klpart, h->klvsum, h->klv);
     if (want_vals) launch_reduce_rows(s4, h->klvsum, n, 1, h->scal + S_H2);
@@ -641,7 +650,7 @@ static int decode_monolithic(FusedStep& s) {
   if (use2) {
     hipLaunchKernelGGL(k_post_mask, dim3(1), dim3(1), 0, s4, h->nmask, nullptr, h->mask_seq_dev, h->mask_host_dev);
     h->mask_want = ++h->mask_seq;      // the host's count moves with the enqueue: an abandoned step cannot skew it
-    h->nmask_zero = true;
+    h->step.nmask_zero = true;
   }
   return decode_end(s, s4, s4 != st);
 }
@@ -660,7 +669,7 @@ static int decode_rank(FusedStep& s) {
   // they ride in the gather of the first low-rank product below (or, without c2, in a gather of their own)
   const Stage sg = use2 ? wide_stage(h) : narrow_stage(h);
   hipLaunchKernelGGL(k_u32x2_to_f64, dim3(1), dim3(1), 0, s4, h->nmask, lane_slot(h, sg, 0), lane_slot(h, sg, 1));
-  if (h->fs_np > 0) launch_reduce_rows(s4, h->rowvals + 6 * (size_t)ld, h->fs_np, 1, lane_slot(h, sg, 2));
+  if (h->step.fs_np > 0) launch_reduce_rows(s4, h->rowvals + 6 * (size_t)ld, h->step.fs_np, 1, lane_slot(h, sg, 2));
   else MCGRA_HIP(hipMemsetAsync(lane_slot(h, sg, 2), 0, sizeof(double), s4));
   if (use2) rows_to_stage2(h, s4, sg, he, h->GZn, h->hmax, 0, 2, reinterpret_cast<const float*>(h->lrRs), 2, he);     // |xc_i|^2 (double) as two words
   else if (kl) {      // + the own rows' v_i, and the rank's share of c2's value in a fourth lane slot
@@ -716,9 +725,9 @@ static int fs_small_terms(FusedStep& s) {
   }
   if (s3 != st) MCGRA_HIP(hipEventRecord(h->ev_join3, s3));
 
-  if (h->sharded && h->fs_dec_forked) {      // the decode's rows and lane slots ride in the gather below
+  if (h->sharded && h->step.fs_dec_forked) {      // the decode's rows and lane slots ride in the gather below
     MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join4, 0));
-    h->fs_dec_forked = false;
+    h->step.fs_dec_forked = false;
   }
   return s.use2 ? xchg_fy(s) : GO;
 }
@@ -744,9 +753,9 @@ static int fs_lr_t(FusedStep& s) {
     }
   }
   if (use2) {
-    if (!h->t3_zero) {                                                                        // t3 = 0
+    if (!h->step.t3_zero) {                                                                        // t3 = 0
       MCGRA_HIP(hipMemset2DAsync(h->lrT + 2 * he, (size_t)h->lr_ldv * 4, 0, 4, n, st));
-      h->t3_zero = true;
+      h->step.t3_zero = true;
     }
     if (h->fused_post && he <= 32) {      // [W | W2] = Xc^T Vc and the per-column terms behind it in one launch
       launch_lrt_lr_post(st, n, he, h->fy, h->FV, fc, h->r, h->cmean, h->fstat, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC,
@@ -778,7 +787,7 @@ static int fs_decode_bwd(FusedStep& s) {
   const int n = s.n, ld = s.ld, hs = s.hs, L = s.L, Le = s.Le, C = s.C, he = s.he;
   const bool use2 = s.use2, want_vals = s.want_vals, use10 = s.use10;
   const double sg = s.sg, k2 = s.k2;
-  if (h->fs_dec_forked) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join4, 0)); h->fs_dec_forked = false; }
+  if (h->step.fs_dec_forked) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join4, 0)); h->step.fs_dec_forked = false; }
   if (use2) {
     launch_lr_xtz(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrQtZ);
     launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrDelta, h->lrRs, -2.f * (float)(sg * k2), h->GZn, h->hmax,
@@ -805,16 +814,16 @@ static int fs_decode_bwd(FusedStep& s) {
   // Backward of both chains, one product on M per level: columns [r o G_P_lv of the victim(adj_norm) chain | G_P_lu of
   // the modified_adj chain] (M symmetric: M^T G = M G; adj_norm^T G = r o (M (r o G) + r o G)), then
   // G_P_{l-1} = (G_T_l W_l^T) o relu'(P_{l-1}) for each chain.  fs_l / fs_l2: the levels still to do.
-  h->fs_l = L - 1;
-  h->fs_l2 = (use10 ? L - 1 : Le - 1);
+  h->step.fs_l = L - 1;
+  h->step.fs_l2 = (use10 ? L - 1 : Le - 1);
   return GO;
 }
 // one level of that backward: the product, while fs_l / fs_l2 have levels left ...
 static int fs_bwd_product(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, fc = s.fc;
-  if (!(h->fs_l >= 1 || h->fs_l2 >= 1)) { h->fs_state = FS_TAIL_FRONT; return GO; }
-  const int lv = h->fs_l, lu = h->fs_l2;
+  if (!(h->step.fs_l >= 1 || h->step.fs_l2 >= 1)) { h->fs_state = FS_TAIL_FRONT; return GO; }
+  const int lv = h->step.fs_l, lu = h->step.fs_l2;
   const int wv = lv >= 1 ? h->wdt[lv] : 0, wu = lu >= 1 ? h->wdt[lu] : 0;
   const float* Xs[2] = {h->GPv + h->off[lv >= 1 ? lv : 0], h->GPu + h->off[lu >= 1 ? lu : 0]};
   const float* rs[2] = {h->r, nullptr};
@@ -828,7 +837,7 @@ static int fs_bwd_product(FusedStep& s) {
 static int fs_bwd_post(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, Le = s.Le, fc = s.fc;
-  const int lv = h->fs_l, lu = h->fs_l2;
+  const int lv = h->step.fs_l, lu = h->step.fs_l2;
   const int wv = lv >= 1 ? h->wdt[lv] : 0;
   if (lv >= 1 && lu >= 1 && h->fused_post && fl_bwd_level_supported(wv, h->wdt[lu], h->wdt[lv - 1], h->wdt[lu - 1])) {
     // both chains' level in one launch (k_an_post + k_copy_cols + two k_rowmat_mask: same operations, same order)
@@ -848,8 +857,8 @@ static int fs_bwd_post(FusedStep& s) {
                          h->GPu + h->off[lu - 1], hs);
     }
   }
-  if (lv >= 1) --h->fs_l;
-  if (lu >= 1) --h->fs_l2;
+  if (lv >= 1) --h->step.fs_l;
+  if (lu >= 1) --h->step.fs_l2;
   h->fs_state = FS_BWD_PRODUCT;
   return GO;
 }
@@ -867,17 +876,17 @@ static int fs_tail_front(FusedStep& s) {
   // (the coefficient of the norm term comes out of k_tail_gd's launch; a rank without rows has no Adam pass to feed)
   if (!(h->fused_post && R1 > R0)) hipLaunchKernelGGL(k_cn, dim3(1), dim3(1), 0, st, h->scal, (float)(c.weight_sup * 0.001), h->mm + 2);
   // (a cut product: the peers' row panels are done at ev_first; the own ones are joined behind the all-to-all)
-  if (h->p1_first && h->p1_inflight) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
+  if (h->carry.p1_first && h->step.p1_inflight) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
   else {
-    if (h->tail_rows > 0 && h->p1_inflight) {      // the pass over the rows that are complete, beside the product's last rounds
+    if (h->step.p1_inflight && h->step.tail_rows > 0) {      // the pass over the rows that are complete, beside the product's last rounds
       MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
-      (void)tail_reduce_call(s, 2, 0, h->tail_rows, false);
-      if (h->tail_rows2 > h->tail_rows) {
+      (void)tail_reduce_call(s, 2, 0, h->step.tail_rows, false);
+      if (h->step.tail_rows2 > h->step.tail_rows) {
         MCGRA_HIP(hipStreamWaitEvent(st, h->ev_second, 0));
-        (void)tail_reduce_call(s, 2, h->tail_rows, h->tail_rows2, false);
-        h->tail_rows = h->tail_rows2;
+        (void)tail_reduce_call(s, 2, h->step.tail_rows, h->step.tail_rows2, false);
+        h->step.tail_rows = h->step.tail_rows2;
       }
-    } else h->tail_rows = 0;
+    } else h->step.tail_rows = 0;
     CHK(join_p1(s));
   }
   // TEST-ONLY mutation guard (tests/test_gpu_fullsize.py; armed by mcgra_attack_test_mutate, which says so on stderr): 1
@@ -898,22 +907,22 @@ static int fs_tail_reduce(FusedStep& s) {
   const int n = s.n, ld = s.ld, R0 = s.R0, R1 = s.R1;
   const bool mse = s.mse, kl = s.kl, use1 = s.use1, want_vals = s.want_vals;
   CHK(join_p1(s));
-  h->p1_first = false;
+  h->carry.p1_first = false;
   if (h->sharded && use1 && R1 > R0)
     hipLaunchKernelGGL(k_a2a_unpack, dim3(2, h->rpr, h->world), dim3(256), 0, st, n, ld, h->rpr, R0, R1, h->rank, h->A2R, h->KX);
   {
     float* ps1 = tail_ps(h);
     double* vpart = tail_vpart(h);
-    h->fs_nblk = tail_reduce_call(s, 2, h->sharded ? R0 : h->tail_rows, R1, want_vals);
-    h->tail_rows = 0;
+    h->step.fs_nblk = tail_reduce_call(s, 2, h->sharded ? R0 : h->step.tail_rows, R1, want_vals);
+    h->step.tail_rows = 0;
     const Stage sgt = narrow_stage(h);
-    if (h->sharded && !(h->fs_nblk > 0 && want_vals)) CHK(lane_zero(h, st, sgt, (mse && !kl) ? 3 : 2));
-    if (h->fs_nblk > 0 && want_vals) {
+    if (h->sharded && !(h->step.fs_nblk > 0 && want_vals)) CHK(lane_zero(h, st, sgt, (mse && !kl) ? 3 : 2));
+    if (h->step.fs_nblk > 0 && want_vals) {
       // HSIC: sum P1 o Xc -> S_H1; MSELoss: sum (F - adj_norm)^2 -> S_V1 and sum (adj_norm - A1)^2 -> S_V2 (k_loss_elem's slots);
       // KL: calc_kl(feature_adj, adj_norm) -> S_H1 (k_kl_rows' slot; c2's value came out of the decode)
-      launch_reduce_rows(st, vpart, h->fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 0) : h->scal + ((mse && !kl) ? S_V1 : S_H1));
-      launch_reduce_rows(st, vpart + h->fs_nblk, h->fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 1) : h->scal + S_V6);
-      if (mse && !kl) launch_reduce_rows(st, vpart + 2 * (size_t)h->fs_nblk, h->fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 2) : h->scal + S_V2);
+      launch_reduce_rows(st, vpart, h->step.fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 0) : h->scal + ((mse && !kl) ? S_V1 : S_H1));
+      launch_reduce_rows(st, vpart + h->step.fs_nblk, h->step.fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 1) : h->scal + S_V6);
+      if (mse && !kl) launch_reduce_rows(st, vpart + 2 * (size_t)h->step.fs_nblk, h->step.fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 2) : h->scal + S_V2);
     }
     {
       const bool cn_in_gd = h->fused_post && R1 > R0;
@@ -953,7 +962,7 @@ static int fs_decide(FusedStep& s) {
     masked = code >= 2u;
     if (code == 1u) ++h->masked_fused_steps;
   }
-  if (masked) h->fs_l = 0;      // (the gathers below count in it)
+  if (masked) h->step.fs_l = 0;      // (the gathers below count in it)
   else h->fs_state = FS_ADAM;
   return GO;
 }
@@ -963,14 +972,14 @@ static int fs_decide(FusedStep& s) {
 static int fs_gather_send(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int ld = s.ld, R0 = s.R0, R1 = s.R1;
-  if (h->fs_l >= 3) {
+  if (h->step.fs_l >= 3) {
     h->fs_state = 0;
     h->fs_open = false;
-    h->planes_valid = false;
+    h->step.planes_valid = false;
     return REDO;
   }
   if (h->sharded && R1 > R0) {
-    float* src = h->fs_l == 0 ? h->M : (h->fs_l == 1 ? h->am : h->av);
+    float* src = h->step.fs_l == 0 ? h->M : (h->step.fs_l == 1 ? h->am : h->av);
     MCGRA_HIP(hipMemcpyAsync(h->NXS + (size_t)R0 * ld, src + (size_t)R0 * ld, sizeof(float) * (size_t)(R1 - R0) * ld,
                              hipMemcpyDeviceToDevice, st));
   }
@@ -980,10 +989,10 @@ static int fs_gather_send(FusedStep& s) {
 static int fs_gather_recv(FusedStep& s) {
   mcgra_attack* h = s.h;
   if (h->sharded) {
-    float* dst = h->fs_l == 0 ? h->M : (h->fs_l == 1 ? h->am : h->av);
+    float* dst = h->step.fs_l == 0 ? h->M : (h->step.fs_l == 1 ? h->am : h->av);
     MCGRA_HIP(hipMemcpyAsync(dst, h->NXS, sizeof(float) * (size_t)s.n * s.ld, hipMemcpyDeviceToDevice, s.st));
   }
-  ++h->fs_l;
+  ++h->step.fs_l;
   h->fs_state = FS_GATHER_SEND;
   return GO;
 }
@@ -1009,7 +1018,7 @@ static int fs_adam(FusedStep& s) {
     MCGRA_KERNEL_CHECK();
   }
   fused_commit(h);
-  if (c.num_edges < 0.5 * s.n2) { CHK(project(h, st)); h->prep_valid = false; }      // (monolithic only: refused at create otherwise)
+  if (c.num_edges < 0.5 * s.n2) { CHK(project(h, st)); h->carry.prep_valid = false; }      // (monolithic only: refused at create otherwise)
   if (h->sharded && h->fs_want) {
     // sum(clamp(adj_changes, 0, 1)) after the update = the row sums the Adam pass just left behind, own rows
     prep_from_partials(st, n, h->G_A, adam_row_sums(h, cnt), h->d, h->r, h->rowsq, h->rowsum, R0, R1);
@@ -1089,7 +1098,8 @@ int mcgra_attack_shard_begin(mcgra_attack_t* h, void* stream, int what, int want
   if (what != MCGRA_SHARD_STEP && what != MCGRA_SHARD_MONITOR && what != MCGRA_SHARD_MONITOR_LAST) { set_error("what = %d", what); return MCGRA_EINVAL; }
   // a step that was begun and never ran to XCHG_DONE (the caller gave up on a collective): its leftovers are dropped
   // by fused_resync at the top of the next step (fs_open is still set); a monitor call holds no such state
-  if (h->fs_active && h->fs_what == MCGRA_SHARD_MONITOR) h->fused_fwd_valid = false;
+  // Rule: none (no stream work).  An abandoned monitoring forward overwrote part of what the last one left:
+  if (h->fs_active && h->fs_what == MCGRA_SHARD_MONITOR) h->carry.fused_fwd_valid = false;
   h->fs_last = what == MCGRA_SHARD_MONITOR_LAST;
   if (h->fs_last) what = MCGRA_SHARD_MONITOR;
   h->fs_what = what; h->fs_want = want_scalars ? 1 : 0;
@@ -1102,6 +1112,7 @@ int mcgra_attack_shard_begin(mcgra_attack_t* h, void* stream, int what, int want
 int mcgra_attack_shard_next(mcgra_attack_t* h, void* stream, mcgra_exchange_t* ex) {
   if (!h || !ex) { set_error("null argument"); return MCGRA_EINVAL; }
   if (!h->fs_active) { set_error("mcgra_attack_shard_begin first"); return MCGRA_EINVAL; }
+  // Rule: as monitor (none; fork_p1_early drops in front of a second fork) / as step (fs_begin and fs_pack_fork take, step_general drops)
   hipStream_t st = (hipStream_t)stream;
   ex->kind = MCGRA_XCHG_DONE; ex->count = 0; ex->offset = ex->offset2 = ex->chunk_bytes = 0;
   int rc;
@@ -1110,7 +1121,7 @@ int mcgra_attack_shard_next(mcgra_attack_t* h, void* stream, mcgra_exchange_t* e
     if (rc == 1) return 0;
     h->fs_active = false;
     if (rc < 0) return rc;
-    h->fused_fwd_valid = true;
+    h->carry.fused_fwd_valid = true;
     return 0;
   }
   rc = fused_step_pt(h, st, ex);
@@ -1126,7 +1137,7 @@ int mcgra_attack_shard_next(mcgra_attack_t* h, void* stream, mcgra_exchange_t* e
   return rc;
 }
 
-int mcgra_attack_shard_scalars(mcgra_attack_t* h, void* stream, double* out) {
+int mcgra_attack_shard_scalars(mcgra_attack_t* h, void* stream, double* out) {      // Rule: none.  It reads scalar slots the caller's stream wrote.
   if (!h || !out) { set_error("null argument"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   if (h->fs_what == MCGRA_SHARD_MONITOR) {
@@ -1160,7 +1171,7 @@ int mcgra_attack_test_mutate(mcgra_attack_t* h, int what) {
 
 int mcgra_attack_product_replay(mcgra_attack_t* h, void* stream, int reps, double* ms_per_launch) {
   if (!h || reps < 1) { set_error("bad argument"); return MCGRA_EINVAL; }
-  if (!h->fused_ok || h->fused_mse || !h->fused_last || h->cfg.w[0] == 0.f) {
+  if (!h->fused_ok || h->fused_mse || !h->carry.fused_last || h->cfg.w[0] == 0.f) {
     set_error("product_replay: the last step must have been a fused low-rank step with the c1 term (w1 != 0)");
     return MCGRA_EINVAL;
   }
@@ -1169,8 +1180,9 @@ int mcgra_attack_product_replay(mcgra_attack_t* h, void* stream, int reps, doubl
   hipStream_t st = (hipStream_t)stream;
   const int P = split3_panel(), p_off = h->row0 / P, p_cnt = h->row1 > h->row0 ? (h->row1 - h->row0 + P - 1) / P : 0;
   if (p_cnt == 0) { if (ms_per_launch) *ms_per_launch = 0.0; return 0; }
-  if (h->early_pack) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));      // (planes a monitor call is still packing: equally valid operands)
-  if (h->p1_early) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));        // (a product a row-block rank's forward forked writes the same scratch)
+  // Rule: wait.  Planes a monitor call is still packing are equally valid operands, and a product a row-block rank's forward forked
+  // writes the same scratch.  (The Kx wait it includes never fires here: kx_early_on requires !lr_ok, this call a fused low-rank step.)
+  CHK(carry_wait(h, st));
   hipEvent_t e0, e1;
   MCGRA_HIP(hipEventCreate(&e0));
   MCGRA_HIP(hipEventCreate(&e1));
@@ -1188,7 +1200,7 @@ int mcgra_attack_product_replay(mcgra_attack_t* h, void* stream, int reps, doubl
   return 0;
 }
 
-int mcgra_attack_get_rows(mcgra_attack_t* h, void* stream, float* out) {
+int mcgra_attack_get_rows(mcgra_attack_t* h, void* stream, float* out) {      // Rule: none.  It reads M, which whatever is in flight also only reads.
   if (!h || !out) { set_error("null argument"); return MCGRA_EINVAL; }
   const int r0 = h->sharded ? h->row0 : 0, r1 = h->sharded ? h->row1 : h->n;
   if (r1 > r0)

@@ -27,8 +27,77 @@ struct GemmTimer {
   double flops = 0;
 };
 
+// ---- What a call leaves for the next (the same table and invariants)
+// (I1) An in-flight flag is true exactly from the launch that forks the work until a wait on its event has been enqueued on the
+//      caller's stream by whoever adopts or drops it.
+// (I2) An adoptable result is true only while M, the model and the graph are the ones it was computed from.
+// (I3) No entry reads a StepScratch field before writing it in the same step or forward (a row-block rank's step or forward spans
+//      mcgra_attack_shard_begin to its last shard_next).  The exceptions are written out at StepScratch.
+// Three transitions change a Carry field from outside the code that forks or adopts it (attack_fused.hip):
+//   carry_wait     the caller's stream waits for the event of every in-flight item; no flag changes
+//   carry_drop     carry_wait, then the in-flight items and their bookkeeping are cleared (their results are scratch nobody reads)
+//   carry_forget   M, the model or the graph changed: the adoptable results are cleared (fused_last describes the last STEP, not
+//                  M: only a fused commit and the general step write it)
+// Besides them a Carry field is written where the work is forked or its result stands (fw_prep, fork_p1 / fork_p1_early, the
+// monitor call, the Adam passes, hsic_terms' masked-pair count, shard_next), and where a step adopts it (fs_begin, fs_pack_fork,
+// step_general).  Every extern "C" entry that takes (h, stream) opens with its rule; a new entry point is a new row:
+//
+//   entry                          rule            what and why
+//   set_model                      forget          nothing in flight reads the model (the pack reads M and r, the products read planes)
+//   set_graph                      drop + forget   skip_fused is kept (see there: a hint about the order of the paths, never about a result)
+//   set_adj_changes                drop + forget   M is overwritten: a pack may still be reading it
+//   get_adj_changes, get_rows      none            they read M, which whatever is in flight also only reads
+//   step (step_general)            take, drop      the fused step goes first (below); the general step adopts the cached forward and the Kx
+//                                                  forked with it, and drops the rest: it packs its own operands
+//     ... fused (fs_begin,         take            the forward a monitor call left, its pack (joined at ev_pack) and a row-block rank's
+//         fs_pack_fork)                            product (handed to step.p1_inflight, joined by join_p1); an abandoned step: fused_resync
+//   monitor                        none            it adds to what is in flight.  Forking an item again replaces it: the pack on its own side
+//                                                  stream (fw_prep), Kx and a rank's product behind a drop (two monitor calls in a row)
+//   finalize                       drop + forget   M is overwritten by the decode; skip_fused is kept (a step may follow: the parity tests do)
+//   copy_buffer, product_replay    wait            scratch under a forked pack / product / Kx is read (or timed over) on the caller's stream
+//   shard_begin                    none            no stream work; an abandoned monitoring forward takes the last one's result with it
+//   shard_next                     as step / monitor
+//   shard_scalars                  none            it reads scalar slots that the caller's stream wrote
+//   buffer (no stream)             --              raw pointers: read them through copy_buffer, or behind the wait it performs
+struct Carry {
+  // -- adoptable results (I2)
+  bool fwd_cached = false;         // adj_norm (ADJN_next), d, r, the victim chain and log-probs of the CURRENT M (general monitor call; fwd_reuse)
+  bool fused_fwd_valid = false;    // both chains, heads, d / r / mean of the CURRENT M are in place (left by the fused monitor call)
+  bool prep_valid = false;         // G_A holds the per-tile row sums of the current M (left by the Adam pass of the tail kernels)
+  bool skip_fused = false;         // the last step's decode masked a pair: the general path goes first (it re-checks).  A hint: stale, it costs
+                                   //   one step by the slower path, so set_graph, finalize and fused_resync keep it (carry_forget's argument)
+  bool fused_last = false;         // the last step ran fused: adj_norm of that iteration was never stored (see em_last)
+  // -- in flight on the side stream when the call returns (I1), each with the event that ends it
+  bool early_pack = false;         // ev_pack: Bpack / the pack's row partials of the CURRENT M (packed beside the forward of this M)
+  bool kx_early = false;           // ev_first (gram_ovl; else it ran on the caller's stream): Kx of the current M, forked by the last monitor call
+  bool p1_early = false;           // ev_join: a row-block rank's pack + product, forked by the forward of the CURRENT M.  Its bookkeeping:
+  bool p1_first = false;           //   the forked product was cut (the all-to-all waits for ev_first only; also set by a step's own fork)
+  int p1_early_cut = 0, p1_early_split = 0;      //   what that launch adds to cut_product_steps / split_steps once a step takes it
+};
+// Scratch flags of one step or forward: on the handle only because the stages need them.  Exceptions to (I3):
+//  - p1_inflight stays set, together with carry.p1_early, across the return of a row-block rank's forward (fs_pack_fork takes both);
+//  - nmask_zero and t3_zero remember that a zero fill is still in place from the step before.  false is always right (the fill is
+//    redone), so whoever may have written the words -- the general step, set_graph, an abandoned step -- just clears them.
+struct StepScratch {
+  bool lr_step = false;            // general step: it takes the low-rank form (no relu-masked pair in the decode)
+  bool p1_inflight = false;        // the product P1 is forked and not yet joined
+  int tail_rows = 0, tail_rows2 = 0;   // rows behind the first / second cut of this step's product (0: no early tail pass)
+  bool planes_valid = false;       // uncentred planes of the CURRENT M are in Bpack (between the pack of a step and its Adam pass: planes_mm)
+  bool nmask_zero = false;         // the decode's masked-pair counter holds 0 (left so by k_post_mask)
+  bool t3_zero = false;            // column 2 he of lrT (t3 of the low-rank factors) holds zeros (fused step; the general path writes it)
+  // the fused step's stages (attack_fused.hip)
+  bool fs_adopted = false;         // fs_begin: the step took the forward a monitor call left (fs_forward then passes)
+  int fs_l = 0;                    // fw_layer_product / fw_layer_post: the forward's layer; fs_decode_bwd, fs_bwd_product / fs_bwd_post:
+  int fs_l2 = 0;                   //   the backward levels still to do, victim chain | modified_adj chain; fs_gather_*: the gather (fs_l)
+  int fs_np = 0;                   // fs_decode: row partials of the decode's entropy term
+  int fs_nblk = 0;                 // fs_tail_reduce: blocks of the tail's first pass (partials of the loss terms' values)
+  bool fs_dec_forked = false;      // fs_decode: the decode runs on the fourth stream; its first reader joins it (fs_small_terms, fs_decode_bwd)
+};
+
 struct mcgra_attack {
   mcgra_attack_config_t cfg;
+  Carry carry;                     // what the last call left for the next (above)
+  StepScratch step;                // scratch flags of the step / forward in progress (above)
   mcgra::AttackPlan plan;          // what create decided (attack_plan.h), never written again; apply_plan copies it into the fields below
   int n = 0, ld = 0, L = 0, Le = 0, C = 0, na = 0, hsum = 0, hmax = 0;
   int off[MCGRA_MAX_LAYERS + 1];   // column offset of layer l inside the concatenated node buffers
@@ -41,9 +110,8 @@ struct mcgra_attack {
   // iteration (:164-167) when eps == 0: mcgra_attack_monitor leaves its adj_norm, degree vectors, chain and
   // log-probs in place and the next step adopts them instead of recomputing (bit-identical, one N x N pass and two
   // skinny products less per step).  MCGRA_NO_FWD_REUSE=1 disables.
-  bool fwd_cached = false, fwd_reuse = true;
+  bool fwd_reuse = true;           // (the adoption itself: Carry::fwd_cached)
   bool fuse_tail = true;           // apply + rank-k + mirror + Adam in one kernel (MCGRA_NO_FUSED_TAIL=1: separate kernels)
-  bool prep_valid = false;         // G_A holds the per-tile row sums of the current M (left by the fused tail kernel)
   int test_mutate = 0;             // TEST-ONLY (mcgra_attack_test_mutate, see attack_fused.hip): 1 wipes P1, 2 drops the tail's rank-k terms,
                                    // 3 zeroes MSELoss / KL's per-pair multipliers, 4 wipes the KL row statistics
   bool keep_gsym = false;          // MCGRA_KEEP_GSYM=1: keep the mirrored packed gradient of each step readable as "G_sym" (parity tests)
@@ -91,7 +159,6 @@ struct mcgra_attack {
   bool profile = false;
   // low-rank linear_HSIC(adj_norm, modified_adj1) (lowrank_kernels.hip); MCGRA_NO_LOWRANK=1 disables
   bool lr_ok = false;              // configuration allows it (HSIC, ReLU embedding, width <= 32)
-  bool lr_step = false;            // the step in flight takes it (no relu-masked pair in the decode)
   int lr_ldv = 0;
   float *lrL = 0, *lrV = 0, *lrT = 0, *lrR = 0, *lrQ = 0, *lrDelta = 0, *lrC = 0;
   double *lrStats = 0, *lrRs = 0, *lrQtZ = 0;
@@ -105,24 +172,19 @@ struct mcgra_attack {
   // the first part, the P1 all-to-all then runs beside the second (attack_fused.hip; MCGRA_A2A_OVERLAP=0 / 1 forces off / on)
   hipEvent_t ev_first = nullptr, ev_second = nullptr;
   int a2a_overlap = 0;             // 0: the product in one piece; 1: cut where it is free or cheap (default); 2: always (MCGRA_A2A_OVERLAP=1)
-  bool p1_first = false;           // the forked product of this step was cut: the all-to-all waits for ev_first only
   // monolithic, n >= 8192: the product is cut behind whole rounds of the chip that cover the first `tail_rows` rows of P1 (both
   // orientations); the tail's first pass over those rows runs beside the product's last rounds (MCGRA_EARLY_TAIL=0 disables)
   bool early_tail_on = true;
-  int tail_rows = 0, tail_rows2 = 0;   // rows behind the first / second cut of this step's product (0: no early tail pass)
   // early pack (attack_fused.hip): the planes of the product's operand are packed on the product's stream as soon as r is
   // known, beside the forward's two products on the caller's stream (ev_r: r ready; ev_pack: planes and row partials ready)
   hipEvent_t ev_r = nullptr, ev_pack = nullptr;
   bool early_pack_on = true;       // MCGRA_EARLY_PACK=0 disables (A/B)
-  bool early_pack = false;         // Bpack / the pack's row partials describe the CURRENT M (packed by the forward of this M)
   bool mse_small_inline = true;    // fused MSELoss step on a small graph: the two one-launch small-operand terms on the caller's stream (MCGRA_MSE_SMALL_INLINE=0: third stream; A/B)
   bool mse_decode_side = false;    // fused MSELoss / KL step on a small graph: the decode on the fourth stream as in the HSIC step (MCGRA_MSE_DECODE_SIDE=1; A/B)
   bool early_p1_on = false;        // row-block rank: pack (uncentred) + N x N x N product forked by the FORWARD, as soon as r is complete
-  bool p1_early = false;           // ... and in flight: forked by the forward of the CURRENT M (a monitor call, or the step's own)
   float* small_slab = nullptr;     // split-K slabs of a small graph's N x N x N products (more than an N x N buffer holds: split3_small_slab_bytes)
   size_t small_slab_bytes = 0;
   bool fs_last = false;            // the monitor call in progress was begun as MCGRA_SHARD_MONITOR_LAST
-  int p1_early_cut = 0, p1_early_split = 0;      // what that launch adds to cut_product_steps / split_steps once a step takes it
   // third stream of the fused step: the small-operand terms c9 / c10 (a chain of ~16 tiny launches that needs only the
   // forward) run beside the low-rank factor chain; its products use their own split-K workspace
   hipStream_t st3 = nullptr;
@@ -141,12 +203,8 @@ struct mcgra_attack {
   unsigned int* mask_seq_dev = nullptr;          // device-side counter of the posts
   unsigned int mask_seq = 0;                     // posts enqueued so far (moves where k_post_mask is launched)
   unsigned int mask_want = 0;                    // sequence number of the post the step in flight will poll for
-  bool p1_inflight = false;
-  bool skip_fused = false;         // the last step's decode masked a pair: the general path goes first (it re-checks)
   int64_t cut_product_steps = 0;   // row-block steps whose product was cut for the all-to-all (a2a_overlap)
   int64_t masked_fused_steps = 0;  // fused steps whose decode relu-masked pairs of live rows (they stand: DESIGN.md section 1b)
-  bool nmask_zero = false;         // the decode's masked-pair counter holds 0 (left so by k_post_mask)
-  bool t3_zero = false;            // column 2 he of lrT (t3 of the low-rank factors) holds zeros (fused step; the general path writes it)
   bool overlap = false;            // MCGRA_OVERLAP=1 forks the N x N x N product onto the engine's own stream
   // P1 through the split kernel of split_symm_bf16.hip instead of the fp32 MFMA SYMM
   bool split_on = false;
@@ -165,7 +223,6 @@ struct mcgra_attack {
   // CURRENT M only -- the monitoring forward forks pack + Kx as soon as adj_norm stands, and the next step finds them in flight
   bool kx_early_on = false;        // (MCGRA_GRAM_KX_EARLY=0: the step packs and forks Kx itself, as in round 5)
   bool small_side_on = false;      // general step: the small-operand terms c9 / c10 (~20 tiny launches) on the third stream, beside the decode and the N x N passes (MCGRA_SMALL_SIDE=0: caller's stream)
-  bool kx_early = false;           // Kx of the current M is in flight / done on the side stream, forked by the last monitor call
   double* gram_diag = 0;           // [2][ld]: |xc_i|^2, |yc_i|^2 (diagonals of the centred Grams: scale bound of the combined Grams)
   unsigned char *Gp0 = 0, *Gp1 = 0, *Gp2 = 0;
   int64_t gram_split_steps = 0;
@@ -176,8 +233,6 @@ struct mcgra_attack {
   bool fused_kl = false;           // ... as the fused KL step (calc = calc_kl: the MSELoss step's data flow + per-row softmax statistics)
   float *klA = 0, *kl1 = 0, *klv = 0;      // fused KL step: logsumexp of adj_norm's rows, of modified_adj1's rows, v_i = the row's share of c2
   double *klpart = 0, *klvsum = 0;         // ... per-(column slice, row) partials of the two passes [64][n][2]; v_i in fp64 [ld]
-  bool fused_fwd_valid = false;    // both chains, heads, d / r / mean of the CURRENT M are in place (left by the monitor call)
-  bool fused_last = false;         // the last step ran fused: adj_norm of that iteration was never stored (see em_last)
   int fcols = 0;                   // leading dimension of FV / FY
   float *FV = 0, *FY = 0;          // right-hand sides / results of the skinny products on M  [n x fcols]
   mcgra::YView fy{nullptr, 0, 1, 0};      // the last such product as its consumers read it (FY, or the split-K slabs in ws)
@@ -190,7 +245,7 @@ struct mcgra_attack {
   bool late_mean = false;
   // ... and with uncentred planes of the CURRENT M in Bpack (between the pack of a step and its Adam pass) the skinny
   // products on M that run beside the N x N x N product read those planes (planes_mm.hip).  MCGRA_PLANES_MM=0 disables.
-  bool planes_mm_on = false, planes_valid = false;
+  bool planes_mm_on = false;       // (the planes' validity: StepScratch::planes_valid)
   bool fused_post = true;          // forward: post pass + next layer's T / heads in one launch (MCGRA_NO_FUSED_POST=1: separate kernels)
   char* pm_scratch = nullptr;
   // Monolithic fused step with the early pack: the forward's two skinny products on the bf16x3 kernel whose blocks fit beside a
@@ -216,13 +271,7 @@ struct mcgra_attack {
   int fs_what = 0, fs_want = 0;    // what mcgra_attack_shard_begin asked for: MCGRA_SHARD_*; scalars (2: already collected)
   bool fs_active = false;          // between shard_begin and the last shard_next
   bool fs_open = false;            // a fused step was started and has not reached a regular exit (see fused_resync)
-  // ... and the stages' own counters and flags:
-  bool fs_adopted = false;         // fs_begin: the step took the forward a monitor call left (fs_forward then passes)
-  int fs_l = 0;                    // fw_layer_product / fw_layer_post: the forward's layer; fs_decode_bwd, fs_bwd_product / fs_bwd_post:
-  int fs_l2 = 0;                   //   the backward levels still to do, victim chain | modified_adj chain; fs_gather_*: the gather (fs_l)
-  int fs_np = 0;                   // fs_decode: row partials of the decode's entropy term
-  int fs_nblk = 0;                 // fs_tail_reduce: blocks of the tail's first pass (partials of the loss terms' values)
-  bool fs_dec_forked = false;      // fs_decode: the decode runs on the fourth stream; its first reader joins it (fs_small_terms, fs_decode_bwd)
+  // ... and the stages' own counters and flags (step.fs_*)
   double fs_scalars[10] = {0};
 };
 
@@ -239,7 +288,9 @@ static inline bool adam_emits_partials(const mcgra_attack* h, bool may_project, 
 
 // attack_fused.hip
 bool fused_step_possible(const mcgra_attack* h);
-int drop_early_p1(mcgra_attack* h, hipStream_t st);      // a product forked by a row-block rank's forward whose step never came
+int carry_wait(mcgra_attack* h, hipStream_t st);         // the transitions of Carry (above)
+int carry_drop(mcgra_attack* h, hipStream_t st);
+void carry_forget(mcgra_attack* h, bool keep_skip_fused = false);
 int fused_forward(mcgra_attack* h, hipStream_t st);
 // returns 1 when the step must be redone by the general path (a relu-masked pair in the decode), 0 when done
 int fused_step(mcgra_attack* h, hipStream_t st, double* scalars_out);

@@ -655,6 +655,16 @@ def engine_from(pkg, z, device="cuda:0", measure=None, weight_param=None, **kw):
     return eng
 
 
+def shard_engines(pkg, z, world, joint=False, **kw):
+    """The row-block ranks of one attack inside this process: (plans, HipShardBackends) for sharded.run_lockstep."""
+    from mc_gra_amd.sharded import RowBlockPlan, HipShardBackend, lockstep_backends
+    n = z["adj"].shape[0]
+    plans = [RowBlockPlan(n, world, r) for r in range(world)]
+    if joint:      # arenas as rows of one tensor: run_lockstep's collectives become single strided copies
+        return plans, lockstep_backends([engine_from(pkg, z, plan=p, **kw) for p in plans], plans)
+    return plans, [HipShardBackend(engine_from(pkg, z, plan=p, **kw), p) for p in plans]
+
+
 class _Layer:
     def __init__(self, W, b):
         import torch

@@ -726,13 +726,7 @@ NXN_ONLY = (0.01, 0.01, 0, 0, 0, 10, 10, 0, 0, 0)        # c1, c2, c6, c7 only: 
 
 
 # ---- row-block sharded step (scope row (e)) -----------------------------------------------------------------
-def _shard_engines(pkg, z, world, joint=False, **kw):
-    from mc_gra_amd.sharded import RowBlockPlan, HipShardBackend, lockstep_backends
-    n = z["adj"].shape[0]
-    plans = [RowBlockPlan(n, world, r) for r in range(world)]
-    if joint:      # arenas as rows of one tensor: run_lockstep's collectives become single strided copies
-        return plans, lockstep_backends([H.engine_from(pkg, z, plan=p, **kw) for p in plans], plans)
-    return plans, [HipShardBackend(H.engine_from(pkg, z, plan=p, **kw), p) for p in plans]
+_shard_engines = H.shard_engines
 
 
 def _gather_rows(bks):
