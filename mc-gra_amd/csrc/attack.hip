@@ -82,7 +82,7 @@ int timer_end(mcgra_attack* h, hipStream_t st, bool big, double flops) {
 // every GEMM of the engine goes through here (timed when profiling)
 int eg(mcgra_attack* h, hipStream_t st, bool ta, bool tb, int M, int N, int K, float alpha, const float* A,
               int lda, const float* B, int ldb, float beta, float* C, int ldc, YView* keep) {
-  const bool big = h->profile && (double)M * N * K >= 0.25 * (double)h->n * h->n * h->n;
+  const bool big = h->profile && (double)M * N * K >= 0.25 * (double)h->p.n * h->p.n * h->p.n;
   CHK(timer_begin(h, st, big));
   MCGRA_HIP(sgemm(st, ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, h->ws, h->ws_bytes, keep));
   return timer_end(h, st, big, 2.0 * M * N * K);
@@ -107,28 +107,28 @@ static int eg_symm(mcgra_attack* h, hipStream_t st, int n, int m, const float* S
 // T[:, off[0]..] must already hold T_0 = X W_0.
 int chain_forward(mcgra_attack* h, hipStream_t st, const float* adj, int adj_ld, int depth, float* T, float* P,
                          float* H, float* S) {
-  const int n = h->n, hs = h->hsum;
+  const int n = h->p.n, hs = h->p.hsum;
   for (int l = 0; l < depth; ++l) {
-    const bool next = l + 1 < h->L;
-    if (!h->has_self && chain_post_fits(h->wdt[l], next ? h->wdt[l + 1] : 0)) {
+    const bool next = l + 1 < h->p.L;
+    if (!h->cfg.has_self && chain_post_fits(h->p.wdt[l], next ? h->p.wdt[l + 1] : 0)) {
       // the product stays in its split-K slabs and ONE launch sums them, adds the bias, applies the activation and forms the
       // next layer's T = H W_{l+1} (sum_slabs_kernel + k_bias_relu + k_rowmat: the same operations in the same order)
       YView y{nullptr, 0, 1, 0};
-      CHK(eg(h, st, false, false, n, h->wdt[l], n, 1.f, adj, adj_ld, T + h->off[l], hs, 0.f, h->Y, h->hmax, &y));
-      launch_chain_post(st, n, h->wdt[l], y, h->b[l], h->act, P + h->off[l], H + h->off[l], hs, next ? h->wdt[l + 1] : 0,
-                        next ? h->W[l + 1] : nullptr, next ? h->wdt[l + 1] : 0, 1, nullptr, next ? T + h->off[l + 1] : nullptr, hs);
+      CHK(eg(h, st, false, false, n, h->p.wdt[l], n, 1.f, adj, adj_ld, T + h->p.off[l], hs, 0.f, h->Y, h->p.hmax, &y));
+      launch_chain_post(st, n, h->p.wdt[l], y, h->b[l], h->cfg.act, P + h->p.off[l], H + h->p.off[l], hs, next ? h->p.wdt[l + 1] : 0,
+                        next ? h->W[l + 1] : nullptr, next ? h->p.wdt[l + 1] : 0, 1, nullptr, next ? T + h->p.off[l + 1] : nullptr, hs);
       continue;
     }
-    CHK(eg(h, st, false, false, n, h->wdt[l], n, 1.f, adj, adj_ld, T + h->off[l], hs, 0.f, h->Y, h->hmax));
-    const float* self = !h->has_self ? nullptr : (l == 0 ? h->S0 : S + h->off[l]);
-    launch_bias_relu(st, n, h->wdt[l], h->Y, h->hmax, h->b[l], self, l == 0 ? h->hmax : hs, h->act, P + h->off[l],
-                     H + h->off[l], hs);
-    if (l + 1 < h->L) {
-      launch_rowmat(st, n, h->wdt[l], h->wdt[l + 1], H + h->off[l], hs, h->W[l + 1], h->wdt[l + 1], 1, nullptr,
-                    T + h->off[l + 1], hs);
-      if (h->has_self)   // x W_top of the next GraphSAGE layer (graphsage.py:44-45)
-        launch_rowmat(st, n, h->wdt[l], h->wdt[l + 1], H + h->off[l], hs, h->Ws[l + 1], h->wdt[l + 1], 1, nullptr,
-                      S + h->off[l + 1], hs);
+    CHK(eg(h, st, false, false, n, h->p.wdt[l], n, 1.f, adj, adj_ld, T + h->p.off[l], hs, 0.f, h->Y, h->p.hmax));
+    const float* self = !h->cfg.has_self ? nullptr : (l == 0 ? h->S0 : S + h->p.off[l]);
+    launch_bias_relu(st, n, h->p.wdt[l], h->Y, h->p.hmax, h->b[l], self, l == 0 ? h->p.hmax : hs, h->cfg.act, P + h->p.off[l],
+                     H + h->p.off[l], hs);
+    if (l + 1 < h->p.L) {
+      launch_rowmat(st, n, h->p.wdt[l], h->p.wdt[l + 1], H + h->p.off[l], hs, h->W[l + 1], h->p.wdt[l + 1], 1, nullptr,
+                    T + h->p.off[l + 1], hs);
+      if (h->cfg.has_self)   // x W_top of the next GraphSAGE layer (graphsage.py:44-45)
+        launch_rowmat(st, n, h->p.wdt[l], h->p.wdt[l + 1], H + h->p.off[l], hs, h->Ws[l + 1], h->p.wdt[l + 1], 1, nullptr,
+                      S + h->p.off[l + 1], hs);
     }
   }
   MCGRA_KERNEL_CHECK();
@@ -137,9 +137,9 @@ int chain_forward(mcgra_attack* h, hipStream_t st, const float* adj, int adj_ld,
 
 // linear1 + log_softmax (models/gcn.py:173-174)
 int head_forward(mcgra_attack* h, hipStream_t st, const float* H, float* Z, float* logp, float* sm) {
-  const int l = h->L - 1;
-  launch_rowmat(st, h->n, h->wdt[l], h->C, H + h->off[l], h->hsum, h->Wlin, 1, h->wdt[l], h->blin, Z, h->C);
-  launch_log_softmax(st, h->n, h->C, Z, h->C, logp, sm, h->C, h->head_act);   // Z keeps the linear output
+  const int l = h->p.L - 1;
+  launch_rowmat(st, h->p.n, h->p.wdt[l], h->p.C, H + h->p.off[l], h->p.hsum, h->Wlin, 1, h->p.wdt[l], h->blin, Z, h->p.C);
+  launch_log_softmax(st, h->p.n, h->p.C, Z, h->p.C, logp, sm, h->p.C, h->cfg.head_act);   // Z keeps the linear output
   MCGRA_KERNEL_CHECK();
   return 0;
 }
@@ -148,23 +148,23 @@ int head_forward(mcgra_attack* h, hipStream_t st, const float* H, float* Z, floa
 // entry.  add_at/Add: extra gradient w.r.t. H_{add_at} (e.g. d loss / d em).
 int chain_backward(mcgra_attack* h, hipStream_t st, const float* adj, int adj_ld, int ltop, const float* P,
                           float* GP, int add_at, const float* Add, int add_ld) {
-  const int n = h->n, hs = h->hsum;
+  const int n = h->p.n, hs = h->p.hsum;
   for (int l = ltop; l >= 1; --l) {
-    if (!h->has_self && chain_post_fits(h->wdt[l], h->wdt[l - 1])) {
+    if (!h->cfg.has_self && chain_post_fits(h->p.wdt[l], h->p.wdt[l - 1])) {
       // G_T_l left in its split-K slabs, summed by the linear backward that reads it (one launch less per level)
       YView y{nullptr, 0, 1, 0};
-      CHK(eg(h, st, true, false, n, h->wdt[l], n, 1.f, adj, adj_ld, GP + h->off[l], hs, 0.f, h->GT, h->hmax, &y));
-      launch_rowmat_mask_view(st, n, h->wdt[l], h->wdt[l - 1], y, h->W[l], 1, h->wdt[l], P + h->off[l - 1], hs, h->act,
-                              (l - 1 == add_at) ? Add : nullptr, add_ld, GP + h->off[l - 1], hs);
+      CHK(eg(h, st, true, false, n, h->p.wdt[l], n, 1.f, adj, adj_ld, GP + h->p.off[l], hs, 0.f, h->GT, h->p.hmax, &y));
+      launch_rowmat_mask_view(st, n, h->p.wdt[l], h->p.wdt[l - 1], y, h->W[l], 1, h->p.wdt[l], P + h->p.off[l - 1], hs, h->cfg.act,
+                              (l - 1 == add_at) ? Add : nullptr, add_ld, GP + h->p.off[l - 1], hs);
       continue;
     }
     // G_T_l = adj^T @ G_P_l
-    CHK(eg(h, st, true, false, n, h->wdt[l], n, 1.f, adj, adj_ld, GP + h->off[l], hs, 0.f, h->GT, h->hmax));
+    CHK(eg(h, st, true, false, n, h->p.wdt[l], n, 1.f, adj, adj_ld, GP + h->p.off[l], hs, 0.f, h->GT, h->p.hmax));
     // G_P_{l-1} = (G_T_l @ W_l^T [+ Add]) * (P_{l-1} > 0)
     // (+ G_P_l @ Ws_l^T: the self path of a GraphSAGE layer)
-    launch_rowmat_mask(st, n, h->wdt[l], h->wdt[l - 1], h->GT, h->hmax, h->W[l], 1, h->wdt[l],
-                       h->has_self ? GP + h->off[l] : nullptr, hs, h->wdt[l], h->Ws[l], 1, h->wdt[l],
-                       P + h->off[l - 1], hs, h->act, (l - 1 == add_at) ? Add : nullptr, add_ld, GP + h->off[l - 1], hs);
+    launch_rowmat_mask(st, n, h->p.wdt[l], h->p.wdt[l - 1], h->GT, h->p.hmax, h->W[l], 1, h->p.wdt[l],
+                       h->cfg.has_self ? GP + h->p.off[l] : nullptr, hs, h->p.wdt[l], h->Ws[l], 1, h->p.wdt[l],
+                       P + h->p.off[l - 1], hs, h->cfg.act, (l - 1 == add_at) ? Add : nullptr, add_ld, GP + h->p.off[l - 1], hs);
   }
   MCGRA_KERNEL_CHECK();
   return 0;
@@ -183,36 +183,6 @@ int mcgra_device_count(void) {
   return c;
 }
 
-// The handle's working copies of what create planned.  A non-zero ori_adj takes the general path only: the fused / low-rank
-// forms assume modified_adj == M and modified_adj1 == offdiag relu(Zn Zn^T), and the monitoring forward (:290-293) runs on
-// the UNclamped M + ori, so there is nothing for the next step to adopt; a later graph without one has the planned paths again.
-static void apply_plan(mcgra_attack* h, bool has_ori) {
-  const AttackPlan& p = h->plan;
-  h->act = h->cfg.act; h->head_act = h->cfg.head_act; h->has_self = h->cfg.has_self;
-  h->fin0 = p.fin0; h->fin1 = p.fin1;
-  h->n = h->cfg.n; h->ld = p.ld; h->L = p.L; h->Le = p.Le; h->C = p.C; h->na = p.na; h->hsum = p.hsum; h->hmax = p.hmax;
-  for (int l = 0; l <= MCGRA_MAX_LAYERS; ++l) { h->off[l] = p.off[l]; h->wdt[l] = p.wdt[l]; }
-  h->keep_gsym = p.keep_gsym; h->testing = p.testing; h->fuse_tail = p.fuse_tail;
-  h->lr_ldv = p.lr_ldv;
-  h->split_on = p.split_on; h->split_planes = p.split_planes; h->split_single = p.split_single; h->split_mode = p.split_mode;
-  h->overlap = p.overlap; h->gram_ovl = p.gram_ovl; h->kx_early_on = p.kx_early_on; h->small_side_on = p.small_side_on;
-  h->fused_mse = p.fused == FUSED_MSE || p.fused == FUSED_KL;      // ("an elementwise measure": every branch of the MSELoss step that is not MSELoss' own arithmetic)
-  h->fused_kl = p.fused == FUSED_KL;
-  h->fcols = p.fcols;
-  h->fused_post = p.fused_post; h->early_pack_on = p.early_pack_on; h->early_p1_on = p.early_p1_on; h->early_tail_on = p.early_tail_on;
-  h->mse_decode_side = p.mse_decode_side; h->mse_small_inline = p.mse_small_inline;
-  h->fwd_x3 = p.fwd_x3; h->p1_behind_pack_on = p.p1_behind_pack_on;
-  h->sharded = p.sharded; h->world = p.world; h->rank = p.rank; h->rpr = p.rpr; h->npad = p.npad; h->row0 = p.row0; h->row1 = p.row1;
-  h->sgw = p.sgw; h->fyw = p.fyw; h->a2a_overlap = p.a2a_overlap;
-  h->has_ori = has_ori;
-  h->lr_ok = p.lr_ok && !has_ori;
-  h->fused_ok = p.fused != FUSED_NONE && !has_ori;
-  h->gram_split = p.gram_split && !has_ori;
-  h->late_mean = p.late_mean && !has_ori;
-  h->planes_mm_on = p.planes_mm_on && !has_ori;
-  h->fwd_reuse = p.fwd_reuse && !has_ori;
-}
-
 // the engine's own events (all without timing)
 static hipEvent_t mcgra_attack::* const ENGINE_EVENTS[] = {
     &mcgra_attack::ev_fork4, &mcgra_attack::ev_join4, &mcgra_attack::ev_fork,  &mcgra_attack::ev_join,  &mcgra_attack::ev_first,
@@ -223,13 +193,10 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
   if (!out || !cfg) { set_error("null argument"); return MCGRA_EINVAL; }
   AttackPlan plan;
   CHK(plan_attack(*cfg, read_plan_env(), &plan));
-  mcgra_attack* h = new mcgra_attack();
-  h->cfg = *cfg;
-  h->plan = plan;
-  apply_plan(h, false);
-  const AttackPlan& p = h->plan;
-  const size_t n = h->n, ld = h->ld, nn = n * ld;
-  const int he = h->wdt[h->Le - 1];
+  mcgra_attack* h = new mcgra_attack(*cfg, plan);
+  const AttackPlan& p = h->p;
+  const size_t n = h->p.n, ld = h->p.ld, nn = n * ld;
+  const int he = h->p.wdt[h->p.Le - 1];
   const bool hsic = cfg->measure == MCGRA_MEASURE_HSIC, cka = cfg->measure == MCGRA_MEASURE_CKA;
   int rc = 0;
 #define A_(f, cnt) if (!rc) rc = dalloc(h, &h->f, (cnt))
@@ -245,30 +212,30 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
   A_(mask_seq_dev, 1);
   A_(rowsq, 2 * ld); h->rowsum = h->rowsq ? h->rowsq + n : nullptr;
   A_(rowvals, 8 * ld); A_(rowsx, ld); A_(rowsy, ld); A_(scal, S_COUNT);
-  A_(labels, n); A_(idx, (size_t)h->na); A_(correct, 4);
-  for (int l = 0; l < h->L && !rc; ++l) {
+  A_(labels, n); A_(idx, (size_t)h->p.na); A_(correct, 4);
+  for (int l = 0; l < h->p.L && !rc; ++l) {
     rc = dalloc(h, &h->W[l], (size_t)cfg->dims[l] * cfg->dims[l + 1]);
     if (!rc) rc = dalloc(h, &h->b[l], (size_t)cfg->dims[l + 1]);
   }
-  A_(Wlin, (size_t)h->C * h->wdt[h->L - 1]); A_(blin, (size_t)h->C);
-  if (h->has_self) {
-    for (int l = 0; l < h->L && !rc; ++l) rc = dalloc(h, &h->Ws[l], (size_t)cfg->dims[l] * cfg->dims[l + 1]);
-    A_(S0, n * (size_t)h->hmax); A_(Sv, n * (size_t)h->hsum); A_(Su, n * (size_t)h->hsum);
+  A_(Wlin, (size_t)h->p.C * h->p.wdt[h->p.L - 1]); A_(blin, (size_t)h->p.C);
+  if (h->cfg.has_self) {
+    for (int l = 0; l < h->p.L && !rc; ++l) rc = dalloc(h, &h->Ws[l], (size_t)cfg->dims[l] * cfg->dims[l + 1]);
+    A_(S0, n * (size_t)h->p.hmax); A_(Sv, n * (size_t)h->p.hsum); A_(Su, n * (size_t)h->p.hsum);
   }
-  const size_t nh = n * h->hsum, nm = n * h->hmax, nc = n * h->C;
+  const size_t nh = n * h->p.hsum, nm = n * h->p.hmax, nc = n * h->p.C;
   A_(Tv, nh); A_(Pv, nh); A_(Hv, nh); A_(GPv, nh); A_(Tu, nh); A_(Pu, nh); A_(Hu, nh); A_(GPu, nh);
   A_(Y, nm); A_(GT, nm); A_(Z, nc); A_(logp, nc); A_(sm, nc); A_(Z2, nc); A_(sm2, nc); A_(GZ, nc); A_(GZ2, nc); A_(Gsm, nc);
   A_(Zn, nm); A_(GZn, nm); A_(Gem, nm);
-  const size_t am_ = (size_t)h->na * h->hmax;
+  const size_t am_ = (size_t)h->p.na * h->p.hmax;
   A_(HA, nm); A_(YA, nc); A_(HAg, am_); A_(HAc, am_); A_(YAg, am_); A_(YAc, am_); A_(Yg, am_); A_(Gg, am_);
   if (cfg->eps != 0.f) { A_(Abuf, nn); A_(gate, nn); A_(colpart_d, (size_t)h->nstrips * ld); }
   if (p.fwd_reuse) { A_(ADJN_next, nn); }
   A_(cm_part, (size_t)64 * 256);      // column-sum partials of launch_colmean_center (small-operand terms)
   if (hsic) { A_(Yg8, am_); }
-  A_(Q, (size_t)h->hmax * h->hmax); A_(Q2, (size_t)h->hmax * h->hmax); A_(Gg2, am_); A_(coef, 16); A_(cst, 8);
+  A_(Q, (size_t)h->p.hmax * h->p.hmax); A_(Q2, (size_t)h->p.hmax * h->p.hmax); A_(Gg2, am_); A_(coef, 16); A_(cst, 8);
   if (p.lr_ok) {
-    A_(lrL, n * 2 * he); A_(lrR, n * 2 * he); A_(lrQ, n * 2 * he); A_(lrV, n * (size_t)h->lr_ldv);
-    A_(lrT, n * (size_t)h->lr_ldv); A_(lrDelta, ld); A_(lrC, ld); A_(lrStats, lr_stats_doubles(he)); A_(lrRs, ld); A_(lrQtZ, lr_qtz_doubles(he));
+    A_(lrL, n * 2 * he); A_(lrR, n * 2 * he); A_(lrQ, n * 2 * he); A_(lrV, n * (size_t)h->p.lr_ldv);
+    A_(lrT, n * (size_t)h->p.lr_ldv); A_(lrDelta, ld); A_(lrC, ld); A_(lrStats, lr_stats_doubles(he)); A_(lrRs, ld); A_(lrQtZ, lr_qtz_doubles(he));
   }
   A_(nmask, 4);
   // packed planes of the split products: the low-rank step's (Apack: H Kf H, per graph; Bpack: Xc) and the Gram evaluation's
@@ -285,7 +252,7 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
     A_(FV, n * fc); A_(em_last, nm); A_(fstat, 256 + fl_wcolsum_scratch_doubles());
     if (!p.sharded) { A_(FY, n * fc); }      // a row-block rank keeps FY in the exchange arena
     A_(rkbuf, fl_tail_pack_bytes((int)n));           // packed fp16 planes of the tail's rank-k panels
-    A_(Zpair, (n + 2) * (size_t)h->hmax);
+    A_(Zpair, (n + 2) * (size_t)h->p.hmax);
     // (a row-block rank cuts the columns of its rows' decode into up to 64 slices: fused_lowrank.hip: fl_decode_slabs)
     A_(ws_dec, (size_t)((p.sharded || p.fused != FUSED_HSIC) ? 64 : lr_decode_slabs((int)n)) * n * he);      // (MSELoss, KL: up to 64 slices too, nothing runs beside their decode)
     if (p.fused == FUSED_KL) { A_(klA, ld); A_(kl1, ld); A_(klv, ld); A_(klvsum, ld); A_(klpart, (size_t)64 * n * 2); }
@@ -299,7 +266,7 @@ int mcgra_attack_create(mcgra_attack_t** out, const mcgra_attack_config_t* cfg) 
   }
   h->ws_bytes = (size_t)64 * n * 64 * sizeof(float);
   A_(ws, h->ws_bytes / sizeof(float));
-  h->ws_small_bytes = (size_t)64 * (h->na > h->hmax ? h->na : h->hmax) * h->hmax * sizeof(float);
+  h->ws_small_bytes = (size_t)64 * (h->p.na > h->p.hmax ? h->p.na : h->p.hmax) * h->p.hmax * sizeof(float);
   A_(ws_small, h->ws_small_bytes / sizeof(float));
 #undef A_
   if (!rc && p.side_streams) {
@@ -353,15 +320,15 @@ int mcgra_attack_set_model(mcgra_attack_t* h, void* stream, const float* const* 
                            const float* Wlin, const float* blin, const float* const* Ws) {
   if (h) carry_forget(h);      // Rule: forget.  Nothing in flight reads the model.
   if (!h || !W || !b || !Wlin || !blin) { set_error("null argument"); return MCGRA_EINVAL; }
-  if ((h->has_self != 0) != (Ws != nullptr)) { set_error("Ws must be given exactly when has_self is set"); return MCGRA_EINVAL; }
+  if ((h->cfg.has_self != 0) != (Ws != nullptr)) { set_error("Ws must be given exactly when has_self is set"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  for (int l = 0; l < h->L; ++l) {
+  for (int l = 0; l < h->p.L; ++l) {
     if (Ws) MCGRA_HIP(hipMemcpyAsync(h->Ws[l], Ws[l], sizeof(float) * h->cfg.dims[l] * h->cfg.dims[l + 1], hipMemcpyDeviceToDevice, st));
     MCGRA_HIP(hipMemcpyAsync(h->W[l], W[l], sizeof(float) * h->cfg.dims[l] * h->cfg.dims[l + 1], hipMemcpyDeviceToDevice, st));
     MCGRA_HIP(hipMemcpyAsync(h->b[l], b[l], sizeof(float) * h->cfg.dims[l + 1], hipMemcpyDeviceToDevice, st));
   }
-  MCGRA_HIP(hipMemcpyAsync(h->Wlin, Wlin, sizeof(float) * h->C * h->wdt[h->L - 1], hipMemcpyDeviceToDevice, st));
-  MCGRA_HIP(hipMemcpyAsync(h->blin, blin, sizeof(float) * h->C, hipMemcpyDeviceToDevice, st));
+  MCGRA_HIP(hipMemcpyAsync(h->Wlin, Wlin, sizeof(float) * h->p.C * h->p.wdt[h->p.L - 1], hipMemcpyDeviceToDevice, st));
+  MCGRA_HIP(hipMemcpyAsync(h->blin, blin, sizeof(float) * h->p.C, hipMemcpyDeviceToDevice, st));
   h->model_set = true;
   return 0;
 }
@@ -374,68 +341,68 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
   if (!h->model_set) { set_error("mcgra_attack_set_model must be called first"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   CHK(carry_drop(h, st));
-  const int n = h->n, ld = h->ld, hs = h->hsum;
+  const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum;
   if (ori_adj) {
-    // (general path only: apply_plan)
-    if (h->sharded) { set_error("a non-zero ori_adj is not supported on a row-block rank"); return MCGRA_ENOSUP; }
+    // (general path only: engine.h, has_ori)
+    if (h->p.sharded) { set_error("a non-zero ori_adj is not supported on a row-block rank"); return MCGRA_ENOSUP; }
     const size_t nn = (size_t)n * ld, nh = (size_t)n * hs;
     int rc = 0;
-#define A1_(p, cnt) if (!rc && !h->p) rc = dalloc(h, &h->p, (cnt))
+#define A1_(f, cnt) if (!rc && !h->f) rc = dalloc(h, &h->f, (cnt))
     A1_(ORI, nn); A1_(Bbuf, nn); A1_(Abuf, nn); A1_(gate, nn); A1_(Te, nh); A1_(Pe, nh); A1_(He, nh); A1_(GPe, nh);
-    if (h->has_self) { A1_(Se, nh); }
+    if (h->cfg.has_self) { A1_(Se, nh); }
 #undef A1_
     if (rc) return rc;
     MCGRA_HIP(hipMemcpy2DAsync(h->ORI, (size_t)ld * 4, ori_adj, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
   }
-  apply_plan(h, ori_adj != nullptr);
+  h->has_ori = ori_adj != nullptr;
   MCGRA_HIP(hipMemcpy2DAsync(h->FADJ, (size_t)ld * 4, feature_adj, (size_t)n * 4, (size_t)n * 4, n, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipMemcpyAsync(h->labels, labels, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
-  MCGRA_HIP(hipMemcpyAsync(h->idx, idx_attack, sizeof(int) * h->na, hipMemcpyDeviceToDevice, st));
+  MCGRA_HIP(hipMemcpyAsync(h->idx, idx_attack, sizeof(int) * h->p.na, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipMemsetAsync(h->cnt, 0, sizeof(float) * ld, st));
-  launch_count_idx(st, h->na, h->idx, h->cnt);
+  launch_count_idx(st, h->p.na, h->idx, h->cnt);
   // T0 = X @ W_0 : the only use of the features inside the loop (models/gcn.py:41)
-  CHK(eg(h, st, false, false, n, h->wdt[0], h->cfg.dims[0], 1.f, features, h->cfg.dims[0], h->W[0], h->wdt[0], 0.f, h->Tv, hs));
-  MCGRA_HIP(hipMemcpy2DAsync(h->Tu, (size_t)hs * 4, h->Tv, (size_t)hs * 4, (size_t)h->wdt[0] * 4, n, hipMemcpyDeviceToDevice, st));
+  CHK(eg(h, st, false, false, n, h->p.wdt[0], h->cfg.dims[0], 1.f, features, h->cfg.dims[0], h->W[0], h->p.wdt[0], 0.f, h->Tv, hs));
+  MCGRA_HIP(hipMemcpy2DAsync(h->Tu, (size_t)hs * 4, h->Tv, (size_t)hs * 4, (size_t)h->p.wdt[0] * 4, n, hipMemcpyDeviceToDevice, st));
   if (h->has_ori)
-    MCGRA_HIP(hipMemcpy2DAsync(h->Te, (size_t)hs * 4, h->Tv, (size_t)hs * 4, (size_t)h->wdt[0] * 4, n, hipMemcpyDeviceToDevice, st));
-  if (h->has_self)   // S0 = X @ Ws_0: the self half of the first GraphSAGE layer, adjacency independent
-    CHK(eg(h, st, false, false, n, h->wdt[0], h->cfg.dims[0], 1.f, features, h->cfg.dims[0], h->Ws[0], h->wdt[0], 0.f, h->S0,
-           h->hmax));
+    MCGRA_HIP(hipMemcpy2DAsync(h->Te, (size_t)hs * 4, h->Tv, (size_t)hs * 4, (size_t)h->p.wdt[0] * 4, n, hipMemcpyDeviceToDevice, st));
+  if (h->cfg.has_self)   // S0 = X @ Ws_0: the self half of the first GraphSAGE layer, adjacency independent
+    CHK(eg(h, st, false, false, n, h->p.wdt[0], h->cfg.dims[0], 1.f, features, h->cfg.dims[0], h->Ws[0], h->p.wdt[0], 0.f, h->S0,
+           h->p.hmax));
   // priors on the TRUE, un-normalised adjacency (topology_attack.py:177-182, :243)
-  CHK(chain_forward(h, st, adj, n, h->L, h->Tu, h->Pu, h->Hu, h->Su));
+  CHK(chain_forward(h, st, adj, n, h->p.L, h->Tu, h->Pu, h->Hu, h->Su));
   CHK(head_forward(h, st, h->Hu, h->Z2, h->YA, nullptr));                                  // Y_A (log-probs)
-  const int le = h->Le - 1;
-  MCGRA_HIP(hipMemcpy2DAsync(h->HA, (size_t)h->hmax * 4, h->Hu + h->off[le], (size_t)hs * 4, (size_t)h->wdt[le] * 4, n,
+  const int le = h->p.Le - 1;
+  MCGRA_HIP(hipMemcpy2DAsync(h->HA, (size_t)h->p.hmax * 4, h->Hu + h->p.off[le], (size_t)hs * 4, (size_t)h->p.wdt[le] * 4, n,
                              hipMemcpyDeviceToDevice, st));                                // H_A_cur
-  launch_gather_rows(st, h->na, h->wdt[le], h->HA, h->hmax, h->idx, h->HAg, h->hmax);
-  launch_gather_rows(st, h->na, h->wdt[le], h->HA, h->hmax, h->idx, h->HAc, h->hmax);
-  launch_colmean_center(st, h->na, h->wdt[le], h->HAc, h->hmax);
-  launch_gather_rows(st, h->na, h->C, h->YA, h->C, h->idx, h->YAg, h->hmax);
-  launch_gather_rows(st, h->na, h->C, h->YA, h->C, h->idx, h->YAc, h->hmax);
-  launch_colmean_center(st, h->na, h->C, h->YAc, h->hmax);
+  launch_gather_rows(st, h->p.na, h->p.wdt[le], h->HA, h->p.hmax, h->idx, h->HAg, h->p.hmax);
+  launch_gather_rows(st, h->p.na, h->p.wdt[le], h->HA, h->p.hmax, h->idx, h->HAc, h->p.hmax);
+  launch_colmean_center(st, h->p.na, h->p.wdt[le], h->HAc, h->p.hmax);
+  launch_gather_rows(st, h->p.na, h->p.C, h->YA, h->p.C, h->idx, h->YAg, h->p.hmax);
+  launch_gather_rows(st, h->p.na, h->p.C, h->YA, h->p.C, h->idx, h->YAc, h->p.hmax);
+  launch_colmean_center(st, h->p.na, h->p.C, h->YAc, h->p.hmax);
   if (h->cfg.measure == MCGRA_MEASURE_CKA) {
     // hsic(H_A, H_A), hsic(Y_A, Y_A) of linear_CKA's denominator (utils.py:1093): |Xc^T Xc|_F^2, constants
-    const int hm = h->hmax;
+    const int hm = h->p.hmax;
     MCGRA_HIP(hipMemsetAsync(h->Q, 0, sizeof(float) * (size_t)hm * hm, st));
-    CHK(eg(h, st, true, false, h->wdt[le], h->wdt[le], h->na, 1.f, h->HAc, hm, h->HAc, hm, 0.f, h->Q, hm));
-    launch_sumsq(st, (size_t)h->wdt[le] * hm, h->Q, h->cst + 1);
+    CHK(eg(h, st, true, false, h->p.wdt[le], h->p.wdt[le], h->p.na, 1.f, h->HAc, hm, h->HAc, hm, 0.f, h->Q, hm));
+    launch_sumsq(st, (size_t)h->p.wdt[le] * hm, h->Q, h->cst + 1);
     MCGRA_HIP(hipMemsetAsync(h->Q, 0, sizeof(float) * (size_t)hm * hm, st));
-    CHK(eg(h, st, true, false, h->C, h->C, h->na, 1.f, h->YAc, hm, h->YAc, hm, 0.f, h->Q, hm));
-    launch_sumsq(st, (size_t)h->C * hm, h->Q, h->cst + 2);
+    CHK(eg(h, st, true, false, h->p.C, h->p.C, h->p.na, 1.f, h->YAc, hm, h->YAc, hm, 0.f, h->Q, hm));
+    launch_sumsq(st, (size_t)h->p.C * hm, h->Q, h->cst + 2);
   }
   if ((h->cfg.measure == MCGRA_MEASURE_HSIC || h->cfg.measure == MCGRA_MEASURE_CKA) && h->cfg.w[0] != 0.f) {
     // centred Gram of feature_adj: constant left factor of c1 (utils.py:1086,1089), from centred columns
     launch_rowsum(st, n, ld, h->FADJ, h->rowsx);
     launch_center_cols(st, n, ld, h->FADJ, h->rowsx, h->cmean, h->XC);
     CHK(eg(h, st, false, true, n, n, n, 1.f, h->XC, ld, h->XC, ld, 0.f, h->KFC, ld));
-    if (h->split_mode == 2) {
-      if (h->split_planes == 2) {
+    if (h->p.split_mode == 2) {
+      if (h->p.split_planes == 2) {
         MCGRA_HIP(hipMemsetAsync(h->amax, 0, sizeof(float), st));
         split_absmax(st, n, ld, h->KFC, nullptr, true, h->amax);
       }
-      split3_pack(st, n, ld, h->KFC, nullptr, true, h->Apack, h->split_planes, h->amax);
+      split3_pack(st, n, ld, h->KFC, nullptr, true, h->Apack, h->p.split_planes, h->amax);
     }
-    if (h->gram_split) {      // max |H Kf H|: part of the scale bound of the combined Gram (split_symm_bf16.hip: k_gram_scales)
+    if (gram_split(h)) {      // max |H Kf H|: part of the scale bound of the combined Gram (split_symm_bf16.hip: k_gram_scales)
       MCGRA_HIP(hipMemsetAsync(h->amax + 5, 0, sizeof(float), st));
       split_absmax(st, n, ld, h->KFC, nullptr, false, h->amax + 5);
     }
@@ -449,8 +416,8 @@ int mcgra_attack_set_graph(mcgra_attack_t* h, void* stream, const float* feature
     split_absmax(st, n, ld, h->FADJ, nullptr, false, h->coef);
   }
   // (small_term's HSIC branch relies on zero pad columns in Q / Q2: see there)
-  MCGRA_HIP(hipMemsetAsync(h->Q, 0, sizeof(float) * (size_t)h->hmax * h->hmax, st));
-  MCGRA_HIP(hipMemsetAsync(h->Q2, 0, sizeof(float) * (size_t)h->hmax * h->hmax, st));
+  MCGRA_HIP(hipMemsetAsync(h->Q, 0, sizeof(float) * (size_t)h->p.hmax * h->p.hmax, st));
+  MCGRA_HIP(hipMemsetAsync(h->Q2, 0, sizeof(float) * (size_t)h->p.hmax * h->p.hmax, st));
   h->step.t3_zero = false;
   MCGRA_KERNEL_CHECK();
   // feature_adj.max() != feature_adj.min() (topology_attack.py:212) is evaluated by the host layer
@@ -480,15 +447,15 @@ int mcgra_attack_set_adj_changes(mcgra_attack_t* h, void* stream, const float* p
   if (h) carry_forget(h);      // Rule: drop + forget.  A pack or product of the old M may still be reading it on the side stream.
   if (!h || !packed) { set_error("null argument"); return MCGRA_EINVAL; }
   CHK(carry_drop(h, (hipStream_t)stream));
-  launch_unpack_sym((hipStream_t)stream, h->n, h->ld, packed, nullptr, 0, h->M);
+  launch_unpack_sym((hipStream_t)stream, h->p.n, h->p.ld, packed, nullptr, 0, h->M);
   MCGRA_KERNEL_CHECK();
   h->m_is_full = true;
   return 0;
 }
 int mcgra_attack_get_adj_changes(mcgra_attack_t* h, void* stream, float* packed) {      // Rule: none.  It reads M, which whatever is in flight also only reads.
   if (!h || !packed) { set_error("null argument"); return MCGRA_EINVAL; }
-  if (h->sharded && !h->m_is_full) { set_error("row-block rank: only rows [row_begin, row_end) are kept between a step and mcgra_attack_finalize (mcgra_attack_get_rows)"); return MCGRA_EINVAL; }
-  launch_pack_tril((hipStream_t)stream, h->n, h->ld, h->M, packed, false);
+  if (h->p.sharded && !h->m_is_full) { set_error("row-block rank: only rows [row_begin, row_end) are kept between a step and mcgra_attack_finalize (mcgra_attack_get_rows)"); return MCGRA_EINVAL; }
+  launch_pack_tril((hipStream_t)stream, h->p.n, h->p.ld, h->M, packed, false);
   MCGRA_KERNEL_CHECK();
   return 0;
 }
@@ -497,7 +464,7 @@ int mcgra_attack_get_adj_changes(mcgra_attack_t* h, void* stream, float* packed)
 // Xg raw gathered constant, Xc its column-centred copy.  Value lands in scal[slot].
 int small_term(mcgra_attack* h, hipStream_t st, int width, const float* Ysrc, int ldy, const float* Xg,
                       const float* Xc, double k_signed, float* G, int ldg, int slot, bool want_value) {
-  const int na = h->na, hm = h->hmax;
+  const int na = h->p.na, hm = h->p.hmax;
   // (own split-K workspace: the fused step runs this chain on a side stream, beside products that use h->ws)
   auto eg = [](mcgra_attack* h, hipStream_t st, bool ta, bool tb, int M, int N, int K, float alpha, const float* A, int lda,
                const float* B, int ldb, float beta, float* C, int ldc) -> int {
@@ -538,8 +505,8 @@ int small_term(mcgra_attack* h, hipStream_t st, int width, const float* Ysrc, in
     launch_kde_term(st, na, width, width, Xg, hm, h->Yg, hm, k_signed, nullptr, 0, false, h->Gg, hm, false, h->scal + slot, h->kde);
     launch_scatter_add_rows(st, na, width, h->Gg, hm, h->idx, 1.f, G, ldg);
   } else if (h->cfg.measure == MCGRA_MEASURE_KL) {   // calc_kl(X[idx], Y[idx]) (:483-487), X constant
-    launch_kl_small(st, na, width, Xg, h->Yg, hm, h->Gg, h->rowvals + 7 * (size_t)h->ld);
-    launch_reduce_rows(st, h->rowvals + 7 * (size_t)h->ld, na, 1, h->scal + slot);
+    launch_kl_small(st, na, width, Xg, h->Yg, hm, h->Gg, h->rowvals + 7 * (size_t)h->p.ld);
+    launch_reduce_rows(st, h->rowvals + 7 * (size_t)h->p.ld, na, 1, h->scal + slot);
     launch_scatter_add_rows(st, na, width, h->Gg, hm, h->idx, (float)k_signed, G, ldg);
   } else {  // HSIC: value |Xc^T Yc|_F^2, gradient 2 Xc (Xc^T Yc)   (utils.py:1085-1089)
     // Y is centred explicitly: Xc^T Y == Xc^T Yc only in exact arithmetic, and with identical rows of Y
@@ -547,7 +514,7 @@ int small_term(mcgra_attack* h, hipStream_t st, int width, const float* Ysrc, in
     // (c10: Y = softmax(output2) is nearly the same row on every node, so the STORED float32 softmax has lost most of what the
     //  centring keeps -- 4.8e-5 of the term's gradient on a 3-layer victim at n = 80, against 8e-6 with the rows recomputed from
     //  the logits in float64 and rounded after the centring: node_kernels.hip, k_softmax8_gather)
-    if (y8) launch_softmax8_centered(st, na, width, h->Z2, h->C, h->idx, h->head_act, h->Yg8, h->Yg, hm, h->cm_part);
+    if (y8) launch_softmax8_centered(st, na, width, h->Z2, h->p.C, h->idx, h->cfg.head_act, h->Yg8, h->Yg, hm, h->cm_part);
     else launch_colmean_center(st, na, width, h->Yg, hm, h->cm_part);
     // one Q per term (c9: Q, c10: Q2): each is only ever written on its term's width x width block, so its pad columns
     // keep the zeros of the allocation and no fill is needed per step
@@ -564,7 +531,7 @@ int small_term(mcgra_attack* h, hipStream_t st, int width, const float* Ysrc, in
 // noise == NULL: modified_adj == M (monitoring forward :290-293 and eps == 0); otherwise adding_noise (:165)
 int forward_common(mcgra_attack* h, hipStream_t st, float* adjn_out, const float* noise,
                           double* adjn_rowsum = nullptr) {
-  const int n = h->n, ld = h->ld;
+  const int n = h->p.n, ld = h->p.ld;
   const bool general = noise != nullptr || h->has_ori;      // (ori != 0: clamp(M + ori) even without noise, :474-478)
   if (!general && h->carry.prep_valid) {
     // d, r and the norm / sparsity sums from the row sums the Adam pass left behind: no pass over M
@@ -582,7 +549,7 @@ int forward_common(mcgra_attack* h, hipStream_t st, float* adjn_out, const float
 // ori != 0, places that use get_modified_adj(ori_adj) WITHOUT adding_noise's clamp: the monitoring forward (:290-293) and
 // the adj_norm of an attack without steps (:142).  adj_norm((1 - I) o M + ori) -> adjn_out; d, r, S_SUM as forward_common.
 static int forward_ori_unclamped(mcgra_attack* h, hipStream_t st, float* adjn_out) {
-  const int n = h->n, ld = h->ld;
+  const int n = h->p.n, ld = h->p.ld;
   launch_axpby2d(st, n, h->M, ld, 1.f, h->ORI, ld, 1.f, h->Bbuf, ld);
   launch_prep(st, false, n, ld, h->Bbuf, nullptr, nullptr, 0.f, nullptr, nullptr, h->d, h->r, h->rowsq, h->rowsum);
   launch_reduce_rows(st, h->rowsum, n, 1, h->scal + S_SUM);
@@ -619,9 +586,9 @@ __global__ void k_post_mask(unsigned int* __restrict__ count_u32, const double* 
 
 // func(x) = clamp(adj_changes - x, 0, 1).sum() (topology_attack.py:398-399), over the strict lower triangle
 static int clamp_sum(mcgra_attack* h, hipStream_t st, float x, bool minmax, double* out, float* mn, float* mx) {
-  launch_clamp_rowsum(st, h->n, h->ld, h->M, x, h->rowsx, minmax ? h->rowmin : nullptr, minmax ? h->rowmax : nullptr);
-  launch_reduce_rows(st, h->rowsx, h->n, 1, h->scal + S_CLAMPSUM);
-  if (minmax) launch_minmax(st, h->n, h->rowmin, h->rowmax, h->mm);
+  launch_clamp_rowsum(st, h->p.n, h->p.ld, h->M, x, h->rowsx, minmax ? h->rowmin : nullptr, minmax ? h->rowmax : nullptr);
+  launch_reduce_rows(st, h->rowsx, h->p.n, 1, h->scal + S_CLAMPSUM);
+  if (minmax) launch_minmax(st, h->p.n, h->rowmin, h->rowmax, h->mm);
   MCGRA_KERNEL_CHECK();
   double s;
   float m2[2] = {0, 0};
@@ -656,7 +623,7 @@ int project(mcgra_attack* h, hipStream_t st) {
       else { a = miu; fa = fm; }
     }
   }
-  launch_shift_clamp(st, h->n, h->ld, h->M, miu);   // clamp(adj_changes - miu, 0, 1); miu = 0 is the plain clamp
+  launch_shift_clamp(st, h->p.n, h->p.ld, h->M, miu);   // clamp(adj_changes - miu, 0, 1); miu = 0 is the plain clamp
   MCGRA_KERNEL_CHECK();
   return 0;
 }
@@ -665,8 +632,8 @@ int project(mcgra_attack* h, hipStream_t st) {
 // scalars_out
 int collect_scalars(mcgra_attack* h, hipStream_t st, double* scalars_out, bool have_clampsum) {
   const mcgra_attack_config_t& c = h->cfg;
-  const int n = h->n, ld = h->ld, C = h->C;
-  const int he = h->wdt[h->Le - 1];
+  const int n = h->p.n, ld = h->p.ld, C = h->p.C;
+  const int he = h->p.wdt[h->p.Le - 1];
   const double sg = sign_of(h);
   const double w1 = c.w[0], w2 = c.w[1], w6 = c.w[5], w7 = c.w[6], w9 = c.w[8], w10 = c.w[9];
   const double k1 = w1 * 1000 * AP_C1, k2 = w2 * 100 * AP_C2, k6 = w6 * 100 * AP_C6, k7 = w7 * AP_C7;
@@ -682,7 +649,7 @@ int collect_scalars(mcgra_attack* h, hipStream_t st, double* scalars_out, bool h
     double s[S_COUNT];
     MCGRA_HIP(hipMemcpyAsync(s, h->scal, sizeof(s), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipStreamSynchronize(st));
-    const double nll = s[S_NLL] / h->na;
+    const double nll = s[S_NLL] / h->p.na;
     const double norm_a = sqrt(0.5 * s[S_SQ]);
     const double origin = nll + norm_a * 0.001;
     double c1v = 0, c2v = 0;
@@ -701,8 +668,8 @@ int collect_scalars(mcgra_attack* h, hipStream_t st, double* scalars_out, bool h
     if (!use2) c2v = 0;
     const double c6v = k6 * (-s[S_V6] / n2), c7v = k7 * (-s[S_V7] / n2);
     double c9v = 0, c10v = 0;
-    if (w9 != 0) c9v = dp ? k9 * sqrt(s[S_C9]) : (hsic || kl) ? k9 * s[S_C9] : k9 * s[S_C9] / ((double)h->na * he);
-    if (w10 != 0) c10v = dp ? k10 * sqrt(s[S_C10]) : (hsic || kl) ? k10 * s[S_C10] : k10 * s[S_C10] / ((double)h->na * C);
+    if (w9 != 0) c9v = dp ? k9 * sqrt(s[S_C9]) : (hsic || kl) ? k9 * s[S_C9] : k9 * s[S_C9] / ((double)h->p.na * he);
+    if (w10 != 0) c10v = dp ? k10 * sqrt(s[S_C10]) : (hsic || kl) ? k10 * s[S_C10] : k10 * s[S_C10] / ((double)h->p.na * C);
     scalars_out[0] = c.weight_sup * origin + sg * (c1v + c2v + c9v + c10v) + c6v + c7v;
     scalars_out[1] = origin; scalars_out[2] = c1v; scalars_out[3] = c2v; scalars_out[4] = c6v; scalars_out[5] = c7v;
     scalars_out[6] = c9v; scalars_out[7] = c10v; scalars_out[8] = 0.5 * s[S_CLAMPSUM]; scalars_out[9] = nll;
@@ -747,12 +714,12 @@ struct GeneralStep {
 //  passes of this step, [3] / [4] out of hsic_gram_scales / the CKA combine, all in front of the products that read them.)
 static int gram_product(mcgra_attack* h, hipStream_t st, hipStream_t gst, const void* Ap, const void* Bp, float* C, float* slab,
                         const float* amax_a, const float* amax_b, int flags, hipEvent_t done) {
-  const int n = h->n, ld = h->ld;
+  const int n = h->p.n, ld = h->p.ld;
   if (gst != st) { MCGRA_HIP(hipEventRecord(h->ev_fork, st)); MCGRA_HIP(hipStreamWaitEvent(gst, h->ev_fork, 0)); }
   CHK(timer_begin(h, gst, h->profile));
   MCGRA_HIP(split3_symm(gst, n, Ap, Bp, C, ld, 0, -1, h->small_slab ? h->small_slab : slab,
                         h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, 2, amax_a, 0, -1,
-                        flags | (h->split_single ? SPLIT_SINGLE : 0), 0, nullptr, 0, nullptr, amax_b));
+                        flags | (h->p.split_single ? SPLIT_SINGLE : 0), 0, nullptr, 0, nullptr, amax_b));
   CHK(timer_end(h, gst, h->profile, 2.0 * (double)n * n * n));
   if (gst != st && done) MCGRA_HIP(hipEventRecord(done, gst));
   return 0;
@@ -760,7 +727,7 @@ static int gram_product(mcgra_attack* h, hipStream_t st, hipStream_t gst, const 
 // Kx = Xc Xc^T from the planes of Xc's rows in Gp0, forked onto the Gram stream: lower tiles, mirrored by the epilogue (full,
 // bitwise symmetric matrix); split-K slabs in G_A, idle until the tail
 static int fork_kx(mcgra_attack* h, hipStream_t st) {
-  hipStream_t gst = (h->gram_ovl && h->st2) ? h->st2 : st;
+  hipStream_t gst = (h->p.gram_ovl && h->st2) ? h->st2 : st;
   return gram_product(h, st, gst, h->Gp0, h->Gp0, h->KX, h->G_A, h->amax + 1, h->amax + 1, SPLIT_TRI, nullptr);
 }
 // Gram-evaluation configurations without a low-rank form (GAT / GraphSAGE victims, CKA, widths > 32, MCGRA_NO_LOWRANK): both packed
@@ -769,7 +736,7 @@ static int fork_kx(mcgra_attack* h, hipStream_t st) {
 // monitor call whose adj_norm the step adopts (kx_early): the same launches on the same data, the same bits.  rowsx holds the column
 // sums of adjn.
 static int gram_pack_fork_kx(mcgra_attack* h, hipStream_t st, const float* adjn) {
-  const int n = h->n, ld = h->ld;
+  const int n = h->p.n, ld = h->p.ld;
   launch_colmean_f32(st, n, ld, h->rowsx, h->cmean);
   pack_center_both(st, n, ld, adjn, h->cmean, h->r, 0.f, h->Gp0, h->Bpack, h->amax + 1, h->gram_diag, reinterpret_cast<double*>(h->XC));
   return fork_kx(h, st);
@@ -786,21 +753,21 @@ static int launch_ky(GeneralStep& s) {
 // P1 = (H Kf H) Xc: value and gradient of c1 in the low-rank path; the only N x N x N product of such a step.  Forked onto st2 (it
 // needs nothing else of the step), joined in front of its only consumer in the tail.
 static int fork_p1(GeneralStep& s) {
-  mcgra_attack* h = s.h; const int n = h->n, ld = h->ld;
-  hipStream_t sp = h->overlap ? h->st2 : s.st;
-  if (h->overlap) { MCGRA_HIP(hipEventRecord(h->ev_fork, s.st)); MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0)); }
-  if (h->split_on && !s.gen) {
+  mcgra_attack* h = s.h; const int n = h->p.n, ld = h->p.ld;
+  hipStream_t sp = h->p.overlap ? h->st2 : s.st;
+  if (h->p.overlap) { MCGRA_HIP(hipEventRecord(h->ev_fork, s.st)); MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0)); }
+  if (h->p.split_on && !s.gen) {
     // planes of Xc^T from the rows of the (symmetric) adj_norm (packed by center_xc), then the plane-reusing kernel
     // (split_symm_bf16.hip); split-K slabs of the ragged last round go to KY, idle on a low-rank step
     CHK(timer_begin(h, sp, h->profile));
     MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, 0, -1, h->small_slab ? h->small_slab : h->KY,
-                          h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->split_planes, h->amax, 0, -1,
-                          h->split_single ? SPLIT_SINGLE : 0));
+                          h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->p.split_planes, h->amax, 0, -1,
+                          h->p.split_single ? SPLIT_SINGLE : 0));
     CHK(timer_end(h, sp, h->profile, 2.0 * (double)n * n * n));
     ++h->split_steps;
   } else
   CHK(eg_symm(h, sp, n, n, h->KFC, ld, h->XC, ld, 0.f, h->KX, ld));
-  if (h->overlap) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
+  if (h->p.overlap) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
   h->step.p1_inflight = true;
   return 0;
 }
@@ -808,7 +775,7 @@ static int fork_p1(GeneralStep& s) {
 // Xc = H adj_norm (and, for the low-rank path, |xc_i|^2 = diag(Kx) from the same pass): the packed operands and the start of Kx
 // of a Gram evaluation, or the operands and the fork of P1 of a low-rank step
 static int center_xc(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   if (s.gen) {                               // possibly asymmetric: true column sums
     if (!h->colpart_d) CHK(dalloc(h, &h->colpart_d, (size_t)h->nstrips * ld));
     launch_colsum(st, n, ld, h->ADJN, h->colpart_d, h->nstrips, h->rowsx);
@@ -819,18 +786,18 @@ static int center_xc(GeneralStep& s) {
     if (!s.kx_adopt) CHK(gram_pack_fork_kx(h, st, h->ADJN));
   } else {
     // (gram_diag: |xc_i|^2 = diag(Kx) for the scale bound of the combined Grams -- only when the low-rank path does not want it)
-    const bool want_lrrs = h->lr_ok && !s.cka && s.use2;
+    const bool want_lrrs = lr_ok(h) && !s.cka && s.use2;
     launch_center_cols(st, n, ld, h->ADJN, h->rowsx, h->cmean, h->XC, want_lrrs ? h->lrRs : (s.gs_path ? h->gram_diag : nullptr),
-                       ((h->split_mode == 2 && h->split_planes == 2) || h->gram_split) ? h->amax + 1 : nullptr);
+                       ((h->p.split_mode == 2 && h->p.split_planes == 2) || gram_split(h)) ? h->amax + 1 : nullptr);
     // Gram evaluation through the split kernel: planes of Xc^T now (cmean is reused by Yc's centring), unless the
     // low-rank product below packs them anyway
-    if (h->gram_split && !s.gen && !(h->lr_ok && !s.cka && s.use1 && h->split_on))
+    if (gram_split(h) && !s.gen && !(lr_ok(h) && !s.cka && s.use1 && h->p.split_on))
       split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, 2, h->amax + 1);
   }
-  if (h->lr_ok && !s.cka && s.use1) {
+  if (lr_ok(h) && !s.cka && s.use1) {
     // bf16 planes of Xc^T (opt-in split path) on the caller's stream, ahead of the fork: cmean is reused later
-    if (h->split_on && !s.gen)
-      split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr);
+    if (h->p.split_on && !s.gen)
+      split3_pack(st, n, ld, h->ADJN, h->cmean, false, h->Bpack, h->p.split_planes, h->amax ? h->amax + 1 : nullptr);
     // (in a run whose decode keeps masking pairs the product would be thrown away: it then waits for this step's own
     // masked-pair count, hsic_terms)
     if (!(h->carry.skip_fused && s.use2)) CHK(fork_p1(s));
@@ -842,7 +809,7 @@ static int center_xc(GeneralStep& s) {
 // ---- forward: adjacency, normalisation (:164-166), victim and embedding chains (:167-185), dot_product_decode +
 // get_modified_adj_after (:187-188)
 static int step_forward(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, L = h->L, Le = h->Le, C = h->C, he = s.he;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum, L = h->p.L, Le = h->p.Le, C = h->p.C, he = s.he;
   // (S_SQ, S_SUM are the first two slots: written by forward_common, kept when its results are adopted)
   MCGRA_HIP(hipMemsetAsync(h->scal + (s.adopt ? 2 : 0), 0, sizeof(double) * (S_COUNT - (s.adopt ? 2 : 0)), st));
   const float* noise_ld = nullptr;
@@ -860,7 +827,7 @@ static int step_forward(GeneralStep& s) {
     CHK(chain_forward(h, st, h->ADJN, ld, L, h->Tv, h->Pv, h->Hv, h->Sv));
     CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->sm));
   }
-  launch_nll_grad(st, n, C, h->logp, h->sm, C, h->labels, h->cnt, (float)(h->cfg.weight_sup / h->na), h->GZ, h->rowvals + 6 * (size_t)ld);
+  launch_nll_grad(st, n, C, h->logp, h->sm, C, h->labels, h->cnt, (float)(h->cfg.weight_sup / h->p.na), h->GZ, h->rowvals + 6 * (size_t)ld);
   launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, n, 1, h->scal + S_NLL);
   // ---- embedding(features, modified_adj - ori_adj) (:185) == first Le layers of victim(features, modified_adj) (:259)
   CHK(chain_forward(h, st, s.A, ld, L, h->Tu, h->Pu, h->Hu, h->Su));
@@ -869,16 +836,16 @@ static int step_forward(GeneralStep& s) {
     launch_axpby2d(st, n, s.A, ld, 1.f, h->ORI, ld, -1.f, h->Bbuf, ld);
     CHK(chain_forward(h, st, h->Bbuf, ld, Le, h->Te, h->Pe, h->He, h->Se));
   }
-  if (h->small_side_on && h->st3 && h->st3 != st && (s.use9 || s.use10)) {
+  if (h->p.small_side_on && h->st3 && h->st3 != st && (s.use9 || s.use10)) {
     MCGRA_HIP(hipEventRecord(h->ev_fork3, st));      // (em and softmax(output2) stand: what the small-operand terms need)
     s.small_side = true;
   }
   // ---- dot_product_decode + get_modified_adj_after (:187-188)
-  launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->hmax, h->nrm, 2.f);
-  CHK(eg(h, st, false, true, n, n, he, 1.f, h->Zn, h->hmax, h->Zn, h->hmax, 0.f, h->A1, ld));
+  launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->p.hmax, h->nrm, 2.f);
+  CHK(eg(h, st, false, true, n, n, he, 1.f, h->Zn, h->p.hmax, h->Zn, h->p.hmax, 0.f, h->A1, ld));
   // (the count of relu-masked pairs is read by the low-rank decision only: HSIC with c2 on a configuration that has the
   // low-rank forms -- every other step skips the counting)
-  const bool count_masked = h->cfg.measure == MCGRA_MEASURE_HSIC && h->lr_ok && h->cfg.w[1] != 0;
+  const bool count_masked = h->cfg.measure == MCGRA_MEASURE_HSIC && lr_ok(h) && h->cfg.w[1] != 0;
   if (count_masked) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, sizeof(unsigned int), st));
   h->step.nmask_zero = false;
   launch_decode_post(st, n, ld, h->A1, h->has_ori ? h->ORI : nullptr, count_masked ? h->nmask : nullptr);
@@ -891,13 +858,13 @@ static int step_forward(GeneralStep& s) {
 // low-rank decode backward
 static void elem_terms(GeneralStep& s, float kmse1, float kmse2, bool y_side = true) {
   mcgra_attack* h = s.h;
-  launch_loss_elem(s.st, h->n, h->ld, h->ADJN, y_side ? h->A1 : nullptr, h->FADJ, kmse1, kmse2, (float)(s.k6 / s.n2),
+  launch_loss_elem(s.st, h->p.n, h->p.ld, h->ADJN, y_side ? h->A1 : nullptr, h->FADJ, kmse1, kmse2, (float)(s.k6 / s.n2),
                    (float)(s.k7 / s.n2), h->G_ADJN, y_side ? h->G_A1 : nullptr, h->rowvals);
-  launch_reduce_rows(s.st, h->rowvals, h->n, 4, h->scal + S_V1);
+  launch_reduce_rows(s.st, h->rowvals, h->p.n, 4, h->scal + S_V1);
 }
 // dot_product(X, Y) = |Y^T X|_F (:480-481); d/dY = X P^T / |P|, d/dX = Y P / |P| with P = Y^T X
 static int dp_terms(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   elem_terms(s, 0.f, 0.f);
   if (s.use1) {   // c1 = k1 dot_product(feature_adj, adj_norm): P = adj_norm^T Fadj
     CHK(eg(h, st, true, false, n, n, n, 1.f, h->ADJN, ld, h->FADJ, ld, 0.f, h->KX, ld));
@@ -921,7 +888,7 @@ static int dp_terms(GeneralStep& s) {
 // c2 = k2 calc(adj_norm, modified_adj1)[0] (:222-225).  Entry (i, j) of an operand meets bin j only and bins j >= 7 are
 // out of reach of values <= 2 in float32 (kde_kernels.hip): the terms live on the first KDE_NXN_COLS columns.
 static int kde_terms(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   elem_terms(s, 0.f, 0.f);      // only the entropy slots are non-zero
   const int kc = n < h->kde_cols ? n : h->kde_cols;      // (set_graph: 8, or as far as feature_adj's values reach)
   if (s.use1) launch_kde_term(st, n, kc, n, h->FADJ, ld, h->ADJN, ld, s.k1, nullptr, 0, false, h->G_ADJN, ld, true, h->scal + S_H1, h->kde);
@@ -930,7 +897,7 @@ static int kde_terms(GeneralStep& s) {
 }
 // calc_kl (:483-487) against softmax(feature_adj) (XC, set_graph)
 static int kl_terms(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   elem_terms(s, 0.f, 0.f);      // only the entropy slots are non-zero
   if (s.use1 || s.use2) {
     launch_kl_rows(st, n, ld, h->ADJN, h->A1, h->XC, s.use1 ? (float)s.k1 : 0.f, s.use2 ? (float)s.k2 : 0.f, h->G_ADJN,
@@ -947,10 +914,10 @@ static int mse_terms(GeneralStep& s) {
 
 // Yc = H modified_adj1 for the Grams (and, on the split kernel, its planes and diag(Ky))
 static void center_yc(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   launch_rowsum(st, n, ld, h->A1, h->rowsy);
-  const bool gs = h->gram_split && !s.gen;
-  if (gs && !h->lr_ok) {
+  const bool gs = gram_split(h) && !s.gen;
+  if (gs && !lr_ok(h)) {
     // rows of Yc (both operands of Ky = Yc Yc^T) and of Yc^T (B operand of G_A1 += LX Yc) in one pass over the symmetric
     // modified_adj1 (entries in [0, 1]), diag(Ky) from the same pass
     launch_colmean_f32(st, n, ld, h->rowsy, h->cmean);
@@ -968,8 +935,8 @@ static void center_yc(GeneralStep& s) {
 // linear_HSIC / linear_CKA (utils.py:1085-1096): the entropy terms, the low-rank decision, and the operands of whichever
 // evaluation the step takes -- the factors of the low-rank forms, or Yc centred (and packed) for the Grams
 static int hsic_terms(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, he = s.he;
-  if (s.want_xc && h->lr_ok && !s.cka) {
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld, he = s.he;
+  if (s.want_xc && lr_ok(h) && !s.cka) {
     // Low-rank path for c2 needs every off-diagonal pair active in the decode's relu (relu'(0) = 0 would
     // mask a pair in the backward); that is data dependent, so the count is read back once per step.
     unsigned int masked = 0;
@@ -992,12 +959,12 @@ static int hsic_terms(GeneralStep& s) {
   if (h->step.lr_step) {
     ++h->lr_steps;
     if (s.use2) {
-      launch_lr_colstats(st, n, he, h->Zn, h->hmax, h->lrStats);
-      launch_lr_prep(st, n, he, h->Zn, h->hmax, h->lrStats, h->lrL, h->lrV, h->lr_ldv, h->lrDelta);
+      launch_lr_colstats(st, n, he, h->Zn, h->p.hmax, h->lrStats);
+      launch_lr_prep(st, n, he, h->Zn, h->p.hmax, h->lrStats, h->lrL, h->lrV, h->p.lr_ldv, h->lrDelta);
       // T = Xc^T [U | D Z | delta^2]: W, W2 and t3 from one pass over Xc
-      CHK(eg(h, st, true, false, n, h->lr_ldv, n, 1.f, h->XC, ld, h->lrV, h->lr_ldv, 0.f, h->lrT, h->lr_ldv));
+      CHK(eg(h, st, true, false, n, h->p.lr_ldv, n, 1.f, h->XC, ld, h->lrV, h->p.lr_ldv, 0.f, h->lrT, h->p.lr_ldv));
       h->step.t3_zero = false;
-      launch_lr_post(st, n, he, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
+      launch_lr_post(st, n, he, h->lrT, h->p.lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
     }
     return 0;
   }
@@ -1016,23 +983,23 @@ static int hsic_terms(GeneralStep& s) {
 // decode they left the caller's queue empty for that long (213 us idle under the profiler, a third of the gain).
 static int small_terms(GeneralStep& s, hipStream_t q) {
   mcgra_attack* h = s.h;
-  MCGRA_HIP(hipMemsetAsync(h->Gem, 0, sizeof(float) * (size_t)h->n * h->hmax, q));
-  if (s.use9) CHK(small_term(h, q, s.he, s.em, h->hsum, h->HAg, h->HAc, s.sg * s.k9, h->Gem, h->hmax, S_C9));
+  MCGRA_HIP(hipMemsetAsync(h->Gem, 0, sizeof(float) * (size_t)h->p.n * h->p.hmax, q));
+  if (s.use9) CHK(small_term(h, q, s.he, s.em, h->p.hsum, h->HAg, h->HAc, s.sg * s.k9, h->Gem, h->p.hmax, S_C9));
   if (s.use10) {
-    MCGRA_HIP(hipMemsetAsync(h->Gsm, 0, sizeof(float) * (size_t)h->n * h->C, q));
-    CHK(small_term(h, q, h->C, h->sm2, h->C, h->YAg, h->YAc, s.sg * s.k10, h->Gsm, h->C, S_C10));
-    launch_softmax_bwd(q, h->n, h->C, h->sm2, h->Gsm, h->C, h->GZ2);
+    MCGRA_HIP(hipMemsetAsync(h->Gsm, 0, sizeof(float) * (size_t)h->p.n * h->p.C, q));
+    CHK(small_term(h, q, h->p.C, h->sm2, h->p.C, h->YAg, h->YAc, s.sg * s.k10, h->Gsm, h->p.C, S_C10));
+    launch_softmax_bwd(q, h->p.n, h->p.C, h->sm2, h->Gsm, h->p.C, h->GZ2);
   }
   return 0;
 }
 static int early_bwd(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, L = h->L, C = h->C, hs = h->hsum;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, L = h->p.L, C = h->p.C, hs = h->p.hsum;
   if (!s.small_side) CHK(small_terms(s, st));
   // ---- backward: victim(adj_norm) chain -> G_adjn
-  if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z, h->GZ);     // through elu(out_att(x)) (gat.py:206)
-  launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                     h->Pv + h->off[L - 1], hs, h->act, nullptr, 0, h->GPv + h->off[L - 1], hs);
-  CHK(chain_backward(h, st, h->ADJN, h->ld, L - 1, h->Pv, h->GPv, -1, nullptr, 0));
+  if (h->cfg.head_act) launch_elu_grad_mul(st, n, C, h->Z, h->GZ);     // through elu(out_att(x)) (gat.py:206)
+  launch_rowmat_mask(st, n, C, h->p.wdt[L - 1], h->GZ, C, h->Wlin, h->p.wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                     h->Pv + h->p.off[L - 1], hs, h->cfg.act, nullptr, 0, h->GPv + h->p.off[L - 1], hs);
+  CHK(chain_backward(h, st, h->ADJN, h->p.ld, L - 1, h->Pv, h->GPv, -1, nullptr, 0));
   if (s.small_side) {      // (behind the victim chain's launches in program order: the caller's queue is fed first)
     MCGRA_HIP(hipStreamWaitEvent(h->st3, h->ev_fork3, 0));
     CHK(small_terms(s, h->st3));
@@ -1043,7 +1010,7 @@ static int early_bwd(GeneralStep& s) {
 
 // G_adjn += sum_l G_P_l T_l^T (+ the low-rank 2 s2 (U M1^T - D Z W^T) of a low-rank step, in the same pass)
 static int victim_rankk(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, he = s.he;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum, he = s.he;
   const bool lr2 = s.hsic && h->step.lr_step && s.use2;
   if (lr2 && rankk_nt_supported(n, n, hs, 2 * he)) {
     MCGRA_HIP(rankk_nt(st, n, n, hs, 1.f, h->GPv, hs, h->Tv, hs, 2 * he, 2.f * (float)(s.sg * s.k2), h->lrL, 2 * he, h->lrR,
@@ -1057,7 +1024,7 @@ static int victim_rankk(GeneralStep& s) {
 // linear_CKA's value sums and the left factors of its gradient products (L1 -> KY, L2 -> KX) from the Grams (lower: in lower
 // tile storage); amax_l2 / amax_l1: their magnitudes, for the split kernel's packs
 static void cka_factors(GeneralStep& s, bool lower, float* amax_l2 = nullptr, float* amax_l1 = nullptr) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   launch_cka_sums(st, n, ld, h->KX, h->KY, h->KFC, s.use1, s.use2, h->rowvals + 4 * (size_t)ld, lower);
   launch_reduce_rows(st, h->rowvals + 4 * (size_t)ld, n, 4, h->scal + S_CK0);
   launch_cka_coef(st, h->scal + S_CK0, h->cst + 0, s.use1 ? (float)s.k1 : 0.f, s.use2 ? (float)s.k2 : 0.f, h->coef);
@@ -1075,7 +1042,7 @@ static void cka_factors(GeneralStep& s, bool lower, float* amax_l2 = nullptr, fl
 // G_adjn += LY Xc (LY = 2 (s1 Kfc + s2 Kyc) is combined and packed beside the third), its slabs in KX (dead: combined and
 // packed).  linear_CKA's factors need both Grams: it combines first.
 static int gram_eval(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st, gst = s.gst; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st, gst = s.gst; const int n = h->p.n, ld = h->p.ld;
   const float s1 = (float)(s.sg * s.k1), s2 = (float)(s.sg * s.k2);
   if (!s.gs_only) {      // (a low-rank configuration whose decode found a dead row: Xc was centred, not packed)
     split3_pack(st, n, ld, h->XC, nullptr, false, h->Gp0, 2, h->amax + 1);
@@ -1086,7 +1053,7 @@ static int gram_eval(GeneralStep& s) {
   const void* LY = h->Gp1;
   if (!s.cka) {
     // operand scales of LY / LX from the diagonals of the centred Grams (known since the centring passes)
-    hsic_gram_scales(st, n, (h->lr_ok && s.use2) ? h->lrRs : h->gram_diag, h->gram_diag + ld, s.use1 ? s1 : 0.f, s.use2 ? s2 : 0.f,
+    hsic_gram_scales(st, n, (lr_ok(h) && s.use2) ? h->lrRs : h->gram_diag, h->gram_diag + ld, s.use1 ? s1 : 0.f, s.use2 ? s2 : 0.f,
                      h->amax);
     if (gst != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
     if (s.use2) {
@@ -1127,7 +1094,7 @@ static int gram_eval(GeneralStep& s) {
 // ---- the same on the fp32 MFMA GEMM: Grams are symmetric, only the 128x128 tiles on or below the diagonal are computed (lower
 // tile storage), and the gradient products read the mirrored half transposed (SYMM): 3 n^3 MACs per step instead of 4
 static int gram_fp32(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld;
   CHK(eg_syrk(h, st, n, n, h->XC, ld, h->KX, ld, s.use2 ? h->YC : nullptr, s.use2 ? h->KY : nullptr));   // H Kx H (and H Ky H)
   if (s.cka) cka_factors(s, true);
   else {
@@ -1145,12 +1112,12 @@ static int gram_fp32(GeneralStep& s) {
 // ---- backward: the low-rank step's decode factors, the forward-only part (unless the Gram evaluation ran it beside its
 // products), the decode, and the modified_adj chain (embedding + output2) down to G_P
 static int step_backward(GeneralStep& s) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->n, ld = h->ld, hs = h->hsum, L = h->L, Le = h->Le, C = h->C, he = s.he;
+  mcgra_attack* h = s.h; hipStream_t st = s.st; const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum, L = h->p.L, Le = h->p.Le, C = h->p.C, he = s.he;
   const bool lr2 = s.hsic && h->step.lr_step && s.use2;
   if (lr2) {
-    CHK(eg(h, st, false, false, n, 2 * he, n, 1.f, h->XC, ld, h->lrT, h->lr_ldv, 0.f, h->lrQ, 2 * he));         // [Q | Q2] = Xc [W | W2]
+    CHK(eg(h, st, false, false, n, 2 * he, n, 1.f, h->XC, ld, h->lrT, h->p.lr_ldv, 0.f, h->lrQ, 2 * he));         // [Q | Q2] = Xc [W | W2]
     if (!lr_decode_supported(he))     // widths without a fused decode backward: d c2 / d A1 += 2 s2 Q Z^T, materialised
-      CHK(eg(h, st, false, true, n, n, he, 2.f * (float)(s.sg * s.k2), h->lrQ, 2 * he, h->Zn, h->hmax, 1.f, h->G_A1, ld));
+      CHK(eg(h, st, false, true, n, n, he, 2.f * (float)(s.sg * s.k2), h->lrQ, 2 * he, h->Zn, h->p.hmax, 1.f, h->G_A1, ld));
     MCGRA_KERNEL_CHECK();
   }
   if (!s.gram_eval) { CHK(early_bwd(s)); CHK(victim_rankk(s)); }      // (a Gram-evaluation step ran both beside its products)
@@ -1160,22 +1127,22 @@ static int step_backward(GeneralStep& s) {
   // ---- backward: decode (S = Zn Zn^T, A1 = offdiag relu(S))
   if (lr2 && lr_decode_supported(he)) {
     // ((G + G^T) o [S > 0]) Zn for G = ie'(A1) + 2 s2 Q Z^T, without materialising G (c7 value from the same pass)
-    const int np = launch_lr_decode_bwd(st, n, ld, he, h->A1, h->Zn, h->hmax, h->lrQ, (float)(s.k7 / s.n2), h->ws,
-                                        h->rowvals + 6 * (size_t)ld, h->GZn, h->hmax, h->lrQtZ);
+    const int np = launch_lr_decode_bwd(st, n, ld, he, h->A1, h->Zn, h->p.hmax, h->lrQ, (float)(s.k7 / s.n2), h->ws,
+                                        h->rowvals + 6 * (size_t)ld, h->GZn, h->p.hmax, h->lrQtZ);
     if (np > 0) launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, np, 1, h->scal + S_V7);
   } else {
     launch_sym_mask(st, n, ld, h->G_A1, h->A1, h->has_ori ? h->ORI : nullptr, h->G_A);    // G_A used as scratch for (G + G^T) * [S > 0]
-    CHK(eg(h, st, false, false, n, he, n, 1.f, h->G_A, ld, h->Zn, h->hmax, 0.f, h->GZn, h->hmax));
+    CHK(eg(h, st, false, false, n, he, n, 1.f, h->G_A, ld, h->Zn, h->p.hmax, 0.f, h->GZn, h->p.hmax));
   }
   if (lr2) {   // the -2 s2 KX D part of d c2 / d A1, applied to Zn directly
     const bool fused = lr_decode_supported(he);
-    launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrDelta, h->lrRs, -2.f * (float)(s.sg * s.k2), h->GZn, h->hmax,
+    launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->p.hmax, h->lrDelta, h->lrRs, -2.f * (float)(s.sg * s.k2), h->GZn, h->p.hmax,
                     h->rowvals + 7 * (size_t)ld, h->rowvals + 5 * (size_t)ld, fused ? h->lrStats + 2 * he : nullptr,
                     fused ? h->lrQtZ : nullptr, 2.f * (float)(s.sg * s.k2));
     launch_reduce_rows(st, h->rowvals + 5 * (size_t)ld, n, 1, h->scal + S_H2);
   }
   if (s.small_side) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join3, 0));      // c9 / c10: Gem, GZ2 and their scalars
-  launch_row_normalize_bwd(st, n, he, h->GZn, h->Zn, h->hmax, h->nrm, h->Gem, h->hmax);
+  launch_row_normalize_bwd(st, n, he, h->GZn, h->Zn, h->p.hmax, h->nrm, h->Gem, h->p.hmax);
 
   // ---- backward: modified_adj chain (embedding + output2) -> G_A
   if (h->has_ori) {
@@ -1183,30 +1150,30 @@ static int step_backward(GeneralStep& s) {
     MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
     MCGRA_HIP(hipMemsetAsync(h->GPe, 0, sizeof(float) * (size_t)n * hs, st));
     if (s.use10) {
-      if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
-      launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                         h->Pu + h->off[L - 1], hs, h->act, nullptr, 0, h->GPu + h->off[L - 1], hs);
+      if (h->cfg.head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
+      launch_rowmat_mask(st, n, C, h->p.wdt[L - 1], h->GZ2, C, h->Wlin, h->p.wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                         h->Pu + h->p.off[L - 1], hs, h->cfg.act, nullptr, 0, h->GPu + h->p.off[L - 1], hs);
       CHK(chain_backward(h, st, s.A, ld, L - 1, h->Pu, h->GPu, -1, nullptr, 0));
     }
-    launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pe + h->off[Le - 1], hs, h->act, h->Gem, h->hmax, h->GPe + h->off[Le - 1], hs);
+    launch_rowmat_mask(st, n, 0, he, h->Gem, h->p.hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pe + h->p.off[Le - 1], hs, h->cfg.act, h->Gem, h->p.hmax, h->GPe + h->p.off[Le - 1], hs);
     CHK(chain_backward(h, st, h->Bbuf, ld, Le - 1, h->Pe, h->GPe, -1, nullptr, 0));
     return 0;
   }
   int ltop;
   if (s.use10) {
     ltop = L - 1;
-    if (h->head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
-    launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pu + h->off[L - 1], hs, h->act, (L - 1 == Le - 1) ? h->Gem : nullptr, h->hmax,
-                       h->GPu + h->off[L - 1], hs);
+    if (h->cfg.head_act) launch_elu_grad_mul(st, n, C, h->Z2, h->GZ2);
+    launch_rowmat_mask(st, n, C, h->p.wdt[L - 1], h->GZ2, C, h->Wlin, h->p.wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pu + h->p.off[L - 1], hs, h->cfg.act, (L - 1 == Le - 1) ? h->Gem : nullptr, h->p.hmax,
+                       h->GPu + h->p.off[L - 1], hs);
   } else {
     ltop = Le - 1;
     if (L > Le) MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
-    launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pu + h->off[Le - 1], hs, h->act, h->Gem, h->hmax, h->GPu + h->off[Le - 1], hs);
+    launch_rowmat_mask(st, n, 0, he, h->Gem, h->p.hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pu + h->p.off[Le - 1], hs, h->cfg.act, h->Gem, h->p.hmax, h->GPu + h->p.off[Le - 1], hs);
   }
-  CHK(chain_backward(h, st, s.A, ld, ltop, h->Pu, h->GPu, Le - 1, h->Gem, h->hmax));
+  CHK(chain_backward(h, st, s.A, ld, ltop, h->Pu, h->GPu, Le - 1, h->Gem, h->p.hmax));
   return 0;
 }
 
@@ -1214,7 +1181,7 @@ static int step_backward(GeneralStep& s) {
 // + clamp (:274-283), scalars
 static int step_tail(GeneralStep& s, double* scalars_out) {
   mcgra_attack* h = s.h; hipStream_t st = s.st; const mcgra_attack_config_t& c = h->cfg;
-  const int n = h->n, ld = h->ld, hs = h->hsum;
+  const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum;
   // the normalisation backward reads G_adjn: behind G_adjn += LY Xc on the Gram stream
   if (s.gram_eval && s.gst != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
   bool normbwd_parts = false;
@@ -1224,7 +1191,7 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
     // Last contribution to G_adjn, and the only consumer of P1: everything above ran beside the forked product.
     // G_adjn += 2 s1 P1 + 2 s2 (D^2 Xc + 1 c^T);  v1 = sum P1 o Xc
     if (h->step.p1_inflight) {
-      if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+      if (h->p.overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
       h->step.p1_inflight = false;
     }
     // ... fused with the two N x N reductions of the normalisation backward that follows (one pass instead of three);
@@ -1252,7 +1219,7 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
   const bool may_project = c.num_edges < 0.5 * s.n2;
   bool adam_done = false;
   // normalisation backward writes G_A (beta = 0), then the chain's outer products accumulate
-  if (h->fuse_tail && rankk_apply_adam_supported(n, ld, hs) && !h->has_ori) {
+  if (h->p.fuse_tail && rankk_apply_adam_supported(n, ld, hs) && !h->has_ori) {
     // one pass over the lower tile pairs: apply step + rank-k update + gradient mirror + Adam, no G_A in between
     launch_normbwd(st, n, ld, h->G_ADJN, s.A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
     // (its row sums of the new M go to G_A, which this path leaves unused; not with a projection still to come)
@@ -1260,7 +1227,7 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
     const bool emit = !s.gen && adam_emits_partials(h, may_project, cnt);
     MCGRA_HIP(rankk_apply_adam(st, n, ld, hs, h->GPu, hs, h->Tu, hs, h->G_ADJN, h->r, h->gd, s.gate, h->M, h->am, h->av, h->mm + 2,
                                (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
-                               h->keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
+                               h->p.keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
                                emit ? adam_row_sums(h, cnt) : nullptr));
     h->carry.prep_valid = emit;
     adam_done = true;
@@ -1280,7 +1247,7 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
   if (!adam_done) {
     h->carry.prep_valid = false;
     launch_adam_sym(st, n, ld, h->G_A, s.gate, h->M, h->am, h->av, h->mm + 2, (float)(1.0 - b1), (float)b2,
-                    (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f, h->keep_gsym ? h->GSYM : nullptr,
+                    (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f, h->p.keep_gsym ? h->GSYM : nullptr,
                     may_project ? 0 : 1);
   }
   MCGRA_KERNEL_CHECK();
@@ -1299,14 +1266,14 @@ int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* sc
     return MCGRA_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (h->sharded && !h->fs_active) {
+  if (h->p.sharded && !h->fs_active) {
     set_error("this engine is a row-block rank: drive it with mcgra_attack_shard_begin / mcgra_attack_shard_next");
     return MCGRA_EINVAL;
   }
   // Rule: the fused step goes first and takes what it adopts (fs_begin, fs_pack_fork); the general step takes Kx and drops the rest, below.
   // (after a step whose decode masked a pair the general path goes first: it reads the masked-pair count itself, and
   // only once that is zero again is the fused step worth enqueueing -- a masked run otherwise pays for both every step)
-  if (!noise && !h->sharded && fused_step_possible(h) && !h->carry.skip_fused) {
+  if (!noise && !h->p.sharded && fused_step_possible(h) && !h->carry.skip_fused) {
     const int rc = fused_step(h, st, scalars_out);      // 1: a relu-masked pair in the decode, the general path redoes the step
     if (rc <= 0) return rc;
   }
@@ -1319,18 +1286,18 @@ int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* sc
 
   const mcgra_attack_config_t& c = h->cfg;
   GeneralStep s{};
-  s.h = h; s.st = st; s.noise = noise; s.he = h->wdt[h->Le - 1]; s.sg = sign_of(h); s.n2 = (double)h->n * h->n;
+  s.h = h; s.st = st; s.noise = noise; s.he = h->p.wdt[h->p.Le - 1]; s.sg = sign_of(h); s.n2 = (double)h->p.n * h->p.n;
   const double w1 = c.w[0], w2 = c.w[1], w6 = c.w[5], w7 = c.w[6], w9 = c.w[8], w10 = c.w[9];
   s.k1 = w1 * 1000 * AP_C1; s.k2 = w2 * 100 * AP_C2; s.k6 = w6 * 100 * AP_C6; s.k7 = w7 * AP_C7; s.k9 = w9 * AP_C9; s.k10 = w10 * AP_C10;
   s.use1 = w1 != 0; s.use2 = w2 != 0; s.use9 = w9 != 0; s.use10 = w10 != 0;
   s.cka = c.measure == MCGRA_MEASURE_CKA;
   s.hsic = c.measure == MCGRA_MEASURE_HSIC || s.cka;      // both run the centred-Gram path
   s.gen = noise != nullptr || h->has_ori;
-  s.A = s.gen ? h->Abuf : h->M; s.gate = s.gen ? h->gate : nullptr; s.em = (h->has_ori ? h->He : h->Hu) + h->off[h->Le - 1];
+  s.A = s.gen ? h->Abuf : h->M; s.gate = s.gen ? h->gate : nullptr; s.em = (h->has_ori ? h->He : h->Hu) + h->p.off[h->p.Le - 1];
   s.want_xc = s.hsic && (s.use1 || s.use2);
-  s.gs_path = h->gram_split && !s.gen && s.want_xc;
-  s.gs_only = s.gs_path && !h->lr_ok;
-  s.gst = (s.gs_path && h->gram_ovl && h->st2) ? h->st2 : st;
+  s.gs_path = gram_split(h) && !s.gen && s.want_xc;
+  s.gs_only = s.gs_path && !lr_ok(h);
+  s.gst = (s.gs_path && h->p.gram_ovl && h->st2) ? h->st2 : st;
   s.adopt = h->carry.fwd_cached && !s.gen; s.kx_adopt = kx_adopt;      // (kx_adopt implies adopt)
   h->carry.fwd_cached = false;
 
@@ -1344,7 +1311,7 @@ int step_general(mcgra_attack_t* h, void* stream, const float* noise, double* sc
     // Join the forked P1 product before the Grams may overwrite KX; a low-rank step joins it as late as possible, in front of
     // its only consumer (step_tail)
     if (h->step.p1_inflight && !h->step.lr_step) {
-      if (h->overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+      if (h->p.overlap) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
       h->step.p1_inflight = false;
     }
     if (s.gram_eval) CHK(gram_eval(s));
@@ -1362,7 +1329,7 @@ long long mcgra_attack_masked_fused_steps(mcgra_attack_t* h) { return h ? (long 
 long long mcgra_attack_cut_product_steps(mcgra_attack_t* h) { return h ? (long long)h->cut_product_steps : 0; }
 int mcgra_attack_product_mode(mcgra_attack_t* h) {
   if (!h) return 0;
-  return plan_product_mode(h->split_single, h->gram_split, h->split_mode, h->split_planes);
+  return plan_product_mode(h->p.split_single, gram_split(h), h->p.split_mode, h->p.split_planes);
 }
 
 int mcgra_attack_path_stats(mcgra_attack_t* h, long long* lowrank_steps, long long* general_steps) {
@@ -1378,7 +1345,7 @@ long long mcgra_attack_gram_split_steps(mcgra_attack_t* h) { return h ? (long lo
 int mcgra_attack_monitor(mcgra_attack_t* h, void* stream, float* out_logp, double* sparsity) {
   if (!h || !h->graph_set) { set_error("engine not set up"); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  if (h->sharded) { set_error("row-block rank: use mcgra_attack_shard_begin(MCGRA_SHARD_MONITOR)"); return MCGRA_EINVAL; }
+  if (h->p.sharded) { set_error("row-block rank: use mcgra_attack_shard_begin(MCGRA_SHARD_MONITOR)"); return MCGRA_EINVAL; }
   // Rule: none.  A monitor call adds to what is in flight; forking an item again replaces it (the pack on its own side stream:
   // fw_prep; Kx behind a drop, below).  It leaves ONE forward: the fused one or the general one.
   if (fused_step_possible(h) && h->carry.fused_last && h->cfg.eps == 0.f) {
@@ -1387,13 +1354,13 @@ int mcgra_attack_monitor(mcgra_attack_t* h, void* stream, float* out_logp, doubl
     h->carry.fused_fwd_valid = true;
     h->carry.fwd_cached = false;
     if (out_logp)
-      MCGRA_HIP(hipMemcpyAsync(out_logp, h->logp, sizeof(float) * (size_t)h->n * h->C, hipMemcpyDeviceToDevice, st));
+      MCGRA_HIP(hipMemcpyAsync(out_logp, h->logp, sizeof(float) * (size_t)h->p.n * h->p.C, hipMemcpyDeviceToDevice, st));
     if (sparsity) {
       double s;
       if (h->carry.early_pack) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));      // (the sum rides on the pack's stream)
       MCGRA_HIP(hipMemcpyAsync(&s, h->scal + S_SUM, sizeof(double), hipMemcpyDeviceToHost, st));
       MCGRA_HIP(hipStreamSynchronize(st));
-      *sparsity = s / ((double)h->n * h->n);
+      *sparsity = s / ((double)h->p.n * h->p.n);
     }
     return 0;
   }
@@ -1402,43 +1369,43 @@ int mcgra_attack_monitor(mcgra_attack_t* h, void* stream, float* out_logp, doubl
   // (adopted by the next step, see fwd_cached) or, without reuse, to the A1 buffer.
   const bool want_xc = (h->cfg.measure == MCGRA_MEASURE_HSIC || h->cfg.measure == MCGRA_MEASURE_CKA) &&
                        (h->cfg.w[0] != 0 || h->cfg.w[1] != 0);
-  float* dst = h->fwd_reuse ? h->ADJN_next : h->A1;
+  float* dst = fwd_reuse(h) ? h->ADJN_next : h->A1;
   if (h->has_ori) CHK(forward_ori_unclamped(h, st, dst));
   else
-  CHK(forward_common(h, st, dst, nullptr, (h->fwd_reuse && want_xc) ? h->rowsx : nullptr));
-  if (h->kx_early_on && want_xc && h->gram_split && !h->lr_ok && !h->has_ori && h->cfg.eps == 0.f && h->have_step) {
+  CHK(forward_common(h, st, dst, nullptr, (fwd_reuse(h) && want_xc) ? h->rowsx : nullptr));
+  if (h->p.kx_early_on && want_xc && gram_split(h) && !lr_ok(h) && !h->has_ori && h->cfg.eps == 0.f && h->have_step) {
     // the next step of this configuration is a Gram evaluation whose first product needs this adj_norm only: packed and forked now,
     // it runs beside the chains below and beside the next step's own forward part instead of behind them (the row partials in G_A
     // that forward_common just consumed make room for the product's split-K slabs)
     CHK(carry_drop(h, st));      // (two monitor calls in a row: the first one's Kx)
     CHK(gram_pack_fork_kx(h, st, dst));
-    if (h->gram_ovl && h->st2) MCGRA_HIP(hipEventRecord(h->ev_first, h->st2));
+    if (h->p.gram_ovl && h->st2) MCGRA_HIP(hipEventRecord(h->ev_first, h->st2));
     h->carry.kx_early = true;
     if (!h->small_slab) h->carry.prep_valid = false;      // (the product's split-K slabs went into G_A, over the row partials forward_common just consumed)
   }
-  CHK(chain_forward(h, st, dst, h->ld, h->L, h->Tv, h->Pv, h->Hv, h->Sv));
-  CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->fwd_reuse ? h->sm : nullptr));
-  h->carry.fwd_cached = h->fwd_reuse;
+  CHK(chain_forward(h, st, dst, h->p.ld, h->p.L, h->Tv, h->Pv, h->Hv, h->Sv));
+  CHK(head_forward(h, st, h->Hv, h->Z, h->logp, fwd_reuse(h) ? h->sm : nullptr));
+  h->carry.fwd_cached = fwd_reuse(h);
   if (out_logp)
-    MCGRA_HIP(hipMemcpyAsync(out_logp, h->logp, sizeof(float) * (size_t)h->n * h->C, hipMemcpyDeviceToDevice, st));
+    MCGRA_HIP(hipMemcpyAsync(out_logp, h->logp, sizeof(float) * (size_t)h->p.n * h->p.C, hipMemcpyDeviceToDevice, st));
   if (sparsity) {
     double s;
     MCGRA_HIP(hipMemcpyAsync(&s, h->scal + S_SUM, sizeof(double), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipStreamSynchronize(st));
-    *sparsity = s / ((double)h->n * h->n);
+    *sparsity = s / ((double)h->p.n * h->p.n);
   }
   return 0;
 }
 
 // out += dot_product_decode2(Z) (topology_attack.py:421-467); Z is [n x w] with leading dim ldz
 static int dd2(mcgra_attack* h, hipStream_t st, int mode, const float* Z, int w, int ldz, float* out) {
-  const int n = h->n, ld = h->ld;
+  const int n = h->p.n, ld = h->p.ld;
   const float* src = Z;
   int lsrc = ldz;
   if (mode == 1 || mode >= 4) {
     const float p = mode == 5 ? 3.f : (mode == 6 ? 5.f : 2.f);
-    launch_row_normalize(st, n, w, Z, ldz, h->GZn, h->hmax, nullptr, p);
-    src = h->GZn; lsrc = h->hmax;
+    launch_row_normalize(st, n, w, Z, ldz, h->GZn, h->p.hmax, nullptr, p);
+    src = h->GZn; lsrc = h->p.hmax;
   }
   CHK(eg(h, st, false, true, n, n, w, 1.f, src, lsrc, src, lsrc, 0.f, h->KX, ld));
   const int emode = (mode == 0 || mode == 1) ? 0 : (mode == 3 ? 3 : 2);
@@ -1452,7 +1419,7 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, cons
   if (!h || !out || !h->graph_set) { set_error("engine not set up / null out"); return MCGRA_EINVAL; }
   if (decode_mode < 0 || decode_mode > 6) { set_error("decode_mode %d", decode_mode); return MCGRA_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  const int n = h->n, ld = h->ld, hs = h->hsum, Le = h->Le, L = h->L;
+  const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum, Le = h->p.Le, L = h->p.L;
   // Rule: drop + forget.  What a monitor call forked for a step that never came reads M, which is overwritten below (:301), and writes
   // scratch; the forward it left and the row sums the Adam pass left describe the old M.  (skip_fused is kept: a step may follow.)
   CHK(carry_drop(h, st));
@@ -1465,12 +1432,12 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, cons
   if (h->carry.fused_last && h->have_step) {
     // the fused step never stores adj_norm; embedding(features, adj_norm) of the last iteration is its victim-chain
     // activation of layer emb_nlayer (shared weights), saved by fused_step
-    launch_row_normalize(st, n, h->wdt[Le - 1], h->em_last, h->hmax, h->Zn, h->hmax, h->nrm, 2.f);
+    launch_row_normalize(st, n, h->p.wdt[Le - 1], h->em_last, h->p.hmax, h->Zn, h->p.hmax, h->nrm, 2.f);
   } else {
     CHK(chain_forward(h, st, h->ADJN, ld, Le, h->Tu, h->Pu, h->Hu, h->Su));
-    launch_row_normalize(st, n, h->wdt[Le - 1], h->Hu + h->off[Le - 1], hs, h->Zn, h->hmax, h->nrm, 2.f);
+    launch_row_normalize(st, n, h->p.wdt[Le - 1], h->Hu + h->p.off[Le - 1], hs, h->Zn, h->p.hmax, h->nrm, 2.f);
   }
-  CHK(eg(h, st, false, true, n, n, h->wdt[Le - 1], 1.f, h->Zn, h->hmax, h->Zn, h->hmax, 0.f, h->M, ld));
+  CHK(eg(h, st, false, true, n, n, h->p.wdt[Le - 1], 1.f, h->Zn, h->p.hmax, h->Zn, h->p.hmax, 0.f, h->M, ld));
   launch_decode_post(st, n, ld, h->M, nullptr);            // adj_changes <- the decode (:301); M stays the state
   h->m_is_full = true;                                     // (every rank of a row-block attack now holds the same, whole M)
   const float* mod = h->M;                                 // modified_adj = get_modified_adj(ori_adj) (:302)
@@ -1483,11 +1450,11 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, cons
   // H_A1, H_A2 = embedding(features, modified_adj) with 1 / 2 layers; Y_A2 = victim (:304-308)
   CHK(chain_forward(h, st, mod, ld, L, h->Tu, h->Pu, h->Hu, h->Su));
   CHK(head_forward(h, st, h->Hu, h->Z2, h->logp, nullptr));
-  CHK(dd2(h, st, decode_mode, h->Hu + h->off[h->fin0 - 1], h->wdt[h->fin0 - 1], hs, out));   // H_A1 (:304-305)
-  CHK(dd2(h, st, decode_mode, h->Hu + h->off[h->fin1 - 1], h->wdt[h->fin1 - 1], hs, out));   // H_A2 (:306-307)
-  CHK(dd2(h, st, decode_mode, h->logp, h->C, h->C, out));
-  if (H_A) CHK(dd2(h, st, decode_mode, H_A, h->wdt[Le - 1], h->wdt[Le - 1], out));   // (:315-316)
-  if (Y_A) CHK(dd2(h, st, decode_mode, Y_A, h->C, h->C, out));                        // (:317-318)
+  CHK(dd2(h, st, decode_mode, h->Hu + h->p.off[h->p.fin0 - 1], h->p.wdt[h->p.fin0 - 1], hs, out));   // H_A1 (:304-305)
+  CHK(dd2(h, st, decode_mode, h->Hu + h->p.off[h->p.fin1 - 1], h->p.wdt[h->p.fin1 - 1], hs, out));   // H_A2 (:306-307)
+  CHK(dd2(h, st, decode_mode, h->logp, h->p.C, h->p.C, out));
+  if (H_A) CHK(dd2(h, st, decode_mode, H_A, h->p.wdt[Le - 1], h->p.wdt[Le - 1], out));   // (:315-316)
+  if (Y_A) CHK(dd2(h, st, decode_mode, Y_A, h->p.C, h->p.C, out));                        // (:317-318)
   if (label_adj) launch_axpby2d(st, n, out, n, 1.f, label_adj, n, 1.f, out, n);       // (:319-320)
   MCGRA_KERNEL_CHECK();
   return 0;
@@ -1495,19 +1462,19 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, cons
 
 int mcgra_attack_buffer(mcgra_attack_t* h, const char* name, float** ptr, int* rows, int* cols, int* ldp) {
   if (!h || !name || !ptr) { set_error("null argument"); return MCGRA_EINVAL; }
-  const int n = h->n, ld = h->ld;
+  const int n = h->p.n, ld = h->p.ld;
   struct E { const char* nm; float* p; int r, c, l; };
-  const int le = h->Le - 1;
+  const int le = h->p.Le - 1;
   const E tab[] = {
       {"M", h->M, n, n, ld}, {"adj_norm", h->ADJN, n, n, ld}, {"A1", h->A1, n, n, ld},
       {"G_adjn", h->G_ADJN, n, n, ld}, {"G_A1", h->G_A1, n, n, ld}, {"G_A", h->G_A, n, n, ld},
       {"G_sym", h->GSYM, n, n, ld}, {"adam_m", h->am, n, n, ld}, {"adam_v", h->av, n, n, ld},
-      {"d", h->d, 1, n, ld}, {"r", h->r, 1, n, ld}, {"logp", h->logp, n, h->C, h->C}, {"sm2", h->sm2, n, h->C, h->C},
-      {"em", (h->has_ori ? h->He : h->Hu) + h->off[le], n, h->wdt[le], h->hsum}, {"G_em", h->Gem, n, h->wdt[le], h->hmax},
-      {"HA", h->HA, n, h->wdt[le], h->hmax}, {"YA", h->YA, n, h->C, h->C}, {"T0", h->Tv, n, h->wdt[0], h->hsum},
+      {"d", h->d, 1, n, ld}, {"r", h->r, 1, n, ld}, {"logp", h->logp, n, h->p.C, h->p.C}, {"sm2", h->sm2, n, h->p.C, h->p.C},
+      {"em", (h->has_ori ? h->He : h->Hu) + h->p.off[le], n, h->p.wdt[le], h->p.hsum}, {"G_em", h->Gem, n, h->p.wdt[le], h->p.hmax},
+      {"HA", h->HA, n, h->p.wdt[le], h->p.hmax}, {"YA", h->YA, n, h->p.C, h->p.C}, {"T0", h->Tv, n, h->p.wdt[0], h->p.hsum},
       {"KFC", h->KFC, n, n, ld},
-      {"GPu", h->GPu, n, h->hsum, h->hsum}, {"GPv", h->GPv, n, h->hsum, h->hsum}, {"GZn", h->GZn, n, h->wdt[le], h->hmax},
-      {"Zn", h->Zn, n, h->wdt[le], h->hmax}, {"gd", h->gd, 1, n, ld},
+      {"GPu", h->GPu, n, h->p.hsum, h->p.hsum}, {"GPv", h->GPv, n, h->p.hsum, h->p.hsum}, {"GZn", h->GZn, n, h->p.wdt[le], h->p.hmax},
+      {"Zn", h->Zn, n, h->p.wdt[le], h->p.hmax}, {"gd", h->gd, 1, n, ld},
   };
   for (const E& e : tab)
     if (strcmp(e.nm, name) == 0) {

@@ -96,36 +96,36 @@ __global__ __launch_bounds__(1024) void k_rmax2(int n, const float* __restrict__
 }
 }  // namespace mcgra
 
-bool fused_step_possible(const mcgra_attack* h) { return h->fused_ok; }
+bool fused_step_possible(const mcgra_attack* h) { return fused_ok(h); }
 
 int64_t fused_exchange_bytes(const mcgra_attack* h) {
-  if (!h->sharded) return 0;
+  if (!h->p.sharded) return 0;
   const int64_t a = 256;
   auto up = [&](int64_t x) { return (x + a - 1) / a * a; };
-  return up((int64_t)h->npad * h->fyw * 4) + up((int64_t)h->npad * h->sgw * 4) + up(16 * 8) +
-         2 * up((int64_t)h->world * h->rpr * h->rpr * 4) + up((int64_t)h->npad * h->ld * 4);
+  return up((int64_t)h->p.npad * h->p.fyw * 4) + up((int64_t)h->p.npad * h->p.sgw * 4) + up(16 * 8) +
+         2 * up((int64_t)h->p.world * h->p.rpr * h->p.rpr * 4) + up((int64_t)h->p.npad * h->p.ld * 4);
 }
 
 // Y rows [row0, row1) = M[rows, :] V      (V = FV [n x ncol]).  A row-block rank needs the result in FY (it is exchanged);
 // a monolithic engine leaves a split-K product as its slabs and hands its consumers a view of them (h->fy).  fwd: one of the
 // forward's products, which run beside the N x N x N product when it is forked behind the early pack (fwd_x3).
 static int mm_rows(mcgra_attack* h, hipStream_t st, int ncol, bool fwd = false) {
-  const int rows = h->row1 - h->row0;
-  h->fy = YView{h->FY, h->sharded ? h->fyw : h->fcols, 1, 0};
+  const int rows = h->p.row1 - h->p.row0;
+  h->fy = YView{h->FY, h->p.sharded ? h->p.fyw : h->p.fcols, 1, 0};
   if (rows <= 0) return 0;
-  if (h->sharded)      // into the product columns of the wide exchange stage
-    return eg(h, st, false, false, rows, ncol, h->n, 1.f, h->M + (size_t)h->row0 * h->ld, h->ld, h->FV, h->fcols, 0.f,
-              h->FY + (size_t)h->row0 * h->fyw, h->fyw);
-  if (h->step.planes_valid && planes_mm_supported(h->n, ncol)) {      // beside the N x N x N product: from its own operand planes
-    MCGRA_HIP(planes_mm(st, h->n, h->Bpack, split3_chunks(h->n, 2), h->amax + 1, h->FV, h->fcols, ncol, h->r, h->ws, h->ws_bytes, &h->fy,
+  if (h->p.sharded)      // into the product columns of the wide exchange stage
+    return eg(h, st, false, false, rows, ncol, h->p.n, 1.f, h->M + (size_t)h->p.row0 * h->p.ld, h->p.ld, h->FV, h->p.fcols, 0.f,
+              h->FY + (size_t)h->p.row0 * h->p.fyw, h->p.fyw);
+  if (h->step.planes_valid && planes_mm_supported(h->p.n, ncol)) {      // beside the N x N x N product: from its own operand planes
+    MCGRA_HIP(planes_mm(st, h->p.n, h->Bpack, split3_chunks(h->p.n, 2), h->amax + 1, h->FV, h->p.fcols, ncol, h->r, h->ws, h->ws_bytes, &h->fy,
                         h->pm_scratch));
     return 0;
   }
-  if (fwd && h->fwd_x3 && h->late_mean) {      // (a configuration decision, not a run-time one: monitor and step adoption stay bit-identical)
-    MCGRA_HIP(skinny_x3(st, h->n, h->M, h->ld, h->FV, h->fcols, ncol, h->ws, h->ws_bytes, &h->fy, h->sx_scratch));
+  if (fwd && h->p.fwd_x3 && late_mean(h)) {      // (a configuration decision, not a run-time one: monitor and step adoption stay bit-identical)
+    MCGRA_HIP(skinny_x3(st, h->p.n, h->M, h->p.ld, h->FV, h->p.fcols, ncol, h->ws, h->ws_bytes, &h->fy, h->sx_scratch));
     return 0;
   }
-  MCGRA_HIP(sgemm(st, false, false, rows, ncol, h->n, 1.f, h->M, h->ld, h->FV, h->fcols, 0.f, h->FY, h->fcols, h->ws, h->ws_bytes,
+  MCGRA_HIP(sgemm(st, false, false, rows, ncol, h->p.n, 1.f, h->M, h->p.ld, h->FV, h->p.fcols, 0.f, h->FY, h->p.fcols, h->ws, h->ws_bytes,
                   &h->fy));
   return 0;
 }
@@ -137,7 +137,7 @@ static int fork_p1_early(const FusedStep& s);
 int carry_wait(mcgra_attack* h, hipStream_t st) {
   const Carry& c = h->carry;
   if (c.early_pack) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
-  if (c.kx_early && h->gram_ovl && h->st2) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
+  if (c.kx_early && h->p.gram_ovl && h->st2) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
   if (c.p1_early) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
   return 0;
 }
@@ -162,11 +162,11 @@ void carry_forget(mcgra_attack* h, bool keep_skip_fused) {
 static int pack_on_side_stream(mcgra_attack* h, hipStream_t st, int p_off, int p_cnt, float* psq, float* psum, bool sums) {
   MCGRA_HIP(hipEventRecord(h->ev_r, st));
   MCGRA_HIP(hipStreamWaitEvent(h->st2, h->ev_r, 0));
-  if (h->amax) hipLaunchKernelGGL(k_rmax2, dim3(1), dim3(1024), 0, h->st2, h->n, h->r, h->amax + 1);
-  split3_pack_from_m(h->st2, h->n, h->ld, h->M, h->r, nullptr, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr, p_off, p_cnt,
+  if (h->amax) hipLaunchKernelGGL(k_rmax2, dim3(1), dim3(1024), 0, h->st2, h->p.n, h->r, h->amax + 1);
+  split3_pack_from_m(h->st2, h->p.n, h->p.ld, h->M, h->r, nullptr, h->Bpack, h->p.split_planes, h->amax ? h->amax + 1 : nullptr, p_off, p_cnt,
                      psq, psum);
   // (|adj_changes|^2 and sum(modified_adj): nothing of the forward needs them -- off the caller's stream too)
-  if (sums) launch_reduce_rows(h->st2, h->rowsq, h->n, 2, h->scal + S_SQ);
+  if (sums) launch_reduce_rows(h->st2, h->rowsq, h->p.n, 2, h->scal + S_SQ);
   MCGRA_HIP(hipEventRecord(h->ev_pack, h->st2));
   return 0;
 }
@@ -183,7 +183,7 @@ static int fw_prep(FusedStep& s) {
   } else {
     launch_prep(st, false, n, ld, h->M, nullptr, nullptr, 0.f, nullptr, nullptr, h->d, h->r, h->rowsq, h->rowsum, R0, R1);
   }
-  if (!h->sharded) {
+  if (!h->p.sharded) {
     // Early pack: the planes of the N x N x N product's operand need r only, and the pack is a pure streaming pass
     // (read M, write planes) while the forward's two skinny products keep the fp32 matrix pipe busy at 3 - 4 TB/s: the
     // pack runs on the product's stream beside them instead of behind them (0.16 ms off the path in front of the product).
@@ -191,15 +191,15 @@ static int fw_prep(FusedStep& s) {
     // skinny_x3.hip, whose blocks fit beside a product block; beside a gemm_f32 forward it was measured a wash, and the
     // product then waits for the forward (ev_fork).
     h->carry.early_pack = false;
-    if (h->late_mean && h->overlap && h->st2 && h->early_pack_on) {
+    if (late_mean(h) && h->p.overlap && h->st2 && h->p.early_pack_on) {
       CHK(pack_on_side_stream(h, st, 0, -1, h->cfg.w[1] != 0 ? h->A1 : nullptr,
-                              pack_row_sums(h, split3_pack_rsq_parts(n, h->split_planes)), !h->p1_behind_pack_on));
+                              pack_row_sums(h, split3_pack_rsq_parts(n, h->p.split_planes)), !h->p.p1_behind_pack_on));
       h->carry.early_pack = true;
       // With the product behind the pack, the pack is on the path: it streams M alone and the product follows it directly;
       // the forward (and the sums above) follow it on the caller's stream, beside the product.
-      if (h->p1_behind_pack_on) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
+      if (h->p.p1_behind_pack_on) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
     }
-    if (!h->carry.early_pack || h->p1_behind_pack_on) launch_reduce_rows(st, h->rowsq, n, 2, h->scal + S_SQ);      // rowsq | rowsum are adjacent, and so are S_SQ | S_SUM
+    if (!h->carry.early_pack || h->p.p1_behind_pack_on) launch_reduce_rows(st, h->rowsq, n, 2, h->scal + S_SQ);      // rowsq | rowsum are adjacent, and so are S_SQ | S_SUM
   } else {
     // own rows of r and d, and this rank's share of |adj_changes|^2 and sum(modified_adj) in the scalar lane: ONE gather
     const Stage sg = narrow_stage(h);
@@ -214,12 +214,12 @@ static int fw_prep(FusedStep& s) {
 // r is complete (a row-block rank: gathered, and its product forked); the layers start
 static int fw_r_done(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
-  if (h->sharded) {
+  if (h->p.sharded) {
     const Stage sg = narrow_stage(h);
     stage_to_rows2(h, st, sg, 1, 0, h->r, 1, 1, 1, h->d, 1);
     lane_sum(h, st, sg, 2, h->scal + S_SQ);          // S_SQ | S_SUM are adjacent
     // r is complete: the N x N x N product needs nothing else of this forward (uncentred planes: KFC 1 = 0)
-    if (h->early_p1_on && s.R1 > s.R0 && !(h->fs_active && h->fs_what == MCGRA_SHARD_MONITOR && h->fs_last)) CHK(fork_p1_early(s));
+    if (h->p.early_p1_on && s.R1 > s.R0 && !(h->fs_active && h->fs_what == MCGRA_SHARD_MONITOR && h->fs_last)) CHK(fork_p1_early(s));
   }
   h->step.fs_l = 0;
   return GO;
@@ -228,14 +228,14 @@ static int fw_r_done(FusedStep& s) {
 static int fw_layer_product(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, fc = s.fc;
-  const bool fused_post = h->fused_post;
-  const int l = h->step.fs_l, w = h->wdt[l];
-  const float* Xs[3] = {h->Tv + h->off[l], h->Tu + h->off[l], h->r};
+  const bool fused_post = h->p.fused_post;
+  const int l = h->step.fs_l, w = h->p.wdt[l];
+  const float* Xs[3] = {h->Tv + h->p.off[l], h->Tu + h->p.off[l], h->r};
   const float* rs[3] = {h->r, nullptr, nullptr};
   const int lds[3] = {hs, hs, 1}, ws[3] = {w, w, 1};
-  const bool with_r = l == 0 && !h->late_mean && !h->fused_mse;   // (late mean: the means come out of the pack; MSELoss: no means)
+  const bool with_r = l == 0 && !late_mean(h) && !h->p.elementwise();   // (late mean: the means come out of the pack; MSELoss: no means)
   // [r o Tv | Tu (| r)] -- already in FV when the previous layer's post pass wrote it (fl_layer_post_next)
-  if (!(l >= 1 && fused_post && fl_layer_post_fused_supported(h->wdt[l - 1], w)))
+  if (!(l >= 1 && fused_post && fl_layer_post_fused_supported(h->p.wdt[l - 1], w)))
     fl_cat_segs(st, n, with_r ? 3 : 2, Xs, lds, rs, ws, h->FV, fc);
   CHK(mm_rows(h, st, 2 * w + (with_r ? 1 : 0), true));
   return xchg_fy(s);
@@ -243,26 +243,26 @@ static int fw_layer_product(FusedStep& s) {
 static int fw_layer_post(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, L = s.L, C = s.C, fc = s.fc;
-  const bool fused_post = h->fused_post;
-  const int l = h->step.fs_l, w = h->wdt[l];
-  const bool wr = l == 0 && !h->late_mean && !h->fused_mse;
+  const bool fused_post = h->p.fused_post;
+  const int l = h->step.fs_l, w = h->p.wdt[l];
+  const bool wr = l == 0 && !late_mean(h) && !h->p.elementwise();
   // the post pass and what follows it on the same rows in ONE launch where the widths allow (<= 32): the next
   // layer's T of both chains + the next product's right-hand side, or -- last layer -- both linear heads with their
   // log-softmax (same operations in the same order as the separate kernels)
-  if (l + 1 < L && fused_post && fl_layer_post_fused_supported(w, h->wdt[l + 1])) {
-    fl_layer_post_next(st, n, w, h->fy, h->FV, fc, h->r, h->b[l], h->Pv + h->off[l], h->Hv + h->off[l], h->Pu + h->off[l],
-                       h->Hu + h->off[l], hs, wr, h->cmean, h->rowsx, h->wdt[l + 1], h->W[l + 1], h->Tv + h->off[l + 1],
-                       h->Tu + h->off[l + 1]);
+  if (l + 1 < L && fused_post && fl_layer_post_fused_supported(w, h->p.wdt[l + 1])) {
+    fl_layer_post_next(st, n, w, h->fy, h->FV, fc, h->r, h->b[l], h->Pv + h->p.off[l], h->Hv + h->p.off[l], h->Pu + h->p.off[l],
+                       h->Hu + h->p.off[l], hs, wr, h->cmean, h->rowsx, h->p.wdt[l + 1], h->W[l + 1], h->Tv + h->p.off[l + 1],
+                       h->Tu + h->p.off[l + 1]);
   } else if (l + 1 == L && fused_post && fl_layer_post_fused_supported(w, C)) {
-    fl_layer_post_head(st, n, w, h->fy, h->FV, fc, h->r, h->b[l], h->Pv + h->off[l], h->Hv + h->off[l], h->Pu + h->off[l],
-                       h->Hu + h->off[l], hs, wr, h->cmean, h->rowsx, C, h->Wlin, h->blin, h->Z, h->logp, h->sm, h->Z2, h->sm2,
-                       h->head_act);
+    fl_layer_post_head(st, n, w, h->fy, h->FV, fc, h->r, h->b[l], h->Pv + h->p.off[l], h->Hv + h->p.off[l], h->Pu + h->p.off[l],
+                       h->Hu + h->p.off[l], hs, wr, h->cmean, h->rowsx, C, h->Wlin, h->blin, h->Z, h->logp, h->sm, h->Z2, h->sm2,
+                       h->cfg.head_act);
   } else {
-    fl_layer_post(st, n, w, h->fy, h->FV, fc, h->r, h->b[l], h->Pv + h->off[l], h->Hv + h->off[l], h->Pu + h->off[l],
-                  h->Hu + h->off[l], hs, wr, h->cmean, h->rowsx);
+    fl_layer_post(st, n, w, h->fy, h->FV, fc, h->r, h->b[l], h->Pv + h->p.off[l], h->Hv + h->p.off[l], h->Pu + h->p.off[l],
+                  h->Hu + h->p.off[l], hs, wr, h->cmean, h->rowsx);
     if (l + 1 < L) {
-      launch_rowmat(st, n, w, h->wdt[l + 1], h->Hv + h->off[l], hs, h->W[l + 1], h->wdt[l + 1], 1, nullptr, h->Tv + h->off[l + 1], hs);
-      launch_rowmat(st, n, w, h->wdt[l + 1], h->Hu + h->off[l], hs, h->W[l + 1], h->wdt[l + 1], 1, nullptr, h->Tu + h->off[l + 1], hs);
+      launch_rowmat(st, n, w, h->p.wdt[l + 1], h->Hv + h->p.off[l], hs, h->W[l + 1], h->p.wdt[l + 1], 1, nullptr, h->Tv + h->p.off[l + 1], hs);
+      launch_rowmat(st, n, w, h->p.wdt[l + 1], h->Hu + h->p.off[l], hs, h->W[l + 1], h->p.wdt[l + 1], 1, nullptr, h->Tu + h->p.off[l + 1], hs);
     }
   }
   if (++h->step.fs_l < L) h->fw_state = FW_LAYER_PRODUCT;
@@ -272,12 +272,12 @@ static int fw_layer_post(FusedStep& s) {
 static int fw_heads(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, L = s.L, C = s.C;
-  if (!(h->fused_post && fl_layer_post_fused_supported(h->wdt[L - 1], C))) {
+  if (!(h->p.fused_post && fl_layer_post_fused_supported(h->p.wdt[L - 1], C))) {
     CHK(head_forward(h, st, h->Hv, h->Z, h->logp, h->sm));
     CHK(head_forward(h, st, h->Hu, h->Z2, nullptr, h->sm2));
   }
-  if (h->late_mean) { if (h->amax && !h->carry.early_pack) hipLaunchKernelGGL(k_rmax2, dim3(1), dim3(1024), 0, st, n, h->r, h->amax + 1); }
-  else if (!h->fused_mse)      // (p1_early: the operand-scale bound is k_rmax2's, and the product in flight reads it)
+  if (late_mean(h)) { if (h->amax && !h->carry.early_pack) hipLaunchKernelGGL(k_rmax2, dim3(1), dim3(1024), 0, st, n, h->r, h->amax + 1); }
+  else if (!h->p.elementwise())      // (p1_early: the operand-scale bound is k_rmax2's, and the product in flight reads it)
     fl_mean_stats(st, n, h->cmean, h->r, h->fstat + 192, (h->amax && !h->carry.p1_early) ? h->amax + 1 : h->mm + 3);
   MCGRA_KERNEL_CHECK();
   return GO;
@@ -303,11 +303,11 @@ int fused_forward(mcgra_attack* h, hipStream_t st) {      // monolithic engines 
 
 // host-side bookkeeping of a fused step that went through (the Adam pass is enqueued)
 static void fused_commit(mcgra_attack* h) {
-  const int n = h->n;
+  const int n = h->p.n;
   h->step.planes_valid = false;          // the Adam pass is enqueued: Bpack no longer describes M
   const bool may_project = h->cfg.num_edges < 0.5 * (double)n * (double)n;
-  h->step.lr_step = !h->fused_mse;
-  if (!h->fused_mse) ++h->lr_steps;      // (the fused MSELoss step has no low-rank form: it counts as a fused step only)
+  h->step.lr_step = !h->p.elementwise();
+  if (!h->p.elementwise()) ++h->lr_steps;      // (the fused MSELoss step has no low-rank form: it counts as a fused step only)
   ++h->fused_steps;
   h->t += 1;
   h->carry.prep_valid = adam_emits_partials(h, may_project, (size_t)n * fl_tail_tiles(n));
@@ -340,13 +340,13 @@ static int fused_resync(mcgra_attack* h, hipStream_t st) {
 // Row partials [n][nt] and value partials of the tail's first pass: the END of KY.  (Its start holds the split-K slabs of the
 // product's ragged rounds, and the second part of a cut product writes them while the early pass over the finished rows runs.)
 static size_t tail_ps_floats(const mcgra_attack* h) {
-  const size_t nt = fl_tail_tiles(h->n);
-  return ((((size_t)h->n * nt + 1) & ~(size_t)1) + 6 * nt * nt + 3) & ~(size_t)3;      // (value partials: up to three per block, fp64)
+  const size_t nt = fl_tail_tiles(h->p.n);
+  return ((((size_t)h->p.n * nt + 1) & ~(size_t)1) + 6 * nt * nt + 3) & ~(size_t)3;      // (value partials: up to three per block, fp64)
 }
-static float* tail_ps(const mcgra_attack* h) { return (h->KY ? h->KY : h->KX) + (size_t)h->n * h->ld - tail_ps_floats(h); }      // (MSELoss engines keep no KY; KX is idle there)
+static float* tail_ps(const mcgra_attack* h) { return (h->KY ? h->KY : h->KX) + (size_t)h->p.n * h->p.ld - tail_ps_floats(h); }      // (MSELoss engines keep no KY; KX is idle there)
 
 static double* tail_vpart(const mcgra_attack* h) {
-  return reinterpret_cast<double*>(tail_ps(h) + (((size_t)h->n * fl_tail_tiles(h->n) + 1) & ~(size_t)1));
+  return reinterpret_cast<double*>(tail_ps(h) + (((size_t)h->p.n * fl_tail_tiles(h->p.n) + 1) & ~(size_t)1));
 }
 
 // k_tail_reduce of the step over rows [R0, R1) (phase 1: only its rank-k panels are packed -- their inputs are ready before
@@ -363,15 +363,15 @@ static int tail_reduce_call(const FusedStep& s, int phase, int R0, int R1, bool 
   const int ll[2] = {hs, 2 * he}, lr_[2] = {hs, 2 * he}, Ks[2] = {hs, 2 * he};
   const bool no_rk = h->test_mutate == 2;      // (TEST-ONLY mutation, see the join below)
   const float al[2] = {no_rk ? 0.f : 1.f, no_rk ? 0.f : a2};
-  if (h->fused_kl)       // calc = calc_kl: softmax(feature_adj) in the place of P1, the row statistics lA / l1 / v as the n-vectors
-    return fl_tail_reduce(st, n, h->ld, pair, R0, R1, 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M, h->XC, h->r,
+  if (h->p.kl())       // calc = calc_kl: softmax(feature_adj) in the place of P1, the row statistics lA / l1 / v as the n-vectors
+    return fl_tail_reduce(st, n, h->p.ld, pair, R0, R1, 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M, h->XC, h->r,
                           h->klA, h->kl1, h->klv, 0.f, 0.f, kie6, h->G_ADJN, ps1, want_vals ? vpart : nullptr, h->rkbuf, phase, h->Zn,
-                          h->hmax, he, kmse1, kmse2, true);
-  if (h->fused_mse)      // calc = MSELoss: feature_adj in the place of P1, S = Zn Zn^T as a third rank-k group
-    return fl_tail_reduce(st, n, h->ld, pair, R0, R1, 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M, h->FADJ, h->r,
+                          h->p.hmax, he, kmse1, kmse2, true);
+  if (h->p.elementwise())      // calc = MSELoss: feature_adj in the place of P1, S = Zn Zn^T as a third rank-k group
+    return fl_tail_reduce(st, n, h->p.ld, pair, R0, R1, 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M, h->FADJ, h->r,
                           h->cmean, nullptr, nullptr, 0.f, 0.f, kie6, h->G_ADJN, ps1, want_vals ? vpart : nullptr, h->rkbuf, phase, h->Zn,
-                          h->hmax, he, kmse1, kmse2);
-  return fl_tail_reduce(st, n, h->ld, pair, R0, R1, use2 ? 2 : 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M,
+                          h->p.hmax, he, kmse1, kmse2);
+  return fl_tail_reduce(st, n, h->p.ld, pair, R0, R1, use2 ? 2 : 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M,
                         use1 ? h->KX : nullptr, h->r, h->cmean, use2 ? h->lrDelta : nullptr, use2 ? h->lrC : nullptr, a1, a2, kie6,
                         h->G_ADJN, ps1, want_vals ? vpart : nullptr, h->rkbuf, phase);
 }
@@ -382,10 +382,10 @@ static int tail_reduce_call(const FusedStep& s, int phase, int R0, int R1, bool 
 // the product (Apack: the graph's; Bpack, amax[1]: the pack's; KX, KY, small_slab: last read by the previous step's tail, which
 // precedes the pack's ev_r) -- the product goes straight behind the pack, beside the forward and whatever follows it.
 static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_pack = false) {
-  const int n = h->n, ld = h->ld, R0 = h->row0, R1 = h->row1;
+  const int n = h->p.n, ld = h->p.ld, R0 = h->p.row0, R1 = h->p.row1;
   const int P = split3_panel(), p_off = R0 / P, p_cnt = R1 > R0 ? (R1 - R0 + P - 1) / P : 0;
-  const bool ovl = h->overlap;
-  const int sflag = h->split_single ? 8 : 0;      // MCGRA_SPLIT_BF16=1: the single-plane product of the same operands (split_symm_bf16.hip)
+  const bool ovl = h->p.overlap;
+  const int sflag = h->p.split_single ? 8 : 0;      // MCGRA_SPLIT_BF16=1: the single-plane product of the same operands (split_symm_bf16.hip)
   h->step.p1_inflight = false;
   if (p_cnt <= 0) return 0;
   hipStream_t sp = ovl ? h->st2 : st;
@@ -395,7 +395,7 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
   }
   CHK(timer_begin(h, sp, h->profile));
   h->carry.p1_first = false;
-  if (h->sharded && h->a2a_overlap && ovl && h->world > 1 && h->test_mutate != 1) {
+  if (h->p.sharded && h->p.a2a_overlap && ovl && h->p.world > 1 && h->test_mutate != 1) {
     // Row panels of the peers first (rotated start: the panel behind the own ones, wrapping), own panels last, the launch
     // cut behind the peers' tiles: the all-to-all that hands them over waits for ev_first only and runs beside the rest.
     // The cut sits on a whole round of the chip when that still leaves own tiles behind it (a cut costs a ragged round).
@@ -405,16 +405,16 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
     int first = (span + slots - 1) / slots * slots;
     // (no whole round left behind the peers' tiles: a cut there costs a second ragged round -- taken while the own
     // panels are at least a quarter of the product, world <= 4, or when forced)
-    if (first >= total) first = (h->world <= 4 || h->a2a_overlap == 2) ? span : 0;
+    if (first >= total) first = (h->p.world <= 4 || h->p.a2a_overlap == 2) ? span : 0;
     if (first > 0 && first < total) {
-      MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, rot, -1, h->KY, sizeof(float) * (size_t)n * ld, h->split_planes,
+      MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, rot, -1, h->KY, sizeof(float) * (size_t)n * ld, h->p.split_planes,
                             h->amax, p_off, p_cnt, 4 | sflag, first, h->ev_first));
       h->carry.p1_first = true;
       ++h->cut_product_steps;
     }
   }
   h->step.tail_rows = h->step.tail_rows2 = 0;
-  if (!h->carry.p1_first && !h->sharded && ovl && h->early_tail_on && n >= 8192 && !want_vals && h->test_mutate != 1) {
+  if (!h->carry.p1_first && !h->p.sharded && ovl && h->p.early_tail_on && n >= 8192 && !want_vals && h->test_mutate != 1) {
     // The tail's first pass needs P1_ij and P1_ji: the rows the product has finished in BOTH orientations.  Its tiles run
     // in groups of four row panels, so behind a cut on whole rounds of the chip at ~0.8 of the launch the first
     // `tail_rows` rows are complete, and the pass over them runs beside the product's last rounds (N = 10 000: the cut
@@ -428,7 +428,7 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
     if (cut2 <= cut || cut2 >= total || rows2 <= rows) { cut2 = 0; rows2 = 0; }
     if (cut >= slots && cut < total && rows >= n / 2) {
       MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, 0, -1, h->KY, sizeof(float) * ((size_t)n * ld - tail_ps_floats(h)),
-                            h->split_planes, h->amax, p_off, p_cnt, sflag, cut, h->ev_first, cut2, cut2 ? h->ev_second : nullptr));
+                            h->p.split_planes, h->amax, p_off, p_cnt, sflag, cut, h->ev_first, cut2, cut2 ? h->ev_second : nullptr));
       h->step.tail_rows = rows;
       h->step.tail_rows2 = rows2;
       ++h->cut_product_steps;
@@ -436,7 +436,7 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
   }
   if (!h->carry.p1_first && h->step.tail_rows == 0)
   MCGRA_HIP(split3_symm(sp, n, h->Apack, h->Bpack, h->KX, ld, 0, -1, h->small_slab ? h->small_slab : h->KY,
-                        h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->split_planes, h->amax, p_off, p_cnt, sflag));
+                        h->small_slab ? h->small_slab_bytes : sizeof(float) * (size_t)n * ld, h->p.split_planes, h->amax, p_off, p_cnt, sflag));
   CHK(timer_end(h, sp, h->profile, 2.0 * (double)n * n * (double)(R1 - R0)));
   ++h->split_steps;
   if (ovl) MCGRA_HIP(hipEventRecord(h->ev_join, h->st2));
@@ -453,9 +453,9 @@ static int fork_p1(mcgra_attack* h, hipStream_t st, bool want_vals, bool behind_
 static int fork_p1_early(const FusedStep& s) {      // (called with R1 > R0: p_cnt > 0)
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   CHK(carry_drop(h, st));      // (two forwards in a row)
-  if (!s.use1 || !h->overlap || !h->st2 || h->test_mutate == 1) return 0;
+  if (!s.use1 || !h->p.overlap || !h->st2 || h->test_mutate == 1) return 0;
   CHK(pack_on_side_stream(h, st, s.p_off, s.p_cnt, s.use2 ? h->A1 : nullptr,
-                          s.use2 ? pack_row_sums(h, split3_pack_rsq_parts(s.n, h->split_planes)) : nullptr, false));
+                          s.use2 ? pack_row_sums(h, split3_pack_rsq_parts(s.n, h->p.split_planes)) : nullptr, false));
   const auto cut0 = h->cut_product_steps, split0 = h->split_steps;
   CHK(fork_p1(h, st, true));
   h->carry.p1_early = h->step.p1_inflight;
@@ -502,10 +502,10 @@ static int fs_pack_fork(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, ld = s.ld, hs = s.hs, Le = s.Le, R0 = s.R0, R1 = s.R1, he = s.he, p_off = s.p_off, p_cnt = s.p_cnt;
   const bool mse = s.mse, use1 = s.use1, use2 = s.use2, want_vals = s.want_vals;
-  const int np = split3_pack_rsq_parts(n, h->split_planes);      // (the pack's per-block row partials: sums of squares in A1, pack_row_sums)
+  const int np = split3_pack_rsq_parts(n, h->p.split_planes);      // (the pack's per-block row partials: sums of squares in A1, pack_row_sums)
   bool behind_pack = false;      // (the product forked behind the early pack: fork_p1)
   // planes of Xc^T rows straight from M, |xc_i|^2 from the same pass
-  if (h->late_mean) {
+  if (late_mean(h)) {
     // uncentred planes ((H Kf H) 1 = 0: the product does not see the centring vector), row sums and sums of squares of
     // adj_norm from the same pass -> the column means (adj_norm is symmetric) and |xc_i|^2
     if (h->carry.early_pack) {
@@ -513,14 +513,14 @@ static int fs_pack_fork(FusedStep& s) {
       // reads the planes or the pack's row partials (k_mean_fin, planes_mm) waits for it here
       MCGRA_HIP(hipStreamWaitEvent(st, h->ev_pack, 0));
       h->carry.early_pack = false;
-      behind_pack = h->p1_behind_pack_on;
+      behind_pack = h->p.p1_behind_pack_on;
     } else
-      split3_pack_from_m(st, n, ld, h->M, h->r, nullptr, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr, 0, -1,
+      split3_pack_from_m(st, n, ld, h->M, h->r, nullptr, h->Bpack, h->p.split_planes, h->amax ? h->amax + 1 : nullptr, 0, -1,
                          use2 ? h->A1 : nullptr, pack_row_sums(h, np));
-    h->step.planes_valid = h->planes_mm_on;          // (the means themselves: behind the fork, below)
+    h->step.planes_valid = planes_mm_on(h);          // (the means themselves: behind the fork, below)
   } else
   if (p_cnt > 0 && !mse && !h->carry.p1_early) {
-    split3_pack_from_m(st, n, ld, h->M, h->r, h->cmean, h->Bpack, h->split_planes, h->amax ? h->amax + 1 : nullptr, p_off, p_cnt,
+    split3_pack_from_m(st, n, ld, h->M, h->r, h->cmean, h->Bpack, h->p.split_planes, h->amax ? h->amax + 1 : nullptr, p_off, p_cnt,
                        use2 ? h->A1 : nullptr);
     if (use2)
       hipLaunchKernelGGL(k_rsq_fin, dim3((R1 - R0 + 3) / 4), dim3(256), 0, st, R0, R1, np, h->A1, h->lrRs);
@@ -541,7 +541,7 @@ static int fs_pack_fork(FusedStep& s) {
   }
 
   // (behind the fork: nothing in front of the product needs them)
-  if (h->late_mean) {
+  if (late_mean(h)) {
     hipLaunchKernelGGL(k_mean_fin, dim3((n + 3) / 4), dim3(256), 0, st, n, np, pack_row_sums(h, np), use2 ? h->A1 : nullptr, h->cmean, h->rowsx,
                        use2 ? h->lrRs : nullptr);
     fl_mean_stats(st, n, h->cmean, h->r, h->fstat + 192, h->mm + 3);      // sum(mean); (the operand-scale bound stays max r^2)
@@ -549,7 +549,7 @@ static int fs_pack_fork(FusedStep& s) {
   if (want_vals) MCGRA_HIP(hipMemsetAsync(h->scal + 2, 0, sizeof(double) * (S_COUNT - 2), st));
   // embedding(features, adj_norm) of this iteration (= the victim chain's activations: shared weights, main.py:190),
   // kept for the post-loop decode (:300): adj_norm itself is never stored
-  MCGRA_HIP(hipMemcpy2DAsync(h->em_last, (size_t)h->hmax * 4, h->Hv + h->off[Le - 1], (size_t)hs * 4, (size_t)he * 4, n,
+  MCGRA_HIP(hipMemcpy2DAsync(h->em_last, (size_t)h->p.hmax * 4, h->Hv + h->p.off[Le - 1], (size_t)hs * 4, (size_t)he * 4, n,
                              hipMemcpyDeviceToDevice, st));
 
   // (the small-operand terms c9 / c10 pick up here on a third stream; their ~16 tiny launches are ENQUEUED further down: the
@@ -567,15 +567,15 @@ static int fs_head_bwd(FusedStep& s) {
   const mcgra_attack_config_t& c = h->cfg;
   const int n = s.n, ld = s.ld, hs = s.hs, L = s.L, C = s.C, he = s.he;
   const bool want_vals = s.want_vals;
-  if (h->fused_post && fl_head_bwd_supported(C, h->wdt[L - 1], he)) {      // k_nll_grad + k_rowmat_mask in one launch
-    fl_head_bwd_nll(st, n, C, h->wdt[L - 1], h->Wlin, h->Pv + h->off[L - 1], h->GPv + h->off[L - 1], hs, h->logp, h->sm, h->labels,
-                    h->cnt, (float)(c.weight_sup / h->na), h->GZ, h->rowvals + 6 * (size_t)ld);
+  if (h->p.fused_post && fl_head_bwd_supported(C, h->p.wdt[L - 1], he)) {      // k_nll_grad + k_rowmat_mask in one launch
+    fl_head_bwd_nll(st, n, C, h->p.wdt[L - 1], h->Wlin, h->Pv + h->p.off[L - 1], h->GPv + h->p.off[L - 1], hs, h->logp, h->sm, h->labels,
+                    h->cnt, (float)(c.weight_sup / h->p.na), h->GZ, h->rowvals + 6 * (size_t)ld);
     if (want_vals) launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, n, 1, h->scal + S_NLL);
   } else {
-    launch_nll_grad(st, n, C, h->logp, h->sm, C, h->labels, h->cnt, (float)(c.weight_sup / h->na), h->GZ, h->rowvals + 6 * (size_t)ld);
+    launch_nll_grad(st, n, C, h->logp, h->sm, C, h->labels, h->cnt, (float)(c.weight_sup / h->p.na), h->GZ, h->rowvals + 6 * (size_t)ld);
     if (want_vals) launch_reduce_rows(st, h->rowvals + 6 * (size_t)ld, n, 1, h->scal + S_NLL);
-    launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                       h->Pv + h->off[L - 1], hs, h->act, nullptr, 0, h->GPv + h->off[L - 1], hs);
+    launch_rowmat_mask(st, n, C, h->p.wdt[L - 1], h->GZ, C, h->Wlin, h->p.wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                       h->Pv + h->p.off[L - 1], hs, h->cfg.act, nullptr, 0, h->GPv + h->p.off[L - 1], hs);
   }
   return GO;
 }
@@ -588,19 +588,19 @@ static int fs_decode_stats(FusedStep& s) {
   // (small-operand terms on the caller's stream -- the fused MSELoss step of a small graph: the zero fills of what they and the
   //  decode accumulate into ride in this launch instead of three launches of their own)
   {
-    const ZeroFill zf{h->Gem, (size_t)n * h->hmax, s.use10 ? h->Gsm : nullptr, s.use10 ? (size_t)n * C : 0, h->nmask, 2};
-    launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->hmax, h->nrm, 2.f, h->Zpair, zero_inline ? &zf : nullptr);
+    const ZeroFill zf{h->Gem, (size_t)n * h->p.hmax, s.use10 ? h->Gsm : nullptr, s.use10 ? (size_t)n * C : 0, h->nmask, 2};
+    launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->p.hmax, h->nrm, 2.f, h->Zpair, zero_inline ? &zf : nullptr);
     if (zero_inline) h->step.nmask_zero = true;
   }
   if (s.kl) {
     // calc_kl's row statistics (logsumexp of adj_norm's and of modified_adj1's rows) from M, r and Zn: the decode backward and
     // the tail need those of EVERY row (d c2 / d A1_ij + d c2 / d A1_ji), so a row-block rank gathers its peers' first
-    (void)fl_decode_stats(st, n, R0, R1, he, h->Zn, h->hmax, h->Zpair, h->M, ld, h->r, h->klpart, h->klA, h->kl1);
+    (void)fl_decode_stats(st, n, R0, R1, he, h->Zn, h->p.hmax, h->Zpair, h->M, ld, h->r, h->klpart, h->klA, h->kl1);
     if (h->test_mutate == 4) {      // TEST-ONLY mutation: the row statistics wiped before the decode and the tail read them
       MCGRA_HIP(hipMemsetAsync(h->klA, 0, sizeof(float) * (size_t)n, st));
       MCGRA_HIP(hipMemsetAsync(h->kl1, 0, sizeof(float) * (size_t)n, st));
     }
-    if (h->sharded) rows_to_stage2(h, st, narrow_stage(h), 1, h->klA, 1, 0, 1, h->kl1, 1, 1);
+    if (h->p.sharded) rows_to_stage2(h, st, narrow_stage(h), 1, h->klA, 1, 0, 1, h->kl1, 1, 1);
   }
   return s.kl ? xchg_sg(s) : GO;
 }
@@ -615,7 +615,7 @@ static int decode_fly(const FusedStep& s, hipStream_t s4, bool forked, bool zero
   }
   if (zero) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, 2 * sizeof(unsigned int), s4));
   h->step.nmask_zero = false;
-  h->step.fs_np = fl_decode_fly(s4, s.n, s.R0, s.R1, s.he, h->Zn, h->hmax, (float)(s.k7 / s.n2), slabs, rowvals, h->GZn, h->hmax, h->nmask, h->Zpair,
+  h->step.fs_np = fl_decode_fly(s4, s.n, s.R0, s.R1, s.he, h->Zn, h->p.hmax, (float)(s.k7 / s.n2), slabs, rowvals, h->GZn, h->p.hmax, h->nmask, h->Zpair,
                            want_vals, mse ? h->M : nullptr, s.ld, h->r, s.kmse2, kl ? h->klA : nullptr, kl ? h->kl1 : nullptr,
                            kl ? h->klpart : nullptr);
   return 0;
@@ -639,7 +639,7 @@ static int decode_monolithic(FusedStep& s) {
   // (an elementwise measure -- MSELoss, KL -- has no factor chain: the caller's stream would only wait for the decode, and the
   //  fork and the join cost it two event round trips (~17 us each): the decode stays on the caller's stream there -- Cora-shaped
   //  MSELoss 0.248 -> 0.214 ms, KL 0.307 -> 0.271; A/B MCGRA_MSE_DECODE_SIDE=1)
-  hipStream_t s4 = (h->st3 != st && n < 4096 && (!mse || h->mse_decode_side)) ? h->st4 : st;
+  hipStream_t s4 = (h->st3 != st && n < 4096 && (!mse || h->p.mse_decode_side)) ? h->st4 : st;
   // (with c2, k_post_mask leaves the counter at zero for the next fused step; the general path does not)
   CHK(decode_fly(s, s4, s4 != st, !h->step.nmask_zero, h->ws_dec, h->rowvals, want_vals));
   if (want_vals) launch_reduce_rows(s4, h->rowvals, h->step.fs_np, 1, h->scal + S_V7);
@@ -671,20 +671,20 @@ static int decode_rank(FusedStep& s) {
   hipLaunchKernelGGL(k_u32x2_to_f64, dim3(1), dim3(1), 0, s4, h->nmask, lane_slot(h, sg, 0), lane_slot(h, sg, 1));
   if (h->step.fs_np > 0) launch_reduce_rows(s4, h->rowvals + 6 * (size_t)ld, h->step.fs_np, 1, lane_slot(h, sg, 2));
   else MCGRA_HIP(hipMemsetAsync(lane_slot(h, sg, 2), 0, sizeof(double), s4));
-  if (use2) rows_to_stage2(h, s4, sg, he, h->GZn, h->hmax, 0, 2, reinterpret_cast<const float*>(h->lrRs), 2, he);     // |xc_i|^2 (double) as two words
+  if (use2) rows_to_stage2(h, s4, sg, he, h->GZn, h->p.hmax, 0, 2, reinterpret_cast<const float*>(h->lrRs), 2, he);     // |xc_i|^2 (double) as two words
   else if (kl) {      // + the own rows' v_i, and the rank's share of c2's value in a fourth lane slot
     fl_kl_v_fin(s4, n, R0, R1, h->klpart, h->klvsum, h->klv);
     if (R1 > R0) launch_reduce_rows(s4, h->klvsum + R0, R1 - R0, 1, lane_slot(h, sg, 3));
     else MCGRA_HIP(hipMemsetAsync(lane_slot(h, sg, 3), 0, sizeof(double), s4));
-    rows_to_stage2(h, s4, sg, he, h->GZn, h->hmax, 0, 1, h->klv, 1, he);
+    rows_to_stage2(h, s4, sg, he, h->GZn, h->p.hmax, 0, 1, h->klv, 1, he);
   }
-  else rows_to_stage(h, s4, sg, he, h->GZn, h->hmax, 0);
+  else rows_to_stage(h, s4, sg, he, h->GZn, h->p.hmax, 0);
   return decode_end(s, s4, dec_side);
 }
 static int fs_decode(FusedStep& s) {
   mcgra_attack* h = s.h;
-  if (s.kl && h->sharded) stage_to_rows2(h, s.st, narrow_stage(h), 1, 0, h->klA, 1, 1, 1, h->kl1, 1);
-  CHK(h->sharded ? decode_rank(s) : decode_monolithic(s));
+  if (s.kl && h->p.sharded) stage_to_rows2(h, s.st, narrow_stage(h), 1, 0, h->klA, 1, 1, 1, h->kl1, 1);
+  CHK(h->p.sharded ? decode_rank(s) : decode_monolithic(s));
   MCGRA_KERNEL_CHECK();
   return s.use2 ? GO : xchg_sg(s);
 }
@@ -698,12 +698,12 @@ static int fs_lr_prep(FusedStep& s) {
   if (!s.use2) return GO;
   // (the dense form where this chain is the critical path -- a row-block rank, a graph whose product is short -- and the
   // slow one beside the long product of a large monolithic graph, which the dense one holds up: lowrank_kernels.hip)
-  launch_lr_colstats(st, n, he, h->Zn, h->hmax, h->lrStats, (h->sharded && h->world > 1) || n < 8192);
+  launch_lr_colstats(st, n, he, h->Zn, h->p.hmax, h->lrStats, (h->p.sharded && h->p.world > 1) || n < 8192);
   // (the right-hand side r o V of the product below comes out of the same launch: fl_cat_scaled's values)
-  launch_lr_prep(st, n, he, h->Zn, h->hmax, h->lrStats, h->lrL, h->lrV, h->lr_ldv, h->lrDelta, h->fused_post ? h->r : nullptr,
-                 h->fused_post ? h->FV : nullptr, fc);
-  fl_wcolsum(st, n, 2 * he, h->lrV, h->lr_ldv, nullptr, h->fstat, nullptr, h->fstat + 256);
-  if (!h->fused_post) fl_cat_scaled(st, n, 2 * he, 2 * he, h->lrV, h->lr_ldv, h->r, h->FV, fc, 0);
+  launch_lr_prep(st, n, he, h->Zn, h->p.hmax, h->lrStats, h->lrL, h->lrV, h->p.lr_ldv, h->lrDelta, h->p.fused_post ? h->r : nullptr,
+                 h->p.fused_post ? h->FV : nullptr, fc);
+  fl_wcolsum(st, n, 2 * he, h->lrV, h->p.lr_ldv, nullptr, h->fstat, nullptr, h->fstat + 256);
+  if (!h->p.fused_post) fl_cat_scaled(st, n, 2 * he, 2 * he, h->lrV, h->p.lr_ldv, h->r, h->FV, fc, 0);
   CHK(mm_rows(h, st, 2 * he));
   return GO;
 }
@@ -716,8 +716,8 @@ static int fs_small_terms(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st, s3 = s.s3;
   const int n = s.n, hs = s.hs, C = s.C, he = s.he;
   const bool zero_inline = s.zero_inline, want_vals = s.want_vals;
-  if (!zero_inline) MCGRA_HIP(hipMemsetAsync(h->Gem, 0, sizeof(float) * (size_t)n * h->hmax, s3));
-  if (s.use9) CHK(small_term(h, s3, he, s.em, hs, h->HAg, h->HAc, s.sg * s.k9, h->Gem, h->hmax, S_C9, want_vals));
+  if (!zero_inline) MCGRA_HIP(hipMemsetAsync(h->Gem, 0, sizeof(float) * (size_t)n * h->p.hmax, s3));
+  if (s.use9) CHK(small_term(h, s3, he, s.em, hs, h->HAg, h->HAc, s.sg * s.k9, h->Gem, h->p.hmax, S_C9, want_vals));
   if (s.use10) {
     if (!zero_inline) MCGRA_HIP(hipMemsetAsync(h->Gsm, 0, sizeof(float) * (size_t)n * C, s3));
     CHK(small_term(h, s3, C, h->sm2, C, h->YAg, h->YAc, s.sg * s.k10, h->Gsm, C, S_C10, want_vals));
@@ -725,7 +725,7 @@ static int fs_small_terms(FusedStep& s) {
   }
   if (s3 != st) MCGRA_HIP(hipEventRecord(h->ev_join3, s3));
 
-  if (h->sharded && h->step.fs_dec_forked) {      // the decode's rows and lane slots ride in the gather below
+  if (h->p.sharded && h->step.fs_dec_forked) {      // the decode's rows and lane slots ride in the gather below
     MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join4, 0));
     h->step.fs_dec_forked = false;
   }
@@ -736,11 +736,11 @@ static int fs_lr_t(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, ld = s.ld, fc = s.fc, he = s.he;
   const bool kl = s.kl, use2 = s.use2;
-  if (h->sharded) {
+  if (h->p.sharded) {
     const Stage sg = use2 ? wide_stage(h) : narrow_stage(h);
-    if (use2) stage_to_rows2(h, st, sg, he, 0, h->GZn, h->hmax, 2, he, reinterpret_cast<float*>(h->lrRs), 2);
-    else if (kl) stage_to_rows2(h, st, sg, he, 0, h->GZn, h->hmax, 1, he, h->klv, 1);
-    else stage_to_rows(h, st, sg, he, 0, h->GZn, h->hmax);
+    if (use2) stage_to_rows2(h, st, sg, he, 0, h->GZn, h->p.hmax, 2, he, reinterpret_cast<float*>(h->lrRs), 2);
+    else if (kl) stage_to_rows2(h, st, sg, he, 0, h->GZn, h->p.hmax, 1, he, h->klv, 1);
+    else stage_to_rows(h, st, sg, he, 0, h->GZn, h->p.hmax);
     lane_sum(h, st, sg, kl ? 4 : 3, h->SC + 8);              // SC[8] masked pairs, SC[9] dead rows, SC[10] entropy term of modified_adj1 (KL: SC[11] the value of c2)
     MCGRA_HIP(hipMemcpyAsync(h->scal + S_V7, h->SC + 10, sizeof(double), hipMemcpyDeviceToDevice, st));
     // A dead embedding row voids the low-rank algebra (k_post_mask).  The counts are posted to mapped host memory now and
@@ -754,19 +754,19 @@ static int fs_lr_t(FusedStep& s) {
   }
   if (use2) {
     if (!h->step.t3_zero) {                                                                        // t3 = 0
-      MCGRA_HIP(hipMemset2DAsync(h->lrT + 2 * he, (size_t)h->lr_ldv * 4, 0, 4, n, st));
+      MCGRA_HIP(hipMemset2DAsync(h->lrT + 2 * he, (size_t)h->p.lr_ldv * 4, 0, 4, n, st));
       h->step.t3_zero = true;
     }
-    if (h->fused_post && he <= 32) {      // [W | W2] = Xc^T Vc and the per-column terms behind it in one launch
-      launch_lrt_lr_post(st, n, he, h->fy, h->FV, fc, h->r, h->cmean, h->fstat, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC,
+    if (h->p.fused_post && he <= 32) {      // [W | W2] = Xc^T Vc and the per-column terms behind it in one launch
+      launch_lrt_lr_post(st, n, he, h->fy, h->FV, fc, h->r, h->cmean, h->fstat, h->lrT, h->p.lr_ldv, h->lrStats, h->lrR, h->lrC,
                          h->rowvals + 7 * (size_t)ld);
     } else {
-      fl_lrt_post(st, n, 2 * he, h->fy, h->FV, fc, h->r, h->cmean, h->fstat, h->lrT, h->lr_ldv);  // [W | W2] = Xc^T Vc
-      launch_lr_post(st, n, he, h->lrT, h->lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
+      fl_lrt_post(st, n, 2 * he, h->fy, h->FV, fc, h->r, h->cmean, h->fstat, h->lrT, h->p.lr_ldv);  // [W | W2] = Xc^T Vc
+      launch_lr_post(st, n, he, h->lrT, h->p.lr_ldv, h->lrStats, h->lrR, h->lrC, h->rowvals + 7 * (size_t)ld);
     }
     // [Q | Q2] = Xc [W | W2]
-    fl_wcolsum(st, n, 2 * he, h->lrT, h->lr_ldv, h->cmean, h->fstat + 64, h->fstat + 128, h->fstat + 256);
-    fl_lrq_pre(st, n, 2 * he, h->lrT, h->lr_ldv, h->r, h->fstat + 64, h->FV, fc);
+    fl_wcolsum(st, n, 2 * he, h->lrT, h->p.lr_ldv, h->cmean, h->fstat + 64, h->fstat + 128, h->fstat + 256);
+    fl_lrq_pre(st, n, 2 * he, h->lrT, h->p.lr_ldv, h->r, h->fstat + 64, h->FV, fc);
     CHK(mm_rows(h, st, 2 * he));
   }
   return use2 ? xchg_fy(s) : GO;
@@ -789,26 +789,26 @@ static int fs_decode_bwd(FusedStep& s) {
   const double sg = s.sg, k2 = s.k2;
   if (h->step.fs_dec_forked) { MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join4, 0)); h->step.fs_dec_forked = false; }
   if (use2) {
-    launch_lr_xtz(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrQtZ);
-    launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->hmax, h->lrDelta, h->lrRs, -2.f * (float)(sg * k2), h->GZn, h->hmax,
+    launch_lr_xtz(st, n, he, h->lrQ, h->Zn, h->p.hmax, h->lrQtZ);
+    launch_lr_part2(st, n, he, h->lrQ, h->Zn, h->p.hmax, h->lrDelta, h->lrRs, -2.f * (float)(sg * k2), h->GZn, h->p.hmax,
                     h->rowvals + 7 * (size_t)ld, h->rowvals + 5 * (size_t)ld, h->lrStats + 2 * he, h->lrQtZ, 2.f * (float)(sg * k2));
     if (want_vals) launch_reduce_rows(st, h->rowvals + 5 * (size_t)ld, n, 1, h->scal + S_H2);
   }
   if (s.s3 != st) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_join3, 0));       // c9 / c10: Gem, GZ2 and their scalars
   // ---- backward: modified_adj chain (embedding + output2), products on M
-  if (use10 && h->fused_post && fl_head_bwd_supported(C, h->wdt[L - 1], he)) {
+  if (use10 && h->p.fused_post && fl_head_bwd_supported(C, h->p.wdt[L - 1], he)) {
     // k_row_normalize_bwd (G_em += ...) + the head's mask pass in one launch
-    fl_head_bwd_em(st, n, C, h->wdt[L - 1], h->Wlin, h->Pu + h->off[L - 1], h->GPu + h->off[L - 1], hs, h->GZ2, he, h->GZn, h->Zn,
-                   h->hmax, h->nrm, h->Gem, h->hmax, L - 1 == Le - 1);
+    fl_head_bwd_em(st, n, C, h->p.wdt[L - 1], h->Wlin, h->Pu + h->p.off[L - 1], h->GPu + h->p.off[L - 1], hs, h->GZ2, he, h->GZn, h->Zn,
+                   h->p.hmax, h->nrm, h->Gem, h->p.hmax, L - 1 == Le - 1);
   } else {
-    launch_row_normalize_bwd(st, n, he, h->GZn, h->Zn, h->hmax, h->nrm, h->Gem, h->hmax);
+    launch_row_normalize_bwd(st, n, he, h->GZn, h->Zn, h->p.hmax, h->nrm, h->Gem, h->p.hmax);
     if (use10) {
-      launch_rowmat_mask(st, n, C, h->wdt[L - 1], h->GZ2, C, h->Wlin, h->wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
-                         h->Pu + h->off[L - 1], hs, h->act, (L - 1 == Le - 1) ? h->Gem : nullptr, h->hmax, h->GPu + h->off[L - 1], hs);
+      launch_rowmat_mask(st, n, C, h->p.wdt[L - 1], h->GZ2, C, h->Wlin, h->p.wdt[L - 1], 1, nullptr, 0, 0, nullptr, 0, 0,
+                         h->Pu + h->p.off[L - 1], hs, h->cfg.act, (L - 1 == Le - 1) ? h->Gem : nullptr, h->p.hmax, h->GPu + h->p.off[L - 1], hs);
     } else {
       if (L > Le) MCGRA_HIP(hipMemsetAsync(h->GPu, 0, sizeof(float) * (size_t)n * hs, st));
-      launch_rowmat_mask(st, n, 0, he, h->Gem, h->hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0, h->Pu + h->off[Le - 1], hs,
-                         h->act, h->Gem, h->hmax, h->GPu + h->off[Le - 1], hs);
+      launch_rowmat_mask(st, n, 0, he, h->Gem, h->p.hmax, h->Wlin, 0, 0, nullptr, 0, 0, nullptr, 0, 0, h->Pu + h->p.off[Le - 1], hs,
+                         h->cfg.act, h->Gem, h->p.hmax, h->GPu + h->p.off[Le - 1], hs);
     }
   }
   // Backward of both chains, one product on M per level: columns [r o G_P_lv of the victim(adj_norm) chain | G_P_lu of
@@ -824,12 +824,12 @@ static int fs_bwd_product(FusedStep& s) {
   const int n = s.n, hs = s.hs, fc = s.fc;
   if (!(h->step.fs_l >= 1 || h->step.fs_l2 >= 1)) { h->fs_state = FS_TAIL_FRONT; return GO; }
   const int lv = h->step.fs_l, lu = h->step.fs_l2;
-  const int wv = lv >= 1 ? h->wdt[lv] : 0, wu = lu >= 1 ? h->wdt[lu] : 0;
-  const float* Xs[2] = {h->GPv + h->off[lv >= 1 ? lv : 0], h->GPu + h->off[lu >= 1 ? lu : 0]};
+  const int wv = lv >= 1 ? h->p.wdt[lv] : 0, wu = lu >= 1 ? h->p.wdt[lu] : 0;
+  const float* Xs[2] = {h->GPv + h->p.off[lv >= 1 ? lv : 0], h->GPu + h->p.off[lu >= 1 ? lu : 0]};
   const float* rs[2] = {h->r, nullptr};
   const int lds[2] = {hs, hs}, ws[2] = {wv, wu};
   if (lv >= 1) fl_cat_segs(st, n, lu >= 1 ? 2 : 1, Xs, lds, rs, ws, h->FV, fc);      // [r o G_P_lv | G_P_lu]
-  else fl_cat_scaled(st, n, wu, wu, h->GPu + h->off[lu], hs, nullptr, h->FV, fc, 0);
+  else fl_cat_scaled(st, n, wu, wu, h->GPu + h->p.off[lu], hs, nullptr, h->FV, fc, 0);
   CHK(mm_rows(h, st, wv + wu));
   return xchg_fy(s);
 }
@@ -838,23 +838,23 @@ static int fs_bwd_post(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, hs = s.hs, Le = s.Le, fc = s.fc;
   const int lv = h->step.fs_l, lu = h->step.fs_l2;
-  const int wv = lv >= 1 ? h->wdt[lv] : 0;
-  if (lv >= 1 && lu >= 1 && h->fused_post && fl_bwd_level_supported(wv, h->wdt[lu], h->wdt[lv - 1], h->wdt[lu - 1])) {
+  const int wv = lv >= 1 ? h->p.wdt[lv] : 0;
+  if (lv >= 1 && lu >= 1 && h->p.fused_post && fl_bwd_level_supported(wv, h->p.wdt[lu], h->p.wdt[lv - 1], h->p.wdt[lu - 1])) {
     // both chains' level in one launch (k_an_post + k_copy_cols + two k_rowmat_mask: same operations, same order)
-    fl_bwd_level(st, n, wv, h->wdt[lu], h->fy, h->FV, fc, h->r, h->wdt[lv - 1], h->W[lv], h->Pv + h->off[lv - 1],
-                 h->GPv + h->off[lv - 1], h->wdt[lu - 1], h->W[lu], h->Pu + h->off[lu - 1], h->GPu + h->off[lu - 1], hs,
-                 (lu - 1 == Le - 1) ? h->Gem : nullptr, h->hmax);
+    fl_bwd_level(st, n, wv, h->p.wdt[lu], h->fy, h->FV, fc, h->r, h->p.wdt[lv - 1], h->W[lv], h->Pv + h->p.off[lv - 1],
+                 h->GPv + h->p.off[lv - 1], h->p.wdt[lu - 1], h->W[lu], h->Pu + h->p.off[lu - 1], h->GPu + h->p.off[lu - 1], hs,
+                 (lu - 1 == Le - 1) ? h->Gem : nullptr, h->p.hmax);
   } else {
     if (lv >= 1) {
-      fl_an_post(st, n, wv, h->fy, h->FV, fc, 0, h->r, h->GT, h->hmax);
-      launch_rowmat_mask(st, n, h->wdt[lv], h->wdt[lv - 1], h->GT, h->hmax, h->W[lv], 1, h->wdt[lv], nullptr, 0, 0, nullptr, 0, 0,
-                         h->Pv + h->off[lv - 1], hs, h->act, nullptr, 0, h->GPv + h->off[lv - 1], hs);
+      fl_an_post(st, n, wv, h->fy, h->FV, fc, 0, h->r, h->GT, h->p.hmax);
+      launch_rowmat_mask(st, n, h->p.wdt[lv], h->p.wdt[lv - 1], h->GT, h->p.hmax, h->W[lv], 1, h->p.wdt[lv], nullptr, 0, 0, nullptr, 0, 0,
+                         h->Pv + h->p.off[lv - 1], hs, h->cfg.act, nullptr, 0, h->GPv + h->p.off[lv - 1], hs);
     }
     if (lu >= 1) {
-      fl_copy_cols(st, n, h->wdt[lu], h->fy, wv, h->GT, h->hmax);
-      launch_rowmat_mask(st, n, h->wdt[lu], h->wdt[lu - 1], h->GT, h->hmax, h->W[lu], 1, h->wdt[lu], nullptr, 0, 0, nullptr, 0, 0,
-                         h->Pu + h->off[lu - 1], hs, h->act, (lu - 1 == Le - 1) ? h->Gem : nullptr, h->hmax,
-                         h->GPu + h->off[lu - 1], hs);
+      fl_copy_cols(st, n, h->p.wdt[lu], h->fy, wv, h->GT, h->p.hmax);
+      launch_rowmat_mask(st, n, h->p.wdt[lu], h->p.wdt[lu - 1], h->GT, h->p.hmax, h->W[lu], 1, h->p.wdt[lu], nullptr, 0, 0, nullptr, 0, 0,
+                         h->Pu + h->p.off[lu - 1], hs, h->cfg.act, (lu - 1 == Le - 1) ? h->Gem : nullptr, h->p.hmax,
+                         h->GPu + h->p.off[lu - 1], hs);
     }
   }
   if (lv >= 1) --h->step.fs_l;
@@ -874,7 +874,7 @@ static int fs_tail_front(FusedStep& s) {
   MCGRA_KERNEL_CHECK();
   (void)tail_reduce_call(s, 1, R0, R1, s.want_vals);
   // (the coefficient of the norm term comes out of k_tail_gd's launch; a rank without rows has no Adam pass to feed)
-  if (!(h->fused_post && R1 > R0)) hipLaunchKernelGGL(k_cn, dim3(1), dim3(1), 0, st, h->scal, (float)(c.weight_sup * 0.001), h->mm + 2);
+  if (!(h->p.fused_post && R1 > R0)) hipLaunchKernelGGL(k_cn, dim3(1), dim3(1), 0, st, h->scal, (float)(c.weight_sup * 0.001), h->mm + 2);
   // (a cut product: the peers' row panels are done at ev_first; the own ones are joined behind the all-to-all)
   if (h->carry.p1_first && h->step.p1_inflight) MCGRA_HIP(hipStreamWaitEvent(st, h->ev_first, 0));
   else {
@@ -894,10 +894,10 @@ static int fs_tail_front(FusedStep& s) {
   // c2) from the gradient -- a parity test that stays green under either is blind to split2_m16_kernel / the fp16-split
   // rank-k rounds of k_tail_reduce
   if (h->test_mutate == 1 && use1) MCGRA_HIP(hipMemsetAsync(h->KX, 0, sizeof(float) * (size_t)n * ld, st));
-  if (h->sharded && use1 && R1 > R0)
-    hipLaunchKernelGGL(k_a2a_pack, dim3(2, h->rpr, h->world), dim3(256), 0, st, n, ld, h->rpr, R0, R1, h->rank, h->KX, h->A2S);
+  if (h->p.sharded && use1 && R1 > R0)
+    hipLaunchKernelGGL(k_a2a_pack, dim3(2, h->p.rpr, h->p.world), dim3(256), 0, st, n, ld, h->p.rpr, R0, R1, h->p.rank, h->KX, h->A2S);
   if (!use1) return GO;
-  if (h->sharded) x_alltoall(s.ex, h->off_a2s, h->off_a2r, (int64_t)h->rpr * h->rpr * 4);
+  if (h->p.sharded) x_alltoall(s.ex, h->off_a2s, h->off_a2r, (int64_t)h->p.rpr * h->p.rpr * 4);
   return AT_XCHG;
 }
 // the product joined, the tail's first pass over the rows still to do, the loss terms' values and gd; a rank gathers gd
@@ -908,28 +908,28 @@ static int fs_tail_reduce(FusedStep& s) {
   const bool mse = s.mse, kl = s.kl, use1 = s.use1, want_vals = s.want_vals;
   CHK(join_p1(s));
   h->carry.p1_first = false;
-  if (h->sharded && use1 && R1 > R0)
-    hipLaunchKernelGGL(k_a2a_unpack, dim3(2, h->rpr, h->world), dim3(256), 0, st, n, ld, h->rpr, R0, R1, h->rank, h->A2R, h->KX);
+  if (h->p.sharded && use1 && R1 > R0)
+    hipLaunchKernelGGL(k_a2a_unpack, dim3(2, h->p.rpr, h->p.world), dim3(256), 0, st, n, ld, h->p.rpr, R0, R1, h->p.rank, h->A2R, h->KX);
   {
     float* ps1 = tail_ps(h);
     double* vpart = tail_vpart(h);
-    h->step.fs_nblk = tail_reduce_call(s, 2, h->sharded ? R0 : h->step.tail_rows, R1, want_vals);
+    h->step.fs_nblk = tail_reduce_call(s, 2, h->p.sharded ? R0 : h->step.tail_rows, R1, want_vals);
     h->step.tail_rows = 0;
     const Stage sgt = narrow_stage(h);
-    if (h->sharded && !(h->step.fs_nblk > 0 && want_vals)) CHK(lane_zero(h, st, sgt, (mse && !kl) ? 3 : 2));
+    if (h->p.sharded && !(h->step.fs_nblk > 0 && want_vals)) CHK(lane_zero(h, st, sgt, (mse && !kl) ? 3 : 2));
     if (h->step.fs_nblk > 0 && want_vals) {
       // HSIC: sum P1 o Xc -> S_H1; MSELoss: sum (F - adj_norm)^2 -> S_V1 and sum (adj_norm - A1)^2 -> S_V2 (k_loss_elem's slots);
       // KL: calc_kl(feature_adj, adj_norm) -> S_H1 (k_kl_rows' slot; c2's value came out of the decode)
-      launch_reduce_rows(st, vpart, h->step.fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 0) : h->scal + ((mse && !kl) ? S_V1 : S_H1));
-      launch_reduce_rows(st, vpart + h->step.fs_nblk, h->step.fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 1) : h->scal + S_V6);
-      if (mse && !kl) launch_reduce_rows(st, vpart + 2 * (size_t)h->step.fs_nblk, h->step.fs_nblk, 1, h->sharded ? lane_slot(h, sgt, 2) : h->scal + S_V2);
+      launch_reduce_rows(st, vpart, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, 0) : h->scal + ((mse && !kl) ? S_V1 : S_H1));
+      launch_reduce_rows(st, vpart + h->step.fs_nblk, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, 1) : h->scal + S_V6);
+      if (mse && !kl) launch_reduce_rows(st, vpart + 2 * (size_t)h->step.fs_nblk, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, 2) : h->scal + S_V2);
     }
     {
-      const bool cn_in_gd = h->fused_post && R1 > R0;
+      const bool cn_in_gd = h->p.fused_post && R1 > R0;
       fl_tail_gd(st, n, R0, R1, ps1, h->d, h->gd, cn_in_gd ? h->scal + S_SQ : nullptr, (float)(c.weight_sup * 0.001),
                  cn_in_gd ? h->mm + 2 : nullptr);
     }
-    if (h->sharded) rows_to_stage(h, st, sgt, 1, h->gd, 1, 0);
+    if (h->p.sharded) rows_to_stage(h, st, sgt, 1, h->gd, 1, 0);
   }
   return xchg_sg(s);
 }
@@ -939,7 +939,7 @@ static int fs_decide(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const bool mse = s.mse, kl = s.kl;
   bool masked = false;
-  if (h->sharded) {
+  if (h->p.sharded) {
     const Stage sgt = narrow_stage(h);
     stage_to_rows(h, st, sgt, 1, 0, h->gd, 1);
     if (mse) lane_sum(h, st, sgt, kl ? 2 : 3, h->SC + 12);   // SC[12] sum (F - adj_norm)^2 (KL: the value of c1), SC[13] entropy term of adj_norm, SC[14] sum (adj_norm - A1)^2
@@ -978,17 +978,17 @@ static int fs_gather_send(FusedStep& s) {
     h->step.planes_valid = false;
     return REDO;
   }
-  if (h->sharded && R1 > R0) {
+  if (h->p.sharded && R1 > R0) {
     float* src = h->step.fs_l == 0 ? h->M : (h->step.fs_l == 1 ? h->am : h->av);
     MCGRA_HIP(hipMemcpyAsync(h->NXS + (size_t)R0 * ld, src + (size_t)R0 * ld, sizeof(float) * (size_t)(R1 - R0) * ld,
                              hipMemcpyDeviceToDevice, st));
   }
-  if (h->sharded) x_allgather(s.ex, h->off_nxn, (int64_t)h->rpr * ld * 4);
+  if (h->p.sharded) x_allgather(s.ex, h->off_nxn, (int64_t)h->p.rpr * ld * 4);
   return AT_XCHG;
 }
 static int fs_gather_recv(FusedStep& s) {
   mcgra_attack* h = s.h;
-  if (h->sharded) {
+  if (h->p.sharded) {
     float* dst = h->step.fs_l == 0 ? h->M : (h->step.fs_l == 1 ? h->am : h->av);
     MCGRA_HIP(hipMemcpyAsync(dst, h->NXS, sizeof(float) * (size_t)s.n * s.ld, hipMemcpyDeviceToDevice, s.st));
   }
@@ -1011,7 +1011,7 @@ static int fs_adam(FusedStep& s) {
     const bool emit = adam_emits_partials(h, may_project, cnt);      // (fused_commit: prep_valid)
     fl_tail_adam(st, n, ld, s.pair, R0, R1, h->G_ADJN, h->gd, h->M, h->am, h->av, h->mm + 2,
                  (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
-                 h->keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
+                 h->p.keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
                  emit ? adam_row_sums(h, cnt) : nullptr,
                  /* the Adam moments are only ever read back through the lower tile pairs (by this kernel and by the general
                     path's tail kernels): their mirrored halves are not written */ 0);
@@ -1019,7 +1019,7 @@ static int fs_adam(FusedStep& s) {
   }
   fused_commit(h);
   if (c.num_edges < 0.5 * s.n2) { CHK(project(h, st)); h->carry.prep_valid = false; }      // (monolithic only: refused at create otherwise)
-  if (h->sharded && h->fs_want) {
+  if (h->p.sharded && h->fs_want) {
     // sum(clamp(adj_changes, 0, 1)) after the update = the row sums the Adam pass just left behind, own rows
     prep_from_partials(st, n, h->G_A, adam_row_sums(h, cnt), h->d, h->r, h->rowsq, h->rowsum, R0, R1);
     const Stage sgc = narrow_stage(h);
@@ -1035,7 +1035,7 @@ static const ScalCopy SCAL_MSE[] = {{S_V1, 12}, {S_V6, 13}, {S_V2, 14}, {S_CLAMP
 static const ScalCopy SCAL_HSIC[] = {{S_H1, 4}, {S_V6, 5}, {S_CLAMPSUM, 6}, {-1, 0}};
 static int fs_scalars(FusedStep& s) {
   mcgra_attack* h = s.h;
-  if (!(h->sharded && h->fs_want)) return GO;
+  if (!(h->p.sharded && h->fs_want)) return GO;
   lane_sum(h, s.st, narrow_stage(h), 1, h->SC + 6);
   for (const ScalCopy* e = s.kl ? SCAL_KL : s.mse ? SCAL_MSE : SCAL_HSIC; e->slot >= 0; ++e)
     MCGRA_HIP(hipMemcpyAsync(h->scal + e->slot, h->SC + e->sc, sizeof(double), hipMemcpyDeviceToDevice, s.st));
@@ -1073,17 +1073,17 @@ int64_t mcgra_attack_exchange_bytes(mcgra_attack_t* h) { return h ? fused_exchan
 
 int mcgra_attack_bind_exchange(mcgra_attack_t* h, void* arena, int64_t bytes) {
   if (!h || !arena) { set_error("null argument"); return MCGRA_EINVAL; }
-  if (!h->sharded) { set_error("not a row-block rank (shard_world == 0)"); return MCGRA_EINVAL; }
+  if (!h->p.sharded) { set_error("not a row-block rank (shard_world == 0)"); return MCGRA_EINVAL; }
   if (bytes < fused_exchange_bytes(h) || ((uintptr_t)arena & 255)) { set_error("exchange arena too small or not 256-byte aligned"); return MCGRA_EINVAL; }
   const int64_t a = 256;
   auto up = [&](int64_t x) { return (x + a - 1) / a * a; };
   h->arena = (char*)arena; h->arena_bytes = bytes;
   int64_t o = 0;
-  h->off_fy = o; o += up((int64_t)h->npad * h->fyw * 4);
-  h->off_sg = o; o += up((int64_t)h->npad * h->sgw * 4);
+  h->off_fy = o; o += up((int64_t)h->p.npad * h->p.fyw * 4);
+  h->off_sg = o; o += up((int64_t)h->p.npad * h->p.sgw * 4);
   h->off_sc = o; o += up(16 * 8);
-  h->off_a2s = o; o += up((int64_t)h->world * h->rpr * h->rpr * 4);
-  h->off_a2r = o; o += up((int64_t)h->world * h->rpr * h->rpr * 4);
+  h->off_a2s = o; o += up((int64_t)h->p.world * h->p.rpr * h->p.rpr * 4);
+  h->off_a2r = o; o += up((int64_t)h->p.world * h->p.rpr * h->p.rpr * 4);
   h->off_nxn = o;
   h->FY = (float*)(h->arena + h->off_fy); h->SG = (float*)(h->arena + h->off_sg); h->SC = (double*)(h->arena + h->off_sc);
   h->A2S = (float*)(h->arena + h->off_a2s); h->A2R = (float*)(h->arena + h->off_a2r); h->NXS = (float*)(h->arena + h->off_nxn);
@@ -1094,7 +1094,7 @@ int mcgra_attack_bind_exchange(mcgra_attack_t* h, void* arena, int64_t bytes) {
 int mcgra_attack_shard_begin(mcgra_attack_t* h, void* stream, int what, int want_scalars) {
   (void)stream;
   if (!h || !h->graph_set) { set_error("engine not set up"); return MCGRA_EINVAL; }
-  if (!h->sharded || !h->arena) { set_error("not a row-block rank, or no exchange arena bound"); return MCGRA_EINVAL; }
+  if (!h->p.sharded || !h->arena) { set_error("not a row-block rank, or no exchange arena bound"); return MCGRA_EINVAL; }
   if (what != MCGRA_SHARD_STEP && what != MCGRA_SHARD_MONITOR && what != MCGRA_SHARD_MONITOR_LAST) { set_error("what = %d", what); return MCGRA_EINVAL; }
   // a step that was begun and never ran to XCHG_DONE (the caller gave up on a collective): its leftovers are dropped
   // by fused_resync at the top of the next step (fs_open is still set); a monitor call holds no such state
@@ -1105,7 +1105,7 @@ int mcgra_attack_shard_begin(mcgra_attack_t* h, void* stream, int what, int want
   h->fs_what = what; h->fs_want = want_scalars ? 1 : 0;
   h->fs_state = 0; h->fw_state = 0;
   h->fs_active = true;
-  if (what == MCGRA_SHARD_STEP && h->world > 1) h->m_is_full = false;      // from here on only the own rows of M are kept current
+  if (what == MCGRA_SHARD_STEP && h->p.world > 1) h->m_is_full = false;      // from here on only the own rows of M are kept current
   return 0;
 }
 
@@ -1144,7 +1144,7 @@ int mcgra_attack_shard_scalars(mcgra_attack_t* h, void* stream, double* out) {  
     double s;
     MCGRA_HIP(hipMemcpyAsync(&s, h->scal + S_SUM, sizeof(double), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipStreamSynchronize(st));
-    out[0] = s / ((double)h->n * h->n);
+    out[0] = s / ((double)h->p.n * h->p.n);
     return 0;
   }
   if (h->fs_want == 2) { for (int i = 0; i < 10; ++i) out[i] = h->fs_scalars[i]; return 0; }
@@ -1154,7 +1154,7 @@ int mcgra_attack_shard_scalars(mcgra_attack_t* h, void* stream, double* out) {  
 
 int mcgra_attack_test_mutate(mcgra_attack_t* h, int what) {
   if (!h || what < 0 || what > 4) { set_error("test_mutate: what = %d", what); return MCGRA_EINVAL; }
-  if (what && !h->testing) {
+  if (what && !h->p.testing) {
     set_error("mcgra_attack_test_mutate: refused -- this engine was not created under MCGRA_TESTING=1 (a defect injector for the "
               "parity suite's mutation guards, never part of a real run)");
     return MCGRA_EINVAL;
@@ -1171,14 +1171,14 @@ int mcgra_attack_test_mutate(mcgra_attack_t* h, int what) {
 
 int mcgra_attack_product_replay(mcgra_attack_t* h, void* stream, int reps, double* ms_per_launch) {
   if (!h || reps < 1) { set_error("bad argument"); return MCGRA_EINVAL; }
-  if (!h->fused_ok || h->fused_mse || !h->carry.fused_last || h->cfg.w[0] == 0.f) {
+  if (!fused_ok(h) || h->p.elementwise() || !h->carry.fused_last || h->cfg.w[0] == 0.f) {
     set_error("product_replay: the last step must have been a fused low-rank step with the c1 term (w1 != 0)");
     return MCGRA_EINVAL;
   }
   // the operand planes of the last step's product are still in Apack / Bpack (Bpack no longer describes M, which does not
   // matter here); KX and KY are scratch between steps
   hipStream_t st = (hipStream_t)stream;
-  const int P = split3_panel(), p_off = h->row0 / P, p_cnt = h->row1 > h->row0 ? (h->row1 - h->row0 + P - 1) / P : 0;
+  const int P = split3_panel(), p_off = h->p.row0 / P, p_cnt = h->p.row1 > h->p.row0 ? (h->p.row1 - h->p.row0 + P - 1) / P : 0;
   if (p_cnt == 0) { if (ms_per_launch) *ms_per_launch = 0.0; return 0; }
   // Rule: wait.  Planes a monitor call is still packing are equally valid operands, and a product a row-block rank's forward forked
   // writes the same scratch.  (The Kx wait it includes never fires here: kx_early_on requires !lr_ok, this call a fused low-rank step.)
@@ -1188,8 +1188,8 @@ int mcgra_attack_product_replay(mcgra_attack_t* h, void* stream, int reps, doubl
   MCGRA_HIP(hipEventCreate(&e1));
   MCGRA_HIP(hipEventRecord(e0, st));
   for (int i = 0; i < reps; ++i)
-    MCGRA_HIP(split3_symm(st, h->n, h->Apack, h->Bpack, h->KX, h->ld, 0, -1, h->KY, sizeof(float) * (size_t)h->n * h->ld, h->split_planes,
-                          h->amax, p_off, p_cnt, h->split_single ? 8 : 0));
+    MCGRA_HIP(split3_symm(st, h->p.n, h->Apack, h->Bpack, h->KX, h->p.ld, 0, -1, h->KY, sizeof(float) * (size_t)h->p.n * h->p.ld, h->p.split_planes,
+                          h->amax, p_off, p_cnt, h->p.split_single ? 8 : 0));
   MCGRA_HIP(hipEventRecord(e1, st));
   MCGRA_HIP(hipEventSynchronize(e1));
   float ms = 0.f;
@@ -1202,9 +1202,9 @@ int mcgra_attack_product_replay(mcgra_attack_t* h, void* stream, int reps, doubl
 
 int mcgra_attack_get_rows(mcgra_attack_t* h, void* stream, float* out) {      // Rule: none.  It reads M, which whatever is in flight also only reads.
   if (!h || !out) { set_error("null argument"); return MCGRA_EINVAL; }
-  const int r0 = h->sharded ? h->row0 : 0, r1 = h->sharded ? h->row1 : h->n;
+  const int r0 = h->p.sharded ? h->p.row0 : 0, r1 = h->p.sharded ? h->p.row1 : h->p.n;
   if (r1 > r0)
-    MCGRA_HIP(hipMemcpy2DAsync(out, (size_t)h->n * 4, h->M + (size_t)r0 * h->ld, (size_t)h->ld * 4, (size_t)h->n * 4, r1 - r0,
+    MCGRA_HIP(hipMemcpy2DAsync(out, (size_t)h->p.n * 4, h->M + (size_t)r0 * h->p.ld, (size_t)h->p.ld * 4, (size_t)h->p.n * 4, r1 - r0,
                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }

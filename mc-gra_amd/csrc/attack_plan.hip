@@ -102,7 +102,7 @@ int plan_attack(const mcgra_attack_config_t& cfg, const PlanEnv& env, AttackPlan
     set_error("bad act / fin_layers");
     return MCGRA_EINVAL;
   }
-  const int n = cfg.n;
+  const int n = p->n = cfg.n;
   // rows of the N x N buffers start on 128-byte lines (ld a multiple of 32 floats; round 3: of 4): the 64- and 128-column
   // tile rows of the tail, the pack and the skinny products are then whole lines (+1 ... 2 % steps/s at N = 10 000, where
   // ld = 10 016; profiles/r04_ab_edge_tiles_ld_align.txt).
@@ -288,7 +288,7 @@ static void plan_text(const AttackPlan& p, char* out, size_t cap) {
     if (len < cap) len += (size_t)snprintf(out + len, cap - len, "%s=%s\n", name, s.c_str());
   };
 #define P_(f) put(#f, (long long)p.f)
-  P_(ld); P_(L); P_(Le); P_(C); P_(na); P_(hsum); P_(hmax); P_(fin0); P_(fin1);
+  P_(n); P_(ld); P_(L); P_(Le); P_(C); P_(na); P_(hsum); P_(hmax); P_(fin0); P_(fin1);
   put_list("off", p.off); put_list("wdt", p.wdt);
   P_(keep_gsym); P_(testing); P_(fwd_reuse); P_(fuse_tail); P_(lr_ok); P_(lr_ldv); P_(split_on); P_(split_planes); P_(split_single);
   P_(split_mode); P_(gram_split); P_(overlap); P_(side_streams); P_(gram_ovl); P_(kx_early_on); P_(small_side_on); P_(fused);

@@ -1,4 +1,6 @@
-// The attack engine's state (one mcgra_attack_t) and the helpers its step implementations share.
+// The attack engine's state (one mcgra_attack_t) and the helpers its step implementations share.  The handle is the constant plan
+// of create (attack_plan.h) and the configuration it was made from, one bit of per-graph state (has_ori), what a call leaves for
+// the next (Carry) and a step's scratch flags (StepScratch), buffers, streams and events, and counters.
 // attack.hip: create / set_* / the general step (every measure, eps != 0, Gram evaluation of linear_HSIC);
 // attack_fused.hip: the low-rank HSIC step evaluated from the learnable adjacency M directly.
 #pragma once
@@ -95,27 +97,22 @@ struct StepScratch {
 };
 
 struct mcgra_attack {
-  mcgra_attack_config_t cfg;
+  mcgra_attack(const mcgra_attack_config_t& c, const mcgra::AttackPlan& plan) : cfg(c), p(plan) {}
+  const mcgra_attack_config_t cfg;
+  const mcgra::AttackPlan p;       // what create decided (attack_plan.h: every switch is described there): the only copy, constant
+  // The one bit of per-graph state (set_graph).  A non-zero ori_adj (never produced by main.py, accepted by the class:
+  // topology_attack.py:164, :185, :188, :302): the general path only (the predicates below the struct).  modified_adj =
+  // clamp(M + ori + eps noise) lives in Abuf (with its clamp gate), the embedding runs on Bbuf = modified_adj - ori in its own
+  // chain (Te / Pe / He / GPe) while output2 keeps the chain on modified_adj.
+  bool has_ori = false;
   Carry carry;                     // what the last call left for the next (above)
   StepScratch step;                // scratch flags of the step / forward in progress (above)
-  mcgra::AttackPlan plan;          // what create decided (attack_plan.h), never written again; apply_plan copies it into the fields below
-  int n = 0, ld = 0, L = 0, Le = 0, C = 0, na = 0, hsum = 0, hmax = 0;
-  int off[MCGRA_MAX_LAYERS + 1];   // column offset of layer l inside the concatenated node buffers
-  int wdt[MCGRA_MAX_LAYERS + 1];   // width of layer l output (dims[l+1])
   int64_t t = 0;                   // Adam step count
   bool have_step = false;
   bool m_is_full = true;           // every row of M is current (a row-block rank after its first step holds its own rows only, until finalize)
-  bool testing = false;            // MCGRA_TESTING=1 at create: mcgra_attack_test_mutate is accepted (refused otherwise)
-  // The monitoring forward of :290-296 (victim on the updated adjacency) is exactly the first forward of the next
-  // iteration (:164-167) when eps == 0: mcgra_attack_monitor leaves its adj_norm, degree vectors, chain and
-  // log-probs in place and the next step adopts them instead of recomputing (bit-identical, one N x N pass and two
-  // skinny products less per step).  MCGRA_NO_FWD_REUSE=1 disables.
-  bool fwd_reuse = true;           // (the adoption itself: Carry::fwd_cached)
-  bool fuse_tail = true;           // apply + rank-k + mirror + Adam in one kernel (MCGRA_NO_FUSED_TAIL=1: separate kernels)
   int test_mutate = 0;             // TEST-ONLY (mcgra_attack_test_mutate, see attack_fused.hip): 1 wipes P1, 2 drops the tail's rank-k terms,
                                    // 3 zeroes MSELoss / KL's per-pair multipliers, 4 wipes the KL row statistics
-  bool keep_gsym = false;          // MCGRA_KEEP_GSYM=1: keep the mirrored packed gradient of each step readable as "G_sym" (parity tests)
-  float* ADJN_next = 0;
+  float* ADJN_next = 0;            // adj_norm of the monitoring forward, adopted by the next step (p.fwd_reuse)
   bool graph_set = false, model_set = false;
   std::vector<void*> allocs;
   // N x N
@@ -132,7 +129,6 @@ struct mcgra_attack {
   float *Wlin = 0, *blin = 0;
   float* Ws[MCGRA_MAX_LAYERS] = {0};   // GraphSAGE self weights (has_self), [dims[l] x dims[l+1]]
   float *S0 = 0, *Sv = 0, *Su = 0;    // self terms X Ws_0 (constant) and H_{l-1} Ws_l of both chains
-  int act = 0, head_act = 0, has_self = 0, fin0 = 1, fin1 = 2;
   // node-level
   float *Tv = 0, *Pv = 0, *Hv = 0, *GPv = 0;   // victim(adj_norm) chain, [n x hsum]
   float *Tu = 0, *Pu = 0, *Hu = 0, *GPu = 0;   // victim/embedding(modified_adj) chain
@@ -140,10 +136,7 @@ struct mcgra_attack {
   float *Zn = 0, *GZn = 0, *Gem = 0;
   float *HA = 0, *YA = 0, *HAg = 0, *HAc = 0, *YAg = 0, *YAc = 0, *Yg = 0, *Gg = 0, *Q = 0;
   float *Q2 = 0, *Gg2 = 0, *coef = 0;
-  // A non-zero ori_adj (never produced by main.py, accepted by the class: topology_attack.py:164, :185, :188, :302): the
-  // general path only.  modified_adj = clamp(M + ori + eps noise) lives in Abuf (with its clamp gate), the embedding runs
-  // on Bbuf = modified_adj - ori in its own chain (Te / Pe / He / GPe) while output2 keeps the chain on modified_adj.
-  bool has_ori = false;
+  // has_ori (above): allocated by the first set_graph that brings one
   float *ORI = 0, *Bbuf = 0, *Te = 0, *Pe = 0, *He = 0, *GPe = 0, *Se = 0;
   float* Abuf = 0;                 // modified_adj after adding_noise (only when eps != 0 or ori != 0; otherwise it is M itself)
   unsigned char* gate = 0;         // clamp pass-through mask of adding_noise's torch.clamp
@@ -157,9 +150,7 @@ struct mcgra_attack {
   size_t ws_bytes = 0;
   int nstrips = 32;
   bool profile = false;
-  // low-rank linear_HSIC(adj_norm, modified_adj1) (lowrank_kernels.hip); MCGRA_NO_LOWRANK=1 disables
-  bool lr_ok = false;              // configuration allows it (HSIC, ReLU embedding, width <= 32)
-  int lr_ldv = 0;
+  // low-rank linear_HSIC(adj_norm, modified_adj1) (lowrank_kernels.hip; p.lr_ok)
   float *lrL = 0, *lrV = 0, *lrT = 0, *lrR = 0, *lrQ = 0, *lrDelta = 0, *lrC = 0;
   double *lrStats = 0, *lrRs = 0, *lrQtZ = 0;
   unsigned int* nmask = 0;
@@ -168,20 +159,10 @@ struct mcgra_attack {
   // right after the normalisation and runs (MFMA-bound) under the HBM-bound rest of the step
   hipStream_t st2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // row-block ranks: the product computes the row panels of the peers first and the own ones last; ev_first is recorded behind
-  // the first part, the P1 all-to-all then runs beside the second (attack_fused.hip; MCGRA_A2A_OVERLAP=0 / 1 forces off / on)
+  // row-block ranks: ev_first is recorded behind the first part of a cut product (p.a2a_overlap; monolithic: p.early_tail_on)
   hipEvent_t ev_first = nullptr, ev_second = nullptr;
-  int a2a_overlap = 0;             // 0: the product in one piece; 1: cut where it is free or cheap (default); 2: always (MCGRA_A2A_OVERLAP=1)
-  // monolithic, n >= 8192: the product is cut behind whole rounds of the chip that cover the first `tail_rows` rows of P1 (both
-  // orientations); the tail's first pass over those rows runs beside the product's last rounds (MCGRA_EARLY_TAIL=0 disables)
-  bool early_tail_on = true;
-  // early pack (attack_fused.hip): the planes of the product's operand are packed on the product's stream as soon as r is
-  // known, beside the forward's two products on the caller's stream (ev_r: r ready; ev_pack: planes and row partials ready)
+  // early pack (p.early_pack_on): ev_r: r ready; ev_pack: planes and row partials ready
   hipEvent_t ev_r = nullptr, ev_pack = nullptr;
-  bool early_pack_on = true;       // MCGRA_EARLY_PACK=0 disables (A/B)
-  bool mse_small_inline = true;    // fused MSELoss step on a small graph: the two one-launch small-operand terms on the caller's stream (MCGRA_MSE_SMALL_INLINE=0: third stream; A/B)
-  bool mse_decode_side = false;    // fused MSELoss / KL step on a small graph: the decode on the fourth stream as in the HSIC step (MCGRA_MSE_DECODE_SIDE=1; A/B)
-  bool early_p1_on = false;        // row-block rank: pack (uncentred) + N x N x N product forked by the FORWARD, as soon as r is complete
   float* small_slab = nullptr;     // split-K slabs of a small graph's N x N x N products (more than an N x N buffer holds: split3_small_slab_bytes)
   size_t small_slab_bytes = 0;
   bool fs_last = false;            // the monitor call in progress was begun as MCGRA_SHARD_MONITOR_LAST
@@ -205,65 +186,32 @@ struct mcgra_attack {
   unsigned int mask_want = 0;                    // sequence number of the post the step in flight will poll for
   int64_t cut_product_steps = 0;   // row-block steps whose product was cut for the all-to-all (a2a_overlap)
   int64_t masked_fused_steps = 0;  // fused steps whose decode relu-masked pairs of live rows (they stand: DESIGN.md section 1b)
-  bool overlap = false;            // MCGRA_OVERLAP=1 forks the N x N x N product onto the engine's own stream
-  // P1 through the split kernel of split_symm_bf16.hip instead of the fp32 MFMA SYMM
-  bool split_on = false;
-  int split_mode = 0;              // 0: fp32 MFMA SYMM; 2: split3_symm_kernel on packed planes
-  unsigned char *Apack = 0, *Bpack = 0;
-  int split_planes = 3;            // 3: bf16 x 3 (six products); 2: fp16 x 2 (three products, operand scales from amax)
-  bool split_single = false;       // MCGRA_SPLIT_BF16=1 (by name only, never a default): P1 as the single-plane product x0 y0 of the fp16 x 2 operands
+  unsigned char *Apack = 0, *Bpack = 0;      // packed planes of the split product's operands (p.split_on)
   float *amax = 0;                 // [0] max |H Kf H| (per graph), [1] max |Xc| (per step, from the centring pass)
   int64_t split_steps = 0;
-  // Gram evaluation (masked / GAT / MCGRA_NO_LOWRANK steps) through the same kernel: planes of Xc, Yc, the combined
-  // Grams and Yc^T; amax[2] = max |Yc|, [3] = max |2 (s1 Kfc + s2 Kyc)|, [4] = max |2 s2 Kxc|, [8..15] = the
-  // (A, B) scale pairs of the four products
-  bool gram_split = false;
-  bool gram_ovl = false;           // its four products on the side stream, beside the rest of the step (MCGRA_GRAM_OVERLAP=0: caller's stream)
-  // a configuration whose every step is a Gram evaluation (no low-rank form): the first product, Kx = Xc Xc^T, needs adj_norm of the
-  // CURRENT M only -- the monitoring forward forks pack + Kx as soon as adj_norm stands, and the next step finds them in flight
-  bool kx_early_on = false;        // (MCGRA_GRAM_KX_EARLY=0: the step packs and forks Kx itself, as in round 5)
-  bool small_side_on = false;      // general step: the small-operand terms c9 / c10 (~20 tiny launches) on the third stream, beside the decode and the N x N passes (MCGRA_SMALL_SIDE=0: caller's stream)
+  // Gram evaluation through the split kernel (p.gram_split)
   double* gram_diag = 0;           // [2][ld]: |xc_i|^2, |yc_i|^2 (diagonals of the centred Grams: scale bound of the combined Grams)
   unsigned char *Gp0 = 0, *Gp1 = 0, *Gp2 = 0;
   int64_t gram_split_steps = 0;
   GemmTimer timer;
-  // fused low-rank step (attack_fused.hip): everything N x N from M and n-vectors; MCGRA_NO_FUSED_LR=1 disables
-  bool fused_ok = false;           // configuration allows it
-  bool fused_mse = false;          // ... as the fused MSELoss step (calc = MSELoss: no product, no low-rank factors; attack_fused.hip)
-  bool fused_kl = false;           // ... as the fused KL step (calc = calc_kl: the MSELoss step's data flow + per-row softmax statistics)
+  // fused step (attack_fused.hip; p.fused)
   float *klA = 0, *kl1 = 0, *klv = 0;      // fused KL step: logsumexp of adj_norm's rows, of modified_adj1's rows, v_i = the row's share of c2
   double *klpart = 0, *klvsum = 0;         // ... per-(column slice, row) partials of the two passes [64][n][2]; v_i in fp64 [ld]
-  int fcols = 0;                   // leading dimension of FV / FY
-  float *FV = 0, *FY = 0;          // right-hand sides / results of the skinny products on M  [n x fcols]
+  float *FV = 0, *FY = 0;          // right-hand sides / results of the skinny products on M  [n x p.fcols]
   mcgra::YView fy{nullptr, 0, 1, 0};      // the last such product as its consumers read it (FY, or the split-K slabs in ws)
   char* rkbuf = 0;                 // packed fp16 planes of the tail's rank-k panels (fl_tail_pack_bytes)
   float *em_last = 0;              // embedding(features, adj_norm) of the last iteration (:300), = its victim-chain activations
   double *fstat = 0;               // small fp64 vectors: colsum(V) [64] | colsum(W) [64] | mean^T W [64] | sum(mean) [2]
-  // Monolithic fused step: the column means of adj_norm come out of the PACK of the product's operand (row sums of the
-  // packed values) instead of out of a 33rd column (M r) of the first forward product; the product's operand is then
-  // packed uncentred -- (H Kf H) 1 = 0, so P1 is the same up to 1e-7 -- and the means are only needed behind the pack.
-  bool late_mean = false;
-  // ... and with uncentred planes of the CURRENT M in Bpack (between the pack of a step and its Adam pass) the skinny
-  // products on M that run beside the N x N x N product read those planes (planes_mm.hip).  MCGRA_PLANES_MM=0 disables.
-  bool planes_mm_on = false;       // (the planes' validity: StepScratch::planes_valid)
-  bool fused_post = true;          // forward: post pass + next layer's T / heads in one launch (MCGRA_NO_FUSED_POST=1: separate kernels)
-  char* pm_scratch = nullptr;
-  // Monolithic fused step with the early pack: the forward's two skinny products on the bf16x3 kernel whose blocks fit beside a
-  // product block (skinny_x3.hip; MCGRA_FWD_X3=0 / 1: gemm_f32 / forced on), and the product forked behind the pack on its own
-  // stream instead of behind the forward (MCGRA_P1_BEHIND_PACK=0 / 1; A/B).  Both default on from n = 8192.
-  bool fwd_x3 = false, p1_behind_pack_on = false;
-  char* sx_scratch = nullptr;      // packed right-hand side of skinny_x3
+  char* pm_scratch = nullptr;      // scratch of planes_mm.hip (p.planes_mm_on)
+  char* sx_scratch = nullptr;      // packed right-hand side of skinny_x3 (p.fwd_x3)
   float* Zpair = nullptr;          // pair-interleaved copy of Zn for the decode's scalar loads (fused_lowrank.hip: k_decode_fly_s)
   int64_t fused_steps = 0;
-  // row-block sharding (mcgra_attack_shard_*): this rank owns rows [row0, row1) of M / am / av
-  bool sharded = false;
-  int world = 1, rank = 0, rpr = 0, npad = 0, row0 = 0, row1 = 0;
+  // row-block sharding (mcgra_attack_shard_*; p.sharded, p.world ... p.fyw)
   char* arena = nullptr;           // caller-owned exchange arena (mcgra_attack_bind_exchange)
   int64_t arena_bytes = 0;
   int64_t off_fy = 0, off_sg = 0, off_sc = 0, off_a2s = 0, off_a2r = 0, off_nxn = 0;
-  float *SG = 0, *A2S = 0, *A2R = 0, *NXS = 0;   // views into the arena: n-vector stage [npad][sgw], all-to-all send / recv, N x N stage
+  float *SG = 0, *A2S = 0, *A2R = 0, *NXS = 0;   // views into the arena: n-vector stage [p.npad][p.sgw], all-to-all send / recv, N x N stage
   double* SC = 0;                  // 16 scalars summed over the ranks (from the stages' scalar lanes)
-  int sgw = 0, fyw = 0;            // row widths (floats, even) of the narrow / wide exchanged node arrays
   // The fused step as a table of stages (attack_fused.hip: FS_STAGES, and FW_STAGES for its forward): a row-block rank runs it
   // to the next exchange point and returns.  The step's constants are rebuilt on every entry (FusedStep); only these cross an
   // exchange:
@@ -275,15 +223,27 @@ struct mcgra_attack {
   double fs_scalars[10] = {0};
 };
 
+// ---- the planned paths as the graph in place allows them
+// A non-zero ori_adj takes the general path only: the fused / low-rank forms assume modified_adj == M and modified_adj1 ==
+// offdiag relu(Zn Zn^T), and the monitoring forward (:290-293) runs on the UNclamped M + ori, so there is nothing for the next
+// step to adopt; a later graph without one has the planned paths again.  (create allocates from the raw plan: the buffers must be
+// there for that later graph.)
+static inline bool lr_ok(const mcgra_attack* h) { return h->p.lr_ok && !h->has_ori; }
+static inline bool fused_ok(const mcgra_attack* h) { return h->p.fused != mcgra::FUSED_NONE && !h->has_ori; }
+static inline bool gram_split(const mcgra_attack* h) { return h->p.gram_split && !h->has_ori; }
+static inline bool late_mean(const mcgra_attack* h) { return h->p.late_mean && !h->has_ori; }
+static inline bool planes_mm_on(const mcgra_attack* h) { return h->p.planes_mm_on && !h->has_ori; }
+static inline bool fwd_reuse(const mcgra_attack* h) { return h->p.fwd_reuse && !h->has_ori; }
+
 // ---- scratch layouts the fused and the general step share
 // The operand pack's per-block row partials in A1: sums of squares [n][np], and behind them (16-byte aligned) the row sums [n][np]
-static inline float* pack_row_sums(const mcgra_attack* h, int np) { return h->A1 + (((size_t)h->n * np + 3) & ~(size_t)3); }
+static inline float* pack_row_sums(const mcgra_attack* h, int np) { return h->A1 + (((size_t)h->p.n * np + 3) & ~(size_t)3); }
 // The row partials of the new M an Adam pass leaves in G_A for the next forward (prep_from_partials): cnt = n * tiles floats,
 // and behind them (8-byte aligned) as many fp64 row sums ...
 static inline double* adam_row_sums(const mcgra_attack* h, size_t cnt) { return reinterpret_cast<double*>(h->G_A + ((cnt + 1) & ~(size_t)1)); }
 // ... which it emits when no projection follows and they fit into G_A.  prep_valid says the same: ONE predicate for both.
 static inline bool adam_emits_partials(const mcgra_attack* h, bool may_project, size_t cnt) {
-  return !may_project && 3 * cnt + 4 <= (size_t)h->n * h->ld;
+  return !may_project && 3 * cnt + 4 <= (size_t)h->p.n * h->p.ld;
 }
 
 // attack_fused.hip

@@ -71,37 +71,37 @@ static inline dim3 g1(size_t count) { return dim3((unsigned)((count + 255) / 256
 // columns | scalar lane], the result of a skinny product on M together with whatever n-vectors and partial scalars are
 // ready at the same point of the step; NARROW = [n-vector columns | scalar lane] for the exchanges without a product.
 struct Stage { float* base; int ld, vec0, lane0; };
-static inline Stage wide_stage(const mcgra_attack* h) { return Stage{h->FY, h->fyw, h->fcols, h->fyw - 2}; }
-static inline Stage narrow_stage(const mcgra_attack* h) { return Stage{h->SG, h->sgw, 0, h->sgw - 2}; }
+static inline Stage wide_stage(const mcgra_attack* h) { return Stage{h->FY, h->p.fyw, h->p.fcols, h->p.fyw - 2}; }
+static inline Stage narrow_stage(const mcgra_attack* h) { return Stage{h->SG, h->p.sgw, 0, h->p.sgw - 2}; }
 static inline void rows_to_stage(mcgra_attack* h, hipStream_t st, const Stage& sg, int w, const float* src, int lds_, int c0) {
-  if (h->row1 > h->row0)
-    hipLaunchKernelGGL(mcgra::k_rows_to_stage, g1((size_t)(h->row1 - h->row0) * w), dim3(256), 0, st, h->row0, h->row1, w, src, lds_, sg.base, sg.ld,
+  if (h->p.row1 > h->p.row0)
+    hipLaunchKernelGGL(mcgra::k_rows_to_stage, g1((size_t)(h->p.row1 - h->p.row0) * w), dim3(256), 0, st, h->p.row0, h->p.row1, w, src, lds_, sg.base, sg.ld,
                        sg.vec0 + c0);
 }
 static inline void rows_to_stage2(mcgra_attack* h, hipStream_t st, const Stage& sg, int w0, const float* s0, int l0, int c0, int w1,
                            const float* s1, int l1, int c1) {
-  if (h->row1 > h->row0)
-    hipLaunchKernelGGL(mcgra::k_rows_to_stage2, g1((size_t)(h->row1 - h->row0) * (w0 + w1)), dim3(256), 0, st, h->row0, h->row1, w0, s0, l0,
+  if (h->p.row1 > h->p.row0)
+    hipLaunchKernelGGL(mcgra::k_rows_to_stage2, g1((size_t)(h->p.row1 - h->p.row0) * (w0 + w1)), dim3(256), 0, st, h->p.row0, h->p.row1, w0, s0, l0,
                        sg.vec0 + c0, w1, s1, l1, sg.vec0 + c1, sg.base, sg.ld);
 }
 static inline void stage_to_rows2(mcgra_attack* h, hipStream_t st, const Stage& sg, int w0, int c0, float* d0, int l0, int w1, int c1,
                            float* d1, int l1) {
-  hipLaunchKernelGGL(mcgra::k_stage_to_rows2, g1((size_t)h->n * (w0 + w1)), dim3(256), 0, st, h->n, sg.base, sg.ld, w0, sg.vec0 + c0, d0, l0, w1,
+  hipLaunchKernelGGL(mcgra::k_stage_to_rows2, g1((size_t)h->p.n * (w0 + w1)), dim3(256), 0, st, h->p.n, sg.base, sg.ld, w0, sg.vec0 + c0, d0, l0, w1,
                      sg.vec0 + c1, d1, l1);
 }
 static inline void stage_to_rows(mcgra_attack* h, hipStream_t st, const Stage& sg, int w, int c0, float* dst, int ldd) {
-  hipLaunchKernelGGL(mcgra::k_stage_to_rows, g1((size_t)h->n * w), dim3(256), 0, st, h->n, w, sg.base, sg.ld, sg.vec0 + c0, dst, ldd);
+  hipLaunchKernelGGL(mcgra::k_stage_to_rows, g1((size_t)h->p.n * w), dim3(256), 0, st, h->p.n, w, sg.base, sg.ld, sg.vec0 + c0, dst, ldd);
 }
 // slot q of this rank's scalar lane (a double)
 static inline double* lane_slot(const mcgra_attack* h, const Stage& sg, int q) {
-  return reinterpret_cast<double*>(sg.base + ((size_t)h->rank * h->rpr + q) * sg.ld + sg.lane0);
+  return reinterpret_cast<double*>(sg.base + ((size_t)h->p.rank * h->p.rpr + q) * sg.ld + sg.lane0);
 }
 static inline int lane_zero(mcgra_attack* h, hipStream_t st, const Stage& sg, int nq) {
   MCGRA_HIP(hipMemset2DAsync(lane_slot(h, sg, 0), (size_t)sg.ld * 4, 0, 8, nq, st));
   return 0;
 }
 static inline void lane_sum(mcgra_attack* h, hipStream_t st, const Stage& sg, int nq, double* out) {
-  hipLaunchKernelGGL(mcgra::k_lane_sum, dim3(1), dim3(64), 0, st, h->world, h->rpr, sg.ld, sg.base + sg.lane0, nq, out);
+  hipLaunchKernelGGL(mcgra::k_lane_sum, dim3(1), dim3(64), 0, st, h->p.world, h->p.rpr, sg.ld, sg.base + sg.lane0, nq, out);
 }
 
 // ---- exchange descriptors (all offsets are bytes from the arena base) ---------------------------------------------------
@@ -134,12 +134,12 @@ static inline FusedStep fused_ctx(mcgra_attack* h, hipStream_t st, mcgra_exchang
   const mcgra_attack_config_t& c = h->cfg;
   FusedStep s{};
   s.h = h; s.st = st; s.ex = ex;
-  s.n = h->n; s.ld = h->ld; s.hs = h->hsum; s.L = h->L; s.Le = h->Le; s.C = h->C; s.fc = h->fcols; s.R0 = h->row0; s.R1 = h->row1;
-  // measure == HSIC (sign -1: :217-220), or -- h->fused_mse -- MSELoss: no product (use1) and no low-rank factors (use2); its two
+  s.n = h->p.n; s.ld = h->p.ld; s.hs = h->p.hsum; s.L = h->p.L; s.Le = h->p.Le; s.C = h->p.C; s.fc = h->p.fcols; s.R0 = h->p.row0; s.R1 = h->p.row1;
+  // measure == HSIC (sign -1: :217-220), or -- h->p.elementwise() -- MSELoss: no product (use1) and no low-rank factors (use2); its two
   // N x N terms are elementwise and live in the decode (d / d modified_adj1) and in the tail's first pass (d / d adj_norm)
-  // -- h->fused_kl (mse is set as well: "an elementwise measure") -- calc_kl: the MSELoss step's data flow with per-row softmax
+  // -- h->p.kl() (mse is set as well: "an elementwise measure") -- calc_kl: the MSELoss step's data flow with per-row softmax
   // statistics in front of the decode (k_decode_stats: one more per-pair pass) and one more gather on a row-block rank
-  const bool mse = s.mse = h->fused_mse, kl = s.kl = h->fused_kl;
+  const bool mse = s.mse = h->p.elementwise(), kl = s.kl = h->p.kl();
   s.sg = mse ? 1.0 : -1.0;
   const double w1 = c.w[0], w2 = c.w[1], w6 = c.w[5], w7 = c.w[6], w9 = c.w[8], w10 = c.w[9];
   s.k1 = w1 * 1000 * AP_C1; s.k2 = w2 * 100 * AP_C2; s.k6 = w6 * 100 * AP_C6; s.k7 = w7 * AP_C7;
@@ -149,24 +149,24 @@ static inline FusedStep fused_ctx(mcgra_attack* h, hipStream_t st, mcgra_exchang
   const bool no_calc = h->test_mutate == 3;
   s.kmse1 = no_calc ? 0.f : kl ? (float)(s.k1 / s.n) : mse ? (float)(s.k1 * 2.0 / s.n2) : 0.f;      // k_loss_elem's multipliers; KL: k / batch (batchmean over rows)
   s.kmse2 = no_calc ? 0.f : kl ? (float)(s.k2 / s.n) : mse ? (float)(s.k2 * 2.0 / s.n2) : 0.f;
-  s.em = h->Hu + h->off[s.Le - 1];
-  s.he = h->wdt[s.Le - 1];
+  s.em = h->Hu + h->p.off[s.Le - 1];
+  s.he = h->p.wdt[s.Le - 1];
   s.a1 = s.use1 ? 2.f * (float)(s.sg * s.k1) : 0.f; s.a2 = s.use2 ? 2.f * (float)(s.sg * s.k2) : 0.f;
   const int P = mcgra::split3_panel();
   s.p_off = s.R0 / P; s.p_cnt = s.R1 > s.R0 ? (s.R1 - s.R0 + P - 1) / P : 0;
   s.nt = mcgra::fl_tail_tiles(s.n);
-  s.pair = !h->sharded;
+  s.pair = !h->p.sharded;
   // side streams: the product on st2, the small-operand terms on st3
-  s.ovl = h->overlap;
+  s.ovl = h->p.overlap;
   // reductions that only feed the returned loss terms are skipped when the caller did not ask for them (a row-block
   // rank keeps them: they ride in exchanges whose layout is fixed)
-  s.want_vals = h->sharded || h->fs_want;
+  s.want_vals = h->p.sharded || h->fs_want;
   // (the fused MSELoss step on a small graph: its small-operand terms are one launch each -- k_mse_small_fused -- and the fork and
   //  the join of a side stream cost the caller's stream more than the two launches do: Cora-shaped 0.214 -> 0.199 ms; KL's terms stay on
   //  their stream -- 0.270 against 0.284 inline as chains of four launches, 0.288 inline as one launch each (built, measured, removed);
   //  A/B MCGRA_MSE_SMALL_INLINE=0)
-  s.s3 = (mse && !kl && !h->sharded && h->mse_small_inline && s.n < 4096) ? st : h->st3;
-  s.zero_inline = s.s3 == st && !h->sharded;      // (see launch_row_normalize in fs_decode_stats)
+  s.s3 = (mse && !kl && !h->p.sharded && h->p.mse_small_inline && s.n < 4096) ? st : h->st3;
+  s.zero_inline = s.s3 == st && !h->p.sharded;      // (see launch_row_normalize in fs_decode_stats)
   return s;
 }
 
@@ -178,16 +178,16 @@ typedef int (*FusedStage)(FusedStep&);
 static inline int run_stages(FusedStep& s, const FusedStage* table, int count, int& next) {
   while (next < count) {
     const int rc = table[next++](s);
-    if (rc == AT_XCHG ? s.h->sharded : rc != GO) return rc;
+    if (rc == AT_XCHG ? s.h->p.sharded : rc != GO) return rc;
   }
   return GO;
 }
 // the two all-gathers a stage may end at: of the wide and of the narrow exchanged node array (attack_fused.hip: Stage)
 static inline int xchg_fy(const FusedStep& s) {      // all-gather of the wide node array
-  if (s.h->sharded) x_allgather(s.ex, s.h->off_fy, (int64_t)s.h->rpr * s.h->fyw * 4);
+  if (s.h->p.sharded) x_allgather(s.ex, s.h->off_fy, (int64_t)s.h->p.rpr * s.h->p.fyw * 4);
   return AT_XCHG;
 }
 static inline int xchg_sg(const FusedStep& s) {      // all-gather of the narrow node array
-  if (s.h->sharded) x_allgather(s.ex, s.h->off_sg, (int64_t)s.h->rpr * s.h->sgw * 4);
+  if (s.h->p.sharded) x_allgather(s.ex, s.h->off_sg, (int64_t)s.h->p.rpr * s.h->p.sgw * 4);
   return AT_XCHG;
 }

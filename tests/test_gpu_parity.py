@@ -1611,6 +1611,36 @@ def test_set_graph_without_ori_restores_the_fused_path(pkg):
     assert eng.fused_steps() == 2
 
 
+@pytest.mark.parametrize("split_bf16", [None, "1"], ids=["default", "single_plane"])
+def test_set_graph_without_ori_restores_the_split_gram_evaluation(pkg, monkeypatch, split_bf16):
+    """The same transition for a configuration whose every step is a Gram evaluation (MCGRA_NO_LOWRANK=1): with a non-zero
+    ori_adj its products run on the fp32 kernel (no split step is counted, and mcgra_attack_product_mode says so), a later
+    set_graph WITHOUT ori_adj has the split evaluation again -- and gives the gradient bits of a fresh engine."""
+    import torch
+    z = _synthetic_case(1100, 11, (16, 16), 4, seed=5)
+    monkeypatch.setenv("MCGRA_NO_LOWRANK", "1")
+    if split_bf16 is not None:
+        monkeypatch.setenv("MCGRA_SPLIT_BF16", split_bf16)
+    fresh = H.engine_from(pkg, z)
+    eng = H.engine_from(pkg, z)
+    planned = 1 if split_bf16 == "1" else 0      # (mcgra_attack_product_mode: 1 is the single-plane product by name, else the fp32 kernel's 0)
+    assert fresh.product_mode() == planned and eng.product_mode() == planned
+    ori = np.triu((np.random.RandomState(1).rand(1100, 1100) < 0.01).astype(np.float32), 1)
+    ori = ori + ori.T
+    eng.set_graph(z["features"], z["adj"], ori, z["feature_adj"], z["labels"], z["idx_attack"])
+    eng.set_adj_changes(H.a0_of(z))
+    eng.step()
+    assert eng.gram_split_steps() == 0 and eng.fused_steps() == 0 and eng.path_stats()["general_steps"] == 1
+    assert eng.product_mode() == 0
+    eng.set_graph(z["features"], z["adj"], None, z["feature_adj"], z["labels"], z["idx_attack"])
+    eng.set_adj_changes(H.a0_of(z))
+    eng.step(); fresh.step()
+    assert eng.gram_split_steps() == 1 and fresh.gram_split_steps() == 1
+    assert eng.product_mode() == planned
+    # (the Adam moments of the handle have seen the ori step, so only the gradient -- which does not -- is compared)
+    assert torch.equal(eng.buffer("G_sym"), fresh.buffer("G_sym"))
+
+
 def test_early_pack_beside_the_forward_is_bit_identical(pkg, monkeypatch):
     """The planes of the N x N x N product's operand are packed on the product's stream as soon as r is known, beside the
     forward's two skinny products (attack_fused.hip: early pack), instead of behind them on the caller's stream
