@@ -304,6 +304,30 @@ int mcgra_top_pairs(void* stream, int n, const float* scores, int ld_scores, con
                     int64_t* pairs /* device [k x 2]: u, v */, float* pair_scores /* device [k], may be NULL */,
                     uint8_t* hits /* device [k], may be NULL; needs labels */);
 
+/* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
+ *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
+ *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score
+ *     scores[idx[a]][idx[b]] and label labels[idx[a]][idx[b]]: row a of the gathered submatrix without its diagonal, so an
+ *     asymmetric matrix is ranked by rows;
+ *   - scores compare as float32 values (-0.0 == +0.0; subnormals and negative scores are ordinary values); the best-first
+ *     ranking of a row is score descending, ties by ascending position b (the position in idx, not the node id);
+ *   - out (device int64 [n_idx][5]), row a = {P, wins, ties, hits, first_rank}: P the positive candidates; wins / ties the
+ *     (positive, negative) candidate pairs whose positive scores higher / the same; hits the positives among the P best of the
+ *     best-first ranking; first_rank = 1 + the candidates that score strictly higher than the best positive, 0 when P == 0.
+ *     With N = n_idx - 1 - P: the row's AUC = (2 wins + ties) / (2 P N), its R-precision = hits / P, its reciprocal rank =
+ *     1 / first_rank, and the reference's calc_mrr on the row (gcn_parameterized.py:18-26: the mean over the positives of
+ *     (1 + the negatives that score strictly higher) / N) = (P N - wins - ties + P) / (P N) -- left to the caller;
+ *   - a candidate score that is NaN or +-inf, or a candidate label other than 0 or 1: MCGRA_EINVAL; the diagonal and the
+ *     unselected rows and columns are not looked at.  After any refusal nothing has been written to out;
+ *   - n_idx (n when idx is NULL) from 2 (MCGRA_EINVAL below) up to MCGRA_NODE_RANK_MAX_NIDX: one workgroup ranks one row
+ *     entirely in LDS; MCGRA_ENOSUP beyond;
+ *   - no floating-point arithmetic: the same bits on every call, whatever order the workgroups run in.
+ * Argument checks that need no device run before any HIP call.  Synchronises `stream`.
+ * Device scratch: 40 bytes per selected node, and 4 bytes per node of the graph when idx is given. */
+#define MCGRA_NODE_RANK_MAX_NIDX 16384
+int mcgra_node_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                            const int64_t* idx, int64_t n_idx, int64_t* out /* device [n_idx][5] */);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

@@ -42,6 +42,7 @@ SYMBOLS = [
     "mcgra_rank_metrics", "mcgra_decode_rank_metrics",
     "mcgra_topk_metrics", "mcgra_top_pairs",
     "mcgra_rank_curves",
+    "mcgra_node_rank_metrics",
 ]
 
 
@@ -123,6 +124,7 @@ def _load():
         "mcgra_top_pairs": [vp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int64, fp, C.c_int, ip, fp, vp],
         "mcgra_rank_curves": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.c_int64, ip, ip, fp, ip, ip, fp,
                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)],
+        "mcgra_node_rank_metrics": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, ip],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

@@ -421,6 +421,78 @@ def top_pairs(pred, k, idx=None, real=None):
     return (pairs, scores) if real is None else (pairs, scores, hits.view(torch.bool))
 
 
+# mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
+# row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
+NODE_RANK_MAX_NIDX = 16384
+NODE_RANK_THREADS = 512
+NODE_RANK_CLASSES = (1024, 2048, 4096, 8192, 16384)
+NODE_RANK_DEGREE_BINS = ((1, 1), (2, 2), (3, 4), (5, 8), (9, 16), (17, 32), (33, None))
+
+
+def _node_rates(cols, n_idx):
+    """The per-node rates and the summary of node_rank_metrics from the five integer columns (numpy int64 [rows, 5]): one
+    float64 division of exact integers each, NaN where the denominator is 0."""
+    P, wins, ties, hits, first = (cols[:, q] for q in range(5))
+    N = n_idx - 1 - P
+    nan = np.full(len(P), np.nan)
+
+    def div(num, den):
+        ok = den > 0
+        return np.where(ok, num.astype(np.float64) / np.where(ok, den, 1).astype(np.float64), nan)
+
+    auc = div(2 * wins + ties, 2 * P * N)
+    rprec = div(hits, P)
+    rr = div(np.ones_like(first), first)
+    mean_rank = div(P * N - wins - ties + P, P * N)
+
+    def mean(x):
+        return float(np.mean(x)) if len(x) else float("nan")
+
+    scored, has_pos = (P > 0) & (N > 0), P > 0
+    by_degree = []
+    for lo, hi in NODE_RANK_DEGREE_BINS:
+        sel = (P >= lo) & (has_pos if hi is None else P <= hi)
+        by_degree.append((lo, hi, int(sel.sum()), mean(auc[sel & scored]), mean(rprec[sel])))
+    summary = {"scored": int(scored.sum()), "macro_auc": mean(auc[scored]), "mrr": mean(rr[has_pos]),
+               "hits_at_1": mean((first[has_pos] == 1).astype(np.float64)), "r_precision": mean(rprec[has_pos]),
+               "by_degree": by_degree}
+    return {"auc": auc, "r_precision": rprec, "reciprocal_rank": rr, "mean_rank": mean_rank}, summary
+
+
+@_on_operand_device
+def node_rank_metrics(real, pred, idx=None):
+    """Whose neighbourhood leaked (mcgra_node_rank_metrics): for each position a of idx (REPEAT-FREE node ids; None: all nodes
+    in order) the candidates are the positions b != a, with score pred[idx[a], idx[b]] and label real[idx[a], idx[b]] -- row a
+    of the gathered submatrix without its diagonal, also for an asymmetric pred -- ranked best first: score descending
+    (float32 values, -0.0 == +0.0), ties by ascending position b.  One workgroup ranks one row in LDS; n_idx <=
+    NODE_RANK_MAX_NIDX (McgraNotSupported beyond).  Returns a dict, one entry per position of idx:
+      "nodes" the ids; "positives" P, "wins" / "ties" the (positive, negative) candidate pairs whose positive scores higher /
+      the same, "hits" the positives among the P best, "first_rank" 1 + the candidates strictly above the best positive (0
+      when P = 0): int64 device tensors, exact;
+      "auc" (2 wins + ties) / (2 P N) with N = n_idx - 1 - P, "r_precision" hits / P, "reciprocal_rank" 1 / first_rank,
+      "mean_rank" (P N - wins - ties + P) / (P N), the reference's calc_mrr (gcn_parameterized.py:18-26: the mean over a row's
+      true edges of their rank among its false ones, over N) on that row: float64 numpy arrays, one division of exact
+      integers each (on the host, from the copied integer columns), NaN where the denominator is 0;
+    and "summary": "scored" (nodes with P > 0 and N > 0), "macro_auc" over those, "mrr", "hits_at_1" (first_rank == 1) and
+    "r_precision" over the nodes with P > 0 -- plain means in index order -- and "by_degree", a list of (lo, hi, count,
+    mean auc, mean r_precision) over P in 1, 2, 3-4, 5-8, 9-16, 17-32, 33 and more (hi None).
+    McgraError for a repeated or out-of-range id, a candidate NaN / inf score or a candidate label other than 0 / 1."""
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
+    rows = ix.numel() if ix is not None else n
+    out = torch.empty(max(rows, 0), 5, device=dev, dtype=torch.int64)
+    check(lib.mcgra_node_rank_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, _p(out)))
+    rates, summary = _node_rates(out.cpu().numpy(), rows)
+    res = {"nodes": ix if ix is not None else torch.arange(n, device=dev, dtype=torch.int64)}
+    res.update({k: out[:, q] for q, k in enumerate(("positives", "wins", "ties", "hits", "first_rank"))})
+    res.update(rates)
+    res["summary"] = summary
+    return res
+
+
 def _curve_first_cap(entries, drop_intermediate):
     """The first attempt's capacity: levels + 1 <= entries + 1 always suffices, and without drop_intermediate little less
     does; with it a curve keeps the corners only, so an eighth of the entries (at least 2^20 points) is tried first and

@@ -22,6 +22,10 @@ reference's roc_curve call returns, and the precision-recall curve beside it, fo
 PATH (roc_fpr_<set>, roc_tpr_<set>, roc_thresholds_<set>, pr_precision_<set>, pr_recall_<set>, pr_thresholds_<set>; sklearn's
 conventions and defaults: drop_intermediate on for the ROC curve, off for the PR curve), computed on the GPU
 (engine.rank_curves, engine.precision_recall_curve), and reports the best F1 over all thresholds.
+--per_node PATH (not in the reference; --mode evaluate only; absent by default, and then nothing changes) asks whose
+neighbourhood leaked: for each node of each of the three index sets, how its true neighbours rank among the set's other nodes
+by its row of modified_adj (engine.node_rank_metrics) -- written as an .npz at PATH (nodes_<set>, positives_<set>, wins_<set>,
+ties_<set>, hits_<set>, first_rank_<set>, auc_<set>), with the macro AUC, the MRR and Hits@1 of each set reported.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -78,11 +82,18 @@ def check_curves_args(args, fail):
         fail(f"--curves draws the curves of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
 
 
+def check_per_node_args(args, fail):
+    """--per_node against the rest of the command line; fail(message) does not return."""
+    if getattr(args, "per_node", None) and args.mode != "evaluate":
+        fail(f"--per_node ranks each node's row of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
         check_topk_args(args, self.error)
         check_curves_args(args, self.error)
+        check_per_node_args(args, self.error)
         return args
 
 
@@ -127,6 +138,7 @@ def build_parser():
     p.add_argument('--topk', type=int, default=None)        # also report the K best pairs' precision / recall / F1
     p.add_argument('--save_edges', type=str, default=None)  # with --topk: the whole-graph edge list as an .npz
     p.add_argument('--curves', type=str, default=None)      # also write the ROC and precision-recall curves as an .npz
+    p.add_argument('--per_node', type=str, default=None)    # also write each node's own ranking counts as an .npz
     return p
 
 
@@ -241,6 +253,24 @@ def curves_report(path, ori_adj, inference_adj, sets):
     return out
 
 
+def per_node_report(path, ori_adj, inference_adj, sets):
+    """--per_node PATH: engine.node_rank_metrics of each index set of `sets` (name -> node ids, None: every node), the integer
+    columns and the per-node AUC written as one .npz at exactly `path` when it is given.  Returns {"per_node_<name>": the
+    set's summary dict}."""
+    real = ori_adj.to(inference_adj.device)
+    out, arrays = {}, {}
+    for name, ix in sets.items():
+        m = engine.node_rank_metrics(real, inference_adj, ix)
+        for k in ("nodes", "positives", "wins", "ties", "hits", "first_rank"):
+            arrays[f"{k}_{name}"] = m[k].cpu().numpy()
+        arrays[f"auc_{name}"] = m["auc"]
+        out[f"per_node_{name}"] = m["summary"]
+    if path:
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+    return out
+
+
 def victim_tensors(m):
     """Every parameter of a victim: the registered ones and those of the layers it keeps in plain lists (models/gcn.py:44,
     graphsage.py:50, gat.py:47 -- as the reference's classes do)."""
@@ -297,6 +327,7 @@ def _exit(message):
 def _run(args, rank, world):
     check_topk_args(args, _exit)
     check_curves_args(args, _exit)
+    check_per_node_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -416,6 +447,10 @@ def _run(args, rank, world):
     if want_curves:         # every rank computes; rank 0 writes the file
         res.update(curves_report(args.curves if rank == 0 else None, ad, inference_adj,
                                  {"attack": idx_attack, "train": idx_train, "all": None}))
+    want_per_node = bool(getattr(args, "per_node", None))
+    if want_per_node:       # every rank computes; rank 0 writes the file
+        res.update(per_node_report(args.per_node if rank == 0 else None, ad, inference_adj,
+                                   {"attack": idx_attack, "train": idx_train, "all": None}))
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
@@ -428,11 +463,14 @@ def _run(args, rank, world):
             save_edges(args.save_edges, ad, inference_adj, res["topk_all"]["k"])
     if want_curves:
         print(f"current best_f1={res['curves_all']['best_f1']} (threshold={res['curves_all']['best_threshold']})")
+    if want_per_node:
+        d = res["per_node_all"]
+        print(f"current macro_auc={d['macro_auc']} mrr={d['mrr']} hits@1={d['hits_at_1']}")
     os.makedirs("./results/", exist_ok=True)
-    # the parameter line names --ap, --topk, --save_edges and --curves only when they are set: without them the log is what
+    # the parameter line names --ap, --topk, --save_edges, --curves and --per_node only when they are set: without them the log is what
     # it was before the flags existed
     hidden = (set() if want_ap else {"ap"}) | (set() if want_topk else {"topk", "save_edges"}) | \
-        (set() if want_curves else {"curves"})
+        (set() if want_curves else {"curves"}) | (set() if want_per_node else {"per_node"})
     shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
     with open(os.path.join("./results", args.log_name), "a") as f:                         # main.py:314-323
         f.write(f"current parameter: {shown}\n")
@@ -450,6 +488,11 @@ def _run(args, rank, world):
                               f"best F1={d['best_f1']} at {d['best_threshold']}" for name, d in
                               (("attack graph", res["curves_attack"]), ("train graph", res["curves_train"]),
                                ("Whole Graph", res["curves_all"]))) + "\n")
+        if want_per_node:
+            for name, d in (("attack graph", res["per_node_attack"]), ("train graph", res["per_node_train"]),
+                            ("Whole Graph", res["per_node_all"])):
+                f.write(f"In {name}: scored nodes={d['scored']} macro AUC={d['macro_auc']} MRR={d['mrr']} "
+                        f"Hits@1={d['hits_at_1']} R-precision={d['r_precision']}\n")
         f.write(f"current density: {res['density']}\n")
     return res
 
