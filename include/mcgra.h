@@ -304,6 +304,69 @@ int mcgra_top_pairs(void* stream, int n, const float* scores, int ld_scores, con
                     int64_t* pairs /* device [k x 2]: u, v */, float* pair_scores /* device [k], may be NULL */,
                     uint8_t* hits /* device [k], may be NULL; needs labels */);
 
+/* The recovered graph WITHOUT the truth: which candidates are edges, decided from the scores alone by a 2-means split (the
+ * reference's PGDAttack.kmeans, baseline.py:88-109, which starts from two random entries, sums float32 in an unspecified
+ * order and stops after 20 rounds; this is a defined, exact and repeatable version of it).
+ *   - candidates, selection, packed position, checks and limits as mcgra_topk_metrics: idx, n_idx REPEAT-FREE device int64
+ *     node ids or NULL for all n nodes; the m = n_idx (n_idx - 1) / 2 pairs of positions a > b with score
+ *     scores[idx[a]][idx[b]] and label labels[idx[a]][idx[b]], p = a (a - 1) / 2 + b; nothing outside the selected strict
+ *     lower triangle is looked at; n_idx from 2 (MCGRA_EINVAL below) to 65 535 (MCGRA_ENOSUP beyond);
+ *   - quantisation: q = rint(s 2^28), round half to even, as an unsigned integer (the product is exact in float32).  A
+ *     selected score must satisfy 0 <= s < 16 (-0.0 counts as 0), so q < 2^32 and any sum of m < 2^31 of them fits 63 bits;
+ *     the range holds the ensemble of up to eight [0, 1] matrices of topology_attack.py:314-320.  A selected score that is
+ *     NaN or +-inf: MCGRA_EINVAL; a finite one below 0 or >= 16: MCGRA_ENOSUP.  Scores of at most 2^-29 (subnormals among
+ *     them) collapse to q = 0: the split does not tell them from 0;
+ *   - the split is Lloyd's iteration on the q, in integers.  lo = min q, hi = max q.  lo == hi (one value): the result is
+ *     DEGENERATE -- iterations = 0, converged = 1, no edges (t = lo + 1, n_high = 0, c0 = c1 = lo, TP = 0) and the thresholds
+ *     are not written.  Otherwise t_0 = floor((lo + hi) / 2) + 1, and round k counts the partition of t_k: the low cluster
+ *     is {q < t_k}, the high cluster {q >= t_k}; c0 = floor(sum_low / n_low), c1 = floor(sum_high / n_high),
+ *     t_{k+1} = floor((c0 + c1) / 2) + 1, so a value equidistant from the two centres goes low (the reference's argmin).
+ *     Both clusters are non-empty in every round (c0 < t_{k+1} <= c1).  iterations = k + 1; the iteration stops when
+ *     t_{k+1} == t_k (converged = 1) or when iterations == max_iter (converged = 0).  What is reported is always the
+ *     partition that was counted, that of t_k;
+ *   - out (host int64[10]) = {m, iterations, converged, t, n_high, c0, c1, P, TP, degenerate}: t, c0, c1 in units of 2^-28;
+ *     P the candidates with label 1 and TP those of them in the high cluster, both -1 when labels is NULL (given, every
+ *     selected label is checked: other than 0 or 1 is MCGRA_EINVAL).  precision = TP / n_high, recall = TP / P,
+ *     F1 = 2 TP / (n_high + P) are left to the caller;
+ *   - *thr_high (host, may be NULL) = the smallest selected score of the high cluster, *thr_low (host, may be NULL) = the
+ *     largest of the low cluster: the bits as stored, -0.0 reported as +0.0.  rint is monotone, so the high cluster is
+ *     exactly {s >= *thr_high} as float32 values: mcgra_threshold_pairs with threshold = *thr_high returns the high cluster;
+ *   - max_iter < 1 and the other argument errors that need no device: MCGRA_EINVAL before any HIP call.  After any refusal
+ *     nothing has been written to out or the thresholds;
+ *   - everything is integer arithmetic merged by integer atomics: the same result whatever order the blocks run in.
+ * Synchronises `stream` (once per four rounds; no kernel waits for another one's progress).
+ * Device scratch: 5 bytes per candidate pair (the 4-byte q and, with labels, the label) plus a few KB. */
+int mcgra_two_means_split(void* stream, int n, const float* scores, int ld_scores,
+                          const float* labels /* may be NULL */, int ld_labels,
+                          const int64_t* idx, int64_t n_idx, int max_iter,
+                          int64_t* out      /* host[10]: m, iterations, converged, t, n_high, c0, c1, P, TP, degenerate */,
+                          float* thr_high   /* host, may be NULL */,
+                          float* thr_low    /* host, may be NULL */);
+
+/* Every candidate with score >= threshold as an edge list in ASCENDING PACKED POSITION: np.nonzero(s >= threshold) over the
+ * scores in packed order.  One entry for three thresholds: *thr_high of mcgra_two_means_split, the reference's filter() cut
+ * (0.9, baseline.py:106-109) and best_thr of mcgra_rank_curves.  Candidates, selection, checks and limits as
+ * mcgra_topk_metrics / mcgra_top_pairs: any finite score, negatives included; a selected NaN or +-inf score, or (given
+ * labels) a selected label other than 0 or 1: MCGRA_EINVAL.
+ *   - the comparison is that of float32 values: -0.0 >= +0.0 holds, subnormals are ordinary values, threshold = +-inf is
+ *     allowed (nothing / everything); a NaN threshold: MCGRA_EINVAL;
+ *   - pairs (device int64 [cap x 2]) = u = idx[a], v = idx[b] (a > b); pair_scores (device [cap], may be NULL) =
+ *     scores[u][v], the bits as stored; hits (device uint8 [cap], may be NULL; needs labels) = 1 where labels[u][v] is 1;
+ *   - counts (host int64[3]) = {m, pairs with score >= threshold, hits among them (-1 without labels)}, written whenever
+ *     the checks pass;
+ *   - capacity, as mcgra_rank_curves: more qualifying pairs than cap: nothing is written to the buffers, the call returns
+ *     MCGRA_ENOMEM, counts holds what is needed and mcgra_last_error() names it.  cap == 0 with pairs NULL asks for the
+ *     counts alone (returns 0);
+ *   - counts NULL, cap < 0, cap > 0 with pairs NULL, hits without labels, a NaN threshold: MCGRA_EINVAL before any HIP call;
+ *   - the order is decided by per-range counts and one scan, never by atomics: the same bits on every call.
+ * Synchronises `stream`.  Device scratch: about 16 KB, and 4 bytes per node of the graph when idx is given. */
+int mcgra_threshold_pairs(void* stream, int n, const float* scores, int ld_scores,
+                          const float* labels /* may be NULL */, int ld_labels,
+                          const int64_t* idx, int64_t n_idx, float threshold, int64_t cap,
+                          int64_t* pairs /* device [cap x 2]: u, v */, float* pair_scores /* device [cap], may be NULL */,
+                          uint8_t* hits  /* device [cap], may be NULL; needs labels */,
+                          int64_t* counts /* host[3]: m, pairs with score >= threshold, hits among them (-1 without labels) */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score

@@ -1,5 +1,6 @@
-// What the ranking entries share (auc.hip: AUC, average precision; topk.hip: the k best pairs): the order-preserving key of
-// a float32 score, the argument predicates, the idx check, integer block sums, and the stable LSD radix sort of 32-bit keys
+// What the ranking entries share (auc.hip: AUC, average precision; topk.hip: the k best pairs; two_means.hip: the 2-means
+// split and the threshold edge list): the order-preserving key of a float32 score, the argument predicates, the idx check,
+// the pair of a packed position, integer block sums, and the stable LSD radix sort of 32-bit keys
 // (optionally with a 32-bit payload) -- per-block digit counts, one scan, a stable scatter.  Everything here is integer
 // work, so no result depends on the order in which blocks run.  Each translation unit gets its own copy of the kernels.
 #pragma once
@@ -29,6 +30,15 @@ __device__ __forceinline__ uint32_t auc_key(float s) {
 __device__ __forceinline__ bool auc_finite(float s) { return (__float_as_uint(s) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool auc_pos(float l) { return __float_as_uint(l) == 0x3f800000u; }
 __device__ __forceinline__ bool auc_neg(float l) { return (__float_as_uint(l) & 0x7fffffffu) == 0u; }
+
+// pair (a, b), a > b >= 0, of packed position p = a (a - 1) / 2 + b
+__device__ __forceinline__ void topk_unpack(uint32_t p, uint32_t& a, uint32_t& b) {
+  uint32_t x = (uint32_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
+  while ((uint64_t)x * (x - 1) / 2 > p) --x;
+  while ((uint64_t)x * (x + 1) / 2 <= p) ++x;
+  a = x;
+  b = p - (uint32_t)((uint64_t)x * (x - 1) / 2);
+}
 
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll

@@ -54,15 +54,6 @@ struct TopkState {
   int flags;
 };
 
-// pair (a, b), a > b >= 0, of packed position p = a (a - 1) / 2 + b
-__device__ __forceinline__ void topk_unpack(uint32_t p, uint32_t& a, uint32_t& b) {
-  uint32_t x = (uint32_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-  while ((uint64_t)x * (x - 1) / 2 > p) --x;
-  while ((uint64_t)x * (x + 1) / 2 <= p) ++x;
-  a = x;
-  b = p - (uint32_t)((uint64_t)x * (x - 1) / 2);
-}
-
 // keys[p] = key of pair p, lab[p] = its label (lab != NULL); st->P += labels that are 1; st->flags |= argument errors.
 // A block owns rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection.
 __global__ __launch_bounds__(AUC_THREADS) void k_topk_emit(int rows, const float* __restrict__ S, int64_t lds,

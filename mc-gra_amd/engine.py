@@ -421,6 +421,69 @@ def top_pairs(pred, k, idx=None, real=None):
     return (pairs, scores) if real is None else (pairs, scores, hits.view(torch.bool))
 
 
+TWO_MEANS_SCALE = 2.0 ** -28      # one unit of the quantised scores of mcgra_two_means_split
+
+
+@_on_operand_device
+def two_means_split(pred, idx=None, real=None, max_iter=256):
+    """Which candidates are edges, decided from the scores alone (mcgra_two_means_split; the reference's PGDAttack.kmeans,
+    baseline.py:88-109, exact and repeatable): Lloyd's 2-means on q = rint(s 2^28) of the candidates of topk_metrics (the pairs
+    of positions a > b of a REPEAT-FREE idx; None: all nodes), in integers, from t_0 = floor((min + max) / 2) + 1, a value
+    equidistant from the two centres going low.  Scores must lie in [0, 16).  Returns {"pairs" (m), "iterations", "converged",
+    "degenerate", "edges" (the size of the high cluster), "threshold" (its smallest score: the high cluster is exactly
+    pred >= threshold, what threshold_pairs returns), "threshold_low" (the largest score of the low cluster), "center_low",
+    "center_high" (c 2^-28 as Python floats), "t", "c0", "c1" (the integers)}; with real also "positives", "hits",
+    "precision" hits / edges, "recall" hits / positives, "f1" 2 hits / (edges + positives).  One distinct value among the
+    candidates is the degenerate case: no edges, iterations 0, thresholds None.  McgraError for a selected NaN / inf score, a
+    label other than 0 / 1 or a repeated id; McgraNotSupported for a finite score outside [0, 16)."""
+    dev = pred.device
+    n = pred.shape[0]
+    assert pred.dim() == 2 and tuple(pred.shape) == (n, n), pred.shape
+    assert real is None or tuple(real.shape) == (n, n), (real.shape, pred.shape)
+    pred = _rows_f32(pred, dev)
+    real = None if real is None else _rows_f32(real, dev)
+    ix = _node_ids(idx, dev)
+    out, hi, lo = (C.c_int64 * 10)(), C.c_float(float("nan")), C.c_float(float("nan"))
+    check(lib.mcgra_two_means_split(_stream(), n, _p(pred), pred.stride(0), _p(real), real.stride(0) if real is not None else 0,
+                                    _p(ix), ix.numel() if ix is not None else n, int(max_iter), out, C.byref(hi), C.byref(lo)))
+    m, it, conv, t, n_high, c0, c1, P, tp, degenerate = (int(v) for v in out)
+    res = {"pairs": m, "iterations": it, "converged": bool(conv), "degenerate": bool(degenerate), "edges": n_high,
+           "threshold": None if degenerate else hi.value, "threshold_low": None if degenerate else lo.value,
+           "center_low": c0 * TWO_MEANS_SCALE, "center_high": c1 * TWO_MEANS_SCALE, "t": t, "c0": c0, "c1": c1}
+    if real is not None:
+        res.update({"positives": P, "hits": tp, "precision": _ratio(tp, n_high), "recall": _ratio(tp, P),
+                    "f1": _ratio(2 * tp, n_high + P)})
+    return res
+
+
+@_on_operand_device
+def threshold_pairs(pred, threshold, idx=None, real=None):
+    """Every candidate of topk_metrics' selection with pred[idx[a], idx[b]] >= threshold (float32 comparison), in ascending
+    packed position (mcgra_threshold_pairs): (pairs [k, 2] int64, scores [k] float32, hits [k] bool or None without real),
+    device tensors.  The counts are asked for first, then exactly k rows are allocated.  With the threshold of
+    two_means_split this is its high cluster; with 0.9 the reference's filter() (baseline.py:106-109)."""
+    dev = pred.device
+    n = pred.shape[0]
+    assert pred.dim() == 2 and tuple(pred.shape) == (n, n), pred.shape
+    assert real is None or tuple(real.shape) == (n, n), (real.shape, pred.shape)
+    pred = _rows_f32(pred, dev)
+    real = None if real is None else _rows_f32(real, dev)
+    ix = _node_ids(idx, dev)
+    rows = ix.numel() if ix is not None else n
+    ldl = real.stride(0) if real is not None else 0
+    counts = (C.c_int64 * 3)()
+    check(lib.mcgra_threshold_pairs(_stream(), n, _p(pred), pred.stride(0), _p(real), ldl, _p(ix), rows, float(threshold), 0,
+                                    None, None, None, counts))
+    k = int(counts[1])
+    pairs = torch.empty(k, 2, device=dev, dtype=torch.int64)
+    scores = torch.empty(k, device=dev, dtype=torch.float32)
+    hits = None if real is None else torch.empty(k, device=dev, dtype=torch.uint8)
+    if k:
+        check(lib.mcgra_threshold_pairs(_stream(), n, _p(pred), pred.stride(0), _p(real), ldl, _p(ix), rows, float(threshold), k,
+                                        _p(pairs), _p(scores), _p(hits), counts))
+    return pairs, scores, None if hits is None else hits.view(torch.bool)
+
+
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
 # row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
 NODE_RANK_MAX_NIDX = 16384

@@ -26,6 +26,13 @@ conventions and defaults: drop_intermediate on for the ROC curve, off for the PR
 neighbourhood leaked: for each node of each of the three index sets, how its true neighbours rank among the set's other nodes
 by its row of modified_adj (engine.node_rank_metrics) -- written as an .npz at PATH (nodes_<set>, positives_<set>, wins_<set>,
 ties_<set>, hits_<set>, first_rank_<set>, auc_<set>), with the macro AUC, the MRR and Hits@1 of each set reported.
+--binarize (not in the reference's main.py; --mode evaluate only; absent by default, and then nothing changes) answers "which
+graph did the attack recover" without the truth: the entries of modified_adj within each index set are split into two
+clusters by an exact integer 2-means (engine.two_means_split; the defined form of PGDAttack.kmeans, baseline.py:88-109), the
+upper cluster is the recovered edge set, and its precision, recall and F1 against the true graph are reported.  The scores
+must lie in [0, 16): every decode branch but brazil's unbounded relu(Z Z^T - I), whose modified_adj is refused when it holds more.
+--save_graph PATH (needs --binarize) writes the whole graph's recovered edges as an .npz of pairs, scores and hits in packed
+order with the threshold and the round count (engine.threshold_pairs).
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -76,6 +83,15 @@ def check_topk_args(args, fail):
         fail(f"--topk scores the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
 
 
+def check_binarize_args(args, fail):
+    """--binarize / --save_graph against the rest of the command line; fail(message) does not return."""
+    binarize, graph = getattr(args, "binarize", False), getattr(args, "save_graph", None)
+    if graph and not binarize:
+        fail("--save_graph needs --binarize")
+    if binarize and args.mode != "evaluate":
+        fail(f"--binarize splits the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
 def check_curves_args(args, fail):
     """--curves against the rest of the command line; fail(message) does not return."""
     if getattr(args, "curves", None) and args.mode != "evaluate":
@@ -92,6 +108,7 @@ class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
         check_topk_args(args, self.error)
+        check_binarize_args(args, self.error)
         check_curves_args(args, self.error)
         check_per_node_args(args, self.error)
         return args
@@ -139,6 +156,8 @@ def build_parser():
     p.add_argument('--save_edges', type=str, default=None)  # with --topk: the whole-graph edge list as an .npz
     p.add_argument('--curves', type=str, default=None)      # also write the ROC and precision-recall curves as an .npz
     p.add_argument('--per_node', type=str, default=None)    # also write each node's own ranking counts as an .npz
+    p.add_argument('--binarize', action='store_true')       # also split modified_adj into edges / no edges by 2-means
+    p.add_argument('--save_graph', type=str, default=None)  # with --binarize: the whole graph's recovered edges as an .npz
     return p
 
 
@@ -230,6 +249,26 @@ def save_edges(path, ori_adj, inference_adj, k):
         pairs, scores, hits = np.zeros((0, 2), np.int64), np.zeros(0, np.float32), np.zeros(0, bool)
     with open(path, "wb") as f:
         np.savez(f, pairs=pairs, scores=scores, hits=hits)
+
+
+def binarize_report(ori_adj, inference_adj, sets):
+    """--binarize: engine.two_means_split of each index set of `sets` (name -> node ids, None: every node) with the true graph
+    beside it for precision, recall and F1.  Returns {"split_<name>": dict}."""
+    real = ori_adj.to(inference_adj.device)
+    return {f"split_{name}": engine.two_means_split(inference_adj, ix, real) for name, ix in sets.items()}
+
+
+def save_graph(path, ori_adj, inference_adj, split):
+    """--save_graph: the high cluster of the whole graph's split, every pair at or above its threshold in packed order
+    (engine.threshold_pairs), as an .npz at exactly `path`; a degenerate split has no edges and a NaN threshold."""
+    if split["degenerate"]:
+        pairs, scores, hits, thr = np.zeros((0, 2), np.int64), np.zeros(0, np.float32), np.zeros(0, bool), float("nan")
+    else:
+        thr = split["threshold"]
+        pairs, scores, hits = (t.cpu().numpy() for t in
+                               engine.threshold_pairs(inference_adj, thr, None, ori_adj.to(inference_adj.device)))
+    with open(path, "wb") as f:
+        np.savez(f, pairs=pairs, scores=scores, hits=hits, threshold=np.float32(thr), iterations=np.int64(split["iterations"]))
 
 
 def curves_report(path, ori_adj, inference_adj, sets):
@@ -326,6 +365,7 @@ def _exit(message):
 
 def _run(args, rank, world):
     check_topk_args(args, _exit)
+    check_binarize_args(args, _exit)
     check_curves_args(args, _exit)
     check_per_node_args(args, _exit)
     device = torch.device(args.device)
@@ -443,6 +483,9 @@ def _run(args, rank, world):
     want_topk = getattr(args, "topk", None) is not None
     if want_topk:           # every rank computes (as the AUCs); the keys exist only with the flag
         res.update(topk_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, args.topk))
+    want_split = bool(getattr(args, "binarize", False))
+    if want_split:          # every rank computes; the keys exist only with the flag
+        res.update(binarize_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}))
     want_curves = bool(getattr(args, "curves", None))
     if want_curves:         # every rank computes; rank 0 writes the file
         res.update(curves_report(args.curves if rank == 0 else None, ad, inference_adj,
@@ -461,16 +504,22 @@ def _run(args, rank, world):
         print(f"current f1={res['topk_all']['f1']} (k={res['topk_all']['k']})")
         if getattr(args, "save_edges", None):
             save_edges(args.save_edges, ad, inference_adj, res["topk_all"]["k"])
+    if want_split:
+        d = res["split_all"]
+        print(f"current split_f1={d['f1']} (edges={d['edges']}, threshold={d['threshold']})")
+        if getattr(args, "save_graph", None):
+            save_graph(args.save_graph, ad, inference_adj, d)
     if want_curves:
         print(f"current best_f1={res['curves_all']['best_f1']} (threshold={res['curves_all']['best_threshold']})")
     if want_per_node:
         d = res["per_node_all"]
         print(f"current macro_auc={d['macro_auc']} mrr={d['mrr']} hits@1={d['hits_at_1']}")
     os.makedirs("./results/", exist_ok=True)
-    # the parameter line names --ap, --topk, --save_edges, --curves and --per_node only when they are set: without them the log is what
-    # it was before the flags existed
+    # the parameter line names --ap, --topk, --save_edges, --binarize, --save_graph, --curves and --per_node only when they are set:
+    # without them the log is what it was before the flags existed
     hidden = (set() if want_ap else {"ap"}) | (set() if want_topk else {"topk", "save_edges"}) | \
-        (set() if want_curves else {"curves"}) | (set() if want_per_node else {"per_node"})
+        (set() if want_curves else {"curves"}) | (set() if want_per_node else {"per_node"}) | \
+        (set() if want_split else {"binarize", "save_graph"})
     shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
     with open(os.path.join("./results", args.log_name), "a") as f:                         # main.py:314-323
         f.write(f"current parameter: {shown}\n")
@@ -483,6 +532,11 @@ def _run(args, rank, world):
             f.write("\t".join(f"In {name}: k={d['k']} P={d['precision']} R={d['recall']} F1={d['f1']}" for name, d in
                               (("attack graph", res["topk_attack"]), ("train graph", res["topk_train"]),
                                ("Whole Graph", res["topk_all"]))) + "\n")
+        if want_split:
+            for name, d in (("attack graph", res["split_attack"]), ("train graph", res["split_train"]),
+                            ("Whole Graph", res["split_all"])):
+                f.write(f"In {name}: split edges={d['edges']} threshold={d['threshold']} rounds={d['iterations']} "
+                        f"P={d['precision']} R={d['recall']} F1={d['f1']}\n")
         if want_curves:
             f.write("\t".join(f"In {name}: ROC points={d['roc_points']} PR points={d['pr_points']} levels={d['levels']} "
                               f"best F1={d['best_f1']} at {d['best_threshold']}" for name, d in
