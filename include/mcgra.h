@@ -367,6 +367,47 @@ int mcgra_threshold_pairs(void* stream, int n, const float* scores, int ld_score
                           uint8_t* hits  /* device [cap], may be NULL; needs labels */,
                           int64_t* counts /* host[3]: m, pairs with score >= threshold, hits among them (-1 without labels) */);
 
+/* How far an AUC of the recovered graph can be trusted, and whether two of them differ: the exact integers of DeLong's
+ * variance of the AUC and of DeLong's covariance of the AUCs of two scorings of the same pairs (DeLong, DeLong and
+ * Clarke-Pearson, Biometrics 44, 1988).
+ *   - candidates, selection and checks as mcgra_topk_metrics: idx, n_idx REPEAT-FREE device int64 node ids or NULL for all n
+ *     nodes; the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b with score scores[idx[a]][idx[b]] and label
+ *     labels[idx[a]][idx[b]]; nothing outside the selected strict lower triangle is looked at.  This is NOT the population of
+ *     mcgra_roc_auc / mcgra_rank_metrics, which range over the ordered entries with the diagonal: every pair appears there
+ *     twice, so a variance over it would be too small by about two.  The AUC that belongs to these integers is the AUC of the
+ *     unordered pairs, theta = T / (2 P N);
+ *   - scores compare as float32 values: -0.0 == +0.0, subnormals and negative scores are ordinary values, ties are float32
+ *     equality;
+ *   - placements, with P candidates of label 1 and N of label 0:
+ *       positive i:  a_i = 2 #{neg: s < s_i} + #{neg: s == s_i}   in [0, 2N]
+ *       negative j:  b_j = 2 #{pos: s > s_j} + #{pos: s == s_j}   in [0, 2P]
+ *     T = sum a_i = sum b_j (twice the Mann-Whitney U), A2 = sum a_i^2, B2 = sum b_j^2; for two score matrices A and B over
+ *     the same labels and selection also A_ab = sum a_i^A a_i^B and B_ab = sum b_j^A b_j^B.  m < 2^31, so every sum is below
+ *     2^95 and leaves as (low, high) 64-bit limbs, value = low + high 2^64;
+ *   - what the caller forms from them (exact rationals, one rounding each):
+ *       var   = (P A2 - T^2) / (4 N^2 P^2 (P - 1)) + (N B2 - T^2) / (4 P^2 N^2 (N - 1))
+ *       cov   = (P A_ab - T_a T_b) / (4 N^2 P^2 (P - 1)) + (N B_ab - T_a T_b) / (4 P^2 N^2 (N - 1))
+ *     P == 0 or N == 0: every sum is 0 and theta is undefined; P == 1 or N == 1: the variance is undefined;
+ *   - a selected score (of either matrix) that is NaN or +-inf, a selected label other than 0 or 1, a repeated or
+ *     out-of-range id: MCGRA_EINVAL;
+ *   - n_idx (n when idx is NULL) from 2 (MCGRA_EINVAL below) up to 65 535 (MCGRA_ENOSUP beyond); out NULL, a matrix NULL or an
+ *     ld below n: MCGRA_EINVAL.  These run before any HIP call.  After any refusal nothing has been written to out and
+ *     mcgra_last_error() names the cause;
+ *   - integer counts merged by integer atomics, no floating-point arithmetic on the device: the same bits on every call, and
+ *     the same integers under any permutation of idx.
+ * Synchronises `stream`.
+ * Only the candidates of label 1 are stored and sorted; those of label 0 are streamed from the matrices.
+ * Device scratch: nothing per candidate pair; 24 bytes per candidate of label 1 and score matrix (its key, the sorted copy, two
+ * 4-byte counts and their 8-byte running sum) + 4 for the sort's second buffer; about 3 MB; 4 bytes per node of the graph when
+ * idx is given. */
+int mcgra_auc_delong(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                     const int64_t* idx, int64_t n_idx,
+                     uint64_t* out /* host[8]: m, P, N, T, A2 lo, A2 hi, B2 lo, B2 hi */);
+int mcgra_auc_delong_paired(void* stream, int n, const float* labels, int ld_labels,
+                            const float* scores_a, int ld_a, const float* scores_b, int ld_b,
+                            const int64_t* idx, int64_t n_idx,
+                            uint64_t* out /* host[17]: m, P, N, T_a, T_b, then lo, hi of A2_a, B2_a, A2_b, B2_b, A_ab, B_ab */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score

@@ -1,0 +1,435 @@
+// How far the AUC of the recovered graph can be trusted: the integers of DeLong's variance of the AUC (mcgra_auc_delong) and
+// of DeLong's covariance of the AUCs of two scorings of the same pairs (mcgra_auc_delong_paired).  DeLong, DeLong and
+// Clarke-Pearson, "Comparing the areas under two or more correlated receiver operating characteristic curves", Biometrics 44
+// (1988).
+//
+// Candidates: those of mcgra_topk_metrics (topk.hip) -- the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b of a
+// repeat-free idx, score scores[idx[a]][idx[b]], label labels[idx[a]][idx[b]]; nothing outside the selected strict lower
+// triangle is looked at.  NOT the population of mcgra_roc_auc (auc.hip), which ranges over the ordered entries with the
+// diagonal: there each pair appears twice and a variance over it would be too small by about two.  The AUC these integers
+// give, T / (2 P N), is the AUC of the unordered pairs.
+// Scores compare as float32 values through the order-preserving key (rank_common.h): -0.0 == +0.0, subnormals and negative
+// scores are ordinary values, ties are float32 equality.
+// Placements, P positives and N negatives:
+//   positive i:  a_i = 2 #{neg: s < s_i} + #{neg: s == s_i}  in [0, 2N]
+//   negative j:  b_j = 2 #{pos: s > s_j} + #{pos: s == s_j}  in [0, 2P]
+//   T = sum a_i (= sum b_j = 2U),  A2 = sum a_i^2,  B2 = sum b_j^2,  and for two scorings A, B of the same pairs
+//   A_ab = sum a_i^A a_i^B,  B_ab = sum b_j^A b_j^B.
+// m < 2^31, so a placement fits 32 bits and a product of two 64; a sum of products is below 2^95.
+//
+// Only the POSITIVES are stored and sorted (a graph has few edges among its pairs); the negatives are streamed from the
+// matrices and never stored.  Passes:
+//   k_auc_index        idx only: range check, repeats (rank_common.h)
+//   k_dl_classify      one read of the selected lower triangle: the argument checks (both score matrices), per-block positive
+//                      counts
+//   k_dl_emit          a second read of the labels: each positive's key (paired: of both matrices) to its slot, at per-block
+//                      offsets (the host's scan of the counts).  Which slot of its block's range a positive takes depends on
+//                      the order the waves run in; every result below is a sum over slots, which no such order changes.  The
+//                      slot pairs the two scorings of a positive
+//   auc_sort           a sorted copy of each scoring's positive keys (the stable LSD radix sort of rank_common.h)
+//   k_dl_negatives     a third read: every negative x finds lb = #positives below x and ub = #positives at or below x in the
+//                      sorted positives -- first in DL_STAGE evenly spaced samples of them staged in LDS, then inside the one
+//                      stretch between two samples -- and that is its placement, b = 2 P - lb - ub, for both scorings at once:
+//                      sum b, the halves of b^2 and of b^A b^B.  It also counts itself into hist[lb] and, when it ties a
+//                      positive, into ties[lb] (32-bit integer atomics; the lanes of a wave that share a bin add once)
+//   k_auc_digit_scan   the running sum of hist
+//   k_dl_positives     every positive slot: l = the first sorted position of its own key; the negatives at or below it are
+//                      cum = hist[0] + ... + hist[l], those equal to it ties[l], so a = 2 cum - ties[l]; sum a, the halves of
+//                      a^2 and of a^A a^B
+// Each product is added as its low and its high 32-bit half into two 64-bit sums, each below 2^31 2^32 = 2^63; they are
+// combined on the host side of the entry (unsigned 128-bit) and leave as (low, high) 64-bit limbs.
+// There is no floating-point arithmetic on the device; everything is integer counts merged by integer atomics, so every call
+// returns the same bits.
+// Device scratch: 24 bytes per POSITIVE and scoring (its key by slot, the sorted copy, hist, ties and the 8-byte running sum)
+// plus 4 for the sort's second buffer, about 3 MB for the sort's counts, and 4 bytes per node of the graph when idx is given:
+// nothing per candidate.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/mcgra.h"
+#include "common.h"
+#include "rank_common.h"
+
+namespace mcgra {
+namespace {
+constexpr int DL_ROW_BLOCKS = 1024;        // blocks of the three passes over the matrix (grid-stride over selected rows)
+constexpr int DL_POS_BLOCKS = 2048;        // at most this many blocks of the pass over the positives (grid-stride)
+constexpr int DL_STAGE = 4096;             // samples of the sorted positives a block of k_dl_negatives keeps in LDS, per scoring
+enum { DL_BAD_SCORE_B = 32 };              // beside the AUC_BAD_* flags: the second score matrix
+
+// slots of the accumulators, per class
+enum { DL_T_A = 0, DL_T_B, DL_SQ_A_LO, DL_SQ_A_HI, DL_SQ_B_LO, DL_SQ_B_HI, DL_X_LO, DL_X_HI, DL_ACC };
+
+// what one scoring's positives need on the device
+struct DlSide {
+  const float* S;        // the score matrix (NULL: no second scoring)
+  int64_t ld;
+  uint32_t* slot;        // [P] the positives' keys by slot
+  uint32_t* sorted;      // [P] ascending
+  uint32_t* hist;        // [P + 1] negatives whose lb is this position
+  uint32_t* ties;        // [P + 1] of those, the ones equal to the positive at this position
+  uint64_t* cum;         // [P + 1] hist[0] + ... + hist[l - 1]
+};
+
+// rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection; f(score_a, score_b, label) for every pair (a, b), b < a
+template <class F>
+__device__ __forceinline__ void dl_for_each(int rows, const float* __restrict__ SA, int64_t lda, const float* __restrict__ SB,
+                                            int64_t ldb, const float* __restrict__ L, int64_t ldl,
+                                            const int64_t* __restrict__ idx, F&& f) {
+  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
+    const int64_t u = idx ? idx[a] : a;
+    const float* arow = SA + u * lda;
+    const float* brow = SB ? SB + u * ldb : nullptr;
+    const float* lrow = L + u * ldl;
+    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
+      const int64_t v = idx ? idx[b] : b;
+      f(arow[v], brow ? brow[v] : 0.f, lrow[v]);
+    }
+  }
+}
+
+// counts[b] = positives of block b's rows; flags |= the argument errors it meets
+__global__ __launch_bounds__(AUC_THREADS) void k_dl_classify(int rows, const float* __restrict__ SA, int64_t lda,
+                                                             const float* __restrict__ SB, int64_t ldb,
+                                                             const float* __restrict__ L, int64_t ldl,
+                                                             const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
+                                                             int* __restrict__ flags) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  uint32_t pos = 0;
+  int f = 0;
+  dl_for_each(rows, SA, lda, SB, ldb, L, ldl, idx, [&](float sa, float sb, float l) {
+    if (!auc_finite(sa)) f |= AUC_BAD_SCORE;
+    if (!auc_finite(sb)) f |= DL_BAD_SCORE_B;
+    if (auc_pos(l)) ++pos;
+    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+  });
+  if (f) atomicOr(flags, f);
+  const uint64_t p = block_sum_u64(pos, sh);
+  if (threadIdx.x == 0) counts[blockIdx.x] = p;
+}
+
+// block b's positives take the slots offs[b] .. (any order inside a block): ka[slot] = key of the pair's score in SA, kb[slot]
+// (SB != NULL) = key of its score in SB
+__global__ __launch_bounds__(AUC_THREADS) void k_dl_emit(int rows, const float* __restrict__ SA, int64_t lda,
+                                                         const float* __restrict__ SB, int64_t ldb,
+                                                         const float* __restrict__ L, int64_t ldl,
+                                                         const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
+                                                         uint32_t* __restrict__ ka, uint32_t* __restrict__ kb) {
+  __shared__ uint32_t cur;
+  if (threadIdx.x == 0) cur = 0;
+  __syncthreads();
+  const uint64_t o_pos = offs[blockIdx.x];
+  const int lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
+    const int64_t u = idx ? idx[a] : a;
+    const float* lrow = L + u * ldl;
+    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
+      const int64_t v = idx ? idx[b] : b;
+      const bool p = auc_pos(lrow[v]);
+      const uint64_t mp = __ballot(p);
+      if (mp == 0) continue;                              // the same in every active lane
+      const int leader = __ffsll((unsigned long long)mp) - 1;
+      uint32_t bp = 0;
+      if (lane == leader) bp = atomicAdd(&cur, (uint32_t)__popcll(mp));
+      bp = __shfl(bp, leader, 64);
+      if (p) {
+        const uint64_t at = o_pos + bp + __popcll(mp & below);
+        ka[at] = auc_key(SA[u * lda + v]);
+        if (SB) kb[at] = auc_key(SB[u * ldb + v]);
+      }
+    }
+  }
+}
+
+// first index in [lo, hi) of the ascending keys B whose key is >= x (UPPER: > x); hi when there is none
+template <bool UPPER, class Keys, class I>
+__device__ __forceinline__ I dl_bound(const Keys& B, I lo, I hi, uint32_t x) {
+  while (lo < hi) {
+    const I mid = lo + ((hi - lo) >> 1);
+    const uint32_t k = B[mid];
+    if (UPPER ? k <= x : k < x) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// dl_bound over all np sorted positives S through the ns samples smp[q] = S[q stride]: the bound among the samples leaves one
+// stretch between two samples.  c = first sample >= x (> x): every position up to (c - 1) stride is below (at or below) x and
+// position c stride is not, so the bound lies in ((c - 1) stride, c stride]; past the last sample it lies before np.
+template <bool UPPER>
+__device__ __forceinline__ uint32_t dl_find(const uint32_t* __restrict__ S, uint32_t np, const uint32_t* smp, uint32_t ns,
+                                            uint32_t stride, uint32_t x) {
+  const uint32_t c = dl_bound<UPPER>(smp, 0u, ns, x);
+  if (c == 0) return 0;
+  const uint32_t lo = (c - 1) * stride + 1, hi = c < ns ? c * stride : np;
+  return dl_bound<UPPER>(S, lo, hi, x);
+}
+
+// h[bin] += 1 for every lane with `on`.  The lanes of the wave that share one of its first DL_SHARED_BINS distinct bins add
+// once (tied scores and scores outside the positives' range put a whole wave into a few bins: one address would serialise 64
+// atomics); lanes left after that hold scattered bins and add on their own.  Every lane that is active in the caller must
+// call it (the loop is the same in all of them).
+constexpr int DL_SHARED_BINS = 4;
+__device__ __forceinline__ void dl_hist_add(uint32_t* __restrict__ h, uint32_t bin, bool on) {
+  const int lane = threadIdx.x & 63;
+  uint64_t todo = __ballot(on);
+  for (int it = 0; it < DL_SHARED_BINS && todo; ++it) {
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t lb = __shfl(bin, leader, 64);
+    const uint64_t same = __ballot(on && bin == lb);
+    if (lane == leader) atomicAdd(&h[lb], (uint32_t)__popcll(same));
+    todo &= ~same;
+  }
+  if ((todo >> lane) & 1ull) atomicAdd(&h[bin], 1u);
+}
+
+// one scoring's share of a negative: lb, ub among the sorted positives, the two counts, the placement 2 np - lb - ub
+__device__ __forceinline__ uint32_t dl_negative(const DlSide& s, uint32_t np, const uint32_t* smp, uint32_t ns, uint32_t stride,
+                                                float score, bool neg) {
+  uint32_t lb = 0, ub = 0;
+  bool tie = false;
+  if (neg) {
+    const uint32_t x = auc_key(score);
+    lb = dl_find<false>(s.sorted, np, smp, ns, stride, x);
+    tie = lb < np && s.sorted[lb] == x;
+    ub = tie ? dl_find<true>(s.sorted, np, smp, ns, stride, x) : lb;
+  }
+  dl_hist_add(s.hist, lb, neg);
+  dl_hist_add(s.ties, lb, tie);
+  return 2u * np - lb - ub;          // <= 2 np < 2^32
+}
+
+// The negatives, streamed: acc[DL_T_A / _B] += b, acc[DL_SQ_*] += the halves of b^2, acc[DL_X_*] += the halves of b^A b^B
+// (sb.S != NULL), and the counts hist / ties of each scoring.
+__global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide sa, DlSide sb, const float* __restrict__ L,
+                                                              int64_t ldl, const int64_t* __restrict__ idx, uint32_t np,
+                                                              unsigned long long* __restrict__ acc) {
+  __shared__ uint32_t smp_a[DL_STAGE], smp_b[DL_STAGE];
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  const bool paired = sb.S != nullptr;
+  const uint32_t stride = (np + DL_STAGE - 1) / DL_STAGE, ns = (np + stride - 1) / stride;
+  for (uint32_t q = threadIdx.x; q < ns; q += AUC_THREADS) {
+    smp_a[q] = sa.sorted[(uint64_t)q * stride];
+    if (paired) smp_b[q] = sb.sorted[(uint64_t)q * stride];
+  }
+  __syncthreads();
+  uint64_t part[DL_ACC] = {};
+  dl_for_each(rows, sa.S, sa.ld, sb.S, sb.ld, L, ldl, idx, [&](float xa, float xb, float l) {
+    const bool neg = !auc_pos(l);                              // the labels were checked: 0 or 1
+    const uint64_t ba = dl_negative(sa, np, smp_a, ns, stride, xa, neg);
+    const uint64_t bb = paired ? dl_negative(sb, np, smp_b, ns, stride, xb, neg) : 0;
+    if (neg) {
+      const uint64_t qa = ba * ba, qb = bb * bb, qx = ba * bb;
+      part[DL_T_A] += ba;
+      part[DL_T_B] += bb;
+      part[DL_SQ_A_LO] += qa & 0xffffffffull;
+      part[DL_SQ_A_HI] += qa >> 32;
+      part[DL_SQ_B_LO] += qb & 0xffffffffull;
+      part[DL_SQ_B_HI] += qb >> 32;
+      part[DL_X_LO] += qx & 0xffffffffull;
+      part[DL_X_HI] += qx >> 32;
+    }
+  });
+#pragma unroll
+  for (int q = 0; q < DL_ACC; ++q) {
+    __syncthreads();
+    const uint64_t tot = block_sum_u64(part[q], sh);
+    if (threadIdx.x == 0 && tot) atomicAdd(&acc[q], (unsigned long long)tot);
+  }
+}
+
+// one scoring's share of the positive at `slot`: a = 2 (negatives at or below it) - (negatives equal to it)
+__device__ __forceinline__ uint64_t dl_positive(const DlSide& s, uint32_t np, uint64_t slot) {
+  const uint32_t l = dl_bound<false>(s.sorted, 0u, np, s.slot[slot]);      // its own key is there: l < np
+  return 2 * (s.cum[l] + s.hist[l]) - s.ties[l];                          // <= 2 N < 2^32
+}
+
+// The positives, by slot: acc[DL_T_A / _B] += a, acc[DL_SQ_*] += the halves of a^2, acc[DL_X_*] += the halves of a^A a^B
+__global__ __launch_bounds__(AUC_THREADS) void k_dl_positives(DlSide sa, DlSide sb, uint32_t np,
+                                                              unsigned long long* __restrict__ acc) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  const bool paired = sb.S != nullptr;
+  uint64_t part[DL_ACC] = {};
+  for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < np; i += (uint64_t)gridDim.x * AUC_THREADS) {
+    const uint64_t aa = dl_positive(sa, np, i), ab = paired ? dl_positive(sb, np, i) : 0;
+    const uint64_t qa = aa * aa, qb = ab * ab, qx = aa * ab;
+    part[DL_T_A] += aa;
+    part[DL_T_B] += ab;
+    part[DL_SQ_A_LO] += qa & 0xffffffffull;
+    part[DL_SQ_A_HI] += qa >> 32;
+    part[DL_SQ_B_LO] += qb & 0xffffffffull;
+    part[DL_SQ_B_HI] += qb >> 32;
+    part[DL_X_LO] += qx & 0xffffffffull;
+    part[DL_X_HI] += qx >> 32;
+  }
+#pragma unroll
+  for (int q = 0; q < DL_ACC; ++q) {
+    __syncthreads();
+    const uint64_t tot = block_sum_u64(part[q], sh);
+    if (threadIdx.x == 0 && tot) atomicAdd(&acc[q], (unsigned long long)tot);
+  }
+}
+
+// the argument checks that need no device
+int dl_check(const char* who, int n, const float* labels, int ld_labels, const float* sa, int ld_a, const float* sb, int ld_b,
+             bool paired, const int64_t* idx, int64_t& n_idx, const uint64_t* out) {
+  if (!idx) n_idx = n;
+  if (n < 1 || !labels || !sa || (paired && !sb) || !out || ld_labels < n || ld_a < n || (paired && ld_b < n) || n_idx < 2) {
+    set_error("%s: bad argument (n >= 1, the matrices and out not NULL, every ld >= n, at least 2 selected nodes)", who);
+    return MCGRA_EINVAL;
+  }
+  if (n_idx > AUC_MAX_NIDX) {
+    set_error("%s: %lld selected nodes; a pair count of more than %lld nodes does not fit 31 bits", who, (long long)n_idx,
+              (long long)AUC_MAX_NIDX);
+    return MCGRA_ENOSUP;
+  }
+  return 0;
+}
+
+// (low, high) limbs of lo + hi 2^32
+void dl_limbs(uint64_t lo, uint64_t hi, uint64_t* out) {
+  typedef unsigned __int128 u128;
+  const u128 x = (u128)lo + ((u128)hi << 32);
+  out[0] = (uint64_t)x;
+  out[1] = (uint64_t)(x >> 64);
+}
+
+// Both entries: m, P, N, then per scoring T, A2 (2 limbs), B2 (2 limbs), then (paired) A_ab, B_ab (2 limbs each).
+struct DlResult {
+  uint64_t m = 0, P = 0, N = 0;
+  uint64_t T[2] = {0, 0}, A2[2][2] = {}, B2[2][2] = {}, Aab[2] = {0, 0}, Bab[2] = {0, 0};
+};
+
+int dl_run(const char* who, hipStream_t st, int n, const float* L, int ldl, const float* SA, int lda, const float* SB, int ldb,
+           const int64_t* idx, int rows, DlResult& r) {
+  AucBufs b;
+  const bool paired = SB != nullptr;
+  const int sides = paired ? 2 : 1;
+  const int g = std::min(rows - 1, DL_ROW_BLOCKS);
+  // one allocation: flags, the two classes' accumulators, the per-block counts
+  struct Head { unsigned long long acc[2][DL_ACC]; int flags; };
+  uint8_t* head = b.get<uint8_t>(sizeof(Head) + sizeof(uint64_t) * (size_t)g);
+  if (!head) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
+  Head* hd = (Head*)head;
+  uint64_t* counts = (uint64_t*)(head + sizeof(Head));
+  static_assert(sizeof(Head) % 8 == 0, "counts is 8-byte aligned");
+  MCGRA_HIP(hipMemsetAsync(hd, 0, sizeof(Head), st));
+  int h_flags = 0;
+  if (idx) {
+    uint32_t* seen = b.get<uint32_t>(n);
+    if (!seen) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
+    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
+    const int gi = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
+    k_auc_index<<<gi, AUC_THREADS, 0, st>>>(n, rows, idx, seen, &hd->flags);
+    MCGRA_KERNEL_CHECK();
+    MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipStreamSynchronize(st));
+    if (h_flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
+    if (h_flags & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
+  }
+  k_dl_classify<<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, &hd->flags);
+  MCGRA_KERNEL_CHECK();
+  std::vector<uint64_t> h(g);
+  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));
+  if (h_flags & (AUC_BAD_SCORE | DL_BAD_SCORE_B | AUC_BAD_LABEL)) {
+    set_error("%s: %s%s%s", who,
+              (h_flags & AUC_BAD_SCORE) ? (paired ? "a selected score of scores_a is NaN or infinite " : "a selected score is NaN or infinite ") : "",
+              (h_flags & DL_BAD_SCORE_B) ? "a selected score of scores_b is NaN or infinite " : "",
+              (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
+    return MCGRA_EINVAL;
+  }
+  uint64_t P = 0;
+  for (int i = 0; i < g; ++i) { const uint64_t p = h[i]; h[i] = P; P += p; }        // counts -> offsets
+  r.m = (uint64_t)rows * (rows - 1) / 2;
+  r.P = P;
+  r.N = r.m - P;
+  if (P == 0 || r.N == 0) return 0;                    // every placement is 0
+  // one allocation for what scales with P: per scoring slot [P4], sorted [P4], hist [P4 + 4], ties [P4 + 4], cum [P4 + 4];
+  // then the sort's second buffer [P4] and its counts.  P4 = P rounded up to 4 keys: every array starts on 16 bytes.
+  const size_t P4 = (P + 3) / 4 * 4, H4 = P4 + 4;
+  const size_t per_side = sizeof(uint32_t) * (2 * P4 + 2 * H4) + sizeof(uint64_t) * H4;
+  const size_t sort_cnt = 256 * (size_t)AUC_SORT_BLOCKS;
+  const size_t bytes = sides * per_side + sizeof(uint32_t) * P4 + sizeof(uint64_t) * sort_cnt + sizeof(uint32_t) * sort_cnt;
+  uint8_t* pool = b.get<uint8_t>(bytes);
+  if (!pool) { set_error("%s: hipMalloc of the scratch of %llu positives failed", who, (unsigned long long)P); return MCGRA_ENOMEM; }
+  DlSide side[2] = {};
+  uint8_t* at = pool;
+  for (int s = 0; s < sides; ++s) {
+    side[s].S = s ? SB : SA;
+    side[s].ld = s ? ldb : lda;
+    side[s].cum = (uint64_t*)at;      at += sizeof(uint64_t) * H4;
+    side[s].slot = (uint32_t*)at;     at += sizeof(uint32_t) * P4;
+    side[s].sorted = (uint32_t*)at;   at += sizeof(uint32_t) * P4;
+    side[s].hist = (uint32_t*)at;     at += sizeof(uint32_t) * H4;
+    side[s].ties = (uint32_t*)at;     at += sizeof(uint32_t) * H4;
+  }
+  uint64_t* off = (uint64_t*)at;      at += sizeof(uint64_t) * sort_cnt;
+  uint32_t* cnt = (uint32_t*)at;      at += sizeof(uint32_t) * sort_cnt;
+  uint32_t* tmp = (uint32_t*)at;
+  MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
+  k_dl_emit<<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, side[0].slot, side[1].slot);
+  MCGRA_KERNEL_CHECK();
+  for (int s = 0; s < sides; ++s) {
+    MCGRA_HIP(hipMemcpyAsync(side[s].sorted, side[s].slot, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, st));
+    if (int rc = auc_sort(st, side[s].sorted, tmp, P, cnt, off)) return rc;
+    MCGRA_HIP(hipMemsetAsync(side[s].hist, 0, sizeof(uint32_t) * 2 * H4, st));          // hist and ties are adjacent
+  }
+  k_dl_negatives<<<g, AUC_THREADS, 0, st>>>(rows, side[0], side[1], L, ldl, idx, (uint32_t)P, hd->acc[1]);
+  MCGRA_KERNEL_CHECK();
+  for (int s = 0; s < sides; ++s) k_auc_digit_scan<<<1, 1024, 0, st>>>(side[s].hist, (int)P, side[s].cum);
+  const int gp = (int)std::min<uint64_t>(DL_POS_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
+  k_dl_positives<<<gp, AUC_THREADS, 0, st>>>(side[0], side[1], (uint32_t)P, hd->acc[0]);
+  MCGRA_KERNEL_CHECK();
+  unsigned long long ha[2][DL_ACC];
+  MCGRA_HIP(hipMemcpyAsync(ha, hd->acc, sizeof(ha), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));                  // also: the scratch is freed on return
+  const unsigned long long *ap = ha[0], *an = ha[1];
+  if (ap[DL_T_A] != an[DL_T_A] || ap[DL_T_B] != an[DL_T_B]) {             // sum a_i == sum b_j == 2U by construction
+    set_error("%s: internal error: the two placement sums differ (%llu, %llu; %llu, %llu)", who, ap[DL_T_A], an[DL_T_A],
+              ap[DL_T_B], an[DL_T_B]);
+    return MCGRA_EHIP;
+  }
+  r.T[0] = ap[DL_T_A];
+  r.T[1] = ap[DL_T_B];
+  dl_limbs(ap[DL_SQ_A_LO], ap[DL_SQ_A_HI], r.A2[0]);
+  dl_limbs(an[DL_SQ_A_LO], an[DL_SQ_A_HI], r.B2[0]);
+  dl_limbs(ap[DL_SQ_B_LO], ap[DL_SQ_B_HI], r.A2[1]);
+  dl_limbs(an[DL_SQ_B_LO], an[DL_SQ_B_HI], r.B2[1]);
+  dl_limbs(ap[DL_X_LO], ap[DL_X_HI], r.Aab);
+  dl_limbs(an[DL_X_LO], an[DL_X_HI], r.Bab);
+  return 0;
+}
+}  // namespace
+}  // namespace mcgra
+
+using namespace mcgra;
+
+extern "C" int mcgra_auc_delong(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                                const int64_t* idx, int64_t n_idx, uint64_t* out) {
+  if (int rc = dl_check("auc_delong", n, labels, ld_labels, scores, ld_scores, nullptr, 0, false, idx, n_idx, out)) return rc;
+  DlResult r;
+  if (int rc = dl_run("auc_delong", (hipStream_t)stream, n, labels, ld_labels, scores, ld_scores, nullptr, 0, idx, (int)n_idx, r))
+    return rc;
+  const uint64_t res[8] = {r.m, r.P, r.N, r.T[0], r.A2[0][0], r.A2[0][1], r.B2[0][0], r.B2[0][1]};
+  memcpy(out, res, sizeof(res));
+  return 0;
+}
+
+extern "C" int mcgra_auc_delong_paired(void* stream, int n, const float* labels, int ld_labels, const float* scores_a, int ld_a,
+                                       const float* scores_b, int ld_b, const int64_t* idx, int64_t n_idx, uint64_t* out) {
+  if (int rc = dl_check("auc_delong_paired", n, labels, ld_labels, scores_a, ld_a, scores_b, ld_b, true, idx, n_idx, out)) return rc;
+  DlResult r;
+  if (int rc = dl_run("auc_delong_paired", (hipStream_t)stream, n, labels, ld_labels, scores_a, ld_a, scores_b, ld_b, idx,
+                      (int)n_idx, r))
+    return rc;
+  const uint64_t res[17] = {r.m, r.P, r.N, r.T[0], r.T[1], r.A2[0][0], r.A2[0][1], r.B2[0][0], r.B2[0][1],
+                            r.A2[1][0], r.A2[1][1], r.B2[1][0], r.B2[1][1], r.Aab[0], r.Aab[1], r.Bab[0], r.Bab[1]};
+  memcpy(out, res, sizeof(res));
+  return 0;
+}

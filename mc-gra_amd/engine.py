@@ -4,6 +4,9 @@ PyTorch is used only as plumbing: it owns the caller-side device buffers and
 the HIP stream.  All arithmetic happens in libmcgra_hip.so.
 """
 import ctypes as C
+import math
+import statistics
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -482,6 +485,128 @@ def threshold_pairs(pred, threshold, idx=None, real=None):
         check(lib.mcgra_threshold_pairs(_stream(), n, _p(pred), pred.stride(0), _p(real), ldl, _p(ix), rows, float(threshold), k,
                                         _p(pairs), _p(scores), _p(hits), counts))
     return pairs, scores, None if hits is None else hits.view(torch.bool)
+
+
+def _limbs(lo, hi):
+    return int(lo) + (int(hi) << 64)
+
+
+def _norm_quantile(level):
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"auc_delong: level = {level!r}; a confidence level lies strictly between 0 and 1")
+    return statistics.NormalDist().inv_cdf((1.0 + level) / 2.0)
+
+
+def _delong_parts(P, N, T_a, T_b, A, B):
+    """(P A - T_a T_b) / (4 N^2 P^2 (P - 1)) + (N B - T_a T_b) / (4 P^2 N^2 (N - 1)) as one exact rational: DeLong's variance
+    (T_a = T_b = T, A = A2, B = B2) or covariance (A = A_ab, B = B_ab).  Needs P, N >= 2."""
+    return (Fraction(P * A - T_a * T_b, 4 * N * N * P * P * (P - 1)) + Fraction(N * B - T_a * T_b, 4 * P * P * N * N * (N - 1)))
+
+
+def delong_stats(ints, level=0.95):
+    """The dict of auc_delong from its integers {"pairs", "positives", "negatives", "T", "A2", "B2"} (Python ints): exact
+    rationals, each rounded to a double once.  No device is involved."""
+    nan = float("nan")
+    zq = _norm_quantile(level)
+    m, P, N, T, A2, B2 = (int(ints[k]) for k in ("pairs", "positives", "negatives", "T", "A2", "B2"))
+    res = {"pairs": m, "positives": P, "negatives": N, "auc": nan, "var": nan, "se": nan, "ci_low": nan, "ci_high": nan,
+           "level": float(level), "ints": dict(ints)}
+    if P == 0 or N == 0:
+        return res
+    res["auc"] = float(Fraction(T, 2 * P * N))
+    if P == 1 or N == 1:
+        return res
+    res["var"] = float(_delong_parts(P, N, T, T, A2, B2))
+    res["se"] = math.sqrt(res["var"])
+    res["ci_low"] = max(0.0, res["auc"] - zq * res["se"])
+    res["ci_high"] = min(1.0, res["auc"] + zq * res["se"])
+    return res
+
+
+def delong_paired_stats(ints, level=0.95):
+    """The dict of auc_delong_paired from its integers {"pairs", "positives", "negatives", "T_a", "T_b", "A2_a", "B2_a", "A2_b",
+    "B2_b", "A_ab", "B_ab"}.  var_delta = var_a + var_b - 2 cov is formed as ONE rational before it is rounded, so the
+    cancellation between two nearly equal scorings is exact."""
+    nan = float("nan")
+    zq = _norm_quantile(level)
+    g = {k: int(v) for k, v in ints.items()}
+    m, P, N = g["pairs"], g["positives"], g["negatives"]
+    res = {"a": delong_stats({"pairs": m, "positives": P, "negatives": N, "T": g["T_a"], "A2": g["A2_a"], "B2": g["B2_a"]}, level),
+           "b": delong_stats({"pairs": m, "positives": P, "negatives": N, "T": g["T_b"], "A2": g["A2_b"], "B2": g["B2_b"]}, level),
+           "cov": nan, "delta": nan, "se_delta": nan, "ci_low": nan, "ci_high": nan, "z": nan, "p_value": nan,
+           "level": float(level), "ints": dict(g)}
+    if P == 0 or N == 0:
+        return res
+    delta = Fraction(g["T_a"] - g["T_b"], 2 * P * N)
+    res["delta"] = float(delta)
+    if P == 1 or N == 1:
+        return res
+    var_a = _delong_parts(P, N, g["T_a"], g["T_a"], g["A2_a"], g["B2_a"])
+    var_b = _delong_parts(P, N, g["T_b"], g["T_b"], g["A2_b"], g["B2_b"])
+    cov = _delong_parts(P, N, g["T_a"], g["T_b"], g["A_ab"], g["B_ab"])
+    var_d = var_a + var_b - 2 * cov
+    res["cov"] = float(cov)
+    res["se_delta"] = math.sqrt(float(var_d))
+    res["ci_low"] = max(-1.0, res["delta"] - zq * res["se_delta"])
+    res["ci_high"] = min(1.0, res["delta"] + zq * res["se_delta"])
+    if var_d == 0:
+        res["z"] = 0.0 if delta == 0 else math.copysign(float("inf"), delta)
+    else:
+        res["z"] = res["delta"] / res["se_delta"]
+    res["p_value"] = math.erfc(abs(res["z"]) / math.sqrt(2.0))
+    return res
+
+
+@_on_operand_device
+def auc_delong(real, pred, idx=None, level=0.95):
+    """How far the AUC of the recovered graph can be trusted (mcgra_auc_delong): DeLong's variance of the AUC (DeLong, DeLong
+    and Clarke-Pearson, Biometrics 44, 1988) over the candidates of topk_metrics -- the m unordered pairs of positions a > b of
+    a REPEAT-FREE idx (None: all nodes), score pred[idx[a], idx[b]], label real[idx[a], idx[b]], float32 comparison with ties
+    counted 1/2.  NOT the population of roc_auc, which counts every pair twice and the diagonal; "auc" here is the AUC of the
+    unordered pairs.  Returns {"pairs" (m), "positives" (P), "negatives" (N), "auc" T / (2 P N), "var", "se" sqrt(var),
+    "ci_low", "ci_high" (auc -+ z se clipped to [0, 1], z the normal quantile of (1 + level) / 2), "level", "ints" (the exact
+    integers T, A2, B2 of the header)}: integer counts from the device, exact rationals on the host, one rounding each, the same
+    bits on every call.  P or N == 0: everything NaN; P or N == 1: the AUC alone; var == 0: the interval is [auc, auc].
+    Caveat: two pairs that share a node are not independent samples, so the interval is a lower bound on the real uncertainty.
+    McgraError for a repeated or out-of-range id, a selected NaN / inf score or a selected label other than 0 / 1."""
+    _norm_quantile(level)
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
+    out = (C.c_uint64 * 8)()
+    check(lib.mcgra_auc_delong(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
+                               ix.numel() if ix is not None else n, out))
+    m, P, N, T = (int(v) for v in out[:4])
+    return delong_stats({"pairs": m, "positives": P, "negatives": N, "T": T, "A2": _limbs(out[4], out[5]),
+                         "B2": _limbs(out[6], out[7])}, level)
+
+
+@_on_operand_device
+def auc_delong_paired(real, pred_a, pred_b, idx=None, level=0.95):
+    """Whether two scorings of the same pairs differ (mcgra_auc_delong_paired): DeLong's test for two correlated AUCs (DeLong
+    et al. 1988) over the candidates of auc_delong.  Returns {"a", "b" (each the dict of auc_delong for that scoring), "cov"
+    (DeLong's covariance of the two AUCs), "delta" auc_a - auc_b, "se_delta" sqrt(var_a + var_b - 2 cov), "ci_low", "ci_high"
+    (delta -+ z se_delta clipped to [-1, 1]), "z" delta / se_delta, "p_value" erfc(|z| / sqrt 2) (two-sided), "level", "ints"}.
+    var_delta == 0: z = 0, p = 1 when delta == 0, else z = +-inf, p = 0.  P or N == 0: everything NaN; P or N == 1: the AUCs
+    and delta alone.  The caveat of auc_delong holds: pairs that share a node are not independent, so se_delta is a
+    lower bound on the real one and the p-value is optimistic.  Refusals as auc_delong, for either matrix."""
+    _norm_quantile(level)
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred_a.shape) == (n, n) and tuple(pred_b.shape) == (n, n), \
+        (real.shape, pred_a.shape, pred_b.shape)
+    real, pred_a, pred_b = _rows_f32(real, dev), _rows_f32(pred_a, dev), _rows_f32(pred_b, dev)
+    ix = _node_ids(idx, dev)
+    out = (C.c_uint64 * 17)()
+    check(lib.mcgra_auc_delong_paired(_stream(), n, _p(real), real.stride(0), _p(pred_a), pred_a.stride(0), _p(pred_b),
+                                      pred_b.stride(0), _p(ix), ix.numel() if ix is not None else n, out))
+    ints = {"pairs": int(out[0]), "positives": int(out[1]), "negatives": int(out[2]), "T_a": int(out[3]), "T_b": int(out[4])}
+    for i, k in enumerate(("A2_a", "B2_a", "A2_b", "B2_b", "A_ab", "B_ab")):
+        ints[k] = _limbs(out[5 + 2 * i], out[6 + 2 * i])
+    return delong_paired_stats(ints, level)
 
 
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the

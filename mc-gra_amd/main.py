@@ -33,6 +33,14 @@ upper cluster is the recovered edge set, and its precision, recall and F1 agains
 must lie in [0, 16): every decode branch but brazil's unbounded relu(Z Z^T - I), whose modified_adj is refused when it holds more.
 --save_graph PATH (needs --binarize) writes the whole graph's recovered edges as an .npz of pairs, scores and hits in packed
 order with the threshold and the round count (engine.threshold_pairs).
+--ci (not in the reference; --mode evaluate only; absent by default, and then nothing changes) says how far the attack's AUC
+can be trusted: DeLong's standard error and 95 % confidence interval of the AUC of the unordered node pairs of each index set
+(engine.auc_delong; integer counts on the GPU, exact rationals on the host).  Pairs that share a node are not independent, so
+the interval is a lower bound on the real uncertainty.
+--versus features|PATH (needs --ci) asks whether the attack beats another scoring of the same pairs: DeLong's paired test
+(engine.auc_delong_paired) of modified_adj against the run's own feature_adj -- the prior the attacker already holds -- or
+against an n x n float32 matrix stored as an .npy at PATH; delta, z and the two-sided p-value of each index set are reported.
+--save_scores PATH (--mode evaluate only) writes modified_adj as that .npy, so that one run can be compared with another.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -104,6 +112,21 @@ def check_per_node_args(args, fail):
         fail(f"--per_node ranks each node's row of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
 
 
+def check_ci_args(args, fail):
+    """--ci / --versus / --save_scores against the rest of the command line; fail(message) does not return."""
+    ci, versus, scores = getattr(args, "ci", False), getattr(args, "versus", None), getattr(args, "save_scores", None)
+    if versus is not None and not ci:
+        fail("--versus needs --ci")
+    if versus is not None and versus == "":
+        fail("--versus takes `features` or the path of an .npy score matrix")
+    if ci and args.mode != "evaluate":
+        fail(f"--ci puts an interval on the AUC of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+    if scores is not None and args.mode != "evaluate":
+        fail(f"--save_scores writes the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+    if scores is not None and scores == "":
+        fail("--save_scores takes the path of the .npy to write")
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
@@ -111,6 +134,7 @@ class _Parser(argparse.ArgumentParser):
         check_binarize_args(args, self.error)
         check_curves_args(args, self.error)
         check_per_node_args(args, self.error)
+        check_ci_args(args, self.error)
         return args
 
 
@@ -158,6 +182,10 @@ def build_parser():
     p.add_argument('--per_node', type=str, default=None)    # also write each node's own ranking counts as an .npz
     p.add_argument('--binarize', action='store_true')       # also split modified_adj into edges / no edges by 2-means
     p.add_argument('--save_graph', type=str, default=None)  # with --binarize: the whole graph's recovered edges as an .npz
+    # absent from the namespace unless given: without them the parameter line of the log is what it was
+    p.add_argument('--ci', action='store_true', default=argparse.SUPPRESS)      # also DeLong's se and interval of the AUC
+    p.add_argument('--versus', type=str, default=argparse.SUPPRESS)            # with --ci: paired test against `features` or an .npy
+    p.add_argument('--save_scores', type=str, default=argparse.SUPPRESS)       # write modified_adj as an .npy for a later --versus
     return p
 
 
@@ -271,6 +299,42 @@ def save_graph(path, ori_adj, inference_adj, split):
         np.savez(f, pairs=pairs, scores=scores, hits=hits, threshold=np.float32(thr), iterations=np.int64(split["iterations"]))
 
 
+CI_LEVEL = 0.95
+
+
+def ci_report(ori_adj, inference_adj, sets, other=None):
+    """--ci: engine.auc_delong of each index set of `sets` (name -> node ids, None: every node); with `other` (--versus: a second
+    n x n score matrix) engine.auc_delong_paired of inference_adj against it instead, whose "a" is the same dict.  Returns
+    {"ci_<name>": dict} and, with `other`, {"versus_<name>": dict}."""
+    real = ori_adj.to(inference_adj.device)
+    out = {}
+    for name, ix in sets.items():
+        if other is None:
+            out[f"ci_{name}"] = engine.auc_delong(real, inference_adj, ix, CI_LEVEL)
+        else:
+            d = engine.auc_delong_paired(real, inference_adj, other.to(inference_adj.device), ix, CI_LEVEL)
+            out[f"ci_{name}"] = d["a"]
+            out[f"versus_{name}"] = d
+    return out
+
+
+def load_versus(path, n):
+    """--versus PATH: the .npy at `path` as an n x n float32 matrix; anything else is refused by name."""
+    try:
+        other = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        _exit(f"--versus {path}: not a readable .npy ({e})")
+    if other.shape != (n, n):
+        _exit(f"--versus {path}: a matrix of shape {tuple(other.shape)}; this graph's modified_adj is {n} x {n}")
+    return torch.from_numpy(np.ascontiguousarray(other, dtype=np.float32))
+
+
+def save_scores(path, inference_adj):
+    """--save_scores: modified_adj as a float32 .npy at exactly `path` (what --versus PATH reads)."""
+    with open(path, "wb") as f:
+        np.save(f, inference_adj.detach().to(torch.float32).cpu().numpy())
+
+
 def curves_report(path, ori_adj, inference_adj, sets):
     """--curves PATH: the ROC curve (drop_intermediate on, as the reference's roc_curve call) and the precision-recall curve
     (drop_intermediate off, sklearn's default) of each index set of `sets` (name -> node ids, None: every node), written as
@@ -368,6 +432,7 @@ def _run(args, rank, world):
     check_binarize_args(args, _exit)
     check_curves_args(args, _exit)
     check_per_node_args(args, _exit)
+    check_ci_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -458,6 +523,10 @@ def _run(args, rank, world):
                 for k in ("feature", "layer1", "layer2", "out", "label"):
                     print(f"{k} ap=", res["ap"][k])
         return res
+    want_ci, versus = bool(getattr(args, "ci", False)), getattr(args, "versus", None)
+    other = None
+    if versus is not None:  # refused before the attack runs, not after it
+        other = feature_adj if versus == "features" else load_versus(versus, adj.shape[0])
     lr = 10 ** args.lr                                                                     # objective(): main.py:282-283
     weight_param = tuple(getattr(args, f"w{i}") for i in range(1, 11))
     model = PGDAttack(model=victim_model, embedding=embedding, H_A=H_A2, Y_A=Y_A, nnodes=adj.shape[0],
@@ -494,6 +563,8 @@ def _run(args, rank, world):
     if want_per_node:       # every rank computes; rank 0 writes the file
         res.update(per_node_report(args.per_node if rank == 0 else None, ad, inference_adj,
                                    {"attack": idx_attack, "train": idx_train, "all": None}))
+    if want_ci:             # every rank computes; the keys exist only with the flag
+        res.update(ci_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, other))
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
@@ -514,6 +585,14 @@ def _run(args, rank, world):
     if want_per_node:
         d = res["per_node_all"]
         print(f"current macro_auc={d['macro_auc']} mrr={d['mrr']} hits@1={d['hits_at_1']}")
+    if want_ci:
+        d = res["ci_all"]
+        print(f"current auc_pairs={d['auc']} se={d['se']} ci=[{d['ci_low']}, {d['ci_high']}]")
+        if other is not None:
+            d = res["versus_all"]
+            print(f"current delta={d['delta']} z={d['z']} p={d['p_value']}")
+    if getattr(args, "save_scores", None):
+        save_scores(args.save_scores, inference_adj)
     os.makedirs("./results/", exist_ok=True)
     # the parameter line names --ap, --topk, --save_edges, --binarize, --save_graph, --curves and --per_node only when they are set:
     # without them the log is what it was before the flags existed
@@ -547,6 +626,15 @@ def _run(args, rank, world):
                             ("Whole Graph", res["per_node_all"])):
                 f.write(f"In {name}: scored nodes={d['scored']} macro AUC={d['macro_auc']} MRR={d['mrr']} "
                         f"Hits@1={d['hits_at_1']} R-precision={d['r_precision']}\n")
+        if want_ci:
+            for name, key in (("attack graph", "attack"), ("train graph", "train"), ("Whole Graph", "all")):
+                d = res[f"ci_{key}"]
+                f.write(f"In {name}: pairs={d['pairs']} positives={d['positives']} AUC of pairs={d['auc']} se={d['se']} "
+                        f"{int(round(100 * d['level']))}% CI=[{d['ci_low']}, {d['ci_high']}]\n")
+                if other is not None:
+                    d = res[f"versus_{key}"]
+                    f.write(f"In {name}: versus {versus}: AUC={d['b']['auc']} delta={d['delta']} se={d['se_delta']} "
+                            f"z={d['z']} p={d['p_value']}\n")
         f.write(f"current density: {res['density']}\n")
     return res
 
