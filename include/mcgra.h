@@ -408,6 +408,35 @@ int mcgra_auc_delong_paired(void* stream, int n, const float* labels, int ld_lab
                             const int64_t* idx, int64_t n_idx,
                             uint64_t* out /* host[17]: m, P, N, T_a, T_b, then lo, hi of A2_a, B2_a, A2_b, B2_b, A_ab, B_ab */);
 
+/* Which nodes carry the AUC, and how far it can be trusted when nodes rather than pairs are the independent units: the exact
+ * integers of the delete-one-node jackknife of the AUC of mcgra_auc_delong (Efron and Stein, Ann. Statist. 9, 1981).
+ *   - candidates, selection, comparison, placements a_p / b_q and checks as mcgra_auc_delong, for one score matrix.  With
+ *     2 psi(p, q) in {0, 1, 2} the doubled win of the candidate p of label 1 over the candidate q of label 0 (2 for a higher
+ *     score, 1 for a tie), a_p = sum_q 2 psi(p, q), b_q = sum_p 2 psi(p, q), T = sum_p a_p;
+ *   - header (host[4]) = m, P, N, T: the values mcgra_auc_delong gives for the same input;
+ *   - out (device uint64 [n_idx][5]), row v = position v of idx (not the node id), over the candidates that contain v:
+ *       P_v, N_v   those of label 1 and of label 0; P_v + N_v = n_idx - 1
+ *       A_v        sum of a_p over its candidates of label 1
+ *       B_v        sum of b_q over its candidates of label 0
+ *       C_v        sum of 2 psi(p, q) over its candidates p of label 1 and its candidates q of label 0
+ *     The candidates that remain when node v is deleted have T - A_v - B_v + C_v (C_v is part of both sums), P - P_v of
+ *     label 1 and N - N_v of label 0, so AUC_-v = (T - A_v - B_v + C_v) / (2 (P - P_v) (N - N_v)) -- left to the caller, with
+ *     the jackknife variance (n_idx - 1) / n_idx sum_v (AUC_-v - mean)^2.  sum P_v = 2 P, sum N_v = 2 N, sum A_v = sum B_v = 2 T;
+ *   - no overflow: n_idx <= 65 535, so P_v, N_v < 2^16 and P, N < 2^31: A_v <= 2 P_v N < 2^48, B_v <= 2 N_v P < 2^48,
+ *     C_v <= 2 P_v N_v < 2^33, T <= 2 P N < 2^61;
+ *   - refusals as mcgra_auc_delong: n_idx (n when idx is NULL) from 2 (MCGRA_EINVAL below) up to 65 535 (MCGRA_ENOSUP beyond),
+ *     header or out NULL, a matrix NULL, an ld below n: before any HIP call; a selected NaN / +-inf score, a selected label
+ *     other than 0 or 1, a repeated or out-of-range id: MCGRA_EINVAL.  No per-node stage bounds the selection further (a
+ *     node's candidates of label 1 are sorted in device memory, not in LDS), so MCGRA_NODE_RANK_MAX_NIDX does not apply.  After
+ *     any refusal nothing has been written to header or out and mcgra_last_error() names the cause;
+ *   - integer counts merged by integer adds, no floating-point arithmetic on the device: the same bits on every call.
+ * Synchronises `stream`.  Only the candidates of label 1 are stored; those of label 0 are streamed from the matrices.
+ * Device scratch: nothing per candidate pair; 52 bytes per selected node; 64 bytes per candidate of label 1; about 3 MB; 4 bytes
+ * per node of the graph when idx is given. */
+int mcgra_auc_node_jackknife(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                             const int64_t* idx, int64_t n_idx, uint64_t* header /* host[4]: m, P, N, T */,
+                             uint64_t* out /* device [n_idx][5]: P_v, N_v, A_v, B_v, C_v */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score

@@ -45,6 +45,7 @@ SYMBOLS = [
     "mcgra_node_rank_metrics",
     "mcgra_two_means_split", "mcgra_threshold_pairs",
     "mcgra_auc_delong", "mcgra_auc_delong_paired",
+    "mcgra_auc_node_jackknife",
 ]
 
 
@@ -133,6 +134,7 @@ def _load():
                                   C.POINTER(C.c_int64)],
         "mcgra_auc_delong": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64)],
         "mcgra_auc_delong_paired": [vp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64)],
+        "mcgra_auc_node_jackknife": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64), ip],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

@@ -43,6 +43,8 @@
 // Device scratch: 24 bytes per POSITIVE and scoring (its key by slot, the sorted copy, hist, ties and the 8-byte running sum)
 // plus 4 for the sort's second buffer, about 3 MB for the sort's counts, and 4 bytes per node of the graph when idx is given:
 // nothing per candidate.
+// DlSide, the searches, the histogram add, the two placements and the device-free checks are in delong_common.h, which
+// node_jackknife.hip shares.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -51,28 +53,16 @@
 
 #include "../../include/mcgra.h"
 #include "common.h"
+#include "delong_common.h"
 #include "rank_common.h"
 
 namespace mcgra {
 namespace {
 constexpr int DL_ROW_BLOCKS = 1024;        // blocks of the three passes over the matrix (grid-stride over selected rows)
 constexpr int DL_POS_BLOCKS = 2048;        // at most this many blocks of the pass over the positives (grid-stride)
-constexpr int DL_STAGE = 4096;             // samples of the sorted positives a block of k_dl_negatives keeps in LDS, per scoring
-enum { DL_BAD_SCORE_B = 32 };              // beside the AUC_BAD_* flags: the second score matrix
 
 // slots of the accumulators, per class
 enum { DL_T_A = 0, DL_T_B, DL_SQ_A_LO, DL_SQ_A_HI, DL_SQ_B_LO, DL_SQ_B_HI, DL_X_LO, DL_X_HI, DL_ACC };
-
-// what one scoring's positives need on the device
-struct DlSide {
-  const float* S;        // the score matrix (NULL: no second scoring)
-  int64_t ld;
-  uint32_t* slot;        // [P] the positives' keys by slot
-  uint32_t* sorted;      // [P] ascending
-  uint32_t* hist;        // [P + 1] negatives whose lb is this position
-  uint32_t* ties;        // [P + 1] of those, the ones equal to the positive at this position
-  uint64_t* cum;         // [P + 1] hist[0] + ... + hist[l - 1]
-};
 
 // rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection; f(score_a, score_b, label) for every pair (a, b), b < a
 template <class F>
@@ -145,64 +135,6 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_emit(int rows, const float* 
   }
 }
 
-// first index in [lo, hi) of the ascending keys B whose key is >= x (UPPER: > x); hi when there is none
-template <bool UPPER, class Keys, class I>
-__device__ __forceinline__ I dl_bound(const Keys& B, I lo, I hi, uint32_t x) {
-  while (lo < hi) {
-    const I mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = B[mid];
-    if (UPPER ? k <= x : k < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// dl_bound over all np sorted positives S through the ns samples smp[q] = S[q stride]: the bound among the samples leaves one
-// stretch between two samples.  c = first sample >= x (> x): every position up to (c - 1) stride is below (at or below) x and
-// position c stride is not, so the bound lies in ((c - 1) stride, c stride]; past the last sample it lies before np.
-template <bool UPPER>
-__device__ __forceinline__ uint32_t dl_find(const uint32_t* __restrict__ S, uint32_t np, const uint32_t* smp, uint32_t ns,
-                                            uint32_t stride, uint32_t x) {
-  const uint32_t c = dl_bound<UPPER>(smp, 0u, ns, x);
-  if (c == 0) return 0;
-  const uint32_t lo = (c - 1) * stride + 1, hi = c < ns ? c * stride : np;
-  return dl_bound<UPPER>(S, lo, hi, x);
-}
-
-// h[bin] += 1 for every lane with `on`.  The lanes of the wave that share one of its first DL_SHARED_BINS distinct bins add
-// once (tied scores and scores outside the positives' range put a whole wave into a few bins: one address would serialise 64
-// atomics); lanes left after that hold scattered bins and add on their own.  Every lane that is active in the caller must
-// call it (the loop is the same in all of them).
-constexpr int DL_SHARED_BINS = 4;
-__device__ __forceinline__ void dl_hist_add(uint32_t* __restrict__ h, uint32_t bin, bool on) {
-  const int lane = threadIdx.x & 63;
-  uint64_t todo = __ballot(on);
-  for (int it = 0; it < DL_SHARED_BINS && todo; ++it) {
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lb = __shfl(bin, leader, 64);
-    const uint64_t same = __ballot(on && bin == lb);
-    if (lane == leader) atomicAdd(&h[lb], (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
-  if ((todo >> lane) & 1ull) atomicAdd(&h[bin], 1u);
-}
-
-// one scoring's share of a negative: lb, ub among the sorted positives, the two counts, the placement 2 np - lb - ub
-__device__ __forceinline__ uint32_t dl_negative(const DlSide& s, uint32_t np, const uint32_t* smp, uint32_t ns, uint32_t stride,
-                                                float score, bool neg) {
-  uint32_t lb = 0, ub = 0;
-  bool tie = false;
-  if (neg) {
-    const uint32_t x = auc_key(score);
-    lb = dl_find<false>(s.sorted, np, smp, ns, stride, x);
-    tie = lb < np && s.sorted[lb] == x;
-    ub = tie ? dl_find<true>(s.sorted, np, smp, ns, stride, x) : lb;
-  }
-  dl_hist_add(s.hist, lb, neg);
-  dl_hist_add(s.ties, lb, tie);
-  return 2u * np - lb - ub;          // <= 2 np < 2^32
-}
-
 // The negatives, streamed: acc[DL_T_A / _B] += b, acc[DL_SQ_*] += the halves of b^2, acc[DL_X_*] += the halves of b^A b^B
 // (sb.S != NULL), and the counts hist / ties of each scoring.
 __global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide sa, DlSide sb, const float* __restrict__ L,
@@ -242,12 +174,6 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide s
   }
 }
 
-// one scoring's share of the positive at `slot`: a = 2 (negatives at or below it) - (negatives equal to it)
-__device__ __forceinline__ uint64_t dl_positive(const DlSide& s, uint32_t np, uint64_t slot) {
-  const uint32_t l = dl_bound<false>(s.sorted, 0u, np, s.slot[slot]);      // its own key is there: l < np
-  return 2 * (s.cum[l] + s.hist[l]) - s.ties[l];                          // <= 2 N < 2^32
-}
-
 // The positives, by slot: acc[DL_T_A / _B] += a, acc[DL_SQ_*] += the halves of a^2, acc[DL_X_*] += the halves of a^A a^B
 __global__ __launch_bounds__(AUC_THREADS) void k_dl_positives(DlSide sa, DlSide sb, uint32_t np,
                                                               unsigned long long* __restrict__ acc) {
@@ -272,22 +198,6 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_positives(DlSide sa, DlSide 
     const uint64_t tot = block_sum_u64(part[q], sh);
     if (threadIdx.x == 0 && tot) atomicAdd(&acc[q], (unsigned long long)tot);
   }
-}
-
-// the argument checks that need no device
-int dl_check(const char* who, int n, const float* labels, int ld_labels, const float* sa, int ld_a, const float* sb, int ld_b,
-             bool paired, const int64_t* idx, int64_t& n_idx, const uint64_t* out) {
-  if (!idx) n_idx = n;
-  if (n < 1 || !labels || !sa || (paired && !sb) || !out || ld_labels < n || ld_a < n || (paired && ld_b < n) || n_idx < 2) {
-    set_error("%s: bad argument (n >= 1, the matrices and out not NULL, every ld >= n, at least 2 selected nodes)", who);
-    return MCGRA_EINVAL;
-  }
-  if (n_idx > AUC_MAX_NIDX) {
-    set_error("%s: %lld selected nodes; a pair count of more than %lld nodes does not fit 31 bits", who, (long long)n_idx,
-              (long long)AUC_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
-  return 0;
 }
 
 // (low, high) limbs of lo + hi 2^32

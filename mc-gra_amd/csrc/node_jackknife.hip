@@ -1,0 +1,339 @@
+// Which nodes carry the AUC of the recovered graph, and how far it can be trusted when nodes, not pairs, are the independent
+// units: the integers of the delete-one-node jackknife of the AUC (mcgra_auc_node_jackknife).  Efron and Stein, "The jackknife
+// estimate of variance", Ann. Statist. 9 (1981).
+//
+// Candidates, comparison and placements: those of mcgra_auc_delong (delong.hip) -- the m = n_idx (n_idx - 1) / 2 unordered pairs
+// of positions a > b of a repeat-free idx, score scores[idx[a]][idx[b]], label labels[idx[a]][idx[b]], float32 values through
+// auc_key, a tie counts 1/2.  With 2 psi(p, q) in {0, 1, 2} the doubled win of positive p over negative q,
+//   a_p = sum_q 2 psi(p, q),  b_q = sum_p 2 psi(p, q),  T = sum a_p = sum b_q,
+// position v of idx gets five integers over the pairs that contain v:
+//   P_v, N_v   its positives and negatives (P_v + N_v = n_idx - 1)
+//   A_v        sum of a_p over its positives            <= 2 P_v N < 2^17 2^31
+//   B_v        sum of b_q over its negatives            <= 2 N_v P < 2^48
+//   C_v        sum of 2 psi(p, q) over its positives p and its negatives q   <= 2 P_v N_v < 2^33
+// Deleting v leaves T - A_v - B_v + C_v (C_v is in both sums), P - P_v positives and N - N_v negatives.
+//
+// Only the positives are stored, as in delong.hip; the negatives are streamed.  Passes:
+//   k_auc_index        idx only: range check, repeats (rank_common.h)
+//   k_nj_classify      one read of the selected lower triangle: the argument checks, per-block positive counts, and P_v
+//                      (deg[a] += 1, deg[b] += 1 per positive: 32-bit integer atomics)
+//   k_nj_emit          a second read of the labels: each positive's key and its endpoints a << 16 | b to a slot of its block's
+//                      range.  Which slot depends on the order the waves run in; the sort below ends that
+//   auc_sort           the positives by key, the endpoints riding along.  Equal keys may keep either order of their endpoints:
+//                      everything below is a sum over the positives of one key
+//   k_nj_lists         every sorted positive i becomes two entries (node a, key) and (node b, key) at 2 i, 2 i + 1
+//   auc_sort           the entries by node, stable, the keys riding along: node v's positives' keys, ascending, are
+//                      lkey[noff[v] .. noff[v + 1]), noff the running sum of deg
+//   k_nj_negatives     a third read.  Every negative x = (a, b) finds its placement b_q among all sorted positives (dl_negative:
+//                      samples in LDS, hist / ties for the positives' pass) and its doubled wins lost to a's positives and to
+//                      b's positives in the two nodes' lists (2 d - lb - ub in a list of d keys).  Row endpoint: the block that
+//                      owns row a sums over its lanes and adds once per row and column chunk.  Column endpoint: a block works
+//                      through the columns in chunks of NJ_COLS; lane t alone meets the columns c0 + t, c0 + t + 256, ... of a
+//                      chunk in every row, so it keeps their sums in LDS without atomics and adds the non-zero ones to the
+//                      node's sum when the chunk ends: global 64-bit atomics per (block, node), not per pair
+//   k_auc_digit_scan   the running sum of hist
+//   k_nj_positives     every sorted positive: a_p as in delong.hip, added to both endpoints' A (64-bit atomics, two per positive)
+//   k_nj_finish        P_v = deg[v], N_v = n_idx - 1 - deg[v]
+// Everything is integer counts merged by integer adds: no floating-point arithmetic on the device, the same bits on every
+// call.  The five columns are summed in scratch and copied to `out` when every check has passed.
+// Device scratch: 40 bytes per selected node + 12 for deg and noff; per POSITIVE 32 bytes (key, endpoints, hist, ties and the
+// 8-byte running sum, the sort's two second buffers) + 32 for the two list entries and their second buffers; about 3 MB for
+// the sort's counts; 4 bytes per node of the graph when idx is given.  Nothing per candidate.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/mcgra.h"
+#include "common.h"
+#include "delong_common.h"
+#include "rank_common.h"
+
+namespace mcgra {
+namespace {
+constexpr int NJ_ROW_BLOCKS = 512;         // blocks of the three passes over the matrix (grid-stride over selected rows)
+constexpr int NJ_POS_BLOCKS = 1024;        // at most this many blocks of the passes over the positives (grid-stride)
+constexpr int NJ_COLS = 2048;              // columns of one chunk of k_nj_negatives: 2 x 8 bytes of LDS each
+static_assert(NJ_COLS % AUC_THREADS == 0, "a lane owns the same columns of every chunk");
+static_assert(AUC_MAX_NIDX <= 0xffff, "a position fits 16 bits");
+enum { NJ_P = 0, NJ_N, NJ_A, NJ_B, NJ_C, NJ_WORDS };     // the columns of out
+
+// counts[b] = positives of block b's rows; deg[v] = positives that contain position v; flags |= the argument errors
+__global__ __launch_bounds__(AUC_THREADS) void k_nj_classify(int rows, const float* __restrict__ S, int64_t lds,
+                                                             const float* __restrict__ L, int64_t ldl,
+                                                             const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
+                                                             uint32_t* __restrict__ deg, int* __restrict__ flags) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  uint32_t pos = 0;
+  int f = 0;
+  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
+    const int64_t u = idx ? idx[a] : a;
+    const float* srow = S + u * lds;
+    const float* lrow = L + u * ldl;
+    uint32_t mine = 0;
+    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
+      const int64_t v = idx ? idx[b] : b;
+      const float l = lrow[v];
+      if (!auc_finite(srow[v])) f |= AUC_BAD_SCORE;
+      if (auc_pos(l)) { ++mine; atomicAdd(&deg[b], 1u); }
+      else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+    }
+    if (mine) atomicAdd(&deg[a], mine);
+    pos += mine;
+  }
+  if (f) atomicOr(flags, f);
+  const uint64_t p = block_sum_u64(pos, sh);
+  if (threadIdx.x == 0) counts[blockIdx.x] = p;
+}
+
+// block b's positives take the slots offs[b] .. (any order inside a block): key[slot], ends[slot] = a << 16 | b
+__global__ __launch_bounds__(AUC_THREADS) void k_nj_emit(int rows, const float* __restrict__ S, int64_t lds,
+                                                         const float* __restrict__ L, int64_t ldl,
+                                                         const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
+                                                         uint32_t* __restrict__ key, uint32_t* __restrict__ ends) {
+  __shared__ uint32_t cur;
+  if (threadIdx.x == 0) cur = 0;
+  __syncthreads();
+  const uint64_t o_pos = offs[blockIdx.x];
+  const int lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
+    const int64_t u = idx ? idx[a] : a;
+    const float* lrow = L + u * ldl;
+    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
+      const int64_t v = idx ? idx[b] : b;
+      const bool p = auc_pos(lrow[v]);
+      const uint64_t mp = __ballot(p);
+      if (mp == 0) continue;                              // the same in every active lane
+      const int leader = __ffsll((unsigned long long)mp) - 1;
+      uint32_t bp = 0;
+      if (lane == leader) bp = atomicAdd(&cur, (uint32_t)__popcll(mp));
+      bp = __shfl(bp, leader, 64);
+      if (p) {
+        const uint64_t at = o_pos + bp + __popcll(mp & below);
+        key[at] = auc_key(S[u * lds + v]);
+        ends[at] = (uint32_t)a << 16 | (uint32_t)b;
+      }
+    }
+  }
+}
+
+// the two list entries of every sorted positive
+__global__ __launch_bounds__(AUC_THREADS) void k_nj_lists(const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ ends,
+                                                          uint32_t np, uint32_t* __restrict__ lnode, uint32_t* __restrict__ lkey) {
+  for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < np; i += (uint64_t)gridDim.x * AUC_THREADS) {
+    const uint32_t e = ends[i], k = sorted[i];
+    lnode[2 * i] = e >> 16;
+    lnode[2 * i + 1] = e & 0xffffu;
+    lkey[2 * i] = k;
+    lkey[2 * i + 1] = k;
+  }
+}
+
+// the doubled wins of a node's d positives (keys ascending at `list`) over a negative of key x: 2 #{> x} + #{== x}
+__device__ __forceinline__ uint32_t nj_lost(const uint32_t* __restrict__ list, uint32_t d, uint32_t x) {
+  if (d == 0) return 0;
+  const uint32_t lb = dl_bound<false>(list, 0u, d, x);
+  const uint32_t ub = dl_bound<true>(list, lb, d, x);
+  return 2u * d - lb - ub;
+}
+
+// The negatives, streamed: out[a][NJ_B] += b_q and out[b][NJ_B] += b_q, out[a][NJ_C] += q's losses to a's positives,
+// out[b][NJ_C] += its losses to b's positives, *t_neg += b_q, and the counts hist / ties.
+__global__ __launch_bounds__(AUC_THREADS) void k_nj_negatives(int rows, DlSide s, const float* __restrict__ L, int64_t ldl,
+                                                              const int64_t* __restrict__ idx, uint32_t np,
+                                                              const uint32_t* __restrict__ lkey, const uint64_t* __restrict__ noff,
+                                                              unsigned long long* __restrict__ out,
+                                                              unsigned long long* __restrict__ t_neg) {
+  __shared__ uint32_t smp[DL_STAGE];
+  __shared__ uint64_t col_b[NJ_COLS], col_c[NJ_COLS];
+  __shared__ uint64_t sh_b[AUC_THREADS / 64], sh_c[AUC_THREADS / 64];
+  const uint32_t stride = (np + DL_STAGE - 1) / DL_STAGE, ns = (np + stride - 1) / stride;
+  for (uint32_t q = threadIdx.x; q < ns; q += AUC_THREADS) smp[q] = s.sorted[(uint64_t)q * stride];
+  __syncthreads();
+  uint64_t total = 0;
+  for (int c0 = 0; c0 + 1 < rows; c0 += NJ_COLS) {                 // column rows - 1 has no row above it
+    for (int j = threadIdx.x; j < NJ_COLS; j += AUC_THREADS) { col_b[j] = 0; col_c[j] = 0; }   // this lane's own columns
+    for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
+      if (a <= c0) continue;                                        // the same in the whole block
+      const int64_t u = idx ? idx[a] : a;
+      const float* srow = s.S + u * s.ld;
+      const float* lrow = L + u * ldl;
+      const uint64_t oa = noff[a];
+      const uint32_t da = (uint32_t)(noff[a + 1] - oa);
+      const int hi = min(a, c0 + NJ_COLS);
+      uint64_t row_b = 0, row_c = 0;
+      for (int b = c0 + threadIdx.x; b < hi; b += AUC_THREADS) {
+        const int64_t v = idx ? idx[b] : b;
+        const float x = srow[v];
+        const bool neg = !auc_pos(lrow[v]);                         // the labels were checked: 0 or 1
+        const uint64_t bq = dl_negative(s, np, smp, ns, stride, x, neg);
+        if (neg) {
+          const uint32_t k = auc_key(x);
+          const uint64_t ob = noff[b];
+          const uint64_t ca = nj_lost(lkey + oa, da, k), cb = nj_lost(lkey + ob, (uint32_t)(noff[b + 1] - ob), k);
+          row_b += bq;
+          row_c += ca;
+          col_b[b - c0] += bq;
+          col_c[b - c0] += cb;
+        }
+      }
+      total += row_b;
+      const uint64_t tb = block_sum_u64(row_b, sh_b), tc = block_sum_u64(row_c, sh_c);
+      if (threadIdx.x == 0) {
+        if (tb) atomicAdd(&out[(size_t)a * NJ_WORDS + NJ_B], (unsigned long long)tb);
+        if (tc) atomicAdd(&out[(size_t)a * NJ_WORDS + NJ_C], (unsigned long long)tc);
+      }
+    }
+    for (int j = threadIdx.x; j < NJ_COLS && c0 + j < rows; j += AUC_THREADS) {
+      if (col_b[j]) atomicAdd(&out[(size_t)(c0 + j) * NJ_WORDS + NJ_B], (unsigned long long)col_b[j]);
+      if (col_c[j]) atomicAdd(&out[(size_t)(c0 + j) * NJ_WORDS + NJ_C], (unsigned long long)col_c[j]);
+    }
+  }
+  __syncthreads();
+  const uint64_t tot = block_sum_u64(total, sh_b);
+  if (threadIdx.x == 0 && tot) atomicAdd(t_neg, (unsigned long long)tot);
+}
+
+// The positives, in sorted order: out[a][NJ_A] += a_p, out[b][NJ_A] += a_p, *t_pos += a_p
+__global__ __launch_bounds__(AUC_THREADS) void k_nj_positives(DlSide s, const uint32_t* __restrict__ ends, uint32_t np,
+                                                              unsigned long long* __restrict__ out,
+                                                              unsigned long long* __restrict__ t_pos) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  uint64_t total = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < np; i += (uint64_t)gridDim.x * AUC_THREADS) {
+    const uint64_t ap = dl_positive(s, np, i);
+    const uint32_t e = ends[i];
+    total += ap;
+    if (ap) {
+      atomicAdd(&out[(size_t)(e >> 16) * NJ_WORDS + NJ_A], (unsigned long long)ap);
+      atomicAdd(&out[(size_t)(e & 0xffffu) * NJ_WORDS + NJ_A], (unsigned long long)ap);
+    }
+  }
+  const uint64_t tot = block_sum_u64(total, sh);
+  if (threadIdx.x == 0 && tot) atomicAdd(t_pos, (unsigned long long)tot);
+}
+
+__global__ __launch_bounds__(AUC_THREADS) void k_nj_finish(int rows, const uint32_t* __restrict__ deg,
+                                                           unsigned long long* __restrict__ out) {
+  for (int v = blockIdx.x * AUC_THREADS + threadIdx.x; v < rows; v += gridDim.x * AUC_THREADS) {
+    out[(size_t)v * NJ_WORDS + NJ_P] = deg[v];
+    out[(size_t)v * NJ_WORDS + NJ_N] = (uint32_t)(rows - 1) - deg[v];
+  }
+}
+
+int nj_run(const char* who, hipStream_t st, int n, const float* L, int ldl, const float* S, int lds, const int64_t* idx, int rows,
+           uint64_t* header, uint64_t* out) {
+  AucBufs b;
+  const int g = std::min(rows - 1, NJ_ROW_BLOCKS);
+  // one allocation for what scales with the selection: the two placement sums, flags, the per-block counts, the staged
+  // answer, noff [rows + 1], deg [rows + 1] (deg[rows] = 0: the scan's last entry is the total)
+  struct Head { unsigned long long t_pos, t_neg; int flags, pad; };
+  static_assert(sizeof(Head) % 8 == 0, "counts is 8-byte aligned");
+  const size_t R1 = (size_t)rows + 1;
+  const size_t head_bytes = sizeof(Head) + sizeof(uint64_t) * ((size_t)g + (size_t)rows * NJ_WORDS + R1) + sizeof(uint32_t) * R1;
+  uint8_t* head = b.get<uint8_t>(head_bytes);
+  if (!head) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
+  Head* hd = (Head*)head;
+  uint64_t* counts = (uint64_t*)(head + sizeof(Head));
+  unsigned long long* stage = (unsigned long long*)(counts + g);
+  uint64_t* noff = (uint64_t*)(stage + (size_t)rows * NJ_WORDS);
+  uint32_t* deg = (uint32_t*)(noff + R1);
+  MCGRA_HIP(hipMemsetAsync(head, 0, head_bytes, st));
+  int h_flags = 0;
+  if (idx) {
+    uint32_t* seen = b.get<uint32_t>(n);
+    if (!seen) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
+    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
+    const int gi = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
+    k_auc_index<<<gi, AUC_THREADS, 0, st>>>(n, rows, idx, seen, &hd->flags);
+    MCGRA_KERNEL_CHECK();
+    MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    MCGRA_HIP(hipStreamSynchronize(st));
+    if (h_flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
+    if (h_flags & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
+  }
+  k_nj_classify<<<g, AUC_THREADS, 0, st>>>(rows, S, lds, L, ldl, idx, counts, deg, &hd->flags);
+  MCGRA_KERNEL_CHECK();
+  std::vector<uint64_t> h(g);
+  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));
+  if (h_flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
+    set_error("%s: %s%s", who, (h_flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
+              (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
+    return MCGRA_EINVAL;
+  }
+  uint64_t P = 0;
+  for (int i = 0; i < g; ++i) { const uint64_t p = h[i]; h[i] = P; P += p; }        // counts -> offsets
+  const uint64_t m = (uint64_t)rows * (rows - 1) / 2, N = m - P;
+  const int gr = (rows + AUC_THREADS - 1) / AUC_THREADS;
+  unsigned long long t[2] = {0, 0};
+  if (P != 0 && N != 0) {                               // else every placement is 0
+    // one allocation for what scales with P.  P4 = P rounded up to 4 keys: every array starts on 16 bytes.  cum [P4 + 4];
+    // key, ends, their second buffers [P4]; hist, ties [P4 + 4]; lnode, lkey, their second buffers [2 P4]; the sort's counts
+    const size_t P4 = (P + 3) / 4 * 4, H4 = P4 + 4;
+    const size_t sort_cnt = 256 * (size_t)AUC_SORT_BLOCKS;
+    const size_t bytes = sizeof(uint64_t) * (H4 + sort_cnt) + sizeof(uint32_t) * (4 * P4 + 2 * H4 + 8 * P4 + sort_cnt);
+    uint8_t* pool = b.get<uint8_t>(bytes);
+    if (!pool) { set_error("%s: hipMalloc of the scratch of %llu positives failed", who, (unsigned long long)P); return MCGRA_ENOMEM; }
+    uint8_t* at = pool;
+    auto take = [&](size_t count, size_t size) { uint8_t* p = at; at += count * size; return p; };
+    DlSide s = {};
+    s.S = S;
+    s.ld = lds;
+    s.cum = (uint64_t*)take(H4, 8);
+    uint64_t* off = (uint64_t*)take(sort_cnt, 8);
+    s.sorted = s.slot = (uint32_t*)take(P4, 4);         // the positives' pass runs over the sorted positives
+    uint32_t* ends = (uint32_t*)take(P4, 4);
+    uint32_t* tmp = (uint32_t*)take(P4, 4);
+    uint32_t* etmp = (uint32_t*)take(P4, 4);
+    s.hist = (uint32_t*)take(H4, 4);
+    s.ties = (uint32_t*)take(H4, 4);
+    uint32_t* lnode = (uint32_t*)take(2 * P4, 4);
+    uint32_t* lkey = (uint32_t*)take(2 * P4, 4);
+    uint32_t* ltmp = (uint32_t*)take(2 * P4, 4);
+    uint32_t* ktmp = (uint32_t*)take(2 * P4, 4);
+    uint32_t* cnt = (uint32_t*)take(sort_cnt, 4);
+    MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
+    k_nj_emit<<<g, AUC_THREADS, 0, st>>>(rows, S, lds, L, ldl, idx, counts, s.sorted, ends);
+    MCGRA_KERNEL_CHECK();
+    if (int rc = auc_sort(st, s.sorted, tmp, P, cnt, off, ends, etmp)) return rc;
+    const int gp = (int)std::min<uint64_t>(NJ_POS_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
+    k_nj_lists<<<gp, AUC_THREADS, 0, st>>>(s.sorted, ends, (uint32_t)P, lnode, lkey);
+    MCGRA_KERNEL_CHECK();
+    if (int rc = auc_sort(st, lnode, ltmp, 2 * P, cnt, off, lkey, ktmp)) return rc;
+    k_auc_digit_scan<<<1, 1024, 0, st>>>(deg, rows + 1, noff);
+    MCGRA_HIP(hipMemsetAsync(s.hist, 0, sizeof(uint32_t) * 2 * H4, st));               // hist and ties are adjacent
+    k_nj_negatives<<<g, AUC_THREADS, 0, st>>>(rows, s, L, ldl, idx, (uint32_t)P, lkey, noff, stage, &hd->t_neg);
+    MCGRA_KERNEL_CHECK();
+    k_auc_digit_scan<<<1, 1024, 0, st>>>(s.hist, (int)P, s.cum);
+    k_nj_positives<<<gp, AUC_THREADS, 0, st>>>(s, ends, (uint32_t)P, stage, &hd->t_pos);
+    MCGRA_KERNEL_CHECK();
+  }
+  k_nj_finish<<<gr, AUC_THREADS, 0, st>>>(rows, deg, stage);
+  MCGRA_KERNEL_CHECK();
+  MCGRA_HIP(hipMemcpyAsync(t, &hd->t_pos, sizeof(t), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));
+  if (t[0] != t[1]) {                                   // sum a_p == sum b_q by construction
+    set_error("%s: internal error: the two placement sums differ (%llu, %llu)", who, t[0], t[1]);
+    return MCGRA_EHIP;
+  }
+  MCGRA_HIP(hipMemcpyAsync(out, stage, sizeof(uint64_t) * NJ_WORDS * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  MCGRA_HIP(hipStreamSynchronize(st));                  // the scratch is freed on return
+  const uint64_t res[4] = {m, P, N, t[0]};
+  memcpy(header, res, sizeof(res));
+  return 0;
+}
+}  // namespace
+}  // namespace mcgra
+
+using namespace mcgra;
+
+extern "C" int mcgra_auc_node_jackknife(void* stream, int n, const float* labels, int ld_labels, const float* scores,
+                                        int ld_scores, const int64_t* idx, int64_t n_idx, uint64_t* header, uint64_t* out) {
+  if (!header) { set_error("auc_node_jackknife: bad argument (header NULL)"); return MCGRA_EINVAL; }
+  if (int rc = dl_check("auc_node_jackknife", n, labels, ld_labels, scores, ld_scores, nullptr, 0, false, idx, n_idx, out)) return rc;
+  return nj_run("auc_node_jackknife", (hipStream_t)stream, n, labels, ld_labels, scores, ld_scores, idx, (int)n_idx, header, out);
+}

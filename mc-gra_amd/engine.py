@@ -609,6 +609,154 @@ def auc_delong_paired(real, pred_a, pred_b, idx=None, level=0.95):
     return delong_paired_stats(ints, level)
 
 
+NODE_JACKKNIFE_COLUMNS = ("P_v", "N_v", "A_v", "B_v", "C_v")
+
+
+def _jackknife_influences(ints):
+    """(m, P, N, auc as a Fraction or None, [(numerator, denominator) of d_v or None]) from the integers of
+    auc_node_jackknife: d_v = AUC - AUC_-v = (T D_v - T_-v D) / (D D_v), D = 2 P N, D_v = 2 (P - P_v) (N - N_v); None where
+    deleting v leaves no positive or no negative.  The denominator depends on the labels alone."""
+    P, N, T = (int(ints[k]) for k in ("positives", "negatives", "T"))
+    cols = [[int(x) for x in ints[k]] for k in NODE_JACKKNIFE_COLUMNS]
+    m = len(cols[0])
+    if any(len(c) != m for c in cols):
+        raise ValueError("node_jackknife_stats: the five columns differ in length")
+    if P == 0 or N == 0:
+        return m, P, N, None, [None] * m
+    D = 2 * P * N
+    d = []
+    for pv, nv, av, bv, cv in zip(*cols):
+        Dv = 2 * (P - pv) * (N - nv)
+        d.append(None if Dv == 0 else (T * Dv - (T - av - bv + cv) * D, D * Dv))
+    return m, P, N, Fraction(T, D), d
+
+
+def _influence_doubles(d):
+    """The exact influences d = (numerator, denominator) or None, each ONE Fraction rounded to a double once; NaN for None."""
+    return [float("nan") if x is None else float(Fraction(*x)) for x in d]
+
+
+def _jackknife(dv, m):
+    """(mean, var) of the delete-one jackknife over the m doubles dv, by math.fsum."""
+    mean = math.fsum(dv) / m
+    return mean, (m - 1) / m * math.fsum((x - mean) ** 2 for x in dv)
+
+
+def node_jackknife_stats(ints, level=0.95):
+    """The dict of auc_node_jackknife from its integers {"pairs", "positives", "negatives", "T" and the per-node sequences "P_v",
+    "N_v", "A_v", "B_v", "C_v"}: the influence d_v = AUC - AUC_-v, AUC_-v = (T - A_v - B_v + C_v) / (2 (P - P_v) (N - N_v)), is
+    ONE exact rational per node, rounded to a double once; the mean and var = (m - 1) / m sum (d_v - mean)^2 over the m nodes
+    are math.fsum of those doubles, so they are the same on every call.  No device is involved."""
+    nan = float("nan")
+    zq = _norm_quantile(level)
+    m, P, N, auc, d = _jackknife_influences(ints)
+    undefined = sum(x is None for x in d)
+    dv = _influence_doubles(d)
+    res = {"pairs": int(ints["pairs"]), "nodes": m, "positives": P, "negatives": N, "auc": nan, "auc_jackknife": nan, "var": nan,
+           "se": nan, "ci_low": nan, "ci_high": nan, "level": float(level), "undefined_nodes": undefined,
+           "influence": torch.tensor(dv, dtype=torch.float64),
+           "ints": {k: (list(int(x) for x in v) if k in NODE_JACKKNIFE_COLUMNS else int(v)) for k, v in ints.items()}}
+    if auc is None:
+        return res
+    res["auc"] = float(auc)
+    if undefined or m < 3:
+        return res
+    mean, var = _jackknife(dv, m)
+    res["auc_jackknife"] = res["auc"] + (m - 1) * mean
+    res["var"] = var
+    res["se"] = math.sqrt(var)
+    res["ci_low"] = max(0.0, res["auc"] - zq * res["se"])
+    res["ci_high"] = min(1.0, res["auc"] + zq * res["se"])
+    return res
+
+
+def node_jackknife_paired_stats(ints_a, ints_b, level=0.95):
+    """The node jackknife of the difference of two scorings' AUCs over the same pairs, from the integers of two
+    auc_node_jackknife calls: d_v = d_v^A - d_v^B is ONE exact rational per node before it is rounded, then the jackknife of
+    node_jackknife_stats.  Returns {"a", "b" (each scoring's dict), "delta" auc_a - auc_b, "delta_jackknife", "var_delta",
+    "se_delta", "ci_low", "ci_high" (delta -+ z se_delta clipped to [-1, 1]), "z", "p_value", "influence", "undefined_nodes",
+    "nodes", "pairs", "positives", "negatives", "level"}; var_delta == 0: z = 0, p = 1 when delta == 0, else z = +-inf, p = 0.
+    ValueError when "pairs", "positives", "negatives", "P_v" or "N_v" differ: the two runs did not see the same pairs."""
+    nan = float("nan")
+    zq = _norm_quantile(level)
+    a, b = node_jackknife_stats(ints_a, level), node_jackknife_stats(ints_b, level)
+    for k in ("pairs", "positives", "negatives", "P_v", "N_v"):
+        if a["ints"][k] != b["ints"][k]:
+            raise ValueError(f"node_jackknife_paired_stats: the two runs disagree in {k}: not two scorings of the same pairs")
+    m, P, N, auc_a, da = _jackknife_influences(ints_a)
+    _, _, _, auc_b, db = _jackknife_influences(ints_b)
+    dv = _influence_doubles([None if x is None else (x[0] - y[0], x[1]) for x, y in zip(da, db)])   # P_v, N_v agree: one denominator
+    res = {"a": a, "b": b, "pairs": a["pairs"], "nodes": m, "positives": P, "negatives": N, "delta": nan, "delta_jackknife": nan,
+           "var_delta": nan, "se_delta": nan, "ci_low": nan, "ci_high": nan, "z": nan, "p_value": nan, "level": float(level),
+           "undefined_nodes": a["undefined_nodes"],
+           "influence": torch.tensor(dv, dtype=torch.float64)}
+    if auc_a is None:
+        return res
+    delta = auc_a - auc_b
+    res["delta"] = float(delta)
+    if a["undefined_nodes"] or m < 3:
+        return res
+    mean, var = _jackknife(dv, m)
+    res["delta_jackknife"] = res["delta"] + (m - 1) * mean
+    res["var_delta"] = var
+    res["se_delta"] = math.sqrt(var)
+    res["ci_low"] = max(-1.0, res["delta"] - zq * res["se_delta"])
+    res["ci_high"] = min(1.0, res["delta"] + zq * res["se_delta"])
+    if var == 0:
+        res["z"] = 0.0 if delta == 0 else math.copysign(float("inf"), delta)
+    else:
+        res["z"] = res["delta"] / res["se_delta"]
+    res["p_value"] = math.erfc(abs(res["z"]) / math.sqrt(2.0))
+    return res
+
+
+def _node_jackknife_ints(real, pred, idx):
+    dev = real.device
+    n = real.shape[0]
+    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
+    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
+    ix = _node_ids(idx, dev)
+    rows = ix.numel() if ix is not None else n
+    header = (C.c_uint64 * 4)()
+    out = torch.empty(max(rows, 0), 5, device=dev, dtype=torch.int64)        # every value is below 2^61
+    check(lib.mcgra_auc_node_jackknife(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, header,
+                                       _p(out)))
+    ints = {"pairs": int(header[0]), "positives": int(header[1]), "negatives": int(header[2]), "T": int(header[3])}
+    ints.update(zip(NODE_JACKKNIFE_COLUMNS, out.t().tolist()))
+    return ints
+
+
+@_on_operand_device
+def auc_node_jackknife(real, pred, idx=None, level=0.95):
+    """How far the AUC of the recovered graph can be trusted when NODES are the independent units, and which nodes carry it
+    (mcgra_auc_node_jackknife): the delete-one-node jackknife of the AUC of auc_delong (Efron and Stein, Ann. Statist. 9, 1981)
+    over the same candidates -- the m_pairs unordered pairs of positions a > b of a REPEAT-FREE idx (None: all nodes), score
+    pred[idx[a], idx[b]], label real[idx[a], idx[b]], float32 comparison with ties counted 1/2.  Per position v of idx the
+    device returns five exact integers over the pairs that contain v (P_v, N_v, the placement sums A_v, B_v and their overlap
+    C_v); deleting v leaves AUC_-v = (T - A_v - B_v + C_v) / (2 (P - P_v) (N - N_v)).  Returns {"pairs", "nodes" (m),
+    "positives", "negatives", "auc" T / (2 P N) (auc_delong's), "auc_jackknife" auc + (m - 1) mean(d) (bias-corrected), "var"
+    (m - 1) / m sum (d_v - mean)^2, "se", "ci_low", "ci_high" (auc -+ z se clipped to [0, 1]), "level", "undefined_nodes",
+    "influence" (float64 [m]: d_v = auc - AUC_-v, positive where the node helps the attack), "ints" (the header and the five
+    columns)}: integer counts from the device, one exact rational per node on the host, the same bits on every call.
+    This se is conservative where DeLong's is optimistic: the node jackknife is biased upward, never downward, when nodes are
+    the exchangeable units, while DeLong's treats pairs that share a node as independent; reporting both brackets the truth.
+    P or N == 0: everything NaN; a node that holds every positive or every negative (its deletion leaves no AUC; counted in
+    "undefined_nodes", its influence NaN) or m == 2: the AUC alone; var == 0: the interval is [auc, auc].  Refusals as
+    auc_delong."""
+    _norm_quantile(level)
+    return node_jackknife_stats(_node_jackknife_ints(real, pred, idx), level)
+
+
+@_on_operand_device
+def auc_node_jackknife_paired(real, pred_a, pred_b, idx=None, level=0.95):
+    """Whether two scorings of the same pairs differ when NODES are the independent units: mcgra_auc_node_jackknife once per
+    scoring, then node_jackknife_paired_stats -- the jackknife of d_v^A - d_v^B, delta, se_delta, the interval clipped to
+    [-1, 1], z and the two-sided p_value.  This se is conservative where DeLong's (auc_delong_paired) is optimistic.  Refusals
+    as auc_delong, for either matrix."""
+    _norm_quantile(level)
+    return node_jackknife_paired_stats(_node_jackknife_ints(real, pred_a, idx), _node_jackknife_ints(real, pred_b, idx), level)
+
+
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
 # row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
 NODE_RANK_MAX_NIDX = 16384

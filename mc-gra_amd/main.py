@@ -37,10 +37,17 @@ order with the threshold and the round count (engine.threshold_pairs).
 can be trusted: DeLong's standard error and 95 % confidence interval of the AUC of the unordered node pairs of each index set
 (engine.auc_delong; integer counts on the GPU, exact rationals on the host).  Pairs that share a node are not independent, so
 the interval is a lower bound on the real uncertainty.
---versus features|PATH (needs --ci) asks whether the attack beats another scoring of the same pairs: DeLong's paired test
+--versus features|PATH (needs --ci or --ci_nodes) asks whether the attack beats another scoring of the same pairs: DeLong's paired test
 (engine.auc_delong_paired) of modified_adj against the run's own feature_adj -- the prior the attacker already holds -- or
 against an n x n float32 matrix stored as an .npy at PATH; delta, z and the two-sided p-value of each index set are reported.
 --save_scores PATH (--mode evaluate only) writes modified_adj as that .npy, so that one run can be compared with another.
+--ci_nodes (not in the reference; --mode evaluate only; absent by default, and then nothing changes) puts the conservative
+bracket beside --ci's optimistic one: the delete-one-node jackknife standard error and 95 % interval of the same AUC
+(engine.auc_node_jackknife; five exact integers per node on the GPU, one exact rational per node on the host).  With --ci the
+ratio se_nodes / se of the two standard errors is reported; with --versus the jackknife of the difference of the two scorings'
+AUCs (engine.auc_node_jackknife_paired).
+--save_influence PATH (needs --ci_nodes) writes, as an .npz at PATH, which nodes carry the attack's AUC: for each index set
+nodes_<set>, the integers P_v_<set>, N_v_<set>, A_v_<set>, B_v_<set>, C_v_<set> and influence_<set> = AUC - AUC without the node.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -115,8 +122,8 @@ def check_per_node_args(args, fail):
 def check_ci_args(args, fail):
     """--ci / --versus / --save_scores against the rest of the command line; fail(message) does not return."""
     ci, versus, scores = getattr(args, "ci", False), getattr(args, "versus", None), getattr(args, "save_scores", None)
-    if versus is not None and not ci:
-        fail("--versus needs --ci")
+    if versus is not None and not ci and not getattr(args, "ci_nodes", False):
+        fail("--versus needs --ci or --ci_nodes")
     if versus is not None and versus == "":
         fail("--versus takes `features` or the path of an .npy score matrix")
     if ci and args.mode != "evaluate":
@@ -127,6 +134,17 @@ def check_ci_args(args, fail):
         fail("--save_scores takes the path of the .npy to write")
 
 
+def check_ci_nodes_args(args, fail):
+    """--ci_nodes / --save_influence against the rest of the command line; fail(message) does not return."""
+    nodes, path = getattr(args, "ci_nodes", False), getattr(args, "save_influence", None)
+    if nodes and args.mode != "evaluate":
+        fail(f"--ci_nodes jackknifes the AUC of the attack's modified_adj over its nodes: --mode evaluate only, not --mode {args.mode}")
+    if path is not None and not nodes:
+        fail("--save_influence needs --ci_nodes")
+    if path is not None and path == "":
+        fail("--save_influence takes the path of the .npz to write")
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
@@ -135,6 +153,7 @@ class _Parser(argparse.ArgumentParser):
         check_curves_args(args, self.error)
         check_per_node_args(args, self.error)
         check_ci_args(args, self.error)
+        check_ci_nodes_args(args, self.error)
         return args
 
 
@@ -186,6 +205,8 @@ def build_parser():
     p.add_argument('--ci', action='store_true', default=argparse.SUPPRESS)      # also DeLong's se and interval of the AUC
     p.add_argument('--versus', type=str, default=argparse.SUPPRESS)            # with --ci: paired test against `features` or an .npy
     p.add_argument('--save_scores', type=str, default=argparse.SUPPRESS)       # write modified_adj as an .npy for a later --versus
+    p.add_argument('--ci_nodes', action='store_true', default=argparse.SUPPRESS)   # also the node-jackknife se and interval of the AUC
+    p.add_argument('--save_influence', type=str, default=argparse.SUPPRESS)    # with --ci_nodes: each node's influence as an .npz
     return p
 
 
@@ -302,6 +323,11 @@ def save_graph(path, ori_adj, inference_adj, split):
 CI_LEVEL = 0.95
 
 
+def _se_ratio(nodes, pairs):
+    """se_nodes / se of one index set: the node jackknife's standard error over DeLong's; NaN where either is undefined."""
+    return nodes["se"] / pairs["se"] if pairs["se"] > 0 else float("nan")
+
+
 def ci_report(ori_adj, inference_adj, sets, other=None):
     """--ci: engine.auc_delong of each index set of `sets` (name -> node ids, None: every node); with `other` (--versus: a second
     n x n score matrix) engine.auc_delong_paired of inference_adj against it instead, whose "a" is the same dict.  Returns
@@ -316,6 +342,36 @@ def ci_report(ori_adj, inference_adj, sets, other=None):
             out[f"ci_{name}"] = d["a"]
             out[f"versus_{name}"] = d
     return out
+
+
+def ci_nodes_report(ori_adj, inference_adj, sets, other=None):
+    """--ci_nodes: engine.auc_node_jackknife of each index set of `sets` (name -> node ids, None: every node); with `other`
+    (--versus) engine.auc_node_jackknife_paired of inference_adj against it instead, whose "a" is the same dict.  Returns
+    {"ci_nodes_<name>": dict} and, with `other`, {"versus_nodes_<name>": dict}."""
+    real = ori_adj.to(inference_adj.device)
+    out = {}
+    for name, ix in sets.items():
+        if other is None:
+            out[f"ci_nodes_{name}"] = engine.auc_node_jackknife(real, inference_adj, ix, CI_LEVEL)
+        else:
+            d = engine.auc_node_jackknife_paired(real, inference_adj, other.to(inference_adj.device), ix, CI_LEVEL)
+            out[f"ci_nodes_{name}"] = d["a"]
+            out[f"versus_nodes_{name}"] = d
+    return out
+
+
+def save_influence(path, res, sets, n):
+    """--save_influence: per index set the node ids, the five integer columns of engine.auc_node_jackknife (int64) and the
+    influence d_v = AUC - AUC_-v (float64, NaN where deleting the node leaves no AUC), as an .npz at exactly `path`."""
+    arrays = {}
+    for name, ix in sets.items():
+        d = res[f"ci_nodes_{name}"]
+        arrays[f"nodes_{name}"] = np.arange(n, dtype=np.int64) if ix is None else np.asarray(ix, dtype=np.int64)
+        for k in engine.NODE_JACKKNIFE_COLUMNS:
+            arrays[f"{k}_{name}"] = np.asarray(d["ints"][k], dtype=np.int64)
+        arrays[f"influence_{name}"] = d["influence"].numpy()
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
 
 
 def load_versus(path, n):
@@ -433,6 +489,7 @@ def _run(args, rank, world):
     check_curves_args(args, _exit)
     check_per_node_args(args, _exit)
     check_ci_args(args, _exit)
+    check_ci_nodes_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -524,6 +581,7 @@ def _run(args, rank, world):
                     print(f"{k} ap=", res["ap"][k])
         return res
     want_ci, versus = bool(getattr(args, "ci", False)), getattr(args, "versus", None)
+    want_ci_nodes = bool(getattr(args, "ci_nodes", False))
     other = None
     if versus is not None:  # refused before the attack runs, not after it
         other = feature_adj if versus == "features" else load_versus(versus, adj.shape[0])
@@ -565,6 +623,8 @@ def _run(args, rank, world):
                                    {"attack": idx_attack, "train": idx_train, "all": None}))
     if want_ci:             # every rank computes; the keys exist only with the flag
         res.update(ci_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, other))
+    if want_ci_nodes:       # every rank computes; the keys exist only with the flag
+        res.update(ci_nodes_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, other))
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
@@ -591,6 +651,15 @@ def _run(args, rank, world):
         if other is not None:
             d = res["versus_all"]
             print(f"current delta={d['delta']} z={d['z']} p={d['p_value']}")
+    if want_ci_nodes:
+        d = res["ci_nodes_all"]
+        ratio = f" se_nodes/se={_se_ratio(d, res['ci_all'])}" if want_ci else ""
+        print(f"current auc_pairs={d['auc']} se_nodes={d['se']} ci_nodes=[{d['ci_low']}, {d['ci_high']}]{ratio}")
+        if other is not None:
+            d = res["versus_nodes_all"]
+            print(f"current delta={d['delta']} se_nodes={d['se_delta']} z={d['z']} p={d['p_value']}")
+        if getattr(args, "save_influence", None):
+            save_influence(args.save_influence, res, {"attack": idx_attack, "train": idx_train, "all": None}, adj.shape[0])
     if getattr(args, "save_scores", None):
         save_scores(args.save_scores, inference_adj)
     os.makedirs("./results/", exist_ok=True)
@@ -634,6 +703,18 @@ def _run(args, rank, world):
                 if other is not None:
                     d = res[f"versus_{key}"]
                     f.write(f"In {name}: versus {versus}: AUC={d['b']['auc']} delta={d['delta']} se={d['se_delta']} "
+                            f"z={d['z']} p={d['p_value']}\n")
+        if want_ci_nodes:
+            for name, key in (("attack graph", "attack"), ("train graph", "train"), ("Whole Graph", "all")):
+                d = res[f"ci_nodes_{key}"]
+                ratio = f" se_nodes/se={_se_ratio(d, res[f'ci_{key}'])}" if want_ci else ""
+                f.write(f"In {name}: nodes={d['nodes']} pairs={d['pairs']} AUC of pairs={d['auc']} "
+                        f"jackknife AUC={d['auc_jackknife']} se_nodes={d['se']} "
+                        f"{int(round(100 * d['level']))}% CI_nodes=[{d['ci_low']}, {d['ci_high']}] "
+                        f"undefined_nodes={d['undefined_nodes']}{ratio}\n")
+                if other is not None:
+                    d = res[f"versus_nodes_{key}"]
+                    f.write(f"In {name}: versus {versus} (nodes): AUC={d['b']['auc']} delta={d['delta']} se_nodes={d['se_delta']} "
                             f"z={d['z']} p={d['p_value']}\n")
         f.write(f"current density: {res['density']}\n")
     return res
