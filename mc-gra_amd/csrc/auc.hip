@@ -3,13 +3,13 @@
 // submatrix.  AUC = U / (P N) with 2U = sum over positives of (2 #negatives with a lower score + #negatives with an equal
 // score) (Mann-Whitney, ties counted 1/2), which is exactly the area under the step curve roc_curve draws.
 //
-// Passes (DESIGN.md "Recovered-adjacency AUC"; k_auc_index and the k_auc_digit_* sort live in rank_common.h, shared with topk.hip):
-//   k_auc_index        idx only: range check, repeats; a repeat-free idx of all n nodes is the whole matrix in another
+// Passes (DESIGN.md "Recovered-adjacency AUC"; the idx check and the sort are rank_common.hip's, shared with the whole family):
+//   rank_check_idx     idx only: range check, repeats; a repeat-free idx of all n nodes is the whole matrix in another
 //                      order (the AUC depends on the multiset of (label, score) pairs only) and runs as idx = NULL
 //   k_auc_classify     one read of the selected scores and labels: argument checks, per-block positive / negative counts
 //   k_auc_emit         a second read: each entry's order-preserving 32-bit key, positives to one region of the
 //                      scratch, negatives to another, at per-block offsets (the host's scan of the counts)
-//   k_auc_digit_*      per region, a stable LSD radix sort of the keys: 4 passes of 8 bits, each a per-block digit
+//   auc_sort           per region, a stable LSD radix sort of the keys: 4 passes of 8 bits, each a per-block digit
 //                      count, one scan of the (digit, block) counts and a stable scatter
 //   k_auc_pairs        each key of the smaller class looks up its lower and upper bound in the sorted larger class;
 //                      the sum of the two is that key's share of 2U
@@ -20,8 +20,9 @@
 //                      its passes are in curves.hip
 // mcgra_decode_auc ranks scores that are never stored, s_ij = dot_product_decode2(Z)_ij of a thin factor Z [n x d]:
 //   k_dec_rows         every row of Z: NaN / inf check, the L2-normalised copy of modes 1 and 4
-//   k_dec_classify     k_auc_classify on the scores dec_for_each decodes, a block owning 64 x 64 tiles of idx x idx
-//   k_dec_emit         k_auc_emit on the same scores; the sort and k_auc_pairs follow unchanged
+//   k_dec_classify     k_auc_classify's body (auc_classify_one) on the scores dec_for_each decodes, a block owning 64 x 64
+//                      tiles of idx x idx
+//   k_dec_emit         k_auc_emit's body (auc_emit_one) on the same scores; the sort and k_auc_pairs follow unchanged
 //   k_dec_scores       the same scores written out (mcgra_decode_scores: the materialised route)
 // Counts and 2U are 64-bit integers merged with global integer atomics, so the result does not depend on the order in
 // which blocks run; the one rounding is the final division (host, exact integer long division, nearest even).
@@ -46,7 +47,7 @@
 
 #include "../../include/mcgra.h"
 #include "common.h"
-#include "rank_common.h"      // the keys, the idx check, the block sums and the radix sort (shared with topk.hip)
+#include "rank_common.h"      // the keys, the checks, the block sums, the bound and the radix sort
 #include "curves.h"           // the third consumer of the sorted regions (curves.hip: mcgra_rank_curves)
 
 namespace mcgra {
@@ -103,6 +104,42 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   __syncthreads();
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
+
+// one selected entry of the classify pass: the argument checks and the counts of positives and of all entries
+__device__ __forceinline__ void auc_classify_one(float s, float l, uint32_t& pos, uint32_t& tot, int& f) {
+  if (!auc_finite(s)) f |= AUC_BAD_SCORE;
+  if (auc_pos(l)) ++pos;
+  else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+  ++tot;
+}
+// what the classify pass leaves: counts[2 b] / counts[2 b + 1] = positives / negatives of block b, flags |= f
+__device__ __forceinline__ void auc_classify_end(uint32_t pos, uint32_t tot, int f, uint64_t* sh, uint64_t* __restrict__ counts,
+                                                 int* __restrict__ flags) {
+  if (f) atomicOr(flags, f);
+  const uint64_t p = block_sum_u64(pos, sh);
+  __syncthreads();
+  const uint64_t t = block_sum_u64(tot, sh);
+  if (threadIdx.x == 0) { counts[2 * blockIdx.x] = p; counts[2 * blockIdx.x + 1] = t - p; }
+}
+// one selected entry of the emit pass: its key behind the block's positives (cur[0]) or negatives (cur[1]) so far.  Not two
+// calls of wave_slot: every lane takes a slot here, and one leader that advances both cursors in one go keeps the two LDS
+// round trips of a step overlapped, as they were.
+__device__ __forceinline__ void auc_emit_one(float s, float l, uint64_t o_pos, uint64_t o_neg, uint32_t* cur,
+                                             uint32_t* __restrict__ keys) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const bool p = auc_pos(l);
+  const uint64_t act = __ballot(1), mp = __ballot(p);
+  const int leader = __ffsll((unsigned long long)act) - 1;
+  uint32_t bp = 0, bn = 0;
+  if (lane == leader) {
+    bp = atomicAdd(&cur[0], (uint32_t)__popcll(mp));
+    bn = atomicAdd(&cur[1], (uint32_t)__popcll(act & ~mp));
+  }
+  bp = __shfl(bp, leader, 64);
+  bn = __shfl(bn, leader, 64);
+  keys[p ? o_pos + bp + __popcll(mp & below) : o_neg + bn + __popcll(act & ~mp & below)] = auc_key(s);
+}
 }  // namespace
 
 // counts[2 b] / counts[2 b + 1] = positives / negatives block b selects; flags |= the argument errors it meets
@@ -113,17 +150,8 @@ __global__ __launch_bounds__(AUC_THREADS) void k_auc_classify(int rows, const fl
   __shared__ uint64_t sh[AUC_THREADS / 64];
   uint32_t pos = 0, tot = 0;
   int f = 0;
-  auc_for_each(rows, S, lds, L, ldl, idx, [&](float s, float l) {
-    if (!auc_finite(s)) f |= AUC_BAD_SCORE;
-    if (auc_pos(l)) ++pos;
-    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-    ++tot;
-  });
-  if (f) atomicOr(flags, f);
-  const uint64_t p = block_sum_u64(pos, sh);
-  __syncthreads();
-  const uint64_t t = block_sum_u64(tot, sh);
-  if (threadIdx.x == 0) { counts[2 * blockIdx.x] = p; counts[2 * blockIdx.x + 1] = t - p; }
+  auc_for_each(rows, S, lds, L, ldl, idx, [&](float s, float l) { auc_classify_one(s, l, pos, tot, f); });
+  auc_classify_end(pos, tot, f, sh, counts, flags);
 }
 
 // keys of block b's positives to keys[offs[2 b] ..), of its negatives to keys[offs[2 b + 1] ..) (any order inside a block)
@@ -135,22 +163,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_auc_emit(int rows, const float*
   if (threadIdx.x < 2) cur[threadIdx.x] = 0;
   __syncthreads();
   const uint64_t o_pos = offs[2 * blockIdx.x], o_neg = offs[2 * blockIdx.x + 1];
-  const int lane = threadIdx.x & 63;
-  const uint64_t below = (1ull << lane) - 1ull;
-  auc_for_each(rows, S, lds, L, ldl, idx, [&](float s, float l) {
-    const bool p = auc_pos(l);
-    const uint64_t act = __ballot(1), mp = __ballot(p);
-    const int leader = __ffsll((unsigned long long)act) - 1;
-    uint32_t bp = 0, bn = 0;
-    if (lane == leader) {
-      bp = atomicAdd(&cur[0], (uint32_t)__popcll(mp));
-      bn = atomicAdd(&cur[1], (uint32_t)__popcll(act & ~mp));
-    }
-    bp = __shfl(bp, leader, 64);
-    bn = __shfl(bn, leader, 64);
-    const uint64_t at = p ? o_pos + bp + __popcll(mp & below) : o_neg + bn + __popcll(act & ~mp & below);
-    keys[at] = auc_key(s);
-  });
+  auc_for_each(rows, S, lds, L, ldl, idx, [&](float s, float l) { auc_emit_one(s, l, o_pos, o_neg, cur, keys); });
 }
 
 // acc += for each key x of A: lower_bound(B, x) + upper_bound(B, x) (a_pos: A holds the positives), or, A holding the
@@ -162,12 +175,8 @@ __global__ __launch_bounds__(AUC_THREADS) void k_auc_pairs(const uint32_t* __res
   uint64_t s = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < na; i += (uint64_t)gridDim.x * AUC_THREADS) {
     const uint32_t x = A[i];
-    uint64_t lo = 0, hi = nbk;                      // first key >= x
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (B[m] < x) lo = m + 1; else hi = m; }
-    const uint64_t lt = lo;
-    hi = nbk;                                       // first key > x
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (B[m] <= x) lo = m + 1; else hi = m; }
-    const uint64_t le = lo;
+    const uint64_t lt = rank_bound<false>(B, (uint64_t)0, nbk, x);       // first key >= x
+    const uint64_t le = rank_bound<true>(B, lt, nbk, x);                 // first key > x
     s += a_pos ? lt + le : (nbk - le) + (nbk - lt);
   }
   const uint64_t tot = block_sum_u64(s, sh);
@@ -184,12 +193,8 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ap_terms(const uint32_t* __rest
   double s = 0.0;
   for (uint64_t i = (uint64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < np; i += (uint64_t)gridDim.x * AUC_THREADS) {
     const uint32_t x = Pk[i];
-    uint64_t lo = 0, hi = i;                        // first positive >= x: Pk[i] == x, so it is at or before i
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (Pk[m] < x) lo = m + 1; else hi = m; }
-    const uint64_t tp = np - lo;
-    lo = 0; hi = nn;                                // first negative >= x
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (Nk[m] < x) lo = m + 1; else hi = m; }
-    const uint64_t fp = nn - lo;
+    const uint64_t tp = np - rank_bound<false>(Pk, (uint64_t)0, i, x);    // first positive >= x: Pk[i] == x, so at or before i
+    const uint64_t fp = nn - rank_bound<false>(Nk, (uint64_t)0, nn, x);   // first negative >= x
     s += (double)tp / (double)(tp + fp);            // tp + fp < 2^33: both conversions exact, one rounding
   }
   const double tot = block_sum_f64(s, sh);
@@ -310,17 +315,9 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dec_classify(int rows, int d, c
   __shared__ uint64_t red[AUC_THREADS / 64];
   uint32_t pos = 0, tot = 0;
   int f = 0;
-  dec_for_each(rows, d, Z, ldz, sig != 0, L, ldl, idx, sh, [&](int64_t, int64_t, float s, float l) {
-    if (!auc_finite(s)) f |= AUC_BAD_SCORE;
-    if (auc_pos(l)) ++pos;
-    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;
-    ++tot;
-  });
-  if (f) atomicOr(flags, f);
-  const uint64_t p = block_sum_u64(pos, red);
-  __syncthreads();
-  const uint64_t n = block_sum_u64(tot, red);
-  if (threadIdx.x == 0) { counts[2 * blockIdx.x] = p; counts[2 * blockIdx.x + 1] = n - p; }
+  dec_for_each(rows, d, Z, ldz, sig != 0, L, ldl, idx, sh,
+               [&](int64_t, int64_t, float s, float l) { auc_classify_one(s, l, pos, tot, f); });
+  auc_classify_end(pos, tot, f, red, counts, flags);
 }
 
 __global__ __launch_bounds__(AUC_THREADS) void k_dec_emit(int rows, int d, const float* __restrict__ Z, int64_t ldz, int sig,
@@ -331,22 +328,8 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dec_emit(int rows, int d, const
   __shared__ uint32_t cur[2];
   if (threadIdx.x < 2) cur[threadIdx.x] = 0;
   const uint64_t o_pos = offs[2 * blockIdx.x], o_neg = offs[2 * blockIdx.x + 1];
-  const int lane = threadIdx.x & 63;
-  const uint64_t below = (1ull << lane) - 1ull;
-  dec_for_each(rows, d, Z, ldz, sig != 0, L, ldl, idx, sh, [&](int64_t, int64_t, float s, float l) {
-    const bool p = auc_pos(l);
-    const uint64_t act = __ballot(1), mp = __ballot(p);
-    const int leader = __ffsll((unsigned long long)act) - 1;
-    uint32_t bp = 0, bn = 0;
-    if (lane == leader) {
-      bp = atomicAdd(&cur[0], (uint32_t)__popcll(mp));
-      bn = atomicAdd(&cur[1], (uint32_t)__popcll(act & ~mp));
-    }
-    bp = __shfl(bp, leader, 64);
-    bn = __shfl(bn, leader, 64);
-    const uint64_t at = p ? o_pos + bp + __popcll(mp & below) : o_neg + bn + __popcll(act & ~mp & below);
-    keys[at] = auc_key(s);
-  });
+  dec_for_each(rows, d, Z, ldz, sig != 0, L, ldl, idx, sh,
+               [&](int64_t, int64_t, float s, float l) { auc_emit_one(s, l, o_pos, o_neg, cur, keys); });
 }
 
 // out[i][j] = s_ij for all nodes: the materialised route
@@ -388,24 +371,16 @@ struct AucRun {
     flags = b.get<int>(1);
     counts = b.get<uint64_t>(2 * AUC_ROW_BLOCKS);
     acc = b.get<unsigned long long>(1);
-    if (!flags || !counts || !acc) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
+    if (!flags || !counts || !acc) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
     MCGRA_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
     MCGRA_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long), st));
     return 0;
   }
   // idx != NULL: range check and repeats; a permutation of all nodes becomes idx = NULL (the same multiset)
   int select(int n, const int64_t*& idx, int64_t n_idx) {
-    if (!idx) return 0;
-    uint32_t* seen = b.get<uint32_t>(n);
-    if (!seen) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-    const int g = (int)std::min<int64_t>(1024, (n_idx + AUC_THREADS - 1) / AUC_THREADS);
-    k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, n_idx, idx, seen, flags);
-    MCGRA_KERNEL_CHECK();
-    MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (h_flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
-    if (!(h_flags & AUC_REPEAT) && n_idx == n) idx = nullptr;
+    bool repeated = false;
+    if (int rc = rank_check_idx(who, st, b, n, idx, n_idx, flags, true, &repeated)) return rc;
+    if (!repeated && n_idx == n) idx = nullptr;
     return 0;
   }
   // Behind the classify pass of g blocks: its counts and flags, the per-block offsets, the emit pass (emit(offs, keys)
@@ -418,15 +393,7 @@ struct AucRun {
     MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipStreamSynchronize(st));
-    if (h_flags & AUC_BAD_FACTOR) {
-      set_error("%s: an entry of Z is NaN or infinite", who);
-      return MCGRA_EINVAL;
-    }
-    if (h_flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-      set_error("%s: %s%s", who, (h_flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite (sklearn: ValueError) " : "",
-                (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1 (sklearn: ValueError)" : "");
-      return MCGRA_EINVAL;
-    }
+    if (int rc = rank_flag_error(who, h_flags)) return rc;     // (sklearn raises ValueError for each of them)
     uint64_t P = 0, N = 0;
     for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
     if ((P == 0 || N == 0) && !cv) {
@@ -490,16 +457,8 @@ namespace {
 // for whatever is asked for
 int rank_matrix(const char* who, void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                 const int64_t* idx, int64_t n_idx, double* auc, double* ap, const CurveRequest* cv = nullptr) {
-  if (n < 1 || !labels || !scores || (!auc && !ap && !cv) || ld_labels < n || ld_scores < n || (idx && n_idx < 1)) {
-    set_error("%s: bad argument", who);
-    return MCGRA_EINVAL;
-  }
-  if (!idx) n_idx = n;
-  if (n_idx > AUC_MAX_NIDX) {
-    set_error("%s: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", who, (long long)n_idx,
-              (long long)AUC_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
+  if (!auc && !ap && !cv) { set_error("%s: bad argument (nothing to compute)", who); return MCGRA_EINVAL; }
+  if (int rc = rank_check_args(who, n, {{labels, ld_labels, true}, {scores, ld_scores, true}}, idx, n_idx, 1)) return rc;
   AucRun run{who, (hipStream_t)stream};
   hipStream_t st = run.st;
   if (int rc = run.begin()) return rc;
@@ -552,7 +511,7 @@ int dec_prepare(const char* who, AucRun& run, int n, int d, const float*& Z, int
   float* Zn = nullptr;
   if (mode == 1 || mode == 4) {
     Zn = run.b.get<float>((size_t)n * d);
-    if (!Zn) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
+    if (!Zn) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
   }
   k_dec_rows<<<std::min((n + 3) / 4, 1024), AUC_THREADS, 0, run.st>>>(n, d, Z, ldz, Zn, run.flags);
   MCGRA_KERNEL_CHECK();
@@ -567,16 +526,11 @@ namespace {
 // mcgra_decode_auc (ap == NULL) and mcgra_decode_rank_metrics
 int rank_decoded(const char* who, void* stream, int n, int d, const float* Z, int ldz, int mode, const float* labels,
                  int ld_labels, const int64_t* idx, int64_t n_idx, double* auc, double* ap) {
-  if (n < 1 || d < 1 || !Z || ldz < d || !labels || (!auc && !ap) || ld_labels < n || (idx && n_idx < 1)) {
-    set_error("%s: bad argument", who);
+  if (d < 1 || !Z || ldz < d || (!auc && !ap)) {
+    set_error("%s: bad argument (Z [n x d], ldz >= d, something to compute)", who);
     return MCGRA_EINVAL;
   }
-  if (!idx) n_idx = n;
-  if (n_idx > AUC_MAX_NIDX) {
-    set_error("%s: %lld selected nodes; 2 P N of more than %lld does not fit 64 bits", who, (long long)n_idx,
-              (long long)AUC_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
+  if (int rc = rank_check_args(who, n, {{labels, ld_labels, true}}, idx, n_idx, 1)) return rc;
   if (d > DEC_MAX_D) {
     set_error("%s: a factor of %d columns (at most %d; mcgra_decode_scores + mcgra_roc_auc / mcgra_rank_metrics take any width)",
               who, d, DEC_MAX_D);
@@ -619,6 +573,5 @@ extern "C" int mcgra_decode_scores(void* stream, int n, int d, const float* Z, i
   MCGRA_KERNEL_CHECK();
   MCGRA_HIP(hipMemcpyAsync(&run.h_flags, run.flags, sizeof(int), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipStreamSynchronize(st));     // also: the normalised copy is freed on return
-  if (run.h_flags & AUC_BAD_FACTOR) { set_error("decode_scores: an entry of Z is NaN or infinite"); return MCGRA_EINVAL; }
-  return 0;
+  return rank_flag_error(run.who, run.h_flags);
 }

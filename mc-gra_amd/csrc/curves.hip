@@ -10,9 +10,9 @@
 // Passes:
 //   k_cv_head_count    per contiguous tile of a region: its level heads.  A head of A is the first key of a run of equal keys;
 //                      a head of B is such a key that A does not hold (one lower bound in A), so every level has one head
-//   k_auc_digit_scan   one block scans the per-tile counts (rank_common.h); entry nb of the scan is the region's total
-//   k_cv_head_cum      cum[i] = heads of the region at indices < i (the tile's offset, then ballots and per-wave counts in
-//                      index order), into the sort's second key buffer, which is free after the sorts
+//   rank_scan          one block scans the per-tile counts (rank_common.hip); entry nb of the scan is the region's total
+//   k_cv_head_cum      cum[i] = heads of the region at indices < i (the tile's offset, then block_rank in index order),
+//                      into the sort's second key buffer, which is free after the sorts
 //   k_cv_levels        every head: one lower bound lb in the other region; its ascending rank among the levels is
 //                      cum_own[i] + cum_other[lb], its counts are (n_own - i, n_other - lb); it writes (tp, fp, key) at
 //                      l = levels - 1 - rank.  Each level is written exactly once
@@ -46,9 +46,7 @@ constexpr int CV_GRID = 4096;              // blocks of the grid-stride pass ove
 
 // first index of R[0, n) whose key is >= x
 __device__ __forceinline__ uint64_t cv_lower(const uint32_t* __restrict__ R, uint64_t n, uint32_t x) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (R[m] < x) lo = m + 1; else hi = m; }
-  return lo;
+  return rank_bound<false>(R, (uint64_t)0, n, x);
 }
 
 // R[i] heads a level: the first key of its run and, EXCL, a key the other region O does not hold
@@ -64,24 +62,6 @@ __device__ __forceinline__ bool cv_head(const uint32_t* __restrict__ R, uint64_t
 // the score of a key (auc_key inverted; the key of -0.0 and +0.0 gives +0.0)
 __device__ __forceinline__ float cv_score(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-// One step of a block's ranking in index order: `before` = flagged lanes below this one in the block, `all` = flagged lanes
-// of the block.  Every lane of the block calls it; w[par] holds the step's per-wave counts (par alternates, so one barrier
-// a step is enough: a wave reaches the step after next only once every wave has read this one).
-struct CvRank { uint32_t before, all; };
-__device__ __forceinline__ CvRank cv_block_rank(bool f, uint32_t (*w)[AUC_THREADS / 64], int par) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint64_t m = __ballot(f);
-  if (lane == 0) w[par][wv] = (uint32_t)__popcll(m);
-  __syncthreads();
-  CvRank r{(uint32_t)__popcll(m & ((1ull << lane) - 1ull)), 0u};
-#pragma unroll
-  for (int q = 0; q < AUC_THREADS / 64; ++q) {
-    if (q < wv) r.before += w[par][q];
-    r.all += w[par][q];
-  }
-  return r;
 }
 
 // roc_curve's and precision_recall_curve's keep rules at level l of L (drop: drop_intermediate and L > 2)
@@ -151,7 +131,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_cv_head_cum(const uint32_t* __r
     const uint64_t e = base + threadIdx.x;
     const bool valid = e < end;
     const bool f = valid && cv_head<EXCL>(R, e, O, no);
-    const CvRank r = cv_block_rank(f, w, par);
+    const BlockRank r = block_rank(f, w, par);
     if (valid) cum[e] = (uint32_t)(run + r.before);
     run += r.all;
   }
@@ -248,27 +228,18 @@ __global__ __launch_bounds__(AUC_THREADS) void k_cv_write(uint64_t L, const uint
     const float thr = valid ? cv_score(lkey[l]) : 0.f;
     if (roc_tps) {                                    // (the same in every lane)
       const bool k = valid && cv_keep_roc(ltp, lfp, L, l, drop != 0);
-      const CvRank r = cv_block_rank(k, wr, par);
+      const BlockRank r = block_rank(k, wr, par);
       if (k) { const uint64_t at = run_r + r.before; roc_tps[at] = tp; roc_fps[at] = fp; roc_thr[at] = thr; }
       run_r += r.all;
     }
     if (pr_tps) {
       const bool k = valid && cv_keep_pr(ltp, L, l, drop != 0);
-      const CvRank r = cv_block_rank(k, wp, par);
+      const BlockRank r = block_rank(k, wp, par);
       if (k) { const uint64_t at = run_p + r.before; pr_tps[at] = tp; pr_fps[at] = fp; pr_thr[at] = thr; }
       run_p += r.all;
     }
   }
 }
-
-namespace {
-// contiguous tiles of `count` items: a multiple of AUC_THREADS each, at most CV_BLOCKS of them
-void cv_tiles(uint64_t count, uint64_t& tile, int& nb) {
-  tile = (count + CV_BLOCKS - 1) / CV_BLOCKS;
-  tile = std::max<uint64_t>(1, (tile + AUC_THREADS - 1) / AUC_THREADS) * AUC_THREADS;
-  nb = (int)((count + tile - 1) / tile);
-}
-}  // namespace
 
 int rank_curves_sorted(const char* who, hipStream_t st, const uint32_t* keys, uint32_t* tmp, uint64_t P, uint64_t nbase,
                        uint64_t N, const CurveRequest& rq) {
@@ -286,17 +257,15 @@ int rank_curves_sorted(const char* who, hipStream_t st, const uint32_t* keys, ui
   uint64_t* res = b.get<uint64_t>(4);
   if (!cnt || !off || !res) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
 
-  uint64_t tile_a, tile_b = AUC_THREADS;
-  int nb_a, nb_b = 0;
-  cv_tiles(na, tile_a, nb_a);
+  const auto [tile_a, nb_a] = rank_tiles(na, CV_BLOCKS, AUC_THREADS);
+  const auto [tile_b, nb_b] = rank_tiles(nbk, CV_BLOCKS, AUC_THREADS);       // no blocks when B is empty
   k_cv_head_count<false><<<nb_a, AUC_THREADS, 0, st>>>(A, na, B, nbk, tile_a, nb_a, cnt);
-  k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt, nb_a + 1, off);
+  rank_scan(st, cnt, nb_a + 1, off);
   uint64_t heads_a = 0, heads_b = 0;
   MCGRA_HIP(hipMemcpyAsync(&heads_a, off + nb_a, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (nbk) {
-    cv_tiles(nbk, tile_b, nb_b);
     k_cv_head_count<true><<<nb_b, AUC_THREADS, 0, st>>>(B, nbk, A, na, tile_b, nb_b, cnt + stride);
-    k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt + stride, nb_b + 1, off + stride);
+    rank_scan(st, cnt + stride, nb_b + 1, off + stride);
     MCGRA_HIP(hipMemcpyAsync(&heads_b, off + stride + nb_b, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   }
   MCGRA_KERNEL_CHECK();
@@ -307,9 +276,7 @@ int rank_curves_sorted(const char* who, hipStream_t st, const uint32_t* keys, ui
   uint32_t* ltp = b.get<uint32_t>(L);
   uint32_t* lfp = b.get<uint32_t>(L);
   uint32_t* lkey = b.get<uint32_t>(L);
-  uint64_t tile_l;
-  int nb_l;
-  cv_tiles(L, tile_l, nb_l);
+  const auto [tile_l, nb_l] = rank_tiles(L, CV_BLOCKS, AUC_THREADS);
   uint64_t* bb = b.get<uint64_t>(3 * (size_t)nb_l);
   if (!ltp || !lfp || !lkey || !bb) { set_error("%s: hipMalloc of %llu levels failed", who, (unsigned long long)L); return MCGRA_ENOMEM; }
   k_cv_head_cum<false><<<nb_a, AUC_THREADS, 0, st>>>(A, na, B, nbk, tile_a, off, cumA);
@@ -324,8 +291,8 @@ int rank_curves_sorted(const char* who, hipStream_t st, const uint32_t* keys, ui
 
   const int drop = (rq.drop_intermediate && L > 2) ? 1 : 0;
   k_cv_keep_count<<<nb_l, AUC_THREADS, 0, st>>>(L, ltp, lfp, drop, tile_l, nb_l, P, cnt, cnt + stride, bb);
-  k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt, nb_l + 1, off);
-  k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt + stride, nb_l + 1, off + stride);
+  rank_scan(st, cnt, nb_l + 1, off);
+  rank_scan(st, cnt + stride, nb_l + 1, off + stride);
   uint64_t kept_roc = 0, kept_pr = 0, h_res[4] = {0, 0, 0, 0};
   MCGRA_HIP(hipMemcpyAsync(&kept_roc, off + nb_l, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipMemcpyAsync(&kept_pr, off + stride + nb_l, sizeof(uint64_t), hipMemcpyDeviceToHost, st));

@@ -19,9 +19,9 @@
 //
 // Only the POSITIVES are stored and sorted (a graph has few edges among its pairs); the negatives are streamed from the
 // matrices and never stored.  Passes:
-//   k_auc_index        idx only: range check, repeats (rank_common.h)
-//   k_dl_classify      one read of the selected lower triangle: the argument checks (both score matrices), per-block positive
-//                      counts
+//   rank_check_idx     idx only: range check, repeats (rank_common.hip)
+//   k_dl_classify      (delong_common.h, as k_dl_emit) one read of the selected lower triangle: the argument checks (both
+//                      score matrices), per-block positive counts
 //   k_dl_emit          a second read of the labels: each positive's key (paired: of both matrices) to its slot, at per-block
 //                      offsets (the host's scan of the counts).  Which slot of its block's range a positive takes depends on
 //                      the order the waves run in; every result below is a sum over slots, which no such order changes.  The
@@ -32,7 +32,7 @@
 //                      stretch between two samples -- and that is its placement, b = 2 P - lb - ub, for both scorings at once:
 //                      sum b, the halves of b^2 and of b^A b^B.  It also counts itself into hist[lb] and, when it ties a
 //                      positive, into ties[lb] (32-bit integer atomics; the lanes of a wave that share a bin add once)
-//   k_auc_digit_scan   the running sum of hist
+//   rank_scan          the running sum of hist
 //   k_dl_positives     every positive slot: l = the first sorted position of its own key; the negatives at or below it are
 //                      cum = hist[0] + ... + hist[l], those equal to it ties[l], so a = 2 cum - ties[l]; sum a, the halves of
 //                      a^2 and of a^A a^B
@@ -43,7 +43,7 @@
 // Device scratch: 24 bytes per POSITIVE and scoring (its key by slot, the sorted copy, hist, ties and the 8-byte running sum)
 // plus 4 for the sort's second buffer, about 3 MB for the sort's counts, and 4 bytes per node of the graph when idx is given:
 // nothing per candidate.
-// DlSide, the searches, the histogram add, the two placements and the device-free checks are in delong_common.h, which
+// DlSide, the searches, the histogram add, the two placements and the positives' stage are in delong_common.h, which
 // node_jackknife.hip shares.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -64,77 +64,6 @@ constexpr int DL_POS_BLOCKS = 2048;        // at most this many blocks of the pa
 // slots of the accumulators, per class
 enum { DL_T_A = 0, DL_T_B, DL_SQ_A_LO, DL_SQ_A_HI, DL_SQ_B_LO, DL_SQ_B_HI, DL_X_LO, DL_X_HI, DL_ACC };
 
-// rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection; f(score_a, score_b, label) for every pair (a, b), b < a
-template <class F>
-__device__ __forceinline__ void dl_for_each(int rows, const float* __restrict__ SA, int64_t lda, const float* __restrict__ SB,
-                                            int64_t ldb, const float* __restrict__ L, int64_t ldl,
-                                            const int64_t* __restrict__ idx, F&& f) {
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* arow = SA + u * lda;
-    const float* brow = SB ? SB + u * ldb : nullptr;
-    const float* lrow = L + u * ldl;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const int64_t v = idx ? idx[b] : b;
-      f(arow[v], brow ? brow[v] : 0.f, lrow[v]);
-    }
-  }
-}
-
-// counts[b] = positives of block b's rows; flags |= the argument errors it meets
-__global__ __launch_bounds__(AUC_THREADS) void k_dl_classify(int rows, const float* __restrict__ SA, int64_t lda,
-                                                             const float* __restrict__ SB, int64_t ldb,
-                                                             const float* __restrict__ L, int64_t ldl,
-                                                             const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
-                                                             int* __restrict__ flags) {
-  __shared__ uint64_t sh[AUC_THREADS / 64];
-  uint32_t pos = 0;
-  int f = 0;
-  dl_for_each(rows, SA, lda, SB, ldb, L, ldl, idx, [&](float sa, float sb, float l) {
-    if (!auc_finite(sa)) f |= AUC_BAD_SCORE;
-    if (!auc_finite(sb)) f |= DL_BAD_SCORE_B;
-    if (auc_pos(l)) ++pos;
-    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-  });
-  if (f) atomicOr(flags, f);
-  const uint64_t p = block_sum_u64(pos, sh);
-  if (threadIdx.x == 0) counts[blockIdx.x] = p;
-}
-
-// block b's positives take the slots offs[b] .. (any order inside a block): ka[slot] = key of the pair's score in SA, kb[slot]
-// (SB != NULL) = key of its score in SB
-__global__ __launch_bounds__(AUC_THREADS) void k_dl_emit(int rows, const float* __restrict__ SA, int64_t lda,
-                                                         const float* __restrict__ SB, int64_t ldb,
-                                                         const float* __restrict__ L, int64_t ldl,
-                                                         const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
-                                                         uint32_t* __restrict__ ka, uint32_t* __restrict__ kb) {
-  __shared__ uint32_t cur;
-  if (threadIdx.x == 0) cur = 0;
-  __syncthreads();
-  const uint64_t o_pos = offs[blockIdx.x];
-  const int lane = threadIdx.x & 63;
-  const uint64_t below = (1ull << lane) - 1ull;
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* lrow = L + u * ldl;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const int64_t v = idx ? idx[b] : b;
-      const bool p = auc_pos(lrow[v]);
-      const uint64_t mp = __ballot(p);
-      if (mp == 0) continue;                              // the same in every active lane
-      const int leader = __ffsll((unsigned long long)mp) - 1;
-      uint32_t bp = 0;
-      if (lane == leader) bp = atomicAdd(&cur, (uint32_t)__popcll(mp));
-      bp = __shfl(bp, leader, 64);
-      if (p) {
-        const uint64_t at = o_pos + bp + __popcll(mp & below);
-        ka[at] = auc_key(SA[u * lda + v]);
-        if (SB) kb[at] = auc_key(SB[u * ldb + v]);
-      }
-    }
-  }
-}
-
 // The negatives, streamed: acc[DL_T_A / _B] += b, acc[DL_SQ_*] += the halves of b^2, acc[DL_X_*] += the halves of b^A b^B
 // (sb.S != NULL), and the counts hist / ties of each scoring.
 __global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide sa, DlSide sb, const float* __restrict__ L,
@@ -150,8 +79,9 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide s
   }
   __syncthreads();
   uint64_t part[DL_ACC] = {};
-  dl_for_each(rows, sa.S, sa.ld, sb.S, sb.ld, L, ldl, idx, [&](float xa, float xb, float l) {
-    const bool neg = !auc_pos(l);                              // the labels were checked: 0 or 1
+  tri_for_each(rows, idx, [&](int, int, int64_t u, int64_t v) {
+    const float xa = sa.S[u * sa.ld + v], xb = paired ? sb.S[u * sb.ld + v] : 0.f;
+    const bool neg = !auc_pos(L[u * ldl + v]);                 // the labels were checked: 0 or 1
     const uint64_t ba = dl_negative(sa, np, smp_a, ns, stride, xa, neg);
     const uint64_t bb = paired ? dl_negative(sb, np, smp_b, ns, stride, xb, neg) : 0;
     if (neg) {
@@ -228,37 +158,13 @@ int dl_run(const char* who, hipStream_t st, int n, const float* L, int ldl, cons
   uint64_t* counts = (uint64_t*)(head + sizeof(Head));
   static_assert(sizeof(Head) % 8 == 0, "counts is 8-byte aligned");
   MCGRA_HIP(hipMemsetAsync(hd, 0, sizeof(Head), st));
-  int h_flags = 0;
-  if (idx) {
-    uint32_t* seen = b.get<uint32_t>(n);
-    if (!seen) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-    const int gi = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
-    k_auc_index<<<gi, AUC_THREADS, 0, st>>>(n, rows, idx, seen, &hd->flags);
-    MCGRA_KERNEL_CHECK();
-    MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (h_flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
-    if (h_flags & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
-  }
-  k_dl_classify<<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, &hd->flags);
+  if (int rc = rank_check_idx(who, st, b, n, idx, rows, &hd->flags)) return rc;
+  k_dl_classify<false><<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, nullptr, &hd->flags);
   MCGRA_KERNEL_CHECK();
-  std::vector<uint64_t> h(g);
-  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipStreamSynchronize(st));
-  if (h_flags & (AUC_BAD_SCORE | DL_BAD_SCORE_B | AUC_BAD_LABEL)) {
-    set_error("%s: %s%s%s", who,
-              (h_flags & AUC_BAD_SCORE) ? (paired ? "a selected score of scores_a is NaN or infinite " : "a selected score is NaN or infinite ") : "",
-              (h_flags & DL_BAD_SCORE_B) ? "a selected score of scores_b is NaN or infinite " : "",
-              (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
-    return MCGRA_EINVAL;
-  }
-  uint64_t P = 0;
-  for (int i = 0; i < g; ++i) { const uint64_t p = h[i]; h[i] = P; P += p; }        // counts -> offsets
-  r.m = (uint64_t)rows * (rows - 1) / 2;
-  r.P = P;
-  r.N = r.m - P;
+  std::vector<uint64_t> h;
+  if (int rc = dl_counted(who, st, counts, &hd->flags, g, paired, rows, h, r.P, r.N)) return rc;
+  const uint64_t P = r.P;
+  r.m = P + r.N;
   if (P == 0 || r.N == 0) return 0;                    // every placement is 0
   // one allocation for what scales with P: per scoring slot [P4], sorted [P4], hist [P4 + 4], ties [P4 + 4], cum [P4 + 4];
   // then the sort's second buffer [P4] and its counts.  P4 = P rounded up to 4 keys: every array starts on 16 bytes.
@@ -283,7 +189,7 @@ int dl_run(const char* who, hipStream_t st, int n, const float* L, int ldl, cons
   uint32_t* cnt = (uint32_t*)at;      at += sizeof(uint32_t) * sort_cnt;
   uint32_t* tmp = (uint32_t*)at;
   MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-  k_dl_emit<<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, side[0].slot, side[1].slot);
+  k_dl_emit<false><<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, side[0].slot, side[1].slot);
   MCGRA_KERNEL_CHECK();
   for (int s = 0; s < sides; ++s) {
     MCGRA_HIP(hipMemcpyAsync(side[s].sorted, side[s].slot, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, st));
@@ -292,7 +198,7 @@ int dl_run(const char* who, hipStream_t st, int n, const float* L, int ldl, cons
   }
   k_dl_negatives<<<g, AUC_THREADS, 0, st>>>(rows, side[0], side[1], L, ldl, idx, (uint32_t)P, hd->acc[1]);
   MCGRA_KERNEL_CHECK();
-  for (int s = 0; s < sides; ++s) k_auc_digit_scan<<<1, 1024, 0, st>>>(side[s].hist, (int)P, side[s].cum);
+  for (int s = 0; s < sides; ++s) rank_scan(st, side[s].hist, (int)P, side[s].cum);
   const int gp = (int)std::min<uint64_t>(DL_POS_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
   k_dl_positives<<<gp, AUC_THREADS, 0, st>>>(side[0], side[1], (uint32_t)P, hd->acc[0]);
   MCGRA_KERNEL_CHECK();
@@ -322,7 +228,8 @@ using namespace mcgra;
 
 extern "C" int mcgra_auc_delong(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                                 const int64_t* idx, int64_t n_idx, uint64_t* out) {
-  if (int rc = dl_check("auc_delong", n, labels, ld_labels, scores, ld_scores, nullptr, 0, false, idx, n_idx, out)) return rc;
+  if (!out) { set_error("auc_delong: bad argument (out NULL)"); return MCGRA_EINVAL; }
+  if (int rc = rank_check_args("auc_delong", n, {{labels, ld_labels, true}, {scores, ld_scores, true}}, idx, n_idx, 2)) return rc;
   DlResult r;
   if (int rc = dl_run("auc_delong", (hipStream_t)stream, n, labels, ld_labels, scores, ld_scores, nullptr, 0, idx, (int)n_idx, r))
     return rc;
@@ -333,7 +240,10 @@ extern "C" int mcgra_auc_delong(void* stream, int n, const float* labels, int ld
 
 extern "C" int mcgra_auc_delong_paired(void* stream, int n, const float* labels, int ld_labels, const float* scores_a, int ld_a,
                                        const float* scores_b, int ld_b, const int64_t* idx, int64_t n_idx, uint64_t* out) {
-  if (int rc = dl_check("auc_delong_paired", n, labels, ld_labels, scores_a, ld_a, scores_b, ld_b, true, idx, n_idx, out)) return rc;
+  if (!out) { set_error("auc_delong_paired: bad argument (out NULL)"); return MCGRA_EINVAL; }
+  if (int rc = rank_check_args("auc_delong_paired", n, {{labels, ld_labels, true}, {scores_a, ld_a, true}, {scores_b, ld_b, true}}, idx,
+                               n_idx, 2))
+    return rc;
   DlResult r;
   if (int rc = dl_run("auc_delong_paired", (hipStream_t)stream, n, labels, ld_labels, scores_a, ld_a, scores_b, ld_b, idx,
                       (int)n_idx, r))

@@ -1,14 +1,17 @@
 // What the placement entries share (delong.hip: DeLong's sums; node_jackknife.hip: the per-node sums): one scoring's device
 // arrays, the search of a negative among the sorted positives through samples staged in LDS, the wave-merged histogram add,
-// a negative's and a positive's placement, and the argument checks that need no device.  Integer work only.  Each
-// translation unit gets its own copy.
+// a negative's and a positive's placement, and the positives' stage -- k_dl_classify, the host's dl_counted behind it, and
+// k_dl_emit -- parameterised by what travels with a positive (NODES false, DeLong: the key of the second scoring, if there is
+// one; NODES true, the jackknife: the pair's endpoints a << 16 | b, and the count of positives per position).  Integer work
+// only.  Each of the two files instantiates its own variant of the two kernels.
 #pragma once
+#include <vector>
+
 #include "rank_common.h"
 
 namespace mcgra {
 namespace {
 constexpr int DL_STAGE = 4096;             // samples of the sorted positives a block of the negatives' pass keeps in LDS, per scoring
-enum { DL_BAD_SCORE_B = 32 };              // beside the AUC_BAD_* flags: the second score matrix
 
 // what one scoring's positives need on the device
 struct DlSide {
@@ -21,28 +24,16 @@ struct DlSide {
   uint64_t* cum;         // [P + 1] hist[0] + ... + hist[l - 1]
 };
 
-// first index in [lo, hi) of the ascending keys B whose key is >= x (UPPER: > x); hi when there is none
-template <bool UPPER, class Keys, class I>
-__device__ __forceinline__ I dl_bound(const Keys& B, I lo, I hi, uint32_t x) {
-  while (lo < hi) {
-    const I mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = B[mid];
-    if (UPPER ? k <= x : k < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// dl_bound over all np sorted positives S through the ns samples smp[q] = S[q stride]: the bound among the samples leaves one
+// rank_bound over all np sorted positives S through the ns samples smp[q] = S[q stride]: the bound among the samples leaves one
 // stretch between two samples.  c = first sample >= x (> x): every position up to (c - 1) stride is below (at or below) x and
 // position c stride is not, so the bound lies in ((c - 1) stride, c stride]; past the last sample it lies before np.
 template <bool UPPER>
 __device__ __forceinline__ uint32_t dl_find(const uint32_t* __restrict__ S, uint32_t np, const uint32_t* smp, uint32_t ns,
                                             uint32_t stride, uint32_t x) {
-  const uint32_t c = dl_bound<UPPER>(smp, 0u, ns, x);
+  const uint32_t c = rank_bound<UPPER>(smp, 0u, ns, x);
   if (c == 0) return 0;
   const uint32_t lo = (c - 1) * stride + 1, hi = c < ns ? c * stride : np;
-  return dl_bound<UPPER>(S, lo, hi, x);
+  return rank_bound<UPPER>(S, lo, hi, x);
 }
 
 // h[bin] += 1 for every lane with `on`.  The lanes of the wave that share one of its first DL_SHARED_BINS distinct bins add
@@ -81,23 +72,72 @@ __device__ __forceinline__ uint32_t dl_negative(const DlSide& s, uint32_t np, co
 
 // one scoring's share of the positive at `slot`: a = 2 (negatives at or below it) - (negatives equal to it)
 __device__ __forceinline__ uint64_t dl_positive(const DlSide& s, uint32_t np, uint64_t slot) {
-  const uint32_t l = dl_bound<false>(s.sorted, 0u, np, s.slot[slot]);      // its own key is there: l < np
+  const uint32_t l = rank_bound<false>(s.sorted, 0u, np, s.slot[slot]);      // its own key is there: l < np
   return 2 * (s.cum[l] + s.hist[l]) - s.ties[l];                          // <= 2 N < 2^32
 }
 
-// the argument checks that need no device
-inline int dl_check(const char* who, int n, const float* labels, int ld_labels, const float* sa, int ld_a, const float* sb,
-                    int ld_b, bool paired, const int64_t* idx, int64_t& n_idx, const void* out) {
-  if (!idx) n_idx = n;
-  if (n < 1 || !labels || !sa || (paired && !sb) || !out || ld_labels < n || ld_a < n || (paired && ld_b < n) || n_idx < 2) {
-    set_error("%s: bad argument (n >= 1, the matrices and out not NULL, every ld >= n, at least 2 selected nodes)", who);
-    return MCGRA_EINVAL;
-  }
-  if (n_idx > AUC_MAX_NIDX) {
-    set_error("%s: %lld selected nodes; a pair count of more than %lld nodes does not fit 31 bits", who, (long long)n_idx,
-              (long long)AUC_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
+// counts[b] = positives of block b's rows; flags |= the argument errors it meets (SB != NULL: of the second scoring too);
+// NODES: deg[v] = positives that contain position v
+template <bool NODES>
+__global__ __launch_bounds__(AUC_THREADS) void k_dl_classify(int rows, const float* __restrict__ SA, int64_t lda,
+                                                             const float* __restrict__ SB, int64_t ldb,
+                                                             const float* __restrict__ L, int64_t ldl,
+                                                             const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
+                                                             uint32_t* __restrict__ deg, int* __restrict__ flags) {
+  __shared__ uint64_t sh[AUC_THREADS / 64];
+  uint32_t pos = 0, mine = 0;                          // mine: this lane's positives of the row at hand
+  int f = 0;
+  tri_for_each(rows, idx, [&](int, int b, int64_t u, int64_t v) {
+    const float l = L[u * ldl + v];
+    if (!auc_finite(SA[u * lda + v])) f |= AUC_BAD_SCORE;
+    if (!NODES && SB && !auc_finite(SB[u * ldb + v])) f |= DL_BAD_SCORE_B;
+    if (auc_pos(l)) { ++mine; if (NODES) atomicAdd(&deg[b], 1u); }
+    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+  }, [&](int a) {
+    if (NODES && mine) atomicAdd(&deg[a], mine);
+    pos += mine;
+    mine = 0;
+  });
+  if (f) atomicOr(flags, f);
+  const uint64_t p = block_sum_u64(pos, sh);
+  if (threadIdx.x == 0) counts[blockIdx.x] = p;
+}
+
+// block b's positives take the slots offs[b] .. (any order inside a block): ka[slot] = key of the pair's score in SA;
+// second[slot] = NODES: its endpoints a << 16 | b; else (SB != NULL) the key of its score in SB
+template <bool NODES>
+__global__ __launch_bounds__(AUC_THREADS) void k_dl_emit(int rows, const float* __restrict__ SA, int64_t lda,
+                                                         const float* __restrict__ SB, int64_t ldb,
+                                                         const float* __restrict__ L, int64_t ldl,
+                                                         const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
+                                                         uint32_t* __restrict__ ka, uint32_t* __restrict__ second) {
+  __shared__ uint32_t cur;
+  if (threadIdx.x == 0) cur = 0;
+  __syncthreads();
+  const uint64_t o_pos = offs[blockIdx.x];
+  tri_for_each(rows, idx, [&](int a, int b, int64_t u, int64_t v) {
+    const bool p = auc_pos(L[u * ldl + v]);
+    const uint64_t at = o_pos + wave_slot(p, &cur);
+    if (!p) return;
+    ka[at] = auc_key(SA[u * lda + v]);
+    if (NODES) second[at] = (uint32_t)a << 16 | (uint32_t)b;
+    else if (SB) second[at] = auc_key(SB[u * ldb + v]);
+  });
+}
+
+// Behind the classify pass of g blocks: its counts and flags come back (one sync), a flagged argument is refused, h[b]
+// becomes the slots before block b, and P, N are the two classes of the rows (rows - 1) / 2 pairs.
+inline int dl_counted(const char* who, hipStream_t st, const uint64_t* counts, const int* flags, int g, bool paired, int rows,
+                      std::vector<uint64_t>& h, uint64_t& P, uint64_t& N) {
+  h.resize(g);
+  int h_flags = 0;
+  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));
+  if (int rc = rank_flag_error(who, h_flags, paired)) return rc;
+  P = 0;
+  for (int i = 0; i < g; ++i) { const uint64_t p = h[i]; h[i] = P; P += p; }        // counts -> offsets
+  N = (uint64_t)rows * (rows - 1) / 2 - P;
   return 0;
 }
 }  // namespace

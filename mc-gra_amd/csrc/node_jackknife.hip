@@ -14,11 +14,12 @@
 // Deleting v leaves T - A_v - B_v + C_v (C_v is in both sums), P - P_v positives and N - N_v negatives.
 //
 // Only the positives are stored, as in delong.hip; the negatives are streamed.  Passes:
-//   k_auc_index        idx only: range check, repeats (rank_common.h)
-//   k_nj_classify      one read of the selected lower triangle: the argument checks, per-block positive counts, and P_v
-//                      (deg[a] += 1, deg[b] += 1 per positive: 32-bit integer atomics)
-//   k_nj_emit          a second read of the labels: each positive's key and its endpoints a << 16 | b to a slot of its block's
-//                      range.  Which slot depends on the order the waves run in; the sort below ends that
+//   rank_check_idx     idx only: range check, repeats (rank_common.hip)
+//   k_dl_classify      (delong_common.h, NODES) one read of the selected lower triangle: the argument checks, per-block
+//                      positive counts, and P_v (deg[a] += 1, deg[b] += 1 per positive: 32-bit integer atomics)
+//   k_dl_emit          (delong_common.h, NODES) a second read of the labels: each positive's key and its endpoints
+//                      a << 16 | b to a slot of its block's range.  Which slot depends on the order the waves run in; the
+//                      sort below ends that
 //   auc_sort           the positives by key, the endpoints riding along.  Equal keys may keep either order of their endpoints:
 //                      everything below is a sum over the positives of one key
 //   k_nj_lists         every sorted positive i becomes two entries (node a, key) and (node b, key) at 2 i, 2 i + 1
@@ -31,7 +32,7 @@
 //                      through the columns in chunks of NJ_COLS; lane t alone meets the columns c0 + t, c0 + t + 256, ... of a
 //                      chunk in every row, so it keeps their sums in LDS without atomics and adds the non-zero ones to the
 //                      node's sum when the chunk ends: global 64-bit atomics per (block, node), not per pair
-//   k_auc_digit_scan   the running sum of hist
+//   rank_scan          the running sum of hist
 //   k_nj_positives     every sorted positive: a_p as in delong.hip, added to both endpoints' A (64-bit atomics, two per positive)
 //   k_nj_finish        P_v = deg[v], N_v = n_idx - 1 - deg[v]
 // Everything is integer counts merged by integer adds: no floating-point arithmetic on the device, the same bits on every
@@ -59,66 +60,6 @@ static_assert(NJ_COLS % AUC_THREADS == 0, "a lane owns the same columns of every
 static_assert(AUC_MAX_NIDX <= 0xffff, "a position fits 16 bits");
 enum { NJ_P = 0, NJ_N, NJ_A, NJ_B, NJ_C, NJ_WORDS };     // the columns of out
 
-// counts[b] = positives of block b's rows; deg[v] = positives that contain position v; flags |= the argument errors
-__global__ __launch_bounds__(AUC_THREADS) void k_nj_classify(int rows, const float* __restrict__ S, int64_t lds,
-                                                             const float* __restrict__ L, int64_t ldl,
-                                                             const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
-                                                             uint32_t* __restrict__ deg, int* __restrict__ flags) {
-  __shared__ uint64_t sh[AUC_THREADS / 64];
-  uint32_t pos = 0;
-  int f = 0;
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* srow = S + u * lds;
-    const float* lrow = L + u * ldl;
-    uint32_t mine = 0;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const int64_t v = idx ? idx[b] : b;
-      const float l = lrow[v];
-      if (!auc_finite(srow[v])) f |= AUC_BAD_SCORE;
-      if (auc_pos(l)) { ++mine; atomicAdd(&deg[b], 1u); }
-      else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-    }
-    if (mine) atomicAdd(&deg[a], mine);
-    pos += mine;
-  }
-  if (f) atomicOr(flags, f);
-  const uint64_t p = block_sum_u64(pos, sh);
-  if (threadIdx.x == 0) counts[blockIdx.x] = p;
-}
-
-// block b's positives take the slots offs[b] .. (any order inside a block): key[slot], ends[slot] = a << 16 | b
-__global__ __launch_bounds__(AUC_THREADS) void k_nj_emit(int rows, const float* __restrict__ S, int64_t lds,
-                                                         const float* __restrict__ L, int64_t ldl,
-                                                         const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
-                                                         uint32_t* __restrict__ key, uint32_t* __restrict__ ends) {
-  __shared__ uint32_t cur;
-  if (threadIdx.x == 0) cur = 0;
-  __syncthreads();
-  const uint64_t o_pos = offs[blockIdx.x];
-  const int lane = threadIdx.x & 63;
-  const uint64_t below = (1ull << lane) - 1ull;
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* lrow = L + u * ldl;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const int64_t v = idx ? idx[b] : b;
-      const bool p = auc_pos(lrow[v]);
-      const uint64_t mp = __ballot(p);
-      if (mp == 0) continue;                              // the same in every active lane
-      const int leader = __ffsll((unsigned long long)mp) - 1;
-      uint32_t bp = 0;
-      if (lane == leader) bp = atomicAdd(&cur, (uint32_t)__popcll(mp));
-      bp = __shfl(bp, leader, 64);
-      if (p) {
-        const uint64_t at = o_pos + bp + __popcll(mp & below);
-        key[at] = auc_key(S[u * lds + v]);
-        ends[at] = (uint32_t)a << 16 | (uint32_t)b;
-      }
-    }
-  }
-}
-
 // the two list entries of every sorted positive
 __global__ __launch_bounds__(AUC_THREADS) void k_nj_lists(const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ ends,
                                                           uint32_t np, uint32_t* __restrict__ lnode, uint32_t* __restrict__ lkey) {
@@ -134,11 +75,13 @@ __global__ __launch_bounds__(AUC_THREADS) void k_nj_lists(const uint32_t* __rest
 // the doubled wins of a node's d positives (keys ascending at `list`) over a negative of key x: 2 #{> x} + #{== x}
 __device__ __forceinline__ uint32_t nj_lost(const uint32_t* __restrict__ list, uint32_t d, uint32_t x) {
   if (d == 0) return 0;
-  const uint32_t lb = dl_bound<false>(list, 0u, d, x);
-  const uint32_t ub = dl_bound<true>(list, lb, d, x);
+  const uint32_t lb = rank_bound<false>(list, 0u, d, x);
+  const uint32_t ub = rank_bound<true>(list, lb, d, x);
   return 2u * d - lb - ub;
 }
 
+// (The walk below is not tri_for_each: the columns go in chunks of NJ_COLS with the rows inside and per-row block sums between
+// them, which the walker's row-by-row order does not give.)
 // The negatives, streamed: out[a][NJ_B] += b_q and out[b][NJ_B] += b_q, out[a][NJ_C] += q's losses to a's positives,
 // out[b][NJ_C] += its losses to b's positives, *t_neg += b_q, and the counts hist / ties.
 __global__ __launch_bounds__(AUC_THREADS) void k_nj_negatives(int rows, DlSide s, const float* __restrict__ L, int64_t ldl,
@@ -241,33 +184,13 @@ int nj_run(const char* who, hipStream_t st, int n, const float* L, int ldl, cons
   uint64_t* noff = (uint64_t*)(stage + (size_t)rows * NJ_WORDS);
   uint32_t* deg = (uint32_t*)(noff + R1);
   MCGRA_HIP(hipMemsetAsync(head, 0, head_bytes, st));
-  int h_flags = 0;
-  if (idx) {
-    uint32_t* seen = b.get<uint32_t>(n);
-    if (!seen) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-    const int gi = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
-    k_auc_index<<<gi, AUC_THREADS, 0, st>>>(n, rows, idx, seen, &hd->flags);
-    MCGRA_KERNEL_CHECK();
-    MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (h_flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
-    if (h_flags & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
-  }
-  k_nj_classify<<<g, AUC_THREADS, 0, st>>>(rows, S, lds, L, ldl, idx, counts, deg, &hd->flags);
+  if (int rc = rank_check_idx(who, st, b, n, idx, rows, &hd->flags)) return rc;
+  k_dl_classify<true><<<g, AUC_THREADS, 0, st>>>(rows, S, lds, nullptr, 0, L, ldl, idx, counts, deg, &hd->flags);
   MCGRA_KERNEL_CHECK();
-  std::vector<uint64_t> h(g);
-  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipMemcpyAsync(&h_flags, &hd->flags, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipStreamSynchronize(st));
-  if (h_flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-    set_error("%s: %s%s", who, (h_flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
-              (h_flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
-    return MCGRA_EINVAL;
-  }
-  uint64_t P = 0;
-  for (int i = 0; i < g; ++i) { const uint64_t p = h[i]; h[i] = P; P += p; }        // counts -> offsets
-  const uint64_t m = (uint64_t)rows * (rows - 1) / 2, N = m - P;
+  std::vector<uint64_t> h;
+  uint64_t P = 0, N = 0;
+  if (int rc = dl_counted(who, st, counts, &hd->flags, g, false, rows, h, P, N)) return rc;
+  const uint64_t m = P + N;
   const int gr = (rows + AUC_THREADS - 1) / AUC_THREADS;
   unsigned long long t[2] = {0, 0};
   if (P != 0 && N != 0) {                               // else every placement is 0
@@ -297,18 +220,18 @@ int nj_run(const char* who, hipStream_t st, int n, const float* L, int ldl, cons
     uint32_t* ktmp = (uint32_t*)take(2 * P4, 4);
     uint32_t* cnt = (uint32_t*)take(sort_cnt, 4);
     MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-    k_nj_emit<<<g, AUC_THREADS, 0, st>>>(rows, S, lds, L, ldl, idx, counts, s.sorted, ends);
+    k_dl_emit<true><<<g, AUC_THREADS, 0, st>>>(rows, S, lds, nullptr, 0, L, ldl, idx, counts, s.sorted, ends);
     MCGRA_KERNEL_CHECK();
     if (int rc = auc_sort(st, s.sorted, tmp, P, cnt, off, ends, etmp)) return rc;
     const int gp = (int)std::min<uint64_t>(NJ_POS_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
     k_nj_lists<<<gp, AUC_THREADS, 0, st>>>(s.sorted, ends, (uint32_t)P, lnode, lkey);
     MCGRA_KERNEL_CHECK();
     if (int rc = auc_sort(st, lnode, ltmp, 2 * P, cnt, off, lkey, ktmp)) return rc;
-    k_auc_digit_scan<<<1, 1024, 0, st>>>(deg, rows + 1, noff);
+    rank_scan(st, deg, rows + 1, noff);
     MCGRA_HIP(hipMemsetAsync(s.hist, 0, sizeof(uint32_t) * 2 * H4, st));               // hist and ties are adjacent
     k_nj_negatives<<<g, AUC_THREADS, 0, st>>>(rows, s, L, ldl, idx, (uint32_t)P, lkey, noff, stage, &hd->t_neg);
     MCGRA_KERNEL_CHECK();
-    k_auc_digit_scan<<<1, 1024, 0, st>>>(s.hist, (int)P, s.cum);
+    rank_scan(st, s.hist, (int)P, s.cum);
     k_nj_positives<<<gp, AUC_THREADS, 0, st>>>(s, ends, (uint32_t)P, stage, &hd->t_pos);
     MCGRA_KERNEL_CHECK();
   }
@@ -333,7 +256,8 @@ using namespace mcgra;
 
 extern "C" int mcgra_auc_node_jackknife(void* stream, int n, const float* labels, int ld_labels, const float* scores,
                                         int ld_scores, const int64_t* idx, int64_t n_idx, uint64_t* header, uint64_t* out) {
-  if (!header) { set_error("auc_node_jackknife: bad argument (header NULL)"); return MCGRA_EINVAL; }
-  if (int rc = dl_check("auc_node_jackknife", n, labels, ld_labels, scores, ld_scores, nullptr, 0, false, idx, n_idx, out)) return rc;
+  if (!header || !out) { set_error("auc_node_jackknife: bad argument (header or out NULL)"); return MCGRA_EINVAL; }
+  if (int rc = rank_check_args("auc_node_jackknife", n, {{labels, ld_labels, true}, {scores, ld_scores, true}}, idx, n_idx, 2))
+    return rc;
   return nj_run("auc_node_jackknife", (hipStream_t)stream, n, labels, ld_labels, scores, ld_scores, idx, (int)n_idx, header, out);
 }

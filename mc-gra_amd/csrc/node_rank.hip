@@ -12,6 +12,7 @@
 //
 // One workgroup of NODE_RANK_THREADS lanes owns one row at a time (rows are dealt over a grid the chip holds) and keeps it in
 // LDS from the gather to the counts:
+//   (rank_check_idx: idx only, range check and repeats -- rank_common.hip)
 //   gather   one read of the row: candidate b becomes the 64-bit composite  key << 32 | (0x7fff - b) << 1 | label  (a valid key
 //            is never 0, so 0 pads the row to its class length and sorts last); the argument predicates run on what is read
 //   sort     an in-place bitonic sort of the composites, descending: key descending, then position ascending, the label riding
@@ -232,16 +233,12 @@ using namespace mcgra;
 
 extern "C" int mcgra_node_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores,
                                        int ld_scores, const int64_t* idx, int64_t n_idx, int64_t* out) {
-  if (!idx) n_idx = n;
-  if (!labels || !scores || !out || n < 1 || ld_labels < n || ld_scores < n || n_idx < 2) {
-    set_error("node_rank_metrics: bad argument");
-    return MCGRA_EINVAL;
-  }
-  if (n_idx > MCGRA_NODE_RANK_MAX_NIDX) {
-    set_error("node_rank_metrics: %lld selected nodes; a row of more than %d nodes does not fit one workgroup's LDS",
-              (long long)n_idx, MCGRA_NODE_RANK_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
+  const char* who = "node_rank_metrics";
+  if (!out) { set_error("%s: bad argument (out NULL)", who); return MCGRA_EINVAL; }
+  // the cap: a row of more nodes does not fit one workgroup's LDS
+  if (int rc = rank_check_args(who, n, {{labels, ld_labels, true}, {scores, ld_scores, true}}, idx, n_idx, 2,
+                               MCGRA_NODE_RANK_MAX_NIDX))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const int rows = (int)n_idx;
   int dev = 0, cus = 0;
@@ -253,18 +250,7 @@ extern "C" int mcgra_node_rank_metrics(void* stream, int n, const float* labels,
   if (!flags || !stage) { set_error("node_rank_metrics: hipMalloc of the scratch of %d rows failed", rows); return MCGRA_ENOMEM; }
   MCGRA_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
   int h = 0;
-  if (idx) {
-    uint32_t* seen = b.get<uint32_t>(n);
-    if (!seen) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-    const int g = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
-    k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, rows, idx, seen, flags);
-    MCGRA_KERNEL_CHECK();
-    MCGRA_HIP(hipMemcpyAsync(&h, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (h & AUC_BAD_INDEX) { set_error("node_rank_metrics: a node id outside [0, %d)", n); return MCGRA_EINVAL; }
-    if (h & AUC_REPEAT) { set_error("node_rank_metrics: idx names a node twice (a pair of a node with itself)"); return MCGRA_EINVAL; }
-  }
+  if (int rc = rank_check_idx(who, st, b, n, idx, rows, flags)) return rc;
   const int c = rows - 1;
   int rc;
   if (c <= 1024) rc = node_rank_launch<1024>(st, cus, rows, scores, ld_scores, labels, ld_labels, idx, stage, flags);
@@ -275,11 +261,7 @@ extern "C" int mcgra_node_rank_metrics(void* stream, int n, const float* labels,
   if (rc) return rc;
   MCGRA_HIP(hipMemcpyAsync(&h, flags, sizeof(int), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipStreamSynchronize(st));
-  if (h & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-    set_error("node_rank_metrics: %s%s", (h & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
-              (h & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
-    return MCGRA_EINVAL;
-  }
+  if (int rc = rank_flag_error(who, h)) return rc;
   MCGRA_HIP(hipMemcpyAsync(out, stage, sizeof(int64_t) * 5 * (size_t)rows, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipStreamSynchronize(st));                          // the scratch is freed on return
   return 0;

@@ -10,15 +10,15 @@
 // np.argsort(-s, kind="stable")[:k] over the scores in packed order.
 //
 // Passes:
-//   k_auc_index        idx only: range check, repeats (rank_common.h)
+//   rank_check_idx     idx only: range check, repeats (rank_common.hip)
 //   k_topk_emit        the one read of the selected lower triangle: argument checks, P (64-bit integer atomics), each
 //                      pair's order-preserving key to keys[p] and, for the metrics, its label to lab[p]
 //   k_topk_hist/_pick  MSB-first radix select, 4 passes of 8 bits: a 256-bin histogram (LDS, merged with integer atomics) of
 //                      the keys that match the prefix found so far, then one block walks the bins from 255 down.  Result:
 //                      the threshold key T, g = #keys above T, r = k - g >= 1 keys equal to T to take.  No sort of the m keys
-//   k_topk_count       per block of a contiguous packed range: #keys above T, #keys equal to T; k_auc_digit_scan scans both
-//   k_topk_take        every block ranks the threshold ties of its range in index order (ballots; wave counts through LDS;
-//                      the scan gives the ties before the block) and takes those of rank < r: TP is counted (metrics), or
+//   k_topk_count       per block of a contiguous packed range: #keys above T, #keys equal to T; rank_scan scans both
+//   k_topk_take        every block ranks the threshold ties of its range in index order (block_rank; the scan gives the
+//                      ties before the block) and takes those of rank < r: TP is counted (metrics), or
 //                      the chosen (key, p) records are compacted in packed order (edge list); the pair of tie rank r - 1 is
 //                      the k-th of the ranking and its score is the threshold reported
 //   auc_sort           edge list: a stable LSD radix sort of the k records by descending key with p as payload; they enter
@@ -55,7 +55,6 @@ struct TopkState {
 };
 
 // keys[p] = key of pair p, lab[p] = its label (lab != NULL); st->P += labels that are 1; st->flags |= argument errors.
-// A block owns rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection.
 __global__ __launch_bounds__(AUC_THREADS) void k_topk_emit(int rows, const float* __restrict__ S, int64_t lds,
                                                            const float* __restrict__ L, int64_t ldl,
                                                            const int64_t* __restrict__ idx, uint32_t* __restrict__ keys,
@@ -63,25 +62,19 @@ __global__ __launch_bounds__(AUC_THREADS) void k_topk_emit(int rows, const float
   __shared__ uint64_t sh[AUC_THREADS / 64];
   uint64_t pos = 0;
   int f = 0;
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* srow = S + u * lds;
-    const float* lrow = L ? L + u * ldl : nullptr;
-    const uint64_t base = (uint64_t)a * (a - 1) / 2;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const int64_t v = idx ? idx[b] : b;
-      const float s = srow[v];
-      if (!auc_finite(s)) f |= AUC_BAD_SCORE;
-      keys[base + b] = auc_key(s);
-      if (lrow) {
-        const float l = lrow[v];
-        const bool p = auc_pos(l);
-        if (p) ++pos;
-        else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-        if (lab) lab[base + b] = p ? 1 : 0;
-      }
+  tri_for_each(rows, idx, [&](int a, int b, int64_t u, int64_t v) {
+    const uint64_t at = (uint64_t)a * (a - 1) / 2 + b;
+    const float s = S[u * lds + v];
+    if (!auc_finite(s)) f |= AUC_BAD_SCORE;
+    keys[at] = auc_key(s);
+    if (L) {
+      const float l = L[u * ldl + v];
+      const bool p = auc_pos(l);
+      if (p) ++pos;
+      else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+      if (lab) lab[at] = p ? 1 : 0;
     }
-  }
+  });
   if (f) atomicOr(&st->flags, f);
   const uint64_t tot = block_sum_u64(pos, sh);
   if (threadIdx.x == 0 && tot) atomicAdd(&st->P, (unsigned long long)tot);
@@ -158,8 +151,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_topk_take(const uint32_t* __res
                                                            uint32_t* __restrict__ rp, TopkState* __restrict__ st) {
   __shared__ uint32_t weq[2][AUC_THREADS / 64], wch[2][AUC_THREADS / 64];
   __shared__ uint64_t sh[AUC_THREADS / 64];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const uint64_t below = (1ull << lane) - 1ull;
+  const int t = threadIdx.x;
   const uint64_t beg = blockIdx.x * tile, end = min(count, beg + tile);
   uint64_t run_eq = off[nb + blockIdx.x] - g;                  // ties before this block
   uint64_t run_ch = off[blockIdx.x] + min(run_eq, r);          // chosen before this block
@@ -170,14 +162,8 @@ __global__ __launch_bounds__(AUC_THREADS) void k_topk_take(const uint32_t* __res
     const bool valid = e < end;
     const uint32_t k = valid ? keys[e] : 0u;
     const bool eq = valid && k == T;
-    const uint64_t meq = __ballot(eq);
-    if (lane == 0) weq[par][w] = (uint32_t)__popcll(meq);
-    __syncthreads();
-    uint64_t rank = run_eq + __popcll(meq & below), all_eq = 0;
-    for (int q = 0; q < AUC_THREADS / 64; ++q) {
-      if (q < w) rank += weq[par][q];
-      all_eq += weq[par][q];
-    }
+    const BlockRank re = block_rank(eq, weq, par);
+    const uint64_t rank = run_eq + re.before;
     const bool chosen = valid && (k > T || (eq && rank < r));
     if (eq && rank == r - 1) {
       uint32_t a, b;
@@ -185,18 +171,11 @@ __global__ __launch_bounds__(AUC_THREADS) void k_topk_take(const uint32_t* __res
       const int64_t u = idx ? idx[a] : a, v = idx ? idx[b] : b;
       st->thr_bits = __float_as_uint(S[u * lds + v]);
     }
-    run_eq += all_eq;
+    run_eq += re.all;
     if (EMIT) {
-      const uint64_t mch = __ballot(chosen);
-      if (lane == 0) wch[par][w] = (uint32_t)__popcll(mch);
-      __syncthreads();
-      uint64_t at = run_ch + __popcll(mch & below), all_ch = 0;
-      for (int q = 0; q < AUC_THREADS / 64; ++q) {
-        if (q < w) at += wch[par][q];
-        all_ch += wch[par][q];
-      }
-      if (chosen) { rk[at] = ~k; rp[at] = (uint32_t)e; }
-      run_ch += all_ch;
+      const BlockRank rc = block_rank(chosen, wch, par);
+      if (chosen) { rk[run_ch + rc.before] = ~k; rp[run_ch + rc.before] = (uint32_t)e; }
+      run_ch += rc.all;
     } else if (chosen && lab[e]) {
       ++tp;
     }
@@ -256,28 +235,14 @@ struct TopkRun {
       return MCGRA_ENOMEM;
     }
     MCGRA_HIP(hipMemsetAsync(state, 0, sizeof(TopkState), st));
-    if (idx) {
-      uint32_t* seen = b.get<uint32_t>(n);
-      if (!seen) { set_error("hipMalloc failed"); return MCGRA_ENOMEM; }
-      MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-      const int g = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
-      k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, rows, idx, seen, &state->flags);
-      MCGRA_KERNEL_CHECK();
-      if (int rc = fetch()) return rc;
-      if (h.flags & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
-      if (h.flags & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
-    }
+    if (int rc = rank_check_idx(who, st, b, n, idx, rows, &state->flags)) return rc;
     k_topk_emit<<<std::min(rows - 1, TOPK_ROW_BLOCKS), AUC_THREADS, 0, st>>>(rows, S, lds, L, ldl, idx, keys, lab, state);
     MCGRA_KERNEL_CHECK();
     if (int rc = fetch()) return rc;
-    if (h.flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-      set_error("%s: %s%s", who, (h.flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
-                (h.flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
-      return MCGRA_EINVAL;
-    }
-    tile = (m + TOPK_BLOCKS - 1) / TOPK_BLOCKS;
-    tile = (tile + AUC_THREADS - 1) / AUC_THREADS * AUC_THREADS;
-    nb = (int)((m + tile - 1) / tile);
+    if (int rc = rank_flag_error(who, h.flags)) return rc;
+    const RankTiles ti = rank_tiles(m, TOPK_BLOCKS, AUC_THREADS);
+    tile = ti.tile;
+    nb = ti.nb;
     return 0;
   }
   // the threshold of the k best, 1 <= k <= m: h.prefix = T, h.remaining = r; then the per-range counts and their scan
@@ -291,7 +256,7 @@ struct TopkRun {
     MCGRA_KERNEL_CHECK();
     if (int rc = fetch()) return rc;      // (also: &k was read)
     k_topk_count<<<nb, AUC_THREADS, 0, st>>>(keys, m, tile, h.prefix, nb, cnt);
-    k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt, 2 * nb, off);
+    rank_scan(st, cnt, 2 * nb, off);
     MCGRA_KERNEL_CHECK();
     return 0;
   }
@@ -299,16 +264,8 @@ struct TopkRun {
 
 int topk_check(const char* who, int n, const float* scores, int ld_scores, const float* labels, int ld_labels,
                const int64_t* idx, int64_t& n_idx, int64_t k, int64_t k_min) {
-  if (!idx) n_idx = n;
-  if (n < 1 || !scores || ld_scores < n || (labels && ld_labels < n) || n_idx < 2 || k < k_min) {
-    set_error("%s: bad argument", who);
-    return MCGRA_EINVAL;
-  }
-  if (n_idx > AUC_MAX_NIDX) {
-    set_error("%s: %lld selected nodes; a packed pair position of more than %lld does not fit 32 bits", who, (long long)n_idx,
-              (long long)AUC_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
+  if (k < k_min) { set_error("%s: bad argument (k = %lld)", who, (long long)k); return MCGRA_EINVAL; }
+  if (int rc = rank_check_args(who, n, {{scores, ld_scores, true}, {labels, ld_labels, false}}, idx, n_idx, 2)) return rc;
   const int64_t m = n_idx * (n_idx - 1) / 2;
   if (k > m) { set_error("%s: k = %lld of %lld pairs", who, (long long)k, (long long)m); return MCGRA_EINVAL; }
   return 0;

@@ -8,7 +8,7 @@
 // DESIGN.md 3f the argument that neither cluster is ever empty).
 //
 // Passes of mcgra_two_means_split:
-//   k_auc_index   idx only: range check, repeats (rank_common.h)
+//   rank_check_idx  idx only: range check, repeats (rank_common.hip)
 //   k_tm_emit     the one read of the selected lower triangle for the rounds: argument checks, q[p] and, given labels, lab[p]
 //                 (the layout of k_topk_emit), P, the sum of all q, min q and max q (integer atomics)
 //   k_tm_start    one lane: t_0 = floor((min + max) / 2) + 1
@@ -21,8 +21,8 @@
 //   k_tm_final    a second read of the selected scores: the smallest score of the high cluster, the largest of the low one
 //                 (min / max of the order-preserving key), and TP from lab[p]
 // Passes of mcgra_threshold_pairs: k_tp_count (per contiguous packed range: argument checks, the pairs at or above the
-// threshold, the hits among them), k_auc_digit_scan, k_tp_write (every block ranks its qualifying pairs in packed order behind
-// the scan's offset).  No atomics decide an order.
+// threshold, the hits among them), rank_scan, k_tp_write (every block ranks its qualifying pairs in packed order, block_rank,
+// behind the scan's offset).  No atomics decide an order.
 // Everything is integers and copied float32 bits, merged by integer atomics or a scan: no result depends on the order in which
 // blocks run, and every call returns the same bits.
 // Device scratch: mcgra_two_means_split 4 bytes per candidate (q) + 1 byte per candidate (the labels, when given) + a few KB;
@@ -44,7 +44,7 @@ constexpr int TM_BLOCKS = 1024;            // at most this many blocks per strea
 constexpr int TM_STEP = 4 * AUC_THREADS;   // q per step of a streaming block (one 16-byte load per lane)
 constexpr int TM_BATCH = 4;                // rounds launched between two reads of the state
 constexpr int TP_BLOCKS = 1024;            // at most this many contiguous packed ranges (and blocks) of mcgra_threshold_pairs
-constexpr int TM_BAD_RANGE = 32;           // a flag beside AUC_BAD_*: a finite selected score below 0 or >= 16
+constexpr int TM_BAD_RANGE = 64;           // a flag beside the shared ones: a finite selected score below 0 or >= 16
 
 struct TmState {
   unsigned long long P, tp;                // candidates with label 1; those of the high cluster
@@ -98,7 +98,6 @@ __device__ __forceinline__ uint32_t block_max_u32(uint32_t v, uint32_t* sh) {
 inline uint32_t tm_key_bits(uint32_t k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
 
 // q[p] = the quantised score of pair p, lab[p] = its label (L != NULL); st: P, total, min, max, flags.
-// A block owns rows a = 1 + blockIdx.x, + gridDim.x, ... of the selection.
 __global__ __launch_bounds__(AUC_THREADS) void k_tm_emit(int rows, const float* __restrict__ S, int64_t lds,
                                                          const float* __restrict__ L, int64_t ldl,
                                                          const int64_t* __restrict__ idx, uint32_t* __restrict__ q,
@@ -108,32 +107,26 @@ __global__ __launch_bounds__(AUC_THREADS) void k_tm_emit(int rows, const float* 
   uint64_t pos = 0, sum = 0;
   uint32_t inv_mn = 0, mx = 0;
   int f = 0;
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* srow = S + u * lds;
-    const float* lrow = L ? L + u * ldl : nullptr;
-    const uint64_t base = (uint64_t)a * (a - 1) / 2;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const int64_t v = idx ? idx[b] : b;
-      const float s = srow[v];
-      const uint32_t bits = __float_as_uint(s);
-      uint32_t x = 0;
-      if (!auc_finite(s)) f |= AUC_BAD_SCORE;
-      else if (!tm_in_range(bits)) f |= TM_BAD_RANGE;
-      else x = tm_quantise(bits & 0x7fffffffu);
-      q[base + b] = x;
-      sum += x;
-      mx = max(mx, x);
-      inv_mn = max(inv_mn, ~x);
-      if (lrow) {
-        const float l = lrow[v];
-        const bool p = auc_pos(l);
-        if (p) ++pos;
-        else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-        lab[base + b] = p ? 1 : 0;
-      }
+  tri_for_each(rows, idx, [&](int a, int b, int64_t u, int64_t v) {
+    const uint64_t at = (uint64_t)a * (a - 1) / 2 + b;
+    const float s = S[u * lds + v];
+    const uint32_t bits = __float_as_uint(s);
+    uint32_t x = 0;
+    if (!auc_finite(s)) f |= AUC_BAD_SCORE;
+    else if (!tm_in_range(bits)) f |= TM_BAD_RANGE;
+    else x = tm_quantise(bits & 0x7fffffffu);
+    q[at] = x;
+    sum += x;
+    mx = max(mx, x);
+    inv_mn = max(inv_mn, ~x);
+    if (L) {
+      const float l = L[u * ldl + v];
+      const bool p = auc_pos(l);
+      if (p) ++pos;
+      else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
+      lab[at] = p ? 1 : 0;
     }
-  }
+  });
   if (f) atomicOr(&st->flags, f);
   const uint64_t tot = block_sum_u64(pos, sh);
   __syncthreads();
@@ -200,21 +193,16 @@ __global__ __launch_bounds__(AUC_THREADS) void k_tm_final(int rows, const float*
   __shared__ uint32_t shm[AUC_THREADS / 64];
   uint64_t tp = 0;
   uint32_t inv_hi = 0, lo = 0;
-  for (int a = 1 + blockIdx.x; a < rows; a += gridDim.x) {
-    const int64_t u = idx ? idx[a] : a;
-    const float* srow = S + u * lds;
-    const uint64_t base = (uint64_t)a * (a - 1) / 2;
-    for (int b = threadIdx.x; b < a; b += AUC_THREADS) {
-      const float s = srow[idx ? idx[b] : b];
-      const uint32_t key = auc_key(s);
-      if ((uint64_t)tm_quantise(__float_as_uint(s) & 0x7fffffffu) >= t) {
-        inv_hi = max(inv_hi, ~key);
-        if (lab && lab[base + b]) ++tp;
-      } else {
-        lo = max(lo, key);
-      }
+  tri_for_each(rows, idx, [&](int a, int b, int64_t u, int64_t v) {
+    const float s = S[u * lds + v];
+    const uint32_t key = auc_key(s);
+    if ((uint64_t)tm_quantise(__float_as_uint(s) & 0x7fffffffu) >= t) {
+      inv_hi = max(inv_hi, ~key);
+      if (lab && lab[(uint64_t)a * (a - 1) / 2 + b]) ++tp;
+    } else {
+      lo = max(lo, key);
     }
-  }
+  });
   const uint64_t btp = block_sum_u64(tp, sh);
   const uint32_t bhi = block_max_u32(inv_hi, shm);
   __syncthreads();
@@ -269,7 +257,6 @@ __global__ __launch_bounds__(AUC_THREADS) void k_tp_write(uint64_t count, uint64
                                                           const uint64_t* __restrict__ off, int64_t* __restrict__ pairs,
                                                           float* __restrict__ pair_scores, uint8_t* __restrict__ hits) {
   __shared__ uint32_t wc[2][AUC_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint64_t beg = blockIdx.x * tile, end = min(count, beg + tile);
   uint64_t run = off[blockIdx.x];
   int par = 0;
@@ -285,55 +272,18 @@ __global__ __launch_bounds__(AUC_THREADS) void k_tp_write(uint64_t count, uint64
       s = S[u * lds + v];
       in = auc_key(s) >= T;
     }
-    const uint64_t mask = __ballot(in);
-    if (lane == 0) wc[par][w] = (uint32_t)__popcll(mask);
-    __syncthreads();                                             // (par alternates: one barrier a step is enough)
-    uint64_t at = run + __popcll(mask & ((1ull << lane) - 1ull)), all = 0;
-    for (int k = 0; k < AUC_THREADS / 64; ++k) {
-      if (k < w) at += wc[par][k];
-      all += wc[par][k];
-    }
+    const BlockRank r = block_rank(in, wc, par);
+    const uint64_t at = run + r.before;
     if (in) {
       pairs[2 * at] = u;
       pairs[2 * at + 1] = v;
       if (pair_scores) pair_scores[at] = s;
       if (hits) hits[at] = auc_pos(L[u * ldl + v]) ? 1 : 0;
     }
-    run += all;
+    run += r.all;
   }
 }
 
-// the arguments both entries share, decided without a device
-int tm_check(const char* who, int n, const float* scores, int ld_scores, const float* labels, int ld_labels,
-             const int64_t* idx, int64_t& n_idx) {
-  if (!idx) n_idx = n;
-  if (n < 1 || !scores || ld_scores < n || (labels && ld_labels < n) || n_idx < 2) {
-    set_error("%s: bad argument", who);
-    return MCGRA_EINVAL;
-  }
-  if (n_idx > AUC_MAX_NIDX) {
-    set_error("%s: %lld selected nodes; a packed pair position of more than %lld does not fit 32 bits", who, (long long)n_idx,
-              (long long)AUC_MAX_NIDX);
-    return MCGRA_ENOSUP;
-  }
-  return 0;
-}
-
-// idx: range and repeats (flags: a zeroed device word)
-int tm_check_idx(const char* who, hipStream_t st, AucBufs& b, int n, const int64_t* idx, int rows, int* flags) {
-  uint32_t* seen = b.get<uint32_t>(n);
-  if (!seen) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
-  MCGRA_HIP(hipMemsetAsync(seen, 0, sizeof(uint32_t) * (size_t)n, st));
-  const int g = (int)std::min<int64_t>(1024, ((int64_t)rows + AUC_THREADS - 1) / AUC_THREADS);
-  k_auc_index<<<g, AUC_THREADS, 0, st>>>(n, rows, idx, seen, flags);
-  MCGRA_KERNEL_CHECK();
-  int f = 0;
-  MCGRA_HIP(hipMemcpyAsync(&f, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipStreamSynchronize(st));
-  if (f & AUC_BAD_INDEX) { set_error("%s: a node id outside [0, %d)", who, n); return MCGRA_EINVAL; }
-  if (f & AUC_REPEAT) { set_error("%s: idx names a node twice (a pair of a node with itself)", who); return MCGRA_EINVAL; }
-  return 0;
-}
 }  // namespace
 }  // namespace mcgra
 
@@ -344,7 +294,7 @@ extern "C" int mcgra_two_means_split(void* stream, int n, const float* scores, i
                                      float* thr_high, float* thr_low) {
   const char* who = "two_means_split";
   if (!out || max_iter < 1) { set_error("%s: bad argument", who); return MCGRA_EINVAL; }
-  if (int rc = tm_check(who, n, scores, ld_scores, labels, ld_labels, idx, n_idx)) return rc;
+  if (int rc = rank_check_args(who, n, {{scores, ld_scores, true}, {labels, ld_labels, false}}, idx, n_idx, 2)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int rows = (int)n_idx;
   const uint64_t m = (uint64_t)rows * (rows - 1) / 2;
@@ -357,8 +307,7 @@ extern "C" int mcgra_two_means_split(void* stream, int n, const float* scores, i
     return MCGRA_ENOMEM;
   }
   MCGRA_HIP(hipMemsetAsync(state, 0, sizeof(TmState), st));
-  if (idx)
-    if (int rc = tm_check_idx(who, st, b, n, idx, rows, &state->flags)) return rc;
+  if (int rc = rank_check_idx(who, st, b, n, idx, rows, &state->flags)) return rc;
   TmState h{};
   auto fetch = [&]() -> int {
     MCGRA_HIP(hipMemcpyAsync(&h, state, sizeof(TmState), hipMemcpyDeviceToHost, st));
@@ -370,11 +319,7 @@ extern "C" int mcgra_two_means_split(void* stream, int n, const float* scores, i
   k_tm_start<<<1, 1, 0, st>>>(state);
   MCGRA_KERNEL_CHECK();
   if (int rc = fetch()) return rc;
-  if (h.flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-    set_error("%s: %s%s", who, (h.flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
-              (h.flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
-    return MCGRA_EINVAL;
-  }
+  if (int rc = rank_flag_error(who, h.flags)) return rc;
   if (h.flags & TM_BAD_RANGE) {
     set_error("%s: a selected score is below 0 or not below 16 (q = rint(s 2^28) must fit 32 bits)", who);
     return MCGRA_ENOSUP;
@@ -418,7 +363,7 @@ extern "C" int mcgra_threshold_pairs(void* stream, int n, const float* scores, i
     set_error("%s: bad argument%s", who, threshold != threshold ? " (the threshold is NaN)" : "");
     return MCGRA_EINVAL;
   }
-  if (int rc = tm_check(who, n, scores, ld_scores, labels, ld_labels, idx, n_idx)) return rc;
+  if (int rc = rank_check_args(who, n, {{scores, ld_scores, true}, {labels, ld_labels, false}}, idx, n_idx, 2)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int rows = (int)n_idx;
   const uint64_t m = (uint64_t)rows * (rows - 1) / 2;
@@ -428,28 +373,21 @@ extern "C" int mcgra_threshold_pairs(void* stream, int n, const float* scores, i
   uint64_t* off = b.get<uint64_t>(TP_BLOCKS + 1);
   if (!state || !cnt || !off) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
   MCGRA_HIP(hipMemsetAsync(state, 0, sizeof(TpState), st));
-  if (idx)
-    if (int rc = tm_check_idx(who, st, b, n, idx, rows, &state->flags)) return rc;
+  if (int rc = rank_check_idx(who, st, b, n, idx, rows, &state->flags)) return rc;
   uint32_t tb;
   memcpy(&tb, &threshold, sizeof(tb));
   if (tb == 0x80000000u) tb = 0u;
   const uint32_t T = (tb & 0x80000000u) ? ~tb : (tb | 0x80000000u);     // auc_key of the threshold (+-inf included)
-  uint64_t tile = (m + TP_BLOCKS - 1) / TP_BLOCKS;
-  tile = (tile + AUC_THREADS - 1) / AUC_THREADS * AUC_THREADS;
-  const int nb = (int)((m + tile - 1) / tile);
+  const auto [tile, nb] = rank_tiles(m, TP_BLOCKS, AUC_THREADS);
   k_tp_count<<<nb, AUC_THREADS, 0, st>>>(m, tile, nb, scores, ld_scores, labels, ld_labels, idx, T, cnt, state);
-  k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt, nb + 1, off);
+  rank_scan(st, cnt, nb + 1, off);
   MCGRA_KERNEL_CHECK();
   TpState h{};
   uint64_t total = 0;
   MCGRA_HIP(hipMemcpyAsync(&h, state, sizeof(TpState), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipMemcpyAsync(&total, off + nb, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipStreamSynchronize(st));
-  if (h.flags & (AUC_BAD_SCORE | AUC_BAD_LABEL)) {
-    set_error("%s: %s%s", who, (h.flags & AUC_BAD_SCORE) ? "a selected score is NaN or infinite " : "",
-              (h.flags & AUC_BAD_LABEL) ? "a selected label is neither 0 nor 1" : "");
-    return MCGRA_EINVAL;
-  }
+  if (int rc = rank_flag_error(who, h.flags)) return rc;
   counts[0] = (int64_t)m; counts[1] = (int64_t)total; counts[2] = labels ? (int64_t)h.hits : -1;
   if ((int64_t)total > cap) {
     if (cap == 0 && !pairs) return 0;                             // the counts alone were asked for

@@ -313,20 +313,29 @@ def _node_ids(idx, dev):
     return ix.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
 
 
+def _ranked(idx, first, *more, factor=None):
+    """What every ranking wrapper starts with.  first and more: the n x n matrices of the call (an entry of more may be None,
+    e.g. an optional real); factor: a thin n x d factor instead of a score matrix.  Returns them as float32 rows on first's
+    device, in that order (factor last), then the node ids on that device (or None), n and the number of selected nodes."""
+    dev, n = first.device, first.shape[0]
+    mats = (first,) + more
+    assert first.dim() == 2 and all(m is None or tuple(m.shape) == (n, n) for m in mats) and \
+        (factor is None or (factor.dim() == 2 and factor.shape[0] == n)), \
+        [None if m is None else tuple(m.shape) for m in mats + (factor,)]
+    ix = _node_ids(idx, dev)
+    mats = [None if m is None else _rows_f32(m, dev) for m in mats + (() if factor is None else (factor,))]
+    return (*mats, ix, n, ix.numel() if ix is not None else n)
+
+
 @_on_operand_device
 def roc_auc(real, pred, idx=None):
     """main.metric_pool (main.py:66-75): roc_curve + auc of real[idx][:, idx] against pred[idx][:, idx], exactly, without
     gathering the submatrix (mcgra_roc_auc).  real, pred: n x n on the device; idx: node ids (tensor, array or list,
     repeats allowed) or None for all nodes.  NaN when one class is absent; McgraError for a NaN / inf score or a label
     other than 0 / 1."""
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
     out = C.c_double()
-    check(lib.mcgra_roc_auc(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
-                            ix.numel() if ix is not None else n, C.byref(out)))
+    check(lib.mcgra_roc_auc(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, C.byref(out)))
     return out.value
 
 
@@ -334,27 +343,18 @@ def roc_auc(real, pred, idx=None):
 def decode_auc(real, Z, mode, idx=None):
     """roc_auc(real, decode_scores(Z, mode), idx), bit for bit, without the n x n score matrix (mcgra_decode_auc): the AUC
     of a prior's decode, main.py:412-437.  Z: n x d, d <= 128; mode 0, 1, 2 or 4 (McgraNotSupported otherwise)."""
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and Z.dim() == 2 and Z.shape[0] == n, (real.shape, Z.shape)
-    real, Z = _rows_f32(real, dev), _rows_f32(Z, dev)
-    ix = _node_ids(idx, dev)
+    real, Z, ix, n, rows = _ranked(idx, real, factor=Z)
     out = C.c_double()
-    check(lib.mcgra_decode_auc(_stream(), n, Z.shape[1], _p(Z), Z.stride(0), int(mode), _p(real), real.stride(0), _p(ix),
-                               ix.numel() if ix is not None else n, C.byref(out)))
+    check(lib.mcgra_decode_auc(_stream(), n, Z.shape[1], _p(Z), Z.stride(0), int(mode), _p(real), real.stride(0), _p(ix), rows,
+                               C.byref(out)))
     return out.value
 
 
 def _rank_metrics(real, pred, idx, want_auc, want_ap):
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
     auc, ap = C.c_double(), C.c_double()
-    check(lib.mcgra_rank_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
-                                 ix.numel() if ix is not None else n, C.byref(auc) if want_auc else None,
-                                 C.byref(ap) if want_ap else None))
+    check(lib.mcgra_rank_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows,
+                                 C.byref(auc) if want_auc else None, C.byref(ap) if want_ap else None))
     return auc.value, ap.value
 
 
@@ -389,14 +389,10 @@ def topk_metrics(real, pred, k=None, idx=None):
     "threshold" (the k-th pair's score)}: exact integers, one float64 division each, NaN for a zero denominator (and for
     the threshold when k = 0).  McgraError for k > m, a repeated or out-of-range id, a selected NaN / inf score or a selected
     label other than 0 / 1."""
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
     counts, thr = (C.c_int64 * 4)(), C.c_float(float("nan"))
-    check(lib.mcgra_topk_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
-                                 ix.numel() if ix is not None else n, int(k or 0), counts, C.byref(thr)))
+    check(lib.mcgra_topk_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, int(k or 0),
+                                 counts, C.byref(thr)))
     kk, P, tp, m = (int(c) for c in counts)
     return {"k": kk, "positives": P, "hits": tp, "pairs": m, "precision": _ratio(tp, kk), "recall": _ratio(tp, P),
             "f1": _ratio(2 * tp, kk + P), "threshold": thr.value}
@@ -408,18 +404,12 @@ def top_pairs(pred, k, idx=None, real=None):
     real is given -- the k best pairs of topk_metrics' ranking, best first (ties by ascending packed position), so the first
     k' rows are the answer for k'.  pairs[i] = (idx[a], idx[b]), a > b; scores[i] = pred[pairs[i, 0], pairs[i, 1]], the bits as
     stored; hits[i] = (real[pairs[i, 0], pairs[i, 1]] == 1).  Device tensors.  1 <= k <= m; refusals as topk_metrics."""
-    dev = pred.device
-    n = pred.shape[0]
-    assert pred.dim() == 2 and tuple(pred.shape) == (n, n), pred.shape
-    assert real is None or tuple(real.shape) == (n, n), (real.shape, pred.shape)
-    pred = _rows_f32(pred, dev)
-    real = None if real is None else _rows_f32(real, dev)
-    ix = _node_ids(idx, dev)
+    pred, real, ix, n, rows = _ranked(idx, pred, real)
     k = int(k)
-    pairs = torch.empty(max(k, 0), 2, device=dev, dtype=torch.int64)
-    scores = torch.empty(max(k, 0), device=dev, dtype=torch.float32)
-    hits = None if real is None else torch.empty(max(k, 0), device=dev, dtype=torch.uint8)
-    check(lib.mcgra_top_pairs(_stream(), n, _p(pred), pred.stride(0), _p(ix), ix.numel() if ix is not None else n, k,
+    pairs = torch.empty(max(k, 0), 2, device=pred.device, dtype=torch.int64)
+    scores = torch.empty(max(k, 0), device=pred.device, dtype=torch.float32)
+    hits = None if real is None else torch.empty(max(k, 0), device=pred.device, dtype=torch.uint8)
+    check(lib.mcgra_top_pairs(_stream(), n, _p(pred), pred.stride(0), _p(ix), rows, k,
                               _p(real), real.stride(0) if real is not None else 0, _p(pairs), _p(scores), _p(hits)))
     return (pairs, scores) if real is None else (pairs, scores, hits.view(torch.bool))
 
@@ -439,16 +429,10 @@ def two_means_split(pred, idx=None, real=None, max_iter=256):
     "precision" hits / edges, "recall" hits / positives, "f1" 2 hits / (edges + positives).  One distinct value among the
     candidates is the degenerate case: no edges, iterations 0, thresholds None.  McgraError for a selected NaN / inf score, a
     label other than 0 / 1 or a repeated id; McgraNotSupported for a finite score outside [0, 16)."""
-    dev = pred.device
-    n = pred.shape[0]
-    assert pred.dim() == 2 and tuple(pred.shape) == (n, n), pred.shape
-    assert real is None or tuple(real.shape) == (n, n), (real.shape, pred.shape)
-    pred = _rows_f32(pred, dev)
-    real = None if real is None else _rows_f32(real, dev)
-    ix = _node_ids(idx, dev)
+    pred, real, ix, n, rows = _ranked(idx, pred, real)
     out, hi, lo = (C.c_int64 * 10)(), C.c_float(float("nan")), C.c_float(float("nan"))
     check(lib.mcgra_two_means_split(_stream(), n, _p(pred), pred.stride(0), _p(real), real.stride(0) if real is not None else 0,
-                                    _p(ix), ix.numel() if ix is not None else n, int(max_iter), out, C.byref(hi), C.byref(lo)))
+                                    _p(ix), rows, int(max_iter), out, C.byref(hi), C.byref(lo)))
     m, it, conv, t, n_high, c0, c1, P, tp, degenerate = (int(v) for v in out)
     res = {"pairs": m, "iterations": it, "converged": bool(conv), "degenerate": bool(degenerate), "edges": n_high,
            "threshold": None if degenerate else hi.value, "threshold_low": None if degenerate else lo.value,
@@ -465,22 +449,15 @@ def threshold_pairs(pred, threshold, idx=None, real=None):
     packed position (mcgra_threshold_pairs): (pairs [k, 2] int64, scores [k] float32, hits [k] bool or None without real),
     device tensors.  The counts are asked for first, then exactly k rows are allocated.  With the threshold of
     two_means_split this is its high cluster; with 0.9 the reference's filter() (baseline.py:106-109)."""
-    dev = pred.device
-    n = pred.shape[0]
-    assert pred.dim() == 2 and tuple(pred.shape) == (n, n), pred.shape
-    assert real is None or tuple(real.shape) == (n, n), (real.shape, pred.shape)
-    pred = _rows_f32(pred, dev)
-    real = None if real is None else _rows_f32(real, dev)
-    ix = _node_ids(idx, dev)
-    rows = ix.numel() if ix is not None else n
+    pred, real, ix, n, rows = _ranked(idx, pred, real)
     ldl = real.stride(0) if real is not None else 0
     counts = (C.c_int64 * 3)()
     check(lib.mcgra_threshold_pairs(_stream(), n, _p(pred), pred.stride(0), _p(real), ldl, _p(ix), rows, float(threshold), 0,
                                     None, None, None, counts))
     k = int(counts[1])
-    pairs = torch.empty(k, 2, device=dev, dtype=torch.int64)
-    scores = torch.empty(k, device=dev, dtype=torch.float32)
-    hits = None if real is None else torch.empty(k, device=dev, dtype=torch.uint8)
+    pairs = torch.empty(k, 2, device=pred.device, dtype=torch.int64)
+    scores = torch.empty(k, device=pred.device, dtype=torch.float32)
+    hits = None if real is None else torch.empty(k, device=pred.device, dtype=torch.uint8)
     if k:
         check(lib.mcgra_threshold_pairs(_stream(), n, _p(pred), pred.stride(0), _p(real), ldl, _p(ix), rows, float(threshold), k,
                                         _p(pairs), _p(scores), _p(hits), counts))
@@ -571,14 +548,9 @@ def auc_delong(real, pred, idx=None, level=0.95):
     Caveat: two pairs that share a node are not independent samples, so the interval is a lower bound on the real uncertainty.
     McgraError for a repeated or out-of-range id, a selected NaN / inf score or a selected label other than 0 / 1."""
     _norm_quantile(level)
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
     out = (C.c_uint64 * 8)()
-    check(lib.mcgra_auc_delong(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix),
-                               ix.numel() if ix is not None else n, out))
+    check(lib.mcgra_auc_delong(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, out))
     m, P, N, T = (int(v) for v in out[:4])
     return delong_stats({"pairs": m, "positives": P, "negatives": N, "T": T, "A2": _limbs(out[4], out[5]),
                          "B2": _limbs(out[6], out[7])}, level)
@@ -594,15 +566,10 @@ def auc_delong_paired(real, pred_a, pred_b, idx=None, level=0.95):
     and delta alone.  The caveat of auc_delong holds: pairs that share a node are not independent, so se_delta is a
     lower bound on the real one and the p-value is optimistic.  Refusals as auc_delong, for either matrix."""
     _norm_quantile(level)
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred_a.shape) == (n, n) and tuple(pred_b.shape) == (n, n), \
-        (real.shape, pred_a.shape, pred_b.shape)
-    real, pred_a, pred_b = _rows_f32(real, dev), _rows_f32(pred_a, dev), _rows_f32(pred_b, dev)
-    ix = _node_ids(idx, dev)
+    real, pred_a, pred_b, ix, n, rows = _ranked(idx, real, pred_a, pred_b)
     out = (C.c_uint64 * 17)()
     check(lib.mcgra_auc_delong_paired(_stream(), n, _p(real), real.stride(0), _p(pred_a), pred_a.stride(0), _p(pred_b),
-                                      pred_b.stride(0), _p(ix), ix.numel() if ix is not None else n, out))
+                                      pred_b.stride(0), _p(ix), rows, out))
     ints = {"pairs": int(out[0]), "positives": int(out[1]), "negatives": int(out[2]), "T_a": int(out[3]), "T_b": int(out[4])}
     for i, k in enumerate(("A2_a", "B2_a", "A2_b", "B2_b", "A_ab", "B_ab")):
         ints[k] = _limbs(out[5 + 2 * i], out[6 + 2 * i])
@@ -711,14 +678,9 @@ def node_jackknife_paired_stats(ints_a, ints_b, level=0.95):
 
 
 def _node_jackknife_ints(real, pred, idx):
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
-    rows = ix.numel() if ix is not None else n
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
     header = (C.c_uint64 * 4)()
-    out = torch.empty(max(rows, 0), 5, device=dev, dtype=torch.int64)        # every value is below 2^61
+    out = torch.empty(max(rows, 0), 5, device=pred.device, dtype=torch.int64)        # every value is below 2^61
     check(lib.mcgra_auc_node_jackknife(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, header,
                                        _p(out)))
     ints = {"pairs": int(header[0]), "positives": int(header[1]), "negatives": int(header[2]), "T": int(header[3])}
@@ -813,16 +775,11 @@ def node_rank_metrics(real, pred, idx=None):
     "r_precision" over the nodes with P > 0 -- plain means in index order -- and "by_degree", a list of (lo, hi, count,
     mean auc, mean r_precision) over P in 1, 2, 3-4, 5-8, 9-16, 17-32, 33 and more (hi None).
     McgraError for a repeated or out-of-range id, a candidate NaN / inf score or a candidate label other than 0 / 1."""
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
-    rows = ix.numel() if ix is not None else n
-    out = torch.empty(max(rows, 0), 5, device=dev, dtype=torch.int64)
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
+    out = torch.empty(max(rows, 0), 5, device=pred.device, dtype=torch.int64)
     check(lib.mcgra_node_rank_metrics(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, _p(out)))
     rates, summary = _node_rates(out.cpu().numpy(), rows)
-    res = {"nodes": ix if ix is not None else torch.arange(n, device=dev, dtype=torch.int64)}
+    res = {"nodes": ix if ix is not None else torch.arange(n, device=pred.device, dtype=torch.int64)}
     res.update({k: out[:, q] for q, k in enumerate(("positives", "wins", "ties", "hits", "first_rank"))})
     res.update(rates)
     res["summary"] = summary
@@ -841,20 +798,14 @@ def _rank_curves(real, pred, idx, drop_intermediate, want_roc, want_pr, want_bes
     """One mcgra_rank_curves call (a second one, sized from its counts, when the first capacity is too small; never a
     third).  Returns (counts, roc, pr, best): counts = (P, N, levels, ROC points, PR points); roc / pr = (tps, fps, thresholds)
     device tensors of exactly that many points (int64, int64, float32) or None; best = (tp, fp, level, threshold) or None."""
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and tuple(pred.shape) == (n, n), (real.shape, pred.shape)
-    real, pred = _rows_f32(real, dev), _rows_f32(pred, dev)
-    ix = _node_ids(idx, dev)
-    rows = ix.numel() if ix is not None else n
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
     cap = max(1, int(first_cap) if first_cap is not None else _curve_first_cap(rows * rows, drop_intermediate))
     counts, best, thr = (C.c_int64 * 5)(), (C.c_int64 * 3)(), C.c_float(float("nan"))
     for attempt in range(2):
         def bufs(want):
             if not want:
                 return None, None, None
-            return (torch.empty(cap, device=dev, dtype=torch.int64), torch.empty(cap, device=dev, dtype=torch.int64),
-                    torch.empty(cap, device=dev, dtype=torch.float32))
+            return tuple(torch.empty(cap, device=pred.device, dtype=t) for t in (torch.int64, torch.int64, torch.float32))
         roc, pr = bufs(want_roc), bufs(want_pr)
         rc = lib.mcgra_rank_curves(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows,
                                    1 if drop_intermediate else 0, cap, _p(roc[0]), _p(roc[1]), _p(roc[2]), _p(pr[0]),
@@ -938,14 +889,10 @@ def rank_curves(real, pred, idx=None, drop_intermediate=True, _first_cap=None):
 
 
 def _decode_rank_metrics(real, Z, mode, idx, want_auc, want_ap):
-    dev = real.device
-    n = real.shape[0]
-    assert real.dim() == 2 and tuple(real.shape) == (n, n) and Z.dim() == 2 and Z.shape[0] == n, (real.shape, Z.shape)
-    real, Z = _rows_f32(real, dev), _rows_f32(Z, dev)
-    ix = _node_ids(idx, dev)
+    real, Z, ix, n, rows = _ranked(idx, real, factor=Z)
     auc, ap = C.c_double(), C.c_double()
     check(lib.mcgra_decode_rank_metrics(_stream(), n, Z.shape[1], _p(Z), Z.stride(0), int(mode), _p(real), real.stride(0),
-                                        _p(ix), ix.numel() if ix is not None else n, C.byref(auc) if want_auc else None,
+                                        _p(ix), rows, C.byref(auc) if want_auc else None,
                                         C.byref(ap) if want_ap else None))
     return auc.value, ap.value
 

@@ -185,6 +185,28 @@ def test_curves_against_the_truth(pkg, name, drop):
         assert np.array_equal(g.cpu().numpy(), w.cpu().numpy(), equal_nan=True)
 
 
+def test_curves_of_1100_selected_nodes(pkg):
+    """n_idx = 1100 of n = 1200 nodes in a shuffled order: more selected rows than the classify and emit passes have blocks
+    (1024), so the first blocks take a second row.  64 score levels, about 1 % positives; both curves and the best level
+    element for element."""
+    import torch
+    from mc_gra_amd import engine as E
+    rng = np.random.RandomState(1100)
+    real = _labels(rng, 1200, 0.01)
+    pred = (np.floor(64 * (rng.rand(1200, 1200) + 0.3 * real) / 1.3) / 64).astype(np.float32)
+    idx = rng.permutation(1200)[:1100].copy()
+    want = T.curves(real, pred, idx, drop_intermediate=True)
+    assert want["counts"][0] > 0 and want["counts"][2] == 64
+    dev = lambda x: torch.as_tensor(x, device="cuda:0")
+    counts, roc, pr, best = E._rank_curves(dev(real), dev(pred), dev(idx), True, True, True, True)
+    print("n_idx 1100: counts", counts, "best", best)
+    assert counts == want["counts"]
+    for got, w, what in ((roc, want["roc"], "roc"), (pr, want["pr"], "pr")):
+        for g, x, part in zip(got, w, ("tps", "fps", "thresholds")):
+            assert np.array_equal(g.cpu().numpy(), x), (what, part)
+    assert best[:3] == want["best"] and best[3] == T.levels(real, pred, idx)[2][want["best"][2]]
+
+
 def test_wrapper_defaults_are_sklearns(pkg):
     from mc_gra_amd import engine as E
     real, pred, ix = _dev_case("n70_zeros")

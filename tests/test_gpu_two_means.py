@@ -271,6 +271,21 @@ def test_threshold_pairs_against_the_truth(pkg, name):
     assert len(T.threshold_pairs(real, pred, s.min(), idx)[0]) == len(s)
 
 
+def test_threshold_pairs_of_1100_selected_nodes(pkg):
+    """n_idx = 1100 of n = 1200 nodes in a shuffled order: m = 604 450 pairs, ranges of 768 pairs (three 256-lane steps a block),
+    positions a beyond 1024.  64 score levels, about 1 % edges, the scores in a wider buffer; a level as the threshold."""
+    from mc_gra_amd import engine as E
+    rng = np.random.RandomState(1100)
+    real = _graph(rng, 1200, 0.01)
+    pred = (rng.randint(0, 64, (1200, 1200)) / 64.0).astype(np.float32)
+    idx = rng.permutation(1200)[:1100].copy()
+    r, p, ix = _dev(real), _dev(pred, 7), _dev(idx)
+    for thr in (0.875, 0.5):
+        want = T.threshold_pairs(real, pred, thr, idx)
+        assert 0 < len(want[0]) < 604450
+        _check_pairs(E.threshold_pairs(p, thr, ix, r), want, ("n_idx 1100", thr))
+
+
 def test_threshold_pairs_negative_scores_and_signed_zeros(pkg):
     """Any finite score is a candidate, and -0.0 >= +0.0 holds: a threshold of +0.0 takes the -0.0 scores."""
     from mc_gra_amd import engine as E
