@@ -437,6 +437,41 @@ int mcgra_auc_node_jackknife(void* stream, int n, const float* labels, int ld_la
                              const int64_t* idx, int64_t n_idx, uint64_t* header /* host[4]: m, P, N, T */,
                              uint64_t* out /* device [n_idx][5]: P_v, N_v, A_v, B_v, C_v */);
 
+/* Whether the recovered graph LOOKS like the real one: degrees, triangles and wedges of the graph a threshold cuts out of the
+ * scores, of the true graph and of their intersection, as exact integers per node and in total.
+ *   - candidates, selection and checks as mcgra_threshold_pairs / mcgra_topk_metrics: idx, n_idx REPEAT-FREE device int64 node
+ *     ids or NULL for all n nodes; with m = n_idx the pairs of positions a > b with score scores[idx[a]][idx[b]] and label
+ *     labels[idx[a]][idx[b]]; nothing outside the selected strict lower triangle is looked at; n_idx from 2 (MCGRA_EINVAL
+ *     below) to 65 535 (MCGRA_ENOSUP beyond);
+ *   - R is the undirected graph on the m positions with the edge {a, b} iff score >= threshold.  The comparison is
+ *     mcgra_threshold_pairs': float32 values, -0.0 >= +0.0 holds, subnormals are ordinary values, threshold = +-inf is allowed
+ *     (nothing / everything); a NaN threshold: MCGRA_EINVAL.  G, when labels are given, has the edge {a, b} iff the label is
+ *     1.  C = R & G, the recovered edges that are true;
+ *   - for a graph X and a position v: d_X(v) is its degree, t_X(v) the number of triangles through v, i.e. of unordered
+ *     {u, w} with vu, vw, uw all in X;
+ *   - out (device int64 [n_idx][6]), row v = position v of idx (not the node id) = {d_R, t_R, d_G, t_G, d_C, t_C}; the last
+ *     four are -1 without labels;
+ *   - header (host int64[9]) = {pairs m (m - 1) / 2, E_R, T_R, W_R, E_G, T_G, W_G, E_C, T_C}: E = sum d / 2 edges,
+ *     T = sum t / 3 triangles, W = sum d (d - 1) / 2 wedges (paths of length two); the G and C entries are -1 without labels.
+ *     Transitivity 3 T / W, the clustering coefficients 2 t / (d (d - 1)) and the comparisons of R with G are left to the
+ *     caller.  E_R and E_C are mcgra_threshold_pairs' counts[1] and counts[2] on the same input;
+ *   - no overflow: t_v <= C(65 534, 2) < 2^31, T < 2^46, W < 2^48;
+ *   - a selected score that is NaN or +-inf (whatever the threshold), given labels a selected label other than 0 or 1, a
+ *     repeated or out-of-range id: MCGRA_EINVAL.  header or out NULL, scores NULL, an ld below n, a NaN threshold and the
+ *     n_idx limits are decided before any HIP call.  After any refusal nothing has been written to header or out and
+ *     mcgra_last_error() names the cause;
+ *   - the device does integer arithmetic only and every output has one writer: the same bits on every call, whatever order
+ *     the blocks run in.
+ * Synchronises `stream`.
+ * Device scratch: each graph as a bit matrix of n_idx rows of ceil(n_idx / 64) 64-bit words -- one graph without labels, three
+ * with them: 3 n_idx ceil(n_idx / 64) 8 bytes, 38 MB at n_idx = 10 000 and 1.6 GB at the capacity; MCGRA_ENOMEM when that
+ * cannot be allocated.  About 100 bytes more, and 4 bytes per node of the graph when idx is given. */
+int mcgra_graph_structure(void* stream, int n, const float* scores, int ld_scores,
+                          const float* labels /* may be NULL */, int ld_labels,
+                          const int64_t* idx, int64_t n_idx, float threshold,
+                          int64_t* header /* host[9]: pairs, E_R, T_R, W_R, E_G, T_G, W_G, E_C, T_C */,
+                          int64_t* out    /* device [n_idx][6]: d_R, t_R, d_G, t_G, d_C, t_C */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score

@@ -46,6 +46,7 @@ SYMBOLS = [
     "mcgra_two_means_split", "mcgra_threshold_pairs",
     "mcgra_auc_delong", "mcgra_auc_delong_paired",
     "mcgra_auc_node_jackknife",
+    "mcgra_graph_structure",
 ]
 
 
@@ -135,6 +136,7 @@ def _load():
         "mcgra_auc_delong": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64)],
         "mcgra_auc_delong_paired": [vp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64)],
         "mcgra_auc_node_jackknife": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64), ip],
+        "mcgra_graph_structure": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_float, C.POINTER(C.c_int64), ip],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

@@ -719,6 +719,105 @@ def auc_node_jackknife_paired(real, pred_a, pred_b, idx=None, level=0.95):
     return node_jackknife_paired_stats(_node_jackknife_ints(real, pred_a, idx), _node_jackknife_ints(real, pred_b, idx), level)
 
 
+GRAPH_STRUCTURE_HEADER = ("pairs", "E_R", "T_R", "W_R", "E_G", "T_G", "W_G", "E_C", "T_C")
+GRAPH_STRUCTURE_COLUMNS = ("d_R", "t_R", "d_G", "t_G", "d_C", "t_C")
+
+
+def _clustering(d, t):
+    """The local clustering coefficients 2 t_v / (d_v (d_v - 1)) as exact rationals (numerator, denominator); 0 / 1 where
+    d_v < 2."""
+    return [(2 * tv, dv * (dv - 1)) if dv >= 2 else (0, 1) for dv, tv in zip(d, t)]
+
+
+def _one_graph_stats(pairs, E, T, W, d, c):
+    # a / b of two Python integers is the correctly rounded quotient: float(Fraction(a, b)) without the gcd
+    m = len(d)
+    hist = [0] * (max(d) + 1)
+    for dv in d:
+        hist[dv] += 1
+    return {"edges": E, "density": E / pairs, "mean_degree": 2 * E / m, "max_degree": max(d),
+            "triangles": T, "wedges": W, "transitivity": 3 * T / W if W else 0.0,
+            "avg_clustering": math.fsum(a / b for a, b in c) / m, "degree_hist": hist}
+
+
+def graph_structure_stats(header, cols):
+    """The doubles of graph_structure from its integers: header = {"pairs", "E_R", "T_R", "W_R", "E_G", "T_G", "W_G", "E_C",
+    "T_C"} and cols = {"d_R", "t_R", "d_G", "t_G", "d_C", "t_C"} (sequences over the m positions; the G and C entries -1 or
+    None without the truth).  Every double is ONE rounding of an exact rational (the correctly rounded quotient of two Python
+    integers), or a math.fsum of such.  No device is involved.
+    Returns {"nodes", "recovered": g(R), "true": g(G) or None, ...}, g(X) = {"edges", "density" E / pairs, "mean_degree"
+    2 E / m, "max_degree", "triangles", "wedges", "transitivity" 3 T / W (0.0 when W == 0, as networkx), "avg_clustering"
+    fsum(c_v) / m with c_v = 2 t_v / (d_v (d_v - 1)) and 0 where d_v < 2 (nx.average_clustering's default), "degree_hist"
+    (nodes per degree 0 .. max_degree)}.  With the truth also: "precision" E_C / E_R, "recall" E_C / E_G, "f1"
+    2 E_C / (E_R + E_G), "triangle_hits" T_C, "triangle_recall" T_C / T_G, "triangle_precision" T_C / T_R (each NaN on a zero
+    denominator), "degree_l1" sum |d_R - d_G| / m, "degree_ks" max_k |#{d_R <= k} - #{d_G <= k}| / m, "degree_corr" Pearson's
+    r of the two degree sequences, sign(c) sqrt(c^2 / (v_R v_G)) from the integer moments c = m sum d_R d_G - sum d_R sum d_G,
+    v_X = m sum d_X^2 - (sum d_X)^2: one rational, one rounding, one square root; NaN when either variance is 0, and
+    "clustering_l1" fsum(|c_R(v) - c_G(v)|) / m."""
+    nan = float("nan")
+    h = {k: int(header[k]) for k in GRAPH_STRUCTURE_HEADER}
+    dR, tR = ([int(x) for x in cols[k]] for k in ("d_R", "t_R"))
+    m = len(dR)
+    have = h["E_G"] >= 0
+    if m < 2 or len(tR) != m or h["pairs"] != m * (m - 1) // 2:
+        raise ValueError("graph_structure_stats: the columns do not belong to the header")
+    cR = _clustering(dR, tR)
+    res = {"nodes": m, "recovered": _one_graph_stats(h["pairs"], h["E_R"], h["T_R"], h["W_R"], dR, cR), "true": None}
+    if not have:
+        return res
+    dG, tG = ([int(x) for x in cols[k]] for k in ("d_G", "t_G"))
+    if len(dG) != m or len(tG) != m:
+        raise ValueError("graph_structure_stats: the columns differ in length")
+    cG = _clustering(dG, tG)
+    res["true"] = _one_graph_stats(h["pairs"], h["E_G"], h["T_G"], h["W_G"], dG, cG)
+    ratio = lambda a, b: a / b if b else nan
+    res.update({"precision": ratio(h["E_C"], h["E_R"]), "recall": ratio(h["E_C"], h["E_G"]),
+                "f1": ratio(2 * h["E_C"], h["E_R"] + h["E_G"]), "triangle_hits": h["T_C"],
+                "triangle_recall": ratio(h["T_C"], h["T_G"]), "triangle_precision": ratio(h["T_C"], h["T_R"]),
+                "degree_l1": sum(abs(a - b) for a, b in zip(dR, dG)) / m})
+    hr, hg = res["recovered"]["degree_hist"], res["true"]["degree_hist"]
+    run = worst = 0
+    for k in range(max(len(hr), len(hg))):
+        run += (hr[k] if k < len(hr) else 0) - (hg[k] if k < len(hg) else 0)
+        worst = max(worst, abs(run))
+    res["degree_ks"] = worst / m
+    sr, sg = sum(dR), sum(dG)
+    cov = m * sum(a * b for a, b in zip(dR, dG)) - sr * sg
+    vr, vg = m * sum(a * a for a in dR) - sr * sr, m * sum(b * b for b in dG) - sg * sg
+    res["degree_corr"] = math.copysign(math.sqrt(cov * cov / (vr * vg)), cov) if vr and vg else nan
+    res["clustering_l1"] = math.fsum(abs(a * q - p * b) / (b * q) for (a, b), (p, q) in zip(cR, cG)) / m
+    return res
+
+
+@_on_operand_device
+def graph_structure(pred, threshold, idx=None, real=None):
+    """Whether the recovered graph looks like the real one (mcgra_graph_structure): degrees, triangles and wedges of R, the
+    graph on the positions of a REPEAT-FREE idx (None: all nodes) with the edge {a, b}, a > b, iff pred[idx[a], idx[b]] >=
+    threshold (threshold_pairs' float32 comparison: its edge list is R); with real also of G (real[idx[a], idx[b]] == 1) and of
+    C = R & G.  Returns {"threshold", "nodes" (m), the header integers "pairs", "E_R", "T_R", "W_R", "E_G", "T_G", "W_G", "E_C",
+    "T_C" (edges, triangles, wedges; -1 for G and C without real), the columns "d_R", "t_R", "d_G", "t_G", "d_C", "t_C" (device
+    int64 [m], row = position in idx: degree and triangles through the node; -1 for G and C without real), "stats"
+    (graph_structure_stats of them)}.  Exact integers from the device (bit matrices, AND + popcount), exact rationals on the
+    host, the same bits on every call.  McgraError for a NaN threshold, a repeated or out-of-range id, a selected NaN / inf
+    score or a selected label other than 0 / 1."""
+    header, cols = _graph_structure_ints(pred, threshold, idx, real)
+    res = {"threshold": float(threshold), "nodes": cols.shape[1]}
+    res.update(zip(GRAPH_STRUCTURE_HEADER, header))
+    res.update(zip(GRAPH_STRUCTURE_COLUMNS, cols))
+    res["stats"] = graph_structure_stats(res, dict(zip(GRAPH_STRUCTURE_COLUMNS, cols.tolist())))
+    return res
+
+
+def _graph_structure_ints(pred, threshold, idx, real):
+    """The device entry alone: (the nine header integers, the six columns as one device int64 tensor [6, m])."""
+    pred, real, ix, n, rows = _ranked(idx, pred, real)
+    header = (C.c_int64 * 9)()
+    out = torch.empty(max(rows, 0), 6, device=pred.device, dtype=torch.int64)
+    check(lib.mcgra_graph_structure(_stream(), n, _p(pred), pred.stride(0), _p(real), real.stride(0) if real is not None else 0,
+                                    _p(ix), rows, float(threshold), header, _p(out)))
+    return [int(v) for v in header], out.t().contiguous()
+
+
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
 # row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
 NODE_RANK_MAX_NIDX = 16384

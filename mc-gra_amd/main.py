@@ -48,6 +48,16 @@ ratio se_nodes / se of the two standard errors is reported; with --versus the ja
 AUCs (engine.auc_node_jackknife_paired).
 --save_influence PATH (needs --ci_nodes) writes, as an .npz at PATH, which nodes carry the attack's AUC: for each index set
 nodes_<set>, the integers P_v_<set>, N_v_<set>, A_v_<set>, B_v_<set>, C_v_<set> and influence_<set> = AUC - AUC without the node.
+--structure split|edges|THRESHOLD (not in the reference; --mode evaluate only; absent by default, and then nothing changes) asks
+whether the recovered graph LOOKS like the real one: modified_adj within each index set is cut at a threshold -- `split`: that
+of the set's own 2-means split (engine.two_means_split; a degenerate split is the empty graph), `edges`: the score of the P-th
+best pair, P the set's true edge count (engine.topk_metrics(k=0); ties at that score may add edges, the real count is reported),
+or a float -- and the degrees, triangles, wedges, transitivity and clustering of that graph are reported beside the true
+graph's, with the triangles both share and the distance between the two degree sequences (engine.graph_structure: bit
+matrices and popcounts on the GPU, exact integers, exact rationals on the host).
+--save_structure PATH (needs --structure) writes, as an .npz at PATH, for each index set nodes_<set>, the six integer columns
+d_R_<set>, t_R_<set>, d_G_<set>, t_G_<set>, d_C_<set>, t_C_<set> (degree and triangles per node in the recovered graph, the true
+graph and their intersection) and threshold_<set>.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -145,6 +155,30 @@ def check_ci_nodes_args(args, fail):
         fail("--save_influence takes the path of the .npz to write")
 
 
+def structure_source(source):
+    """--structure SOURCE as "split", "edges" or a finite float; None for anything else."""
+    if source in ("split", "edges"):
+        return source
+    try:
+        thr = float(source)
+    except (TypeError, ValueError):
+        return None
+    return thr if np.isfinite(thr) else None
+
+
+def check_structure_args(args, fail):
+    """--structure / --save_structure against the rest of the command line; fail(message) does not return."""
+    source, path = getattr(args, "structure", None), getattr(args, "save_structure", None)
+    if path is not None and source is None:
+        fail("--save_structure needs --structure")
+    if path is not None and path == "":
+        fail("--save_structure takes the path of the .npz to write")
+    if source is not None and args.mode != "evaluate":
+        fail(f"--structure measures the graph cut out of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+    if source is not None and structure_source(source) is None:
+        fail(f"--structure takes `split`, `edges` or a finite threshold, not {source!r}")
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
@@ -154,6 +188,7 @@ class _Parser(argparse.ArgumentParser):
         check_per_node_args(args, self.error)
         check_ci_args(args, self.error)
         check_ci_nodes_args(args, self.error)
+        check_structure_args(args, self.error)
         return args
 
 
@@ -207,6 +242,8 @@ def build_parser():
     p.add_argument('--save_scores', type=str, default=argparse.SUPPRESS)       # write modified_adj as an .npy for a later --versus
     p.add_argument('--ci_nodes', action='store_true', default=argparse.SUPPRESS)   # also the node-jackknife se and interval of the AUC
     p.add_argument('--save_influence', type=str, default=argparse.SUPPRESS)    # with --ci_nodes: each node's influence as an .npz
+    p.add_argument('--structure', type=str, default=argparse.SUPPRESS)         # also degrees, triangles and clustering of the cut graph
+    p.add_argument('--save_structure', type=str, default=argparse.SUPPRESS)    # with --structure: the per-node columns as an .npz
     return p
 
 
@@ -374,6 +411,41 @@ def save_influence(path, res, sets, n):
         np.savez(f, **arrays)
 
 
+def structure_threshold(source, real, inference_adj, ix):
+    """The threshold of one index set for --structure SOURCE (structure_source's value): `split`: the smallest score of the
+    high cluster of the set's 2-means split; `edges`: the score of the P-th best pair, P the set's true edge count; +inf (the
+    empty graph) for a degenerate split or P == 0; a float: itself."""
+    if source == "split":
+        d = engine.two_means_split(inference_adj, ix)
+        return float("inf") if d["degenerate"] else d["threshold"]
+    if source == "edges":
+        d = engine.topk_metrics(real, inference_adj, 0, ix)
+        return d["threshold"] if d["k"] else float("inf")
+    return float(source)
+
+
+def structure_report(ori_adj, inference_adj, sets, source):
+    """--structure: engine.graph_structure of each index set of `sets` (name -> node ids, None: every node) at the threshold
+    structure_threshold gives for it, with the true graph beside it.  Returns {"structure_<name>": dict}."""
+    real = ori_adj.to(inference_adj.device)
+    return {f"structure_{name}": engine.graph_structure(inference_adj, structure_threshold(source, real, inference_adj, ix), ix, real)
+            for name, ix in sets.items()}
+
+
+def save_structure(path, res, sets, n):
+    """--save_structure: per index set the node ids, the six integer columns of engine.graph_structure (int64) and the threshold
+    (float32), as an .npz at exactly `path`."""
+    arrays = {}
+    for name, ix in sets.items():
+        d = res[f"structure_{name}"]
+        arrays[f"nodes_{name}"] = np.arange(n, dtype=np.int64) if ix is None else np.asarray(ix, dtype=np.int64)
+        for k in engine.GRAPH_STRUCTURE_COLUMNS:
+            arrays[f"{k}_{name}"] = d[k].cpu().numpy()
+        arrays[f"threshold_{name}"] = np.float32(d["threshold"])
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
 def load_versus(path, n):
     """--versus PATH: the .npy at `path` as an n x n float32 matrix; anything else is refused by name."""
     try:
@@ -490,6 +562,7 @@ def _run(args, rank, world):
     check_per_node_args(args, _exit)
     check_ci_args(args, _exit)
     check_ci_nodes_args(args, _exit)
+    check_structure_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -625,6 +698,10 @@ def _run(args, rank, world):
         res.update(ci_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, other))
     if want_ci_nodes:       # every rank computes; the keys exist only with the flag
         res.update(ci_nodes_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None}, other))
+    want_structure = getattr(args, "structure", None) is not None
+    if want_structure:      # every rank computes; the keys exist only with the flag
+        res.update(structure_report(ad, inference_adj, {"attack": idx_attack, "train": idx_train, "all": None},
+                                    structure_source(args.structure)))
     res["path"] = dict(model.history.get("path", {}), world=world)
     if rank != 0:           # every rank holds the same modified_adj; rank 0 reports
         return res
@@ -660,6 +737,13 @@ def _run(args, rank, world):
             print(f"current delta={d['delta']} se_nodes={d['se_delta']} z={d['z']} p={d['p_value']}")
         if getattr(args, "save_influence", None):
             save_influence(args.save_influence, res, {"attack": idx_attack, "train": idx_train, "all": None}, adj.shape[0])
+    if want_structure:
+        d = res["structure_all"]
+        q = d["stats"]
+        print(f"current transitivity={q['recovered']['transitivity']} (true {q['true']['transitivity']}) "
+              f"triangles={d['T_C']}/{d['T_G']} degree_corr={q['degree_corr']} degree_ks={q['degree_ks']}")
+        if getattr(args, "save_structure", None):
+            save_structure(args.save_structure, res, {"attack": idx_attack, "train": idx_train, "all": None}, adj.shape[0])
     if getattr(args, "save_scores", None):
         save_scores(args.save_scores, inference_adj)
     os.makedirs("./results/", exist_ok=True)
@@ -716,6 +800,15 @@ def _run(args, rank, world):
                     d = res[f"versus_nodes_{key}"]
                     f.write(f"In {name}: versus {versus} (nodes): AUC={d['b']['auc']} delta={d['delta']} se_nodes={d['se_delta']} "
                             f"z={d['z']} p={d['p_value']}\n")
+        if want_structure:
+            for name, key in (("attack graph", "attack"), ("train graph", "train"), ("Whole Graph", "all")):
+                d = res[f"structure_{key}"]
+                q = d["stats"]
+                f.write(f"In {name}: structure at {d['threshold']}: edges={d['E_R']} (true {d['E_G']}, shared {d['E_C']}) "
+                        f"triangles={d['T_R']} (true {d['T_G']}, shared {d['T_C']}) "
+                        f"transitivity={q['recovered']['transitivity']} (true {q['true']['transitivity']}) "
+                        f"clustering={q['recovered']['avg_clustering']} (true {q['true']['avg_clustering']}) "
+                        f"degree_corr={q['degree_corr']} degree_ks={q['degree_ks']} degree_l1={q['degree_l1']}\n")
         f.write(f"current density: {res['density']}\n")
     return res
 
