@@ -1,0 +1,393 @@
+"""The optional reports of `main.py --mode evaluate` (none is in the reference; main.py's docstring says what each flag asks):
+per report the argument check, the computation on the device, the console lines, the --save_* file and the log lines, and at
+the bottom REPORTS, the one ordered table of them that main.py's parser, run and log loop over.  To add a report, add an entry.
+
+`sets` is always index set name -> node ids (None: every node); fail(message) does not return; a --save_* file is written at
+exactly the path given.  engine functions are looked up as engine.<fn> at the call."""
+import argparse
+import collections
+
+import numpy as np
+import torch
+
+from . import engine
+
+SET_TITLES = (("attack graph", "attack"), ("train graph", "train"), ("Whole Graph", "all"))
+CI_LEVEL = 0.95
+
+
+# what one evaluate run hands its reports: real is the true adjacency on the device of inference_adj (the attack's modified_adj),
+# other the second n x n score matrix of --versus and versus the flag as given (both None without it)
+Context = collections.namedtuple("Context", "real inference_adj sets n rank other versus args")
+
+
+class Report:
+    """One optional report: check(args, fail) refuses a bad command line, wanted(args) says whether it is on, compute(ctx) runs
+    on every rank and returns the keys to merge into the result, console(res, ctx) and log(res, ctx) return the lines rank 0
+    prints and logs, save(res, ctx) writes rank 0's --save_* file when one was asked for."""
+    def __init__(self, flags, check, wanted, compute, console, log, save=lambda res, ctx: None):
+        self.flags = flags      # the namespace names it owns: hidden from the log's parameter line while it is off
+        self.check, self.wanted, self.compute, self.console, self.log, self.save = check, wanted, compute, console, log, save
+
+
+def _on(flag, given=False):
+    """wanted(args) of a report: its flag is set or, with `given` (a flag whose 0 asks for something), there at all."""
+    return lambda args: getattr(args, flag, None) is not None if given else bool(getattr(args, flag, None))
+
+
+def _per_set(res, key):
+    """(title, the report's dict) of each index set, in the log's order."""
+    return [(title, res[f"{key}_{name}"]) for title, name in SET_TITLES]
+
+
+def _save_npz(path, **arrays):
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def _save_per_set(path, res, key, ctx, columns):
+    """One .npz with, per index set, nodes_<set> and every array of columns(res["<key>_<set>"]) as <name>_<set>."""
+    arrays = {}
+    for name, ix in ctx.sets.items():
+        arrays[f"nodes_{name}"] = np.arange(ctx.n, dtype=np.int64) if ix is None else np.asarray(ix, dtype=np.int64)
+        arrays.update({f"{k}_{name}": v for k, v in columns(res[f"{key}_{name}"]).items()})
+    _save_npz(path, **arrays)
+
+
+def check_topk_args(args, fail):
+    topk, edges = getattr(args, "topk", None), getattr(args, "save_edges", None)
+    if edges and topk is None:
+        fail("--save_edges needs --topk")
+    if topk is not None and topk < 0:
+        fail("--topk takes K >= 0 (0: each index set's own true edge count)")
+    if topk is not None and args.mode != "evaluate":
+        fail(f"--topk scores the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+def topk_report(real, inference_adj, sets, K):
+    """--topk K: {"topk_<name>": engine.topk_metrics of the index set}, K clamped to its pair count (K = 0: its true edge count)."""
+    out = {}
+    for name, ix in sets.items():
+        rows = inference_adj.shape[0] if ix is None else len(ix)
+        out[f"topk_{name}"] = engine.topk_metrics(real, inference_adj, min(K, rows * (rows - 1) // 2), ix)
+    return out
+
+
+def save_edges(res, ctx):
+    """--save_edges: the k best pairs of the whole graph in ranking order (engine.top_pairs)."""
+    k = res["topk_all"]["k"]
+    if k > 0:
+        pairs, scores, hits = (t.cpu().numpy() for t in engine.top_pairs(ctx.inference_adj, k, None, ctx.real))
+    else:
+        pairs, scores, hits = np.zeros((0, 2), np.int64), np.zeros(0, np.float32), np.zeros(0, bool)
+    _save_npz(ctx.args.save_edges, pairs=pairs, scores=scores, hits=hits)
+
+
+def _topk_log(res, ctx):
+    return ["\t".join(f"In {title}: k={d['k']} P={d['precision']} R={d['recall']} F1={d['f1']}" for title, d in _per_set(res, "topk"))]
+
+
+def check_binarize_args(args, fail):
+    binarize, graph = getattr(args, "binarize", False), getattr(args, "save_graph", None)
+    if graph and not binarize:
+        fail("--save_graph needs --binarize")
+    if binarize and args.mode != "evaluate":
+        fail(f"--binarize splits the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+def save_graph(res, ctx):
+    """--save_graph: every pair of the whole graph at or above its split's threshold; a degenerate split: no edges, a NaN threshold."""
+    split = res["split_all"]
+    if split["degenerate"]:
+        pairs, scores, hits, thr = np.zeros((0, 2), np.int64), np.zeros(0, np.float32), np.zeros(0, bool), float("nan")
+    else:
+        thr = split["threshold"]
+        pairs, scores, hits = (t.cpu().numpy() for t in engine.threshold_pairs(ctx.inference_adj, thr, None, ctx.real))
+    _save_npz(ctx.args.save_graph, pairs=pairs, scores=scores, hits=hits, threshold=np.float32(thr),
+              iterations=np.int64(split["iterations"]))
+
+
+def _binarize_log(res, ctx):
+    return [f"In {title}: split edges={d['edges']} threshold={d['threshold']} rounds={d['iterations']} "
+            f"P={d['precision']} R={d['recall']} F1={d['f1']}" for title, d in _per_set(res, "split")]
+
+
+def check_curves_args(args, fail):
+    if getattr(args, "curves", None) and args.mode != "evaluate":
+        fail(f"--curves draws the curves of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+def curves_report(ctx):
+    """--curves PATH: the ROC curve (drop_intermediate on, as the reference's roc_curve call) and the precision-recall curve (off,
+    sklearn's default) of each index set, written by rank 0 as one .npz.  Returns {"curves_<name>": point counts and best F1}."""
+    out, arrays = {}, {}
+    for name, ix in ctx.sets.items():
+        c = engine.rank_curves(ctx.real, ctx.inference_adj, ix)
+        pr = engine.precision_recall_curve(ctx.real, ctx.inference_adj, ix)
+        for k, t in zip(("fpr", "tpr", "thresholds"), c["roc"]):
+            arrays[f"roc_{k}_{name}"] = t.cpu().numpy()
+        for k, t in zip(("precision", "recall", "thresholds"), pr):
+            arrays[f"pr_{k}_{name}"] = t.cpu().numpy()
+        out[f"curves_{name}"] = {"roc_points": c["roc_points"], "pr_points": int(pr[2].numel()), "levels": c["levels"],
+                                 "best_f1": c["best_f1"]["f1"], "best_threshold": c["best_f1"]["threshold"]}
+    if ctx.rank == 0:
+        _save_npz(ctx.args.curves, **arrays)
+    return out
+
+
+def _curves_log(res, ctx):
+    return ["\t".join(f"In {title}: ROC points={d['roc_points']} PR points={d['pr_points']} levels={d['levels']} "
+                      f"best F1={d['best_f1']} at {d['best_threshold']}" for title, d in _per_set(res, "curves"))]
+
+
+def check_per_node_args(args, fail):
+    if getattr(args, "per_node", None) and args.mode != "evaluate":
+        fail(f"--per_node ranks each node's row of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+def per_node_report(ctx):
+    """--per_node PATH: engine.node_rank_metrics of each index set, the integer columns and the per-node AUC written by rank 0
+    as one .npz at PATH while they are at hand.  Returns {"per_node_<name>": the set's summary dict}."""
+    out, arrays = {}, {}
+    for name, ix in ctx.sets.items():
+        m = engine.node_rank_metrics(ctx.real, ctx.inference_adj, ix)
+        for k in ("nodes", "positives", "wins", "ties", "hits", "first_rank"):
+            arrays[f"{k}_{name}"] = m[k].cpu().numpy()
+        arrays[f"auc_{name}"] = m["auc"]
+        out[f"per_node_{name}"] = m["summary"]
+    if ctx.rank == 0:
+        _save_npz(ctx.args.per_node, **arrays)
+    return out
+
+
+def _per_node_log(res, ctx):
+    return [f"In {title}: scored nodes={d['scored']} macro AUC={d['macro_auc']} MRR={d['mrr']} "
+            f"Hits@1={d['hits_at_1']} R-precision={d['r_precision']}" for title, d in _per_set(res, "per_node")]
+
+
+def check_ci_args(args, fail):
+    ci, versus, scores = getattr(args, "ci", False), getattr(args, "versus", None), getattr(args, "save_scores", None)
+    if versus is not None and not ci and not getattr(args, "ci_nodes", False):
+        fail("--versus needs --ci or --ci_nodes")
+    if versus is not None and versus == "":
+        fail("--versus takes `features` or the path of an .npy score matrix")
+    if ci and args.mode != "evaluate":
+        fail(f"--ci puts an interval on the AUC of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+    if scores is not None and args.mode != "evaluate":
+        fail(f"--save_scores writes the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+    if scores is not None and scores == "":
+        fail("--save_scores takes the path of the .npy to write")
+
+
+def check_ci_nodes_args(args, fail):
+    nodes, path = getattr(args, "ci_nodes", False), getattr(args, "save_influence", None)
+    if nodes and args.mode != "evaluate":
+        fail(f"--ci_nodes jackknifes the AUC of the attack's modified_adj over its nodes: --mode evaluate only, not --mode {args.mode}")
+    if path is not None and not nodes:
+        fail("--save_influence needs --ci_nodes")
+    if path is not None and path == "":
+        fail("--save_influence takes the path of the .npz to write")
+
+
+def load_versus(path, n):
+    """--versus PATH: the .npy at `path` as an n x n float32 matrix; anything else is refused by name."""
+    try:
+        other = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--versus {path}: not a readable .npy ({e})")
+    if other.shape != (n, n):
+        raise SystemExit(f"--versus {path}: a matrix of shape {tuple(other.shape)}; this graph's modified_adj is {n} x {n}")
+    return torch.from_numpy(np.ascontiguousarray(other, dtype=np.float32))
+
+
+def save_scores(path, inference_adj):
+    """--save_scores: modified_adj as a float32 .npy (what --versus PATH reads)."""
+    with open(path, "wb") as f:
+        np.save(f, inference_adj.detach().to(torch.float32).cpu().numpy())
+
+
+def interval_report(real, inference_adj, sets, other, single, paired, key, versus_key):
+    """{"<key>_<name>": single(real, inference_adj, ix, CI_LEVEL)} over the index sets; with `other` (--versus: a second n x n
+    score matrix) paired(real, inference_adj, other, ix, CI_LEVEL) instead, whose "a" is that dict, as "<versus_key>_<name>" too."""
+    out = {}
+    for name, ix in sets.items():
+        if other is None:
+            out[f"{key}_{name}"] = single(real, inference_adj, ix, CI_LEVEL)
+        else:
+            d = paired(real, inference_adj, other.to(inference_adj.device), ix, CI_LEVEL)
+            out[f"{key}_{name}"] = d["a"]
+            out[f"{versus_key}_{name}"] = d
+    return out
+
+
+def ci_report(real, inference_adj, sets, other=None):
+    """--ci: DeLong's interval of each index set (engine.auc_delong / engine.auc_delong_paired): ci_<name>, versus_<name>."""
+    return interval_report(real, inference_adj, sets, other, engine.auc_delong, engine.auc_delong_paired, "ci", "versus")
+
+
+def _se_ratio(res, ctx, name):
+    """` se_nodes/se=<the jackknife's standard error over DeLong's, NaN where that is zero>` of one index set: only beside --ci."""
+    if not getattr(ctx.args, "ci", False):
+        return ""
+    nodes, pairs = res[f"ci_nodes_{name}"], res[f"ci_{name}"]
+    return f" se_nodes/se={nodes['se'] / pairs['se'] if pairs['se'] > 0 else float('nan')}"
+
+
+def _ci_console(res, ctx):
+    d = res["ci_all"]
+    lines = [f"current auc_pairs={d['auc']} se={d['se']} ci=[{d['ci_low']}, {d['ci_high']}]"]
+    if ctx.other is not None:
+        d = res["versus_all"]
+        lines.append(f"current delta={d['delta']} z={d['z']} p={d['p_value']}")
+    return lines
+
+
+def _ci_log(res, ctx):
+    lines = []
+    for title, name in SET_TITLES:
+        d = res[f"ci_{name}"]
+        lines.append(f"In {title}: pairs={d['pairs']} positives={d['positives']} AUC of pairs={d['auc']} se={d['se']} "
+                     f"{int(round(100 * d['level']))}% CI=[{d['ci_low']}, {d['ci_high']}]")
+        if ctx.other is not None:
+            d = res[f"versus_{name}"]
+            lines.append(f"In {title}: versus {ctx.versus}: AUC={d['b']['auc']} delta={d['delta']} se={d['se_delta']} "
+                         f"z={d['z']} p={d['p_value']}")
+    return lines
+
+
+def _ci_nodes_console(res, ctx):
+    d = res["ci_nodes_all"]
+    lines = [f"current auc_pairs={d['auc']} se_nodes={d['se']} ci_nodes=[{d['ci_low']}, {d['ci_high']}]{_se_ratio(res, ctx, 'all')}"]
+    if ctx.other is not None:
+        d = res["versus_nodes_all"]
+        lines.append(f"current delta={d['delta']} se_nodes={d['se_delta']} z={d['z']} p={d['p_value']}")
+    return lines
+
+
+def _ci_nodes_log(res, ctx):
+    lines = []
+    for title, name in SET_TITLES:
+        d = res[f"ci_nodes_{name}"]
+        lines.append(f"In {title}: nodes={d['nodes']} pairs={d['pairs']} AUC of pairs={d['auc']} jackknife AUC={d['auc_jackknife']} "
+                     f"se_nodes={d['se']} {int(round(100 * d['level']))}% CI_nodes=[{d['ci_low']}, {d['ci_high']}] "
+                     f"undefined_nodes={d['undefined_nodes']}{_se_ratio(res, ctx, name)}")
+        if ctx.other is not None:
+            d = res[f"versus_nodes_{name}"]
+            lines.append(f"In {title}: versus {ctx.versus} (nodes): AUC={d['b']['auc']} delta={d['delta']} "
+                         f"se_nodes={d['se_delta']} z={d['z']} p={d['p_value']}")
+    return lines
+
+
+def save_influence(res, ctx):
+    """--save_influence: the jackknife's five int64 columns and d_v = AUC - AUC_-v (float64, NaN where deleting v leaves no AUC)."""
+    _save_per_set(ctx.args.save_influence, res, "ci_nodes", ctx, lambda d: {
+        **{k: np.asarray(d["ints"][k], dtype=np.int64) for k in engine.NODE_JACKKNIFE_COLUMNS}, "influence": d["influence"].numpy()})
+
+
+def structure_source(source):
+    """--structure SOURCE as "split", "edges" or a finite float; None for anything else."""
+    if source in ("split", "edges"):
+        return source
+    try:
+        thr = float(source)
+    except (TypeError, ValueError):
+        return None
+    return thr if np.isfinite(thr) else None
+
+
+def check_structure_args(args, fail):
+    source, path = getattr(args, "structure", None), getattr(args, "save_structure", None)
+    if path is not None and source is None:
+        fail("--save_structure needs --structure")
+    if path is not None and path == "":
+        fail("--save_structure takes the path of the .npz to write")
+    if source is not None and args.mode != "evaluate":
+        fail(f"--structure measures the graph cut out of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+    if source is not None and structure_source(source) is None:
+        fail(f"--structure takes `split`, `edges` or a finite threshold, not {source!r}")
+
+
+def structure_threshold(source, real, inference_adj, ix):
+    """The threshold of one index set for --structure SOURCE (structure_source's value); +inf, the empty graph, for a degenerate
+    split or a set without true edges."""
+    if source == "split":
+        d = engine.two_means_split(inference_adj, ix)
+        return float("inf") if d["degenerate"] else d["threshold"]
+    if source == "edges":
+        d = engine.topk_metrics(real, inference_adj, 0, ix)
+        return d["threshold"] if d["k"] else float("inf")
+    return float(source)
+
+
+def structure_report(ctx):
+    """--structure: {"structure_<name>": engine.graph_structure of the index set at its structure_threshold, beside the true graph}."""
+    source, real, pred = structure_source(ctx.args.structure), ctx.real, ctx.inference_adj
+    return {f"structure_{name}": engine.graph_structure(pred, structure_threshold(source, real, pred, ix), ix, real)
+            for name, ix in ctx.sets.items()}
+
+
+def _structure_console(res, ctx):
+    d = res["structure_all"]
+    q = d["stats"]
+    return [f"current transitivity={q['recovered']['transitivity']} (true {q['true']['transitivity']}) "
+            f"triangles={d['T_C']}/{d['T_G']} degree_corr={q['degree_corr']} degree_ks={q['degree_ks']}"]
+
+
+def _structure_log(res, ctx):
+    lines = []
+    for title, d in _per_set(res, "structure"):
+        q = d["stats"]
+        lines.append(f"In {title}: structure at {d['threshold']}: edges={d['E_R']} (true {d['E_G']}, shared {d['E_C']}) "
+                     f"triangles={d['T_R']} (true {d['T_G']}, shared {d['T_C']}) "
+                     f"transitivity={q['recovered']['transitivity']} (true {q['true']['transitivity']}) "
+                     f"clustering={q['recovered']['avg_clustering']} (true {q['true']['avg_clustering']}) "
+                     f"degree_corr={q['degree_corr']} degree_ks={q['degree_ks']} degree_l1={q['degree_l1']}")
+    return lines
+
+
+def save_structure(res, ctx):
+    """--save_structure: the six int64 columns of engine.graph_structure and the threshold (float32)."""
+    _save_per_set(ctx.args.save_structure, res, "structure", ctx, lambda d: {
+        **{k: d[k].cpu().numpy() for k in engine.GRAPH_STRUCTURE_COLUMNS}, "threshold": np.float32(d["threshold"])})
+
+
+def _saver(flag, write):
+    """write(res, ctx) when the --save_* flag names a file."""
+    return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
+
+
+# in the order in which the reports are computed, printed and logged
+REPORTS = (
+    Report(flags=("topk", "save_edges"), check=check_topk_args, wanted=_on("topk", given=True),
+           compute=lambda ctx: topk_report(ctx.real, ctx.inference_adj, ctx.sets, ctx.args.topk),
+           console=lambda res, ctx: [f"current f1={res['topk_all']['f1']} (k={res['topk_all']['k']})"],
+           log=_topk_log, save=_saver("save_edges", save_edges)),
+    Report(flags=("binarize", "save_graph"), check=check_binarize_args, wanted=_on("binarize"),    # split_<set>: the 2-means split
+           compute=lambda ctx: {f"split_{s}": engine.two_means_split(ctx.inference_adj, ix, ctx.real) for s, ix in ctx.sets.items()},
+           console=lambda res, ctx: ["current split_f1={f1} (edges={edges}, threshold={threshold})".format(**res["split_all"])],
+           log=_binarize_log, save=_saver("save_graph", save_graph)),
+    Report(flags=("curves",), check=check_curves_args, wanted=_on("curves"), compute=curves_report,
+           console=lambda res, ctx: ["current best_f1={best_f1} (threshold={best_threshold})".format(**res["curves_all"])],
+           log=_curves_log),
+    Report(flags=("per_node",), check=check_per_node_args, wanted=_on("per_node"), compute=per_node_report,
+           console=lambda res, ctx: ["current macro_auc={macro_auc} mrr={mrr} hits@1={hits_at_1}".format(**res["per_node_all"])],
+           log=_per_node_log),
+    Report(flags=("ci",), check=check_ci_args, wanted=_on("ci"),
+           compute=lambda ctx: ci_report(ctx.real, ctx.inference_adj, ctx.sets, ctx.other), console=_ci_console, log=_ci_log),
+    Report(flags=("ci_nodes", "save_influence"), check=check_ci_nodes_args, wanted=_on("ci_nodes"),
+           compute=lambda ctx: interval_report(ctx.real, ctx.inference_adj, ctx.sets, ctx.other, engine.auc_node_jackknife,
+                                               engine.auc_node_jackknife_paired, "ci_nodes", "versus_nodes"),
+           console=_ci_nodes_console, log=_ci_nodes_log, save=_saver("save_influence", save_influence)),
+    Report(flags=("structure", "save_structure"), check=check_structure_args, wanted=_on("structure", given=True),
+           compute=structure_report, console=_structure_console, log=_structure_log, save=_saver("save_structure", save_structure)),
+)
+
+
+def shown_parameters(args):
+    """The namespace that the log's parameter line prints: args without `ap` while --ap is off and without the flags of every
+    report that is off, so that a run without a flag logs what it logged before the flag existed."""
+    hidden = set() if getattr(args, "ap", False) else {"ap"}
+    for r in REPORTS:
+        if not r.wanted(args):
+            hidden.update(r.flags)
+    return argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})

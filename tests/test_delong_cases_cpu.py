@@ -413,6 +413,7 @@ def test_engine_entries_refuse_wrong_shapes_host_tensors_and_levels(pkg):
 # ---------------------------------------------------------------------------------------------------- command line
 def test_parser_ci_flags_are_absent_by_default_and_evaluate_only(pkg, capsys, tmp_path):
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     p = M.build_parser()
     plain = p.parse_args([])
     assert not any(hasattr(plain, k) for k in ("ci", "versus", "save_scores"))
@@ -438,20 +439,20 @@ def test_parser_ci_flags_are_absent_by_default_and_evaluate_only(pkg, capsys, tm
     with pytest.raises(SystemExit, match="evaluate only"):
         M._run(argparse.Namespace(save_scores="s.npy", mode="notrain_test"), 0, 1)
     calls = []
-    M.check_ci_args(argparse.Namespace(mode="prepare"), calls.append)
-    M.check_ci_args(argparse.Namespace(ci=True, versus="x.npy", save_scores="s.npy", mode="evaluate"), calls.append)
-    M.check_ci_args(argparse.Namespace(ci=True, mode="evaluate"), calls.append)
+    R.check_ci_args(argparse.Namespace(mode="prepare"), calls.append)
+    R.check_ci_args(argparse.Namespace(ci=True, versus="x.npy", save_scores="s.npy", mode="evaluate"), calls.append)
+    R.check_ci_args(argparse.Namespace(ci=True, mode="evaluate"), calls.append)
     assert calls == []
-    M.check_ci_args(argparse.Namespace(ci=True, versus="", mode="evaluate"), calls.append)
-    M.check_ci_args(argparse.Namespace(save_scores="", mode="evaluate"), calls.append)
+    R.check_ci_args(argparse.Namespace(ci=True, versus="", mode="evaluate"), calls.append)
+    R.check_ci_args(argparse.Namespace(save_scores="", mode="evaluate"), calls.append)
     assert len(calls) == 2 and "features" in calls[0] and ".npy" in calls[1]
     # --versus PATH: a matrix of another shape, or no .npy at all, is refused by name
     path = str(tmp_path / "other.npy")
     np.save(path, np.zeros((4, 5), np.float32))
     with pytest.raises(SystemExit, match=r"other\.npy.*\(4, 5\).*7 x 7"):
-        M.load_versus(path, 7)
+        R.load_versus(path, 7)
     with pytest.raises(SystemExit, match=r"missing\.npy"):
-        M.load_versus(str(tmp_path / "missing.npy"), 7)
+        R.load_versus(str(tmp_path / "missing.npy"), 7)
     np.save(path, np.arange(49, dtype=np.float64).reshape(7, 7))
-    t = M.load_versus(path, 7)
+    t = R.load_versus(path, 7)
     assert tuple(t.shape) == (7, 7) and str(t.dtype) == "torch.float32" and float(t[6, 6]) == 48.0

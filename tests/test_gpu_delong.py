@@ -224,6 +224,7 @@ def test_main_evaluate_ci_versus_and_save_scores(pkg, tmp_path, monkeypatch, cap
     round-trips through --versus PATH to delta = 0, z = 0, p = 1; a run without the flags returns and logs what it did before
     the flags existed."""
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     root = os.path.join(H.GOLDEN, "dataset")
     monkeypatch.chdir(tmp_path)
     argv = ["--dataset", "usair", "--dataset_root", root, "--epochs", "3", "--measure", "MSELoss", "--w2", "100", "--w6", "100",
@@ -283,7 +284,7 @@ def test_main_evaluate_ci_versus_and_save_scores(pkg, tmp_path, monkeypatch, cap
         assert v["a"] == res[f"ci_{name}"]
     # --ci alone is the single entry: the same dicts, no versus_* keys
     sets = {"attack": seen[0][3], "train": seen[1][3], "all": None}
-    alone = M.ci_report(_dev(real), _dev(pa), sets)
+    alone = R.ci_report(_dev(real), _dev(pa), sets)
     assert sorted(alone) == ["ci_all", "ci_attack", "ci_train"]
     for name in sets:
         assert alone[f"ci_{name}"] == res[f"ci_{name}"], name

@@ -254,6 +254,7 @@ def test_main_evaluate_structure_and_save_structure(pkg, tmp_path, monkeypatch, 
     --save_structure writes the six columns of each set; --structure edges cuts at the P-th best score; a run without the flags
     returns and logs what it did before the flags existed."""
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     root = os.path.join(H.GOLDEN, "dataset")
     monkeypatch.chdir(tmp_path)
     argv = ["--dataset", "usair", "--dataset_root", root, "--epochs", "3", "--measure", "MSELoss", "--w2", "100", "--w6", "100",
@@ -319,6 +320,6 @@ def test_main_evaluate_structure_and_save_structure(pkg, tmp_path, monkeypatch, 
         s = np.sort(TM.K.packed(real, pred, idx)[0])[::-1]
         assert thr == float(s[v["E_G"] - 1]) and v["E_R"] == int((s >= np.float32(thr)).sum())
     real, pred, idx, _, _ = seen[0]
-    assert M.structure_threshold(M.structure_source("0.25"), _dev(real), _dev(pred), idx) == 0.25
-    assert M.structure_threshold("edges", _dev(np.zeros_like(real)), _dev(pred), idx) == float("inf")      # P = 0: the empty graph
-    assert M.structure_threshold("split", None, _dev(np.full_like(pred, 0.5)), idx) == float("inf")        # a degenerate split
+    assert R.structure_threshold(R.structure_source("0.25"), _dev(real), _dev(pred), idx) == 0.25
+    assert R.structure_threshold("edges", _dev(np.zeros_like(real)), _dev(pred), idx) == float("inf")      # P = 0: the empty graph
+    assert R.structure_threshold("split", None, _dev(np.full_like(pred, 0.5)), idx) == float("inf")        # a degenerate split

@@ -284,11 +284,12 @@ def test_main_evaluate_topk_and_save_edges(pkg, tmp_path, monkeypatch, capsys):
 
 
 def test_main_topk_report_clamps_k_to_the_pair_count(pkg):
-    """--topk K above a set's pair count: k = m in the returned dict (main.topk_report), everything taken."""
+    """--topk K above a set's pair count: k = m in the returned dict (reports.topk_report), everything taken."""
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     real, pred, _, _ = CASES["n80_continuous_asym"]
     sub = np.arange(5, 25)
-    rep = M.topk_report(_dev(real), _dev(pred), {"all": None, "sub": sub}, 10 ** 9)
+    rep = R.topk_report(_dev(real), _dev(pred), {"all": None, "sub": sub}, 10 ** 9)
     for key, idx in (("topk_all", None), ("topk_sub", sub)):
         d = rep[key]
         _check_metrics(d, T.top_k(real, pred, T.top_k(real, pred, 1, idx)["pairs"], idx), key)

@@ -336,6 +336,7 @@ def test_engine_entry_refuses_wrong_shapes_and_host_tensors(pkg):
 # ---------------------------------------------------------------------------------------------------- command line
 def test_parser_structure_flags_are_absent_by_default_and_evaluate_only(pkg, capsys):
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     p = M.build_parser()
     plain = p.parse_args([])
     assert not any(hasattr(plain, k) for k in ("structure", "save_structure"))
@@ -344,10 +345,10 @@ def test_parser_structure_flags_are_absent_by_default_and_evaluate_only(pkg, cap
     assert a.structure == "split" and a.save_structure == "s.npz"
     assert p.parse_args(["--structure", "edges"]).structure == "edges" and p.parse_args(["--structure", "0.9"]).structure == "0.9"
     assert p.parse_args(["--structure=-0.25"]).structure == "-0.25"
-    assert (M.structure_source("split"), M.structure_source("edges"), M.structure_source("0.9"), M.structure_source("-1e-3")) == \
+    assert (R.structure_source("split"), R.structure_source("edges"), R.structure_source("0.9"), R.structure_source("-1e-3")) == \
         ("split", "edges", 0.9, -0.001)
     for bad in ("", "Split", "kmeans", "nan", "inf", "-inf", "0.5x"):
-        assert M.structure_source(bad) is None
+        assert R.structure_source(bad) is None
         with pytest.raises(SystemExit):
             p.parse_args([f"--structure={bad}"])
         assert "`split`, `edges` or a finite threshold" in capsys.readouterr().err
@@ -369,6 +370,6 @@ def test_parser_structure_flags_are_absent_by_default_and_evaluate_only(pkg, cap
     with pytest.raises(SystemExit, match="needs --structure"):
         M._run(argparse.Namespace(save_structure="s.npz", mode="evaluate"), 0, 1)
     calls = []
-    M.check_structure_args(argparse.Namespace(mode="prepare"), calls.append)
-    M.check_structure_args(argparse.Namespace(structure="0.5", save_structure="s.npz", mode="evaluate"), calls.append)
+    R.check_structure_args(argparse.Namespace(mode="prepare"), calls.append)
+    R.check_structure_args(argparse.Namespace(structure="0.5", save_structure="s.npz", mode="evaluate"), calls.append)
     assert calls == []

@@ -387,6 +387,7 @@ def test_engine_entries_refuse_wrong_shapes_host_tensors_and_levels(pkg):
 # ---------------------------------------------------------------------------------------------------- command line
 def test_parser_ci_nodes_flags_are_absent_by_default_and_evaluate_only(pkg, capsys):
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     p = M.build_parser()
     plain = p.parse_args([])
     assert not any(hasattr(plain, k) for k in ("ci_nodes", "save_influence"))
@@ -416,9 +417,9 @@ def test_parser_ci_nodes_flags_are_absent_by_default_and_evaluate_only(pkg, caps
     with pytest.raises(SystemExit, match="needs --ci_nodes"):
         M._run(argparse.Namespace(save_influence="i.npz", mode="evaluate"), 0, 1)
     calls = []
-    M.check_ci_nodes_args(argparse.Namespace(mode="prepare"), calls.append)
-    M.check_ci_nodes_args(argparse.Namespace(ci_nodes=True, save_influence="i.npz", mode="evaluate"), calls.append)
-    M.check_ci_args(argparse.Namespace(ci_nodes=True, versus="x.npy", mode="evaluate"), calls.append)
+    R.check_ci_nodes_args(argparse.Namespace(mode="prepare"), calls.append)
+    R.check_ci_nodes_args(argparse.Namespace(ci_nodes=True, save_influence="i.npz", mode="evaluate"), calls.append)
+    R.check_ci_args(argparse.Namespace(ci_nodes=True, versus="x.npy", mode="evaluate"), calls.append)
     assert calls == []
-    M.check_ci_nodes_args(argparse.Namespace(ci_nodes=True, save_influence="", mode="evaluate"), calls.append)
+    R.check_ci_nodes_args(argparse.Namespace(ci_nodes=True, save_influence="", mode="evaluate"), calls.append)
     assert len(calls) == 1 and ".npz" in calls[0]

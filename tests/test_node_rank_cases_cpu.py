@@ -220,6 +220,7 @@ def test_node_rates_of_the_wrapper_are_the_truths(pkg):
 # ---------------------------------------------------------------------------------------------------- command line
 def test_parser_per_node_is_absent_by_default_and_evaluate_only(pkg, capsys):
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     p = M.build_parser()
     assert p.parse_args([]).per_node is None
     assert p.parse_args(["--per_node", "n.npz"]).per_node == "n.npz"
@@ -231,21 +232,28 @@ def test_parser_per_node_is_absent_by_default_and_evaluate_only(pkg, capsys):
     with pytest.raises(SystemExit, match="evaluate only"):
         M._run(argparse.Namespace(per_node="n.npz", mode="prepare"), 0, 1)
     calls = []
-    M.check_per_node_args(argparse.Namespace(per_node=None, mode="prepare"), calls.append)
-    M.check_per_node_args(argparse.Namespace(mode="prepare"), calls.append)
-    M.check_per_node_args(argparse.Namespace(per_node="x", mode="evaluate"), calls.append)
+    R.check_per_node_args(argparse.Namespace(per_node=None, mode="prepare"), calls.append)
+    R.check_per_node_args(argparse.Namespace(mode="prepare"), calls.append)
+    R.check_per_node_args(argparse.Namespace(per_node="x", mode="evaluate"), calls.append)
     assert calls == []
 
 
 def test_per_node_is_hidden_from_the_parameter_line_when_unset(pkg):
-    """The log's parameter line is built from vars(args) minus `hidden`; per_node joins that set exactly when it is unset."""
-    import inspect
+    """The log's parameter line prints reports.shown_parameters(args): per_node is in it exactly when --per_node is set, and each
+    of the flags that are hidden while unset brings exactly its own names."""
     from mc_gra_amd import main as M
-    src = inspect.getsource(M._run)
-    assert '(set() if want_per_node else {"per_node"})' in src and 'want_per_node = bool(getattr(args, "per_node", None))' in src
+    from mc_gra_amd import reports as R
+    older = ("ap", "topk", "save_edges", "curves", "per_node", "binarize", "save_graph")
     args = M.build_parser().parse_args([])
-    shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in {"ap", "topk", "save_edges", "curves", "per_node"}})
-    assert "per_node" not in str(shown) and "per_node" in str(args)
+    assert all(f" {k}=" in str(args) for k in older)
+    assert not any(f" {k}=" in str(R.shown_parameters(args)) for k in older)
+    for argv, own in ((["--per_node", "n.npz"], ("per_node",)), (["--ap"], ("ap",)), (["--topk", "0"], ("topk", "save_edges")),
+                      (["--topk", "5", "--save_edges", "e.npz"], ("topk", "save_edges")), (["--curves", "c.npz"], ("curves",)),
+                      (["--binarize"], ("binarize", "save_graph"))):
+        args = M.build_parser().parse_args(argv)
+        text = str(R.shown_parameters(args))
+        assert [k for k in older if f" {k}=" in text] == list(own), (argv, text)
+        assert all(f" {k}={getattr(args, k)!r}" in text for k in own)
 
 
 # --------------------------------------------------------------------------------- the inputs of the GPU test cases

@@ -262,6 +262,7 @@ def test_engine_entries_refuse_wrong_shapes_and_host_tensors(pkg):
 # ---------------------------------------------------------------------------------------------------- command line
 def test_parser_binarize_is_absent_by_default_and_evaluate_only(pkg, capsys):
     from mc_gra_amd import main as M
+    from mc_gra_amd import reports as R
     p = M.build_parser()
     assert p.parse_args([]).binarize is False and p.parse_args([]).save_graph is None
     a = p.parse_args(["--binarize", "--save_graph", "g.npz"])
@@ -280,20 +281,24 @@ def test_parser_binarize_is_absent_by_default_and_evaluate_only(pkg, capsys):
     with pytest.raises(SystemExit, match="needs --binarize"):
         M._run(argparse.Namespace(binarize=False, save_graph="g.npz", mode="evaluate"), 0, 1)
     calls = []
-    M.check_binarize_args(argparse.Namespace(binarize=False, save_graph=None, mode="prepare"), calls.append)
-    M.check_binarize_args(argparse.Namespace(mode="prepare"), calls.append)
-    M.check_binarize_args(argparse.Namespace(binarize=True, save_graph="x", mode="evaluate"), calls.append)
+    R.check_binarize_args(argparse.Namespace(binarize=False, save_graph=None, mode="prepare"), calls.append)
+    R.check_binarize_args(argparse.Namespace(mode="prepare"), calls.append)
+    R.check_binarize_args(argparse.Namespace(binarize=True, save_graph="x", mode="evaluate"), calls.append)
     assert calls == []
 
 
 def test_binarize_is_hidden_from_the_parameter_line_when_unset(pkg):
-    """The log's parameter line is built from vars(args) minus `hidden`; the two flags join that set exactly when unset."""
-    import inspect
+    """The log's parameter line prints reports.shown_parameters(args): the two flags are in it exactly when --binarize is set,
+    and none of the other flags that are hidden while unset comes with them."""
     from mc_gra_amd import main as M
-    src = inspect.getsource(M._run)
-    assert '(set() if want_split else {"binarize", "save_graph"})' in src
-    assert 'want_split = bool(getattr(args, "binarize", False))' in src
+    from mc_gra_amd import reports as R
+    older = ("ap", "topk", "save_edges", "curves", "per_node", "binarize", "save_graph")
     args = M.build_parser().parse_args([])
-    hidden = {"ap", "topk", "save_edges", "curves", "per_node", "binarize", "save_graph"}
-    shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
-    assert "binarize" not in str(shown) and "save_graph" not in str(shown) and "binarize" in str(args)
+    assert all(f" {k}=" in str(args) for k in older)
+    assert not any(f" {k}=" in str(R.shown_parameters(args)) for k in older)
+    for argv, own in ((["--binarize"], ("binarize", "save_graph")), (["--binarize", "--save_graph", "g.npz"], ("binarize", "save_graph"))):
+        args = M.build_parser().parse_args(argv)
+        text = str(R.shown_parameters(args))
+        assert [k for k in older if f" {k}=" in text] == list(own), (argv, text)
+        assert f"binarize=True, save_graph={args.save_graph!r}" in text
+        assert vars(R.shown_parameters(args)) == {k: v for k, v in vars(args).items() if k not in set(older) - set(own)}
