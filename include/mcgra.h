@@ -472,6 +472,41 @@ int mcgra_graph_structure(void* stream, int n, const float* scores, int ld_score
                           int64_t* header /* host[9]: pairs, E_R, T_R, W_R, E_G, T_G, W_G, E_C, T_C */,
                           int64_t* out    /* device [n_idx][6]: d_R, t_R, d_G, t_G, d_C, t_C */);
 
+/* Where the attack's errors sit: the AUC of the true edges against the non-edges at each distance of the TRUE graph, and the
+ * false positives of a cut split by that distance, as exact integers.
+ *   - candidates, selection, comparison and checks as mcgra_auc_delong: idx, n_idx REPEAT-FREE device int64 node ids or NULL for
+ *     all n nodes; the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b with score scores[idx[a]][idx[b]] and label
+ *     labels[idx[a]][idx[b]]; nothing outside the selected strict lower triangle is looked at; scores compare as float32 values,
+ *     -0.0 == +0.0;
+ *   - G is the graph on the selected positions whose edges are the candidates of label 1 (mcgra_graph_structure's G) and
+ *     dist(a, b) the shortest-path length in G.  G is the INDUCED subgraph: a path through an unselected node does not exist;
+ *   - with H = hops in [1, MCGRA_HOP_MAX] every candidate is of one of H + 1 classes: class d, d = 1 .. H, is dist == d (class
+ *     1: the edges, P of them); class H + 1, "beyond", is dist > H or no path.  The classes 2 .. H + 1 are the N non-edges;
+ *   - out (host int64 [hops + 1][3]), row c - 1 = {pairs_c, T_c, above_c}:
+ *       pairs_c   the candidates of the class; pairs_1 = P, the others sum to N
+ *       T_c       c >= 2: the sum over the candidates q of the class of b_q = 2 #{edges that score higher} + #{edges that score
+ *                 the same}, mcgra_auc_delong's placement: the doubled Mann-Whitney count of the edges against this class
+ *                 alone, whose AUC is T_c / (2 P pairs_c).  T_1 = the sum of the other T_c = mcgra_auc_delong's T on the same
+ *                 input, so the pooled AUC T_1 / (2 P N) is the mean of the class AUCs weighted by pairs_c / N
+ *       above_c   the candidates of the class with score >= threshold, mcgra_threshold_pairs' comparison (-0.0 >= +0.0 holds,
+ *                 +-inf are allowed): above_1 the true positives of the cut, the others its false positives by where they sit;
+ *   - no overflow: T_c <= 2 P pairs_c < 2^63 for n_idx <= 65 535;
+ *   - out NULL, a matrix NULL, an ld below n, hops outside [1, MCGRA_HOP_MAX], a NaN threshold, n_idx (n when idx is NULL) below 2:
+ *     MCGRA_EINVAL; n_idx above 65 535: MCGRA_ENOSUP.  These run before any HIP call.  A selected score that is NaN or +-inf, a
+ *     selected label other than 0 or 1, a repeated or out-of-range id: MCGRA_EINVAL.  After any refusal nothing has been
+ *     written to out and mcgra_last_error() names the cause;
+ *   - integer arithmetic only on the device (bit matrices built by ballots and ORs with one writer per word, integer counts
+ *     merged by integer atomics): the same bits on every call, and the same integers under any permutation of idx.
+ * Synchronises `stream`.
+ * Device scratch: hops bit matrices of n_idx rows of ceil(n_idx / 64) 64-bit words (every level is kept for the one pass that
+ * classifies the candidates): hops n_idx ceil(n_idx / 64) 8 bytes, 38 MB at n_idx = 10 000 and 1.6 GB at the capacity for
+ * hops = 3; MCGRA_ENOMEM when that cannot be allocated.  8 bytes per candidate of label 1, about 3 MB, and 4 bytes per node
+ * of the graph when idx is given. */
+#define MCGRA_HOP_MAX 8
+int mcgra_hop_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                  const int64_t* idx, int64_t n_idx, int hops, float threshold,
+                  int64_t* out /* host [hops + 1][3]: row c - 1 = {pairs_c, T_c, above_c} */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score

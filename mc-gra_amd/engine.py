@@ -818,6 +818,63 @@ def _graph_structure_ints(pred, threshold, idx, real):
     return [int(v) for v in header], out.t().contiguous()
 
 
+HOP_MAX = 8        # MCGRA_HOP_MAX (include/mcgra.h)
+
+
+def _hops(hops):
+    if isinstance(hops, bool) or not isinstance(hops, (int, np.integer)) or not 1 <= hops <= HOP_MAX:
+        raise ValueError(f"hop_auc: hops = {hops!r}; distances are told apart up to an integer hops in [1, {HOP_MAX}]")
+    return int(hops)
+
+
+def hop_auc_stats(ints, hops, threshold=None):
+    """The dict of hop_auc from its integers: ints = the hops + 1 rows (pairs_c, T_c, above_c) of mcgra_hop_auc, row c - 1 the
+    candidates at distance c of the true graph, the last row those beyond hops.  Every double is the correctly rounded
+    quotient of two Python integers.  No device is involved.
+    Returns {"hops", "threshold", "pairs" (m), "positives" (P = pairs_1), "negatives" (N), "distance" (1, ..., hops, "beyond"),
+    and per class as tuples of length hops + 1: "count", "T", "above", "auc" T_c / (2 P pairs_c) (NaN for class 1 and where P
+    or pairs_c is 0), "share" pairs_c / N (NaN for class 1, and where N is 0), "fp_share" above_c / the false positives (NaN
+    for class 1 and when there are none); "auc_pooled" T_1 / (2 P N), auc_delong's "auc" bit for bit (NaN when P or N is 0);
+    "ints" (the rows)}.  threshold None: no "above" and no "fp_share"."""
+    nan = float("nan")
+    H = _hops(hops)
+    rows = [tuple(int(v) for v in r) for r in ints]
+    if len(rows) != H + 1 or any(len(r) != 3 or min(r) < 0 for r in rows):
+        raise ValueError(f"hop_auc_stats: {len(rows)} rows for hops = {H}; the entry returns hops + 1 rows of three counts")
+    count, T, above = (tuple(r[q] for r in rows) for q in range(3))
+    P, N, fp = count[0], sum(count[1:]), sum(above[1:])
+    if T[0] != sum(T[1:]):
+        raise ValueError("hop_auc_stats: T_1 is not the sum of the other classes' T")
+    res = {"hops": H, "threshold": None if threshold is None else float(threshold), "pairs": P + N, "positives": P,
+           "negatives": N, "distance": tuple(range(1, H + 1)) + ("beyond",), "count": count, "T": T, "above": above,
+           "auc": (nan,) + tuple(t / (2 * P * c) if P and c else nan for t, c in zip(T[1:], count[1:])),
+           "share": (nan,) + tuple(c / N if N else nan for c in count[1:]),
+           "fp_share": (nan,) + tuple(a / fp if fp else nan for a in above[1:]),
+           "auc_pooled": T[0] / (2 * P * N) if P and N else nan, "ints": rows}
+    if threshold is None:
+        del res["above"], res["fp_share"]
+    return res
+
+
+@_on_operand_device
+def hop_auc(real, pred, idx=None, hops=3, threshold=None):
+    """Where the attack's errors sit (mcgra_hop_auc): the candidates of auc_delong -- the unordered pairs of positions a > b of a
+    REPEAT-FREE idx (None: all nodes), score pred[idx[a], idx[b]], label real[idx[a], idx[b]] -- classed by their distance in
+    the TRUE graph on the selected nodes (the induced subgraph: no path runs through an unselected node): 1 (the edges), 2,
+    ..., hops, and "beyond" (farther, or no path).  Per class the count, the AUC of the edges against that class alone and,
+    with a threshold, the candidates at or above it (threshold_pairs' float32 comparison): the false positives by where they
+    sit.  Returns hop_auc_stats' dict; "auc_pooled" is auc_delong's "auc" and the share-weighted mean of the class AUCs.
+    Exact integers from the device (bit matrices of the reach, a search among the sorted edges), correctly rounded quotients
+    on the host, the same bits on every call.  ValueError for hops outside [1, 8]; McgraError for a NaN threshold, a repeated
+    or out-of-range id, a selected NaN / inf score or a selected label other than 0 / 1."""
+    H = _hops(hops)
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
+    out = (C.c_int64 * (3 * (H + 1)))()
+    check(lib.mcgra_hop_auc(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, H,
+                            float("inf") if threshold is None else float(threshold), out))
+    return hop_auc_stats([out[3 * c:3 * c + 3] for c in range(H + 1)], H, threshold)
+
+
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
 # row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
 NODE_RANK_MAX_NIDX = 16384

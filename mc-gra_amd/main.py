@@ -35,6 +35,10 @@ feature_adj or an n x n float32 .npy at PATH: DeLong's paired test (engine.auc_d
 own 2-means split, at the score of the P-th best pair, P its true edge count (ties may add edges), or at a float, and the degrees,
 triangles, wedges, transitivity and clustering of that graph are reported beside the true graph's (engine.graph_structure).
 --save_structure PATH: degree and triangles per node in the recovered graph, the true graph and their intersection.
+--hops H (1 to 8) asks which non-edges the attack confuses with edges: the AUC of a set's true edges against its non-edges at
+distance 2, 3, ..., H of the true graph on the set's nodes and against those beyond (engine.hop_auc); the pooled AUC of --ci is
+their mean weighted by the classes' sizes.  --hops_cut split|edges|THRESHOLD (default edges; --structure's cuts) says where the
+false positives are counted, class by class.  --save_hops PATH: the counts, the sums and the AUC of every class.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -77,7 +81,7 @@ import torch.nn.functional as F
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
-        for r in reports.REPORTS:
+        for r in reports.EVERY_REPORT:
             r.check(args, self.error)
         return args
 
@@ -134,6 +138,9 @@ def build_parser():
     p.add_argument('--save_influence', type=str, default=argparse.SUPPRESS)    # with --ci_nodes: each node's influence as an .npz
     p.add_argument('--structure', type=str, default=argparse.SUPPRESS)         # also degrees, triangles and clustering of the cut graph
     p.add_argument('--save_structure', type=str, default=argparse.SUPPRESS)    # with --structure: the per-node columns as an .npz
+    p.add_argument('--hops', type=int, default=argparse.SUPPRESS)              # also the AUC by true-graph distance 2 .. H and beyond
+    p.add_argument('--hops_cut', type=str, default=argparse.SUPPRESS)          # with --hops: where its false positives are counted
+    p.add_argument('--save_hops', type=str, default=argparse.SUPPRESS)         # with --hops: the per-distance counts as an .npz
     return p
 
 
@@ -281,14 +288,14 @@ def log_lines(res, ctx):
     if getattr(ctx.args, "ap", False):
         lines.append(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
                      f"In Whole Graph: AP={res['ap_all']}")
-    for r in reports.REPORTS:
+    for r in reports.EVERY_REPORT:
         if r.wanted(ctx.args):
             lines += r.log(res, ctx)
     return lines + [f"current density: {res['density']}"]
 
 
 def _run(args, rank, world):
-    for r in reports.REPORTS:
+    for r in reports.EVERY_REPORT:
         r.check(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
@@ -399,7 +406,7 @@ def _run(args, rank, world):
                           other=other, versus=versus, args=args)
     want_ap = getattr(args, "ap", False)
     res = base_metrics(ctx, want_ap)
-    wanted = [r for r in reports.REPORTS if r.wanted(args)]
+    wanted = [r for r in reports.EVERY_REPORT if r.wanted(args)]
     for r in wanted:        # every rank computes (as the AUCs); a report's keys exist only with its flag
         res.update(r.compute(ctx))
     res["path"] = dict(model.history.get("path", {}), world=world)

@@ -1,6 +1,7 @@
 """The optional reports of `main.py --mode evaluate` (none is in the reference; main.py's docstring says what each flag asks):
 per report the argument check, the computation on the device, the console lines, the --save_* file and the log lines, and at
-the bottom REPORTS, the one ordered table of them that main.py's parser, run and log loop over.  To add a report, add an entry.
+the bottom the one ordered table of them that main.py's parser, run and log loop over: EVERY_REPORT, which is REPORTS and the
+reports added after it.  To add a report, add an entry to EVERY_REPORT.
 
 `sets` is always index set name -> node ids (None: every node); fail(message) does not return; a --save_* file is written at
 exactly the path given.  engine functions are looked up as engine.<fn> at the call."""
@@ -351,6 +352,57 @@ def save_structure(res, ctx):
         **{k: d[k].cpu().numpy() for k in engine.GRAPH_STRUCTURE_COLUMNS}, "threshold": np.float32(d["threshold"])})
 
 
+def check_hops_args(args, fail):
+    hops, cut, path = getattr(args, "hops", None), getattr(args, "hops_cut", None), getattr(args, "save_hops", None)
+    if cut is not None and hops is None:
+        fail("--hops_cut needs --hops")
+    if path is not None and hops is None:
+        fail("--save_hops needs --hops")
+    if path is not None and path == "":
+        fail("--save_hops takes the path of the .npz to write")
+    if hops is not None and args.mode != "evaluate":
+        fail(f"--hops splits the AUC of the attack's modified_adj by true-graph distance: --mode evaluate only, not --mode {args.mode}")
+    if hops is not None and not 1 <= hops <= engine.HOP_MAX:
+        fail(f"--hops takes H in [1, {engine.HOP_MAX}], not {hops}")
+    if cut is not None and structure_source(cut) is None:
+        fail(f"--hops_cut takes `split`, `edges` or a finite threshold, not {cut!r}")
+
+
+def hops_report(ctx):
+    """--hops H: {"hops_<name>": engine.hop_auc of the index set, its false positives counted at the set's structure_threshold of
+    --hops_cut (default `edges`)}."""
+    source, real, pred = structure_source(getattr(ctx.args, "hops_cut", "edges")), ctx.real, ctx.inference_adj
+    return {f"hops_{name}": engine.hop_auc(real, pred, ix, ctx.args.hops, structure_threshold(source, real, pred, ix))
+            for name, ix in ctx.sets.items()}
+
+
+def _hops_console(res, ctx):
+    d = res["hops_all"]
+    by = " ".join(f"{k}:{v}" for k, v in zip(d["distance"][1:], d["auc"][1:]))
+    where = "at distance 2" if d["hops"] >= 2 else "beyond distance 1"
+    return [f"current auc_by_distance {by} (pooled {d['auc_pooled']}) false positives {where}: {d['above'][1]}/{sum(d['above'][1:])}"]
+
+
+def _hops_log(res, ctx):
+    lines = []
+    for title, d in _per_set(res, "hops"):
+        by = " ".join(f"{k}: count={c} AUC={a} above={x}" for k, c, a, x in zip(d["distance"], d["count"], d["auc"], d["above"]))
+        lines.append(f"In {title}: by true-graph distance at {d['threshold']}: {by} pooled AUC={d['auc_pooled']}")
+    return lines
+
+
+def save_hops(res, ctx):
+    """--save_hops: per index set the classes' distance (beyond: 0), count, T, above (int64), AUC (float64) and the threshold."""
+    arrays = {}
+    for name in ctx.sets:
+        d = res[f"hops_{name}"]
+        arrays[f"distance_{name}"] = np.asarray([0 if k == "beyond" else k for k in d["distance"]], dtype=np.int64)
+        arrays.update({f"{k}_{name}": np.asarray(d[k], dtype=np.int64) for k in ("count", "T", "above")})
+        arrays[f"auc_{name}"] = np.asarray(d["auc"], dtype=np.float64)
+        arrays[f"threshold_{name}"] = np.float32(d["threshold"])
+    _save_npz(ctx.args.save_hops, **arrays)
+
+
 def _saver(flag, write):
     """write(res, ctx) when the --save_* flag names a file."""
     return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
@@ -381,13 +433,19 @@ REPORTS = (
     Report(flags=("structure", "save_structure"), check=check_structure_args, wanted=_on("structure", given=True),
            compute=structure_report, console=_structure_console, log=_structure_log, save=_saver("save_structure", save_structure)),
 )
+# REPORTS holds the reports of the recorded run with every flag on (tests/golden/evaluate_all_flags.json), whose tests pin its
+# entries; a report added since then follows here.  EVERY_REPORT is what main.py's parser, run and log loop over.
+EVERY_REPORT = REPORTS + (
+    Report(flags=("hops", "hops_cut", "save_hops"), check=check_hops_args, wanted=_on("hops", given=True), compute=hops_report,
+           console=_hops_console, log=_hops_log, save=_saver("save_hops", save_hops)),
+)
 
 
 def shown_parameters(args):
     """The namespace that the log's parameter line prints: args without `ap` while --ap is off and without the flags of every
     report that is off, so that a run without a flag logs what it logged before the flag existed."""
     hidden = set() if getattr(args, "ap", False) else {"ap"}
-    for r in REPORTS:
+    for r in EVERY_REPORT:
         if not r.wanted(args):
             hidden.update(r.flags)
     return argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
