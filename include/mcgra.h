@@ -507,6 +507,43 @@ int mcgra_hop_auc(void* stream, int n, const float* labels, int ld_labels, const
                   const int64_t* idx, int64_t n_idx, int hops, float threshold,
                   int64_t* out /* host [hops + 1][3]: row c - 1 = {pairs_c, T_c, above_c} */);
 
+/* What the attack knows beyond the node classes: the AUC of the true edges against the non-edges of the SAME stratum of class
+ * pairs, and the pairs at or above a cut per stratum, as exact integers.
+ *   - candidates, selection, comparison and checks as mcgra_auc_delong: idx, n_idx REPEAT-FREE device int64 node ids or NULL for
+ *     all n nodes; the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b with score scores[idx[a]][idx[b]] and label
+ *     labels[idx[a]][idx[b]]; nothing outside the selected strict lower triangle is looked at; scores compare as float32 values,
+ *     -0.0 == +0.0;
+ *   - node_class (device int32 [n]) is indexed by node id, not by position: the class of position a is c_a = node_class[idx[a]],
+ *     in [0, n_class) for every selected node (the unselected entries are not looked at), n_class = C in [1, MCGRA_CLASS_MAX];
+ *   - strata (HOST uint8 [C][C]) is symmetric with every entry below n_strata = G, G in [1, C_max (C_max + 1) / 2 = 136]: the
+ *     stratum of a candidate is strata[c_a][c_b].  A stratum that no candidate falls into is legal and gives a zero row;
+ *   - out (host int64 [n_strata][5]), row g = {pairs_g, P_g, T_g, above_g, hits_g}:
+ *       pairs_g   the candidates of the stratum; they sum to m
+ *       P_g       those of label 1; N_g = pairs_g - P_g
+ *       T_g       the sum over the non-edges q of the stratum of b_q = 2 #{edges of the same stratum that score higher} +
+ *                 #{edges of the same stratum that score the same}: mcgra_auc_delong's placement restricted to the stratum,
+ *                 whose AUC is T_g / (2 P_g N_g)
+ *       above_g   the candidates of the stratum with score >= threshold, mcgra_threshold_pairs' comparison (-0.0 >= +0.0 holds,
+ *                 +-inf are allowed)
+ *       hits_g    those of label 1 among them;
+ *   - no overflow: T_g <= 2 P_g N_g < 2^63 for n_idx <= 65 535;
+ *   - out, node_class, strata or a matrix NULL, an ld below n, n_class or n_strata out of range, an asymmetric table or an entry
+ *     >= n_strata, a NaN threshold, n_idx (n when idx is NULL) below 2: MCGRA_EINVAL; n_idx above 65 535: MCGRA_ENOSUP.  These run
+ *     before any HIP call.  A selected score that is NaN or +-inf, a selected label other than 0 or 1, a repeated or out-of-range
+ *     id, a selected node whose class is outside [0, n_class): MCGRA_EINVAL.  After any refusal nothing has been written to out
+ *     and mcgra_last_error() names the cause;
+ *   - integer arithmetic only on the device (a radix sort of the edges by stratum and score, searches inside a stratum's
+ *     segment, integer counts merged by integer atomics): the same bits on every call, the same integers under any permutation
+ *     of idx and under any renaming of the classes with their table.
+ * Synchronises `stream`.
+ * Device scratch: 16 bytes per candidate of label 1, about 3 MB, one byte per selected node, and 4 bytes per node of the graph
+ * when idx is given. */
+#define MCGRA_CLASS_MAX 16
+int mcgra_class_auc(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                    const int64_t* idx, int64_t n_idx, const int32_t* node_class, int n_class,
+                    const uint8_t* strata /* host [n_class][n_class] */, int n_strata, float threshold,
+                    int64_t* out /* host [n_strata][5]: row g = {pairs_g, P_g, T_g, above_g, hits_g} */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score

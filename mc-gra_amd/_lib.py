@@ -48,6 +48,7 @@ SYMBOLS = [
     "mcgra_auc_node_jackknife",
     "mcgra_graph_structure",
     "mcgra_hop_auc",
+    "mcgra_class_auc",
 ]
 
 
@@ -139,6 +140,8 @@ def _load():
         "mcgra_auc_node_jackknife": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64), ip],
         "mcgra_graph_structure": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_float, C.POINTER(C.c_int64), ip],
         "mcgra_hop_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.c_float, C.POINTER(C.c_int64)],
+        "mcgra_class_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, ip, C.c_int, C.POINTER(C.c_uint8), C.c_int,
+                            C.c_float, C.POINTER(C.c_int64)],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

@@ -54,9 +54,10 @@ RankTiles rank_tiles(uint64_t count, int max_blocks, int step);
 // off[i] = cnt[0] + ... + cnt[i - 1] over len entries (one block; the caller checks the launch)
 void rank_scan(hipStream_t st, const uint32_t* cnt, int len, uint64_t* off);
 // stable LSD radix sort of keys[0, count) (a multiple-of-4 aligned region), tmp the same size; result in keys.  pay != NULL:
-// pay[i] travels with keys[i] (ptmp the same size; result in pay).  cnt, off: 256 * AUC_SORT_BLOCKS entries each.
+// pay[i] travels with keys[i] (ptmp the same size; result in pay).  cnt, off: 256 * AUC_SORT_BLOCKS entries each.  bits (a
+// multiple of 8): every key is below 2^bits, bits / 8 passes; after an odd number of them the result is in tmp (and ptmp).
 int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, uint32_t* cnt, uint64_t* off, uint32_t* pay = nullptr,
-             uint32_t* ptmp = nullptr);
+             uint32_t* ptmp = nullptr, int bits = 32);
 
 // ---- device side
 namespace {

@@ -176,11 +176,11 @@ void rank_scan(hipStream_t st, const uint32_t* cnt, int len, uint64_t* off) {
 }
 
 int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, uint32_t* cnt, uint64_t* off, uint32_t* pay,
-             uint32_t* ptmp) {
+             uint32_t* ptmp, int bits) {
   if (count < 2) return 0;
   const auto [tile, nb] = rank_tiles(count, AUC_SORT_BLOCKS, AUC_SORT_TILE);
   uint32_t *src = keys, *dst = tmp, *psrc = pay, *pdst = ptmp;
-  for (int shift = 0; shift < 32; shift += 8) {
+  for (int shift = 0; shift < bits; shift += 8) {
     k_auc_digit_count<<<nb, AUC_THREADS, 0, st>>>(src, count, tile, shift, nb, cnt);
     rank_scan(st, cnt, 256 * nb, off);
     if (pay) k_auc_digit_scatter<true><<<nb, AUC_THREADS, 0, st>>>(src, dst, psrc, pdst, count, tile, shift, nb, off);
@@ -189,7 +189,7 @@ int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, uint
     x = psrc; psrc = pdst; pdst = x;
   }
   MCGRA_KERNEL_CHECK();
-  return 0;                                         // four passes: the sorted keys are back in `keys`
+  return 0;                                         // bits = 32, four passes: the sorted keys are back in `keys`
 }
 
 }  // namespace mcgra

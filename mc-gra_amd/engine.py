@@ -875,6 +875,129 @@ def hop_auc(real, pred, idx=None, hops=3, threshold=None):
     return hop_auc_stats([out[3 * c:3 * c + 3] for c in range(H + 1)], H, threshold)
 
 
+CLASS_MAX = 16                                     # MCGRA_CLASS_MAX (include/mcgra.h)
+STRATA_MAX = CLASS_MAX * (CLASS_MAX + 1) // 2      # one stratum per unordered class pair
+CLASS_STRATA = ("one", "same", "own", "blocks")
+
+
+def class_strata(C, how):
+    """(table, names) of a partition of the unordered class pairs of C classes into strata: table a symmetric uint8 array
+    [C][C], table[i][j] the stratum of a pair with one end in class i and the other in class j, names the strata's names.
+    how "one": every pair in one stratum ("all"); "same": 0 = both ends in one class, 1 = not ("same", "different"); "own":
+    stratum c = both ends in class c, stratum C = the ends in different classes ("0", ..., "different"); "blocks": one stratum
+    per unordered class pair i <= j in lexicographic order ("i-j")."""
+    if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or not 1 <= C <= CLASS_MAX:
+        raise ValueError(f"class_strata: C = {C!r}; an integer number of classes in [1, {CLASS_MAX}]")
+    C = int(C)
+    i, j = np.indices((C, C))
+    if how == "one":
+        table, names = np.zeros((C, C), np.uint8), ("all",)
+    elif how == "same":
+        table, names = (i != j).astype(np.uint8), ("same", "different")
+    elif how == "own":
+        table, names = np.where(i == j, i, C).astype(np.uint8), tuple(str(c) for c in range(C)) + ("different",)
+    elif how == "blocks":
+        lo, hi = np.minimum(i, j), np.maximum(i, j)
+        table = (lo * C - lo * (lo - 1) // 2 + hi - lo).astype(np.uint8)          # the pairs (lo, lo), ..., (lo, C - 1) follow lo's
+        names = tuple(f"{a}-{b}" for a in range(C) for b in range(a, C))
+    else:
+        raise ValueError(f"class_strata: how = {how!r}; one of {', '.join(CLASS_STRATA)}")
+    return table, names
+
+
+def class_auc_stats(ints, names=None, threshold=None):
+    """The dict of class_auc from its integers: ints = the G rows (pairs_g, P_g, T_g, above_g, hits_g) of mcgra_class_auc.
+    Every double is the correctly rounded quotient of two Python integers, NaN on a zero denominator.  No device is involved.
+    Returns, per stratum as tuples of length G: "count", "positives", "negatives", "T", "above", "hits", "auc" T_g / (2 P_g
+    N_g), "pair_share" pairs_g / m, "edge_share" P_g / P, "precision" hits_g / above_g, "recall" hits_g / P_g; and overall
+    "auc_within" sum T_g / sum 2 P_g N_g (the chance that an edge outranks a non-edge of its own stratum, ties half),
+    "auc_adjusted" sum P_g AUC_g / sum P_g over the strata with P_g N_g > 0 (the covariate-adjusted AUC of Janes and Pepe,
+    Biometrika 96, 2009: ONE Fraction, rounded once), "pairs" (m), "names", "threshold", "ints" (the rows).  threshold None:
+    no "above", "hits", "precision" and "recall"."""
+    nan = float("nan")
+    rows = [tuple(int(v) for v in r) for r in ints]
+    if not 1 <= len(rows) <= STRATA_MAX or any(len(r) != 5 or min(r) < 0 for r in rows):
+        raise ValueError(f"class_auc_stats: {len(rows)} rows; the entry returns 1 to {STRATA_MAX} rows of five counts")
+    names = tuple(str(g) for g in range(len(rows))) if names is None else tuple(names)
+    if len(names) != len(rows):
+        raise ValueError(f"class_auc_stats: {len(names)} names for {len(rows)} strata")
+    count, pos, T, above, hits = (tuple(r[q] for r in rows) for q in range(5))
+    neg = tuple(c - p for c, p in zip(count, pos))
+    if min(neg) < 0 or any(t > 2 * p * n for t, p, n in zip(T, pos, neg)) or any(h > min(p, a) for h, p, a in zip(hits, pos, above)):
+        raise ValueError("class_auc_stats: the rows are not counts of one selection (P_g <= pairs_g, T_g <= 2 P_g N_g, "
+                         "hits_g <= min(P_g, above_g))")
+    ratio = lambda a, b: a / b if b else nan
+    m, P = sum(count), sum(pos)
+    live = [g for g in range(len(rows)) if pos[g] and neg[g]]
+    adjusted = sum((Fraction(T[g], 2 * neg[g]) for g in live), Fraction(0))          # sum P_g AUC_g
+    res = {"names": names, "threshold": None if threshold is None else float(threshold), "pairs": m,
+           "count": count, "positives": pos, "negatives": neg, "T": T, "above": above, "hits": hits,
+           "auc": tuple(ratio(t, 2 * p * n) for t, p, n in zip(T, pos, neg)),
+           "pair_share": tuple(ratio(c, m) for c in count), "edge_share": tuple(ratio(p, P) for p in pos),
+           "precision": tuple(ratio(h, a) for h, a in zip(hits, above)), "recall": tuple(ratio(h, p) for h, p in zip(hits, pos)),
+           "auc_within": ratio(sum(T), sum(2 * p * n for p, n in zip(pos, neg))),
+           "auc_adjusted": float(adjusted / sum(pos[g] for g in live)) if live else nan, "ints": rows}
+    if threshold is None:
+        del res["above"], res["hits"], res["precision"], res["recall"]
+    return res
+
+
+def _node_classes(classes, n, idx):
+    """classes as an int64 numpy vector of length n and the largest class among the selected nodes (idx None: all; ids outside
+    [0, n) are left to the entry to refuse).  ValueError for a wrong length, a dtype that is not integer, a negative class of
+    a selected node."""
+    if isinstance(classes, torch.Tensor):
+        classes = classes.detach().cpu().numpy()
+    cl = np.asarray(classes)
+    if cl.dtype == bool or not np.issubdtype(cl.dtype, np.integer):
+        raise ValueError(f"class_auc: classes of dtype {cl.dtype}; the node classes are integers")
+    if cl.shape != (n,):
+        raise ValueError(f"class_auc: classes of shape {tuple(cl.shape)}; one class per node of the graph, ({n},)")
+    cl = cl.astype(np.int64)
+    sel = cl
+    if idx is not None:
+        ix = idx.detach().cpu().numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
+        ix = ix.reshape(-1).astype(np.int64)
+        sel = cl[ix[(ix >= 0) & (ix < n)]]
+    if sel.size and sel.min() < 0:
+        raise ValueError(f"class_auc: a selected node of class {int(sel.min())}; the classes are 0, 1, ...")
+    return cl, int(sel.max()) if sel.size else 0
+
+
+@_on_operand_device
+def class_auc(real, pred, classes, idx=None, strata="blocks", threshold=None):
+    """What the attack knows beyond the node classes (mcgra_class_auc): the candidates of auc_delong -- the unordered pairs of
+    positions a > b of a REPEAT-FREE idx (None: all nodes), score pred[idx[a], idx[b]], label real[idx[a], idx[b]] -- split into
+    strata by the classes of their two ends, and per stratum the AUC of ITS edges against ITS non-edges: a scoring that has
+    learnt nothing but "same class" scores 0.5 inside every stratum.  classes: one integer per node of the graph (tensor, array
+    or list of length n, indexed by node id).  strata: "one", "same", "own" or "blocks" (class_strata's partitions of C = the
+    largest selected class + 1 classes) or a (table, names) pair of one's own, table symmetric [C][C] with entries below
+    len(names).  With a threshold also the candidates at or above it per stratum (threshold_pairs' float32 comparison) and the
+    edges among them.  Returns class_auc_stats' dict.  Exact integers from the device (a sort of the edges by stratum and
+    score, a search inside the stratum's segment), correctly rounded quotients on the host, the same bits on every call.
+    ValueError for more than 16 classes, classes of a wrong length or dtype, a negative class of a selected node, a table that
+    is not [C][C]; McgraError for whatever the entry refuses: an asymmetric table, a selected class the table does not hold, a
+    NaN threshold, a repeated or out-of-range id, a selected NaN / inf score or a selected label other than 0 / 1."""
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
+    cl, top = _node_classes(classes, n, idx)
+    if isinstance(strata, str):
+        if top >= CLASS_MAX:
+            raise ValueError(f"class_auc: a selected node of class {top}; at most {CLASS_MAX} classes, 0 to {CLASS_MAX - 1}")
+        table, names = class_strata(top + 1, strata)
+    else:
+        table, names = strata
+        table, names = np.ascontiguousarray(np.asarray(table), dtype=np.uint8), tuple(names)
+        if table.ndim != 2 or table.shape[0] != table.shape[1] or not 1 <= table.shape[0] <= CLASS_MAX:
+            raise ValueError(f"class_auc: a strata table of shape {tuple(table.shape)}; [C][C] with C in [1, {CLASS_MAX}]")
+    G = len(names)
+    node_class = torch.as_tensor(np.clip(cl, -1, 2 ** 31 - 1).astype(np.int32), device=pred.device)     # what is clipped is refused
+    out = (C.c_int64 * (5 * max(G, 1)))()
+    check(lib.mcgra_class_auc(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, _p(node_class),
+                              table.shape[0], table.ctypes.data_as(C.POINTER(C.c_uint8)), G,
+                              float("inf") if threshold is None else float(threshold), out))
+    return class_auc_stats([out[5 * g:5 * g + 5] for g in range(G)], names, threshold)
+
+
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
 # row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
 NODE_RANK_MAX_NIDX = 16384

@@ -39,6 +39,13 @@ triangles, wedges, transitivity and clustering of that graph are reported beside
 distance 2, 3, ..., H of the true graph on the set's nodes and against those beyond (engine.hop_auc); the pooled AUC of --ci is
 their mean weighted by the classes' sizes.  --hops_cut split|edges|THRESHOLD (default edges; --structure's cuts) says where the
 false positives are counted, class by class.  --save_hops PATH: the counts, the sums and the AUC of every class.
+--by_class labels|degree|PATH asks what the attack knows beyond the node classes it was handed: the AUC of a set's true edges
+against the non-edges of the SAME stratum of class pairs (engine.class_auc) -- same-class and different-class pairs, and every
+unordered class pair as a block, with the blocks' pooled-within and covariate-adjusted AUC beside the pooled AUC of --ci, and
+the share of same-class pairs among the true edges, the recovered pairs and all pairs.  The classes are the run's node labels,
+min(15, bit_length) of a node's degree in the true graph, or an integer .npy with one class in [0, 16) per node.
+--by_class_cut split|edges|THRESHOLD (default edges; --structure's cuts) says where the recovered pairs are counted.
+--save_by_class PATH: the counts, the sums and the AUC of every block, and the class of every node.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -81,7 +88,7 @@ import torch.nn.functional as F
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
-        for r in reports.EVERY_REPORT:
+        for r in reports.ALL_REPORTS:
             r.check(args, self.error)
         return args
 
@@ -141,6 +148,9 @@ def build_parser():
     p.add_argument('--hops', type=int, default=argparse.SUPPRESS)              # also the AUC by true-graph distance 2 .. H and beyond
     p.add_argument('--hops_cut', type=str, default=argparse.SUPPRESS)          # with --hops: where its false positives are counted
     p.add_argument('--save_hops', type=str, default=argparse.SUPPRESS)         # with --hops: the per-distance counts as an .npz
+    p.add_argument('--by_class', type=str, default=argparse.SUPPRESS)          # also the AUC within the classes of labels | degree | an .npy
+    p.add_argument('--by_class_cut', type=str, default=argparse.SUPPRESS)      # with --by_class: where its pairs above a cut are counted
+    p.add_argument('--save_by_class', type=str, default=argparse.SUPPRESS)     # with --by_class: the per-block counts as an .npz
     return p
 
 
@@ -288,14 +298,14 @@ def log_lines(res, ctx):
     if getattr(ctx.args, "ap", False):
         lines.append(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
                      f"In Whole Graph: AP={res['ap_all']}")
-    for r in reports.EVERY_REPORT:
+    for r in reports.ALL_REPORTS:
         if r.wanted(ctx.args):
             lines += r.log(res, ctx)
     return lines + [f"current density: {res['density']}"]
 
 
 def _run(args, rank, world):
-    for r in reports.EVERY_REPORT:
+    for r in reports.ALL_REPORTS:
         r.check(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
@@ -391,6 +401,8 @@ def _run(args, rank, world):
     other = None
     if versus is not None:  # refused before the attack runs, not after it
         other = feature_adj if versus == "features" else reports.load_versus(versus, adj.shape[0])
+    by_class = getattr(args, "by_class", None)
+    classes = None if by_class is None else reports.node_classes(by_class, labels, adj)    # refused before the attack runs too
     lr = 10 ** args.lr                                                                     # objective(): main.py:282-283
     weight_param = tuple(getattr(args, f"w{i}") for i in range(1, 11))
     model = PGDAttack(model=victim_model, embedding=embedding, H_A=H_A2, Y_A=Y_A, nnodes=adj.shape[0],
@@ -403,10 +415,10 @@ def _run(args, rank, world):
     inference_adj = model.modified_adj                     # stays on the device: the three AUCs run there (main.py:247-250)
     ctx = reports.Context(real=ad.to(inference_adj.device), inference_adj=inference_adj,
                           sets={"attack": idx_attack, "train": idx_train, "all": None}, n=adj.shape[0], rank=rank,
-                          other=other, versus=versus, args=args)
+                          other=other, versus=versus, args=args, classes=classes)
     want_ap = getattr(args, "ap", False)
     res = base_metrics(ctx, want_ap)
-    wanted = [r for r in reports.EVERY_REPORT if r.wanted(args)]
+    wanted = [r for r in reports.ALL_REPORTS if r.wanted(args)]
     for r in wanted:        # every rank computes (as the AUCs); a report's keys exist only with its flag
         res.update(r.compute(ctx))
     res["path"] = dict(model.history.get("path", {}), world=world)

@@ -1,7 +1,8 @@
 """The optional reports of `main.py --mode evaluate` (none is in the reference; main.py's docstring says what each flag asks):
 per report the argument check, the computation on the device, the console lines, the --save_* file and the log lines, and at
-the bottom the one ordered table of them that main.py's parser, run and log loop over: EVERY_REPORT, which is REPORTS and the
-reports added after it.  To add a report, add an entry to EVERY_REPORT.
+the bottom the one ordered table of them that main.py's parser, run and log loop over: ALL_REPORTS, which is REPORTS, then
+EVERY_REPORT's hops report (two tuples that tests pin), then the reports added after them.  To add a report, add an entry to
+ALL_REPORTS.
 
 `sets` is always index set name -> node ids (None: every node); fail(message) does not return; a --save_* file is written at
 exactly the path given.  engine functions are looked up as engine.<fn> at the call."""
@@ -18,8 +19,9 @@ CI_LEVEL = 0.95
 
 
 # what one evaluate run hands its reports: real is the true adjacency on the device of inference_adj (the attack's modified_adj),
-# other the second n x n score matrix of --versus and versus the flag as given (both None without it)
-Context = collections.namedtuple("Context", "real inference_adj sets n rank other versus args")
+# other the second n x n score matrix of --versus and versus the flag as given (both None without it), classes the int64 class
+# of every node of --by_class (None without it)
+Context = collections.namedtuple("Context", "real inference_adj sets n rank other versus args classes", defaults=(None,))
 
 
 class Report:
@@ -403,6 +405,106 @@ def save_hops(res, ctx):
     _save_npz(ctx.args.save_hops, **arrays)
 
 
+def check_by_class_args(args, fail):
+    source, cut, path = (getattr(args, k, None) for k in ("by_class", "by_class_cut", "save_by_class"))
+    if cut is not None and source is None:
+        fail("--by_class_cut needs --by_class")
+    if path is not None and source is None:
+        fail("--save_by_class needs --by_class")
+    if path is not None and path == "":
+        fail("--save_by_class takes the path of the .npz to write")
+    if source is not None and args.mode != "evaluate":
+        fail(f"--by_class splits the AUC of the attack's modified_adj by the classes of a pair's ends: --mode evaluate only, "
+             f"not --mode {args.mode}")
+    if source is not None and source == "":
+        fail("--by_class takes `labels`, `degree` or the path of an integer .npy with one class per node")
+    if cut is not None and structure_source(cut) is None:
+        fail(f"--by_class_cut takes `split`, `edges` or a finite threshold, not {cut!r}")
+
+
+def degree_classes(degrees):
+    """--by_class degree: min(15, d.bit_length()) of each degree d -- 0, 1, 2-3, 4-7, ..., 16384 and more."""
+    return np.asarray([min(engine.CLASS_MAX - 1, int(d).bit_length()) for d in degrees], dtype=np.int64)
+
+
+def node_classes(source, labels, adj):
+    """--by_class SOURCE as an int64 vector with one class in [0, 16) per node: `labels` the run's node labels, `degree`
+    degree_classes of the degrees in the whole true graph adj, anything else the path of an integer .npy of length n.  What is
+    no such vector is refused by name."""
+    n = adj.shape[0]
+    if source == "labels":
+        cl = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+    elif source == "degree":
+        dense = adj.cpu() if isinstance(adj, torch.Tensor) else torch.as_tensor(np.asarray(adj))
+        return degree_classes((dense != 0).sum(1).tolist())
+    else:
+        try:
+            cl = np.load(source, allow_pickle=False)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--by_class {source}: not a readable .npy ({e})")
+    if cl.dtype == bool or not np.issubdtype(cl.dtype, np.integer):
+        raise SystemExit(f"--by_class {source}: classes of dtype {cl.dtype}; one integer class per node")
+    if cl.shape != (n,):
+        raise SystemExit(f"--by_class {source}: classes of shape {tuple(cl.shape)}; this graph has {n} nodes")
+    cl = cl.astype(np.int64)
+    if cl.min() < 0 or cl.max() >= engine.CLASS_MAX:
+        raise SystemExit(f"--by_class {source}: classes from {int(cl.min())} to {int(cl.max())}; at most {engine.CLASS_MAX} "
+                         f"classes, 0 to {engine.CLASS_MAX - 1}")
+    return cl
+
+
+def by_class_report(ctx):
+    """--by_class SOURCE: {"by_class_<name>": per index set engine.class_auc of ctx.classes with the strata `same` and `blocks`
+    at the set's structure_threshold of --by_class_cut (default `edges`), engine.auc_delong's auc as auc_pooled, and the shares
+    of same-class pairs among the true edges, the pairs at or above the cut and all pairs}."""
+    source, real, pred = structure_source(getattr(ctx.args, "by_class_cut", "edges")), ctx.real, ctx.inference_adj
+    C = int(np.max(ctx.classes)) + 1
+    ratio = lambda a, b: a / b if b else float("nan")
+    out = {}
+    for name, ix in ctx.sets.items():
+        thr = structure_threshold(source, real, pred, ix)
+        same = engine.class_auc(real, pred, ctx.classes, ix, engine.class_strata(C, "same"), thr)
+        blocks = engine.class_auc(real, pred, ctx.classes, ix, engine.class_strata(C, "blocks"), thr)
+        out[f"by_class_{name}"] = {
+            "source": ctx.args.by_class, "classes": C, "threshold": thr,
+            "auc_pooled": engine.auc_delong(real, pred, ix, CI_LEVEL)["auc"], "same": same, "blocks": blocks,
+            "homophily": {"true": ratio(same["positives"][0], sum(same["positives"])),
+                          "recovered": ratio(same["above"][0], sum(same["above"])), "pairs": ratio(same["count"][0], same["pairs"])}}
+    return out
+
+
+def _by_class_text(d):
+    s, b, h = d["same"], d["blocks"], d["homophily"]
+    return (f"same-class AUC={s['auc'][0]} different-class AUC={s['auc'][1]} within blocks={b['auc_within']} "
+            f"adjusted={b['auc_adjusted']} (pooled {d['auc_pooled']}) same-class share: true edges={h['true']} "
+            f"recovered={h['recovered']} pairs={h['pairs']}")
+
+
+def _by_class_console(res, ctx):
+    return [f"current auc_by_class {_by_class_text(res['by_class_all'])}"]
+
+
+def _by_class_log(res, ctx):
+    return [f"In {title}: by class ({d['source']}, {d['classes']} classes) at {d['threshold']}: {_by_class_text(d)}"
+            for title, d in _per_set(res, "by_class")]
+
+
+def save_by_class(res, ctx):
+    """--save_by_class: per index set the blocks' two classes, count, positives, T, above, hits (int64) and AUC (float64), the
+    five integers of the `same` split [2][5] and the threshold; once the class of every node."""
+    arrays = {"classes": np.asarray(ctx.classes, dtype=np.int64)}
+    for name in ctx.sets:
+        d = res[f"by_class_{name}"]
+        b, C = d["blocks"], d["classes"]
+        arrays[f"class_i_{name}"] = np.asarray([i for i in range(C) for _ in range(i, C)], dtype=np.int64)
+        arrays[f"class_j_{name}"] = np.asarray([j for i in range(C) for j in range(i, C)], dtype=np.int64)
+        arrays.update({f"{k}_{name}": np.asarray(b[k], dtype=np.int64) for k in ("count", "positives", "T", "above", "hits")})
+        arrays[f"auc_{name}"] = np.asarray(b["auc"], dtype=np.float64)
+        arrays[f"same_ints_{name}"] = np.asarray(d["same"]["ints"], dtype=np.int64)
+        arrays[f"threshold_{name}"] = np.float32(d["threshold"])
+    _save_npz(ctx.args.save_by_class, **arrays)
+
+
 def _saver(flag, write):
     """write(res, ctx) when the --save_* flag names a file."""
     return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
@@ -434,10 +536,15 @@ REPORTS = (
            compute=structure_report, console=_structure_console, log=_structure_log, save=_saver("save_structure", save_structure)),
 )
 # REPORTS holds the reports of the recorded run with every flag on (tests/golden/evaluate_all_flags.json), whose tests pin its
-# entries; a report added since then follows here.  EVERY_REPORT is what main.py's parser, run and log loop over.
+# entries; the hops report, added since then, follows here.
 EVERY_REPORT = REPORTS + (
     Report(flags=("hops", "hops_cut", "save_hops"), check=check_hops_args, wanted=_on("hops", given=True), compute=hops_report,
            console=_hops_console, log=_hops_log, save=_saver("save_hops", save_hops)),
+)
+# EVERY_REPORT ends with the hops report, as its tests pin it; ALL_REPORTS is what main.py's parser, run and log loop over.
+ALL_REPORTS = EVERY_REPORT + (
+    Report(flags=("by_class", "by_class_cut", "save_by_class"), check=check_by_class_args, wanted=_on("by_class", given=True),
+           compute=by_class_report, console=_by_class_console, log=_by_class_log, save=_saver("save_by_class", save_by_class)),
 )
 
 
@@ -445,7 +552,7 @@ def shown_parameters(args):
     """The namespace that the log's parameter line prints: args without `ap` while --ap is off and without the flags of every
     report that is off, so that a run without a flag logs what it logged before the flag existed."""
     hidden = set() if getattr(args, "ap", False) else {"ap"}
-    for r in EVERY_REPORT:
+    for r in ALL_REPORTS:
         if not r.wanted(args):
             hidden.update(r.flags)
     return argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
