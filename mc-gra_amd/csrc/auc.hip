@@ -410,15 +410,14 @@ struct AucRun {
     }
     uint32_t* keys = b.get<uint32_t>(nbase + N);
     uint32_t* tmp = b.get<uint32_t>(nbase + N);
-    uint32_t* cnt = b.get<uint32_t>(256 * AUC_SORT_BLOCKS);
-    uint64_t* off = b.get<uint64_t>(256 * AUC_SORT_BLOCKS);
+    const SortScratch ss(b);
     double* part = ap ? b.get<double>(AP_BLOCKS + 1) : nullptr;      // the per-block partials, then the result
-    if (!keys || !tmp || !cnt || !off || (ap && !part)) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
+    if (!keys || !tmp || !ss.cnt || (ap && !part)) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
     MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
     emit(counts, keys);
     MCGRA_KERNEL_CHECK();
-    if (int rc = auc_sort(st, keys, tmp, P, cnt, off)) return rc;
-    if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, cnt, off)) return rc;
+    if (int rc = auc_sort(st, keys, tmp, P, ss)) return rc;
+    if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, ss)) return rc;
     if (cv) return rank_curves_sorted(who, st, keys, tmp, P, nbase, N, *cv);
     unsigned long long u2 = 0;
     if (auc) {

@@ -9,19 +9,18 @@
 // STRATUM that score higher} + #{edges of the stratum that score the same}, above_g (score >= threshold,
 // mcgra_threshold_pairs' comparison) and hits_g (label 1 among those).
 // Passes:
-//   rank_check_idx  idx only: range check, repeats (rank_common.hip)
+//   DlStage         (delong_common.hip) rank_check_idx; k_dl_classify: one read of the selected strict lower triangle, the
+//                   argument checks (NaN / inf score, label other than 0 / 1) and per-block counts of the edges
 //   k_ca_classes    the selected nodes' classes, read through idx once: cls[a] = node_class[idx[a]] as a byte by POSITION (what
 //                   the two passes over the triangle read, coalesced), a class outside [0, C) flagged in a word of its own
-//   k_dl_classify   (delong_common.h) one read of the selected strict lower triangle: the argument checks (NaN / inf score,
-//                   label other than 0 / 1) and per-block counts of the edges
 //   k_ca_emit       k_dl_emit with the stratum as what travels with an edge's key
 //   auc_sort        by key, the stratum as payload; then ONE more stable pass by the stratum's eight bits, the key as payload:
 //                   the edges are stratum-major and ascending inside a stratum
 //   k_ca_stream     ONE pass over the selected strict lower triangle.  Every block finds the segments seg[g] .. seg[g + 1] of the
 //                   strata by G + 1 searches in the sorted strata (no count pass, no scan) and stages the table, the segment
 //                   offsets and DL_STAGE samples of the sorted keys in LDS.  Every candidate counts for pairs, P, above and hits
-//                   of its stratum; a non-edge finds lb and ub INSIDE its stratum's segment (ca_find: dl_find's search through
-//                   the samples, bounded to the segment) and adds 2 P_g - lb - ub, both relative to the segment.  The counters
+//                   of its stratum; a non-edge finds its placement INSIDE its stratum's segment (delong_common.h's dl_placement
+//                   through the samples, bounded to the segment) and adds it.  The counters
 //                   are per block in LDS: the four counts as 32-bit words added once per wave for each of its first
 //                   CA_SHARED_BINS distinct strata (ballots, as dl_hist_add: G = 2 puts a whole wave on two strata) and lane by
 //                   lane for the strata left (G = 28 .. 136 scatters them); the sums b_q as 64-bit words in CA_TSLOTS copies
@@ -56,9 +55,10 @@ static_assert((CA_TSLOTS & (CA_TSLOTS - 1)) == 0 && CA_TSLOTS <= 64, "a lane's c
 enum { CA_PAIRS = 0, CA_P, CA_ABOVE, CA_HITS, CA_COUNTS };        // the 32-bit counters of a stratum
 enum { CA_OUT_PAIRS = 0, CA_OUT_P, CA_OUT_T, CA_OUT_ABOVE, CA_OUT_HITS, CA_COLS };
 
+// what follows the stage's counts on the device, then cls: one byte per selected position
 struct CaHead {
   unsigned long long acc[CA_STRATA][CA_COLS];
-  int flags, class_flags;
+  int class_flags, pad;
   uint8_t tab[CA_CLASSES * CA_CLASSES];              // strata[c_a][c_b] at c_a * C + c_b
 };
 
@@ -95,18 +95,6 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ca_emit(int rows, int C, const 
     ka[at] = auc_key(S[u * lds + v]);
     strat[at] = tab[cls[a] * C + cls[b]];
   });
-}
-
-// dl_find bounded to the segment [lo, hi) of the ascending keys S, lo < hi: the samples smp[q] = S[q stride] whose positions
-// lie in the segment are q in [qlo, qhi); c = the first of them >= x (> x).  Position (c - 1) stride is below (at or below) x
-// when c > qlo, position c stride is not when c < qhi; the bound lies between them, or between them and the segment's ends.
-template <bool UPPER>
-__device__ __forceinline__ uint32_t ca_find(const uint32_t* __restrict__ S, uint32_t lo, uint32_t hi, const uint32_t* smp,
-                                            uint32_t stride, uint32_t x) {
-  const uint32_t qlo = (lo + stride - 1) / stride, qhi = (hi + stride - 1) / stride;
-  const uint32_t c = rank_bound<UPPER>(smp, qlo, qhi, x);
-  const uint32_t slo = c > qlo ? (c - 1) * stride + 1 : lo, shi = c < qhi ? c * stride : hi;
-  return rank_bound<UPPER>(S, slo, shi, x);
 }
 
 // cnt[g][CA_PAIRS ..] += this candidate, for every lane that is active in the caller (the loop is the same in all of them).
@@ -150,12 +138,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ca_stream(int rows, int C, int 
   __shared__ uint32_t cnt[CA_STRATA * CA_COUNTS];
   __shared__ uint32_t seg[CA_STRATA + 1];
   __shared__ uint8_t tab[CA_CLASSES * CA_CLASSES];
-  uint32_t stride = 1;
-  if (np) {
-    stride = (np + DL_STAGE - 1) / DL_STAGE;
-    const uint32_t ns = (np + stride - 1) / stride;
-    for (uint32_t q = threadIdx.x; q < ns; q += AUC_THREADS) smp[q] = sorted[(uint64_t)q * stride];
-  }
+  const uint32_t stride = dl_stage(sorted, np, smp).stride;
   for (int q = threadIdx.x; q < G * CA_TSLOTS; q += AUC_THREADS) tsum[q] = 0;
   for (int q = threadIdx.x; q < G * CA_COUNTS; q += AUC_THREADS) cnt[q] = 0;
   if ((int)threadIdx.x <= G) seg[threadIdx.x] = rank_bound<false>(strat, 0u, np, (uint32_t)threadIdx.x);   // G + 1 <= 137 lanes
@@ -168,9 +151,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ca_stream(int rows, int C, int 
     if (!pos) {
       const uint32_t lo = seg[g], hi = seg[g + 1];
       if (lo < hi) {
-        const uint32_t lb = ca_find<false>(sorted, lo, hi, smp, stride, x);
-        const uint32_t ub = (lb < hi && sorted[lb] == x) ? ca_find<true>(sorted, lo, hi, smp, stride, x) : lb;
-        const uint64_t bq = 2ull * (hi - lo) - (lb - lo) - (ub - lo);          // <= 2 P_g < 2^32
+        const uint64_t bq = dl_placement(sorted, smp, stride, dl_segment(lo, hi, stride), x);      // <= 2 P_g < 2^32
         if (bq) atomicAdd(&tsum[g * CA_TSLOTS + (threadIdx.x & (CA_TSLOTS - 1))], (unsigned long long)bq);
       }
     }
@@ -217,27 +198,17 @@ extern "C" int mcgra_class_auc(void* stream, int n, const float* labels, int ld_
   if (int rc = rank_check_args(who, n, {{labels, ld_labels, true}, {scores, ld_scores, true}}, idx, n_idx, 2)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int m = (int)n_idx;
-  const int g = std::min(m - 1, CA_ROW_BLOCKS);
   AucBufs b;
-  uint8_t* head = b.get<uint8_t>(sizeof(CaHead) + sizeof(uint64_t) * (size_t)g + (size_t)m);
-  if (!head) {
-    (void)hipGetLastError();
-    set_error("%s: hipMalloc failed", who);
-    return MCGRA_ENOMEM;
-  }
-  CaHead* hd = (CaHead*)head;
-  uint64_t* counts = (uint64_t*)(head + sizeof(CaHead));
-  uint8_t* cls = (uint8_t*)(counts + g);
-  static_assert(sizeof(CaHead) % 8 == 0, "counts is 8-byte aligned");
+  DlStage stage{who, st, b, n, labels, scores, nullptr, ld_labels, ld_scores, 0, idx, m, std::min(m - 1, CA_ROW_BLOCKS)};
+  if (int rc = stage.start(sizeof(CaHead) + (size_t)m)) return rc;
+  const int g = stage.g;
+  CaHead* hd = (CaHead*)stage.extra;
+  uint8_t* cls = stage.extra + sizeof(CaHead);
   uint8_t tab[CA_CLASSES * CA_CLASSES] = {};
   memcpy(tab, strata, (size_t)C * C);
-  MCGRA_HIP(hipMemsetAsync(hd, 0, sizeof(CaHead), st));
   MCGRA_HIP(hipMemcpyAsync(hd->tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
-  if (int rc = rank_check_idx(who, st, b, n, idx, m, &hd->flags)) return rc;
   k_ca_classes<<<std::min(CA_ROW_BLOCKS, (m + AUC_THREADS - 1) / AUC_THREADS), AUC_THREADS, 0, st>>>(m, C, node_class, idx, cls,
                                                                                                      &hd->class_flags);
-  k_dl_classify<false><<<g, AUC_THREADS, 0, st>>>(m, scores, ld_scores, nullptr, 0, labels, ld_labels, idx, counts, nullptr,
-                                                  &hd->flags);
   MCGRA_KERNEL_CHECK();
   int class_flags = 0;
   MCGRA_HIP(hipMemcpyAsync(&class_flags, &hd->class_flags, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -246,35 +217,22 @@ extern "C" int mcgra_class_auc(void* stream, int n, const float* labels, int ld_
     set_error("%s: a selected node's class is outside [0, %d)", who, C);
     return MCGRA_EINVAL;
   }
-  std::vector<uint64_t> h;
-  uint64_t P = 0, N = 0;
-  if (int rc = dl_counted(who, st, counts, &hd->flags, g, false, m, h, P, N)) return rc;
+  if (int rc = stage.counted()) return rc;
+  const uint64_t P = stage.P, N = stage.N;
   uint32_t *sorted = nullptr, *strat = nullptr;
   if (P) {
-    // one allocation for what scales with P: the sort's counts, the keys, the strata, the sort's second buffers.  P4 = P rounded
-    // up to 4 keys: every array starts on 16 bytes
-    const size_t P4 = (P + 3) / 4 * 4, sort_cnt = 256 * (size_t)AUC_SORT_BLOCKS;
-    uint8_t* pool = b.get<uint8_t>((sizeof(uint64_t) + sizeof(uint32_t)) * sort_cnt + 4 * sizeof(uint32_t) * P4);
-    if (!pool) {
-      (void)hipGetLastError();
-      set_error("%s: hipMalloc of the scratch of %llu edges failed", who, (unsigned long long)P);
-      return MCGRA_ENOMEM;
-    }
-    uint64_t* off = (uint64_t*)pool;
-    uint32_t* cnt = (uint32_t*)(off + sort_cnt);
-    uint32_t *ka = cnt + sort_cnt, *kb = ka + P4, *sa = kb + P4, *sb = sa + P4;
-    MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-    k_ca_emit<<<g, AUC_THREADS, 0, st>>>(m, C, scores, ld_scores, labels, ld_labels, idx, cls, hd->tab, counts, ka, sa);
+    Carver c{};
+    if (int rc = stage.pool(4, 0, c, "edges")) return rc;              // the keys, the strata, the sort's second buffers
+    uint32_t *ka = c.take<uint32_t>(stage.P4), *kb = c.take<uint32_t>(stage.P4);
+    uint32_t *sa = c.take<uint32_t>(stage.P4), *sb = c.take<uint32_t>(stage.P4);
+    k_ca_emit<<<g, AUC_THREADS, 0, st>>>(m, C, scores, ld_scores, labels, ld_labels, idx, cls, hd->tab, stage.counts, ka, sa);
     MCGRA_KERNEL_CHECK();
-    if (int rc = auc_sort(st, ka, kb, P, cnt, off, sa, sb)) return rc;                 // by key: back in ka, sa
-    if (int rc = auc_sort(st, sa, sb, P, cnt, off, ka, kb, 8)) return rc;              // one pass by stratum: in sb, kb
+    if (int rc = auc_sort(st, ka, kb, P, stage.sort, sa, sb)) return rc;               // by key: back in ka, sa
+    if (int rc = auc_sort(st, sa, sb, P, stage.sort, ka, kb, 8)) return rc;            // one pass by stratum: in sb, kb
     sorted = P > 1 ? kb : ka;                                                          // (fewer than two edges: nothing moved)
     strat = P > 1 ? sb : sa;
   }
-  uint32_t tb;
-  memcpy(&tb, &threshold, sizeof(tb));
-  if (tb == 0x80000000u) tb = 0u;
-  const uint32_t T = (tb & 0x80000000u) ? ~tb : (tb | 0x80000000u);     // auc_key of the threshold (+-inf included)
+  const uint32_t T = auc_key_host(threshold);
   k_ca_stream<<<g, AUC_THREADS, 0, st>>>(m, C, G, scores, ld_scores, labels, ld_labels, idx, cls, hd->tab, sorted, strat,
                                          (uint32_t)P, T, &hd->acc[0][0]);
   MCGRA_KERNEL_CHECK();

@@ -20,8 +20,8 @@
 // Only the POSITIVES are stored and sorted (a graph has few edges among its pairs); the negatives are streamed from the
 // matrices and never stored.  Passes:
 //   rank_check_idx     idx only: range check, repeats (rank_common.hip)
-//   k_dl_classify      (delong_common.h, as k_dl_emit) one read of the selected lower triangle: the argument checks (both
-//                      score matrices), per-block positive counts
+//   k_dl_classify      (DlStage of delong_common.hip, as k_dl_emit) one read of the selected lower triangle: the argument
+//                      checks (both score matrices), per-block positive counts
 //   k_dl_emit          a second read of the labels: each positive's key (paired: of both matrices) to its slot, at per-block
 //                      offsets (the host's scan of the counts).  Which slot of its block's range a positive takes depends on
 //                      the order the waves run in; every result below is a sum over slots, which no such order changes.  The
@@ -43,8 +43,8 @@
 // Device scratch: 24 bytes per POSITIVE and scoring (its key by slot, the sorted copy, hist, ties and the 8-byte running sum)
 // plus 4 for the sort's second buffer, about 3 MB for the sort's counts, and 4 bytes per node of the graph when idx is given:
 // nothing per candidate.
-// DlSide, the searches, the histogram add, the two placements and the positives' stage are in delong_common.h, which
-// node_jackknife.hip shares.
+// DlSide, the staged samples, the searches, the histogram add and the two placements are in delong_common.h, the positives'
+// stage in delong_common.hip; node_jackknife.hip, hop_auc.hip and class_auc.hip share them.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -72,18 +72,15 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide s
   __shared__ uint32_t smp_a[DL_STAGE], smp_b[DL_STAGE];
   __shared__ uint64_t sh[AUC_THREADS / 64];
   const bool paired = sb.S != nullptr;
-  const uint32_t stride = (np + DL_STAGE - 1) / DL_STAGE, ns = (np + stride - 1) / stride;
-  for (uint32_t q = threadIdx.x; q < ns; q += AUC_THREADS) {
-    smp_a[q] = sa.sorted[(uint64_t)q * stride];
-    if (paired) smp_b[q] = sb.sorted[(uint64_t)q * stride];
-  }
+  const DlSamples sm = dl_stage(sa.sorted, np, smp_a);
+  if (paired) dl_stage(sb.sorted, np, smp_b);
   __syncthreads();
   uint64_t part[DL_ACC] = {};
   tri_for_each(rows, idx, [&](int, int, int64_t u, int64_t v) {
     const float xa = sa.S[u * sa.ld + v], xb = paired ? sb.S[u * sb.ld + v] : 0.f;
     const bool neg = !auc_pos(L[u * ldl + v]);                 // the labels were checked: 0 or 1
-    const uint64_t ba = dl_negative(sa, np, smp_a, ns, stride, xa, neg);
-    const uint64_t bb = paired ? dl_negative(sb, np, smp_b, ns, stride, xb, neg) : 0;
+    const uint64_t ba = dl_negative(sa, np, smp_a, sm, xa, neg);
+    const uint64_t bb = paired ? dl_negative(sb, np, smp_b, sm, xb, neg) : 0;
     if (neg) {
       const uint64_t qa = ba * ba, qb = bb * bb, qx = ba * bb;
       part[DL_T_A] += ba;
@@ -96,12 +93,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_negatives(int rows, DlSide s
       part[DL_X_HI] += qx >> 32;
     }
   });
-#pragma unroll
-  for (int q = 0; q < DL_ACC; ++q) {
-    __syncthreads();
-    const uint64_t tot = block_sum_u64(part[q], sh);
-    if (threadIdx.x == 0 && tot) atomicAdd(&acc[q], (unsigned long long)tot);
-  }
+  block_add_u64(part, sh, acc);
 }
 
 // The positives, by slot: acc[DL_T_A / _B] += a, acc[DL_SQ_*] += the halves of a^2, acc[DL_X_*] += the halves of a^A a^B
@@ -122,12 +114,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_dl_positives(DlSide sa, DlSide 
     part[DL_X_LO] += qx & 0xffffffffull;
     part[DL_X_HI] += qx >> 32;
   }
-#pragma unroll
-  for (int q = 0; q < DL_ACC; ++q) {
-    __syncthreads();
-    const uint64_t tot = block_sum_u64(part[q], sh);
-    if (threadIdx.x == 0 && tot) atomicAdd(&acc[q], (unsigned long long)tot);
-  }
+  block_add_u64(part, sh, acc);
 }
 
 // (low, high) limbs of lo + hi 2^32
@@ -147,63 +134,45 @@ struct DlResult {
 int dl_run(const char* who, hipStream_t st, int n, const float* L, int ldl, const float* SA, int lda, const float* SB, int ldb,
            const int64_t* idx, int rows, DlResult& r) {
   AucBufs b;
-  const bool paired = SB != nullptr;
-  const int sides = paired ? 2 : 1;
-  const int g = std::min(rows - 1, DL_ROW_BLOCKS);
-  // one allocation: flags, the two classes' accumulators, the per-block counts
-  struct Head { unsigned long long acc[2][DL_ACC]; int flags; };
-  uint8_t* head = b.get<uint8_t>(sizeof(Head) + sizeof(uint64_t) * (size_t)g);
-  if (!head) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
-  Head* hd = (Head*)head;
-  uint64_t* counts = (uint64_t*)(head + sizeof(Head));
-  static_assert(sizeof(Head) % 8 == 0, "counts is 8-byte aligned");
-  MCGRA_HIP(hipMemsetAsync(hd, 0, sizeof(Head), st));
-  if (int rc = rank_check_idx(who, st, b, n, idx, rows, &hd->flags)) return rc;
-  k_dl_classify<false><<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, nullptr, &hd->flags);
-  MCGRA_KERNEL_CHECK();
-  std::vector<uint64_t> h;
-  if (int rc = dl_counted(who, st, counts, &hd->flags, g, paired, rows, h, r.P, r.N)) return rc;
-  const uint64_t P = r.P;
+  const int sides = SB ? 2 : 1;
+  DlStage stage{who, st, b, n, L, SA, SB, ldl, lda, ldb, idx, rows, std::min(rows - 1, DL_ROW_BLOCKS)};
+  typedef unsigned long long Acc[2][DL_ACC];            // the two classes' accumulators
+  if (int rc = stage.start(sizeof(Acc))) return rc;
+  if (int rc = stage.counted()) return rc;
+  Acc& acc = *(Acc*)stage.extra;
+  const uint64_t P = r.P = stage.P;
+  r.N = stage.N;
   r.m = P + r.N;
   if (P == 0 || r.N == 0) return 0;                    // every placement is 0
-  // one allocation for what scales with P: per scoring slot [P4], sorted [P4], hist [P4 + 4], ties [P4 + 4], cum [P4 + 4];
-  // then the sort's second buffer [P4] and its counts.  P4 = P rounded up to 4 keys: every array starts on 16 bytes.
-  const size_t P4 = (P + 3) / 4 * 4, H4 = P4 + 4;
-  const size_t per_side = sizeof(uint32_t) * (2 * P4 + 2 * H4) + sizeof(uint64_t) * H4;
-  const size_t sort_cnt = 256 * (size_t)AUC_SORT_BLOCKS;
-  const size_t bytes = sides * per_side + sizeof(uint32_t) * P4 + sizeof(uint64_t) * sort_cnt + sizeof(uint32_t) * sort_cnt;
-  uint8_t* pool = b.get<uint8_t>(bytes);
-  if (!pool) { set_error("%s: hipMalloc of the scratch of %llu positives failed", who, (unsigned long long)P); return MCGRA_ENOMEM; }
+  // per scoring cum, slot, sorted, hist, ties; then the sort's second buffer
+  const size_t P4 = stage.P4, H4 = stage.H4;
+  Carver c{};
+  if (int rc = stage.pool(sides * 2 + 1, sides * 4, c)) return rc;
   DlSide side[2] = {};
-  uint8_t* at = pool;
   for (int s = 0; s < sides; ++s) {
     side[s].S = s ? SB : SA;
     side[s].ld = s ? ldb : lda;
-    side[s].cum = (uint64_t*)at;      at += sizeof(uint64_t) * H4;
-    side[s].slot = (uint32_t*)at;     at += sizeof(uint32_t) * P4;
-    side[s].sorted = (uint32_t*)at;   at += sizeof(uint32_t) * P4;
-    side[s].hist = (uint32_t*)at;     at += sizeof(uint32_t) * H4;
-    side[s].ties = (uint32_t*)at;     at += sizeof(uint32_t) * H4;
+    side[s].cum = c.take<uint64_t>(H4);
+    side[s].slot = c.take<uint32_t>(P4);
+    side[s].sorted = c.take<uint32_t>(P4);
+    side[s].hist = c.take<uint32_t>(H4);
+    side[s].ties = c.take<uint32_t>(H4);
   }
-  uint64_t* off = (uint64_t*)at;      at += sizeof(uint64_t) * sort_cnt;
-  uint32_t* cnt = (uint32_t*)at;      at += sizeof(uint32_t) * sort_cnt;
-  uint32_t* tmp = (uint32_t*)at;
-  MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-  k_dl_emit<false><<<g, AUC_THREADS, 0, st>>>(rows, SA, lda, SB, ldb, L, ldl, idx, counts, side[0].slot, side[1].slot);
-  MCGRA_KERNEL_CHECK();
+  uint32_t* tmp = c.take<uint32_t>(P4);
+  if (int rc = stage.emit(side[0].slot, side[1].slot)) return rc;
   for (int s = 0; s < sides; ++s) {
     MCGRA_HIP(hipMemcpyAsync(side[s].sorted, side[s].slot, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, st));
-    if (int rc = auc_sort(st, side[s].sorted, tmp, P, cnt, off)) return rc;
+    if (int rc = auc_sort(st, side[s].sorted, tmp, P, stage.sort)) return rc;
     MCGRA_HIP(hipMemsetAsync(side[s].hist, 0, sizeof(uint32_t) * 2 * H4, st));          // hist and ties are adjacent
   }
-  k_dl_negatives<<<g, AUC_THREADS, 0, st>>>(rows, side[0], side[1], L, ldl, idx, (uint32_t)P, hd->acc[1]);
+  k_dl_negatives<<<stage.g, AUC_THREADS, 0, st>>>(rows, side[0], side[1], L, ldl, idx, (uint32_t)P, acc[1]);
   MCGRA_KERNEL_CHECK();
   for (int s = 0; s < sides; ++s) rank_scan(st, side[s].hist, (int)P, side[s].cum);
   const int gp = (int)std::min<uint64_t>(DL_POS_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
-  k_dl_positives<<<gp, AUC_THREADS, 0, st>>>(side[0], side[1], (uint32_t)P, hd->acc[0]);
+  k_dl_positives<<<gp, AUC_THREADS, 0, st>>>(side[0], side[1], (uint32_t)P, acc[0]);
   MCGRA_KERNEL_CHECK();
   unsigned long long ha[2][DL_ACC];
-  MCGRA_HIP(hipMemcpyAsync(ha, hd->acc, sizeof(ha), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipMemcpyAsync(ha, acc, sizeof(ha), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipStreamSynchronize(st));                  // also: the scratch is freed on return
   const unsigned long long *ap = ha[0], *an = ha[1];
   if (ap[DL_T_A] != an[DL_T_A] || ap[DL_T_B] != an[DL_T_B]) {             // sum a_i == sum b_j == 2U by construction

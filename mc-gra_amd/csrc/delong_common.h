@@ -1,15 +1,55 @@
-// What the placement entries share (delong.hip: DeLong's sums; node_jackknife.hip: the per-node sums): one scoring's device
-// arrays, the search of a negative among the sorted positives through samples staged in LDS, the wave-merged histogram add,
-// a negative's and a positive's placement, and the positives' stage -- k_dl_classify, the host's dl_counted behind it, and
-// k_dl_emit -- parameterised by what travels with a positive (NODES false, DeLong: the key of the second scoring, if there is
-// one; NODES true, the jackknife: the pair's endpoints a << 16 | b, and the count of positives per position).  Integer work
-// only.  Each of the two files instantiates its own variant of the two kernels.
+// What the placement entries share (delong.hip: DeLong's sums; node_jackknife.hip: the per-node sums; hop_auc.hip: the sums by
+// distance; class_auc.hip: the sums inside a stratum).
+// Host side, defined once in delong_common.hip with its kernels (k_dl_classify, k_dl_emit): the positives' stage, DlStage.
+// Device side, inlined into each file's kernels: one scoring's device arrays, the samples of the sorted positives a block
+// stages in LDS, the search of a key among the sorted positives (or a segment of them) through the samples, a candidate's
+// placement, the wave-merged histogram add, and a negative's and a positive's share of DeLong's counts.  Integer work only.
 #pragma once
 #include <vector>
 
 #include "rank_common.h"
 
 namespace mcgra {
+// ---- host side (delong_common.hip)
+// The positives' stage of an entry over the candidates of mcgra_auc_delong: the pairs of positions a > b of `rows` selected
+// nodes, label L[idx[a]][idx[b]], score SA[..] (SB != NULL: a second scoring of the same pairs), g blocks grid-striding over
+// the selected rows.  In order:
+//   start    one allocation {flags | the per-block counts | `extra` bytes of the caller's, 8-byte aligned}, zeroed;
+//            rank_check_idx; k_dl_classify: the argument checks and the positives per block (deg != NULL, an offset into
+//            extra: also deg[v] = the positives that contain position v).  Returns with the kernel in flight
+//   counted  one sync: a flagged argument is refused; P, N = the two classes of the rows (rows - 1) / 2 candidates
+//   pool     one allocation for what scales with P -- `p4` arrays of P4 and `h4` arrays of H4 32-bit words (P4 = P rounded up
+//            to 4 keys, H4 = P4 + 4; a 64-bit array counts twice) and the sort's scratch; returns the carver behind the sort's
+//            scratch.  The per-block offsets (the scan of the counts) replace the counts on the device
+//   emit     k_dl_emit: block b's positives take the slots offs[b] .. (any order inside a block): ka[slot] = the key of the
+//            pair's score in SA; second[slot] = with deg its endpoints a << 16 | b, else (SB != NULL) the key of its score in
+//            SB.  An entry that carries something else launches its own kernel on `counts` instead
+struct DlStage {
+  const char* who;
+  hipStream_t st;
+  AucBufs& b;
+  int n;
+  const float *L, *SA, *SB;
+  int ldl, lda, ldb;
+  const int64_t* idx;
+  int rows, g;
+
+  int* flags = nullptr;
+  uint64_t* counts = nullptr;          // [g]; the offsets after pool()
+  uint8_t* extra = nullptr;
+  uint32_t* deg = nullptr;
+  uint64_t P = 0, N = 0;
+  size_t P4 = 0, H4 = 0;
+  SortScratch sort;
+  std::vector<uint64_t> h;
+
+  int start(size_t extra_bytes, ptrdiff_t deg_at = -1);
+  int counted();
+  int pool(size_t p4, size_t h4, Carver& c, const char* what = "positives");
+  int emit(uint32_t* ka, uint32_t* second);
+};
+
+// ---- device side
 namespace {
 constexpr int DL_STAGE = 4096;             // samples of the sorted positives a block of the negatives' pass keeps in LDS, per scoring
 
@@ -24,16 +64,51 @@ struct DlSide {
   uint64_t* cum;         // [P + 1] hist[0] + ... + hist[l - 1]
 };
 
-// rank_bound over all np sorted positives S through the ns samples smp[q] = S[q stride]: the bound among the samples leaves one
-// stretch between two samples.  c = first sample >= x (> x): every position up to (c - 1) stride is below (at or below) x and
-// position c stride is not, so the bound lies in ((c - 1) stride, c stride]; past the last sample it lies before np.
+// The samples smp[q] = S[q stride], q < ns, of the np ascending keys S that a block stages in LDS (at most DL_STAGE of them;
+// np == 0: none).  The caller's barrier publishes them.
+struct DlSamples { uint32_t stride, ns; };
+__device__ __forceinline__ DlSamples dl_stage(const uint32_t* __restrict__ S, uint32_t np, uint32_t* smp) {
+  DlSamples s{1u, 0u};
+  if (np) {
+    s.stride = (np + DL_STAGE - 1) / DL_STAGE;
+    s.ns = (np + s.stride - 1) / s.stride;
+    for (uint32_t q = threadIdx.x; q < s.ns; q += AUC_THREADS) smp[q] = S[(uint64_t)q * s.stride];
+  }
+  return s;
+}
+
+// A segment [lo, hi) of S and the samples whose positions lie in it, q in [qlo, qhi)
+struct DlSeg { uint32_t lo, hi, qlo, qhi; };
+__device__ __forceinline__ DlSeg dl_all(uint32_t np, DlSamples s) { return {0u, np, 0u, s.ns}; }
+__device__ __forceinline__ DlSeg dl_segment(uint32_t lo, uint32_t hi, uint32_t stride) {
+  return {lo, hi, (lo + stride - 1) / stride, (hi + stride - 1) / stride};
+}
+
+// rank_bound over the segment g of the ascending keys S through the samples: c = the first sample of the segment >= x (> x).
+// Position (c - 1) stride is below (at or below) x when c > qlo, position c stride is not when c < qhi; the bound lies between
+// them, or between them and the segment's ends.
 template <bool UPPER>
-__device__ __forceinline__ uint32_t dl_find(const uint32_t* __restrict__ S, uint32_t np, const uint32_t* smp, uint32_t ns,
-                                            uint32_t stride, uint32_t x) {
-  const uint32_t c = rank_bound<UPPER>(smp, 0u, ns, x);
-  if (c == 0) return 0;
-  const uint32_t lo = (c - 1) * stride + 1, hi = c < ns ? c * stride : np;
-  return rank_bound<UPPER>(S, lo, hi, x);
+__device__ __forceinline__ uint32_t dl_find(const uint32_t* __restrict__ S, const uint32_t* smp, uint32_t stride, DlSeg g,
+                                            uint32_t x) {
+  const uint32_t c = rank_bound<UPPER>(smp, g.qlo, g.qhi, x);
+  const uint32_t slo = c > g.qlo ? (c - 1) * stride + 1 : g.lo, shi = c < g.qhi ? c * stride : g.hi;
+  return rank_bound<UPPER>(S, slo, shi, x);
+}
+
+// The placement of a candidate of key x against the positives of the segment: 2 #{above x} + #{equal to x} = 2 (hi - lo) -
+// (lb - lo) - (ub - lo) <= 2 np < 2^32; lb = the first position at or above x, tie = whether that one equals x.
+__device__ __forceinline__ uint32_t dl_placement(const uint32_t* __restrict__ S, const uint32_t* smp, uint32_t stride, DlSeg g,
+                                                 uint32_t x, uint32_t& lb, bool& tie) {
+  lb = dl_find<false>(S, smp, stride, g, x);
+  tie = lb < g.hi && S[lb] == x;
+  const uint32_t ub = tie ? dl_find<true>(S, smp, stride, g, x) : lb;
+  return 2u * (g.hi - g.lo) - (lb - g.lo) - (ub - g.lo);
+}
+__device__ __forceinline__ uint32_t dl_placement(const uint32_t* __restrict__ S, const uint32_t* smp, uint32_t stride, DlSeg g,
+                                                 uint32_t x) {
+  uint32_t lb;
+  bool tie;
+  return dl_placement(S, smp, stride, g, x, lb, tie);
 }
 
 // h[bin] += 1 for every lane with `on`.  The lanes of the wave that share one of its first DL_SHARED_BINS distinct bins add
@@ -54,20 +129,15 @@ __device__ __forceinline__ void dl_hist_add(uint32_t* __restrict__ h, uint32_t b
   if ((todo >> lane) & 1ull) atomicAdd(&h[bin], 1u);
 }
 
-// one scoring's share of a negative: lb, ub among the sorted positives, the two counts, the placement 2 np - lb - ub
-__device__ __forceinline__ uint32_t dl_negative(const DlSide& s, uint32_t np, const uint32_t* smp, uint32_t ns, uint32_t stride,
-                                                float score, bool neg) {
-  uint32_t lb = 0, ub = 0;
+// one scoring's share of a negative: its placement among the sorted positives and the two counts
+__device__ __forceinline__ uint32_t dl_negative(const DlSide& s, uint32_t np, const uint32_t* smp, DlSamples sm, float score,
+                                                bool neg) {
+  uint32_t lb = 0, b = 0;
   bool tie = false;
-  if (neg) {
-    const uint32_t x = auc_key(score);
-    lb = dl_find<false>(s.sorted, np, smp, ns, stride, x);
-    tie = lb < np && s.sorted[lb] == x;
-    ub = tie ? dl_find<true>(s.sorted, np, smp, ns, stride, x) : lb;
-  }
+  if (neg) b = dl_placement(s.sorted, smp, sm.stride, dl_all(np, sm), auc_key(score), lb, tie);
   dl_hist_add(s.hist, lb, neg);
   dl_hist_add(s.ties, lb, tie);
-  return 2u * np - lb - ub;          // <= 2 np < 2^32
+  return b;                          // (0 for a positive: the callers use it under `neg`)
 }
 
 // one scoring's share of the positive at `slot`: a = 2 (negatives at or below it) - (negatives equal to it)
@@ -76,69 +146,5 @@ __device__ __forceinline__ uint64_t dl_positive(const DlSide& s, uint32_t np, ui
   return 2 * (s.cum[l] + s.hist[l]) - s.ties[l];                          // <= 2 N < 2^32
 }
 
-// counts[b] = positives of block b's rows; flags |= the argument errors it meets (SB != NULL: of the second scoring too);
-// NODES: deg[v] = positives that contain position v
-template <bool NODES>
-__global__ __launch_bounds__(AUC_THREADS) void k_dl_classify(int rows, const float* __restrict__ SA, int64_t lda,
-                                                             const float* __restrict__ SB, int64_t ldb,
-                                                             const float* __restrict__ L, int64_t ldl,
-                                                             const int64_t* __restrict__ idx, uint64_t* __restrict__ counts,
-                                                             uint32_t* __restrict__ deg, int* __restrict__ flags) {
-  __shared__ uint64_t sh[AUC_THREADS / 64];
-  uint32_t pos = 0, mine = 0;                          // mine: this lane's positives of the row at hand
-  int f = 0;
-  tri_for_each(rows, idx, [&](int, int b, int64_t u, int64_t v) {
-    const float l = L[u * ldl + v];
-    if (!auc_finite(SA[u * lda + v])) f |= AUC_BAD_SCORE;
-    if (!NODES && SB && !auc_finite(SB[u * ldb + v])) f |= DL_BAD_SCORE_B;
-    if (auc_pos(l)) { ++mine; if (NODES) atomicAdd(&deg[b], 1u); }
-    else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-  }, [&](int a) {
-    if (NODES && mine) atomicAdd(&deg[a], mine);
-    pos += mine;
-    mine = 0;
-  });
-  if (f) atomicOr(flags, f);
-  const uint64_t p = block_sum_u64(pos, sh);
-  if (threadIdx.x == 0) counts[blockIdx.x] = p;
-}
-
-// block b's positives take the slots offs[b] .. (any order inside a block): ka[slot] = key of the pair's score in SA;
-// second[slot] = NODES: its endpoints a << 16 | b; else (SB != NULL) the key of its score in SB
-template <bool NODES>
-__global__ __launch_bounds__(AUC_THREADS) void k_dl_emit(int rows, const float* __restrict__ SA, int64_t lda,
-                                                         const float* __restrict__ SB, int64_t ldb,
-                                                         const float* __restrict__ L, int64_t ldl,
-                                                         const int64_t* __restrict__ idx, const uint64_t* __restrict__ offs,
-                                                         uint32_t* __restrict__ ka, uint32_t* __restrict__ second) {
-  __shared__ uint32_t cur;
-  if (threadIdx.x == 0) cur = 0;
-  __syncthreads();
-  const uint64_t o_pos = offs[blockIdx.x];
-  tri_for_each(rows, idx, [&](int a, int b, int64_t u, int64_t v) {
-    const bool p = auc_pos(L[u * ldl + v]);
-    const uint64_t at = o_pos + wave_slot(p, &cur);
-    if (!p) return;
-    ka[at] = auc_key(SA[u * lda + v]);
-    if (NODES) second[at] = (uint32_t)a << 16 | (uint32_t)b;
-    else if (SB) second[at] = auc_key(SB[u * ldb + v]);
-  });
-}
-
-// Behind the classify pass of g blocks: its counts and flags come back (one sync), a flagged argument is refused, h[b]
-// becomes the slots before block b, and P, N are the two classes of the rows (rows - 1) / 2 pairs.
-inline int dl_counted(const char* who, hipStream_t st, const uint64_t* counts, const int* flags, int g, bool paired, int rows,
-                      std::vector<uint64_t>& h, uint64_t& P, uint64_t& N) {
-  h.resize(g);
-  int h_flags = 0;
-  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCGRA_HIP(hipStreamSynchronize(st));
-  if (int rc = rank_flag_error(who, h_flags, paired)) return rc;
-  P = 0;
-  for (int i = 0; i < g; ++i) { const uint64_t p = h[i]; h[i] = P; P += p; }        // counts -> offsets
-  N = (uint64_t)rows * (rows - 1) / 2 - P;
-  return 0;
-}
 }  // namespace
 }  // namespace mcgra

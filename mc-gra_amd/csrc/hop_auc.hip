@@ -10,27 +10,22 @@
 // no path.  Per class c: pairs_c, above_c = those with score >= threshold (mcgra_threshold_pairs' comparison) and, for
 // c >= 2, T_c = the sum over the class's candidates q of b_q = 2 #{edges that score higher} + #{edges that score the same}.
 //
-// A graph is mcgra_graph_structure's row-major BIT matrix: m rows of W = ceil(m / 64) 64-bit words, bit (a, b) at word b / 64
-// of row a, bit b % 64; zero pad bits at positions >= m.  reach_h has bit (a, b) iff a walk of 1 .. h edges joins a and b, so
-// for a != b iff dist(a, b) <= h (its diagonal is set from h = 2 on: there and back; no pass reads it).
+// A graph is a bit matrix (bit_graph.h).  reach_h has bit (a, b) iff a walk of 1 .. h edges joins a and b, so for a != b iff
+// dist(a, b) <= h (its diagonal is set from h = 2 on: there and back; no pass reads it).
 // Passes:
-//   rank_check_idx  idx only: range check, repeats (rank_common.hip)
-//   k_dl_classify   (delong_common.h) one read of the selected strict lower triangle: the argument checks (NaN / inf score,
-//                   label other than 0 / 1) and per-block counts of the positives
-//   k_ha_pack       a read of the labels in 64 x 64 tiles of positions, graph_structure.hip's tile for one graph: a ballot IS
-//                   the word (row a, word B), the tile's words parked in LDS and a second ballot per column give the mirrored
-//                   word (row b, word A).  Every word of reach_1 = G has one writer
+//   DlStage         (delong_common.hip) rank_check_idx; k_dl_classify: one read of the selected strict lower triangle, the
+//                   argument checks (NaN / inf score, label other than 0 / 1) and per-block counts of the positives; later
+//                   k_dl_emit: the positives' keys to their slots; auc_sort sorts them in place
+//   k_ha_pack       bg_pack_tile with the one bit "label is 1": reach_1 = G
 //   k_ha_expand     H - 1 times, from level h's matrix into level h + 1's: one block per row a.  reach_h+1[a] = reach_h[a] |
 //                   OR over the neighbours u of a in G of reach_h[u].  The neighbours are the set bits of G's row a (in LDS,
-//                   walked as a scalar loop); lane t owns the words t, t + 256, .. of the row and ORs the same words of every
-//                   neighbour's row in (coalesced), HA_BATCH neighbours of one word at a time while it holds as many (a hub's
-//                   row is one block's work).  One writer per word, no atomics, never in place
-//   k_dl_emit       (delong_common.h) the positives' keys to their slots; auc_sort sorts them in place
+//                   bg_for_each_neighbour); lane t owns the words t, t + 256, .. of the row and ORs the same words of every
+//                   neighbour's row in (coalesced).  One writer per word, no atomics, never in place
 //   k_ha_stream     ONE pass over the selected strict lower triangle that reads all H levels: the class of a candidate is
-//                   H - #{levels whose bit (a, b) is set} (the levels are nested), 0 for an edge; a non-edge finds lb and ub
-//                   among the sorted positives (delong_common.h's dl_find through samples in LDS), b = 2 P - lb - ub.  Per
-//                   class pairs, T and above accumulate in registers, then block_sum_u64, then one 64-bit integer atomic per
-//                   class, quantity and block
+//                   H - #{levels whose bit (a, b) is set} (the levels are nested), 0 for an edge; a non-edge finds its
+//                   placement among the sorted positives (delong_common.h's dl_placement through samples in LDS).  Per class
+//                   pairs, T and above accumulate in registers, then block_add_u64: one 64-bit integer atomic per class,
+//                   quantity and block
 // Integer arithmetic only: the same bits on every call and under any permutation of idx.  `out` is written by the host once
 // everything has come back.
 // Device scratch: H bit matrices of 8 m W bytes (all levels are kept for the one stream pass; H = 3: 38 MB at m = 10 000, 1.6 GB
@@ -40,79 +35,34 @@
 #include <string.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "../../include/mcgra.h"
+#include "bit_graph.h"
 #include "common.h"
 #include "delong_common.h"
 #include "rank_common.h"
 
 namespace mcgra {
 namespace {
-constexpr int HA_TILE = 64;                          // positions per tile side = bits per word = lanes per wave
-constexpr int HA_WAVES = AUC_THREADS / 64;           // waves per block
-constexpr int HA_ROWS = HA_TILE / HA_WAVES;          // rows (pack) or columns (mirror) of a tile per wave
-constexpr int HA_BATCH = 8;                          // neighbours of one word whose rows a block of the expansion reads together
-constexpr int HA_MAX_W = (int)((AUC_MAX_NIDX + 63) / 64);      // words per row at the capacity: 8 KiB of LDS
-constexpr int HA_LANE_WORDS = HA_MAX_W / AUC_THREADS;          // words of a row a lane of the expansion owns, at most
+constexpr int HA_LANE_WORDS = BG_MAX_W / AUC_THREADS;          // words of a row a lane of the expansion owns, at most
 constexpr int HA_ROW_BLOCKS = 1024;                  // blocks of the passes over the selected rows (grid-stride)
 constexpr int HA_CLASSES = MCGRA_HOP_MAX + 1;        // distances 1 .. MCGRA_HOP_MAX and beyond
-static_assert(HA_ROWS <= 64 && HA_TILE == 64, "a wave parks its words in its first HA_ROWS lanes");
-static_assert(HA_LANE_WORDS * AUC_THREADS == HA_MAX_W, "the lanes of one block cover a row of the capacity");
+static_assert(HA_LANE_WORDS * AUC_THREADS == BG_MAX_W, "the lanes of one block cover a row of the capacity");
 
 enum { HA_PAIRS = 0, HA_T, HA_ABOVE, HA_COLS };
-
-struct HaHead {
-  unsigned long long acc[HA_CLASSES][HA_COLS];
-  int flags, pad;
-};
 
 // Tile (A, B), B <= A, of block p = A (A + 1) / 2 + B: G's words (row a, word B) and (row b, word A).  The labels were checked.
 __global__ __launch_bounds__(AUC_THREADS) void k_ha_pack(int m, int W, const float* __restrict__ L, int64_t ldl,
                                                          const int64_t* __restrict__ idx, uint64_t* __restrict__ MG) {
-  __shared__ uint64_t tG[HA_TILE];
-  uint32_t A1, B;
-  topk_unpack(blockIdx.x, A1, B);                                // A1 = A + 1 > B
-  const int A = (int)A1 - 1, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = HA_TILE * (int)B + lane;                         // this lane's column
-  const int64_t v = b < m ? (idx ? idx[b] : (int64_t)b) : 0;
-  uint64_t mine = 0;                                             // lane i < HA_ROWS: the word of row wv * HA_ROWS + i
-#pragma unroll 4
-  for (int i = 0; i < HA_ROWS; ++i) {
-    const int a = HA_TILE * A + wv * HA_ROWS + i;                // the same in every lane of the wave
-    bool g = false;
-    if (a < m && b < a) {                                        // so b < m
-      const int64_t u = idx ? idx[a] : (int64_t)a;
-      g = auc_pos(L[u * ldl + v]);
-    }
-    const uint64_t w = __ballot(g);
-    if (lane == i) mine = w;
-  }
-  if (lane < HA_ROWS) {
-    const int r = wv * HA_ROWS + lane, a = HA_TILE * A + r;
-    tG[r] = mine;
-    if (A != (int)B && a < m) MG[(size_t)a * W + B] = mine;      // the diagonal tile stores below
-  }
-  __syncthreads();
-  const uint64_t row = tG[lane];                                 // this lane's ROW of the tile
-  mine = 0;
-#pragma unroll 4
-  for (int i = 0; i < HA_ROWS; ++i) {
-    const int c = wv * HA_ROWS + i;                              // column c of the tile: bit r of the mirrored word = bit c of row r
-    const uint64_t w = __ballot((row >> c) & 1ull);
-    if (lane == i) mine = w;
-  }
-  if (lane < HA_ROWS) {
-    const int c = wv * HA_ROWS + lane, r = HA_TILE * (int)B + c;
-    if (A == (int)B) mine |= tG[c];                              // columns below the diagonal | columns above it
-    if (r < m) MG[(size_t)r * W + A] = mine;
-  }
+  __shared__ uint64_t tile[1][BG_TILE];
+  bg_pack_tile<1>(m, W, idx, tile, [&](int64_t u, int64_t v, bool (&bit)[1]) { bit[0] = auc_pos(L[u * ldl + v]); },
+                  [&](size_t at, const uint64_t (&w)[1]) { MG[at] = w[0]; });
 }
 
 // Block v: out row v = in row v | the rows of `in` of v's neighbours in G.
 __global__ __launch_bounds__(AUC_THREADS) void k_ha_expand(int W, const uint64_t* __restrict__ G, const uint64_t* __restrict__ in,
                                                            uint64_t* __restrict__ out) {
-  __shared__ uint64_t row[HA_MAX_W];
+  __shared__ uint64_t row[BG_MAX_W];
   const size_t v = blockIdx.x;
   uint64_t acc[HA_LANE_WORDS];
 #pragma unroll
@@ -125,40 +75,26 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ha_expand(int W, const uint64_t
     }
   }
   __syncthreads();
-  for (int j = 0; j < W; ++j) {
-    const uint64_t x = row[j];
-    uint64_t bits = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32) |
-                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);      // the same in every lane: a scalar loop
-    // the set bits are the neighbours u = 64 j + bit of v (u < m: the pad bits are 0)
-    while (__popcll(bits) >= HA_BATCH) {
-      const uint64_t* pu[HA_BATCH];
-#pragma unroll
-      for (int q = 0; q < HA_BATCH; ++q) {
-        pu[q] = in + (size_t)(HA_TILE * j + __ffsll((unsigned long long)bits) - 1) * W;
-        bits &= bits - 1;
-      }
+  for (int j = 0; j < W; ++j)
+    bg_for_each_neighbour(row[j], j, in, W, [&](auto& pu) {
 #pragma unroll
       for (int q = 0; q < HA_LANE_WORDS; ++q) {
         const int k = threadIdx.x + q * AUC_THREADS;
         if (k < W) {
-          uint64_t y[HA_BATCH];
+          uint64_t y[BG_BATCH];
 #pragma unroll
-          for (int s = 0; s < HA_BATCH; ++s) y[s] = pu[s][k];
+          for (int s = 0; s < BG_BATCH; ++s) y[s] = pu[s][k];
 #pragma unroll
-          for (int s = 0; s < HA_BATCH; ++s) acc[q] |= y[s];
+          for (int s = 0; s < BG_BATCH; ++s) acc[q] |= y[s];
         }
       }
-    }
-    while (bits) {
-      const uint64_t* __restrict__ pu = in + (size_t)(HA_TILE * j + __ffsll((unsigned long long)bits) - 1) * W;
-      bits &= bits - 1;
+    }, [&](const uint64_t* __restrict__ pu) {
 #pragma unroll
       for (int q = 0; q < HA_LANE_WORDS; ++q) {
         const int k = threadIdx.x + q * AUC_THREADS;
         if (k < W) acc[q] |= pu[k];
       }
-    }
-  }
+    });
 #pragma unroll
   for (int q = 0; q < HA_LANE_WORDS; ++q) {
     const int k = threadIdx.x + q * AUC_THREADS;
@@ -174,12 +110,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ha_stream(int rows, int W, int 
                                                            uint32_t T, unsigned long long* __restrict__ acc) {
   __shared__ uint32_t smp[DL_STAGE];
   __shared__ uint64_t sh[AUC_THREADS / 64];
-  uint32_t stride = 1, ns = 0;
-  if (np) {
-    stride = (np + DL_STAGE - 1) / DL_STAGE;
-    ns = (np + stride - 1) / stride;
-    for (uint32_t q = threadIdx.x; q < ns; q += AUC_THREADS) smp[q] = sorted[(uint64_t)q * stride];
-  }
+  const DlSamples sm = dl_stage(sorted, np, smp);
   __syncthreads();
   uint32_t cnt[HA_CLASSES] = {}, abv[HA_CLASSES] = {};           // a lane sees fewer than 2^32 candidates
   uint64_t sum[HA_CLASSES] = {};
@@ -189,11 +120,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ha_stream(int rows, int W, int 
     int cls = H;                                                 // the levels are nested: H - #{levels that hold the pair}
     for (int h = 0; h < H; ++h) cls -= (int)((M[h * plane + at] >> (b & 63)) & 1ull);
     uint64_t bq = 0;
-    if (cls > 0 && np) {
-      const uint32_t lb = dl_find<false>(sorted, np, smp, ns, stride, x);
-      const uint32_t ub = (lb < np && sorted[lb] == x) ? dl_find<true>(sorted, np, smp, ns, stride, x) : lb;
-      bq = 2ull * np - lb - ub;                                  // <= 2 np < 2^32
-    }
+    if (cls > 0 && np) bq = dl_placement(sorted, smp, sm.stride, dl_all(np, sm), x);
     const bool above = x >= T;
 #pragma unroll
     for (int c = 0; c < HA_CLASSES; ++c) {
@@ -207,12 +134,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_ha_stream(int rows, int W, int 
   for (int c = 0; c < HA_CLASSES; ++c) {
     if (c <= H) {                                                // the same in every lane
       const uint64_t part[HA_COLS] = {cnt[c], sum[c], abv[c]};
-#pragma unroll
-      for (int q = 0; q < HA_COLS; ++q) {
-        __syncthreads();
-        const uint64_t tot = block_sum_u64(part[q], sh);
-        if (threadIdx.x == 0 && tot) atomicAdd(&acc[c * HA_COLS + q], (unsigned long long)tot);
-      }
+      block_add_u64(part, sh, acc + c * HA_COLS);
     }
   }
 }
@@ -236,59 +158,35 @@ extern "C" int mcgra_hop_auc(void* stream, int n, const float* labels, int ld_la
   hipStream_t st = (hipStream_t)stream;
   const int m = (int)n_idx, W = (m + 63) / 64, H = hops;
   const size_t plane = (size_t)m * W;
-  const int g = std::min(m - 1, HA_ROW_BLOCKS);
   AucBufs b;
-  uint8_t* head = b.get<uint8_t>(sizeof(HaHead) + sizeof(uint64_t) * (size_t)g);
   uint64_t* M = b.get<uint64_t>(plane * H);
-  if (!head || !M) {
-    (void)hipGetLastError();                                      // the refusal is reported here, not by the next launch check
+  if (!M) {
     set_error("%s: hipMalloc of %d bit matrices of %d x %d words (%llu bytes) failed", who, H, m, W,
               (unsigned long long)(plane * H * sizeof(uint64_t)));
     return MCGRA_ENOMEM;
   }
-  HaHead* hd = (HaHead*)head;
-  uint64_t* counts = (uint64_t*)(head + sizeof(HaHead));
-  static_assert(sizeof(HaHead) % 8 == 0, "counts is 8-byte aligned");
-  MCGRA_HIP(hipMemsetAsync(hd, 0, sizeof(HaHead), st));
-  if (int rc = rank_check_idx(who, st, b, n, idx, m, &hd->flags)) return rc;
-  k_dl_classify<false><<<g, AUC_THREADS, 0, st>>>(m, scores, ld_scores, nullptr, 0, labels, ld_labels, idx, counts, nullptr,
-                                                  &hd->flags);
-  MCGRA_KERNEL_CHECK();
-  std::vector<uint64_t> h;
-  uint64_t P = 0, N = 0;
-  if (int rc = dl_counted(who, st, counts, &hd->flags, g, false, m, h, P, N)) return rc;
-  const unsigned tiles = (unsigned)W * (unsigned)(W + 1) / 2;           // at most 1024 * 1025 / 2
-  k_ha_pack<<<tiles, AUC_THREADS, 0, st>>>(m, W, labels, ld_labels, idx, M);
+  DlStage stage{who, st, b, n, labels, scores, nullptr, ld_labels, ld_scores, 0, idx, m, std::min(m - 1, HA_ROW_BLOCKS)};
+  typedef unsigned long long Acc[HA_CLASSES][HA_COLS];
+  if (int rc = stage.start(sizeof(Acc))) return rc;
+  if (int rc = stage.counted()) return rc;
+  const uint64_t P = stage.P, N = stage.N;
+  const int g = stage.g;
+  k_ha_pack<<<bg_tiles(W), AUC_THREADS, 0, st>>>(m, W, labels, ld_labels, idx, M);
   for (int lv = 1; lv < H; ++lv) k_ha_expand<<<m, AUC_THREADS, 0, st>>>(W, M, M + (lv - 1) * plane, M + lv * plane);
   MCGRA_KERNEL_CHECK();
   uint32_t* sorted = nullptr;
   if (P) {
-    // one allocation for what scales with P: the sort's counts, the keys, the sort's second buffer.  P4 = P rounded up to 4
-    // keys: every array starts on 16 bytes
-    const size_t P4 = (P + 3) / 4 * 4, sort_cnt = 256 * (size_t)AUC_SORT_BLOCKS;
-    uint8_t* pool = b.get<uint8_t>((sizeof(uint64_t) + sizeof(uint32_t)) * sort_cnt + 2 * sizeof(uint32_t) * P4);
-    if (!pool) {
-      (void)hipGetLastError();
-      set_error("%s: hipMalloc of the scratch of %llu positives failed", who, (unsigned long long)P);
-      return MCGRA_ENOMEM;
-    }
-    uint64_t* off = (uint64_t*)pool;
-    uint32_t* cnt = (uint32_t*)(off + sort_cnt);
-    sorted = cnt + sort_cnt;
-    uint32_t* tmp = sorted + P4;
-    MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-    k_dl_emit<false><<<g, AUC_THREADS, 0, st>>>(m, scores, ld_scores, nullptr, 0, labels, ld_labels, idx, counts, sorted, nullptr);
-    MCGRA_KERNEL_CHECK();
-    if (int rc = auc_sort(st, sorted, tmp, P, cnt, off)) return rc;
+    Carver c{};
+    if (int rc = stage.pool(2, 0, c)) return rc;                        // the keys, the sort's second buffer
+    sorted = c.take<uint32_t>(stage.P4);
+    if (int rc = stage.emit(sorted, nullptr)) return rc;
+    if (int rc = auc_sort(st, sorted, c.take<uint32_t>(stage.P4), P, stage.sort)) return rc;
   }
-  uint32_t tb;
-  memcpy(&tb, &threshold, sizeof(tb));
-  if (tb == 0x80000000u) tb = 0u;
-  const uint32_t T = (tb & 0x80000000u) ? ~tb : (tb | 0x80000000u);     // auc_key of the threshold (+-inf included)
-  k_ha_stream<<<g, AUC_THREADS, 0, st>>>(m, W, H, scores, ld_scores, idx, M, plane, sorted, (uint32_t)P, T, &hd->acc[0][0]);
+  const uint32_t T = auc_key_host(threshold);
+  k_ha_stream<<<g, AUC_THREADS, 0, st>>>(m, W, H, scores, ld_scores, idx, M, plane, sorted, (uint32_t)P, T, (unsigned long long*)stage.extra);
   MCGRA_KERNEL_CHECK();
-  unsigned long long ha[HA_CLASSES][HA_COLS];
-  MCGRA_HIP(hipMemcpyAsync(ha, hd->acc, sizeof(ha), hipMemcpyDeviceToHost, st));
+  Acc ha;
+  MCGRA_HIP(hipMemcpyAsync(ha, stage.extra, sizeof(ha), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipStreamSynchronize(st));                                  // the scratch is freed on return
   unsigned long long all = 0, t1 = 0;
   for (int c = 0; c <= H; ++c) { all += ha[c][HA_PAIRS]; t1 += ha[c][HA_T]; }

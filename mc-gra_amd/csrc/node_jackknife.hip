@@ -15,9 +15,9 @@
 //
 // Only the positives are stored, as in delong.hip; the negatives are streamed.  Passes:
 //   rank_check_idx     idx only: range check, repeats (rank_common.hip)
-//   k_dl_classify      (delong_common.h, NODES) one read of the selected lower triangle: the argument checks, per-block
-//                      positive counts, and P_v (deg[a] += 1, deg[b] += 1 per positive: 32-bit integer atomics)
-//   k_dl_emit          (delong_common.h, NODES) a second read of the labels: each positive's key and its endpoints
+//   k_dl_classify      (DlStage of delong_common.hip, NODES) one read of the selected lower triangle: the argument checks,
+//                      per-block positive counts, and P_v (deg[a] += 1, deg[b] += 1 per positive: 32-bit integer atomics)
+//   k_dl_emit          (DlStage, NODES) a second read of the labels: each positive's key and its endpoints
 //                      a << 16 | b to a slot of its block's range.  Which slot depends on the order the waves run in; the
 //                      sort below ends that
 //   auc_sort           the positives by key, the endpoints riding along.  Equal keys may keep either order of their endpoints:
@@ -92,8 +92,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_nj_negatives(int rows, DlSide s
   __shared__ uint32_t smp[DL_STAGE];
   __shared__ uint64_t col_b[NJ_COLS], col_c[NJ_COLS];
   __shared__ uint64_t sh_b[AUC_THREADS / 64], sh_c[AUC_THREADS / 64];
-  const uint32_t stride = (np + DL_STAGE - 1) / DL_STAGE, ns = (np + stride - 1) / stride;
-  for (uint32_t q = threadIdx.x; q < ns; q += AUC_THREADS) smp[q] = s.sorted[(uint64_t)q * stride];
+  const DlSamples sm = dl_stage(s.sorted, np, smp);
   __syncthreads();
   uint64_t total = 0;
   for (int c0 = 0; c0 + 1 < rows; c0 += NJ_COLS) {                 // column rows - 1 has no row above it
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(AUC_THREADS) void k_nj_negatives(int rows, DlSide s
         const int64_t v = idx ? idx[b] : b;
         const float x = srow[v];
         const bool neg = !auc_pos(lrow[v]);                         // the labels were checked: 0 or 1
-        const uint64_t bq = dl_negative(s, np, smp, ns, stride, x, neg);
+        const uint64_t bq = dl_negative(s, np, smp, sm, x, neg);
         if (neg) {
           const uint32_t k = auc_key(x);
           const uint64_t ob = noff[b];
@@ -134,9 +133,8 @@ __global__ __launch_bounds__(AUC_THREADS) void k_nj_negatives(int rows, DlSide s
       if (col_c[j]) atomicAdd(&out[(size_t)(c0 + j) * NJ_WORDS + NJ_C], (unsigned long long)col_c[j]);
     }
   }
-  __syncthreads();
-  const uint64_t tot = block_sum_u64(total, sh_b);
-  if (threadIdx.x == 0 && tot) atomicAdd(t_neg, (unsigned long long)tot);
+  const uint64_t tot[1] = {total};
+  block_add_u64(tot, sh_b, t_neg);
 }
 
 // The positives, in sorted order: out[a][NJ_A] += a_p, out[b][NJ_A] += a_p, *t_pos += a_p
@@ -169,81 +167,61 @@ __global__ __launch_bounds__(AUC_THREADS) void k_nj_finish(int rows, const uint3
 int nj_run(const char* who, hipStream_t st, int n, const float* L, int ldl, const float* S, int lds, const int64_t* idx, int rows,
            uint64_t* header, uint64_t* out) {
   AucBufs b;
-  const int g = std::min(rows - 1, NJ_ROW_BLOCKS);
-  // one allocation for what scales with the selection: the two placement sums, flags, the per-block counts, the staged
-  // answer, noff [rows + 1], deg [rows + 1] (deg[rows] = 0: the scan's last entry is the total)
-  struct Head { unsigned long long t_pos, t_neg; int flags, pad; };
-  static_assert(sizeof(Head) % 8 == 0, "counts is 8-byte aligned");
-  const size_t R1 = (size_t)rows + 1;
-  const size_t head_bytes = sizeof(Head) + sizeof(uint64_t) * ((size_t)g + (size_t)rows * NJ_WORDS + R1) + sizeof(uint32_t) * R1;
-  uint8_t* head = b.get<uint8_t>(head_bytes);
-  if (!head) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
-  Head* hd = (Head*)head;
-  uint64_t* counts = (uint64_t*)(head + sizeof(Head));
-  unsigned long long* stage = (unsigned long long*)(counts + g);
-  uint64_t* noff = (uint64_t*)(stage + (size_t)rows * NJ_WORDS);
-  uint32_t* deg = (uint32_t*)(noff + R1);
-  MCGRA_HIP(hipMemsetAsync(head, 0, head_bytes, st));
-  if (int rc = rank_check_idx(who, st, b, n, idx, rows, &hd->flags)) return rc;
-  k_dl_classify<true><<<g, AUC_THREADS, 0, st>>>(rows, S, lds, nullptr, 0, L, ldl, idx, counts, deg, &hd->flags);
-  MCGRA_KERNEL_CHECK();
-  std::vector<uint64_t> h;
-  uint64_t P = 0, N = 0;
-  if (int rc = dl_counted(who, st, counts, &hd->flags, g, false, rows, h, P, N)) return rc;
-  const uint64_t m = P + N;
-  const int gr = (rows + AUC_THREADS - 1) / AUC_THREADS;
+  DlStage stage{who, st, b, n, L, S, nullptr, ldl, lds, 0, idx, rows, std::min(rows - 1, NJ_ROW_BLOCKS)};
+  // behind the stage's counts, what scales with the selection: the two placement sums, the staged answer, noff [rows + 1],
+  // deg [rows + 1] (deg[rows] = 0: the scan's last entry is the total)
+  const size_t R1 = (size_t)rows + 1, words = 2 + (size_t)rows * NJ_WORDS + R1;
+  if (int rc = stage.start(sizeof(uint64_t) * words + sizeof(uint32_t) * R1, sizeof(uint64_t) * words)) return rc;
+  unsigned long long* t_sums = (unsigned long long*)stage.extra;           // {t_pos, t_neg}
+  unsigned long long* out_stage = t_sums + 2;
+  uint64_t* noff = (uint64_t*)(out_stage + (size_t)rows * NJ_WORDS);
+  uint32_t* deg = stage.deg;
+  if (int rc = stage.counted()) return rc;
+  const uint64_t P = stage.P, N = stage.N, m = P + N;
+  const int g = stage.g, gr = (rows + AUC_THREADS - 1) / AUC_THREADS;
   unsigned long long t[2] = {0, 0};
   if (P != 0 && N != 0) {                               // else every placement is 0
-    // one allocation for what scales with P.  P4 = P rounded up to 4 keys: every array starts on 16 bytes.  cum [P4 + 4];
-    // key, ends, their second buffers [P4]; hist, ties [P4 + 4]; lnode, lkey, their second buffers [2 P4]; the sort's counts
-    const size_t P4 = (P + 3) / 4 * 4, H4 = P4 + 4;
-    const size_t sort_cnt = 256 * (size_t)AUC_SORT_BLOCKS;
-    const size_t bytes = sizeof(uint64_t) * (H4 + sort_cnt) + sizeof(uint32_t) * (4 * P4 + 2 * H4 + 8 * P4 + sort_cnt);
-    uint8_t* pool = b.get<uint8_t>(bytes);
-    if (!pool) { set_error("%s: hipMalloc of the scratch of %llu positives failed", who, (unsigned long long)P); return MCGRA_ENOMEM; }
-    uint8_t* at = pool;
-    auto take = [&](size_t count, size_t size) { uint8_t* p = at; at += count * size; return p; };
+    // cum; key, ends, their second buffers; hist, ties; lnode, lkey, their second buffers [2 P4]
+    const size_t P4 = stage.P4, H4 = stage.H4;
+    Carver c{};
+    if (int rc = stage.pool(4 + 8, 2 + 2, c)) return rc;
     DlSide s = {};
     s.S = S;
     s.ld = lds;
-    s.cum = (uint64_t*)take(H4, 8);
-    uint64_t* off = (uint64_t*)take(sort_cnt, 8);
-    s.sorted = s.slot = (uint32_t*)take(P4, 4);         // the positives' pass runs over the sorted positives
-    uint32_t* ends = (uint32_t*)take(P4, 4);
-    uint32_t* tmp = (uint32_t*)take(P4, 4);
-    uint32_t* etmp = (uint32_t*)take(P4, 4);
-    s.hist = (uint32_t*)take(H4, 4);
-    s.ties = (uint32_t*)take(H4, 4);
-    uint32_t* lnode = (uint32_t*)take(2 * P4, 4);
-    uint32_t* lkey = (uint32_t*)take(2 * P4, 4);
-    uint32_t* ltmp = (uint32_t*)take(2 * P4, 4);
-    uint32_t* ktmp = (uint32_t*)take(2 * P4, 4);
-    uint32_t* cnt = (uint32_t*)take(sort_cnt, 4);
-    MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-    k_dl_emit<true><<<g, AUC_THREADS, 0, st>>>(rows, S, lds, nullptr, 0, L, ldl, idx, counts, s.sorted, ends);
-    MCGRA_KERNEL_CHECK();
-    if (int rc = auc_sort(st, s.sorted, tmp, P, cnt, off, ends, etmp)) return rc;
+    s.cum = c.take<uint64_t>(H4);
+    s.sorted = s.slot = c.take<uint32_t>(P4);           // the positives' pass runs over the sorted positives
+    uint32_t* ends = c.take<uint32_t>(P4);
+    uint32_t* tmp = c.take<uint32_t>(P4);
+    uint32_t* etmp = c.take<uint32_t>(P4);
+    s.hist = c.take<uint32_t>(H4);
+    s.ties = c.take<uint32_t>(H4);
+    uint32_t* lnode = c.take<uint32_t>(2 * P4);
+    uint32_t* lkey = c.take<uint32_t>(2 * P4);
+    uint32_t* ltmp = c.take<uint32_t>(2 * P4);
+    uint32_t* ktmp = c.take<uint32_t>(2 * P4);
+    if (int rc = stage.emit(s.sorted, ends)) return rc;
+    if (int rc = auc_sort(st, s.sorted, tmp, P, stage.sort, ends, etmp)) return rc;
     const int gp = (int)std::min<uint64_t>(NJ_POS_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
     k_nj_lists<<<gp, AUC_THREADS, 0, st>>>(s.sorted, ends, (uint32_t)P, lnode, lkey);
     MCGRA_KERNEL_CHECK();
-    if (int rc = auc_sort(st, lnode, ltmp, 2 * P, cnt, off, lkey, ktmp)) return rc;
+    if (int rc = auc_sort(st, lnode, ltmp, 2 * P, stage.sort, lkey, ktmp)) return rc;
     rank_scan(st, deg, rows + 1, noff);
     MCGRA_HIP(hipMemsetAsync(s.hist, 0, sizeof(uint32_t) * 2 * H4, st));               // hist and ties are adjacent
-    k_nj_negatives<<<g, AUC_THREADS, 0, st>>>(rows, s, L, ldl, idx, (uint32_t)P, lkey, noff, stage, &hd->t_neg);
+    k_nj_negatives<<<g, AUC_THREADS, 0, st>>>(rows, s, L, ldl, idx, (uint32_t)P, lkey, noff, out_stage, t_sums + 1);
     MCGRA_KERNEL_CHECK();
     rank_scan(st, s.hist, (int)P, s.cum);
-    k_nj_positives<<<gp, AUC_THREADS, 0, st>>>(s, ends, (uint32_t)P, stage, &hd->t_pos);
+    k_nj_positives<<<gp, AUC_THREADS, 0, st>>>(s, ends, (uint32_t)P, out_stage, t_sums);
     MCGRA_KERNEL_CHECK();
   }
-  k_nj_finish<<<gr, AUC_THREADS, 0, st>>>(rows, deg, stage);
+  k_nj_finish<<<gr, AUC_THREADS, 0, st>>>(rows, deg, out_stage);
   MCGRA_KERNEL_CHECK();
-  MCGRA_HIP(hipMemcpyAsync(t, &hd->t_pos, sizeof(t), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipMemcpyAsync(t, t_sums, sizeof(t), hipMemcpyDeviceToHost, st));
   MCGRA_HIP(hipStreamSynchronize(st));
   if (t[0] != t[1]) {                                   // sum a_p == sum b_q by construction
     set_error("%s: internal error: the two placement sums differ (%llu, %llu)", who, t[0], t[1]);
     return MCGRA_EHIP;
   }
-  MCGRA_HIP(hipMemcpyAsync(out, stage, sizeof(uint64_t) * NJ_WORDS * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  MCGRA_HIP(hipMemcpyAsync(out, out_stage, sizeof(uint64_t) * NJ_WORDS * (size_t)rows, hipMemcpyDeviceToDevice, st));
   MCGRA_HIP(hipStreamSynchronize(st));                  // the scratch is freed on return
   const uint64_t res[4] = {m, P, N, t[0]};
   memcpy(header, res, sizeof(res));

@@ -1,13 +1,17 @@
-// What the ranking entries share (auc.hip, curves.hip, topk.hip, node_rank.hip, two_means.hip, delong.hip, node_jackknife.hip).
+// What the ranking entries share (auc.hip, curves.hip, topk.hip, node_rank.hip, two_means.hip, delong.hip, node_jackknife.hip,
+// graph_structure.hip, hop_auc.hip, class_auc.hip).
 // Device side, inlined into each file's kernels: the order-preserving key of a float32 score, the label predicates, the pair of
 // a packed position, integer block sums, the walk over the selected lower triangle (tri_for_each), the bound of a key in
 // ascending keys (rank_bound), a lane's slot behind a wave-shared cursor (wave_slot) and its rank among the flagged lanes of a
 // block (block_rank).  Host side, defined once in rank_common.hip: the checks of the arguments and of idx, the table from
 // flag bits to refusals, the tile rule, one scan, and the stable LSD radix sort of 32-bit keys (optionally with a 32-bit
-// payload); their kernels are compiled there and nowhere else.  Everything here is integer work, so no result depends on the
+// payload); their kernels are compiled there and nowhere else.  Here too: the scratch allocations of a call (AucBufs), the
+// carver of one of them into arrays, and the sort's scratch.  Everything here is integer work, so no result depends on the
 // order in which blocks run.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
+#include <string.h>
 
 #include <initializer_list>
 #include <vector>
@@ -19,6 +23,7 @@ namespace mcgra {
 constexpr int AUC_THREADS = 256;
 constexpr int AUC_SORT_TILE = 1024;        // keys staged per step of a sort block (256 lanes x one 16-byte load)
 constexpr int AUC_SORT_BLOCKS = 1024;      // at most this many tiles of keys per sort pass
+constexpr size_t AUC_SORT_COUNTS = 256 * (size_t)AUC_SORT_BLOCKS;      // the (digit, tile) counts of one sort pass
 constexpr int64_t AUC_MAX_NIDX = 65535;    // 2 P N <= 2 (n_idx^2 / 2)^2 < 2^63; a packed pair position fits 32 bits
 
 // DL_BAD_SCORE_B: the second score matrix of a paired entry
@@ -31,9 +36,43 @@ struct AucBufs {
   template <typename T>
   T* get(size_t count) {
     void* q = nullptr;
-    if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) return nullptr;
+    if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();             // the caller reports the refusal, not the launch check of the next call
+      return nullptr;
+    }
     p.push_back(q);
     return (T*)q;
+  }
+};
+
+// One allocation carved into arrays front to back; every array starts on 16 bytes (the sort loads four keys at a time).
+// bytes<T>(count) is what take<T>(count) uses up.
+struct Carver {
+  uint8_t* at;
+  size_t left;
+  template <typename T>
+  static constexpr size_t bytes(size_t count) { return (count * sizeof(T) + 15) / 16 * 16; }
+  template <typename T>
+  T* take(size_t count) {
+    const size_t need = bytes<T>(count);
+    assert(need <= left);
+    T* q = (T*)at;
+    at += need;
+    left -= need;
+    return q;
+  }
+};
+
+// The sort's scratch: AUC_SORT_COUNTS entries each, carved from a caller's allocation or (b) an allocation of its own
+// (cnt == NULL: hipMalloc failed).
+struct SortScratch {
+  uint32_t* cnt = nullptr;
+  uint64_t* off = nullptr;
+  SortScratch() = default;
+  static constexpr size_t BYTES = Carver::bytes<uint32_t>(AUC_SORT_COUNTS) + Carver::bytes<uint64_t>(AUC_SORT_COUNTS);
+  explicit SortScratch(Carver& c) : cnt(c.take<uint32_t>(AUC_SORT_COUNTS)), off(c.take<uint64_t>(AUC_SORT_COUNTS)) {}
+  explicit SortScratch(AucBufs& b) : cnt(nullptr), off(nullptr) {
+    if (uint8_t* q = b.get<uint8_t>(BYTES)) { Carver c{q, BYTES}; *this = SortScratch(c); }
   }
 };
 
@@ -54,20 +93,28 @@ RankTiles rank_tiles(uint64_t count, int max_blocks, int step);
 // off[i] = cnt[0] + ... + cnt[i - 1] over len entries (one block; the caller checks the launch)
 void rank_scan(hipStream_t st, const uint32_t* cnt, int len, uint64_t* off);
 // stable LSD radix sort of keys[0, count) (a multiple-of-4 aligned region), tmp the same size; result in keys.  pay != NULL:
-// pay[i] travels with keys[i] (ptmp the same size; result in pay).  cnt, off: 256 * AUC_SORT_BLOCKS entries each.  bits (a
-// multiple of 8): every key is below 2^bits, bits / 8 passes; after an odd number of them the result is in tmp (and ptmp).
-int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, uint32_t* cnt, uint64_t* off, uint32_t* pay = nullptr,
+// pay[i] travels with keys[i] (ptmp the same size; result in pay).  bits (a multiple of 8): every key is below 2^bits,
+// bits / 8 passes; after an odd number of them the result is in tmp (and ptmp).
+int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, const SortScratch& ss, uint32_t* pay = nullptr,
              uint32_t* ptmp = nullptr, int bits = 32);
 
-// ---- device side
-namespace {
-// float32 -> unsigned key with the same order; -0.0 and +0.0 are one value.  Bit tests throughout, so that no
-// floating-point mode (denormal flushing) can merge a subnormal with zero.
-__device__ __forceinline__ uint32_t auc_key(float s) {
-  uint32_t u = __float_as_uint(s);
+// ---- both sides
+// float32 (its bits) -> unsigned key with the same order; -0.0 and +0.0 are one value, +-inf are ordinary values.  Bit tests
+// throughout, so that no floating-point mode (denormal flushing) can merge a subnormal with zero.
+__host__ __device__ inline uint32_t auc_key_bits(uint32_t u) {
   if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// the key of a threshold, for the kernels that compare auc_key(score) >= T
+inline uint32_t auc_key_host(float s) {
+  uint32_t u;
+  memcpy(&u, &s, sizeof(u));
+  return auc_key_bits(u);
+}
+
+// ---- device side
+namespace {
+__device__ __forceinline__ uint32_t auc_key(float s) { return auc_key_bits(__float_as_uint(s)); }
 __device__ __forceinline__ bool auc_finite(float s) { return (__float_as_uint(s) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool auc_pos(float l) { return __float_as_uint(l) == 0x3f800000u; }
 __device__ __forceinline__ bool auc_neg(float l) { return (__float_as_uint(l) & 0x7fffffffu) == 0u; }
@@ -95,6 +142,16 @@ __device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* sh) {
   if (threadIdx.x == 0)
     for (int w = 0; w < AUC_THREADS / 64; ++w) t += sh[w];
   return t;
+}
+// acc[q] += the block's sum of part[q] for each of the Q counters: one 64-bit atomic per non-zero counter and block
+template <int Q>
+__device__ __forceinline__ void block_add_u64(const uint64_t (&part)[Q], uint64_t* sh, unsigned long long* __restrict__ acc) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    __syncthreads();                                  // sh is reused
+    const uint64_t tot = block_sum_u64(part[q], sh);
+    if (threadIdx.x == 0 && tot) atomicAdd(&acc[q], (unsigned long long)tot);
+  }
 }
 
 // The selected strict lower triangle: f(a, b, u, v) for every pair of positions b < a of the rows a = 1 + blockIdx.x,

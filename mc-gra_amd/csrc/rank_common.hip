@@ -175,10 +175,12 @@ void rank_scan(hipStream_t st, const uint32_t* cnt, int len, uint64_t* off) {
   k_auc_digit_scan<<<1, 1024, 0, st>>>(cnt, len, off);
 }
 
-int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, uint32_t* cnt, uint64_t* off, uint32_t* pay,
-             uint32_t* ptmp, int bits) {
+int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, const SortScratch& ss, uint32_t* pay, uint32_t* ptmp,
+             int bits) {
   if (count < 2) return 0;
-  const auto [tile, nb] = rank_tiles(count, AUC_SORT_BLOCKS, AUC_SORT_TILE);
+  const auto [tile, nb] = rank_tiles(count, AUC_SORT_BLOCKS, AUC_SORT_TILE);      // 256 nb <= AUC_SORT_COUNTS
+  uint32_t* cnt = ss.cnt;
+  uint64_t* off = ss.off;
   uint32_t *src = keys, *dst = tmp, *psrc = pay, *pdst = ptmp;
   for (int shift = 0; shift < bits; shift += 8) {
     k_auc_digit_count<<<nb, AUC_THREADS, 0, st>>>(src, count, tile, shift, nb, cnt);

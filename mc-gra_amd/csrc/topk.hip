@@ -212,8 +212,7 @@ struct TopkRun {
   TopkState h{};                          // the host's copy, after emit() and after select()
   uint32_t* keys = nullptr;
   uint8_t* lab = nullptr;
-  uint32_t* cnt = nullptr;
-  uint64_t* off = nullptr;
+  SortScratch ss{b};                      // also the counts of select() and their scan
   uint64_t m = 0, tile = 0;
   int nb = 0;
 
@@ -228,9 +227,7 @@ struct TopkRun {
     state = b.get<TopkState>(1);
     keys = b.get<uint32_t>(m);
     lab = want_lab ? b.get<uint8_t>(m) : nullptr;
-    cnt = b.get<uint32_t>(256 * AUC_SORT_BLOCKS);
-    off = b.get<uint64_t>(256 * AUC_SORT_BLOCKS);
-    if (!state || !keys || (want_lab && !lab) || !cnt || !off) {
+    if (!state || !keys || (want_lab && !lab) || !ss.cnt) {
       set_error("%s: hipMalloc of the scratch of %llu pairs failed", who, (unsigned long long)m);
       return MCGRA_ENOMEM;
     }
@@ -255,8 +252,8 @@ struct TopkRun {
     }
     MCGRA_KERNEL_CHECK();
     if (int rc = fetch()) return rc;      // (also: &k was read)
-    k_topk_count<<<nb, AUC_THREADS, 0, st>>>(keys, m, tile, h.prefix, nb, cnt);
-    rank_scan(st, cnt, 2 * nb, off);
+    k_topk_count<<<nb, AUC_THREADS, 0, st>>>(keys, m, tile, h.prefix, nb, ss.cnt);
+    rank_scan(st, ss.cnt, 2 * nb, ss.off);
     MCGRA_KERNEL_CHECK();
     return 0;
   }
@@ -288,7 +285,7 @@ extern "C" int mcgra_topk_metrics(void* stream, int n, const float* labels, int 
   if (kk == 0) return 0;
   if (int rc = run.select(kk)) return rc;
   const uint64_t r = run.h.remaining, g = kk - r;
-  k_topk_take<false><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, run.lab, run.m, run.tile, run.h.prefix, g, r, run.nb, run.off,
+  k_topk_take<false><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, run.lab, run.m, run.tile, run.h.prefix, g, r, run.nb, run.ss.off,
                                                      scores, ld_scores, idx, nullptr, nullptr, run.state);
   MCGRA_KERNEL_CHECK();
   if (int rc = run.fetch()) return rc;
@@ -313,10 +310,10 @@ extern "C" int mcgra_top_pairs(void* stream, int n, const float* scores, int ld_
   if (!rk || !rp || !tk || !tp) { set_error("top_pairs: hipMalloc of %llu records failed", (unsigned long long)kk); return MCGRA_ENOMEM; }
   if (int rc = run.select(kk)) return rc;
   const uint64_t r = run.h.remaining, g = kk - r;
-  k_topk_take<true><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, nullptr, run.m, run.tile, run.h.prefix, g, r, run.nb, run.off,
+  k_topk_take<true><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, nullptr, run.m, run.tile, run.h.prefix, g, r, run.nb, run.ss.off,
                                                     scores, ld_scores, idx, rk, rp, run.state);
   MCGRA_KERNEL_CHECK();
-  if (int rc = auc_sort(st, rk, tk, kk, run.cnt, run.off, rp, tp)) return rc;
+  if (int rc = auc_sort(st, rk, tk, kk, run.ss, rp, tp)) return rc;
   const int gw = (int)std::min<uint64_t>(2048, (kk + AUC_THREADS - 1) / AUC_THREADS);
   k_topk_write<<<gw, AUC_THREADS, 0, st>>>(kk, rp, scores, ld_scores, labels, ld_labels, idx, pairs, pair_scores, hits);
   MCGRA_KERNEL_CHECK();

@@ -374,10 +374,7 @@ extern "C" int mcgra_threshold_pairs(void* stream, int n, const float* scores, i
   if (!state || !cnt || !off) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
   MCGRA_HIP(hipMemsetAsync(state, 0, sizeof(TpState), st));
   if (int rc = rank_check_idx(who, st, b, n, idx, rows, &state->flags)) return rc;
-  uint32_t tb;
-  memcpy(&tb, &threshold, sizeof(tb));
-  if (tb == 0x80000000u) tb = 0u;
-  const uint32_t T = (tb & 0x80000000u) ? ~tb : (tb | 0x80000000u);     // auc_key of the threshold (+-inf included)
+  const uint32_t T = auc_key_host(threshold);
   const auto [tile, nb] = rank_tiles(m, TP_BLOCKS, AUC_THREADS);
   k_tp_count<<<nb, AUC_THREADS, 0, st>>>(m, tile, nb, scores, ld_scores, labels, ld_labels, idx, T, cnt, state);
   rank_scan(st, cnt, nb + 1, off);

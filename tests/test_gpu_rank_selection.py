@@ -4,7 +4,7 @@ pinned across all of them at once, at n = 9 with an idx of 5 nodes.  Run with -m
 Two populations.  The ORDERED entries of auc.hip (roc_auc, rank_metrics, rank_curves, decode_auc, decode_rank_metrics) range
 over every ordered entry of the gathered submatrix: a repeated id is accepted and a permutation of all nodes is the whole
 matrix.  The PAIR entries (topk_metrics, top_pairs, node_rank_metrics, two_means_split, threshold_pairs, auc_delong,
-auc_delong_paired, auc_node_jackknife) range over the pairs of positions a > b of a repeat-free idx of at least two nodes,
+auc_delong_paired, auc_node_jackknife, graph_structure, hop_auc, class_auc) range over the pairs of positions a > b of a repeat-free idx of at least two nodes,
 and their answer depends on the order of idx.  (mcgra_decode_scores takes neither idx nor labels: nothing of this applies.)
 
 Every entry is called through its engine wrapper and reduced to plain Python values; the expected values are those of the
@@ -17,8 +17,11 @@ import numpy as np
 import pytest
 
 from tests import ap_truth as AP
+from tests import class_truth as CL
 from tests import curve_truth as CT
 from tests import delong_truth as DT
+from tests import graph_structure_truth as GS
+from tests import hop_truth as HT
 from tests import node_jackknife_truth as NJ
 from tests import node_rank_truth as NR
 from tests import topk_truth as TK
@@ -33,6 +36,8 @@ INSIDE = (5, 2)                             # positions a = 2 > b = 1 of IDX: an
 PERM = [4, 8, 1, 6, 0, 3, 7, 2, 5]          # all nodes in another order
 MODE = 0                                    # decode mode of the decode entries: sigmoid(relu(<z_i, z_j> - [i == j]))
 THR = 0.5
+HOPS = 2                                    # hop_auc: distances 1, 2 and beyond
+CLASSES = (np.arange(N) % 3).tolist()       # class_auc: three node classes, strata "same" (same class, different classes)
 AP_TOL = 34 * 2.0 ** -53                    # k_ap_terms: (T + 32) 2^-53 with T = 1 term per lane, + the truth's own rounding
 
 
@@ -151,6 +156,21 @@ def _got_node_rank(E, real, pred, idx):
     return np.stack([g[k].cpu().numpy() for k in ("positives", "wins", "ties", "hits", "first_rank")], 1).tolist()
 
 
+def _got_graph_structure(E, real, pred, idx):
+    g = E.graph_structure(pred, THR, idx, real)
+    return [g[k] for k in GS.HEADER], [g[k].tolist() for k in GS.COLUMNS]
+
+
+def _want_graph_structure(real, pred, idx):
+    w = GS.ints(real, pred, THR, idx)
+    return [w[k] for k in GS.HEADER], [w[k] for k in GS.COLUMNS]
+
+
+def _want_class_auc(real, pred, idx):
+    table, names = CL.strata(3, "same")
+    return CL.ints(real, pred, CLASSES, idx, table, len(names), THR)
+
+
 # name -> (population, reads a factor Z instead of a score matrix, got, want)
 ENTRIES = {
     "roc_auc": ("ordered", False, lambda E, r, p, i: E.roc_auc(r, p, i), lambda r, p, i: _auc_exact(*AP.level_counts(r, p, i))),
@@ -171,6 +191,11 @@ ENTRIES = {
                           lambda r, p, i: DT.paired_ints(r, p, PRED_B, i)),
     "auc_node_jackknife": ("pairs", False, lambda E, r, p, i: E.auc_node_jackknife(r, p, i)["ints"],
                            lambda r, p, i: NJ.ints(r, p, i)),
+    "graph_structure": ("pairs", False, _got_graph_structure, _want_graph_structure),
+    "hop_auc": ("pairs", False, lambda E, r, p, i: [list(c) for c in E.hop_auc(r, p, i, HOPS, THR)["ints"]],
+                lambda r, p, i: HT.ints(r, p, i, HOPS, THR)),
+    "class_auc": ("pairs", False, lambda E, r, p, i: [list(c) for c in E.class_auc(r, p, CLASSES, i, "same", THR)["ints"]],
+                  _want_class_auc),
 }
 ALL = sorted(ENTRIES)
 ORDERED = [e for e in ALL if ENTRIES[e][0] == "ordered"]
