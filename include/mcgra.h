@@ -265,6 +265,62 @@ int mcgra_decode_rank_metrics(void* stream, int n, int d, const float* Z, int ld
  * mcgra_dot_product_decode2, whose product runs on the MFMA GEMM.  Synchronises. */
 int mcgra_decode_scores(void* stream, int n, int d, const float* Z, int ldz, int mode, float* out, int ld_out);
 
+/* Link-stealing distance baselines: Attack-0 of He et al., "Stealing Links from Graph Neural Networks" (USENIX Security
+ * 2021) scores a node pair by a distance between the two nodes' rows of a thin matrix Z [n x d] (leading dimension
+ * ldz >= d; any d >= 1, the kernels stream it in chunks) -- posteriors, embeddings or features.  The metric ids, in the
+ * paper's order; mcgra_pair_metric_name(id) is the one table of their names (NULL outside 0 .. 7). */
+#define MCGRA_PAIR_COSINE 0
+#define MCGRA_PAIR_EUCLIDEAN 1
+#define MCGRA_PAIR_CORRELATION 2
+#define MCGRA_PAIR_CHEBYSHEV 3
+#define MCGRA_PAIR_BRAYCURTIS 4
+#define MCGRA_PAIR_CANBERRA 5
+#define MCGRA_PAIR_CITYBLOCK 6
+#define MCGRA_PAIR_SQEUCLIDEAN 7
+#define MCGRA_PAIR_METRICS 8
+const char* mcgra_pair_metric_name(int metric);
+/* The score of a pair is s_ij = 0.0f - dist(z_i, z_j): higher means more like an edge.  With a = z_ik, b = z_jk, every
+ * distance is accumulated k ascending in fp32, one defined operation chain per k (scipy.spatial.distance's definitions):
+ *     cityblock     sum |a - b|                               sqeuclidean   sum fma(a - b, a - b, .)
+ *     euclidean     sqrtf(sqeuclidean)                        chebyshev     max |a - b|
+ *     braycurtis    (sum |a - b|) / (sum |a + b|); a zero denominator gives 0
+ *     canberra      sum |a - b| / (|a| + |b|); a term whose denominator is zero is 0 (scipy's rule)
+ *     cosine        max(0, 1 - <zn_i, zn_j>), <., .> one fma per k, zn = z / max(|z|_2, 1e-12) computed once into an
+ *                   n x d scratch.  A zero row is therefore at distance 1 from every row, itself included (scipy: NaN)
+ *     correlation   cosine on the rows minus their own mean, mean = (sum of the row) / d.  A row whose entries are all
+ *                   equal is centred to exact zeros whatever its sum rounds to, so it is at distance 1 from every row
+ *                   (scipy: NaN), and d == 1 makes all pairs tie at distance 1.  The row sums are taken in a fixed order
+ *                   (entry l, l + 64, ... per lane, then a fixed tree over the 64 lanes): the same bits on every call
+ *   - |a - b|, |a + b|, |a| + |b|, (a - b)^2 and a b give the same bits with a and b swapped, so s_ij and s_ji are the same
+ *     bits; the diagonal is the pair (i, i)'s own score (0 for the six difference metrics, about 1e-7 at most for cosine
+ *     and correlation, whose rows are normalised in fp32);
+ *   - the library is built -O3 without fast-math; hipcc then gives IEEE division and square root
+ *     (-fhip-fp32-correctly-rounded-divide-sqrt is its default).  Nothing here relies on either being correctly
+ *     rounded: both are functions of their operands' bits alone, which is all the symmetry and the repeatability need;
+ *   - a NaN or +-inf anywhere in Z (any row), or for cosine / correlation a row whose sum of squares overflows
+ *     float32: MCGRA_EINVAL;
+ *   - metric outside 0 .. 7, n < 1, d < 1, Z NULL, ldz < d, out NULL or ld_out < n: MCGRA_EINVAL before any HIP call.
+ * mcgra_pair_distance_scores materialises out [n x n] (leading dimension ld_out >= n), bitwise symmetric; after a
+ * refusal nothing has been written.  Synchronises `stream`. */
+int mcgra_pair_distance_scores(void* stream, int n, int d, const float* Z, int ldz, int metric, float* out, int ld_out);
+/* The same scores, ranked without being stored.  The population is that of mcgra_auc_delong / mcgra_topk_metrics, NOT
+ * mcgra_roc_auc's ordered entries with the diagonal: idx, n_idx REPEAT-FREE device int64 node ids, or NULL for all n nodes;
+ * the candidates are the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b, score s of (idx[a], idx[b]), label
+ * labels[idx[a]][idx[b]] (labels n x n, ld_labels >= n).  n_idx from 2 to 65 535.
+ *   - counts (host int64[4]) = {m, P, N, T}, T twice the Mann-Whitney U as defined for mcgra_auc_delong: bit for bit
+ *     mcgra_auc_delong's integers on what mcgra_pair_distance_scores writes, and the same under any permutation of idx;
+ *   - *auc = the nearest double of T / (2 P N); *ap follows mcgra_rank_metrics' definition and fixed summation order on
+ *     these pairs.  auc, ap: host doubles; either may be NULL, not both.  P == 0 or N == 0: *auc = NaN (T = 0); P == 0:
+ *     *ap = NaN; N == 0: *ap = 1.0 exactly;
+ *   - before any HIP call: the argument errors above, ld_labels < n, labels NULL, n_idx < 2, auc and ap both NULL or counts
+ *     NULL: MCGRA_EINVAL; n_idx > 65 535: MCGRA_ENOSUP;
+ *   - the refusals of Z above; a selected score that overflows to a non-finite value, a selected label other than 0 or 1,
+ *     a repeated or out-of-range id: MCGRA_EINVAL.  After a refusal nothing has been written.
+ * Synchronises `stream`.  Device scratch: two 4-byte keys per selected pair, the normalised copy, about 3 MB. */
+int mcgra_pair_distance_rank_metrics(void* stream, int n, int d, const float* Z, int ldz, int metric, const float* labels,
+                                     int ld_labels, const int64_t* idx, int64_t n_idx, double* auc, double* ap,
+                                     int64_t* counts /* host[4]: m, P, N, T */);
+
 /* The recovered graph: the k best-scored node pairs of `scores` within idx, and how many of them are edges of `labels`.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL
  *     for all n nodes in order.  The candidates are the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b; pair

@@ -49,7 +49,11 @@ SYMBOLS = [
     "mcgra_graph_structure",
     "mcgra_hop_auc",
     "mcgra_class_auc",
+    "mcgra_pair_metric_name", "mcgra_pair_distance_scores", "mcgra_pair_distance_rank_metrics",
 ]
+
+# the metric ids MCGRA_PAIR_* of include/mcgra.h, in id order (mcgra_pair_metric_name is the library's copy)
+PAIR_METRICS = ("cosine", "euclidean", "correlation", "chebyshev", "braycurtis", "canberra", "cityblock", "sqeuclidean")
 
 
 class AttackConfig(C.Structure):
@@ -142,6 +146,9 @@ def _load():
         "mcgra_hop_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.c_float, C.POINTER(C.c_int64)],
         "mcgra_class_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, ip, C.c_int, C.POINTER(C.c_uint8), C.c_int,
                             C.c_float, C.POINTER(C.c_int64)],
+        "mcgra_pair_distance_scores": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int],
+        "mcgra_pair_distance_rank_metrics": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, ip, C.c_int64,
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],
@@ -177,6 +184,8 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
+    lib.mcgra_pair_metric_name.argtypes = [C.c_int]
+    lib.mcgra_pair_metric_name.restype = C.c_char_p
     lib.mcgra_attack_fused_steps.argtypes = [vp]
     lib.mcgra_attack_fused_steps.restype = C.c_longlong
     lib.mcgra_attack_masked_fused_steps.argtypes = [vp]

@@ -49,11 +49,11 @@
 #include "common.h"
 #include "rank_common.h"      // the keys, the checks, the block sums, the bound and the radix sort
 #include "curves.h"           // the third consumer of the sorted regions (curves.hip: mcgra_rank_curves)
+#include "auc_run.h"          // AucRun and the bodies of the classify and emit passes (shared with pair_distance.hip)
 
 namespace mcgra {
 
 namespace {
-constexpr int AUC_ROW_BLOCKS = 1024;       // blocks of the two passes over the matrix (grid-stride over selected rows)
 constexpr int AP_BLOCKS = 4096;            // at most this many blocks (and float64 partials) of k_ap_terms
 static_assert(AUC_THREADS == 256, "block_sum_f64 adds four waves as (w0 + w1) + (w2 + w3)");
 
@@ -105,41 +105,6 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// one selected entry of the classify pass: the argument checks and the counts of positives and of all entries
-__device__ __forceinline__ void auc_classify_one(float s, float l, uint32_t& pos, uint32_t& tot, int& f) {
-  if (!auc_finite(s)) f |= AUC_BAD_SCORE;
-  if (auc_pos(l)) ++pos;
-  else if (!auc_neg(l)) f |= AUC_BAD_LABEL;   // also NaN
-  ++tot;
-}
-// what the classify pass leaves: counts[2 b] / counts[2 b + 1] = positives / negatives of block b, flags |= f
-__device__ __forceinline__ void auc_classify_end(uint32_t pos, uint32_t tot, int f, uint64_t* sh, uint64_t* __restrict__ counts,
-                                                 int* __restrict__ flags) {
-  if (f) atomicOr(flags, f);
-  const uint64_t p = block_sum_u64(pos, sh);
-  __syncthreads();
-  const uint64_t t = block_sum_u64(tot, sh);
-  if (threadIdx.x == 0) { counts[2 * blockIdx.x] = p; counts[2 * blockIdx.x + 1] = t - p; }
-}
-// one selected entry of the emit pass: its key behind the block's positives (cur[0]) or negatives (cur[1]) so far.  Not two
-// calls of wave_slot: every lane takes a slot here, and one leader that advances both cursors in one go keeps the two LDS
-// round trips of a step overlapped, as they were.
-__device__ __forceinline__ void auc_emit_one(float s, float l, uint64_t o_pos, uint64_t o_neg, uint32_t* cur,
-                                             uint32_t* __restrict__ keys) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t below = (1ull << lane) - 1ull;
-  const bool p = auc_pos(l);
-  const uint64_t act = __ballot(1), mp = __ballot(p);
-  const int leader = __ffsll((unsigned long long)act) - 1;
-  uint32_t bp = 0, bn = 0;
-  if (lane == leader) {
-    bp = atomicAdd(&cur[0], (uint32_t)__popcll(mp));
-    bn = atomicAdd(&cur[1], (uint32_t)__popcll(act & ~mp));
-  }
-  bp = __shfl(bp, leader, 64);
-  bn = __shfl(bn, leader, 64);
-  keys[p ? o_pos + bp + __popcll(mp & below) : o_neg + bn + __popcll(act & ~mp & below)] = auc_key(s);
-}
 }  // namespace
 
 // counts[2 b] / counts[2 b + 1] = positives / negatives block b selects; flags |= the argument errors it meets
@@ -356,95 +321,82 @@ double auc_divide(uint64_t num, uint64_t den) {
   return ldexp((double)q, 1 - sh);
 }
 
-// What mcgra_roc_auc / mcgra_rank_metrics and mcgra_decode_auc / mcgra_decode_rank_metrics share around their two passes
-// over the selected pairs.
-struct AucRun {
-  const char* who;
-  hipStream_t st;
-  AucBufs b;
-  int* flags = nullptr;
-  uint64_t* counts = nullptr;
-  unsigned long long* acc = nullptr;
-  int h_flags = 0;
-
-  int begin() {
-    flags = b.get<int>(1);
-    counts = b.get<uint64_t>(2 * AUC_ROW_BLOCKS);
-    acc = b.get<unsigned long long>(1);
-    if (!flags || !counts || !acc) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
-    MCGRA_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long), st));
-    return 0;
-  }
-  // idx != NULL: range check and repeats; a permutation of all nodes becomes idx = NULL (the same multiset)
-  int select(int n, const int64_t*& idx, int64_t n_idx) {
-    bool repeated = false;
-    if (int rc = rank_check_idx(who, st, b, n, idx, n_idx, flags, true, &repeated)) return rc;
-    if (!repeated && n_idx == n) idx = nullptr;
-    return 0;
-  }
-  // Behind the classify pass of g blocks: its counts and flags, the per-block offsets, the emit pass (emit(offs, keys)
-  // launches it), the two sorts, then what was asked for: auc != NULL the pair count and the division, ap != NULL the
-  // average-precision terms and their sum (both read the same sorted regions); cv != NULL (then auc == ap == NULL) the
-  // curves of curves.hip, which also take a single-class selection.
-  template <class Emit>
-  int finish(int g, Emit&& emit, double* auc, double* ap, const CurveRequest* cv = nullptr) {
-    std::vector<uint64_t> h(2 * (size_t)g);
-    MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (int rc = rank_flag_error(who, h_flags)) return rc;     // (sklearn raises ValueError for each of them)
-    uint64_t P = 0, N = 0;
-    for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
-    if ((P == 0 || N == 0) && !cv) {
-      if (auc) *auc = NAN;                              // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
-      if (ap) *ap = P == 0 ? NAN : 1.0;                 // a mean over no positives; no negatives: every term is TP / TP
-      return 0;
-    }
-    // positives at [0, P), negatives at [nbase, nbase + N): each region starts on a 16-byte boundary
-    const uint64_t nbase = (P + 3) / 4 * 4;
-    for (uint64_t op = 0, on = nbase, i = 0; i < (uint64_t)g; ++i) {
-      const uint64_t p = h[2 * i], q = h[2 * i + 1];
-      h[2 * i] = op; h[2 * i + 1] = on;
-      op += p; on += q;
-    }
-    uint32_t* keys = b.get<uint32_t>(nbase + N);
-    uint32_t* tmp = b.get<uint32_t>(nbase + N);
-    const SortScratch ss(b);
-    double* part = ap ? b.get<double>(AP_BLOCKS + 1) : nullptr;      // the per-block partials, then the result
-    if (!keys || !tmp || !ss.cnt || (ap && !part)) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
-    MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
-    emit(counts, keys);
-    MCGRA_KERNEL_CHECK();
-    if (int rc = auc_sort(st, keys, tmp, P, ss)) return rc;
-    if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, ss)) return rc;
-    if (cv) return rank_curves_sorted(who, st, keys, tmp, P, nbase, N, *cv);
-    unsigned long long u2 = 0;
-    if (auc) {
-      const bool a_pos = P <= N;                      // look the smaller class up in the larger one
-      const uint32_t* A = a_pos ? keys : keys + nbase;
-      const uint32_t* B = a_pos ? keys + nbase : keys;
-      const uint64_t na = a_pos ? P : N, nbk = a_pos ? N : P;
-      const int gp = (int)std::min<uint64_t>(4096, (na + AUC_THREADS - 1) / AUC_THREADS);
-      k_auc_pairs<<<gp, AUC_THREADS, 0, st>>>(A, na, B, nbk, a_pos ? 1 : 0, acc);
-      MCGRA_KERNEL_CHECK();
-      MCGRA_HIP(hipMemcpyAsync(&u2, acc, sizeof(u2), hipMemcpyDeviceToHost, st));
-    }
-    double h_ap = 0.0;
-    if (ap) {
-      const int ga = (int)std::min<uint64_t>(AP_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
-      k_ap_terms<<<ga, AUC_THREADS, 0, st>>>(keys, P, keys + nbase, N, part);
-      k_ap_sum<<<1, AUC_THREADS, 0, st>>>(part, ga, P, part + AP_BLOCKS);
-      MCGRA_KERNEL_CHECK();
-      MCGRA_HIP(hipMemcpyAsync(&h_ap, part + AP_BLOCKS, sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    MCGRA_HIP(hipStreamSynchronize(st));
-    if (auc) *auc = auc_divide((uint64_t)u2, 2 * P * N);
-    if (ap) *ap = h_ap;
-    return 0;
-  }
-};
 }  // namespace
+
+// AucRun (auc_run.h): what mcgra_roc_auc / mcgra_rank_metrics, mcgra_decode_auc / mcgra_decode_rank_metrics and
+// mcgra_pair_distance_rank_metrics share around their two passes over the selected pairs.
+int AucRun::begin() {
+  flags = b.get<int>(1);
+  counts = b.get<uint64_t>(2 * AUC_ROW_BLOCKS);
+  acc = b.get<unsigned long long>(1);
+  if (!flags || !counts || !acc) { set_error("%s: hipMalloc failed", who); return MCGRA_ENOMEM; }
+  MCGRA_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
+  MCGRA_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long), st));
+  return 0;
+}
+int AucRun::select(int n, const int64_t*& idx, int64_t n_idx) {
+  bool repeated = false;
+  if (int rc = rank_check_idx(who, st, b, n, idx, n_idx, flags, true, &repeated)) return rc;
+  if (!repeated && n_idx == n) idx = nullptr;
+  return 0;
+}
+int AucRun::finish(int g, const AucEmit& emit, double* auc, double* ap, const CurveRequest* cv, uint64_t* pnt) {
+  std::vector<uint64_t> h(2 * (size_t)g);
+  MCGRA_HIP(hipMemcpyAsync(h.data(), counts, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+  MCGRA_HIP(hipStreamSynchronize(st));
+  if (int rc = rank_flag_error(who, h_flags)) return rc;     // (sklearn raises ValueError for each of them)
+  uint64_t P = 0, N = 0;
+  for (int i = 0; i < g; ++i) { P += h[2 * i]; N += h[2 * i + 1]; }
+  if ((P == 0 || N == 0) && !cv) {
+    if (auc) *auc = NAN;                              // roc_curve: tpr or fpr is 0 / 0 (sklearn warns), auc is NaN
+    if (ap) *ap = P == 0 ? NAN : 1.0;                 // a mean over no positives; no negatives: every term is TP / TP
+    if (pnt) { pnt[0] = P; pnt[1] = N; pnt[2] = 0; }
+    return 0;
+  }
+  // positives at [0, P), negatives at [nbase, nbase + N): each region starts on a 16-byte boundary
+  const uint64_t nbase = (P + 3) / 4 * 4;
+  for (uint64_t op = 0, on = nbase, i = 0; i < (uint64_t)g; ++i) {
+    const uint64_t p = h[2 * i], q = h[2 * i + 1];
+    h[2 * i] = op; h[2 * i + 1] = on;
+    op += p; on += q;
+  }
+  uint32_t* keys = b.get<uint32_t>(nbase + N);
+  uint32_t* tmp = b.get<uint32_t>(nbase + N);
+  const SortScratch ss(b);
+  double* part = ap ? b.get<double>(AP_BLOCKS + 1) : nullptr;      // the per-block partials, then the result
+  if (!keys || !tmp || !ss.cnt || (ap && !part)) { set_error("%s: hipMalloc of 2 x %llu keys failed", who, (unsigned long long)(nbase + N)); return MCGRA_ENOMEM; }
+  MCGRA_HIP(hipMemcpyAsync(counts, h.data(), sizeof(uint64_t) * h.size(), hipMemcpyHostToDevice, st));
+  emit(counts, keys);
+  MCGRA_KERNEL_CHECK();
+  if (int rc = auc_sort(st, keys, tmp, P, ss)) return rc;
+  if (int rc = auc_sort(st, keys + nbase, tmp + nbase, N, ss)) return rc;
+  if (cv) return rank_curves_sorted(who, st, keys, tmp, P, nbase, N, *cv);
+  unsigned long long u2 = 0;
+  if (auc) {
+    const bool a_pos = P <= N;                      // look the smaller class up in the larger one
+    const uint32_t* A = a_pos ? keys : keys + nbase;
+    const uint32_t* B = a_pos ? keys + nbase : keys;
+    const uint64_t na = a_pos ? P : N, nbk = a_pos ? N : P;
+    const int gp = (int)std::min<uint64_t>(4096, (na + AUC_THREADS - 1) / AUC_THREADS);
+    k_auc_pairs<<<gp, AUC_THREADS, 0, st>>>(A, na, B, nbk, a_pos ? 1 : 0, acc);
+    MCGRA_KERNEL_CHECK();
+    MCGRA_HIP(hipMemcpyAsync(&u2, acc, sizeof(u2), hipMemcpyDeviceToHost, st));
+  }
+  double h_ap = 0.0;
+  if (ap) {
+    const int ga = (int)std::min<uint64_t>(AP_BLOCKS, (P + AUC_THREADS - 1) / AUC_THREADS);
+    k_ap_terms<<<ga, AUC_THREADS, 0, st>>>(keys, P, keys + nbase, N, part);
+    k_ap_sum<<<1, AUC_THREADS, 0, st>>>(part, ga, P, part + AP_BLOCKS);
+    MCGRA_KERNEL_CHECK();
+    MCGRA_HIP(hipMemcpyAsync(&h_ap, part + AP_BLOCKS, sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  MCGRA_HIP(hipStreamSynchronize(st));
+  if (auc) *auc = auc_divide((uint64_t)u2, 2 * P * N);
+  if (ap) *ap = h_ap;
+  if (pnt) { pnt[0] = P; pnt[1] = N; pnt[2] = (uint64_t)u2; }
+  return 0;
+}
 
 }  // namespace mcgra
 

@@ -1200,6 +1200,55 @@ def decode_scores(Z, mode):
     return out
 
 
+PAIR_METRICS = _lib.PAIR_METRICS      # the link-stealing distances, in the id order of MCGRA_PAIR_* (include/mcgra.h)
+
+
+def pair_metric_id(metric):
+    """A link-stealing metric given by name (PAIR_METRICS) or by id as its id; ValueError for anything else."""
+    if isinstance(metric, str):
+        if metric in PAIR_METRICS:
+            return PAIR_METRICS.index(metric)
+    elif isinstance(metric, (int, np.integer)) and not isinstance(metric, bool) and 0 <= int(metric) < len(PAIR_METRICS):
+        return int(metric)
+    raise ValueError(f"pair distance metric {metric!r}: one of {', '.join(PAIR_METRICS)} (or its id 0 .. {len(PAIR_METRICS) - 1})")
+
+
+@_on_operand_device
+def pair_distance_scores(Z, metric):
+    """The link-stealing baseline's scores, materialised (mcgra_pair_distance_scores): out[i, j] = 0.0 - dist(Z[i], Z[j])
+    for one of the eight metrics of PAIR_METRICS (He et al., USENIX Security 2021, Attack-0), higher = more like an edge.
+    Z: n x d on the device, any d.  Each distance is one fp32 chain over k ascending, so the matrix is bitwise symmetric and the
+    same bits on every call.  McgraError for a NaN / inf in Z."""
+    m = pair_metric_id(metric)
+    Z = _rows_f32(Z, Z.device)
+    n, d = Z.shape
+    out = torch.empty(n, n, device=Z.device, dtype=torch.float32)
+    check(lib.mcgra_pair_distance_scores(_stream(), n, d, _p(Z), Z.stride(0), m, _p(out), n))
+    return out
+
+
+@_on_operand_device
+def pair_distance_rank_metrics(real, Z, metric, idx=None):
+    """How well a distance between two nodes' rows of Z tells the edges of `real` from the non-edges, without the n x n score
+    matrix (mcgra_pair_distance_rank_metrics).  The population is auc_delong's: the m unordered pairs of positions a > b of a
+    REPEAT-FREE idx (None: all nodes), label real[idx[a], idx[b]].  Returns {"pairs" (m), "positives" (P), "negatives" (N),
+    "T" (twice the Mann-Whitney U), "auc" T / (2 P N), "ap"}: the integers and "auc" are bit for bit
+    auc_delong(real, pair_distance_scores(Z, metric), idx)'s, "ap" is sklearn's average_precision_score on those pairs.  P or
+    N == 0: "auc" NaN; P == 0: "ap" NaN; N == 0: "ap" 1.0.  McgraError for a NaN / inf in Z, a selected score that overflows,
+    a selected label other than 0 / 1, a repeated or out-of-range id."""
+    m = pair_metric_id(metric)
+    real, Z, ix, n, rows = _ranked(idx, real, factor=Z)
+    auc, ap = C.c_double(), C.c_double()
+    counts = (C.c_int64 * 4)()
+    check(lib.mcgra_pair_distance_rank_metrics(_stream(), n, Z.shape[1], _p(Z), Z.stride(0), m, _p(real), real.stride(0), _p(ix),
+                                               rows, C.byref(auc), C.byref(ap), counts))
+    pairs, P, N, T = (int(v) for v in counts)
+    if P and N:      # the device's one rounding is the exact rational's
+        exact = float(Fraction(T, 2 * P * N))
+        assert exact == auc.value, (exact, auc.value)
+    return {"pairs": pairs, "positives": P, "negatives": N, "T": T, "auc": auc.value, "ap": ap.value}
+
+
 @_device_operands
 def gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=0):
     """GCN.forward (eval) and, when emb_nlayer > 0, embedding_GCN.forward."""

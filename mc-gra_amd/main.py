@@ -46,6 +46,14 @@ the share of same-class pairs among the true edges, the recovered pairs and all 
 min(15, bit_length) of a node's degree in the true graph, or an integer .npy with one class in [0, 16) per node.
 --by_class_cut split|edges|THRESHOLD (default edges; --structure's cuts) says where the recovered pairs are counted.
 --save_by_class PATH: the counts, the sums and the AUC of every block, and the class of every node.
+--mode link_stealing (not in the reference) is the baseline every paper in this line compares with, Attack-0 of He et al.,
+"Stealing Links from Graph Neural Networks" (USENIX Security 2021): notrain_test's flow up to the priors -- no attack, nothing
+written -- then the AUC (with --ap the average precision too) of the unordered node pairs of attack, train and all scored by
+minus a distance between the two nodes' rows of `posteriors` (exp(Y_A)), `embedding` (H_A2) or `features`, for each of cosine,
+euclidean, correlation, chebyshev, braycurtis, canberra, cityblock and sqeuclidean (engine.pair_distance_rank_metrics: pair by
+pair on the GPU, no n x n score matrix); one `link stealing <source> <metric>: auc_attack=... auc_train=... auc_all=...` line each.
+--versus SOURCE:METRIC (--mode evaluate, with --ci or --ci_nodes) takes one of those 24 scorings as the other side of the paired
+tests (engine.pair_distance_scores): does the attack beat this baseline on these pairs, with delta, se_delta, z and p_value.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -112,7 +120,7 @@ def build_parser():
     p.add_argument('--iter', type=int, default=1)
     p.add_argument('--max_eval', type=int, default=100)
     p.add_argument('--log_name', type=str, default="result.txt")
-    p.add_argument("--mode", type=str, default="evaluate", choices=["evaluate", "prepare", "notrain_test"])
+    p.add_argument("--mode", type=str, default="evaluate", choices=["evaluate", "prepare", "notrain_test", "link_stealing"])
     p.add_argument("--measure", type=str, default="HSIC", choices=["HSIC", "MSELoss", "KL", "KDE", "CKA", "DP"])
     p.add_argument("--measure2", type=str, default="HSIC")
     p.add_argument("--nofeature", action='store_true')
@@ -139,7 +147,7 @@ def build_parser():
     p.add_argument('--save_graph', type=str, default=None)  # with --binarize: the whole graph's recovered edges as an .npz
     # absent from the namespace unless given: without them the parameter line of the log is what it was
     p.add_argument('--ci', action='store_true', default=argparse.SUPPRESS)      # also DeLong's se and interval of the AUC
-    p.add_argument('--versus', type=str, default=argparse.SUPPRESS)            # with --ci: paired test against `features` or an .npy
+    p.add_argument('--versus', type=str, default=argparse.SUPPRESS)            # with --ci: paired test against `features`, SOURCE:METRIC or an .npy
     p.add_argument('--save_scores', type=str, default=argparse.SUPPRESS)       # write modified_adj as an .npy for a later --versus
     p.add_argument('--ci_nodes', action='store_true', default=argparse.SUPPRESS)   # also the node-jackknife se and interval of the AUC
     p.add_argument('--save_influence', type=str, default=argparse.SUPPRESS)    # with --ci_nodes: each node's influence as an .npz
@@ -221,6 +229,42 @@ def prior_rank_metrics(adj, feature_adj, H_A1, H_A2, Y_A, label_adj, dataset):
     both = {"feature": matrix(feature_adj), "layer1": thin(H_A1), "layer2": thin(H_A2), "out": thin(Y_A),
             "label": matrix(label_adj)}
     return {k: float(v[0]) for k, v in both.items()}, {k: float(v[1]) for k, v in both.items()}
+
+
+def link_sources(Y_A, H_A2, features, device):
+    """What a link-stealing distance is taken between (reports.LINK_SOURCES), each n x d float32 on the device: the victim's
+    posteriors exp(Y_A) (Y_A is the log-softmax the attack itself is given), the embedding H_A2, the preprocessed features."""
+    feats = features.to_dense() if features.is_sparse else features
+    return {"posteriors": torch.exp(Y_A.detach().to(device=device, dtype=torch.float32)),
+            "embedding": H_A2.detach().to(device=device, dtype=torch.float32),
+            "features": feats.detach().to(device=device, dtype=torch.float32)}
+
+
+def link_stealing_metrics(real, sources, sets, want_ap):
+    """--mode link_stealing: Attack-0 of He et al. (USENIX Security 2021) on this run's victim.  For every source, each of
+    engine.PAIR_METRICS and every index set, the AUC (with want_ap the average precision too) of the unordered node pairs
+    scored by minus the distance of their two rows (engine.pair_distance_rank_metrics: no n x n score matrix).
+    out[source][metric][set] = {"auc", "pairs", "positives"} (+ "ap")."""
+    keep = ("auc", "pairs", "positives") + (("ap",) if want_ap else ())
+    out = {}
+    for source, Z in sources.items():
+        out[source] = {}
+        for metric in engine.PAIR_METRICS:
+            per_set = {name: engine.pair_distance_rank_metrics(real, Z, metric, ix) for name, ix in sets.items()}
+            out[source][metric] = {name: {k: d[k] for k in keep} for name, d in per_set.items()}
+    return out
+
+
+def link_stealing_lines(res, want_ap):
+    """One line per source and metric of link_stealing_metrics' result."""
+    lines = []
+    for source, by_metric in res.items():
+        for metric, by_set in by_metric.items():
+            line = f"link stealing {source} {metric}: " + " ".join(f"auc_{name}={d['auc']}" for name, d in by_set.items())
+            if want_ap:
+                line += " " + " ".join(f"ap_{name}={d['ap']}" for name, d in by_set.items())
+            lines.append(line)
+    return lines
 
 
 def victim_tensors(m):
@@ -397,10 +441,21 @@ def _run(args, rank, world):
                 for k in ("feature", "layer1", "layer2", "out", "label"):
                     print(f"{k} ap=", res["ap"][k])
         return res
+    if args.mode == "link_stealing":                                                       # no attack either
+        want_ap = getattr(args, "ap", False)
+        sets = {"attack": idx_attack, "train": idx_train, "all": None}
+        res = {"link_stealing": link_stealing_metrics(ad, link_sources(Y_A, H_A2, features, device), sets, want_ap)}
+        if rank == 0:
+            print("\n".join(link_stealing_lines(res["link_stealing"], want_ap)))
+        return res
     versus = getattr(args, "versus", None)
     other = None
     if versus is not None:  # refused before the attack runs, not after it
-        other = feature_adj if versus == "features" else reports.load_versus(versus, adj.shape[0])
+        baseline = reports.versus_baseline(versus, _exit)
+        if baseline is not None:
+            other = engine.pair_distance_scores(link_sources(Y_A, H_A2, features, device)[baseline[0]], baseline[1])
+        else:
+            other = feature_adj if versus == "features" else reports.load_versus(versus, adj.shape[0])
     by_class = getattr(args, "by_class", None)
     classes = None if by_class is None else reports.node_classes(by_class, labels, adj)    # refused before the attack runs too
     lr = 10 ** args.lr                                                                     # objective(): main.py:282-283

@@ -168,12 +168,31 @@ def _per_node_log(res, ctx):
             f"Hits@1={d['hits_at_1']} R-precision={d['r_precision']}" for title, d in _per_set(res, "per_node")]
 
 
+LINK_SOURCES = ("posteriors", "embedding", "features")      # what a link-stealing distance is taken between (main.py)
+
+
+def versus_baseline(versus, fail):
+    """--versus SOURCE:METRIC, a link-stealing baseline of the run itself, as (source, metric); None for any other value
+    (`features`, or a path).  A value is read as the shortcut when its SOURCE is one of LINK_SOURCES or its METRIC one of
+    engine.PAIR_METRICS; the other half is then refused by name when it is not one too."""
+    source, sep, metric = (versus or "").partition(":")
+    if not sep or (source not in LINK_SOURCES and metric not in engine.PAIR_METRICS):
+        return None
+    if source not in LINK_SOURCES:
+        fail(f"--versus {versus}: source `{source}` is not one of {', '.join(LINK_SOURCES)}")
+    if metric not in engine.PAIR_METRICS:
+        fail(f"--versus {versus}: metric `{metric}` is not one of {', '.join(engine.PAIR_METRICS)}")
+    return source, metric
+
+
 def check_ci_args(args, fail):
     ci, versus, scores = getattr(args, "ci", False), getattr(args, "versus", None), getattr(args, "save_scores", None)
     if versus is not None and not ci and not getattr(args, "ci_nodes", False):
         fail("--versus needs --ci or --ci_nodes")
     if versus is not None and versus == "":
         fail("--versus takes `features` or the path of an .npy score matrix")
+    if versus is not None:
+        versus_baseline(versus, fail)
     if ci and args.mode != "evaluate":
         fail(f"--ci puts an interval on the AUC of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
     if scores is not None and args.mode != "evaluate":
