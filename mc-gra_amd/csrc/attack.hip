@@ -1212,11 +1212,7 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
   }
   // Adam's scalars first: the fused tail below consumes them
   h->t += 1;
-  const double b1 = 0.9, b2 = 0.999;
-  const double bc1 = 1.0 - pow(b1, (double)h->t), bc2 = 1.0 - pow(b2, (double)h->t);
   hipLaunchKernelGGL(k_cn, dim3(1), dim3(1), 0, st, h->scal, (float)(c.weight_sup * 0.001), h->mm + 2);
-  // clamp(a,0,1).sum() <= n(n-1)/2, so a larger budget can never trigger the bisection (:339)
-  const bool may_project = c.num_edges < 0.5 * s.n2;
   bool adam_done = false;
   // normalisation backward writes G_A (beta = 0), then the chain's outer products accumulate
   if (h->p.fuse_tail && rankk_apply_adam_supported(n, ld, hs) && !h->has_ori) {
@@ -1224,11 +1220,8 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
     launch_normbwd(st, n, ld, h->G_ADJN, s.A, h->r, h->d, h->rowpart, nb_colpart, nb_strips, h->gd, nullptr, normbwd_parts);
     // (its row sums of the new M go to G_A, which this path leaves unused; not with a projection still to come)
     const size_t cnt = (size_t)n * rankk_apply_adam_tiles(n);
-    const bool emit = !s.gen && adam_emits_partials(h, may_project, cnt);
-    MCGRA_HIP(rankk_apply_adam(st, n, ld, hs, h->GPu, hs, h->Tu, hs, h->G_ADJN, h->r, h->gd, s.gate, h->M, h->am, h->av, h->mm + 2,
-                               (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
-                               h->p.keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
-                               emit ? adam_row_sums(h, cnt) : nullptr));
+    const bool emit = !s.gen && adam_emits_partials(h, cnt);
+    MCGRA_HIP(rankk_apply_adam(st, n, ld, hs, h->GPu, hs, h->Tu, hs, h->G_ADJN, h->r, h->gd, s.gate, adam_update(h, h->t, emit ? cnt : 0)));
     h->carry.prep_valid = emit;
     adam_done = true;
   } else if (rankk_nt_supported(n, n, hs, 0) && !h->has_ori) {
@@ -1246,13 +1239,11 @@ static int step_tail(GeneralStep& s, double* scalars_out) {
   // ---- packed-gradient mirror + Adam + projection + clamp (:274-283)
   if (!adam_done) {
     h->carry.prep_valid = false;
-    launch_adam_sym(st, n, ld, h->G_A, s.gate, h->M, h->am, h->av, h->mm + 2, (float)(1.0 - b1), (float)b2,
-                    (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f, h->p.keep_gsym ? h->GSYM : nullptr,
-                    may_project ? 0 : 1);
+    launch_adam_sym(st, n, ld, h->G_A, s.gate, adam_update(h, h->t));
   }
   MCGRA_KERNEL_CHECK();
   h->have_step = true;
-  if (may_project) { CHK(project(h, st)); h->carry.prep_valid = false; }
+  if (may_project(h)) { CHK(project(h, st)); h->carry.prep_valid = false; }
 
   if (scalars_out) CHK(collect_scalars(h, st, scalars_out));
   return 0;

@@ -303,14 +303,12 @@ int fused_forward(mcgra_attack* h, hipStream_t st) {      // monolithic engines 
 
 // host-side bookkeeping of a fused step that went through (the Adam pass is enqueued)
 static void fused_commit(mcgra_attack* h) {
-  const int n = h->p.n;
   h->step.planes_valid = false;          // the Adam pass is enqueued: Bpack no longer describes M
-  const bool may_project = h->cfg.num_edges < 0.5 * (double)n * (double)n;
   h->step.lr_step = !h->p.elementwise();
   if (!h->p.elementwise()) ++h->lr_steps;      // (the fused MSELoss step has no low-rank form: it counts as a fused step only)
   ++h->fused_steps;
   h->t += 1;
-  h->carry.prep_valid = adam_emits_partials(h, may_project, (size_t)n * fl_tail_tiles(n));
+  h->carry.prep_valid = adam_emits_partials(h, (size_t)h->p.n * fl_tail_tiles(h->p.n));
   h->have_step = true;
   h->carry.fused_last = true;
 }
@@ -352,28 +350,33 @@ static double* tail_vpart(const mcgra_attack* h) {
 // k_tail_reduce of the step over rows [R0, R1) (phase 1: only its rank-k panels are packed -- their inputs are ready before
 // the N x N x N product is joined; 2: the pass itself).  Returns the number of blocks (partials of the loss-term values).
 static int tail_reduce_call(const FusedStep& s, int phase, int R0, int R1, bool want_vals) {
-  mcgra_attack* h = s.h; hipStream_t st = s.st;
-  const int n = s.n, hs = s.hs, he = s.he;
-  const bool pair = s.pair, use1 = s.use1, use2 = s.use2;
-  const float a1 = s.a1, a2 = s.a2, kie6 = (float)(s.k6 / s.n2), kmse1 = s.kmse1, kmse2 = s.kmse2;
-  float* ps1 = tail_ps(h);                                       // [n][nt]
-  double* vpart = tail_vpart(h);
-  const float* Ls[2] = {h->GPv, h->lrL};
-  const float* Rs[2] = {h->Tv, h->lrR};
-  const int ll[2] = {hs, 2 * he}, lr_[2] = {hs, 2 * he}, Ks[2] = {hs, 2 * he};
+  mcgra_attack* h = s.h;
+  const int hs = s.hs, he = s.he;
   const bool no_rk = h->test_mutate == 2;      // (TEST-ONLY mutation, see the join below)
-  const float al[2] = {no_rk ? 0.f : 1.f, no_rk ? 0.f : a2};
-  if (h->p.kl())       // calc = calc_kl: softmax(feature_adj) in the place of P1, the row statistics lA / l1 / v as the n-vectors
-    return fl_tail_reduce(st, n, h->p.ld, pair, R0, R1, 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M, h->XC, h->r,
-                          h->klA, h->kl1, h->klv, 0.f, 0.f, kie6, h->G_ADJN, ps1, want_vals ? vpart : nullptr, h->rkbuf, phase, h->Zn,
-                          h->p.hmax, he, kmse1, kmse2, true);
-  if (h->p.elementwise())      // calc = MSELoss: feature_adj in the place of P1, S = Zn Zn^T as a third rank-k group
-    return fl_tail_reduce(st, n, h->p.ld, pair, R0, R1, 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M, h->FADJ, h->r,
-                          h->cmean, nullptr, nullptr, 0.f, 0.f, kie6, h->G_ADJN, ps1, want_vals ? vpart : nullptr, h->rkbuf, phase, h->Zn,
-                          h->p.hmax, he, kmse1, kmse2);
-  return fl_tail_reduce(st, n, h->p.ld, pair, R0, R1, use2 ? 2 : 1, Ls, ll, Rs, lr_, Ks, al, h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, h->M,
-                        use1 ? h->KX : nullptr, h->r, h->cmean, use2 ? h->lrDelta : nullptr, use2 ? h->lrC : nullptr, a1, a2, kie6,
-                        h->G_ADJN, ps1, want_vals ? vpart : nullptr, h->rkbuf, phase);
+  TailOperands t{};
+  t.gs[0] = RankK{h->GPv, hs, h->Tv, hs, hs, no_rk ? 0.f : 1.f};
+  t.u = RankK{h->GPu, hs, h->Tu, hs, no_rk ? 0 : hs, 1.f};
+  t.M = h->M; t.r = h->r;
+  t.a1 = s.a1; t.a2 = s.a2; t.k1 = s.kmse1; t.k2 = s.kmse2; t.kie6 = (float)(s.k6 / s.n2);      // (a1, a2 | k1, k2: zero for the other kinds)
+  t.G2 = h->G_ADJN; t.ps = tail_ps(h); t.vpart = want_vals ? tail_vpart(h) : nullptr; t.rkbuf = h->rkbuf;
+  switch (s.kind) {
+    case FUSED_KL:      // calc = calc_kl
+      t.P = h->XC; t.rowa = h->klA; t.rowb = h->kl1; t.rowc = h->klv;
+      t.Zn = h->Zn; t.ldz = h->p.hmax; t.hz = he;
+      break;
+    case FUSED_MSE:     // calc = MSELoss
+      t.P = h->FADJ; t.rowa = h->cmean;
+      t.Zn = h->Zn; t.ldz = h->p.hmax; t.hz = he;
+      break;
+    default:            // linear_HSIC in its low-rank form
+      if (s.use1) t.P = h->KX;
+      t.rowa = h->cmean;
+      if (s.use2) {
+        t.gs[1] = RankK{h->lrL, 2 * he, h->lrR, 2 * he, 2 * he, no_rk ? 0.f : s.a2};
+        t.rowb = h->lrDelta; t.rowc = h->lrC;
+      }
+  }
+  return fl_tail_reduce(s.st, s.kind, s.n, h->p.ld, s.pair, R0, R1, t, phase);
 }
 
 // The N x N x N product P1 = KFC Xc^T[:, own rows] (c1) on the side stream -- forked here: the caller's stream is recorded, the side
@@ -501,7 +504,7 @@ static int fs_forward(FusedStep& s) {
 static int fs_pack_fork(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, ld = s.ld, hs = s.hs, Le = s.Le, R0 = s.R0, R1 = s.R1, he = s.he, p_off = s.p_off, p_cnt = s.p_cnt;
-  const bool mse = s.mse, use1 = s.use1, use2 = s.use2, want_vals = s.want_vals;
+  const bool mse = s.elementwise(), use1 = s.use1, use2 = s.use2, want_vals = s.want_vals;
   const int np = split3_pack_rsq_parts(n, h->p.split_planes);      // (the pack's per-block row partials: sums of squares in A1, pack_row_sums)
   bool behind_pack = false;      // (the product forked behind the early pack: fork_p1)
   // planes of Xc^T rows straight from M, |xc_i|^2 from the same pass
@@ -592,7 +595,7 @@ static int fs_decode_stats(FusedStep& s) {
     launch_row_normalize(st, n, he, s.em, hs, h->Zn, h->p.hmax, h->nrm, 2.f, h->Zpair, zero_inline ? &zf : nullptr);
     if (zero_inline) h->step.nmask_zero = true;
   }
-  if (s.kl) {
+  if (s.kl()) {
     // calc_kl's row statistics (logsumexp of adj_norm's and of modified_adj1's rows) from M, r and Zn: the decode backward and
     // the tail need those of EVERY row (d c2 / d A1_ij + d c2 / d A1_ji), so a row-block rank gathers its peers' first
     (void)fl_decode_stats(st, n, R0, R1, he, h->Zn, h->p.hmax, h->Zpair, h->M, ld, h->r, h->klpart, h->klA, h->kl1);
@@ -602,22 +605,24 @@ static int fs_decode_stats(FusedStep& s) {
     }
     if (h->p.sharded) rows_to_stage2(h, st, narrow_stage(h), 1, h->klA, 1, 0, 1, h->kl1, 1, 1);
   }
-  return s.kl ? xchg_sg(s) : GO;
+  return s.kl() ? xchg_sg(s) : GO;
 }
 // What both decodes share: the fork onto s4 (forked: s4 is the fourth stream), the masked-pair counter cleared, k_decode_fly
 // over the own rows with its row partials in rowvals (fs_np of them) ...
 static int decode_fly(const FusedStep& s, hipStream_t s4, bool forked, bool zero, float* slabs, double* rowvals, bool want_vals) {
   mcgra_attack* h = s.h;
-  const bool mse = s.mse, kl = s.kl;
   if (forked) {
     MCGRA_HIP(hipEventRecord(h->ev_fork4, s.st));
     MCGRA_HIP(hipStreamWaitEvent(s4, h->ev_fork4, 0));
   }
   if (zero) MCGRA_HIP(hipMemsetAsync(h->nmask, 0, 2 * sizeof(unsigned int), s4));
   h->step.nmask_zero = false;
-  h->step.fs_np = fl_decode_fly(s4, s.n, s.R0, s.R1, s.he, h->Zn, h->p.hmax, (float)(s.k7 / s.n2), slabs, rowvals, h->GZn, h->p.hmax, h->nmask, h->Zpair,
-                           want_vals, mse ? h->M : nullptr, s.ld, h->r, s.kmse2, kl ? h->klA : nullptr, kl ? h->kl1 : nullptr,
-                           kl ? h->klpart : nullptr);
+  DecodeOperands d{};
+  d.Z = h->Zn; d.ldz = h->p.hmax; d.zpair = h->Zpair; d.kie7 = (float)(s.k7 / s.n2);
+  d.slabs = slabs; d.v7part = rowvals; d.GZn = h->GZn; d.ldg = h->p.hmax; d.nmask = h->nmask;
+  if (s.elementwise()) { d.M = h->M; d.ldm = s.ld; d.r = h->r; d.k2 = s.kmse2; }
+  if (s.kl()) { d.lseA = h->klA; d.lse1 = h->kl1; d.vrow = h->klpart; }
+  h->step.fs_np = fl_decode_fly(s4, s.kind, s.n, s.R0, s.R1, s.he, d, want_vals);
   return 0;
 }
 // ... and its end on s4, behind whatever the variant put there: fs_dec_forked asks the first reader of its results to join
@@ -630,7 +635,7 @@ static int decode_end(const FusedStep& s, hipStream_t s4, bool forked) {
 static int decode_monolithic(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, R0 = s.R0, R1 = s.R1;
-  const bool mse = s.mse, kl = s.kl, use2 = s.use2, want_vals = s.want_vals;
+  const bool mse = s.elementwise(), kl = s.kl(), use2 = s.use2, want_vals = s.want_vals;
   // monolithic, small graphs (where the step is bound by its chain of dependent node-level kernels): the decode -- the
   // longest of them, and it needs only Zn -- on a fourth stream with its own slabs, beside the low-rank factor chain;
   // joined in front of the first consumer of G_Zn (n = 2708: 0.60 -> 0.54 ms per step).  At N = 10 000 the chain hides
@@ -658,7 +663,7 @@ static int decode_monolithic(FusedStep& s) {
 static int decode_rank(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, ld = s.ld, R0 = s.R0, R1 = s.R1, he = s.he;
-  const bool kl = s.kl, use2 = s.use2;
+  const bool kl = s.kl(), use2 = s.use2;
   // row-block rank: the decode of the own rows -- the longest node-level kernel of a rank's step, and at world 8 that
   // chain, not the product, is the rank's critical path -- on the fourth stream with its own slabs, beside the column
   // statistics, the factor prep and the first low-rank product; joined in front of the gather its results ride in
@@ -683,7 +688,7 @@ static int decode_rank(FusedStep& s) {
 }
 static int fs_decode(FusedStep& s) {
   mcgra_attack* h = s.h;
-  if (s.kl && h->p.sharded) stage_to_rows2(h, s.st, narrow_stage(h), 1, 0, h->klA, 1, 1, 1, h->kl1, 1);
+  if (s.kl() && h->p.sharded) stage_to_rows2(h, s.st, narrow_stage(h), 1, 0, h->klA, 1, 1, 1, h->kl1, 1);
   CHK(h->p.sharded ? decode_rank(s) : decode_monolithic(s));
   MCGRA_KERNEL_CHECK();
   return s.use2 ? GO : xchg_sg(s);
@@ -735,7 +740,7 @@ static int fs_small_terms(FusedStep& s) {
 static int fs_lr_t(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const int n = s.n, ld = s.ld, fc = s.fc, he = s.he;
-  const bool kl = s.kl, use2 = s.use2;
+  const bool kl = s.kl(), use2 = s.use2;
   if (h->p.sharded) {
     const Stage sg = use2 ? wide_stage(h) : narrow_stage(h);
     if (use2) stage_to_rows2(h, st, sg, he, 0, h->GZn, h->p.hmax, 2, he, reinterpret_cast<float*>(h->lrRs), 2);
@@ -900,12 +905,19 @@ static int fs_tail_front(FusedStep& s) {
   if (h->p.sharded) x_alltoall(s.ex, h->off_a2s, h->off_a2r, (int64_t)h->p.rpr * h->p.rpr * 4);
   return AT_XCHG;
 }
+// The values of the loss terms that the tail's first pass sums, by FusedKind: `count` groups of partials in vpart, the slots of
+// scal they belong to, and where a row-block rank's sums over the ranks stand in SC (sc0 ...: fs_decide puts them there).
+//   HSIC: sum P1 o Xc | the entropy term of adj_norm;  MSELoss: sum (F - adj_norm)^2 | entropy | sum (adj_norm - A1)^2
+//   (k_loss_elem's slots);  KL: calc_kl(feature_adj, adj_norm) (k_kl_rows' slot) | entropy -- c2's value came out of the decode
+struct TailVals { int count, slot[3], sc0; };
+static const TailVals TAIL_VALS[] = {{0, {0, 0, 0}, 0}, {2, {S_H1, S_V6, 0}, 4}, {3, {S_V1, S_V6, S_V2}, 12}, {2, {S_H1, S_V6, 0}, 12}};
 // the product joined, the tail's first pass over the rows still to do, the loss terms' values and gd; a rank gathers gd
 static int fs_tail_reduce(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
   const mcgra_attack_config_t& c = h->cfg;
   const int n = s.n, ld = s.ld, R0 = s.R0, R1 = s.R1;
-  const bool mse = s.mse, kl = s.kl, use1 = s.use1, want_vals = s.want_vals;
+  const bool use1 = s.use1, want_vals = s.want_vals;
+  const TailVals& tv = TAIL_VALS[s.kind];
   CHK(join_p1(s));
   h->carry.p1_first = false;
   if (h->p.sharded && use1 && R1 > R0)
@@ -916,14 +928,10 @@ static int fs_tail_reduce(FusedStep& s) {
     h->step.fs_nblk = tail_reduce_call(s, 2, h->p.sharded ? R0 : h->step.tail_rows, R1, want_vals);
     h->step.tail_rows = 0;
     const Stage sgt = narrow_stage(h);
-    if (h->p.sharded && !(h->step.fs_nblk > 0 && want_vals)) CHK(lane_zero(h, st, sgt, (mse && !kl) ? 3 : 2));
-    if (h->step.fs_nblk > 0 && want_vals) {
-      // HSIC: sum P1 o Xc -> S_H1; MSELoss: sum (F - adj_norm)^2 -> S_V1 and sum (adj_norm - A1)^2 -> S_V2 (k_loss_elem's slots);
-      // KL: calc_kl(feature_adj, adj_norm) -> S_H1 (k_kl_rows' slot; c2's value came out of the decode)
-      launch_reduce_rows(st, vpart, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, 0) : h->scal + ((mse && !kl) ? S_V1 : S_H1));
-      launch_reduce_rows(st, vpart + h->step.fs_nblk, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, 1) : h->scal + S_V6);
-      if (mse && !kl) launch_reduce_rows(st, vpart + 2 * (size_t)h->step.fs_nblk, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, 2) : h->scal + S_V2);
-    }
+    if (h->p.sharded && !(h->step.fs_nblk > 0 && want_vals)) CHK(lane_zero(h, st, sgt, tv.count));
+    if (h->step.fs_nblk > 0 && want_vals)
+      for (int q = 0; q < tv.count; ++q)
+        launch_reduce_rows(st, vpart + q * (size_t)h->step.fs_nblk, h->step.fs_nblk, 1, h->p.sharded ? lane_slot(h, sgt, q) : h->scal + tv.slot[q]);
     {
       const bool cn_in_gd = h->p.fused_post && R1 > R0;
       fl_tail_gd(st, n, R0, R1, ps1, h->d, h->gd, cn_in_gd ? h->scal + S_SQ : nullptr, (float)(c.weight_sup * 0.001),
@@ -937,14 +945,11 @@ static int fs_tail_reduce(FusedStep& s) {
 // three gathers on a row-block rank); otherwise the Adam pass is next.
 static int fs_decide(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
-  const bool mse = s.mse, kl = s.kl;
   bool masked = false;
   if (h->p.sharded) {
     const Stage sgt = narrow_stage(h);
     stage_to_rows(h, st, sgt, 1, 0, h->gd, 1);
-    if (mse) lane_sum(h, st, sgt, kl ? 2 : 3, h->SC + 12);   // SC[12] sum (F - adj_norm)^2 (KL: the value of c1), SC[13] entropy term of adj_norm, SC[14] sum (adj_norm - A1)^2
-    else
-      lane_sum(h, st, sgt, 2, h->SC + 4);                      // SC[4] sum P1 o Xc, SC[5] entropy term of adj_norm
+    lane_sum(h, st, sgt, TAIL_VALS[s.kind].count, h->SC + TAIL_VALS[s.kind].sc0);      // HSIC: SC[4], SC[5]; MSELoss: SC[12 .. 14]; KL: SC[12], SC[13]
   }
   if (s.use2) {
     const unsigned int want = h->mask_want;
@@ -1000,25 +1005,15 @@ static int fs_gather_recv(FusedStep& s) {
 // was asked for scalars gathers its share of the clamp sum
 static int fs_adam(FusedStep& s) {
   mcgra_attack* h = s.h; hipStream_t st = s.st;
-  const mcgra_attack_config_t& c = h->cfg;
   const int n = s.n, ld = s.ld, R0 = s.R0, R1 = s.R1;
   const size_t cnt = (size_t)n * s.nt;      // (the Adam pass's row partials of the new M: adam_row_sums)
-  {
-    const double b1 = 0.9, b2 = 0.999;
-    const int64_t t = h->t + 1;                          // (the host's count moves in fused_commit)
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    const bool may_project = c.num_edges < 0.5 * s.n2;
-    const bool emit = adam_emits_partials(h, may_project, cnt);      // (fused_commit: prep_valid)
-    fl_tail_adam(st, n, ld, s.pair, R0, R1, h->G_ADJN, h->gd, h->M, h->am, h->av, h->mm + 2,
-                 (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(c.lr / bc1), (float)sqrt(bc2), 1e-8f,
-                 h->p.keep_gsym ? h->GSYM : nullptr, may_project ? 0 : 1, emit ? h->G_A : nullptr,
-                 emit ? adam_row_sums(h, cnt) : nullptr,
-                 /* the Adam moments are only ever read back through the lower tile pairs (by this kernel and by the general
-                    path's tail kernels): their mirrored halves are not written */ 0);
-    MCGRA_KERNEL_CHECK();
-  }
+  // step t + 1: the host's count moves in fused_commit, whose prep_valid is the same adam_emits_partials
+  fl_tail_adam(st, n, ld, s.pair, R0, R1, h->G_ADJN, h->gd, adam_update(h, h->t + 1, adam_emits_partials(h, cnt) ? cnt : 0),
+               /* the Adam moments are only ever read back through the lower tile pairs (by this kernel and by the general
+                  path's tail kernels): their mirrored halves are not written */ 0);
+  MCGRA_KERNEL_CHECK();
   fused_commit(h);
-  if (c.num_edges < 0.5 * s.n2) { CHK(project(h, st)); h->carry.prep_valid = false; }      // (monolithic only: refused at create otherwise)
+  if (may_project(h)) { CHK(project(h, st)); h->carry.prep_valid = false; }      // (monolithic only: refused at create otherwise)
   if (h->p.sharded && h->fs_want) {
     // sum(clamp(adj_changes, 0, 1)) after the update = the row sums the Adam pass just left behind, own rows
     prep_from_partials(st, n, h->G_A, adam_row_sums(h, cnt), h->d, h->r, h->rowsq, h->rowsum, R0, R1);
@@ -1028,17 +1023,17 @@ static int fs_adam(FusedStep& s) {
   }
   return h->fs_want ? xchg_sg(s) : GO;
 }
-// A row-block rank's returned loss terms: summed over the ranks into SC (fs_lr_t, fs_decide, below), then to their slots of scal
-struct ScalCopy { int slot, sc; };
-static const ScalCopy SCAL_KL[] = {{S_H1, 12}, {S_V6, 13}, {S_H2, 11}, {S_CLAMPSUM, 6}, {-1, 0}};
-static const ScalCopy SCAL_MSE[] = {{S_V1, 12}, {S_V6, 13}, {S_V2, 14}, {S_CLAMPSUM, 6}, {-1, 0}};
-static const ScalCopy SCAL_HSIC[] = {{S_H1, 4}, {S_V6, 5}, {S_CLAMPSUM, 6}, {-1, 0}};
+// A row-block rank's returned loss terms: summed over the ranks into SC (fs_lr_t, fs_decide, below), then to their slots of scal:
+// the tail's values (TAIL_VALS), KL's c2 (SC[11], from the decode) and the clamp sum
 static int fs_scalars(FusedStep& s) {
   mcgra_attack* h = s.h;
   if (!(h->p.sharded && h->fs_want)) return GO;
   lane_sum(h, s.st, narrow_stage(h), 1, h->SC + 6);
-  for (const ScalCopy* e = s.kl ? SCAL_KL : s.mse ? SCAL_MSE : SCAL_HSIC; e->slot >= 0; ++e)
-    MCGRA_HIP(hipMemcpyAsync(h->scal + e->slot, h->SC + e->sc, sizeof(double), hipMemcpyDeviceToDevice, s.st));
+  const TailVals& tv = TAIL_VALS[s.kind];
+  auto copy = [&](int slot, int sc) { return hipMemcpyAsync(h->scal + slot, h->SC + sc, sizeof(double), hipMemcpyDeviceToDevice, s.st); };
+  for (int q = 0; q < tv.count; ++q) MCGRA_HIP(copy(tv.slot[q], tv.sc0 + q));
+  if (s.kl()) MCGRA_HIP(copy(S_H2, 11));
+  MCGRA_HIP(copy(S_CLAMPSUM, 6));
   return GO;
 }
 static const FusedStage FS_STAGES[FS_COUNT] = {

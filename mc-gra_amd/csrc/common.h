@@ -73,14 +73,26 @@ hipError_t rankk_nt(hipStream_t st, int M, int N, int K1, float alpha1, const fl
                     float* C, int ldc, const float* Gn = nullptr, int ldg = 0, const float* rn = nullptr,
                     const float* gdn = nullptr);   // Gn != NULL: C = products + (Gn_ij rn_i rn_j + gdn_i), beta ignored
 
+// One step's Adam update (:274-283) as its three kernels take it: k_adam_sym (nxn_kernels.hip), k_rankk_apply_adam (rankk_f32.hip)
+// and k_tail_adam (fused_lowrank.hip).  Built once per step by adam_update (engine.h), which holds the hyper-parameters.
+struct AdamUpdate {
+  float *M, *am, *av;              // the learnable adjacency and its two moments
+  float omb1, b2, omb2;            // 1 - beta1, beta2, 1 - beta2
+  float step_size, sqrt_bc2, eps;  // lr / (1 - beta1^t), sqrt(1 - beta2^t), Adam's epsilon
+  const float* cn;                 // device scalar: the coefficient of M in the packed gradient (k_cn)
+  float* gsym_dbg;                 // NULL, or where the mirrored packed gradient is kept ("G_sym", parity tests)
+  int do_clamp;                    // 0: a projection follows and clamps
+  // [n][tiles]: per-tile row sums of the new M (and of its squares, diagonal excluded), NULL: not emitted (k_adam_sym has none);
+  // prep_from_partials turns them into k_prep's outputs without another pass over M
+  float* ps_out;
+  double* pq_out;
+};
+
 // the tail of a step in one pass: normalisation-backward apply + rank-k update + gradient mirror + Adam (rankk_f32.hip)
 bool rankk_apply_adam_supported(int n, int ld, int K);
 hipError_t rankk_apply_adam(hipStream_t st, int n, int ld, int K, const float* GP, int ldp, const float* TT, int ldt,
-                            const float* G, const float* rn, const float* gdn, const unsigned char* gate, float* M, float* am,
-                            float* av, const float* cn, float omb1, float b2, float omb2, float step_size, float sqrt_bc2,
-                            float eps, float* gsym_dbg, int do_clamp, float* ps_out = nullptr, double* pq_out = nullptr);
-// ps_out / pq_out [n][rankk_apply_adam_tiles(n)]: per-tile row sums of the new M (and of its squares, diagonal excluded);
-// prep_from_partials turns them into k_prep's outputs without another pass over M
+                            const float* G, const float* rn, const float* gdn, const unsigned char* gate, const AdamUpdate& u);
+// (u.ps_out / u.pq_out: rankk_apply_adam_tiles(n) tiles per row)
 int rankk_apply_adam_tiles(int n);
 void prep_from_partials(hipStream_t st, int n, const float* ps, const double* pq, float* d, float* r, double* rowsq,
                         double* rowsum, int row0 = 0, int row1 = -1);

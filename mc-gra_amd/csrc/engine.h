@@ -5,6 +5,7 @@
 // attack_fused.hip: the low-rank HSIC step evaluated from the learnable adjacency M directly.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <vector>
@@ -241,9 +242,27 @@ static inline float* pack_row_sums(const mcgra_attack* h, int np) { return h->A1
 // The row partials of the new M an Adam pass leaves in G_A for the next forward (prep_from_partials): cnt = n * tiles floats,
 // and behind them (8-byte aligned) as many fp64 row sums ...
 static inline double* adam_row_sums(const mcgra_attack* h, size_t cnt) { return reinterpret_cast<double*>(h->G_A + ((cnt + 1) & ~(size_t)1)); }
+// The edge-budget projection (:339) can follow the Adam pass: clamp(a, 0, 1).sum() <= n (n - 1) / 2, so a larger budget never
+// triggers the bisection.
+static inline bool may_project(const mcgra_attack* h) { return h->cfg.num_edges < 0.5 * (double)h->p.n * (double)h->p.n; }
 // ... which it emits when no projection follows and they fit into G_A.  prep_valid says the same: ONE predicate for both.
-static inline bool adam_emits_partials(const mcgra_attack* h, bool may_project, size_t cnt) {
-  return !may_project && 3 * cnt + 4 <= (size_t)h->p.n * h->p.ld;
+static inline bool adam_emits_partials(const mcgra_attack* h, size_t cnt) {
+  return !may_project(h) && 3 * cnt + 4 <= (size_t)h->p.n * h->p.ld;
+}
+// Adam step t (1-based) on M / am / av, for whichever of the three Adam kernels runs it: the only copy of the hyper-parameters
+// (torch.optim.Adam's defaults).  emit_cnt: 0, or the pass leaves its cnt row partials of the new M in G_A (adam_row_sums).
+static inline mcgra::AdamUpdate adam_update(const mcgra_attack* h, int64_t t, size_t emit_cnt = 0) {
+  const double b1 = 0.9, b2 = 0.999;
+  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
+  mcgra::AdamUpdate u{};
+  u.M = h->M; u.am = h->am; u.av = h->av;
+  u.omb1 = (float)(1.0 - b1); u.b2 = (float)b2; u.omb2 = (float)(1.0 - b2);
+  u.step_size = (float)(h->cfg.lr / bc1); u.sqrt_bc2 = (float)sqrt(bc2); u.eps = 1e-8f;
+  u.cn = h->mm + 2;
+  u.gsym_dbg = h->p.keep_gsym ? h->GSYM : nullptr;
+  u.do_clamp = may_project(h) ? 0 : 1;
+  if (emit_cnt) { u.ps_out = h->G_A; u.pq_out = adam_row_sums(h, emit_cnt); }
+  return u;
 }
 
 // attack_fused.hip

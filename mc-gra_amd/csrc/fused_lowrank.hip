@@ -757,9 +757,8 @@ __device__ __forceinline__ void rk_sym(const RkRounds& F, int ti, int tj, float 
 // modified_adj1_ij = [i != j] relu(S_ij) recomputed per pair, and
 //   Gs_ij = rank-k + 2 ie'(an) + kmse1 (2 an - F_ij - F_ji) + 2 kmse2 (an - A1_ij)        (an = adj_norm_ij; a1 / a2 unused)
 // vpart: v1 = sum (F - an)^2 (both orientations), v6 as before, and a third block of partials v2 = sum (an - A1)^2.
-// MODE 2 (the fused KL step): calc = calc_kl (:197-198, :483-487: KLDivLoss(batchmean) over rows).  P1 points at softmax(feature_adj)
-// (rows; constant per graph), `mean` / `delta` / `cvec` carry the row statistics lA_i = logsumexp_j an_ij, l1_i = logsumexp_j A1_ij
-// and v_i (k_decode_stats, k_decode_fly<.., 2>), kmse1 / kmse2 carry k1 / n and k2 / n:
+// MODE 2 (the fused KL step): calc = calc_kl (:197-198, :483-487: KLDivLoss(batchmean) over rows).  What P1, mean / delta / cvec and
+// kmse1 / kmse2 hold then (Fs = softmax(feature_adj), the row statistics lA, l1, v, k1 / n and k2 / n): TailOperands, kernels.h.
 //   d c1 / d an_ij = (k1/n) (exp(an_ij - lA_i) - Fs_ij)            d c2 / d an_ij = (k2/n) exp(an_ij - lA_i) (t_ij - v_i),
 //   t_ij = (an_ij - lA_i) - (A1_ij - l1_i);        Gs_ij = rank-k + 2 ie'(an) + [both, (i, j) + (j, i)]
 // every sum of an (i, j) and a (j, i) quantity is formed from separately rounded products (no fp contraction in that block), so
@@ -1177,6 +1176,11 @@ void fl_lrq_post(hipStream_t st, int n, int w, YView Y, const float* Vs, int ldv
   LAUNCH(k_lrq_post, g1((size_t)n * w), dim3(256), st, n, w, Y, Vs, ldv, r, mean, colsum, mw, msum, Q, ldq);
 }
 
+// The instantiation of a per-pair kernel (k_decode_fly, k_tail_reduce) for a step of `kind`, with or without the loss terms' values:
+// its place in a table laid out {KL, MSELoss, HSIC} x {with, without}.  The kernels' MODE is kind - FUSED_HSIC.
+static_assert(FUSED_HSIC == 1 && FUSED_MSE == 2 && FUSED_KL == 3, "MODE = kind - FUSED_HSIC");
+static int mode_slot(FusedKind kind, bool want_values) { return 2 * (FUSED_KL - kind) + (want_values ? 0 : 1); }
+
 // decode recomputed per pair for rows [row0, row1); returns the number of v7 partials (0 and GZn = 0 when kie7 == 0:
 // then only the mask count is produced, by the same kernel with kie7 = 0).  slabs: lr_decode_slabs(n) * n * h floats.
 // column slices of the decode of a ROW RANGE: a row-block rank has 1 / world of the row blocks, so it cuts the columns finer to
@@ -1199,32 +1203,23 @@ int fl_decode_slabs(int n, int rows, bool alone) {
   const int js0 = lr_decode_slabs(n);
   return js < js0 ? js0 : js;
 }
-int fl_decode_fly(hipStream_t st, int n, int row0, int row1, int h, const float* Z, int ldz, float kie7, float* slabs,
-                  double* v7part, float* GZn, int ldg, unsigned int* nmask, const float* zpair, bool want_v7, const float* Mm, int ldm,
-                  const float* rvec, float kmse2, const float* lseA, const float* lse1, double* vrow) {
+int fl_decode_fly(hipStream_t st, FusedKind kind, int n, int row0, int row1, int h, const DecodeOperands& o, bool want_v7) {
   const int rows = row1 - row0;
   if (rows <= 0) return 0;
-  const bool mse = Mm != nullptr;      // the fused MSELoss / KL step: + d calc(adj_norm, modified_adj1) / d modified_adj1
-  const bool kl = mse && lseA != nullptr;
-  const int nb = (rows + 255) / 256, js = fl_decode_slabs(n, rows, mse);
-  const int jper = mse ? (((n + js - 1) / js + 3) & ~3) : (n + js - 1) / js;     // (MSE: the 16-byte loads of M's tiles start on column quads)
-  const f32x2* zp = reinterpret_cast<const f32x2*>(zpair);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nb, js), dim3(256), 0, st, n, row0, row1, Z, ldz, zp, kie7, jper, slabs, v7part, nmask, Mm, ldm, rvec, kmse2,
-                       lseA, lse1, vrow);
-  };
-#define MCGRA_DECODE(H_)                                      \
-  do {                                                        \
-    if (kl && want_v7) go(k_decode_fly<H_, true, 2>);         \
-    else if (kl) go(k_decode_fly<H_, false, 2>);              \
-    else if (mse && want_v7) go(k_decode_fly<H_, true, 1>);   \
-    else if (mse) go(k_decode_fly<H_, false, 1>);             \
-    else if (want_v7) go(k_decode_fly<H_, true, 0>);          \
-    else go(k_decode_fly<H_, false, 0>);                      \
-  } while (0)
-  if (h == 8) MCGRA_DECODE(8); else if (h == 16) MCGRA_DECODE(16); else MCGRA_DECODE(32);
-#undef MCGRA_DECODE
-  LAUNCH(k_sum_slabs_rows, g1((size_t)rows * h), dim3(256), st, n, row0, row1, h, js, slabs, GZn, ldg);
+  const bool alone = kind != FUSED_HSIC;
+  const int nb = (rows + 255) / 256, js = fl_decode_slabs(n, rows, alone);
+  const int jper = alone ? (((n + js - 1) / js + 3) & ~3) : (n + js - 1) / js;     // (MSELoss, KL: the 16-byte loads of M's tiles start on column quads)
+  using Kern = decltype(&k_decode_fly<8, true, 0>);
+  static const Kern kerns[3][6] = {
+      {k_decode_fly<8, true, 2>, k_decode_fly<8, false, 2>, k_decode_fly<8, true, 1>, k_decode_fly<8, false, 1>, k_decode_fly<8, true, 0>,
+       k_decode_fly<8, false, 0>},
+      {k_decode_fly<16, true, 2>, k_decode_fly<16, false, 2>, k_decode_fly<16, true, 1>, k_decode_fly<16, false, 1>, k_decode_fly<16, true, 0>,
+       k_decode_fly<16, false, 0>},
+      {k_decode_fly<32, true, 2>, k_decode_fly<32, false, 2>, k_decode_fly<32, true, 1>, k_decode_fly<32, false, 1>, k_decode_fly<32, true, 0>,
+       k_decode_fly<32, false, 0>}};
+  LAUNCH(kerns[h == 8 ? 0 : h == 16 ? 1 : 2][mode_slot(kind, want_v7)], dim3(nb, js), dim3(256), st, n, row0, row1, o.Z, o.ldz,
+         reinterpret_cast<const f32x2*>(o.zpair), o.kie7, jper, o.slabs, o.v7part, o.nmask, o.M, o.ldm, o.r, o.k2, o.lseA, o.lse1, o.vrow);
+  LAUNCH(k_sum_slabs_rows, g1((size_t)rows * h), dim3(256), st, n, row0, row1, h, js, o.slabs, o.GZn, o.ldg);
   return nb * js;
 }
 // The fused KL step's row statistics for rows [row0, row1): lseA_i = logsumexp_j adj_norm_ij, lse1_i = logsumexp_j modified_adj1_ij.
@@ -1257,28 +1252,22 @@ size_t fl_tail_pack_bytes(int n) {
   return (size_t)2 * 3 * RK_MAXR / 2 * (nt * RK_PANEL + ((nt * sizeof(int) + 255) & ~(size_t)255));
 }
 
-// vpart (nullable): nblk v1 partials followed by nblk v6 partials, nblk = nt * (tile rows) = the return value.  The rank-k
-// terms {L, R, K, alpha} (K <= 64 each, at most two) feed Gs; {Lu, Ru, Ku} (the modified_adj chain) is added to G2 unscaled.
-// rkbuf: fl_tail_pack_bytes(n) of scratch for the packed panels.  phase: 0 = pack the panels and run the pass, 1 = pack
-// only, 2 = the pass only (same arguments as the phase-1 call).
-int fl_tail_reduce(hipStream_t st, int n, int ld, bool pair, int row0, int row1, int nfac, const float* const* L,
-                   const int* ldl, const float* const* R, const int* ldr, const int* K, const float* alpha,
-                   const float* Lu, int ldlu, const float* Ru, int ldru, int Ku, const float* M, const float* P1,
-                   const float* r, const float* mean, const float* delta, const float* cvec,
-                   float a1, float a2, float kie6, float* G2, float* ps, double* vpart, char* rkbuf, int phase, const float* Zn, int ldz,
-                   int hz, float kmse1, float kmse2, bool kl) {
+// The tail's first pass over rows [row0, row1); returns its number of blocks, nt * (tile rows).  phase: 0 = pack the rank-k panels
+// and run the pass, 1 = pack only (their inputs are ready before the N x N x N product is joined), 2 = the pass only, with the
+// operands of the phase-1 call: both build the same panel layout from them.
+int fl_tail_reduce(hipStream_t st, FusedKind kind, int n, int ld, bool pair, int row0, int row1, const TailOperands& o, int phase) {
   const int nt = fl_tail_tiles(n), t0 = row0 / FT, t1 = (row1 + FT - 1) / FT;
   if (t1 <= t0) return 0;
   RkPackJobs J{};
   RkRounds F{}, FU{}, FZ{};
   const size_t slot = (size_t)nt * RK_PANEL, eslot = ((size_t)nt * sizeof(int) + 255) & ~(size_t)255;
-  char* cur = rkbuf;
-  auto add = [&](RkRounds& G, const float* Lm, int ll, const float* Rm, int lr_, int Kf, float al) {
-    for (int c0 = 0; c0 < Kf; c0 += RK_KMAX) {
-      const int kw = Kf - c0 < RK_KMAX ? Kf - c0 : RK_KMAX, g = G.count++;
+  char* cur = o.rkbuf;
+  auto add = [&](RkRounds& G, const RankK& t) {
+    for (int c0 = 0; c0 < t.K; c0 += RK_KMAX) {
+      const int kw = t.K - c0 < RK_KMAX ? t.K - c0 : RK_KMAX, g = G.count++;
       for (int side = 0; side < 2; ++side) {
         const int q = J.count++;
-        J.src[q] = side ? Rm : Lm; J.ld[q] = side ? lr_ : ll; J.c0[q] = c0; J.kw[q] = kw; J.alpha[q] = side ? 1.f : al;
+        J.src[q] = side ? t.R : t.L; J.ld[q] = side ? t.ldr : t.ldl; J.c0[q] = c0; J.kw[q] = kw; J.alpha[q] = side ? 1.f : t.alpha;
         J.out[q] = cur; cur += slot;
         J.eout[q] = reinterpret_cast<int*>(cur); cur += eslot;
         (side ? G.R[g] : G.L[g]) = J.out[q];
@@ -1287,28 +1276,16 @@ int fl_tail_reduce(hipStream_t st, int n, int ld, bool pair, int row0, int row1,
       G.ksteps[g] = (kw + 15) / 16;
     }
   };
-  for (int f = 0; f < nfac; ++f) add(F, L[f], ldl[f], R[f], ldr[f], K[f], alpha[f]);
-  if (Ku > 0) add(FU, Lu, ldlu, Ru, ldru, Ku, 1.f);
-  if (Zn) add(FZ, Zn, ldz, Zn, ldz, hz, 0.5f);      // (0.5 zn_i) . zn_j + zn_i . (0.5 zn_j) = S_ij: the fused MSELoss step
-  // phase 1: only the panels are packed (their inputs are ready before the N x N x N product is joined); 2: only the pass
+  for (const RankK& t : o.gs) add(F, t);
+  add(FU, o.u);
+  if (kind != FUSED_HSIC) add(FZ, RankK{o.Zn, o.ldz, o.Zn, o.ldz, o.hz, 0.5f});      // (0.5 zn_i) . zn_j + zn_i . (0.5 zn_j) = S_ij
   if (phase != 2) LAUNCH(k_pack_rk, dim3(nt, J.count), dim3(256), st, n, J);
   if (phase == 1) return nt * (t1 - t0);
-  dim3 grid(nt, t1 - t0);
-  if (Zn && kl) {      // the fused KL step: mean / delta / cvec = the row statistics lA / l1 / v, kmse1 / kmse2 = k1 / n, k2 / n
-    if (vpart)
-      LAUNCH((k_tail_reduce<true, 2>), grid, dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, M, P1, r, mean, delta, cvec, a1, a2, kie6, kmse1, kmse2, G2, ps, vpart);
-    else
-      LAUNCH((k_tail_reduce<false, 2>), grid, dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, M, P1, r, mean, delta, cvec, a1, a2, kie6, kmse1, kmse2, G2, ps, nullptr);
-  } else if (Zn) {
-    if (vpart)
-      LAUNCH((k_tail_reduce<true, 1>), grid, dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, M, P1, r, mean, delta, cvec, a1, a2, kie6, kmse1, kmse2, G2, ps, vpart);
-    else
-      LAUNCH((k_tail_reduce<false, 1>), grid, dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, M, P1, r, mean, delta, cvec, a1, a2, kie6, kmse1, kmse2, G2, ps, nullptr);
-  } else
-  if (vpart)
-    LAUNCH((k_tail_reduce<true, 0>), grid, dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, M, P1, r, mean, delta, cvec, a1, a2, kie6, 0.f, 0.f, G2, ps, vpart);
-  else
-    LAUNCH((k_tail_reduce<false, 0>), grid, dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, M, P1, r, mean, delta, cvec, a1, a2, kie6, 0.f, 0.f, G2, ps, nullptr);
+  using Kern = decltype(&k_tail_reduce<true, 0>);
+  static const Kern kerns[6] = {k_tail_reduce<true, 2>, k_tail_reduce<false, 2>, k_tail_reduce<true, 1>,
+                                k_tail_reduce<false, 1>, k_tail_reduce<true, 0>, k_tail_reduce<false, 0>};
+  LAUNCH(kerns[mode_slot(kind, o.vpart != nullptr)], dim3(nt, t1 - t0), dim3(256), st, n, ld, pair ? 1 : 0, t0, F, FU, FZ, o.M, o.P, o.r, o.rowa,
+         o.rowb, o.rowc, o.a1, o.a2, o.kie6, o.k1, o.k2, o.G2, o.ps, o.vpart);
   return nt * (t1 - t0);
 }
 void fl_tail_gd(hipStream_t st, int n, int row0, int row1, const float* ps, const float* d, float* gd, const double* sq, float coef,
@@ -1316,13 +1293,12 @@ void fl_tail_gd(hipStream_t st, int n, int row0, int row1, const float* ps, cons
   if (row1 <= row0) return;
   LAUNCH(k_tail_gd, dim3((row1 - row0 + 3) / 4), dim3(256), st, n, row0, row1, fl_tail_tiles(n), ps, d, gd, sq, coef, cn_out);
 }
-void fl_tail_adam(hipStream_t st, int n, int ld, bool pair, int row0, int row1, const float* G2, const float* gd, float* M,
-                  float* am, float* av, const float* cn, float omb1, float b2, float omb2, float step_size, float sqrt_bc2,
-                  float eps, float* gsym_dbg, int do_clamp, float* ps_out, double* pq_out, int mirror_moments) {
+void fl_tail_adam(hipStream_t st, int n, int ld, bool pair, int row0, int row1, const float* G2, const float* gd, const AdamUpdate& u,
+                  int mirror_moments) {
   const int nt = fl_tail_tiles(n), t0 = row0 / FT, t1 = (row1 + FT - 1) / FT;
   if (t1 <= t0) return;
-  LAUNCH(k_tail_adam, dim3(nt, t1 - t0), dim3(256), st, n, ld, pair ? 1 : 0, t0, G2, gd, M, am, av, cn, omb1, b2, omb2, step_size,
-         sqrt_bc2, eps, gsym_dbg, do_clamp, ps_out, pq_out, mirror_moments);
+  LAUNCH(k_tail_adam, dim3(nt, t1 - t0), dim3(256), st, n, ld, pair ? 1 : 0, t0, G2, gd, u.M, u.am, u.av, u.cn, u.omb1, u.b2, u.omb2, u.step_size,
+         u.sqrt_bc2, u.eps, u.gsym_dbg, u.do_clamp, u.ps_out, u.pq_out, mirror_moments);
 }
 
 }  // namespace mcgra

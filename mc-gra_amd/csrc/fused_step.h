@@ -122,7 +122,10 @@ struct FusedStep {
   hipStream_t st;
   mcgra_exchange_t* ex;      // a row-block rank's stage that ends at an exchange describes it here (monolithic: NULL, never written)
   int n, ld, hs, L, Le, C, fc, R0, R1;
-  bool mse, kl, use1, use2, use9, use10;
+  mcgra::FusedKind kind;     // which fused step this is (the plan's p.fused): stated here once, read by every stage and passed to the launchers
+  bool elementwise() const { return kind == mcgra::FUSED_MSE || kind == mcgra::FUSED_KL; }      // (the plan's wording: attack_plan.h)
+  bool kl() const { return kind == mcgra::FUSED_KL; }
+  bool use1, use2, use9, use10;
   double sg, k1, k2, k6, k7, k9, k10, n2;
   float kmse1, kmse2, a1, a2;
   const float* em;           // the embedding chain's last activations, width he
@@ -137,9 +140,10 @@ static inline FusedStep fused_ctx(mcgra_attack* h, hipStream_t st, mcgra_exchang
   s.n = h->p.n; s.ld = h->p.ld; s.hs = h->p.hsum; s.L = h->p.L; s.Le = h->p.Le; s.C = h->p.C; s.fc = h->p.fcols; s.R0 = h->p.row0; s.R1 = h->p.row1;
   // measure == HSIC (sign -1: :217-220), or -- h->p.elementwise() -- MSELoss: no product (use1) and no low-rank factors (use2); its two
   // N x N terms are elementwise and live in the decode (d / d modified_adj1) and in the tail's first pass (d / d adj_norm)
-  // -- h->p.kl() (mse is set as well: "an elementwise measure") -- calc_kl: the MSELoss step's data flow with per-row softmax
+  // -- h->p.kl() (also "an elementwise measure") -- calc_kl: the MSELoss step's data flow with per-row softmax
   // statistics in front of the decode (k_decode_stats: one more per-pair pass) and one more gather on a row-block rank
-  const bool mse = s.mse = h->p.elementwise(), kl = s.kl = h->p.kl();
+  s.kind = (mcgra::FusedKind)h->p.fused;
+  const bool mse = s.elementwise(), kl = s.kl();
   s.sg = mse ? 1.0 : -1.0;
   const double w1 = c.w[0], w2 = c.w[1], w6 = c.w[5], w7 = c.w[6], w9 = c.w[8], w10 = c.w[9];
   s.k1 = w1 * 1000 * AP_C1; s.k2 = w2 * 100 * AP_C2; s.k6 = w6 * 100 * AP_C6; s.k7 = w7 * AP_C7;
@@ -165,7 +169,7 @@ static inline FusedStep fused_ctx(mcgra_attack* h, hipStream_t st, mcgra_exchang
   //  the join of a side stream cost the caller's stream more than the two launches do: Cora-shaped 0.214 -> 0.199 ms; KL's terms stay on
   //  their stream -- 0.270 against 0.284 inline as chains of four launches, 0.288 inline as one launch each (built, measured, removed);
   //  A/B MCGRA_MSE_SMALL_INLINE=0)
-  s.s3 = (mse && !kl && !h->p.sharded && h->p.mse_small_inline && s.n < 4096) ? st : h->st3;
+  s.s3 = (s.kind == mcgra::FUSED_MSE && !h->p.sharded && h->p.mse_small_inline && s.n < 4096) ? st : h->st3;
   s.zero_inline = s.s3 == st && !h->p.sharded;      // (see launch_row_normalize in fs_decode_stats)
   return s;
 }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "attack_plan.h"
+
 namespace mcgra {
 
 // ---- nxn_kernels.hip
@@ -43,9 +45,7 @@ void launch_normbwd(hipStream_t st, int n, int ld, const float* G, const float* 
                     const float* d, float* rowpart, float* colpart, int nstrips, float* gd, float* GA,
                     bool have_parts = false);     // have_parts: rowpart / colpart already hold the two reductions
 void launch_sym_mask(hipStream_t st, int n, int ld, const float* G, const float* A1, const float* ori, float* out);
-void launch_adam_sym(hipStream_t st, int n, int ld, const float* GA, const unsigned char* gate, float* M,
-                     float* am, float* av, const float* cn, float omb1, float b2, float omb2, float step_size,
-                     float sqrt_bc2, float eps, float* gsym_dbg, int do_clamp);
+void launch_adam_sym(hipStream_t st, int n, int ld, const float* GA, const unsigned char* gate, const AdamUpdate& u);      // (common.h)
 void launch_clamp_rowsum(hipStream_t st, int n, int ld, const float* M, float x, double* rows, float* rowmin, float* rowmax);
 void launch_shift_clamp(hipStream_t st, int n, int ld, float* M, float x);
 void launch_minmax(hipStream_t st, int n, const float* rowmin, const float* rowmax, float* out);
@@ -170,28 +170,61 @@ void fl_lrt_post(hipStream_t st, int n, int w, YView Y, const float* Vs, int ldv
 void fl_lrq_pre(hipStream_t st, int n, int w, const float* W, int ldw, const float* r, const double* colsum, float* Vs, int ldv);
 void fl_lrq_post(hipStream_t st, int n, int w, YView Y, const float* Vs, int ldv, const float* r, const float* mean,
                  const double* colsum, const double* mw, const double* msum, float* Q, int ldq);
-int fl_decode_fly(hipStream_t st, int n, int row0, int row1, int h, const float* Z, int ldz, float kie7, float* slabs,
-                  double* v7part, float* GZn, int ldg, unsigned int* nmask, const float* zpair, bool want_v7 = true,
-                  const float* Mm = nullptr, int ldm = 0, const float* rvec = nullptr, float kmse2 = 0.f,
-                  const float* lseA = nullptr, const float* lse1 = nullptr, double* vrow = nullptr);      // Mm != NULL: the fused MSELoss step (+ kmse2 (adj_norm - A1) term); + lseA / lse1 / vrow: the fused KL step (kmse2 = k2 / n)   // zpair: Zn pair-interleaved, (n + 1) / 2 * 2 * h floats (launch_row_normalize writes it)
-int fl_decode_slabs(int n, int rows, bool alone);
+// -- The two per-pair passes of the fused step: the decode (k_decode_fly) and the tail's first pass (k_tail_reduce).  WHICH step
+//    runs is their `kind` argument (FusedKind, attack_plan.h: HSIC, MSELoss or KL; the kernels' MODE is kind - FUSED_HSIC), never
+//    read off the operands; what an operand MEANS for each kind is written here and nowhere else.  A field a kind does not use
+//    stays unset (zero).
+struct DecodeOperands {
+  const float* Z; int ldz;         // Zn [n x h], and
+  const float* zpair;              //   its pair-interleaved copy, (n + 1) / 2 * 2 * h floats (launch_row_normalize writes both)
+  float kie7;                      // coefficient of the entropy term of modified_adj1 (0: only the mask count is produced, GZn = 0)
+  float* slabs;                    // fl_decode_slabs * n * h floats of scratch (the backward's column slices)
+  double* v7part;                  // partials of the entropy term's value (summed when want_v7; their count is the return value)
+  float* GZn; int ldg;             // out: d / d Zn
+  unsigned int* nmask;             // [0] += masked pairs, [1] += dead rows
+  // MSELoss and KL: + d calc(adj_norm, modified_adj1) / d modified_adj1, adj_norm_ij formed from M and r per pair
+  const float* M; int ldm;
+  const float* r;
+  float k2;                        // MSELoss: 2 k2 / n^2 (k_loss_elem's multiplier); KL: k2 / n (batchmean over rows)
+  // KL: the row statistics of fl_decode_stats, and the per-(column slice, row) partials of v_i (fl_kl_v_fin sums them)
+  const float *lseA, *lse1;
+  double* vrow;
+};
+// alpha L R^T, K columns (ldl / ldr: the factors' leading dimensions)
+struct RankK { const float* L; int ldl; const float* R; int ldr; int K; float alpha; };
+struct TailOperands {
+  RankK gs[2];                     // the rank-k terms of Gs (K <= 64 each; K = 0: none): the victim chain; HSIC with c2: the low-rank factors
+  RankK u;                         // the modified_adj chain's term, added to G2 (its alpha is 1)
+  const float* M; const float* r;
+  //                  HSIC                              MSELoss                          KL
+  const float* P;     // P1 = (H Kf H) Xc (NULL: no c1)  feature_adj                      softmax(feature_adj) (rows)
+  const float* rowa;  // column means of adj_norm        n readable floats (loaded,       lA_i = logsumexp_j adj_norm_ij
+                      //                                 never used: the means' buffer)
+  const float* rowb;  // delta (NULL: no c2)             --                               l1_i = logsumexp_j modified_adj1_ij
+  const float* rowc;  // c (with delta)                  --                               v_i, the row's share of c2's value
+  float a1, a2;       // 2 sign k1, 2 sign k2            --                               --
+  float k1, k2;       // --                              2 k1 / n^2, 2 k2 / n^2           k1 / n, k2 / n
+  float kie6;                      // coefficient of the entropy term of adj_norm
+  const float* Zn; int ldz, hz;    // MSELoss and KL: S = Zn Zn^T as a third rank-k group (modified_adj1 per pair)
+  float* G2;                       // out: Gs r_i r_j + u's term
+  float* ps;                       // out [n][fl_tail_tiles(n)]: row partials of the normalisation backward's reductions
+  double* vpart;                   // NULL, or the blocks' partials of the loss terms' values: v1 | v6 (| v2: MSELoss), each as
+                                   //   many as the return value
+  char* rkbuf;                     // fl_tail_pack_bytes(n) of scratch: the packed rank-k panels
+};
+// returns the number of v7 partials (0 without rows)
+int fl_decode_fly(hipStream_t st, FusedKind kind, int n, int row0, int row1, int h, const DecodeOperands& o, bool want_v7 = true);
+int fl_decode_slabs(int n, int rows, bool alone);      // alone: nothing MFMA-bound runs beside the decode (an elementwise kind)
 int fl_decode_stats(hipStream_t st, int n, int row0, int row1, int h, const float* Z, int ldz, const float* zpair, const float* Mm, int ldm,
                     const float* rvec, double* part, float* lseA, float* lse1);      // the fused KL step: row logsumexp of adj_norm and modified_adj1
 void fl_kl_v_fin(hipStream_t st, int n, int row0, int row1, const double* vrow, double* vsum, float* vf);
 int fl_tail_tiles(int n);
 bool fl_tail_supported(int n, int ld, int kmax);
-int fl_tail_reduce(hipStream_t st, int n, int ld, bool pair, int row0, int row1, int nfac, const float* const* L,
-                   const int* ldl, const float* const* R, const int* ldr, const int* K, const float* alpha,
-                   const float* Lu, int ldlu, const float* Ru, int ldru, int Ku, const float* M, const float* P1,
-                   const float* r, const float* mean, const float* delta, const float* cvec,
-                   float a1, float a2, float kie6, float* G2, float* ps, double* vpart, char* rkbuf, int phase = 0,
-                   const float* Zn = nullptr, int ldz = 0, int hz = 0, float kmse1 = 0.f, float kmse2 = 0.f,
-                   bool kl = false);      // Zn != NULL: the fused MSELoss step (P1 = feature_adj); + kl: the fused KL step (P1 = softmax(feature_adj), mean / delta / cvec = lA / l1 / v)
+int fl_tail_reduce(hipStream_t st, FusedKind kind, int n, int ld, bool pair, int row0, int row1, const TailOperands& o, int phase = 0);
 size_t fl_tail_pack_bytes(int n);
 void fl_tail_gd(hipStream_t st, int n, int row0, int row1, const float* ps, const float* d, float* gd, const double* sq = nullptr,
                 float coef = 0.f, float* cn_out = nullptr);
-void fl_tail_adam(hipStream_t st, int n, int ld, bool pair, int row0, int row1, const float* G2, const float* gd, float* M,
-                  float* am, float* av, const float* cn, float omb1, float b2, float omb2, float step_size, float sqrt_bc2,
-                  float eps, float* gsym_dbg, int do_clamp, float* ps_out, double* pq_out, int mirror_moments);
+void fl_tail_adam(hipStream_t st, int n, int ld, bool pair, int row0, int row1, const float* G2, const float* gd, const AdamUpdate& u,
+                  int mirror_moments);
 
 }  // namespace mcgra

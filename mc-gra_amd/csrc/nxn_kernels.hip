@@ -1046,11 +1046,10 @@ void launch_sym_mask(hipStream_t st, int n, int ld, const float* G, const float*
   const int t = (n + TP - 1) / TP;
   LAUNCH(k_sym_mask, dim3(t, t), dim3(256), st, n, ld, G, A1, ori, out);
 }
-void launch_adam_sym(hipStream_t st, int n, int ld, const float* GA, const unsigned char* gate, float* M,
-                     float* am, float* av, const float* cn, float omb1, float b2, float omb2, float step_size,
-                     float sqrt_bc2, float eps, float* gsym_dbg, int do_clamp) {
+void launch_adam_sym(hipStream_t st, int n, int ld, const float* GA, const unsigned char* gate, const AdamUpdate& u) {
   const int t = (n + TP - 1) / TP;
-  LAUNCH(k_adam_sym, dim3(t, t), dim3(256), st, n, ld, GA, gate, M, am, av, cn, omb1, b2, omb2, step_size, sqrt_bc2, eps, gsym_dbg, do_clamp);
+  LAUNCH(k_adam_sym, dim3(t, t), dim3(256), st, n, ld, GA, gate, u.M, u.am, u.av, u.cn, u.omb1, u.b2, u.omb2, u.step_size, u.sqrt_bc2, u.eps,
+         u.gsym_dbg, u.do_clamp);
 }
 void launch_clamp_rowsum(hipStream_t st, int n, int ld, const float* M, float x, double* rows, float* rowmin, float* rowmax) {
   LAUNCH(k_clamp_rowsum, dim3(n), dim3(ROW_THREADS), st, n, ld, M, x, rows, rowmin, rowmax);

@@ -349,14 +349,13 @@ bool rankk_apply_adam_supported(int n, int ld, int K) {
   return K > 0 && K <= 4 * RK_KMAX && (ld % 4) == 0 && n >= 256;      // (beyond RK_KMAX: the panels in rounds of RK_KMAX columns)
 }
 hipError_t rankk_apply_adam(hipStream_t st, int n, int ld, int K, const float* GP, int ldp, const float* TT, int ldt,
-                            const float* G, const float* rn, const float* gdn, const unsigned char* gate, float* M, float* am,
-                            float* av, const float* cn, float omb1, float b2, float omb2, float step_size, float sqrt_bc2,
-                            float eps, float* gsym_dbg, int do_clamp, float* ps_out, double* pq_out) {
+                            const float* G, const float* rn, const float* gdn, const unsigned char* gate, const AdamUpdate& u) {
   const int t = (n + RA_T - 1) / RA_T;
   const int vp = ((K % 4) == 0 && (ldp % 4) == 0 && (ldt % 4) == 0 && (uintptr_t)GP % 16 == 0 && (uintptr_t)TT % 16 == 0) ? 1 : 0;
-#define MCGRA_RA_LAUNCH(KM)                                                                                             \
-  hipLaunchKernelGGL(k_rankk_apply_adam<KM>, dim3(t, t), dim3(256), 0, st, n, ld, K, GP, ldp, TT, ldt, vp, G, rn, gdn, gate, M, \
-                     am, av, cn, omb1, b2, omb2, step_size, sqrt_bc2, eps, gsym_dbg, do_clamp, ps_out, pq_out)
+#define MCGRA_RA_LAUNCH(KM)                                                                                               \
+  hipLaunchKernelGGL(k_rankk_apply_adam<KM>, dim3(t, t), dim3(256), 0, st, n, ld, K, GP, ldp, TT, ldt, vp, G, rn, gdn, gate, u.M, \
+                     u.am, u.av, u.cn, u.omb1, u.b2, u.omb2, u.step_size, u.sqrt_bc2, u.eps, u.gsym_dbg, u.do_clamp, u.ps_out,   \
+                     u.pq_out)
   if (K <= 32) MCGRA_RA_LAUNCH(32);
   else MCGRA_RA_LAUNCH(64);
 #undef MCGRA_RA_LAUNCH
