@@ -600,6 +600,36 @@ int mcgra_class_auc(void* stream, int n, const float* labels, int ld_labels, con
                     const uint8_t* strata /* host [n_class][n_class] */, int n_strata, float threshold,
                     int64_t* out /* host [n_strata][5]: row g = {pairs_g, P_g, T_g, above_g, hits_g} */);
 
+/* Which summand carries an ensemble: mcgra_auc_delong's T of up to 255 subset sums of up to eight components, in one pass.
+ *   - candidates, selection, label checks and idx rules as mcgra_auc_delong: idx, n_idx REPEAT-FREE device int64 node ids or NULL
+ *     for all n nodes; the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b with label labels[idx[a]][idx[b]];
+ *   - comps: a HOST array of K device pointers, K in [1, MCGRA_SUBSET_MAX_K], component k an n x n float32 matrix of leading
+ *     dimension ld_comps, read at [idx[a]][idx[b]] only;
+ *   - masks: a HOST array of n_masks in [1, MCGRA_SUBSET_MAX_MASKS] masks, each in [1, 2^K); bit k selects component k.  Repeats
+ *     are allowed and give equal T;
+ *   - the score of a pair under mask M is the float32 sum of its components k in M in ascending k: s = c_first; s = s + c_next;
+ *     ... (one rounding per add, no fma, no other order);
+ *   - out (host uint64 [3 + n_masks]) = {m, P, N, T_0, ..., T_{n_masks - 1}}: P the pairs of label 1, N = m - P, T_s =
+ *     mcgra_auc_delong's T (twice the Mann-Whitney count of the edges over the non-edges, ties counted once; -0.0 == +0.0) on the
+ *     materialised sum of masks[s], whose AUC is T_s / (2 P N).  T_s <= 2 P N < 2^63 for n_idx <= 65 535;
+ *   - out, comps, masks, labels or a component NULL, K or n_masks out of range, a mask outside [1, 2^K), an ld below n, n_idx (n
+ *     when idx is NULL) below 2: MCGRA_EINVAL; n_idx above 65 535: MCGRA_ENOSUP.  These run before any HIP call.  A selected
+ *     component value or a subset sum (of a mask asked for, or of one of its prefixes in ascending k) that is NaN or +-inf, a
+ *     selected label other than 0 or 1, a repeated or out-of-range id: MCGRA_EINVAL.  After any refusal nothing has been
+ *     written to out and mcgra_last_error() names the cause;
+ *   - integer arithmetic on the device apart from the adds (a radix sort of the edges' sums by mask and score, searches inside a
+ *     mask's segment, integer counts merged by integer atomics): the same bits on every call, the same integers under any
+ *     permutation of idx.
+ * Synchronises `stream`.
+ * Device scratch: 16 bytes per candidate of label 1 and distinct mask, about 3 MB, and 4 bytes per node of the graph when idx
+ * is given. */
+#define MCGRA_SUBSET_MAX_K 8
+#define MCGRA_SUBSET_MAX_MASKS 255
+int mcgra_subset_auc(void* stream, int n, const float* labels, int ld_labels,
+                     const float* const* comps /* host [K] device pointers */, int K, int ld_comps, const int64_t* idx,
+                     int64_t n_idx, const uint32_t* masks /* host [n_masks] */, int n_masks,
+                     uint64_t* out /* host [3 + n_masks]: {m, P, N, T_0, ...} */);
+
 /* Whose neighbourhood leaked: the ranking of every selected node's own candidates, as exact integer counts per node.
  *   - the selection: idx, n_idx REPEAT-FREE device int64 node ids (a repeated or out-of-range id: MCGRA_EINVAL), or NULL for
  *     all n nodes in order.  For position a of idx the candidates are the n_idx - 1 positions b != a; candidate b has score
@@ -828,6 +858,20 @@ int mcgra_attack_monitor(mcgra_attack_t* h, void* stream, float* out_logp, doubl
 int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode,
                           const float* H_A, const float* Y_A, const float* label_adj,
                           float* out);
+
+/* mcgra_attack_finalize with its summands kept apart: the same carry rule, the same M afterwards.  Component k is written as an
+ * n x n matrix (ld = n) at comps + k n n, in the order in which mcgra_attack_finalize adds them: 0 learned (modified_adj of
+ * :302, with ori_adj when there is one), 1 feature, 2 H_A1, 3 H_A2, 4 Y_A2, 5 ori_HA (H_A), 6 ori_YA (Y_A), 7 label
+ * (MCGRA_ENSEMBLE_COMPONENTS of them; comps holds all eight slots).  A component whose input is NULL is not written and its
+ * bit is clear in *present (host; may be NULL).  Each component is the bits mcgra_attack_finalize adds (a decode accumulates
+ * into `out` there, into a zeroed matrix here).  out may be NULL; otherwise out [n x n] = the float32 sum of the components of
+ * out_mask in ascending k, s = c_first; s = s + c_next; ...: for an out_mask equal to the given inputs, mcgra_attack_finalize's
+ * out bit for bit.  Refused (MCGRA_EINVAL, before anything is touched) beside mcgra_attack_finalize's refusals: NULL comps, an
+ * out_mask with a bit outside present, out_mask == 0 with a non-NULL out. */
+#define MCGRA_ENSEMBLE_COMPONENTS 8
+int mcgra_attack_finalize_components(mcgra_attack_t* h, void* stream, int decode_mode,
+                                     const float* H_A, const float* Y_A, const float* label_adj,
+                                     unsigned out_mask, float* out, float* comps, unsigned* present);
 
 /* Device pointer + shape of a named intermediate of the last step, for parity
  * tests ("adj_norm", "A1", "em", "G_adjn", "G_A1", "G_A", "G_sym", "M", "d",

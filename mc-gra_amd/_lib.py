@@ -49,6 +49,7 @@ SYMBOLS = [
     "mcgra_graph_structure",
     "mcgra_hop_auc",
     "mcgra_class_auc",
+    "mcgra_subset_auc", "mcgra_attack_finalize_components",
     "mcgra_pair_metric_name", "mcgra_pair_distance_scores", "mcgra_pair_distance_rank_metrics",
 ]
 
@@ -146,6 +147,8 @@ def _load():
         "mcgra_hop_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.c_float, C.POINTER(C.c_int64)],
         "mcgra_class_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, ip, C.c_int, C.POINTER(C.c_uint8), C.c_int,
                             C.c_float, C.POINTER(C.c_int64)],
+        "mcgra_subset_auc": [vp, C.c_int, fp, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, ip, C.c_int64,
+                             C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint64)],
         "mcgra_pair_distance_scores": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int],
         "mcgra_pair_distance_rank_metrics": [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, ip, C.c_int64,
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
@@ -172,6 +175,7 @@ def _load():
         "mcgra_attack_path_stats": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
         "mcgra_attack_monitor": [vp, vp, fp, C.POINTER(C.c_double)],
         "mcgra_attack_finalize": [vp, vp, C.c_int, fp, fp, fp, fp],
+        "mcgra_attack_finalize_components": [vp, vp, C.c_int, fp, fp, fp, C.c_uint, fp, fp, C.POINTER(C.c_uint)],
         "mcgra_attack_buffer": [vp, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int)],
         "mcgra_attack_copy_buffer": [vp, vp, C.c_char_p, fp, C.c_int],

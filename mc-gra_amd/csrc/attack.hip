@@ -1405,11 +1405,12 @@ static int dd2(mcgra_attack* h, hipStream_t st, int mode, const float* Z, int w,
   return 0;
 }
 
-int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, const float* H_A, const float* Y_A,
-                          const float* label_adj, float* out) {
-  if (!h || !out || !h->graph_set) { set_error("engine not set up / null out"); return MCGRA_EINVAL; }
-  if (decode_mode < 0 || decode_mode > 6) { set_error("decode_mode %d", decode_mode); return MCGRA_EINVAL; }
-  hipStream_t st = (hipStream_t)stream;
+// The post-loop ensemble (:300-324), behind both entries.  comps == NULL (mcgra_attack_finalize): every summand is added to out
+// as it is made.  comps != NULL (mcgra_attack_finalize_components): summand k goes to its own matrix comps + k n n -- a matrix is
+// copied, a decode accumulates into a zeroed one, so that it is the bits the first form adds -- and then, when out_mask holds it,
+// into out by the same add.  The arguments were checked.
+static int finalize_run(mcgra_attack* h, hipStream_t st, int decode_mode, const float* H_A, const float* Y_A,
+                        const float* label_adj, unsigned out_mask, float* out, float* comps) {
   const int n = h->p.n, ld = h->p.ld, hs = h->p.hsum, Le = h->p.Le, L = h->p.L;
   // Rule: drop + forget.  What a monitor call forked for a step that never came reads M, which is overwritten below (:301), and writes
   // scratch; the forward it left and the row sums the Adam pass left describe the old M.  (skip_fused is kept: a step may follow.)
@@ -1436,18 +1437,64 @@ int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, cons
     launch_axpby2d(st, n, h->M, ld, 1.f, h->ORI, ld, 1.f, h->Bbuf, ld);
     mod = h->Bbuf;
   }
+  const size_t nn = (size_t)n * n;
+  bool started = false;                                    // out holds a summand
+  // out = X, then out = out + X: s = c_first; s = s + c_next; ...
+  auto add = [&](const float* X, int ldx) {
+    if (started) launch_axpby2d(st, n, out, n, 1.f, X, ldx, 1.f, out, n);
+    else launch_axpby2d(st, n, X, ldx, 1.f, nullptr, 0, 1.f, out, n);
+    started = true;
+  };
+  // summand k, an n x n matrix X
+  auto matrix = [&](int k, const float* X, int ldx) {
+    if (!comps) { add(X, ldx); return; }
+    launch_axpby2d(st, n, X, ldx, 1.f, nullptr, 0, 1.f, comps + k * nn, n);
+    if (out && (out_mask >> k & 1u)) add(comps + k * nn, n);
+  };
+  // summand k, dot_product_decode2 of Z
+  auto decode = [&](int k, const float* Z, int w, int ldz) -> int {
+    if (!comps) return dd2(h, st, decode_mode, Z, w, ldz, out);      // (learned and feature came first: out is started)
+    MCGRA_HIP(hipMemsetAsync(comps + k * nn, 0, sizeof(float) * nn, st));
+    CHK(dd2(h, st, decode_mode, Z, w, ldz, comps + k * nn));
+    if (out && (out_mask >> k & 1u)) add(comps + k * nn, n);
+    return 0;
+  };
   // out = modified_adj + feature_adj (:314)
-  launch_axpby2d(st, n, mod, ld, 1.f, h->FADJ, ld, 1.f, out, n);
+  matrix(0, mod, ld);
+  matrix(1, h->FADJ, ld);
   // H_A1, H_A2 = embedding(features, modified_adj) with 1 / 2 layers; Y_A2 = victim (:304-308)
   CHK(chain_forward(h, st, mod, ld, L, h->Tu, h->Pu, h->Hu, h->Su));
   CHK(head_forward(h, st, h->Hu, h->Z2, h->logp, nullptr));
-  CHK(dd2(h, st, decode_mode, h->Hu + h->p.off[h->p.fin0 - 1], h->p.wdt[h->p.fin0 - 1], hs, out));   // H_A1 (:304-305)
-  CHK(dd2(h, st, decode_mode, h->Hu + h->p.off[h->p.fin1 - 1], h->p.wdt[h->p.fin1 - 1], hs, out));   // H_A2 (:306-307)
-  CHK(dd2(h, st, decode_mode, h->logp, h->p.C, h->p.C, out));
-  if (H_A) CHK(dd2(h, st, decode_mode, H_A, h->p.wdt[Le - 1], h->p.wdt[Le - 1], out));   // (:315-316)
-  if (Y_A) CHK(dd2(h, st, decode_mode, Y_A, h->p.C, h->p.C, out));                        // (:317-318)
-  if (label_adj) launch_axpby2d(st, n, out, n, 1.f, label_adj, n, 1.f, out, n);       // (:319-320)
+  CHK(decode(2, h->Hu + h->p.off[h->p.fin0 - 1], h->p.wdt[h->p.fin0 - 1], hs));   // H_A1 (:304-305)
+  CHK(decode(3, h->Hu + h->p.off[h->p.fin1 - 1], h->p.wdt[h->p.fin1 - 1], hs));   // H_A2 (:306-307)
+  CHK(decode(4, h->logp, h->p.C, h->p.C));
+  if (H_A) CHK(decode(5, H_A, h->p.wdt[Le - 1], h->p.wdt[Le - 1]));   // (:315-316)
+  if (Y_A) CHK(decode(6, Y_A, h->p.C, h->p.C));                        // (:317-318)
+  if (label_adj) matrix(7, label_adj, n);                             // (:319-320)
   MCGRA_KERNEL_CHECK();
+  return 0;
+}
+
+int mcgra_attack_finalize(mcgra_attack_t* h, void* stream, int decode_mode, const float* H_A, const float* Y_A,
+                          const float* label_adj, float* out) {
+  if (!h || !out || !h->graph_set) { set_error("engine not set up / null out"); return MCGRA_EINVAL; }
+  if (decode_mode < 0 || decode_mode > 6) { set_error("decode_mode %d", decode_mode); return MCGRA_EINVAL; }
+  return finalize_run(h, (hipStream_t)stream, decode_mode, H_A, Y_A, label_adj, 0u, out, nullptr);
+}
+
+int mcgra_attack_finalize_components(mcgra_attack_t* h, void* stream, int decode_mode, const float* H_A, const float* Y_A,
+                                     const float* label_adj, unsigned out_mask, float* out, float* comps, unsigned* present) {
+  if (!h || !h->graph_set) { set_error("engine not set up"); return MCGRA_EINVAL; }
+  if (decode_mode < 0 || decode_mode > 6) { set_error("decode_mode %d", decode_mode); return MCGRA_EINVAL; }
+  const unsigned have = 0x1fu | (H_A ? 1u << 5 : 0u) | (Y_A ? 1u << 6 : 0u) | (label_adj ? 1u << 7 : 0u);
+  if (!comps) { set_error("finalize_components: null comps"); return MCGRA_EINVAL; }
+  if (out_mask & ~have) {
+    set_error("finalize_components: out_mask 0x%x names a component that is not given (present 0x%x)", out_mask, have);
+    return MCGRA_EINVAL;
+  }
+  if (out && !out_mask) { set_error("finalize_components: out_mask 0 with an out to write"); return MCGRA_EINVAL; }
+  CHK(finalize_run(h, (hipStream_t)stream, decode_mode, H_A, Y_A, label_adj, out_mask, out, comps));
+  if (present) *present = have;
   return 0;
 }
 

@@ -998,6 +998,110 @@ def class_auc(real, pred, classes, idx=None, strata="blocks", threshold=None):
     return class_auc_stats([out[5 * g:5 * g + 5] for g in range(G)], names, threshold)
 
 
+# the summands of mcgra_attack_finalize, in the order in which it adds them (mcgra_attack_finalize_components' slots)
+ENSEMBLE_COMPONENTS = ("learned", "feature", "H_A1", "H_A2", "Y_A2", "ori_HA", "ori_YA", "label")
+SUBSET_MAX_K = 8            # MCGRA_SUBSET_MAX_K (include/mcgra.h)
+SUBSET_MAX_MASKS = 255      # MCGRA_SUBSET_MAX_MASKS
+ENSEMBLE_BASE = 0x1f        # the five summands that no flag switches off
+
+
+def _subset_masks(op, masks, K):
+    """masks as a list of Python ints, each in [1, 2^K); ValueError otherwise."""
+    masks = list(masks)
+    if not 1 <= len(masks) <= SUBSET_MAX_MASKS:
+        raise ValueError(f"{op}: {len(masks)} masks; 1 to {SUBSET_MAX_MASKS}")
+    for q in masks:
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q < (1 << K):
+            raise ValueError(f"{op}: mask {q!r}; an integer in [1, {1 << K}) selects among {K} components")
+    return [int(q) for q in masks]
+
+
+@_on_operand_device
+def subset_auc(real, comps, masks, idx=None):
+    """Which summand carries an ensemble (mcgra_subset_auc): for every mask of `masks` the AUC of the candidates of auc_delong --
+    the unordered pairs of positions a > b of a REPEAT-FREE idx (None: all nodes), label real[idx[a], idx[b]] -- scored by the
+    float32 sum of the components the mask selects, added in ascending k (bit k of a mask: component k), in ONE pass over the
+    pairs.  comps: a [K, n, n] tensor or a list of K n x n tensors, K from 1 to 8; masks: 1 to 255 integers in [1, 2^K),
+    repeats allowed.  Returns {"pairs", "positives", "negatives", "masks", "T" (per mask auc_delong's integer T on the
+    materialised sum), "auc" (per mask the nearest double of T / (2 P N), NaN when P or N is 0)}: exact integers from the device,
+    the same bits on every call.  ValueError for a wrong K, shape or mask; McgraError for whatever the entry refuses: a repeated
+    or out-of-range id, a selected label other than 0 / 1, a selected component value or subset sum that is NaN or inf."""
+    if isinstance(comps, torch.Tensor):
+        comps = comps.unbind(0) if comps.dim() == 3 else ()
+    comps = list(comps)
+    if not 1 <= len(comps) <= SUBSET_MAX_K:
+        raise ValueError(f"subset_auc: comps is a [K, n, n] tensor or a list of K n x n tensors, K in [1, {SUBSET_MAX_K}]")
+    K = len(comps)
+    masks = _subset_masks("subset_auc", masks, K)
+    n = real.shape[0]
+    if real.dim() != 2 or any(not isinstance(c, torch.Tensor) or tuple(c.shape) != (n, n) for c in comps) or real.shape[1] != n:
+        raise ValueError(f"subset_auc: real and every component are {n} x {n} tensors")
+    real, ix, n, rows = _ranked(idx, real)
+    comps = [_rows_f32(c, real.device) for c in comps]
+    if len({c.stride(0) for c in comps}) > 1:          # one leading dimension for all of them
+        comps = [c.contiguous() for c in comps]
+    ptrs = (C.c_void_p * K)(*[c.data_ptr() for c in comps])
+    out = (C.c_uint64 * (3 + len(masks)))()
+    check(lib.mcgra_subset_auc(_stream(), n, _p(real), real.stride(0), ptrs, K, comps[0].stride(0), _p(ix), rows,
+                               (C.c_uint32 * len(masks))(*masks), len(masks), out))
+    m, P, N = (int(v) for v in out[:3])
+    T = [int(v) for v in out[3:]]
+    return {"pairs": m, "positives": P, "negatives": N, "masks": masks, "T": T,
+            "auc": [float(Fraction(t, 2 * P * N)) if P and N else float("nan") for t in T]}
+
+
+def ablation_masks(present, used):
+    """The subsets of the ensemble's summands that main.py --ablate ranks, as a de-duplicated ordered list of at most 25 masks
+    (bit k: ENSEMBLE_COMPONENTS[k]): `used`; each present component alone; `used` without each of its components (not the empty
+    set); components 0-4 with each subset of {ori_HA, ori_YA, label} that is present, in the binary order of (useH_A, useY_A,
+    useY) -- the paper's flag table.  present holds the base five, used is a non-empty subset of present.  No device."""
+    full = (1 << len(ENSEMBLE_COMPONENTS)) - 1
+    for name, v in (("present", present), ("used", used)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= full:
+            raise ValueError(f"ablation_masks: {name} = {v!r}; a mask of the {len(ENSEMBLE_COMPONENTS)} components")
+    present, used = int(present), int(used)
+    if present & ENSEMBLE_BASE != ENSEMBLE_BASE or not used or used & ~present:
+        raise ValueError(f"ablation_masks: present = {present:#x}, used = {used:#x}; present holds the base five "
+                         f"({ENSEMBLE_BASE:#x}) and used is a non-empty subset of it")
+    bits = [k for k in range(len(ENSEMBLE_COMPONENTS)) if present >> k & 1]
+    table = [used] + [1 << k for k in bits] + [used & ~(1 << k) for k in bits if used >> k & 1 and used != 1 << k]
+    table += flag_table_masks(present)
+    return list(dict.fromkeys(table))
+
+
+def flag_table_masks(present):
+    """Components 0-4 plus each subset of {5, 6, 7} that `present` holds, in the binary order of (useH_A, useY_A, useY)."""
+    out = []
+    for q in range(8):
+        extra = q << 5
+        if extra & ~int(present) == 0:
+            out.append(ENSEMBLE_BASE | extra)
+    return out
+
+
+def shapley_shares(K, value):
+    """The exact Shapley values of K players of the game v(empty) = 1/2, v(S) = value[mask of S] (a Fraction for every non-zero
+    mask below 2^K): share_i = sum over S without i of |S|! (K - |S| - 1)! / K! (v(S + i) - v(S)), as Fractions whose sum is
+    v(full) - 1/2 exactly.  No device."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= SUBSET_MAX_K:
+        raise ValueError(f"shapley_shares: K = {K!r}; 1 to {SUBSET_MAX_K} players")
+    K = int(K)
+    if set(value) != set(range(1, 1 << K)) or not all(isinstance(v, Fraction) for v in value.values()):
+        raise ValueError(f"shapley_shares: value maps every mask in [1, {1 << K}) to a Fraction")
+    v = dict(value)
+    v[0] = Fraction(1, 2)
+    fact = [math.factorial(q) for q in range(K + 1)]
+    shares = []
+    for i in range(K):
+        s = Fraction(0)
+        for S in range(1 << K):
+            if not S >> i & 1:
+                size = bin(S).count("1")
+                s += Fraction(fact[size] * fact[K - size - 1], fact[K]) * (v[S | 1 << i] - v[S])
+        shares.append(s)
+    return shares
+
+
 # mcgra_node_rank_metrics (csrc/node_rank.hip): the header's MCGRA_NODE_RANK_MAX_NIDX, the workgroup's lane count, and the
 # row-length classes (candidates per row, n_idx - 1: a row runs in the smallest class that holds it)
 NODE_RANK_MAX_NIDX = 16384
@@ -1463,6 +1567,29 @@ class AttackEngine:
                                             _p(out)))
             torch.cuda.current_stream().synchronize()
         return out
+
+    def finalize_components(self, decode_mode, H_A=None, Y_A=None, label_adj=None, out_mask=None, want_out=True):
+        """finalize with its summands kept apart (mcgra_attack_finalize_components): (out, comps, present) -- comps the
+        [8, n, n] stack in the order of ENSEMBLE_COMPONENTS (the slot of an input that is None: zeros), present the mask of the
+        slots that were written, out the float32 sum of the components of out_mask in ascending order (None: every present one;
+        then finalize's out bit for bit), or None with want_out=False.  8 n^2 floats stay on the device."""
+        dev = self.device
+        H_A = _dev_f32(H_A, dev) if H_A is not None else None
+        Y_A = _dev_f32(Y_A, dev) if Y_A is not None else None
+        label_adj = _dev_f32(label_adj, dev) if label_adj is not None else None
+        have = ENSEMBLE_BASE | (H_A is not None) << 5 | (Y_A is not None) << 6 | (label_adj is not None) << 7
+        out_mask = have if out_mask is None else int(out_mask)
+        out = torch.empty(self.n, self.n, device=dev, dtype=torch.float32) if want_out else None
+        comps = torch.empty(len(ENSEMBLE_COMPONENTS), self.n, self.n, device=dev, dtype=torch.float32)
+        present = C.c_uint(0)
+        with torch.cuda.device(dev):
+            for k in range(len(ENSEMBLE_COMPONENTS)):
+                if not have >> k & 1:
+                    comps[k].zero_()
+            check(lib.mcgra_attack_finalize_components(self._h, _stream(), int(decode_mode), _p(H_A), _p(Y_A), _p(label_adj),
+                                                       out_mask, _p(out), _p(comps), C.byref(present)))
+            torch.cuda.current_stream().synchronize()
+        return out, comps, int(present.value)
 
     def buffer(self, name):
         """Copy of a named intermediate (parity tests)."""

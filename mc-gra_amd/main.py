@@ -46,6 +46,16 @@ the share of same-class pairs among the true edges, the recovered pairs and all 
 min(15, bit_length) of a node's degree in the true graph, or an integer .npy with one class in [0, 16) per node.
 --by_class_cut split|edges|THRESHOLD (default edges; --structure's cuts) says where the recovered pairs are counted.
 --save_by_class PATH: the counts, the sums and the AUC of every block, and the class of every node.
+--ablate [table|shapley] asks which summand of modified_adj carries it.  After the loop modified_adj is a sum of up to eight
+matrices (engine.ENSEMBLE_COMPONENTS: the learned adjacency, feature_adj, the decodes of H_A1 / H_A2 / Y_A2 on the recovered graph,
+the decodes of the priors H_A and Y_A, the label adjacency); the attack keeps them apart (every prior it holds is decoded, the
+use flags only choose what modified_adj sums, so modified_adj is bit for bit what it is without the flag) and ONE pass over a
+set's pairs ranks many subset sums (engine.subset_auc).  `table` (the default): the sum in use, every present summand alone, the
+sum in use without each of its summands, and the base five with every combination of --useH_A --useY_A --useY -- the paper's
+flag table from one run.  `shapley`: every non-empty subset of the present summands and each summand's exact Shapley share of
+AUC - 1/2.  On polblogs / usair the decode branch itself depends on the use flags: there a subset's AUC is that of THIS run's
+decode mode, not of a rerun with other flags; for cora, citeseer, AIDS and brazil the flag table is the rerun's.
+--save_ablation PATH: every subset's mask, T and AUC per index set.
 --mode link_stealing (not in the reference) is the baseline every paper in this line compares with, Attack-0 of He et al.,
 "Stealing Links from Graph Neural Networks" (USENIX Security 2021): notrain_test's flow up to the priors -- no attack, nothing
 written -- then the AUC (with --ap the average precision too) of the unordered node pairs of attack, train and all scored by
@@ -75,14 +85,14 @@ if __package__ in (None, ""):          # run as a script: load the hyphenated di
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import mcgra_loader
     mcgra_loader.load()
-    from mc_gra_amd import engine, reports, utils
+    from mc_gra_amd import engine, reports, topology_attack, utils
     from mc_gra_amd.dataset import Dataset
     from mc_gra_amd.models.gcn import GCN, embedding_GCN
     from mc_gra_amd.models.gat import GAT, embedding_gat
     from mc_gra_amd.models.graphsage import graphsage, embedding_graphsage
     from mc_gra_amd.topology_attack import PGDAttack
 else:
-    from . import engine, reports, utils
+    from . import engine, reports, topology_attack, utils
     from .dataset import Dataset
     from .models.gcn import GCN, embedding_GCN
     from .models.gat import GAT, embedding_gat
@@ -96,7 +106,7 @@ import torch.nn.functional as F
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
-        for r in reports.ALL_REPORTS:
+        for r in reports.REPORT_TABLE:
             r.check(args, self.error)
         return args
 
@@ -159,6 +169,8 @@ def build_parser():
     p.add_argument('--by_class', type=str, default=argparse.SUPPRESS)          # also the AUC within the classes of labels | degree | an .npy
     p.add_argument('--by_class_cut', type=str, default=argparse.SUPPRESS)      # with --by_class: where its pairs above a cut are counted
     p.add_argument('--save_by_class', type=str, default=argparse.SUPPRESS)     # with --by_class: the per-block counts as an .npz
+    p.add_argument('--ablate', type=str, nargs='?', const='table', default=argparse.SUPPRESS)   # also the AUC of subsets of modified_adj's summands
+    p.add_argument('--save_ablation', type=str, default=argparse.SUPPRESS)     # with --ablate: every subset's T and AUC as an .npz
     return p
 
 
@@ -342,14 +354,14 @@ def log_lines(res, ctx):
     if getattr(ctx.args, "ap", False):
         lines.append(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
                      f"In Whole Graph: AP={res['ap_all']}")
-    for r in reports.ALL_REPORTS:
+    for r in reports.REPORT_TABLE:
         if r.wanted(ctx.args):
             lines += r.log(res, ctx)
     return lines + [f"current density: {res['density']}"]
 
 
 def _run(args, rank, world):
-    for r in reports.ALL_REPORTS:
+    for r in reports.REPORT_TABLE:
         r.check(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
@@ -468,12 +480,15 @@ def _run(args, rank, world):
                  idx_test, adj, features, init_adj, labels, idx_attack, num_edges, 0, epochs=args.epochs,
                  label_adj=label_adj)
     inference_adj = model.modified_adj                     # stays on the device: the three AUCs run there (main.py:247-250)
-    ctx = reports.Context(real=ad.to(inference_adj.device), inference_adj=inference_adj,
+    ctx = reports.RunContext(real=ad.to(inference_adj.device), inference_adj=inference_adj,
                           sets={"attack": idx_attack, "train": idx_train, "all": None}, n=adj.shape[0], rank=rank,
-                          other=other, versus=versus, args=args, classes=classes)
+                          other=other, versus=versus, args=args, classes=classes,
+                          components=None if not getattr(args, "ablate", None) else {
+                              "stack": model.components, "present": model.components_present, "used": model.component_mask,
+                              "decode_mode": topology_attack._decode_mode(args)})
     want_ap = getattr(args, "ap", False)
     res = base_metrics(ctx, want_ap)
-    wanted = [r for r in reports.ALL_REPORTS if r.wanted(args)]
+    wanted = [r for r in reports.REPORT_TABLE if r.wanted(args)]
     for r in wanted:        # every rank computes (as the AUCs); a report's keys exist only with its flag
         res.update(r.compute(ctx))
     res["path"] = dict(model.history.get("path", {}), world=world)

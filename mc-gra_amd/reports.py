@@ -1,13 +1,14 @@
 """The optional reports of `main.py --mode evaluate` (none is in the reference; main.py's docstring says what each flag asks):
 per report the argument check, the computation on the device, the console lines, the --save_* file and the log lines, and at
-the bottom the one ordered table of them that main.py's parser, run and log loop over: ALL_REPORTS, which is REPORTS, then
-EVERY_REPORT's hops report (two tuples that tests pin), then the reports added after them.  To add a report, add an entry to
-ALL_REPORTS.
+the bottom the one ordered table of them that main.py's parser, run and log loop over: REPORT_TABLE, which is REPORTS, then
+EVERY_REPORT's hops report, then ALL_REPORTS' by_class report (three tuples that tests pin), then the reports added after them.
+To add a report, add an entry to REPORT_TABLE.
 
 `sets` is always index set name -> node ids (None: every node); fail(message) does not return; a --save_* file is written at
 exactly the path given.  engine functions are looked up as engine.<fn> at the call."""
 import argparse
 import collections
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -22,6 +23,10 @@ CI_LEVEL = 0.95
 # other the second n x n score matrix of --versus and versus the flag as given (both None without it), classes the int64 class
 # of every node of --by_class (None without it)
 Context = collections.namedtuple("Context", "real inference_adj sets n rank other versus args classes", defaults=(None,))
+# Context (whose fields tests pin) and, last, components: what --ablate needs of the attack (None without it): {"stack" the
+# [8, n, n] summands of modified_adj on the device, "present", "used" (masks over engine.ENSEMBLE_COMPONENTS), "decode_mode"}.
+# What main.py builds; every report reads its fields by name, so either form serves the reports that came before --ablate.
+RunContext = collections.namedtuple("RunContext", Context._fields + ("components",), defaults=(None, None))
 
 
 class Report:
@@ -524,6 +529,105 @@ def save_by_class(res, ctx):
     _save_npz(ctx.args.save_by_class, **arrays)
 
 
+ABLATE_HOW = ("table", "shapley")
+
+
+def check_ablate_args(args, fail):
+    how, path = getattr(args, "ablate", None), getattr(args, "save_ablation", None)
+    if path is not None and how is None:
+        fail("--save_ablation needs --ablate")
+    if path is not None and path == "":
+        fail("--save_ablation takes the path of the .npz to write")
+    if how is not None and how not in ABLATE_HOW:
+        fail(f"--ablate takes {' or '.join(ABLATE_HOW)}, not {how!r}")
+    if how is not None and args.mode != "evaluate":
+        fail(f"--ablate ranks the subsets of the summands of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+def _mask_names(mask):
+    return tuple(nm for k, nm in enumerate(engine.ENSEMBLE_COMPONENTS) if mask >> k & 1)
+
+
+def ablation_masks(present, used, how):
+    """The masks --ablate HOW ranks: engine.ablation_masks' table, or with `shapley` every non-empty subset of the present
+    components, the subset q of the present components in ascending order at place q - 1 (the table's masks are among them)."""
+    if how != "shapley":
+        return engine.ablation_masks(present, used)
+    bits = [k for k in range(len(engine.ENSEMBLE_COMPONENTS)) if present >> k & 1]
+    return [sum(1 << k for j, k in enumerate(bits) if q >> j & 1) for q in range(1, 1 << len(bits))]
+
+
+def ablation_stats(d, present, used, decode_mode, how):
+    """One index set's dict of --ablate from engine.subset_auc's dict d over ablation_masks(present, used, how).  No device."""
+    names = engine.ENSEMBLE_COMPONENTS
+    bits = [k for k in range(len(names)) if present >> k & 1]
+    auc, P, N = dict(zip(d["masks"], d["auc"])), d["positives"], d["negatives"]
+    res = {"components": names, "present": present, "used": used, "decode_mode": decode_mode,
+           "pairs": d["pairs"], "positives": P, "negatives": N,
+           "subsets": [{"mask": q, "names": _mask_names(q), "T": t, "auc": a} for q, t, a in zip(d["masks"], d["T"], d["auc"])],
+           "auc_used": auc[used], "alone": {names[k]: auc[1 << k] for k in bits},
+           "without": {names[k]: auc[used & ~(1 << k)] for k in bits if used >> k & 1 and used != 1 << k},
+           "flag_table": [{"useH_A": bool(q >> 5 & 1), "useY_A": bool(q >> 6 & 1), "useY": bool(q >> 7 & 1), "mask": q, "auc": auc[q]}
+                          for q in engine.flag_table_masks(present)]}
+    if how == "shapley":
+        nan = float("nan")
+        res["shapley"], res["shapley_sum"] = {names[k]: nan for k in bits}, nan
+        if P and N:           # the game on the present components: player j is component bits[j]
+            T = dict(zip(d["masks"], d["T"]))
+            value = {q: Fraction(T[sum(1 << k for j, k in enumerate(bits) if q >> j & 1)], 2 * P * N)
+                     for q in range(1, 1 << len(bits))}
+            shares = engine.shapley_shares(len(bits), value)
+            res["shapley"] = {names[k]: float(s) for k, s in zip(bits, shares)}
+            res["shapley_sum"] = float(sum(shares))
+    return res
+
+
+def ablation_report(ctx):
+    """--ablate: {"ablation_<name>": ablation_stats of engine.subset_auc over the index set}: every subset in one pass."""
+    c, how = ctx.components, ctx.args.ablate
+    masks = ablation_masks(c["present"], c["used"], how)
+    return {f"ablation_{name}": ablation_stats(engine.subset_auc(ctx.real, c["stack"], masks, ix), c["present"], c["used"],
+                                               c["decode_mode"], how) for name, ix in ctx.sets.items()}
+
+
+def _ablation_text(d):
+    pairs = lambda m: " ".join(f"{k}={v}" for k, v in m.items())
+    flags = " ".join(f"{int(r['useH_A'])}{int(r['useY_A'])}{int(r['useY'])}={r['auc']}" for r in d["flag_table"])
+    return (f"used={'+'.join(_mask_names(d['used']))} auc={d['auc_used']} | alone: {pairs(d['alone'])} | "
+            f"without: {pairs(d['without'])}"), flags
+
+
+def _ablation_console(res, ctx):
+    d = res["ablation_all"]
+    lines = [f"current ablation {_ablation_text(d)[0]}"]
+    if "shapley" in d:
+        lines.append("current shapley " + " ".join(f"{k}={v}" for k, v in d["shapley"].items()))
+    return lines
+
+
+def _ablation_log(res, ctx):
+    lines = []
+    for title, d in _per_set(res, "ablation"):
+        text, flags = _ablation_text(d)
+        shapley = " | shapley: " + " ".join(f"{k}={v}" for k, v in d["shapley"].items()) if "shapley" in d else ""
+        lines.append(f"In {title}: ablation (decode mode {d['decode_mode']}) {text} | flags HA,YA,Y: {flags}{shapley}")
+    return lines
+
+
+def save_ablation(res, ctx):
+    """--save_ablation: masks (uint32) and names once; per index set T (int64) and auc (float64) of every mask, counts =
+    {pairs, positives, negatives} (int64) and shapley (float64 per component; NaN for an absent one or without `shapley`)."""
+    first = res["ablation_all"]
+    arrays = {"masks": np.asarray([r["mask"] for r in first["subsets"]], dtype=np.uint32), "names": np.asarray(first["components"])}
+    for name in ctx.sets:
+        d = res[f"ablation_{name}"]
+        arrays[f"T_{name}"] = np.asarray([r["T"] for r in d["subsets"]], dtype=np.int64)
+        arrays[f"auc_{name}"] = np.asarray([r["auc"] for r in d["subsets"]], dtype=np.float64)
+        arrays[f"counts_{name}"] = np.asarray([d["pairs"], d["positives"], d["negatives"]], dtype=np.int64)
+        arrays[f"shapley_{name}"] = np.asarray([d.get("shapley", {}).get(nm, float("nan")) for nm in d["components"]], dtype=np.float64)
+    _save_npz(ctx.args.save_ablation, **arrays)
+
+
 def _saver(flag, write):
     """write(res, ctx) when the --save_* flag names a file."""
     return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
@@ -560,10 +664,15 @@ EVERY_REPORT = REPORTS + (
     Report(flags=("hops", "hops_cut", "save_hops"), check=check_hops_args, wanted=_on("hops", given=True), compute=hops_report,
            console=_hops_console, log=_hops_log, save=_saver("save_hops", save_hops)),
 )
-# EVERY_REPORT ends with the hops report, as its tests pin it; ALL_REPORTS is what main.py's parser, run and log loop over.
+# EVERY_REPORT ends with the hops report, as its tests pin it; the by_class report follows.
 ALL_REPORTS = EVERY_REPORT + (
     Report(flags=("by_class", "by_class_cut", "save_by_class"), check=check_by_class_args, wanted=_on("by_class", given=True),
            compute=by_class_report, console=_by_class_console, log=_by_class_log, save=_saver("save_by_class", save_by_class)),
+)
+# ALL_REPORTS ends with the by_class report, as its tests pin it; REPORT_TABLE is what main.py's parser, run and log loop over.
+REPORT_TABLE = ALL_REPORTS + (
+    Report(flags=("ablate", "save_ablation"), check=check_ablate_args, wanted=_on("ablate"), compute=ablation_report,
+           console=_ablation_console, log=_ablation_log, save=_saver("save_ablation", save_ablation)),
 )
 
 
@@ -571,7 +680,7 @@ def shown_parameters(args):
     """The namespace that the log's parameter line prints: args without `ap` while --ap is off and without the flags of every
     report that is off, so that a run without a flag logs what it logged before the flag existed."""
     hidden = set() if getattr(args, "ap", False) else {"ap"}
-    for r in ALL_REPORTS:
+    for r in REPORT_TABLE:
         if not r.wanted(args):
             hidden.update(r.flags)
     return argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})

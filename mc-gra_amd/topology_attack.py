@@ -361,5 +361,21 @@ class PGDAttack(BaseAttack):
             # priors): it runs replicated, on rank 0's priors, and every rank returns the same modified_adj
             H_A = _bcast(dist, to_dev(H_A), host_staged) if H_A is not None else None
             Y_A = _bcast(dist, to_dev(Y_A), host_staged) if Y_A is not None else None
+        if getattr(args, "ablate", None):
+            # the summands kept apart (main.py --ablate): every prior this object holds and the label adjacency are decoded,
+            # whatever the use flags say; the flags choose which of them modified_adj sums (the same bits as finalize's)
+            held = []
+            for name, t, shape, given in (("H_A", self.H_A, (n, dims[emb_nlayer]), H_A),
+                                          ("Y_A", self.Y_A, (n, int(Wlin.shape[0])), Y_A)):
+                if given is None and t is not None:          # held but not used: not checked, not broadcast above
+                    if tuple(t.shape) != shape:
+                        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {shape}")
+                    given = t.detach() if plan is None else _bcast(dist, to_dev(t.detach()), host_staged)
+                held.append(given)
+            used = 0x1f | (H_A is not None) << 5 | (Y_A is not None) << 6 | (use_Y and label_adj is not None) << 7
+            out, comps, present = eng.finalize_components(_decode_mode(args), held[0], held[1], label_adj, out_mask=used)
+            self.modified_adj = out.detach()
+            self.components, self.component_mask, self.components_present = comps.detach(), used, present
+            return 0, 0, 0, 0
         self.modified_adj = eng.finalize(_decode_mode(args), H_A, Y_A, label_adj if use_Y else None).detach()
         return 0, 0, 0, 0
