@@ -654,6 +654,52 @@ int mcgra_subset_auc(void* stream, int n, const float* labels, int ld_labels,
 int mcgra_node_rank_metrics(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
                             const int64_t* idx, int64_t n_idx, int64_t* out /* device [n_idx][5] */);
 
+/* The k-nearest-neighbour graph of the scores: every selected node keeps its own k best-scored partners, and the lists are
+ * symmetrised as the union ("either end picks the other") and as the mutual graph ("both do").  A local cut, beside the global
+ * cuts of mcgra_topk_metrics and mcgra_threshold_pairs; its in-degrees measure hubness (Radovanovic, Nanopoulos and Ivanovic,
+ * JMLR 11, 2010).
+ *   - selection, candidates and ranking as mcgra_node_rank_metrics: idx, n_idx REPEAT-FREE device int64 node ids or NULL for
+ *     all n nodes in order; m = n_idx positions; for position a the candidates are the positions b != a with score
+ *     scores[idx[a]][idx[b]] (row a of the gathered submatrix without its diagonal: an asymmetric matrix is ranked by rows);
+ *     float32 comparison, -0.0 == +0.0, subnormals and negative scores ordinary values; best first = score descending, ties by
+ *     ascending position b (the position in idx, not the node id);
+ *   - L_k(a) = the first k positions of row a's ranking.  D: the arc a -> b iff b is in L_k(a) (every out-degree is k);
+ *     U: {a, b} iff a -> b or b -> a; Mu: {a, b} iff both; with labels G: {a, b}, a > b, iff labels[idx[a]][idx[b]] == 1 (the
+ *     strict lower triangle, as mcgra_graph_structure reads it);
+ *   - header (host int64[8]) = {pairs m (m - 1) / 2, k, E_U, E_M, E_G, H_D, H_U, H_M}: the edge counts of U, Mu and G, the
+ *     arcs of D whose pair is an edge of G, the edges of U and of Mu that are edges of G; the last four -1 without labels;
+ *   - out (device int64 [m][7]), row a = {in, d_U, d_M, d_G, h_D, h_U, h_M}: in = |{b : b -> a}|, the degrees in U, Mu and G,
+ *     h_D = |L_k(a) & N_G(a)|, the neighbours in U / Mu that are neighbours in G; the last four -1 without labels.
+ *     sum in = m k, d_M = k + in - d_U, E_U + E_M = m k, H_D = H_U + H_M;
+ *   - lists (device int32 [m][k], may be NULL), row a = L_k(a) as positions, in ranking order;
+ *   - the edge list of U in ASCENDING PACKED POSITION a (a - 1) / 2 + b (a > b), capacity as mcgra_threshold_pairs: pairs
+ *     (device int64 [cap][2]) = u = idx[a], v = idx[b]; pair_scores (device [cap], may be NULL) = scores[u][v], the bits as
+ *     stored; kind (device uint8 [cap], may be NULL): bit 0 a -> b, bit 1 b -> a, 3 mutual; hits (device uint8 [cap], may be
+ *     NULL; needs labels) = 1 where {a, b} is an edge of G.  cap == 0 with pairs NULL asks for no list.  E_U > cap: MCGRA_ENOMEM
+ *     with header, out and lists written, nothing in the four list buffers, and mcgra_last_error() naming what is needed;
+ *     cap = m k always suffices.  The order comes from per-node counts and one scan, never from atomics;
+ *   - n_idx from 2 (MCGRA_EINVAL below) up to MCGRA_KNN_MAX_NIDX (one workgroup selects one row in LDS; MCGRA_ENOSUP beyond);
+ *     1 <= k <= m - 1, else MCGRA_EINVAL; k above MCGRA_KNN_MAX_K: MCGRA_ENOSUP;
+ *   - a candidate score that is NaN or +-inf, given labels a selected label (strict lower triangle) other than 0 or 1, a
+ *     repeated or out-of-range id: MCGRA_EINVAL; the diagonal and the unselected rows and columns are not looked at.  After any
+ *     refusal nothing has been written to header, out, lists or the list buffers;
+ *   - header, out or scores NULL, an ld below n, the limits on n_idx and k, cap < 0, cap > 0 with pairs NULL, hits without
+ *     labels: refused before any HIP call;
+ *   - integer arithmetic and key comparisons only: the same bits on every call, whatever order the workgroups run in.
+ * A row is selected (four radix rounds over its keys in LDS), not sorted; only the k winners are sorted, and only for lists.
+ * Synchronises `stream`.  Device scratch: two bit matrices of m x ceil(m / 64) 64-bit words and a third with labels (96 MB at
+ * the capacity), 12 bytes per selected node, and 4 bytes per node of the graph when idx is given; a failed allocation:
+ * MCGRA_ENOMEM. */
+#define MCGRA_KNN_MAX_NIDX 16384
+#define MCGRA_KNN_MAX_K 1024
+int mcgra_knn_graph(void* stream, int n, const float* scores, int ld_scores,
+                    const float* labels /* may be NULL */, int ld_labels,
+                    const int64_t* idx, int64_t n_idx, int64_t k,
+                    int64_t* header /* host[8] */, int64_t* out /* device [n_idx][7] */,
+                    int32_t* lists /* device [n_idx][k], may be NULL */, int64_t cap,
+                    int64_t* pairs /* device [cap x 2]: u, v */, float* pair_scores /* device [cap], may be NULL */,
+                    uint8_t* kind /* device [cap], may be NULL */, uint8_t* hits /* device [cap], may be NULL; needs labels */);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

@@ -42,7 +42,7 @@ SYMBOLS = [
     "mcgra_rank_metrics", "mcgra_decode_rank_metrics",
     "mcgra_topk_metrics", "mcgra_top_pairs",
     "mcgra_rank_curves",
-    "mcgra_node_rank_metrics",
+    "mcgra_node_rank_metrics", "mcgra_knn_graph",
     "mcgra_two_means_split", "mcgra_threshold_pairs",
     "mcgra_auc_delong", "mcgra_auc_delong_paired",
     "mcgra_auc_node_jackknife",
@@ -136,6 +136,8 @@ def _load():
         "mcgra_rank_curves": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.c_int64, ip, ip, fp, ip, ip, fp,
                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)],
         "mcgra_node_rank_metrics": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, ip],
+        "mcgra_knn_graph": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int64, C.POINTER(C.c_int64), ip, ip,
+                            C.c_int64, ip, fp, vp, vp],
         "mcgra_two_means_split": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.POINTER(C.c_int64),
                                   C.POINTER(C.c_float), C.POINTER(C.c_float)],
         "mcgra_threshold_pairs": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_float, C.c_int64, ip, fp, vp,

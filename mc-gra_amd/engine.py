@@ -1169,6 +1169,102 @@ def node_rank_metrics(real, pred, idx=None):
     return res
 
 
+# mcgra_knn_graph (csrc/knn_graph.hip): the header's MCGRA_KNN_MAX_NIDX and MCGRA_KNN_MAX_K, the row-length classes of the
+# select (selected nodes per row: a row runs in the smallest class that holds it), the names of header[8] and of out[m][7]
+KNN_MAX_NIDX = 16384
+KNN_MAX_K = 1024
+KNN_CLASSES = (1024, 4096, 16384)
+KNN_HEADER = ("pairs", "k", "E_U", "E_M", "E_G", "H_D", "H_U", "H_M")
+KNN_COLUMNS = ("in", "d_U", "d_M", "d_G", "h_D", "h_U", "h_M")
+KNN_IN_BINS = ((0, 0),) + NODE_RANK_DEGREE_BINS
+
+
+def knn_graph_stats(header, cols):
+    """The doubles of knn_graph from its integers: header = {"pairs", "k", "E_U", "E_M", "E_G", "H_D", "H_U", "H_M"} and cols =
+    {"in", "d_U", "d_M", ...} (sequences over the m positions; only the first three are read).  No device is involved; every
+    double is one float64 division of exact integers, NaN on a zero denominator (and without the truth, E_G == -1, where "hits"
+    is None).  Returns {"nodes", "k", "directed", "union", "mutual", "hubness"}:
+      each graph = {"edges" (the m k arcs for "directed"), "positives" (E_G; 2 E_G for "directed": a true edge can be found
+      from either end), "hits" (H_D / H_U / H_M), "precision" hits / edges, "recall" hits / positives, "f1" 2 hits /
+      (edges + positives)}, "union" and "mutual" also "isolated", their nodes of degree 0;
+      "hubness" = {"max_in", "orphans" (in == 0: in nobody's list), "skewness" of the in-degrees (Radovanovic et al., JMLR
+      2010) = m3 / m2^1.5 with m2 = sum (in - k)^2 / m, m3 = sum (in - k)^3 / m (the mean of in is exactly k), computed as
+      sign(S3) sqrt(S3^2 m / S2^3) from the integer sums: one rational, one rounding, one square root; NaN when m2 == 0,
+      "in_hist" a list of (lo, hi, nodes) over in = 0, 1, 2, 3-4, 5-8, 9-16, 17-32, 33 and more (hi None)}."""
+    nan = float("nan")
+    h = {q: int(header[q]) for q in KNN_HEADER}
+    ind, dU, dM = (np.asarray(cols[q], dtype=np.int64).reshape(-1) for q in ("in", "d_U", "d_M"))
+    m, k = len(ind), h["k"]
+    if m < 2 or len(dU) != m or len(dM) != m or h["pairs"] != m * (m - 1) // 2 or int(ind.sum()) != m * k:
+        raise ValueError("knn_graph_stats: the columns do not belong to the header")
+    have = h["E_G"] >= 0
+
+    def graph(edges, positives, hits):
+        if not have:
+            return {"edges": edges, "positives": None, "hits": None, "precision": nan, "recall": nan, "f1": nan}
+        return {"edges": edges, "positives": positives, "hits": hits, "precision": _ratio(hits, edges),
+                "recall": _ratio(hits, positives), "f1": _ratio(2 * hits, edges + positives)}
+
+    res = {"nodes": m, "k": k, "directed": graph(m * k, 2 * h["E_G"], h["H_D"]),
+           "union": graph(h["E_U"], h["E_G"], h["H_U"]), "mutual": graph(h["E_M"], h["E_G"], h["H_M"])}
+    res["union"]["isolated"] = int((dU == 0).sum())
+    res["mutual"]["isolated"] = int((dM == 0).sum())
+    dev = ind - k                      # int64 holds the sum of cubes while m^4 < 2^63 (2^56 at the capacity); else Python integers
+    if m > 40000:
+        dev = dev.astype(object)
+    S2, S3 = int((dev * dev).sum()), int((dev * dev * dev).sum())
+    res["hubness"] = {"max_in": int(ind.max()), "orphans": int((ind == 0).sum()),
+                      "skewness": math.copysign(math.sqrt(S3 * S3 * m / S2 ** 3), S3) if S2 else nan,
+                      "in_hist": [(lo, hi, int(((ind >= lo) & (ind <= (ind.max() if hi is None else hi))).sum()))
+                                  for lo, hi in KNN_IN_BINS]}
+    return res
+
+
+@_on_operand_device
+def knn_graph(pred, k, idx=None, real=None, lists=False, edges=False):
+    """The k-nearest-neighbour graph of the scores (mcgra_knn_graph): a local cut beside the global cuts of topk_metrics and
+    threshold_pairs.  For each position a of idx (REPEAT-FREE node ids; None: all nodes in order) the candidates are the positions
+    b != a with score pred[idx[a], idx[b]] -- row a of the gathered submatrix without its diagonal, also for an asymmetric pred --
+    ranked best first as node_rank_metrics does: score descending (float32 values, -0.0 == +0.0), ties by ascending position b.
+    L_k(a) is the first k of them; D has the arc a -> b iff b is in L_k(a), U the edge {a, b} iff either arc exists, Mu iff both;
+    with real, G has {a, b}, a > b, iff real[idx[a], idx[b]] == 1.  1 <= k <= min(m - 1, KNN_MAX_K) and m <= KNN_MAX_NIDX
+    (McgraError for k outside [1, m - 1], McgraNotSupported beyond the two capacities).  Returns {"k", "nodes" (m), the header
+    integers "pairs", "E_U", "E_M", "E_G", "H_D", "H_U", "H_M" (edges of U, Mu, G; arcs of D, edges of U and of Mu that are edges
+    of G; -1 for the last four without real), the columns "in", "d_U", "d_M", "d_G", "h_D", "h_U", "h_M" (device int64 [m], row =
+    position in idx: in-degree in D, degrees in U, Mu, G, and how many of L_k(a), of the U- and of the Mu-neighbours are
+    G-neighbours; -1 for the last four without real), "stats" (knn_graph_stats of them)}; with lists also "lists" (device int32
+    [m, k]: L_k(a) as positions, in ranking order); with edges also U's edge list in ascending packed position a (a - 1) / 2 + b:
+    "pairs_list" [E_U, 2] int64 = (idx[a], idx[b]), a > b, "scores" [E_U] float32 (the bits as stored), "kind" [E_U] uint8 (bit 0
+    a -> b, bit 1 b -> a, 3 mutual) and "hits" [E_U] bool (None without real).  Exact integers from the device (a radix select of
+    each row in LDS, bit matrices, popcounts), the same bits on every call.  McgraError for a repeated or out-of-range id, a
+    candidate NaN / inf score or a selected label other than 0 / 1."""
+    pred, real, ix, n, rows = _ranked(idx, pred, real)
+    k, dev = int(k), pred.device
+    header = (C.c_int64 * 8)()
+    out = torch.empty(max(rows, 0), 7, device=dev, dtype=torch.int64)
+    ok = 2 <= rows <= KNN_MAX_NIDX and 1 <= k <= min(rows - 1, KNN_MAX_K)      # otherwise the entry refuses: allocate nothing
+    nn = torch.empty(rows, k, device=dev, dtype=torch.int32) if lists and ok else None
+    cap = rows * k if edges and ok else 0
+    pairs = torch.empty(cap, 2, device=dev, dtype=torch.int64) if cap else None
+    scores = torch.empty(cap, device=dev, dtype=torch.float32) if cap else None
+    kind = torch.empty(cap, device=dev, dtype=torch.uint8) if cap else None
+    hits = torch.empty(cap, device=dev, dtype=torch.uint8) if cap and real is not None else None
+    check(lib.mcgra_knn_graph(_stream(), n, _p(pred), pred.stride(0), _p(real), real.stride(0) if real is not None else 0,
+                              _p(ix), rows, k, header, _p(out), _p(nn), cap, _p(pairs), _p(scores), _p(kind), _p(hits)))
+    cols = out.t().contiguous()
+    res = {"k": k, "nodes": rows}
+    res.update(zip(KNN_HEADER, (int(v) for v in header)))
+    res.update(zip(KNN_COLUMNS, cols))
+    res["stats"] = knn_graph_stats(res, dict(zip(KNN_COLUMNS[:3], cols[:3].cpu().numpy())))
+    if lists:
+        res["lists"] = nn
+    if edges:
+        E = res["E_U"]
+        res.update({"pairs_list": pairs[:E], "scores": scores[:E], "kind": kind[:E],
+                    "hits": None if hits is None else hits[:E].view(torch.bool)})
+    return res
+
+
 def _curve_first_cap(entries, drop_intermediate):
     """The first attempt's capacity: levels + 1 <= entries + 1 always suffices, and without drop_intermediate little less
     does; with it a curve keeps the corners only, so an eighth of the entries (at least 2^20 points) is tried first and

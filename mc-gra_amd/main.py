@@ -56,6 +56,12 @@ flag table from one run.  `shapley`: every non-empty subset of the present summa
 AUC - 1/2.  On polblogs / usair the decode branch itself depends on the use flags: there a subset's AUC is that of THIS run's
 decode mode, not of a rerun with other flags; for cora, citeseer, AIDS and brazil the flag table is the rerun's.
 --save_ablation PATH: every subset's mask, T and AUC per index set.
+--knn K asks for the recovered graph as a LOCAL cut: every node of a set keeps its own K best-scored partners (its row of
+modified_adj; engine.knn_graph), and the lists are symmetrised as the union (either end picks the other) and as the mutual graph
+(both do).  Each is scored against the true graph, beside the F1 of --topk's global cut at exactly the same number of edges,
+with the nodes either leaves without an edge and the hubness of the lists: the largest in-degree, the nodes in nobody's list and
+the skewness of the in-degrees.  K = 0 takes each set's own mean true degree, rounded; K is clamped to the set's size less one
+and to 1024.  --save_knn PATH: per node the in-degree, the degrees and the hits; the whole graph's union as an edge list.
 --mode link_stealing (not in the reference) is the baseline every paper in this line compares with, Attack-0 of He et al.,
 "Stealing Links from Graph Neural Networks" (USENIX Security 2021): notrain_test's flow up to the priors -- no attack, nothing
 written -- then the AUC (with --ap the average precision too) of the unordered node pairs of attack, train and all scored by
@@ -106,7 +112,7 @@ import torch.nn.functional as F
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
-        for r in reports.REPORT_TABLE:
+        for r in reports.EVALUATE_REPORTS:
             r.check(args, self.error)
         return args
 
@@ -171,6 +177,8 @@ def build_parser():
     p.add_argument('--save_by_class', type=str, default=argparse.SUPPRESS)     # with --by_class: the per-block counts as an .npz
     p.add_argument('--ablate', type=str, nargs='?', const='table', default=argparse.SUPPRESS)   # also the AUC of subsets of modified_adj's summands
     p.add_argument('--save_ablation', type=str, default=argparse.SUPPRESS)     # with --ablate: every subset's T and AUC as an .npz
+    p.add_argument('--knn', type=int, default=argparse.SUPPRESS)               # also the k-nearest-neighbour graphs of the scores
+    p.add_argument('--save_knn', type=str, default=argparse.SUPPRESS)          # with --knn: the per-node columns and the union's edges as an .npz
     return p
 
 
@@ -354,14 +362,14 @@ def log_lines(res, ctx):
     if getattr(ctx.args, "ap", False):
         lines.append(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
                      f"In Whole Graph: AP={res['ap_all']}")
-    for r in reports.REPORT_TABLE:
+    for r in reports.EVALUATE_REPORTS:
         if r.wanted(ctx.args):
             lines += r.log(res, ctx)
     return lines + [f"current density: {res['density']}"]
 
 
 def _run(args, rank, world):
-    for r in reports.REPORT_TABLE:
+    for r in reports.EVALUATE_REPORTS:
         r.check(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
@@ -488,7 +496,7 @@ def _run(args, rank, world):
                               "decode_mode": topology_attack._decode_mode(args)})
     want_ap = getattr(args, "ap", False)
     res = base_metrics(ctx, want_ap)
-    wanted = [r for r in reports.REPORT_TABLE if r.wanted(args)]
+    wanted = [r for r in reports.EVALUATE_REPORTS if r.wanted(args)]
     for r in wanted:        # every rank computes (as the AUCs); a report's keys exist only with its flag
         res.update(r.compute(ctx))
     res["path"] = dict(model.history.get("path", {}), world=world)

@@ -1,8 +1,9 @@
 """The optional reports of `main.py --mode evaluate` (none is in the reference; main.py's docstring says what each flag asks):
 per report the argument check, the computation on the device, the console lines, the --save_* file and the log lines, and at
 the bottom the one ordered table of them that main.py's parser, run and log loop over: REPORT_TABLE, which is REPORTS, then
-EVERY_REPORT's hops report, then ALL_REPORTS' by_class report (three tuples that tests pin), then the reports added after them.
-To add a report, add an entry to REPORT_TABLE.
+EVERY_REPORT's hops report, then ALL_REPORTS' by_class report, then the ablate report (four tuples that tests pin); what main.py
+loops over is EVALUATE_REPORTS, which is REPORT_TABLE and then the reports added after it.
+To add a report, add an entry to EVALUATE_REPORTS.
 
 `sets` is always index set name -> node ids (None: every node); fail(message) does not return; a --save_* file is written at
 exactly the path given.  engine functions are looked up as engine.<fn> at the call."""
@@ -628,6 +629,77 @@ def save_ablation(res, ctx):
     _save_npz(ctx.args.save_ablation, **arrays)
 
 
+def check_knn_args(args, fail):
+    knn, path = getattr(args, "knn", None), getattr(args, "save_knn", None)
+    if path is not None and knn is None:
+        fail("--save_knn needs --knn")
+    if path is not None and path == "":
+        fail("--save_knn takes the path of the .npz to write")
+    if knn is not None and knn < 0:
+        fail("--knn takes K >= 0 (0: each index set's own mean true degree)")
+    if knn is not None and args.mode != "evaluate":
+        fail(f"--knn keeps each node's own k best partners in the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
+
+
+def knn_k(K, m, P):
+    """The k of one index set of m nodes and P true edges for --knn K: K >= 1 as given; K = 0 the set's mean true degree 2 P / m
+    rounded half up, in integers, at least 1; either clamped to min(m - 1, engine.KNN_MAX_K)."""
+    k = K if K >= 1 else max(1, (4 * P + m) // (2 * m))
+    return min(k, m - 1, engine.KNN_MAX_K)
+
+
+def knn_report(ctx):
+    """--knn K: {"knn_<name>": per index set the stats of engine.knn_graph at knn_k, with k, nodes, pairs, positives, the seven
+    columns (numpy int64, for --save_knn) and global_f1_union / global_f1_mutual, the F1 of engine.topk_metrics -- the global
+    cut -- at exactly the union's and the mutual graph's edge counts (NaN at 0 edges)}."""
+    real, pred, out = ctx.real, ctx.inference_adj, {}
+    for name, ix in ctx.sets.items():
+        m = ctx.n if ix is None else len(ix)
+        if m > engine.KNN_MAX_NIDX:
+            raise SystemExit(f"--knn: the index set `{name}` has {m} nodes; engine.knn_graph takes at most {engine.KNN_MAX_NIDX}")
+        P = engine.topk_metrics(real, pred, 0, ix)["positives"]
+        g = engine.knn_graph(pred, knn_k(ctx.args.knn, m, P), ix, real)
+        f1_at = lambda E: engine.topk_metrics(real, pred, E, ix)["f1"] if E else float("nan")
+        out[f"knn_{name}"] = {"stats": g["stats"], "k": g["k"], "nodes": m, "pairs": g["pairs"], "positives": P,
+                              "global_f1_union": f1_at(g["E_U"]), "global_f1_mutual": f1_at(g["E_M"]),
+                              "columns": {q: g[q].cpu().numpy() for q in engine.KNN_COLUMNS}}
+    return out
+
+
+def _knn_text(d):
+    q = d["stats"]
+    u, mu, hub = q["union"], q["mutual"], q["hubness"]
+    return (f"k={d['k']} union f1={u['f1']} (edges={u['edges']}, isolated={u['isolated']}; global f1={d['global_f1_union']}) "
+            f"mutual f1={mu['f1']} (edges={mu['edges']}, isolated={mu['isolated']}; global f1={d['global_f1_mutual']}) "
+            f"max_in={hub['max_in']} orphans={hub['orphans']} skew={hub['skewness']}")
+
+
+def _knn_log(res, ctx):
+    lines = []
+    for title, d in _per_set(res, "knn"):
+        q = d["stats"]
+        lines.append(f"In {title}: knn {_knn_text(d)} | nodes={d['nodes']} positives={d['positives']} "
+                     f"lists P={q['directed']['precision']} R={q['directed']['recall']} "
+                     f"union P={q['union']['precision']} R={q['union']['recall']} "
+                     f"mutual P={q['mutual']['precision']} R={q['mutual']['recall']}")
+    return lines
+
+
+def save_knn(res, ctx):
+    """--save_knn: per index set nodes, k and the seven int64 columns of engine.knn_graph; for the whole graph the union's edge
+    list in packed order: pairs, scores, kind (bit 0 a -> b, bit 1 b -> a) and hits."""
+    arrays = {}
+    for name, ix in ctx.sets.items():
+        d = res[f"knn_{name}"]
+        arrays[f"nodes_{name}"] = np.arange(ctx.n, dtype=np.int64) if ix is None else np.asarray(ix, dtype=np.int64)
+        arrays[f"k_{name}"] = np.int64(d["k"])
+        arrays.update({f"{q}_{name}": np.asarray(d["columns"][q], dtype=np.int64) for q in engine.KNN_COLUMNS})
+    g = engine.knn_graph(ctx.inference_adj, res["knn_all"]["k"], None, ctx.real, edges=True)
+    arrays.update({"pairs": g["pairs_list"].cpu().numpy(), "scores": g["scores"].cpu().numpy(), "kind": g["kind"].cpu().numpy(),
+                   "hits": g["hits"].cpu().numpy()})
+    _save_npz(ctx.args.save_knn, **arrays)
+
+
 def _saver(flag, write):
     """write(res, ctx) when the --save_* flag names a file."""
     return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
@@ -669,10 +741,15 @@ ALL_REPORTS = EVERY_REPORT + (
     Report(flags=("by_class", "by_class_cut", "save_by_class"), check=check_by_class_args, wanted=_on("by_class", given=True),
            compute=by_class_report, console=_by_class_console, log=_by_class_log, save=_saver("save_by_class", save_by_class)),
 )
-# ALL_REPORTS ends with the by_class report, as its tests pin it; REPORT_TABLE is what main.py's parser, run and log loop over.
+# ALL_REPORTS ends with the by_class report, as its tests pin it; the ablate report follows.
 REPORT_TABLE = ALL_REPORTS + (
     Report(flags=("ablate", "save_ablation"), check=check_ablate_args, wanted=_on("ablate"), compute=ablation_report,
            console=_ablation_console, log=_ablation_log, save=_saver("save_ablation", save_ablation)),
+)
+# REPORT_TABLE ends with the ablate report, as its tests pin it; EVALUATE_REPORTS is what main.py's parser, run and log loop over.
+EVALUATE_REPORTS = REPORT_TABLE + (
+    Report(flags=("knn", "save_knn"), check=check_knn_args, wanted=_on("knn", given=True), compute=knn_report,
+           console=lambda res, ctx: [f"current knn {_knn_text(res['knn_all'])}"], log=_knn_log, save=_saver("save_knn", save_knn)),
 )
 
 
@@ -680,7 +757,7 @@ def shown_parameters(args):
     """The namespace that the log's parameter line prints: args without `ap` while --ap is off and without the flags of every
     report that is off, so that a run without a flag logs what it logged before the flag existed."""
     hidden = set() if getattr(args, "ap", False) else {"ap"}
-    for r in REPORT_TABLE:
+    for r in EVALUATE_REPORTS:
         if not r.wanted(args):
             hidden.update(r.flags)
     return argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
