@@ -700,6 +700,54 @@ int mcgra_knn_graph(void* stream, int n, const float* scores, int ld_scores,
                     int64_t* pairs /* device [cap x 2]: u, v */, float* pair_scores /* device [cap], may be NULL */,
                     uint8_t* kind /* device [cap], may be NULL */, uint8_t* hits /* device [cap], may be NULL; needs labels */);
 
+/* Which edges leak: every true edge's own placement among the non-edges, by how deep the edge sits in the TRUE graph -- the
+ * common neighbours of its two ends (its embeddedness) and the smaller of their degrees -- as exact integers per stratum and,
+ * on request, edge by edge.  The positives' side of what mcgra_hop_auc does for the non-edges.
+ *   - candidates, selection, comparison and checks as mcgra_auc_delong: idx, n_idx REPEAT-FREE device int64 node ids or NULL for
+ *     all n nodes; the m = n_idx (n_idx - 1) / 2 unordered pairs of positions a > b with score scores[idx[a]][idx[b]] and label
+ *     labels[idx[a]][idx[b]]; nothing outside the selected strict lower triangle is looked at; scores compare as float32 values,
+ *     -0.0 == +0.0;
+ *   - G is the graph on the selected positions whose edges are the candidates of label 1 (mcgra_graph_structure's G), the INDUCED
+ *     subgraph: a neighbour that is not selected does not exist.  For every edge e = {a, b} of G:
+ *       a_e   2 #{non-edges that score lower} + #{non-edges that score the same}, in [0, 2 N]: mcgra_auc_delong's placement of a
+ *             positive against ALL N non-edges of the selection
+ *       c_e   |N_G(a) & N_G(b)|, the triangles of G through the edge; its class ec = min(c_e, 15)
+ *       d_e   min(deg_G(a), deg_G(b)); its class dc = min(15, bit_length(d_e)): 1, 2-3, 4-7, ..., 16384 and more.  dc >= 1 for
+ *             every edge, so the rows dc = 0 stay zero;
+ *   - header (host int64[6]) = {m, P, N, T, above_pos, above_neg}: T = the sum of the a_e = mcgra_auc_delong's T on the same
+ *     input; above_* = the candidates of label 1 / 0 with score >= threshold, mcgra_threshold_pairs' comparison (-0.0 >= +0.0
+ *     holds, +-inf are allowed);
+ *   - table (host int64 [16][16][3]), cell (ec, dc) = {P, T, above} over the edges of the cell: the P sum to P, the T to T, the
+ *     above to above_pos; an edge class's AUC against all non-edges is T_cell / (2 P_cell N).  P == 0 or N == 0: every T is 0;
+ *   - the edges in ASCENDING PACKED POSITION a (a - 1) / 2 + b, capacity as mcgra_threshold_pairs: pairs (device int64 [cap][2])
+ *     = u = idx[a], v = idx[b]; and, each of which may be NULL, pair_scores (device [cap]) = scores[u][v], the bits as stored;
+ *     placement (device int64 [cap]) = a_e; common (device int32 [cap]) = c_e, uncapped; deg (device int32 [cap][2]) =
+ *     deg_G(a), deg_G(b).  cap == 0 with every column NULL asks for the integers alone.  0 < cap < P: MCGRA_ENOMEM with header
+ *     and table written, nothing in the columns, and mcgra_last_error() naming what is needed (header[1]); rows past P are not
+ *     written.  The order comes from a sort of the edges' positions, never from atomics;
+ *   - no overflow: T_cell <= 2 P_cell N < 2^63 for n_idx <= 65 535; c_e, d_e < 2^16;
+ *   - header or table NULL, a matrix NULL, an ld below n, a NaN threshold, cap < 0, cap > 0 with pairs NULL, cap == 0 with a
+ *     column given, n_idx (n when idx is NULL) below 2: MCGRA_EINVAL; n_idx above 65 535: MCGRA_ENOSUP.  These run before any HIP
+ *     call.  A selected score that is NaN or +-inf, a selected label other than 0 or 1, a repeated or out-of-range id:
+ *     MCGRA_EINVAL.  After any of these refusals nothing has been written to header, table or the columns and
+ *     mcgra_last_error() names the cause;
+ *   - integer arithmetic only on the device (a bit matrix built by ballots with one writer per word, AND + popcount, two radix
+ *     sorts, integer counts and degrees merged by integer atomics): the same bits on every call; header and table are the same under any
+ *     permutation of idx, the columns hold the same rows.
+ * Synchronises `stream`.
+ * Device scratch: one bit matrix of n_idx rows of ceil(n_idx / 64) 64-bit words (13 MB at n_idx = 10 000, 537 MB at the
+ * capacity; MCGRA_ENOMEM when that cannot be allocated), 28 bytes per candidate of label 1 (its key, the sort's second buffer,
+ * two 4-byte counts, their 8-byte running sum, its packed ends), 4 bytes per selected node, about 3 MB, and 4 bytes per node of
+ * the graph when idx is given. */
+#define MCGRA_EXPOSURE_CLASSES 16
+int mcgra_edge_exposure(void* stream, int n, const float* labels, int ld_labels, const float* scores, int ld_scores,
+                        const int64_t* idx, int64_t n_idx, float threshold, int64_t cap,
+                        int64_t* pairs /* device [cap x 2]: u, v */, float* pair_scores /* device [cap], may be NULL */,
+                        int64_t* placement /* device [cap], may be NULL */, int32_t* common /* device [cap], may be NULL */,
+                        int32_t* deg /* device [cap x 2], may be NULL */,
+                        int64_t* header /* host[6]: m, P, N, T, above_pos, above_neg */,
+                        int64_t* table /* host [16][16][3]: cell (ec, dc) = {P, T, above} */);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

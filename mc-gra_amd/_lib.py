@@ -47,7 +47,7 @@ SYMBOLS = [
     "mcgra_auc_delong", "mcgra_auc_delong_paired",
     "mcgra_auc_node_jackknife",
     "mcgra_graph_structure",
-    "mcgra_hop_auc",
+    "mcgra_hop_auc", "mcgra_edge_exposure",
     "mcgra_class_auc",
     "mcgra_subset_auc", "mcgra_attack_finalize_components",
     "mcgra_pair_metric_name", "mcgra_pair_distance_scores", "mcgra_pair_distance_rank_metrics",
@@ -147,6 +147,8 @@ def _load():
         "mcgra_auc_node_jackknife": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.POINTER(C.c_uint64), ip],
         "mcgra_graph_structure": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_float, C.POINTER(C.c_int64), ip],
         "mcgra_hop_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_int, C.c_float, C.POINTER(C.c_int64)],
+        "mcgra_edge_exposure": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, C.c_float, C.c_int64, ip, fp, ip, vp, vp,
+                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
         "mcgra_class_auc": [vp, C.c_int, fp, C.c_int, fp, C.c_int, ip, C.c_int64, ip, C.c_int, C.POINTER(C.c_uint8), C.c_int,
                             C.c_float, C.POINTER(C.c_int64)],
         "mcgra_subset_auc": [vp, C.c_int, fp, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, ip, C.c_int64,

@@ -875,6 +875,106 @@ def hop_auc(real, pred, idx=None, hops=3, threshold=None):
     return hop_auc_stats([out[3 * c:3 * c + 3] for c in range(H + 1)], H, threshold)
 
 
+EXPOSURE_CLASSES = 16                              # MCGRA_EXPOSURE_CLASSES (include/mcgra.h)
+EXPOSURE_MAX_NIDX = 65535                          # the capacity of the placement entries
+EXPOSURE_FIRST_CAP = 8                             # edge_exposure(edges=True) first allocates this many rows per selected node
+EXPOSURE_HEADER = ("pairs", "positives", "negatives", "T", "above_pos", "above_neg")
+# the classes of an edge: ec = min(common neighbours, 15); dc = min(15, bit_length(min degree))
+EXPOSURE_COMMON_NAMES = tuple(str(c) for c in range(EXPOSURE_CLASSES - 1)) + (f"{EXPOSURE_CLASSES - 1}+",)
+EXPOSURE_DEGREE_NAMES = ("0", "1") + tuple(f"{1 << (c - 1)}-{(1 << c) - 1}" for c in range(2, EXPOSURE_CLASSES - 1)) + \
+    (f"{1 << (EXPOSURE_CLASSES - 2)}+",)
+
+
+def edge_exposure_stats(header, table):
+    """The doubles of edge_exposure from its integers: header = mcgra_edge_exposure's six (m, P, N, T, above_pos, above_neg),
+    table its 16 x 16 x 3 cells (ec, dc) -> (count, T, above) over the true edges with ec = min(common neighbours, 15) and
+    dc = min(15, bit_length(min degree)).  No device is involved; every double is the correctly rounded quotient of two Python
+    integers, NaN on a zero denominator.  Returns {"pairs", "positives" (P), "negatives" (N), "T", "above_pos", "above_neg",
+    "auc_pooled" T / (2 P N) (auc_delong's "auc" bit for bit), "recall" above_pos / P, "precision" above_pos / (above_pos +
+    above_neg), the marginals "by_embeddedness" and "by_degree", each {"names" (EXPOSURE_COMMON_NAMES: "0" ... "14", "15+";
+    EXPOSURE_DEGREE_NAMES: "0", "1", "2-3", "4-7", ..., "16384+") and as tuples over the 16 classes "count", "T", "above", "auc"
+    T_c / (2 count_c N): the class's edges against ALL non-edges, "recall" above_c / count_c, "share" count_c / P, "lift" auc_c -
+    auc_pooled = (T_c P - T count_c) / (2 count_c P N)}, and "cells", the non-empty cells of the joint table in (ec, dc) order:
+    {"ec", "dc", "common", "degree" (the two names), "count", "T", "above", "auc", "recall", "share"}}."""
+    nan = float("nan")
+    K = EXPOSURE_CLASSES
+    hd = tuple(int(v) for v in header)
+    tb = tuple(tuple(tuple(int(v) for v in cell) for cell in row) for row in table)
+    if len(hd) != 6 or min(hd) < 0 or len(tb) != K or any(len(row) != K or any(len(cell) != 3 or min(cell) < 0 for cell in row)
+                                                          for row in tb):
+        raise ValueError(f"edge_exposure_stats: six header integers and {K} x {K} x 3 table integers, none negative")
+    m, P, N, T, above_pos, above_neg = hd
+    sums = tuple(sum(cell[q] for row in tb for cell in row) for q in range(3))
+    if m != P + N or sums != (P, T, above_pos):
+        raise ValueError(f"edge_exposure_stats: the cells sum to {sums}; the header says {(P, T, above_pos)} of {m} = {P} + {N}")
+
+    def doubles(count, t, above):
+        return {"auc": t / (2 * count * N) if count and N else nan, "recall": _ratio(above, count), "share": _ratio(count, P)}
+
+    def marginal(names, cells_of):
+        rows = [tuple(sum(cell[q] for cell in cells_of(c)) for q in range(3)) for c in range(K)]
+        d = [doubles(*r) for r in rows]
+        res = {"names": names, "count": tuple(r[0] for r in rows), "T": tuple(r[1] for r in rows), "above": tuple(r[2] for r in rows)}
+        res.update({q: tuple(x[q] for x in d) for q in ("auc", "recall", "share")})
+        res["lift"] = tuple((t * P - T * c) / (2 * c * P * N) if c and N else nan for c, t, _ in rows)
+        return res
+
+    res = dict(zip(EXPOSURE_HEADER, hd))
+    res.update({"auc_pooled": T / (2 * P * N) if P and N else nan, "recall": _ratio(above_pos, P),
+                "precision": _ratio(above_pos, above_pos + above_neg),
+                "by_embeddedness": marginal(EXPOSURE_COMMON_NAMES, lambda c: tb[c]),
+                "by_degree": marginal(EXPOSURE_DEGREE_NAMES, lambda c: [tb[e][c] for e in range(K)]),
+                "cells": [{"ec": e, "dc": c, "common": EXPOSURE_COMMON_NAMES[e], "degree": EXPOSURE_DEGREE_NAMES[c],
+                           "count": tb[e][c][0], "T": tb[e][c][1], "above": tb[e][c][2], **doubles(*tb[e][c])}
+                          for e in range(K) for c in range(K) if tb[e][c][0]]})
+    return res
+
+
+@_on_operand_device
+def edge_exposure(real, pred, idx=None, threshold=None, edges=False):
+    """Which edges leak (mcgra_edge_exposure): every true edge's own placement among the non-edges, by where the edge sits in
+    the TRUE graph.  The candidates are auc_delong's -- the unordered pairs of positions a > b of a REPEAT-FREE idx (None: all
+    nodes), score pred[idx[a], idx[b]], label real[idx[a], idx[b]] -- and G is the true graph on the selected nodes (the induced
+    subgraph: an unselected neighbour does not exist).  Every edge of G has its placement a_e = 2 #{non-edges scoring lower} +
+    #{non-edges scoring the same}, its embeddedness c_e = the common neighbours of its ends in G (the triangles through it) and
+    d_e = the smaller of their degrees in G; the edges are classed by ec = min(c_e, 15) and dc = min(15, bit_length(d_e)).
+    threshold (None: +inf, nothing is above): where "above" is counted, threshold_pairs' float32 comparison.
+    Returns {"pairs" (m), "positives" (P), "negatives" (N), "T" (auc_delong's), "above_pos", "above_neg", "threshold", "table"
+    (16 x 16 x 3 nested tuples of Python ints, cell (ec, dc) = (count, T, above)), "ints" (the six header integers), "stats"
+    (edge_exposure_stats of them)}; with edges also the edge list in ascending packed position a (a - 1) / 2 + b as device
+    tensors: "pairs_list" [P, 2] int64 = (idx[a], idx[b]), "scores" [P] float32 (the bits as stored), "placement" [P] int64,
+    "common" [P] int32 (c_e, uncapped) and "deg" [P, 2] int32 (the degrees of a and of b); the columns are first allocated for
+    EXPOSURE_FIRST_CAP edges per selected node, and the entry runs a second time only when the graph has more.
+    Exact integers from the device (a bit matrix, AND + popcount, a search among the sorted edges), correctly rounded quotients
+    on the host, the same bits on every call.  McgraError for a NaN threshold, a repeated or out-of-range id, a selected NaN /
+    inf score or a selected label other than 0 / 1."""
+    real, pred, ix, n, rows = _ranked(idx, real, pred)
+    dev, K = pred.device, EXPOSURE_CLASSES
+    thr = float("inf") if threshold is None else float(threshold)
+    header, table = (C.c_int64 * 6)(), (C.c_int64 * (K * K * 3))()
+    cap = EXPOSURE_FIRST_CAP * rows if edges and 2 <= rows <= EXPOSURE_MAX_NIDX else 0
+    for attempt in range(2):
+        cols = (torch.empty(cap, 2, device=dev, dtype=torch.int64), torch.empty(cap, device=dev, dtype=torch.float32),
+                torch.empty(cap, device=dev, dtype=torch.int64), torch.empty(cap, device=dev, dtype=torch.int32),
+                torch.empty(cap, 2, device=dev, dtype=torch.int32)) if cap else (None,) * 5
+        header[1] = -1
+        rc = lib.mcgra_edge_exposure(_stream(), n, _p(real), real.stride(0), _p(pred), pred.stride(0), _p(ix), rows, thr, cap,
+                                     *(_p(t) for t in cols), header, table)
+        if rc == -4 and header[1] > cap and attempt == 0:     # MCGRA_ENOMEM with the header written: more edges than cap
+            cap = int(header[1])
+            continue
+        check(rc)
+        break
+    P = int(header[1])
+    hd = [int(v) for v in header]
+    tb = tuple(tuple(tuple(int(table[(e * K + c) * 3 + q]) for q in range(3)) for c in range(K)) for e in range(K))
+    res = dict(zip(EXPOSURE_HEADER, hd))
+    res.update({"threshold": None if threshold is None else thr, "table": tb, "ints": hd, "stats": edge_exposure_stats(hd, tb)})
+    if edges:
+        res.update(zip(("pairs_list", "scores", "placement", "common", "deg"), (t[:P] for t in cols)))       # (cap > 0 here)
+    return res
+
+
 CLASS_MAX = 16                                     # MCGRA_CLASS_MAX (include/mcgra.h)
 STRATA_MAX = CLASS_MAX * (CLASS_MAX + 1) // 2      # one stratum per unordered class pair
 CLASS_STRATA = ("one", "same", "own", "blocks")

@@ -62,6 +62,12 @@ modified_adj; engine.knn_graph), and the lists are symmetrised as the union (eit
 with the nodes either leaves without an edge and the hubness of the lists: the largest in-degree, the nodes in nobody's list and
 the skewness of the in-degrees.  K = 0 takes each set's own mean true degree, rounded; K is clamped to the set's size less one
 and to 1024.  --save_knn PATH: per node the in-degree, the degrees and the hits; the whole graph's union as an edge list.
+--exposure asks which edges leak: every true edge of a set is placed among ALL the set's non-edges (engine.edge_exposure) and the
+edges are classed by their embeddedness, the common neighbours of their two ends in the true graph on the set's nodes (0, 1, ...,
+14, 15+), and by the smaller of the two degrees (1, 2-3, 4-7, ...); per class the count, the AUC of the class's edges against all
+non-edges -- the pooled AUC of --ci is their mean weighted by the counts -- and the recall at a cut.  --exposure_cut
+split|edges|THRESHOLD (default edges; --structure's cuts) says where.  --save_exposure PATH: every set's 16 x 16 table and the
+whole graph's true edges one by one: placement, common neighbours, degrees.
 --mode link_stealing (not in the reference) is the baseline every paper in this line compares with, Attack-0 of He et al.,
 "Stealing Links from Graph Neural Networks" (USENIX Security 2021): notrain_test's flow up to the priors -- no attack, nothing
 written -- then the AUC (with --ap the average precision too) of the unordered node pairs of attack, train and all scored by
@@ -112,7 +118,7 @@ import torch.nn.functional as F
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, *a, **k):
         args = super().parse_args(*a, **k)
-        for r in reports.EVALUATE_REPORTS:
+        for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS:
             r.check(args, self.error)
         return args
 
@@ -179,6 +185,9 @@ def build_parser():
     p.add_argument('--save_ablation', type=str, default=argparse.SUPPRESS)     # with --ablate: every subset's T and AUC as an .npz
     p.add_argument('--knn', type=int, default=argparse.SUPPRESS)               # also the k-nearest-neighbour graphs of the scores
     p.add_argument('--save_knn', type=str, default=argparse.SUPPRESS)          # with --knn: the per-node columns and the union's edges as an .npz
+    p.add_argument('--exposure', action='store_true', default=argparse.SUPPRESS)   # also the true edges' AUC by common neighbours and min degree
+    p.add_argument('--exposure_cut', type=str, default=argparse.SUPPRESS)      # with --exposure: where the recovered true edges are counted
+    p.add_argument('--save_exposure', type=str, default=argparse.SUPPRESS)     # with --exposure: the tables and the whole graph's edges as an .npz
     return p
 
 
@@ -362,14 +371,14 @@ def log_lines(res, ctx):
     if getattr(ctx.args, "ap", False):
         lines.append(f"In attack graph: AP={res['ap_attack']}\tIn train graph: AP={res['ap_train']}\t"
                      f"In Whole Graph: AP={res['ap_all']}")
-    for r in reports.EVALUATE_REPORTS:
+    for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS:
         if r.wanted(ctx.args):
             lines += r.log(res, ctx)
     return lines + [f"current density: {res['density']}"]
 
 
 def _run(args, rank, world):
-    for r in reports.EVALUATE_REPORTS:
+    for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS:
         r.check(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
@@ -496,7 +505,7 @@ def _run(args, rank, world):
                               "decode_mode": topology_attack._decode_mode(args)})
     want_ap = getattr(args, "ap", False)
     res = base_metrics(ctx, want_ap)
-    wanted = [r for r in reports.EVALUATE_REPORTS if r.wanted(args)]
+    wanted = [r for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS if r.wanted(args)]
     for r in wanted:        # every rank computes (as the AUCs); a report's keys exist only with its flag
         res.update(r.compute(ctx))
     res["path"] = dict(model.history.get("path", {}), world=world)

@@ -2,8 +2,9 @@
 per report the argument check, the computation on the device, the console lines, the --save_* file and the log lines, and at
 the bottom the one ordered table of them that main.py's parser, run and log loop over: REPORT_TABLE, which is REPORTS, then
 EVERY_REPORT's hops report, then ALL_REPORTS' by_class report, then the ablate report (four tuples that tests pin); what main.py
-loops over is EVALUATE_REPORTS, which is REPORT_TABLE and then the reports added after it.
-To add a report, add an entry to EVALUATE_REPORTS.
+loops over is EVALUATE_REPORTS, which is REPORT_TABLE and then the knn report (a fifth pinned tuple), followed by LATER_REPORTS,
+the reports added since.
+To add a report, add an entry to LATER_REPORTS.
 
 `sets` is always index set name -> node ids (None: every node); fail(message) does not return; a --save_* file is written at
 exactly the path given.  engine functions are looked up as engine.<fn> at the call."""
@@ -700,6 +701,61 @@ def save_knn(res, ctx):
     _save_npz(ctx.args.save_knn, **arrays)
 
 
+def check_exposure_args(args, fail):
+    on, cut, path = "exposure" in vars(args), getattr(args, "exposure_cut", None), getattr(args, "save_exposure", None)
+    if cut is not None and not on:
+        fail("--exposure_cut needs --exposure")
+    if path is not None and not on:
+        fail("--save_exposure needs --exposure")
+    if path is not None and path == "":
+        fail("--save_exposure takes the path of the .npz to write")
+    if on and args.mode != "evaluate":
+        fail(f"--exposure splits the true edges of the attack's modified_adj by where they sit in the true graph: "
+             f"--mode evaluate only, not --mode {args.mode}")
+    if cut is not None and structure_source(cut) is None:
+        fail(f"--exposure_cut takes `split`, `edges` or a finite threshold, not {cut!r}")
+
+
+def exposure_report(ctx):
+    """--exposure: {"exposure_<name>": engine.edge_exposure of the index set, its true edges at or above the set's
+    structure_threshold of --exposure_cut (default `edges`) counted class by class}."""
+    source, real, pred = structure_source(getattr(ctx.args, "exposure_cut", "edges")), ctx.real, ctx.inference_adj
+    return {f"exposure_{name}": engine.edge_exposure(real, pred, ix, structure_threshold(source, real, pred, ix))
+            for name, ix in ctx.sets.items()}
+
+
+def _exposure_text(d, auc_only):
+    """`by common neighbours ... (pooled ...) | by min degree ...` over the classes that hold edges."""
+    q = d["stats"]
+
+    def by(mg):
+        if auc_only:
+            return " ".join(f"{k}:{a}" for k, c, a in zip(mg["names"], mg["count"], mg["auc"]) if c)
+        return " ".join(f"{k}: count={c} AUC={a} recall={r}" for k, c, a, r in zip(mg["names"], mg["count"], mg["auc"], mg["recall"]) if c)
+
+    return f"by common neighbours {by(q['by_embeddedness'])} (pooled {q['auc_pooled']}) | by min degree {by(q['by_degree'])}"
+
+
+def _exposure_log(res, ctx):
+    return [f"In {title}: exposure at {d['threshold']}: edges={d['positives']} recall={d['stats']['recall']} "
+            f"precision={d['stats']['precision']} {_exposure_text(d, False)}" for title, d in _per_set(res, "exposure")]
+
+
+def save_exposure(res, ctx):
+    """--save_exposure: per index set nodes, the 16 x 16 x 3 table (int64) and the threshold (float32); for the whole graph the
+    true edges in packed order: pairs, scores, placement, common and deg."""
+    arrays = {}
+    for name, ix in ctx.sets.items():
+        d = res[f"exposure_{name}"]
+        arrays[f"nodes_{name}"] = np.arange(ctx.n, dtype=np.int64) if ix is None else np.asarray(ix, dtype=np.int64)
+        arrays[f"table_{name}"] = np.asarray(d["table"], dtype=np.int64)
+        arrays[f"threshold_{name}"] = np.float32(d["threshold"])
+    g = engine.edge_exposure(ctx.real, ctx.inference_adj, None, res["exposure_all"]["threshold"], edges=True)
+    arrays.update({"pairs": g["pairs_list"].cpu().numpy(), "scores": g["scores"].cpu().numpy(),
+                   "placement": g["placement"].cpu().numpy(), "common": g["common"].cpu().numpy(), "deg": g["deg"].cpu().numpy()})
+    _save_npz(ctx.args.save_exposure, **arrays)
+
+
 def _saver(flag, write):
     """write(res, ctx) when the --save_* flag names a file."""
     return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
@@ -751,13 +807,19 @@ EVALUATE_REPORTS = REPORT_TABLE + (
     Report(flags=("knn", "save_knn"), check=check_knn_args, wanted=_on("knn", given=True), compute=knn_report,
            console=lambda res, ctx: [f"current knn {_knn_text(res['knn_all'])}"], log=_knn_log, save=_saver("save_knn", save_knn)),
 )
+# EVALUATE_REPORTS ends with the knn report, as its tests pin it; the reports added since follow here, and main.py loops over both.
+LATER_REPORTS = (
+    Report(flags=("exposure", "exposure_cut", "save_exposure"), check=check_exposure_args, wanted=lambda args: "exposure" in vars(args),
+           compute=exposure_report, console=lambda res, ctx: [f"current exposure {_exposure_text(res['exposure_all'], True)}"],
+           log=_exposure_log, save=_saver("save_exposure", save_exposure)),
+)
 
 
 def shown_parameters(args):
     """The namespace that the log's parameter line prints: args without `ap` while --ap is off and without the flags of every
     report that is off, so that a run without a flag logs what it logged before the flag existed."""
     hidden = set() if getattr(args, "ap", False) else {"ap"}
-    for r in EVALUATE_REPORTS:
+    for r in EVALUATE_REPORTS + LATER_REPORTS:
         if not r.wanted(args):
             hidden.update(r.flags)
     return argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
