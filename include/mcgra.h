@@ -748,6 +748,41 @@ int mcgra_edge_exposure(void* stream, int n, const float* labels, int ld_labels,
                         int64_t* header /* host[6]: m, P, N, T, above_pos, above_neg */,
                         int64_t* table /* host [16][16][3]: cell (ec, dc) = {P, T, above} */);
 
+/* A defended victim's graph: the edge-level differential-privacy mechanisms EdgeRand and LapGraph of Wu et al., "LinkTeller:
+ * Recovering Private Edges from Graph Neural Networks via Influence Analysis" (IEEE S&P 2022), applied to the graph of adj.
+ *   - the pairs: positions a > b of all n nodes, label adj[a][b] (only the strict lower triangle of adj is read; a value there
+ *     other than 0 or 1: MCGRA_EINVAL), packed position p = a (a - 1) / 2 + b, m = n (n - 1) / 2, E the pairs of label 1;
+ *   - the generator: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ *     0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter = (p, 0, replicate, 0), result words w0 .. w3.  One call per
+ *     pair and no state: pair p's draw depends on (seed, replicate, p) alone -- not on n, the grid or the call;
+ *   - MCGRA_DP_EDGERAND: randomised response.  T = floor(2^32 / (1 + e^eps) + 1/2) in double on the host; pair p's label is
+ *     flipped iff w0 < T: with probability q = T / 2^32, which is LinkTeller's "with probability 2 / (1 + e^eps) replace the
+ *     cell by a fair coin".  realised = {q, ln((1 - q) / q)} (inf when T = 0, the identity);
+ *   - MCGRA_DP_LAPGRAPH: eps1 = 0.01 eps for the edge count, eps2 = 0.99 eps for the cells.  For a draw, u = ((w0 >> 8) + 1/2)
+ *     2^-24 in (0, 1), sigma = +1 iff bit 31 of w1 is clear, Lap(beta) = sigma beta (-ln u), in double throughout.  Cell p:
+ *     v_p = float32(label + Lap(1 / eps2)), ONE rounding of the double sum.  The target count = clamp(rint(E + Lap(1 / eps1)), 0, m)
+ *     from the draw at counter (m, 0, replicate, 0), on the host.  The result holds the `target` best pairs by v descending
+ *     (float32 values), ties by ascending p: mcgra_topk_metrics' ranking, by its radix select.  realised = {the count's noise,
+ *     NaN};
+ *   - out [n x n] = the perturbed graph: 0 / 1, symmetric, zero diagonal; columns from n to ld_out are not touched.  noisy
+ *     (LapGraph only; may be NULL) [n x n] = v mirrored, 0 on the diagonal; with NULL the cells live in scratch of the call;
+ *   - counts (host int64[6]) = {m, E, target (EdgeRand: -1), kept, added, removed}: the pairs of label 1 that stay, the pairs of
+ *     label 0 that become edges, the pairs of label 1 that do not.  kept + removed = E; kept + added = the edge count of out
+ *     (LapGraph: = target).  Integer block sums merged by integer atomics: the same bits on every call; realised may be NULL;
+ *   - n < 2 or n > 65 535 (p must fit 32 bits), eps <= 0 or not finite, a mechanism other than the two, noisy with EdgeRand, adj,
+ *     out or counts NULL, an ld below n: MCGRA_EINVAL before any HIP call, nothing written.  A label other than 0 or 1, or
+ *     (LapGraph, eps below about 1e-37) a cell that overflows float32: MCGRA_EINVAL with counts and realised not written; out
+ *     and noisy may hold part of a result then.
+ * Synchronises `stream`.  EdgeRand is one pass: it reads 2 n^2 bytes and writes 4 n^2.  Device scratch: none for EdgeRand; for
+ * LapGraph 5 bytes per pair (the keys of the select and the selection as bytes), about 3 MB, and 4 n^2 bytes when noisy is
+ * NULL; MCGRA_ENOMEM when that cannot be allocated. */
+#define MCGRA_DP_EDGERAND 0
+#define MCGRA_DP_LAPGRAPH 1
+int mcgra_dp_perturb_graph(void* stream, int n, const float* adj, int ld_adj, int mechanism, double eps, uint64_t seed,
+                           uint32_t replicate, float* out, int ld_out, float* noisy /* device n x n or NULL */, int ld_noisy,
+                           int64_t* counts /* host[6]: m, E, target, kept, added, removed */,
+                           double* realised /* host[2], may be NULL */);
+
 /* GCN.forward in eval mode (models/gcn.py:164-174): log_softmax(linear1(
  * relu(adj @ (... relu(adj @ (X @ W0) + b0) ...)))).  X [n x nfeat],
  * W[l] [dims[l] x dims[l+1]], b[l] [dims[l+1]], Wlin [nclass x dims[nlayer]].

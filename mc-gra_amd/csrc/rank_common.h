@@ -1,5 +1,5 @@
 // What the ranking entries share (auc.hip, curves.hip, topk.hip, node_rank.hip, two_means.hip, delong.hip, node_jackknife.hip,
-// graph_structure.hip, hop_auc.hip, class_auc.hip).
+// graph_structure.hip, hop_auc.hip, class_auc.hip; dp_graph.hip takes topk.hip's selection through topk_mark).
 // Device side, inlined into each file's kernels: the order-preserving key of a float32 score, the label predicates, the pair of
 // a packed position, integer block sums, the walk over the selected lower triangle (tri_for_each), the bound of a key in
 // ascending keys (rank_bound), a lane's slot behind a wave-shared cursor (wave_slot) and its rank among the flagged lanes of a
@@ -97,6 +97,11 @@ void rank_scan(hipStream_t st, const uint32_t* cnt, int len, uint64_t* off);
 // bits / 8 passes; after an odd number of them the result is in tmp (and ptmp).
 int auc_sort(hipStream_t st, uint32_t* keys, uint32_t* tmp, uint64_t count, const SortScratch& ss, uint32_t* pay = nullptr,
              uint32_t* ptmp = nullptr, int bits = 32);
+// topk.hip: mark[p] = 1 where pair p (positions a > b of all n nodes, p = a (a - 1) / 2 + b) is one of the k best of
+// mcgra_topk_metrics' ranking of scores' strict lower triangle (descending float32 value, ties by ascending p), else 0; mark:
+// device, n (n - 1) / 2 bytes; 2 <= n <= AUC_MAX_NIDX and 1 <= k <= n (n - 1) / 2 are the caller's to hold.  The emit, the radix
+// select and the take of the two entries, nothing of its own; a NaN or +-inf score: MCGRA_EINVAL.  Synchronises the stream.
+int topk_mark(const char* who, hipStream_t stream, int n, const float* scores, int ld_scores, uint64_t k, uint8_t* mark);
 
 // ---- both sides
 // float32 (its bits) -> unsigned key with the same order; -0.0 and +0.0 are one value, +-inf are ordinary values.  Bit tests

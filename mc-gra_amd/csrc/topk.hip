@@ -1,5 +1,6 @@
 // The recovered graph: the k best-scored unordered node pairs of a scored square matrix restricted to idx, as counts
 // (mcgra_topk_metrics: TP among the k best, P among all candidates) and as an edge list in ranking order (mcgra_top_pairs).
+// Inside the library also as a byte per pair in packed order (topk_mark, for dp_graph.hip's LapGraph).
 //
 // Candidates: the m = n_idx (n_idx - 1) / 2 pairs of positions a > b of idx (idx == NULL: all n nodes in order); pair (a, b)
 // is nodes u = idx[a], v = idx[b], its score scores[u][v], its label labels[u][v] (the strict lower triangle of the gathered
@@ -140,15 +141,19 @@ __global__ __launch_bounds__(AUC_THREADS) void k_topk_count(const uint32_t* __re
 // The k best of block b's range, in index order, 256 keys a step: a key above T, or a key equal to T whose rank among ALL
 // keys equal to T (off[nb + b] - g before this block, then the earlier steps, the earlier waves, the lower lanes) is below
 // r.  EMIT: the chosen (~key, p) go to rk / rp at their rank among the chosen, off[b] + min(ties before the block, r) before
-// this block (packed order).  Otherwise st->tp += the chosen with label 1.  The tie of rank r - 1 is the k-th pair: its
-// score goes to st->thr_bits.
-template <bool EMIT>
+// this block (packed order).  MARK: mark[p] = 1 for a chosen pair, 0 for every other one (the selection as a mask in packed
+// order, topk_mark).  Otherwise st->tp += the chosen with label 1.  The tie of rank r - 1 is the k-th pair: its score goes to
+// st->thr_bits.
+enum TakeMode { TAKE_COUNT, TAKE_EMIT, TAKE_MARK };
+template <TakeMode MODE>
 __global__ __launch_bounds__(AUC_THREADS) void k_topk_take(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab,
                                                            uint64_t count, uint64_t tile, uint32_t T, uint64_t g, uint64_t r,
                                                            int nb, const uint64_t* __restrict__ off,
                                                            const float* __restrict__ S, int64_t lds,
                                                            const int64_t* __restrict__ idx, uint32_t* __restrict__ rk,
-                                                           uint32_t* __restrict__ rp, TopkState* __restrict__ st) {
+                                                           uint32_t* __restrict__ rp, uint8_t* __restrict__ mark,
+                                                           TopkState* __restrict__ st) {
+  constexpr bool EMIT = MODE == TAKE_EMIT;
   __shared__ uint32_t weq[2][AUC_THREADS / 64], wch[2][AUC_THREADS / 64];
   __shared__ uint64_t sh[AUC_THREADS / 64];
   const int t = threadIdx.x;
@@ -176,11 +181,13 @@ __global__ __launch_bounds__(AUC_THREADS) void k_topk_take(const uint32_t* __res
       const BlockRank rc = block_rank(chosen, wch, par);
       if (chosen) { rk[run_ch + rc.before] = ~k; rp[run_ch + rc.before] = (uint32_t)e; }
       run_ch += rc.all;
+    } else if (MODE == TAKE_MARK) {
+      if (valid) mark[e] = chosen ? 1 : 0;
     } else if (chosen && lab[e]) {
       ++tp;
     }
   }
-  if (!EMIT) {
+  if (MODE == TAKE_COUNT) {
     const uint64_t tot = block_sum_u64(tp, sh);
     if (t == 0 && tot) atomicAdd(&st->tp, (unsigned long long)tot);
   }
@@ -268,6 +275,20 @@ int topk_check(const char* who, int n, const float* scores, int ld_scores, const
   return 0;
 }
 }  // namespace
+
+// rank_common.h: the k best pairs of all n nodes as a mask in packed order, for a caller inside the library (dp_graph.hip).
+int topk_mark(const char* who, hipStream_t stream, int n, const float* scores, int ld_scores, uint64_t k, uint8_t* mark) {
+  TopkRun run{who, stream};
+  if (int rc = run.emit(n, scores, ld_scores, nullptr, 0, nullptr, n, false)) return rc;
+  if (int rc = run.select(k)) return rc;
+  const uint64_t r = run.h.remaining, g = k - r;
+  k_topk_take<TAKE_MARK><<<run.nb, AUC_THREADS, 0, stream>>>(run.keys, nullptr, run.m, run.tile, run.h.prefix, g, r, run.nb,
+                                                            run.ss.off, scores, ld_scores, nullptr, nullptr, nullptr, mark,
+                                                            run.state);
+  MCGRA_KERNEL_CHECK();
+  MCGRA_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
+  return 0;
+}
 }  // namespace mcgra
 
 using namespace mcgra;
@@ -285,8 +306,8 @@ extern "C" int mcgra_topk_metrics(void* stream, int n, const float* labels, int 
   if (kk == 0) return 0;
   if (int rc = run.select(kk)) return rc;
   const uint64_t r = run.h.remaining, g = kk - r;
-  k_topk_take<false><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, run.lab, run.m, run.tile, run.h.prefix, g, r, run.nb, run.ss.off,
-                                                     scores, ld_scores, idx, nullptr, nullptr, run.state);
+  k_topk_take<TAKE_COUNT><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, run.lab, run.m, run.tile, run.h.prefix, g, r, run.nb,
+                                                          run.ss.off, scores, ld_scores, idx, nullptr, nullptr, nullptr, run.state);
   MCGRA_KERNEL_CHECK();
   if (int rc = run.fetch()) return rc;
   counts[2] = (int64_t)run.h.tp;
@@ -310,8 +331,8 @@ extern "C" int mcgra_top_pairs(void* stream, int n, const float* scores, int ld_
   if (!rk || !rp || !tk || !tp) { set_error("top_pairs: hipMalloc of %llu records failed", (unsigned long long)kk); return MCGRA_ENOMEM; }
   if (int rc = run.select(kk)) return rc;
   const uint64_t r = run.h.remaining, g = kk - r;
-  k_topk_take<true><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, nullptr, run.m, run.tile, run.h.prefix, g, r, run.nb, run.ss.off,
-                                                    scores, ld_scores, idx, rk, rp, run.state);
+  k_topk_take<TAKE_EMIT><<<run.nb, AUC_THREADS, 0, st>>>(run.keys, nullptr, run.m, run.tile, run.h.prefix, g, r, run.nb,
+                                                         run.ss.off, scores, ld_scores, idx, rk, rp, nullptr, run.state);
   MCGRA_KERNEL_CHECK();
   if (int rc = auc_sort(st, rk, tk, kk, run.ss, rp, tp)) return rc;
   const int gw = (int)std::min<uint64_t>(2048, (kk + AUC_THREADS - 1) / AUC_THREADS);

@@ -1549,6 +1549,70 @@ def pair_distance_rank_metrics(real, Z, metric, idx=None):
     return {"pairs": pairs, "positives": P, "negatives": N, "T": T, "auc": auc.value, "ap": ap.value}
 
 
+DP_MECHANISMS = ("edgerand", "lapgraph")      # MCGRA_DP_EDGERAND, MCGRA_DP_LAPGRAPH (include/mcgra.h)
+DP_MAX_N = 65535                               # a packed pair position fits 32 bits
+
+
+def dp_mechanism_id(mechanism):
+    """An edge-DP mechanism given by name (DP_MECHANISMS) as its id; ValueError for anything else."""
+    if isinstance(mechanism, str) and mechanism in DP_MECHANISMS:
+        return DP_MECHANISMS.index(mechanism)
+    raise ValueError(f"dp mechanism {mechanism!r}: one of {', '.join(DP_MECHANISMS)}")
+
+
+def dp_perturb_graph(adj, mechanism, eps, seed, replicate=0, want_noisy=False, out=None):
+    """The graph a defended victim is trained on and answers from (mcgra_dp_perturb_graph): adj's graph under EdgeRand
+    (randomised response on every node pair) or LapGraph (Laplace noise on every pair, then the noisy top-E~) of Wu et al.,
+    "LinkTeller" (IEEE S&P 2022), with edge-level privacy budget eps.  adj: n x n on the device, 2 <= n <= 65 535; only its
+    strict lower triangle is read, and a value there other than 0 / 1 is a McgraError.  Every pair's randomness is one
+    Philox4x32-10 draw keyed by (seed, replicate, packed position): the same bits on every call, rank and device.
+    Returns (perturbed, info): perturbed n x n float32 on adj's device (0 / 1, symmetric, zero diagonal; written into `out`
+    when one is given, whose columns beyond n stay as they are), info = {"mechanism", "eps", "seed", "replicate", "pairs" m,
+    "edges" E, "target" (LapGraph's E~; -1 for EdgeRand), "edges_out" = kept + added, "kept", "added", "removed",
+    "flip_probability" q and "eps_realised" ln((1 - q) / q) (EdgeRand: the probability realised by the 32-bit threshold; NaN
+    for LapGraph), "count_noise" (LapGraph: the Laplace noise of the edge count; NaN for EdgeRand)}; with want_noisy (LapGraph
+    only) info["noisy"] = the noisy cells, n x n float32, mirrored, 0 on the diagonal.
+    ValueError, before anything is called on the device, for an unknown mechanism, an eps that is not a finite number above 0,
+    a seed outside [0, 2^64), a replicate outside [0, 2^32), want_noisy with EdgeRand, an adj that is not n x n with n in range
+    or not on a device, and an `out` that is not n float32 rows of unit inner stride on adj's device."""
+    mech = dp_mechanism_id(mechanism)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not math.isfinite(eps) or not eps > 0:
+        raise ValueError(f"dp_perturb_graph: eps = {eps!r}; a finite number above 0")
+    for name, v, bits in (("seed", seed, 64), ("replicate", replicate, 32)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << bits:
+            raise ValueError(f"dp_perturb_graph: {name} = {v!r}; an integer in [0, 2^{bits})")
+    if want_noisy and mech != DP_MECHANISMS.index("lapgraph"):
+        raise ValueError("dp_perturb_graph: want_noisy asks for LapGraph's noisy cells; EdgeRand has none")
+    if not isinstance(adj, torch.Tensor) or adj.dim() != 2 or adj.shape[0] != adj.shape[1] or not 2 <= adj.shape[0] <= DP_MAX_N:
+        raise ValueError(f"dp_perturb_graph: adj of shape {tuple(getattr(adj, 'shape', ()))}; n x n with 2 <= n <= {DP_MAX_N}")
+    n = adj.shape[0]
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, n)
+                            or out.stride(1) != 1 or out.stride(0) < n or out.device != adj.device):
+        raise ValueError(f"dp_perturb_graph: out must be {n} x {n} float32 rows of unit inner stride on adj's device")
+    return _dp_perturb_graph(adj, mech, float(eps), int(seed), int(replicate), bool(want_noisy), out)
+
+
+@_on_operand_device
+def _dp_perturb_graph(adj, mech, eps, seed, replicate, want_noisy, out):
+    adj = _rows_f32(adj, adj.device)
+    n = adj.shape[0]
+    if out is None:
+        out = torch.empty(n, n, device=adj.device, dtype=torch.float32)
+    noisy = torch.empty(n, n, device=adj.device, dtype=torch.float32) if want_noisy else None
+    counts, realised = (C.c_int64 * 6)(), (C.c_double * 2)()
+    check(lib.mcgra_dp_perturb_graph(_stream(), n, _p(adj), adj.stride(0), mech, eps, seed, replicate, _p(out), out.stride(0),
+                                     _p(noisy), n if want_noisy else 0, counts, realised))
+    m, E, target, kept, added, removed = (int(c) for c in counts)
+    lap = mech == DP_MECHANISMS.index("lapgraph")
+    info = {"mechanism": DP_MECHANISMS[mech], "eps": eps, "seed": seed, "replicate": replicate, "pairs": m, "edges": E,
+            "target": target, "edges_out": kept + added, "kept": kept, "added": added, "removed": removed,
+            "flip_probability": float("nan") if lap else realised[0], "eps_realised": float("nan") if lap else realised[1],
+            "count_noise": realised[0] if lap else float("nan")}
+    if want_noisy:
+        info["noisy"] = noisy
+    return out, info
+
+
 @_device_operands
 def gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=0):
     """GCN.forward (eval) and, when emb_nlayer > 0, embedding_GCN.forward."""

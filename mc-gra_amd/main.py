@@ -76,6 +76,18 @@ euclidean, correlation, chebyshev, braycurtis, canberra, cityblock and sqeuclide
 pair on the GPU, no n x n score matrix); one `link stealing <source> <metric>: auc_attack=... auc_train=... auc_all=...` line each.
 --versus SOURCE:METRIC (--mode evaluate, with --ci or --ci_nodes) takes one of those 24 scorings as the other side of the paired
 tests (engine.pair_distance_scores): does the attack beat this baseline on these pairs, with delta, se_delta, z and p_value.
+--dp_defense edgerand|lapgraph --dp_eps EPS [--dp_seed S] (not in the reference, whose --defense only loads weight files it does not
+ship; --defense and --add_noise stay parsed and unused, as there) defends the victim with one of the two edge-level differential-
+privacy mechanisms of Wu et al., "LinkTeller" (IEEE S&P 2022): EdgeRand, randomised response on every node pair, or LapGraph,
+Laplace noise on every pair and then the noisy top-E~ (engine.dp_perturb_graph: one Philox draw per pair keyed by the seed and the
+pair, so every run, rank and device perturbs alike; S defaults to --seed).  The victim is trained on, and answers from, the
+perturbed graph: the fit, the priors H_A / Y_A / H_A1 / H_A2, the test accuracy and the graph the attack is handed.  Every score --
+the AUCs, every report above, the baselines of --mode link_stealing, the priors of --mode notrain_test -- stays against the TRUE
+graph, so each becomes a report about a defended victim.  The result gains `defense` (what the mechanism kept, added and removed,
+the realised flip probability or the count's noise, and the defended victim's test accuracy: the utility side of the trade) and
+one `defense ...` line; --mode evaluate also reports auc_perturbed_*, the AUC of modified_adj against the perturbed graph: which of
+the two graphs the attack recovered.  --save_defense PATH: the perturbed graph's edge list in packed order, the pairs added and
+removed, and those scalars.  --mode evaluate, notrain_test and link_stealing.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -188,6 +200,10 @@ def build_parser():
     p.add_argument('--exposure', action='store_true', default=argparse.SUPPRESS)   # also the true edges' AUC by common neighbours and min degree
     p.add_argument('--exposure_cut', type=str, default=argparse.SUPPRESS)      # with --exposure: where the recovered true edges are counted
     p.add_argument('--save_exposure', type=str, default=argparse.SUPPRESS)     # with --exposure: the tables and the whole graph's edges as an .npz
+    p.add_argument('--dp_defense', type=str, choices=list(engine.DP_MECHANISMS), default=argparse.SUPPRESS)   # train the victim on an edge-DP graph
+    p.add_argument('--dp_eps', type=float, default=argparse.SUPPRESS)          # with --dp_defense: the edge-level privacy budget
+    p.add_argument('--dp_seed', type=int, default=argparse.SUPPRESS)           # with --dp_defense: the mechanism's seed (default: --seed)
+    p.add_argument('--save_defense', type=str, default=argparse.SUPPRESS)      # with --dp_defense: the perturbed graph and what changed as an .npz
     return p
 
 
@@ -395,6 +411,12 @@ def _run(args, rank, world):
             import torch.distributed as dist
             dist.barrier()
         return None
+    # --dp_defense: the victim is trained on, and answers from, the perturbed graph; everything that scores the attack keeps
+    # the true one.  Every rank computes the same graph from the same seed (engine.dp_perturb_graph), so nothing is broadcast
+    victim_adj, perturbed, defense = adj, None, None
+    if "dp_defense" in vars(args):
+        perturbed, dp_info = engine.dp_perturb_graph(adj.to(device), args.dp_defense, args.dp_eps, reports.defense_seed(args))
+        victim_adj = perturbed.cpu()
     feature_adj = dot_product_decode(features, args.dataset)
     if args.nofeature:
         feature_adj = torch.eye(*feature_adj.size())
@@ -404,7 +426,7 @@ def _run(args, rank, world):
     if args.arch == "gcn":                                                                 # main.py:175-190
         victim_model = GCN(nfeat=nfeat, nclass=nclass, nhid=16, nlayer=args.nlayers, dropout=0.5, weight_decay=5e-4,
                            device=device).to(device)
-        victim_model.fit(features, adj, labels, idx_train, idx_val, verbose=False)
+        victim_model.fit(features, victim_adj, labels, idx_train, idx_val, verbose=False)
         embedding = embedding_GCN(nfeat=nfeat, nhid=16, nlayer=args.nlayers, device=device)
         embedding.gc = deepcopy(victim_model.gc)
     elif args.arch == "sage":                                                              # main.py:193-210
@@ -412,13 +434,13 @@ def _run(args, rank, world):
                                  weight_decay=5e-4, device=device).to(device)
         for l in victim_model.gc:
             l.to(device)
-        victim_model.fit(features, adj, labels, idx_train, idx_val, verbose=False)
+        victim_model.fit(features, victim_adj, labels, idx_train, idx_val, verbose=False)
         embedding = embedding_graphsage(nfeat=nfeat, nhid=16, nlayer=args.nlayers, device=device)
         embedding.gc = deepcopy(victim_model.gc)
     else:                                                                                  # main.py:213-231
         victim_model = GAT(nfeat=nfeat, nclass=nclass, nhid=16, nlayer=args.nlayers, dropout=0.5, alpha=0.1, nheads=5,
                            device=device).to(device)
-        victim_model.fit(features, adj, labels, idx_train, idx_val, train_iters=getattr(args, "gat_train_iters", 200))
+        victim_model.fit(features, victim_adj, labels, idx_train, idx_val, train_iters=getattr(args, "gat_train_iters", 200))
         embedding = embedding_gat(nfeat=nfeat, nclass=nclass, nhid=16, nlayer=args.nlayers, dropout=0.5, alpha=0.1,
                                   nheads=5, device=device)
         embedding.attentions = victim_model.attentions
@@ -441,14 +463,22 @@ def _run(args, rank, world):
     embedding = embedding.to(device)
     with torch.no_grad():
         fd, ad = features.to(device), adj.to(device)
-        embedding(fd, ad)                                                                  # H_A     main.py:235
-        Y_A = victim_model(fd, ad)                                                         # main.py:236
+        vd = ad if perturbed is None else perturbed        # what the victim answers from; ad stays the truth of every score
+        embedding(fd, vd)                                                                  # H_A     main.py:235
+        Y_A = victim_model(fd, vd)                                                         # main.py:236
         embedding.set_layers(1)
-        H_A1 = embedding(fd, ad)                                                           # main.py:238-239
+        H_A1 = embedding(fd, vd)                                                           # main.py:238-239
         embedding.set_layers(2)
-        H_A2 = embedding(fd, ad)                                                           # main.py:240-241
-        out = victim_model(fd, utils.normalize_adj_tensor(ad))
-        print("Test set results:", "accuracy= {:.4f}".format(utils.accuracy(out[idx_test], labels.to(device)[idx_test]).item()))
+        H_A2 = embedding(fd, vd)                                                           # main.py:240-241
+        out = victim_model(fd, utils.normalize_adj_tensor(vd))
+        test_accuracy = utils.accuracy(out[idx_test], labels.to(device)[idx_test]).item()
+        print("Test set results:", "accuracy= {:.4f}".format(test_accuracy))
+    if perturbed is not None:
+        defense = {"perturbed": perturbed, "info": dict(dp_info, test_accuracy=test_accuracy)}
+        if rank == 0:
+            print(reports.defense_line(defense["info"]))
+            if getattr(args, "save_defense", None):
+                reports.save_defense(args.save_defense, ad, perturbed, defense["info"])
     idx_attack = np.array(random.sample(range(adj.shape[0]), int(adj.shape[0] * args.nlabel)))   # main.py:244
     num_edges = int(0.5 * args.density * adj.sum() / adj.shape[0] ** 2 * len(idx_attack) ** 2)
 
@@ -461,6 +491,8 @@ def _run(args, rank, world):
             res["ap"] = aps
         else:
             res = prior_aucs(ad, feature_adj, H_A1, H_A2, Y_A, label_adj, args.dataset)
+        if defense is not None:
+            res["defense"] = dict(defense["info"])
         if rank == 0:
             print("feautre adj=", res["feature"])
             print("layer1 adj=", res["layer1"])
@@ -474,6 +506,8 @@ def _run(args, rank, world):
         want_ap = getattr(args, "ap", False)
         sets = {"attack": idx_attack, "train": idx_train, "all": None}
         res = {"link_stealing": link_stealing_metrics(ad, link_sources(Y_A, H_A2, features, device), sets, want_ap)}
+        if defense is not None:
+            res["defense"] = dict(defense["info"])
         if rank == 0:
             print("\n".join(link_stealing_lines(res["link_stealing"], want_ap)))
         return res
@@ -494,15 +528,16 @@ def _run(args, rank, world):
     if getattr(args, "adj_changes_init", None) is not None:      # (tests: a seeded start; adj_changes is a public attribute, :77)
         model.adj_changes = args.adj_changes_init
     model.attack(args, None, lr, 0, args.weight_sup, weight_param, feature_adj, 0, 0, 0, idx_train, idx_val,
-                 idx_test, adj, features, init_adj, labels, idx_attack, num_edges, 0, epochs=args.epochs,
+                 idx_test, victim_adj, features, init_adj, labels, idx_attack, num_edges, 0, epochs=args.epochs,
                  label_adj=label_adj)
     inference_adj = model.modified_adj                     # stays on the device: the three AUCs run there (main.py:247-250)
-    ctx = reports.RunContext(real=ad.to(inference_adj.device), inference_adj=inference_adj,
-                          sets={"attack": idx_attack, "train": idx_train, "all": None}, n=adj.shape[0], rank=rank,
-                          other=other, versus=versus, args=args, classes=classes,
-                          components=None if not getattr(args, "ablate", None) else {
-                              "stack": model.components, "present": model.components_present, "used": model.component_mask,
-                              "decode_mode": topology_attack._decode_mode(args)})
+    ctx = reports.DefendedContext(real=ad.to(inference_adj.device), inference_adj=inference_adj,
+                                  sets={"attack": idx_attack, "train": idx_train, "all": None}, n=adj.shape[0], rank=rank,
+                                  other=other, versus=versus, args=args, classes=classes,
+                                  components=None if not getattr(args, "ablate", None) else {
+                                      "stack": model.components, "present": model.components_present, "used": model.component_mask,
+                                      "decode_mode": topology_attack._decode_mode(args)},
+                                  defense=defense)
     want_ap = getattr(args, "ap", False)
     res = base_metrics(ctx, want_ap)
     wanted = [r for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS if r.wanted(args)]

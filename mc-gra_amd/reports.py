@@ -29,6 +29,10 @@ Context = collections.namedtuple("Context", "real inference_adj sets n rank othe
 # [8, n, n] summands of modified_adj on the device, "present", "used" (masks over engine.ENSEMBLE_COMPONENTS), "decode_mode"}.
 # What main.py builds; every report reads its fields by name, so either form serves the reports that came before --ablate.
 RunContext = collections.namedtuple("RunContext", Context._fields + ("components",), defaults=(None, None))
+# RunContext (pinned as well) and, last, defense: what --dp_defense did before the victim was trained (None without it):
+# {"perturbed" the graph the victim saw, n x n on the device, "info" engine.dp_perturb_graph's info and "test_accuracy"}.
+# real stays the TRUE graph: every report scores the attack against what the defence protects.
+DefendedContext = collections.namedtuple("DefendedContext", RunContext._fields + ("defense",), defaults=(None, None, None))
 
 
 class Report:
@@ -756,6 +760,70 @@ def save_exposure(res, ctx):
     _save_npz(ctx.args.save_exposure, **arrays)
 
 
+DEFENSE_MODES = ("evaluate", "notrain_test", "link_stealing")      # the modes that have a victim to defend
+DEFENSE_SCALARS = ("mechanism", "eps", "seed", "replicate", "pairs", "edges", "target", "edges_out", "kept", "added", "removed",
+                   "flip_probability", "eps_realised", "count_noise", "test_accuracy")
+
+
+def check_defense_args(args, fail):
+    on, eps = "dp_defense" in vars(args), getattr(args, "dp_eps", None)
+    for flag in ("dp_eps", "dp_seed", "save_defense"):
+        if getattr(args, flag, None) is not None and not on:
+            fail(f"--{flag} needs --dp_defense")
+    if not on:
+        return
+    if args.dp_defense not in engine.DP_MECHANISMS:
+        fail(f"--dp_defense takes one of {', '.join(engine.DP_MECHANISMS)}, not {args.dp_defense!r}")
+    if eps is None:
+        fail("--dp_defense needs --dp_eps, the edge-level privacy budget")
+    if not (eps > 0 and eps < float("inf")):
+        fail(f"--dp_eps takes a finite privacy budget above 0, not {eps!r}")
+    if not 0 <= defense_seed(args) < 1 << 64:
+        fail(f"--dp_seed takes an integer in [0, 2^64), not {defense_seed(args)!r} (it defaults to --seed)")
+    if getattr(args, "save_defense", None) == "":
+        fail("--save_defense takes the path of the .npz to write")
+    if args.mode not in DEFENSE_MODES:
+        fail(f"--dp_defense perturbs the graph the victim is trained on: --mode {', '.join(DEFENSE_MODES)} only, "
+             f"not --mode {args.mode}")
+
+
+def defense_seed(args):
+    """--dp_seed, or --seed without it."""
+    seed = getattr(args, "dp_seed", None)
+    return int(args.seed if seed is None else seed)
+
+
+def defense_line(d):
+    """The one line that says what the defence did to the graph and what it cost the victim."""
+    return (f"defense {d['mechanism']} eps={d['eps']} edges {d['edges']}->{d['edges_out']} (kept {d['kept']}, added {d['added']}, "
+            f"removed {d['removed']}) test_accuracy={d['test_accuracy']}")
+
+
+def defense_report(ctx):
+    """--dp_defense in --mode evaluate: {"defense": what the mechanism did (engine.dp_perturb_graph's info) and the defended
+    victim's test accuracy, "auc_perturbed_<name>": metric_pool of modified_adj against the PERTURBED graph on the index set --
+    beside auc_<name>, which is against the true one: which of the two graphs did the attack recover}."""
+    res = {"defense": dict(ctx.defense["info"])}
+    res.update({f"auc_perturbed_{name}": float(engine.roc_auc(ctx.defense["perturbed"], ctx.inference_adj, ix))
+                for name, ix in ctx.sets.items()})
+    return res
+
+
+def _defense_log(res, ctx):
+    return [defense_line(res["defense"]) + " " + " ".join(f"auc_perturbed_{name}={res[f'auc_perturbed_{name}']}" for _, name in SET_TITLES)]
+
+
+def save_defense(path, real, perturbed, d):
+    """--save_defense: the perturbed graph's edges in packed order (edge_list [edges_out, 2] int64, rows (a, b) with a > b), the
+    pairs the mechanism added and removed (added_list, removed_list, packed order too) and every scalar of DEFENSE_SCALARS."""
+    pairs, _, true = engine.threshold_pairs(perturbed, 0.5, None, real)
+    gone, _, still = engine.threshold_pairs(real, 0.5, None, perturbed)
+    arrays = {"edge_list": pairs.cpu().numpy(), "added_list": pairs[~true].cpu().numpy(), "removed_list": gone[~still].cpu().numpy()}
+    for k in DEFENSE_SCALARS:
+        arrays[k] = np.array(d[k], dtype=np.uint64 if k == "seed" else None)
+    _save_npz(path, **arrays)
+
+
 def _saver(flag, write):
     """write(res, ctx) when the --save_* flag names a file."""
     return lambda res, ctx: write(res, ctx) if getattr(ctx.args, flag, None) else None
@@ -812,6 +880,11 @@ LATER_REPORTS = (
     Report(flags=("exposure", "exposure_cut", "save_exposure"), check=check_exposure_args, wanted=lambda args: "exposure" in vars(args),
            compute=exposure_report, console=lambda res, ctx: [f"current exposure {_exposure_text(res['exposure_all'], True)}"],
            log=_exposure_log, save=_saver("save_exposure", save_exposure)),
+    # --dp_defense: main.py perturbs the graph before the victim is trained, prints defense_line and writes --save_defense in every
+    # mode that has a victim; what is left for --mode evaluate is here
+    Report(flags=("dp_defense", "dp_eps", "dp_seed", "save_defense"), check=check_defense_args,
+           wanted=lambda args: "dp_defense" in vars(args), compute=defense_report,
+           console=lambda res, ctx: [f"current auc_perturbed={res['auc_perturbed_all']}"], log=_defense_log),
 )
 
 
