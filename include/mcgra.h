@@ -137,7 +137,8 @@ int mcgra_dot_product_decode2(void* stream, int n, int d, const float* Z, int mo
 /* utils.MutualInformation(sigma=0.4, num_bins=c, normalize=True)(X, Y)[0] (utils.py:980-1049) for X, Y [m x c]: the
  * operand's width is the number of bins (topology_attack.py:199-201, :244-246, :261-263), entry (i, j) meets bin j
  * (utils.py:995).  *out = the value; gX, gY (optional, [m x c]) = d value / dX, d value / dY.  c > 32: square operands
- * (m == c) whose values keep at most 32 bins within reach of a float32 kernel value; MCGRA_ENOSUP otherwise. */
+ * (m == c) whose values keep at most 32 bins within reach of a float32 kernel value; MCGRA_ENOSUP otherwise, and
+ * MCGRA_EINVAL for such an operand with an infinite entry.  A refusal writes nothing to out, gX or gY. */
 int mcgra_mutual_information(void* stream, int m, int c, const float* X, const float* Y, float* out, float* gX, float* gY);
 
 /* CudaCKA.linear_HSIC (utils.py:1085-1089) for X [m x dx], Y [m x dy]:

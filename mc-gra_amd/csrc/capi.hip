@@ -314,6 +314,8 @@ int mcgra_mutual_information(void* stream, int m, int c, const float* X, const f
     MCGRA_HIP(hipMemcpyAsync(h2, am, sizeof(h2), hipMemcpyDeviceToHost, st));
     MCGRA_HIP(hipStreamSynchronize(st));
     const float vmax = h2[0] > h2[1] ? h2[0] : h2[1];
+    // the same test as set_graph's (attack.hip): floorf of an infinite maximum has no int
+    if (!(vmax < 1e30f)) { set_error("mutual_information: an operand holds a non-finite value"); return MCGRA_EINVAL; }
     // bin j sits at j c / (c - 1) >= j; exp(-0.5 ((v - b) / 0.32)^2) == 0 in float32 once b - v > 4.62
     act = (int)floorf(vmax + 4.7f) + 1;
     if (act > c) act = c;

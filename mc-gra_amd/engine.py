@@ -233,10 +233,10 @@ def mutual_information(X, Y, want_grad=False):
     its gradients w.r.t. X and Y (mcgra_mutual_information)."""
     m, c = X.shape
     assert Y.shape == X.shape
-    X, Y = X.contiguous(), Y.contiguous()
+    X, Y = _f32(X), _f32(Y)
     out = torch.zeros(1, device=X.device, dtype=torch.float32)
-    gX = torch.empty_like(X) if want_grad else None
-    gY = torch.empty_like(Y) if want_grad else None
+    gX = torch.empty(m, c, device=X.device, dtype=torch.float32) if want_grad else None
+    gY = torch.empty(m, c, device=X.device, dtype=torch.float32) if want_grad else None
     check(lib.mcgra_mutual_information(_stream(), m, c, _p(X), _p(Y), _p(out), _p(gX), _p(gY)))
     return (out[0], gX, gY) if want_grad else out[0]
 

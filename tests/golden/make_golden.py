@@ -486,6 +486,10 @@ def gen_ops_kde(tmp):
     out = {}
     cases = [("nxn48", 48, 48, 0.0, 1.0), ("nxn160", 160, 160, 0.0, 1.0), ("nxn160_ori", 160, 160, 0.0, 2.0),
              ("em16", 60, 16, 0.0, 4.0), ("sm7", 60, 7, None, None), ("wide20", 40, 20, -1.0, 21.0)]
+    # the forms of csrc/kde_kernels.hip: a second block of rows at 9 and 17 columns, one whole block at 32, the smallest wide
+    # square operand, and a wide square one whose values reach 25 columns.  Appended: the stream of the six above is unchanged
+    cases += [("w9_m65", 65, 9, -1.0, 10.0), ("w17_m129", 129, 17, -1.0, 18.0), ("w32_m64", 64, 32, -1.0, 33.0),
+              ("nxn33", 33, 33, 0.0, 1.0), ("nxn200_hi20", 200, 200, 0.0, 20.0)]
     for tag, m, c, lo, hi in cases:
         if lo is None:      # Y_A (log-probs) against softmax(output2): the operands of c10 (:261-265)
             X = torch.log_softmax(torch.tensor(rng.randn(m, c).astype(np.float32)) * 2, 1).numpy()

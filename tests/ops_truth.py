@@ -16,6 +16,10 @@ requires every case to sit at least 10 bounds away from each defect that applies
   tail256   everything past the last whole 256 columns of a row dropped
   past1024  everything past the first 1024 rows dropped from the final reduction
 the others are named where they apply.
+
+mutual_information (measure KDE's arithmetic, csrc/kde_kernels.hip) returns gradients too and stands at the end of the file
+with its own defects, a float32 emulation of its kernel values and its own cases; its bins alone come from torch.linspace,
+as the reference's do.
 """
 import functools
 import math
@@ -642,3 +646,250 @@ def gcn_case(name):
     Wlin = (rng.randn(nclass, dims[-1]) / math.sqrt(dims[-1])).astype(np.float32)
     blin = (0.1 * rng.randn(nclass)).astype(np.float32)
     return X, adj, W, b, Wlin, blin
+
+
+# ------------------------------------------------------------------------------------- utils.MutualInformation (KDE)
+KDE_SIGMA = 2 * 0.4 ** 2                        # self.sigma (utils.py:985), the double
+KDE_SIGMA_F32 = float(np.float32(KDE_SIGMA))    # the float32 scalar the kernels divide by
+KDE_EPS = 1e-10                                 # self.epsilon (utils.py:988)
+KDE_MAXC = 32                                   # the widest template of csrc/kde_kernels.hip
+KDE_ROWS = 64                                   # rows per block of k_kde_stats
+KDE_GRAD_TOL = 3e-6                             # of the operand's largest float64 gradient magnitude
+                                                # (tests/test_gpu_parity.py::test_mutual_information_op_against_the_reference)
+MI_DEFECTS = ("lastrow", "tail64", "first_block", "m_padded", "lastcol", "cols8", "bins_from_reach", "joint_transposed",
+              "no_marginal")
+
+
+def kde_bins(nb):
+    """torch.linspace(0, nb, nb).float() (utils.py:990-991) by the formula of kde_bin in csrc/kde_kernels.hip, every step
+    rounded to float32: step = nb / (nb - 1), step * j below the middle, fma(-step, nb - 1 - j, nb) from it on (the fma is
+    taken exactly in double and rounded once: its operands are float32, so the double product is exact)."""
+    if nb <= 1:
+        return np.zeros(max(nb, 0), np.float32)
+    step = np.float32(nb) / np.float32(nb - 1)
+    j = np.arange(nb)
+    lo = (step * j.astype(np.float32)).astype(np.float32)
+    hi = (np.float64(nb) - np.float64(step) * (nb - 1 - j).astype(np.float64)).astype(np.float32)
+    return np.where(j < nb // 2, lo, hi).astype(np.float32)
+
+
+def kde_reach(X, Y):
+    """The number of leading columns a wide square operand is evaluated on (mcgra_mutual_information): bin j sits at
+    j c / (c - 1) >= j and a float32 kernel value is exactly 0 once b - v > 4.62, so act = floor(max |v| + 4.7) + 1.
+    Not capped: beyond KDE_MAXC the op refuses."""
+    vmax = np.float32(max(np.abs(X).max(), np.abs(Y).max()))
+    return int(np.floor(vmax + np.float32(4.7))) + 1
+
+
+def _kde_dH(p):
+    """d (-p log2(p + eps)) / dp"""
+    return -(np.log2(p + KDE_EPS) + p / ((p + KDE_EPS) * math.log(2.0)))
+
+
+def _mi(X, Y, defect=None, f32_kernel=False):
+    """utils.MutualInformation(sigma=0.4, num_bins=c, normalize=True) on X, Y [m x c] (utils.py:980-1049) and its backward by
+    hand, in float64.  `values - bins.unsqueeze(0).unsqueeze(0)` (:995) puts bin j against column j:
+      k_ij = exp(-0.5 ((v_ij - b_j) / sigma)^2),  pdf = mean_i k / (sum_j mean_i k + eps) (:998-1000),
+      joint = k1^T k2 / (sum + eps) (:1004-1010),  H = -sum p log2(p + eps),  V = 2 (H1 + H2 - H12) / (H1 + H2) (:1035-1043).
+    Backward: dV/dH12 = -2 / S and dV/dH1 = dV/dH2 = 2 H12 / S^2 with S = H1 + H2; through p = q / (sum q + eps):
+    g_q = (g_p - sum g_p p) / (sum q + eps); dV/dk1_ia = g_q1_a / m + sum_b g_J_ab k2_ib (k2 likewise with the joint's table
+    transposed); dk/dv = -k (v - b) / sigma^2.
+    f32_kernel: the kernel values as the device forms them, (v - b) / 0.32f, t t, expf(-0.5 t t), every step rounded to
+    float32, on the columns within reach of a wide square operand; everything after them in float64 as on the device.
+    Returns a dict: val, gX, gY, dk1, dk2 (dV/dk), z1, z2 (the exponents), k1, k2."""
+    X32, Y32 = np.asarray(X, np.float32), np.asarray(Y, np.float32)
+    m, c = X32.shape
+    wide = c > KDE_MAXC
+    rows, cols, mdiv = np.ones(m, bool), np.ones(c, bool), float(m)
+    if f32_kernel:
+        bins = kde_bins(c)
+    else:
+        import torch
+        bins = torch.linspace(0, c, c).float().numpy()
+    if defect == "lastrow":
+        rows[-1] = False
+    elif defect == "tail64":
+        rows[KDE_ROWS * (m // KDE_ROWS):] = False
+    elif defect == "first_block":
+        rows[KDE_ROWS:] = False
+    elif defect == "m_padded":
+        mdiv = float(KDE_ROWS * ((m + KDE_ROWS - 1) // KDE_ROWS))
+    elif defect == "lastcol":
+        cols[-1] = False
+    elif defect == "cols8":
+        cols[8:] = False
+    elif defect == "bins_from_reach":
+        act = min(kde_reach(X32, Y32), c)
+        bins = np.concatenate([kde_bins(act), np.full(c - act, 1e30, np.float32)])
+    if f32_kernel and wide:
+        cols[min(kde_reach(X32, Y32), c):] = False
+    b = bins.astype(np.float64)[None, :]
+    if f32_kernel:
+        s32 = np.float32(KDE_SIGMA)
+        t = ((X32 - bins[None, :]).astype(np.float32) / s32).astype(np.float32), ((Y32 - bins[None, :]).astype(np.float32) / s32).astype(np.float32)
+        h = [(np.float32(-0.5) * (tt * tt).astype(np.float32)).astype(np.float32) for tt in t]
+        with np.errstate(under="ignore"):
+            k1, k2 = (np.exp(hh.astype(np.float64)).astype(np.float32).astype(np.float64) for hh in h)
+        z1, z2 = (hh.astype(np.float64) for hh in h)
+        sig = KDE_SIGMA_F32
+    else:
+        sig = KDE_SIGMA
+        z1, z2 = -0.5 * ((_f64(X32) - b) / sig) ** 2, -0.5 * ((_f64(Y32) - b) / sig) ** 2
+        with np.errstate(under="ignore"):
+            k1, k2 = np.exp(z1), np.exp(z2)
+    k1, k2 = k1 * cols[None, :], k2 * cols[None, :]
+    q1, q2 = k1[rows].sum(0) / mdiv, k2[rows].sum(0) / mdiv
+    n1, n2 = q1.sum() + KDE_EPS, q2.sum() + KDE_EPS
+    p1, p2 = q1 / n1, q2 / n2
+    J = k1[rows].T @ k2[rows]
+    nJ = J.sum() + KDE_EPS
+    P = J / nJ
+    H1, H2, H12 = -(p1 * np.log2(p1 + KDE_EPS)).sum(), -(p2 * np.log2(p2 + KDE_EPS)).sum(), -(P * np.log2(P + KDE_EPS)).sum()
+    S = H1 + H2
+    val = 2.0 * (S - H12) / S
+    gH, gH12 = 2.0 * H12 / (S * S), -2.0 / S
+    gp1, gp2, gP = gH * _kde_dH(p1), gH * _kde_dH(p2), gH12 * _kde_dH(P)
+    gq1, gq2 = (gp1 - (gp1 * p1).sum()) / n1 / m, (gp2 - (gp2 * p2).sum()) / n2 / m      # d pdf / d k = 1 / m
+    gJ = (gP - (gP * P).sum()) / nJ
+    if defect == "no_marginal":
+        gq1, gq2 = 0.0 * gq1, 0.0 * gq2
+    if defect == "joint_transposed":
+        gJ = gJ.T
+    dk1 = (gq1[None, :] + k2 @ gJ.T) * cols[None, :]
+    dk2 = (gq2[None, :] + k1 @ gJ) * cols[None, :]
+    gX = dk1 * k1 * (-(_f64(X32) - b) / (sig * sig))
+    gY = dk2 * k2 * (-(_f64(Y32) - b) / (sig * sig))
+    if f32_kernel:
+        gX, gY = gX.astype(np.float32).astype(np.float64), gY.astype(np.float32).astype(np.float64)
+    return dict(val=float(val), gX=gX, gY=gY, dk1=dk1, dk2=dk2, z1=z1, z2=z2, k1=k1, k2=k2)
+
+
+def mutual_information(X, Y, defect=None):
+    """(value, dvalue/dX, dvalue/dY) of utils.MutualInformation(sigma=0.4, num_bins=X.shape[1], normalize=True)(X, Y)
+    (utils.py:980-1049) in float64; the bins are torch.linspace(0, c, c).float() as float32 values, as the reference's double
+    run has them.  Defects (the sums are the two column sums of the kernel values and their c x c product):
+      lastrow          the last row left out of all three sums
+      tail64           the rows past the last whole 64 left out of them
+      first_block      only the first 64 rows counted
+      m_padded         the marginals' mean taken over m rounded up to 64.  The normalised pdf does not see a common factor, so
+                       the value keeps; what moves is the marginal part of the gradient, whose d pdf / d k stays 1 / m: it
+                       comes out (padded m) / m too large
+      lastcol          the last column dropped (non-square operands; a wide square operand's last column carries nothing)
+      cols8            a wide square operand cut at 8 columns whatever its values reach
+      bins_from_reach  the bins of a wide square operand spaced for the evaluated width, not for N
+      joint_transposed the joint's gradient table indexed [b][a]
+      no_marginal      the gradient without the part through the marginals"""
+    r = _mi(X, Y, defect)
+    return r["val"], r["gX"], r["gY"]
+
+
+def mutual_information_f32(X, Y):
+    """The same with the kernel values rounded as the device rounds them (see _mi): what a correct float32 evaluation
+    returns, up to the last bit of expf.  tests/test_ops_cases_cpu.py holds it to a third of the tolerances."""
+    r = _mi(X, Y, f32_kernel=True)
+    return r["val"], r["gX"], r["gY"]
+
+
+def mutual_information_bound(X, Y, r=None):
+    """The value's bound.  A kernel value k = expf(-0.5f (t t)), t = (v - b) / 0.32f, carries relative to k: on the exponent
+    z = -0.5 t^2 twice the relative error of t -- the subtraction u, the division 2 u, so 6 u |z| -- one rounding of the
+    square, u |z|, and 0.32f against the reference's 0.32 (2.24e-8 = 0.375 u on sigma), 0.75 u |z|: below 8 u |z|; expf within
+    1 ulp: 2 u.  e_k = (8 |z| + 2) u k.  Everything after the kernel values is double on the device, so the value moves by
+    sum |dV/dk1| e_k1 + sum |dV/dk2| e_k2 to first order, dV/dk from the truth's own backward; times SAFETY, + u |V| for the
+    returned float.  r: _mi(X, Y) where the caller has it."""
+    r = _mi(X, Y) if r is None else r
+    e1 = (8.0 * np.abs(r["z1"]) + 2.0) * U * r["k1"]
+    e2 = (8.0 * np.abs(r["z2"]) + 2.0) * U * r["k2"]
+    return SAFETY * float((np.abs(r["dk1"]) * e1).sum() + (np.abs(r["dk2"]) * e2).sum()) + U * abs(r["val"])
+
+
+MI_EMB = ((1, 7), (2, 7), (63, 8), (64, 8), (65, 9), (128, 16), (129, 17), (257, 32), (1030, 32), (5000, 32), (300, 1), (32, 32))
+MI_LOGP = ((300, 2), (1030, 7), (1030, 9))
+MI_CASES = tuple(("emb", m, c) for m, c in MI_EMB) + tuple(("logp", m, c) for m, c in MI_LOGP) + (
+    ("nxn1", 33, 33), ("nxn1", 257, 257), ("nxn1", 1030, 1030), ("nxn2", 1030, 1030), ("nxn20", 257, 257), ("reach32", 300, 300))
+MI_RAW_CASES = (("emb", 65, 9), ("nxn2", 1030, 1030))        # the raw C ABI with one or both gradient outputs absent
+MI_REACH = {("nxn1", 33, 33): 6, ("nxn1", 257, 257): 6, ("nxn1", 1030, 1030): 6, ("nxn2", 1030, 1030): 7, ("nxn20", 257, 257): 25,
+            ("reach32", 300, 300): 32}
+
+
+def mi_defects(kind, m, c):
+    """The defects that change anything at this case.  'lastcol' needs a last column that carries something: the bin of
+    column c - 1 is c, which the values of a wide square operand never come near (that is why it is cut at its reach), nor
+    do log-probabilities and probabilities (<= 1) once c > 5."""
+    wide = c > KDE_MAXC
+    out = []
+    if m > 1:
+        out.append("lastrow")
+    if m % KDE_ROWS and m > KDE_ROWS:
+        out.append("tail64")
+    if m > KDE_ROWS:
+        out.append("first_block")
+    if m % KDE_ROWS:
+        out.append("m_padded")
+    if not wide and c > 1 and (kind == "emb" or c <= 5):
+        out.append("lastcol")
+    if wide and MI_REACH[(kind, m, c)] > 8:
+        out.append("cols8")
+    if wide:
+        out.append("bins_from_reach")
+    if c > 1:
+        out.append("joint_transposed")
+    out.append("no_marginal")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def mi_case(kind, m, c):
+    """Operands of mutual_information; in every kind Y depends on X and follows another law, so the joint is neither
+    symmetric nor the product of its marginals.
+      emb      X uniform over [-1, c + 1], so every bin is met; Y a noisy affine function of X with a drift per column
+      logp     X a log-softmax, Y a softmax of correlated logits (the operands of c10)
+      nxn<hi>  X uniform over [0, hi], Y = clip(0.5 X + 0.5 hi r^2, 0, hi) with r uniform: the N x N operands
+      reach32  nxn26 with X's largest entry planted at exactly 27.0: floor(27 + 4.7) + 1 = 32 columns, the last reach the op
+               accepts (mi_refused_case raises the entry to 27.5)"""
+    assert m >= 1 and c >= 1
+    rng = np.random.RandomState(16000 + 31 * m + c)
+    if kind == "emb":
+        X = rng.uniform(-1.0, c + 1.0, (m, c))
+        j = np.arange(c)
+        if m > 1:       # with few rows too, every column meets its bin.  Not at m = 1: the joint of one row is the product of its
+            # marginals, the value 0 but for eps, and only kernel sums small enough for eps to count leave anything to compare
+            X[j % m, j] = j * (c / max(c - 1.0, 1.0)) + 0.15 * np.sin(1.0 + j)
+        if m > 2:       # and the last row meets all of them: among thousands of uniform rows it would carry next to nothing
+            X[m - 1] = j * (c / max(c - 1.0, 1.0)) + 0.2 * np.cos(3.0 * j)
+        Y = 0.97 * X + 0.4 + 0.3 * np.cos(j)[None, :] + 0.3 * rng.randn(m, c)
+    elif kind == "logp":
+        L = 2.0 * rng.randn(m, c)
+        L2 = 0.7 * L + 1.4 * rng.randn(m, c)
+        X = L - L.max(1)[:, None]
+        X = X - np.log(np.exp(X).sum(1))[:, None]
+        Y = np.exp(L2 - L2.max(1)[:, None])
+        Y = Y / Y.sum(1)[:, None]
+    else:
+        assert m == c
+        hi = 26.0 if kind == "reach32" else float(kind[3:])
+        X = rng.uniform(0.0, hi, (m, c))
+        Y = np.clip(0.5 * X + 0.5 * hi * rng.rand(m, c) ** 2, 0.0, hi)
+        if kind == "reach32":
+            X[5, 27] = 27.0
+    X, Y = X.astype(np.float32), Y.astype(np.float32)
+    X.setflags(write=False)
+    Y.setflags(write=False)
+    return X, Y
+
+
+@functools.lru_cache(maxsize=None)
+def mi_refused_case():
+    """The reach32 operands with the planted entry raised to 27.5: floor(27.5 + 4.7) + 1 = 33 columns, refused."""
+    X, Y = mi_case("reach32", 300, 300)
+    X = X.copy()
+    X[5, 27] = 27.5
+    return X, Y
+
+
+@functools.lru_cache(maxsize=None)
+def mi_truth(kind, m, c):
+    """(value, gX, gY, bound of the value) of a case, computed once a process."""
+    X, Y = mi_case(kind, m, c)
+    r = _mi(X, Y)
+    return r["val"], r["gX"], r["gY"], mutual_information_bound(X, Y, r)

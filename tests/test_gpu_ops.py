@@ -3,7 +3,14 @@ case runs the C ABI through the host wrappers, compares with the float64 truth a
 bound of the float32 evaluation computed from the same inputs (elementwise for a matrix; a scalar's bound holds the rounding of
 the returned float).  Every op runs twice and must return the same bits: these kernels add no floats atomically and reduce in a
 fixed order.  tests/test_ops_cases_cpu.py shows without a device that each case here would tell a wrong kernel from a right
-one.  Each test prints max |error| / bound (DESIGN.md section 5 holds the table).  Run with -m gpu."""
+one.  Each test prints max |error| / bound (DESIGN.md section 5 holds the table).  Run with -m gpu.
+
+mutual_information (the whole arithmetic of measure KDE) is held to the same kind of truth at every form of its three kernels,
+through the wrapper and the raw C ABI with a gradient output absent.  Its kernels came out right at every case: the largest
+value error is 0.12 of its bound, the largest gradient error 0.26 of the 3e-6 it is held to.  What was wrong lay around them:
+engine.mutual_information handed float64 or half tensors to the C ABI as they were and allocated the gradients in the
+operands' dtype, and the wide-square branch took floorf of an infinite maximum (status 0 with a 0 / 0 value); both are fixed
+and tested here."""
 import numpy as np
 import pytest
 
@@ -219,6 +226,106 @@ def test_gcn_forward_within_the_float32_bound(E, name, emb):
         assert E.gcn_forward(*args)[1] is None
 
 
+# --------------------------------------------------------------------------------------------------- mutual_information
+EINVAL, ENOSUP = -1, -3
+POISON = -7.25
+
+
+def mi_twice(E, X, Y):
+    """(value, gX, gY) as numpy arrays, after a second call has returned the same bits of all three."""
+    runs = [E.mutual_information(X, Y, want_grad=True) for _ in range(2)]
+    a, b = ([t.detach().cpu().numpy() for t in r] for r in runs)
+    assert all(x.dtype == np.float32 and x.tobytes() == y.tobytes() for x, y in zip(a, b)), "two runs on the same inputs differ"
+    return a
+
+
+def mi_raw(pkg, E, X, Y, want_x, want_y):
+    """The raw C ABI on device tensors; the outputs are poisoned first and an output not asked for is handed over as NULL.
+    Returns (status, out, gX buffer, gY buffer) as numpy arrays."""
+    import torch
+    m, c = X.shape
+    out, gX, gY = (torch.full(s, POISON, device=DEV) for s in ((1,), (m, c), (m, c)))
+    rc = pkg._lib.lib.mcgra_mutual_information(E._stream(), m, c, E._p(X), E._p(Y), E._p(out), E._p(gX if want_x else None),
+                                               E._p(gY if want_y else None))
+    torch.cuda.synchronize()
+    return rc, out.cpu().numpy(), gX.cpu().numpy(), gY.cpu().numpy()
+
+
+@pytest.mark.parametrize("kind,m,c", T.MI_CASES)
+def test_mutual_information_within_the_float32_bound(E, kind, m, c):
+    """mcgra_mutual_information (k_kde_stats, k_kde_tables, k_kde_grad of csrc/kde_kernels.hip) at every form it has: 8, 16 and
+    32 columns from both sides of each switch; one block of k_kde_stats' 64 rows and of k_kde_grad's 128, with and without a
+    ragged tail, up to the 79 partials k_kde_tables sums at m = 5000; c = 32 against c = 33, where a square operand is cut at
+    the reach of its values (6, 7, 25 and 32 columns).
+    The value: a kernel value k = expf(-0.5f (t t)), t = (v - b) / 0.32f, carries relative to k, on its exponent z = -0.5 t^2,
+    6 u |z| from t (the subtraction u, the division 2 u, doubled by the square), u |z| from the square's rounding and
+    0.75 u |z| for 0.32f against the reference's 0.32, and 2 u for expf: (8 |z| + 2) u.  Everything after the kernel values is
+    double, so the bound is SAFETY sum (|dV/dk1| e_k1 + |dV/dk2| e_k2) + u |V| with dV/dk from the truth's own backward
+    (ops_truth.mutual_information_bound).  The gradients: within 3e-6 of that operand's largest float64 gradient magnitude,
+    the figure tests/test_gpu_parity.py holds this op to; tests/test_ops_cases_cpu.py shows that a correct float32 evaluation
+    uses at most a third of it at every case, and that every defect it knows moves a case by ten."""
+    Xn, Yn = T.mi_case(kind, m, c)
+    X, Y = dev(Xn), dev(Yn)
+    v, gx, gy, bound = T.mi_truth(kind, m, c)
+    val, GX, GY = mi_twice(E, X, Y)
+    assert val.shape == () and GX.shape == GY.shape == (m, c)
+    assert twice(lambda: E.mutual_information(X, Y)).tobytes() == val.tobytes()
+    within("mutual_information", (kind, m, c), val, v, bound)
+    for nm, G, g in (("gX", GX, gx), ("gY", GY, gy)):
+        tol = T.KDE_GRAD_TOL * np.abs(g).max()
+        err = np.abs(G.astype(np.float64) - g).max()
+        print(f"[ops] mutual_information({nm}) {(kind, m, c)}: max |error| / bound = {err / tol:.4f} (max |error| {err:.3e})")
+        assert np.isfinite(G).all() and err <= tol, (kind, m, c, nm, err / tol)
+    if c > T.KDE_MAXC:
+        act = T.MI_REACH[(kind, m, c)]
+        for G in (GX, GY):
+            assert not G[:, act:].any() and G[:, :act].any()
+
+
+@pytest.mark.parametrize("kind,m,c", T.MI_RAW_CASES)
+def test_mutual_information_with_a_gradient_output_absent(pkg, E, kind, m, c):
+    """The attack engine never asks for both gradients.  gX = NULL, gY = NULL and both: the value and the gradient that is
+    asked for are the bits of the call with both, and a buffer not handed over keeps its poison."""
+    X, Y = (dev(a) for a in T.mi_case(kind, m, c))
+    rc, val, GX, GY = mi_raw(pkg, E, X, Y, True, True)
+    assert rc == 0 and val[0] != POISON and not (GX == POISON).any() and not (GY == POISON).any()
+    w = [t.cpu().numpy() for t in E.mutual_information(X, Y, want_grad=True)]
+    assert val[0].tobytes() == w[0].tobytes() and GX.tobytes() == w[1].tobytes() and GY.tobytes() == w[2].tobytes()
+    for want_x, want_y in ((False, True), (True, False), (False, False)):
+        rc, v1, g1x, g1y = mi_raw(pkg, E, X, Y, want_x, want_y)
+        assert rc == 0 and v1.tobytes() == val.tobytes(), (want_x, want_y)
+        assert g1x.tobytes() == GX.tobytes() if want_x else (g1x == POISON).all(), (want_x, want_y)
+        assert g1y.tobytes() == GY.tobytes() if want_y else (g1y == POISON).all(), (want_x, want_y)
+
+
+def test_mutual_information_refusals_write_nothing(pkg, E):
+    """A wide square operand whose values reach 33 columns (one entry raised from 27.0, the last accepted, to 27.5) is
+    MCGRA_ENOSUP and the message names the value and the reach; a wide operand that is not square is MCGRA_ENOSUP; one with an
+    infinite entry is MCGRA_EINVAL by name (floorf of an infinite maximum has no int: the op used to return 0 / 0 with status
+    0).  None of them writes to out, gX or gY."""
+    import torch
+    L = pkg._lib.lib
+    untouched = lambda r: all((a == POISON).all() for a in r[1:])
+    X, Y = (dev(a) for a in T.mi_refused_case())
+    r = mi_raw(pkg, E, X, Y, True, True)
+    msg = L.mcgra_last_error()
+    assert r[0] == ENOSUP and b"27.5" in msg and b"33" in msg and untouched(r), (r[0], msg)
+    with pytest.raises(pkg._lib.McgraNotSupported, match="27.5"):
+        E.mutual_information(X, Y, want_grad=True)
+    r = mi_raw(pkg, E, X[:40, :33].contiguous(), Y[:40, :33].contiguous(), True, True)
+    assert r[0] == ENOSUP and b"square" in L.mcgra_last_error() and untouched(r)
+    Xn, Yn = T.mi_case("nxn1", 33, 33)
+    for which, bad in ((0, np.inf), (1, -np.inf), (1, np.inf)):
+        ops = [Xn.copy(), Yn.copy()]
+        ops[which][7, 31] = bad
+        r = mi_raw(pkg, E, dev(ops[0]), dev(ops[1]), True, True)
+        msg = L.mcgra_last_error()
+        assert r[0] == EINVAL and b"mutual_information" in msg and b"finite" in msg and untouched(r), (which, bad, r[0], msg)
+    with pytest.raises(pkg._lib.McgraError, match="mutual_information"):
+        E.mutual_information(dev(ops[0]), dev(ops[1]))
+    assert torch.isfinite(E.mutual_information(dev(Xn), dev(Yn)))          # and the op goes on working afterwards
+
+
 # --------------------------------------------------------------------------------------------------- wrappers' operands
 def variants(t):
     """The same values as t in forms the C ABI cannot read: float64, non-contiguous, with autograd history."""
@@ -238,7 +345,12 @@ def test_converting_wrappers_take_any_float_tensor(E, HS):
     A, P, Z = dev(T.norm_case(257)), dev(T.ie_case(257)), dev(T.decode_case(257, 7))
     an, orin = T.adj_case(257)
     a, ori = dev(an), dev(orin)
+    MX, MY = (dev(t) for t in T.mi_case("emb", 129, 17))
     ops = {
+        "mutual_information": (lambda X_, Y_: E.mutual_information(X_, Y_), [MX, MY]),
+        "mutual_information(value)": (lambda X_, Y_: E.mutual_information(X_, Y_, want_grad=True)[0], [MX, MY]),
+        "mutual_information(gX)": (lambda X_, Y_: E.mutual_information(X_, Y_, want_grad=True)[1], [MX, MY]),
+        "mutual_information(gY)": (lambda X_, Y_: E.mutual_information(X_, Y_, want_grad=True)[2], [MX, MY]),
         "normalize_adj_tensor": (lambda A_: E.normalize_adj_tensor(A_), [A]),
         "get_modified_adj": (lambda a_, o_: E.get_modified_adj(a_, o_, 257), [a, ori]),
         "pack_tril": (lambda o_: E.pack_tril(o_), [ori]),
@@ -264,6 +376,11 @@ def test_converting_wrappers_take_any_float_tensor(E, HS):
             assert got.detach().cpu().numpy().tobytes() == plain.tobytes(), (name, k)
         mixed = fn(*[f[i % 3] for i, f in enumerate(forms)])
         assert mixed.detach().cpu().numpy().tobytes() == plain.tobytes(), (name, "mixed")
+    import torch
+    for form in zip(variants(MX), variants(MY)):          # the gradients: float32 of the operands' shape, whatever the operands are
+        for t in E.mutual_information(*form, want_grad=True):
+            assert t.dtype == torch.float32 and t.is_contiguous() and not t.requires_grad and t.grad_fn is None
+            assert t.shape in ((), MX.shape)
     c = T.gcn_case("n300_l3")
     X, adj, W, b, Wlin, blin = (dev(c[0]), dev(c[1]), [dev(w) for w in c[2]], [dev(x) for x in c[3]], dev(c[4]), dev(c[5]))
     lp, emb = E.gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=2)
@@ -299,6 +416,7 @@ def test_a_host_operand_beside_a_device_one_is_refused(E, HS):
     host = X.cpu()
     for name, call in {"mse": lambda: E.mse(X, host), "linear_hsic": lambda: E.linear_hsic(X, host), "sgemm": lambda: E.sgemm(X, host, tb=True),
                        "hsic_regular": lambda: E.hsic_regular(X, host, 1.0), "mmd": lambda: HS.mmd(X, host, 1.0),
+                       "mutual_information": lambda: E.mutual_information(X, host, want_grad=True),
                        "get_modified_adj": lambda: E.get_modified_adj(X[0], torch.zeros(6, 6), 6),
                        "gcn_forward": lambda: E.gcn_forward(X, X, [host], [host[0]], host, host[0])}.items():
         with pytest.raises(ValueError, match=name):

@@ -3,7 +3,10 @@ reproduce the reference's own values in tests/golden/ops.npz within the float32 
 tests/test_oracle_golden.py for the same keys); (b) every case of tests/test_gpu_ops.py can tell a wrong kernel from a right
 one: under each defect that applies to it the float64 answer moves by at least 10 of the case's bounds (a condition on the
 inputs: a case that misses it gets other inputs, never another factor); (c) the refusals the arguments alone decide, with
-pointers that are never followed; (d) the wrappers refuse what they cannot hand to the C ABI."""
+pointers that are never followed; (d) the wrappers refuse what they cannot hand to the C ABI.
+mutual_information has a section of its own: its truth against the reference's double run (tests/golden/ops_kde.npz), its
+cases against their defects, a float32 emulation of the kernel values that has to stay within a third of the tolerances the
+GPU test asserts, and the bins of kde_bin (csrc/kde_kernels.hip) against torch.linspace bit for bit."""
 import argparse
 import ctypes
 import os
@@ -269,6 +272,80 @@ def test_bounds_are_first_order_sums_with_a_named_safety_factor():
     E = T._dist_err(x, x)
     r = (x.astype(np.float64) ** 2).sum(1)
     assert np.allclose(E[0, 0], 10 * T.U * 4 * r[0]) and np.allclose(T.distmat_bound(x), T.SAFETY * E)
+
+
+# ------------------------------------------------------------------------------------------------ mutual_information
+KDE_OPS = np.load(os.path.join(H.GOLDEN, "ops_kde.npz"))
+
+
+@pytest.mark.parametrize("tag", [str(c) for c in KDE_OPS["cases"]])
+def test_truth_mutual_information_is_the_reference(tag):
+    """The float64 truth against the reference module's run on double tensors: the value to 1e-12, the gradients (stored as
+    float32 in the fixture) to 1e-7 of their largest magnitude."""
+    z = KDE_OPS
+    v, gx, gy = T.mutual_information(z[f"{tag}_x"], z[f"{tag}_y"])
+    assert abs(v - float(z[f"{tag}_val64"][0])) <= 1e-12
+    assert rel(gx, z[f"{tag}_gx64"]) <= 1e-7 and rel(gy, z[f"{tag}_gy64"]) <= 1e-7
+
+
+def test_mutual_information_cases_cover_every_kernel_form():
+    """What the shapes are there for: the three template widths from both sides of their switches, one and several blocks of
+    k_kde_stats (64 rows) and k_kde_grad (128 rows) with and without a ragged tail, dozens of partials for k_kde_tables'
+    loop, both sides of the c > 32 switch, and wide square operands that reach 6, 7, 25 and 32 columns -- and 33, refused."""
+    shapes = {(m, c) for _, m, c in T.MI_CASES}
+    assert {c for _, c in shapes} >= {1, 2, 7, 8, 9, 16, 17, 32, 33} and {m for m, _ in shapes} >= {1, 2, 63, 64, 65, 128, 129, 257, 1030, 5000}
+    assert (32, 32) in shapes and (33, 33) in shapes and set(T.MI_RAW_CASES) <= set(T.MI_CASES)
+    for case in T.MI_CASES:
+        X, Y = T.mi_case(*case)
+        assert X.dtype == Y.dtype == np.float32 and X.shape == Y.shape == case[1:]
+        if case[2] > T.KDE_MAXC:
+            assert T.kde_reach(X, Y) == T.MI_REACH[case] <= T.KDE_MAXC, case
+    X, Y = T.mi_case("reach32", 300, 300)
+    assert X.max() == 27.0 == X[5, 27] and Y.max() <= 26.0
+    Xr, Yr = T.mi_refused_case()
+    assert Xr.max() == 27.5 and (Xr != X).sum() == 1 and T.kde_reach(Xr, Yr) == 33
+
+
+@pytest.mark.parametrize("kind,m,c", T.MI_CASES)
+def test_mutual_information_cases_resolve_their_defects(kind, m, c):
+    """Under every defect that applies the truth's value moves by FACTOR of its bound, or a gradient by FACTOR tolerances
+    (KDE_GRAD_TOL of that operand's largest magnitude); and the float32 emulation of the kernel values -- what a correct
+    evaluation returns -- uses at most a third of either, the condition that keeps the tolerances honest."""
+    X, Y = T.mi_case(kind, m, c)
+    v, gx, gy, b = T.mi_truth(kind, m, c)
+    mx, my = np.abs(gx).max(), np.abs(gy).max()
+    assert np.isfinite(v) and np.isfinite(gx).all() and np.isfinite(gy).all() and mx > 0 and my > 0
+    assert 1e3 * 2.0 ** -53 < b < 1e-4 * max(abs(v), 1e-2), (v, b)       # float32's part, well above the device's double arithmetic
+    ev, egx, egy = T.mutual_information_f32(X, Y)
+    assert abs(ev - v) <= b / 3, (abs(ev - v), b)
+    assert np.abs(egx - gx).max() <= T.KDE_GRAD_TOL / 3 * mx and np.abs(egy - gy).max() <= T.KDE_GRAD_TOL / 3 * my, (
+        np.abs(egx - gx).max() / mx, np.abs(egy - gy).max() / my)
+    if c > T.KDE_MAXC:           # cut at the reach: exact zeros from there on, something below it
+        act = T.MI_REACH[(kind, m, c)]
+        assert not egx[:, act:].any() and not egy[:, act:].any() and egx[:, :act].any() and egy[:, :act].any()
+        assert np.abs(gx[:, act:]).max() <= 1e-30 * mx and np.abs(gy[:, act:]).max() <= 1e-30 * my
+    defects = T.mi_defects(kind, m, c)
+    assert set(defects) <= set(T.MI_DEFECTS) and "no_marginal" in defects
+    for d in defects:
+        dv, dgx, dgy = T.mutual_information(X, Y, defect=d)
+        moved = (abs(dv - v) >= FACTOR * b or np.abs(dgx - gx).max() >= FACTOR * T.KDE_GRAD_TOL * mx
+                 or np.abs(dgy - gy).max() >= FACTOR * T.KDE_GRAD_TOL * my)
+        assert moved, (d, abs(dv - v) / b, np.abs(dgx - gx).max() / mx, np.abs(dgy - gy).max() / my)
+
+
+def test_every_mutual_information_defect_is_met_by_some_case():
+    met = {d for case in T.MI_CASES for d in T.mi_defects(*case)}
+    assert met == set(T.MI_DEFECTS)
+    assert "cols8" in T.mi_defects("nxn20", 257, 257) and "cols8" not in T.mi_defects("nxn2", 1030, 1030)
+    assert "lastcol" not in T.mi_defects("nxn1", 33, 33) and "lastcol" in T.mi_defects("emb", 32, 32)
+
+
+def test_kde_bins_are_torch_linspace_bit_for_bit():
+    """kde_bin's formula (csrc/kde_kernels.hip), evaluated in numpy with float32 roundings, against the reference's
+    torch.linspace(0, nb, nb).float() for every width up to 64 and every square size the cases and the fixture use."""
+    import torch
+    for nb in list(range(1, 65)) + [160, 200, 257, 300, 1030]:
+        assert T.kde_bins(nb).tobytes() == torch.linspace(0, nb, nb).float().numpy().tobytes(), nb
 
 
 # ------------------------------------------------------------------------------------------------------- (c) refusals
