@@ -794,6 +794,45 @@ int mcgra_gcn_forward(void* stream, int n, int nfeat, int nlayer, const int32_t*
                       const float* const* b, const float* Wlin, const float* blin,
                       int nclass, int emb_nlayer, float* emb_out, float* out);
 
+/* The LinkTeller influence attack of Wu et al., "LinkTeller: Recovering Private Edges from Graph Neural Networks via Influence
+ * Analysis" (IEEE S&P 2022): how much node u's output moves when node v's features are scaled, for every ordered pair.
+ *   - the victim is what mcgra_gcn_forward computes: H^0 = X, P^l = A (H^l W_l) + b_l, H^{l+1} = relu(P^l) for l = 0 .. L-1,
+ *     Z = H^L Wlin^T + blin, O = log_softmax(Z).  The model arguments are mcgra_gcn_forward's; A = adj is any dense n x n float32
+ *     propagation matrix (row stride ld_adj) whose support is symmetric: a_uw != 0 <=> a_wu != 0;
+ *   - for a source v, X^(v) is X with row v multiplied by (1 + Delta), Delta = float32(delta) (the paper's delta is 1e-4).
+ *     I[v -> u] = || O(X^(v))_u - O(X)_u ||_2 / Delta.  output = MCGRA_INFLUENCE_LOG_POSTERIORS takes O as the victim returns it,
+ *     MCGRA_INFLUENCE_POSTERIORS takes exp(O).  symmetrize = 0: out[v][u] = I[v -> u] (the row is the source; the diagonal is the
+ *     self-influence); symmetrize = 1: out[a][b] = max(I[a -> b], I[b -> a]), bitwise symmetric;
+ *   - the computed form is never two forwards subtracted in float32 (that carries u |O| / Delta of cancellation noise).  The base
+ *     pre-activations P^l are kept and the differences carried:  dT^0 = 0 except row v = Delta (x_v W_0);
+ *     dP^l_u = sum over w in F_l(v), ascending w, of a_uw dT^l_w;  dH^{l+1}_u = max(dP, -P) if P > 0 else max(P + dP, 0), which is
+ *     relu(P + dP) - relu(P) without cancellation and follows a unit that the perturbation switches on or off;
+ *     dT^{l+1} = dH^{l+1} W_{l+1};  dZ = dH^L Wlin^T;  dlogp_k = dZ_k - log1p(sum_j p_j expm1(dZ_j)), p = exp(O);
+ *     dp_k = p_k expm1(dlogp_k); the norm is the square root of the sum over k ascending of the squares, divided by Delta;
+ *   - the frontier is structural: F_0(v) = {v}, F_{l+1}(v) = {u : a_uw != 0 for some w in F_l(v)}.  Outside F_L(v) the output is
+ *     exactly +0.0.  One source costs its L-hop neighbourhood, not n rows; a frontier that reaches all n nodes (a hub, a complete
+ *     graph, an EdgeRand graph at small eps) is computed correctly but walks dense row lists: counts[1] tells;
+ *   - out: device n x n (row stride ld_out); columns from n to ld_out are not touched.  counts (host int64[3]) = {the non-zero
+ *     cells of adj, the reached ordered pairs sum_v |F_L(v)|, max_v |F_L(v)|}: exact integers, the same on every call;
+ *   - every sum has a fixed order and no float is merged atomically: the same bits on every call and on every grid (the number of
+ *     workgroups follows the device and the scratch budget; MCGRA_INFLUENCE_GROUPS in the environment lowers it);
+ *   - MCGRA_EINVAL before any HIP call, nothing written: a NULL pointer (W[l], b[l] included), n, nfeat or nclass < 1, a width
+ *     < 1, dims[0] != nfeat, an ld below n, nlayer outside 1 .. MCGRA_MAX_LAYERS, a delta whose float32 is not finite, is 0 or has
+ *     |Delta| >= 1, output or symmetrize outside 0 / 1.  MCGRA_ENOSUP: n > 65 535, a hidden width or nclass above
+ *     MCGRA_INFLUENCE_MAX_WIDTH (one lane owns one column).  MCGRA_EINVAL with counts not written: an asymmetric support, a NaN
+ *     or an infinity in adj, X or the weights, a base output that is not finite (X W_0, a pre-activation, which relu would hide,
+ *     or O); out is not written then either.
+ * Synchronises `stream`.  Device scratch: the base forward's node buffers ((L + 4) n hm floats and mcgra_gcn_forward's product
+ * workspace of 64 n hm floats, hm the widest layer), the row lists (8 bytes per non-zero cell of adj, 8 n bytes of offsets) and
+ * two slabs of n x hm floats per workgroup, at most 512 MB of them together; MCGRA_ENOMEM when that cannot be allocated. */
+#define MCGRA_INFLUENCE_MAX_WIDTH 64
+#define MCGRA_INFLUENCE_LOG_POSTERIORS 0
+#define MCGRA_INFLUENCE_POSTERIORS 1
+int mcgra_influence_scores(void* stream, int n, int nfeat, int nlayer, const int32_t* dims, const float* X, const float* adj,
+                           int ld_adj, const float* const* W, const float* const* b, const float* Wlin, const float* blin,
+                           int nclass, double delta, int output, int symmetrize, float* out, int ld_out,
+                           int64_t* counts /* host[3]: nnz, reached, max_reach */);
+
 /* -------------------------------------------------------- attack engine --
  * One object per PGDAttack instance.  It owns the learnable adjacency
  * (adj_changes, kept dense-symmetric in HBM), the Adam moments and all

@@ -51,7 +51,7 @@ SYMBOLS = [
     "mcgra_class_auc",
     "mcgra_subset_auc", "mcgra_attack_finalize_components",
     "mcgra_pair_metric_name", "mcgra_pair_distance_scores", "mcgra_pair_distance_rank_metrics",
-    "mcgra_dp_perturb_graph",
+    "mcgra_dp_perturb_graph", "mcgra_influence_scores",
 ]
 
 # the metric ids MCGRA_PAIR_* of include/mcgra.h, in id order (mcgra_pair_metric_name is the library's copy)
@@ -159,6 +159,9 @@ def _load():
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
         "mcgra_dp_perturb_graph": [vp, C.c_int, fp, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, fp, C.c_int, fp, C.c_int,
                                    C.POINTER(C.c_int64), C.POINTER(C.c_double)],
+        "mcgra_influence_scores": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.c_int, C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_double, C.c_int, C.c_int, fp, C.c_int,
+                                   C.POINTER(C.c_int64)],
         "mcgra_mutual_information": [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp],
         "mcgra_gcn_forward": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_void_p),
                               C.POINTER(C.c_void_p), fp, fp, C.c_int, C.c_int, fp, fp],

@@ -1631,6 +1631,95 @@ def gcn_forward(X, adj, W, b, Wlin, blin, emb_nlayer=0):
     return out, emb
 
 
+INFLUENCE_OUTPUTS = ("log_posteriors", "posteriors")      # MCGRA_INFLUENCE_LOG_POSTERIORS, MCGRA_INFLUENCE_POSTERIORS (include/mcgra.h)
+INFLUENCE_SYMMETRIZE = ("directed", "max")
+INFLUENCE_MAX_N = 65535
+INFLUENCE_MAX_WIDTH = 64                                  # MCGRA_INFLUENCE_MAX_WIDTH: one lane owns one column
+
+
+def victim_gcn_tensors(model):
+    """(W, b, Wlin, blin) of a models.gcn.GCN, as gcn_forward and influence_scores take them; ValueError for a victim that is
+    not one (GraphSAGE's self weights, GAT's attention heads, a GCN without relu or without biases)."""
+    gc, lin = getattr(model, "gc", None), getattr(model, "linear1", None)
+    if (type(model).__name__ != "GCN" or not gc or lin is None or not getattr(model, "with_relu", True)
+            or any(getattr(l, "weight", None) is None or getattr(l, "bias", None) is None for l in gc) or lin.bias is None):
+        raise ValueError("influence_scores: the victim must be a models.gcn.GCN with relu and biases (GraphSAGE and GAT victims "
+                         "are not covered)")
+    return [l.weight for l in gc], [l.bias for l in gc], lin.weight, lin.bias
+
+
+def influence_scores(model_or_tensors, X, adj, delta=1e-4, output="posteriors", symmetrize="max"):
+    """The LinkTeller influence attack of Wu et al. (IEEE S&P 2022) on a GCN victim (mcgra_influence_scores): entry (v, u) of the
+    directed matrix is || O(X with row v scaled by 1 + Delta)_u - O(X)_u ||_2 / Delta, Delta = float32(delta), O the victim's
+    log-posteriors (output "log_posteriors") or their exp ("posteriors"); symmetrize "max" (the pair score
+    max(I[a -> b], I[b -> a]), bitwise symmetric) or "directed" (the row is the source).  model_or_tensors: a models.gcn.GCN or
+    (W, b, Wlin, blin) as gcn_forward takes them; X n x nfeat; adj any dense n x n float32 propagation matrix with a symmetric
+    support, n <= 65 535, every width and the class count <= 64.  The differences are carried along the support, never two
+    forwards subtracted; outside the L-hop reach of a source the entry is exactly +0.0; the same bits on every call.
+    Returns (matrix, info): n x n float32 on adj's device, info = {"delta" (Delta as a float), "output", "symmetrize", "nnz"
+    (non-zero cells of adj), "reached" (ordered pairs within reach), "max_reach"}.  Rank the matrix with auc_delong,
+    topk_metrics and top_pairs.  ValueError, before anything is called on the device, for a bad argument; McgraError for an
+    asymmetric support or a NaN / infinity in an operand or in the victim's base output."""
+    if not (isinstance(output, str) and output in INFLUENCE_OUTPUTS):
+        raise ValueError(f"influence_scores: output {output!r}: one of {', '.join(INFLUENCE_OUTPUTS)}")
+    if not (isinstance(symmetrize, str) and symmetrize in INFLUENCE_SYMMETRIZE):
+        raise ValueError(f"influence_scores: symmetrize {symmetrize!r}: one of {', '.join(INFLUENCE_SYMMETRIZE)}")
+    if isinstance(delta, bool) or not isinstance(delta, (int, float, np.integer, np.floating)):
+        raise ValueError(f"influence_scores: delta = {delta!r}; a number")
+    with np.errstate(over="ignore"):
+        d32 = float(np.float32(delta))
+    if not math.isfinite(d32) or d32 == 0.0 or abs(d32) >= 1.0:
+        raise ValueError(f"influence_scores: delta = {delta!r}; its float32 must be finite, not 0 and below 1 in magnitude")
+    if isinstance(model_or_tensors, (tuple, list)):
+        if len(model_or_tensors) != 4:
+            raise ValueError("influence_scores: the victim as tensors is (W, b, Wlin, blin)")
+        W, b, Wlin, blin = model_or_tensors
+    else:
+        W, b, Wlin, blin = victim_gcn_tensors(model_or_tensors)
+    W, b = list(W), list(b)
+    if not 1 <= len(W) <= _lib.MAX_LAYERS or len(b) != len(W):
+        raise ValueError(f"influence_scores: {len(W)} layers with {len(b)} biases; 1 to {_lib.MAX_LAYERS} layers, one bias each")
+    ts = [X, adj, Wlin, blin] + W + b
+    if any(not isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("influence_scores: X, adj and every weight must be tensors")
+    if X.dim() != 2 or adj.dim() != 2 or adj.shape[0] != adj.shape[1] or adj.shape[0] != X.shape[0] or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"influence_scores: X of shape {tuple(X.shape)} and adj of shape {tuple(adj.shape)}; n x nfeat and n x n")
+    widths = [X.shape[1]]
+    for l, (w, x) in enumerate(zip(W, b)):
+        if w.dim() != 2 or w.shape[0] != widths[-1] or w.shape[1] < 1 or tuple(x.shape) != (w.shape[1],):
+            raise ValueError(f"influence_scores: layer {l} has a weight of shape {tuple(w.shape)} and a bias of shape "
+                             f"{tuple(x.shape)} behind {widths[-1]} columns")
+        widths.append(w.shape[1])
+    if Wlin.dim() != 2 or Wlin.shape[1] != widths[-1] or Wlin.shape[0] < 1 or tuple(blin.shape) != (Wlin.shape[0],):
+        raise ValueError(f"influence_scores: the head has a weight of shape {tuple(Wlin.shape)} and a bias of shape "
+                         f"{tuple(blin.shape)} behind {widths[-1]} columns")
+    if adj.shape[0] > INFLUENCE_MAX_N or max(widths[1:] + [Wlin.shape[0]]) > INFLUENCE_MAX_WIDTH:
+        raise ValueError(f"influence_scores: n = {adj.shape[0]}, widths {widths[1:]}, {Wlin.shape[0]} classes; up to "
+                         f"{INFLUENCE_MAX_N} nodes and {INFLUENCE_MAX_WIDTH} columns")
+    return _influence_scores(adj, X, W, b, Wlin, blin, float(delta), INFLUENCE_OUTPUTS.index(output),
+                             INFLUENCE_SYMMETRIZE.index(symmetrize))
+
+
+@_device_operands
+def _influence_scores(adj, X, W, b, Wlin, blin, delta, output, symmetrize):
+    dev = adj.device
+    adj = _rows_f32(adj, dev)
+    X, Wlin, blin = (_f32(t).to(dev) for t in (X, Wlin, blin))
+    W, b = [_f32(w).to(dev) for w in W], [_f32(x).to(dev) for x in b]
+    n, nfeat = X.shape
+    L = len(W)
+    dims = (C.c_int32 * (L + 1))(*([nfeat] + [w.shape[1] for w in W]))
+    Wp = (C.c_void_p * L)(*[w.data_ptr() for w in W])
+    bp = (C.c_void_p * L)(*[x.data_ptr() for x in b])
+    out = torch.empty(n, n, device=dev, dtype=torch.float32)
+    counts = (C.c_int64 * 3)()
+    check(lib.mcgra_influence_scores(_stream(), n, nfeat, L, dims, _p(X), _p(adj), adj.stride(0), Wp, bp, _p(Wlin), _p(blin),
+                                     Wlin.shape[0], delta, output, symmetrize, _p(out), out.stride(0), counts))
+    info = {"delta": float(np.float32(delta)), "output": INFLUENCE_OUTPUTS[output], "symmetrize": INFLUENCE_SYMMETRIZE[symmetrize],
+            "nnz": int(counts[0]), "reached": int(counts[1]), "max_reach": int(counts[2])}
+    return out, info
+
+
 # ---------------------------------------------------------------- the engine
 def attack_config(n, dims, nclass, emb_nlayer, measure, weight_sup, weight_param, lr, num_edges, n_attack, eps=0.0,
                   act="relu", head_act="none", has_self=False, fin_layers=(1, 2), plan=None):

@@ -87,7 +87,21 @@ graph, so each becomes a report about a defended victim.  The result gains `defe
 the realised flip probability or the count's noise, and the defended victim's test accuracy: the utility side of the trade) and
 one `defense ...` line; --mode evaluate also reports auc_perturbed_*, the AUC of modified_adj against the perturbed graph: which of
 the two graphs the attack recovered.  --save_defense PATH: the perturbed graph's edge list in packed order, the pairs added and
-removed, and those scalars.  --mode evaluate, notrain_test and link_stealing.
+removed, and those scalars.  --mode evaluate, notrain_test, link_stealing and link_teller.
+--mode link_teller (not in the reference) is the attack those two mechanisms were designed against, the influence attack of Wu et
+al., "LinkTeller" (IEEE S&P 2022): link_stealing's flow up to the priors -- no attack, no engine object, nothing written -- then every
+node's features are scaled by 1 + delta in turn (--lt_delta, default 1e-4) and every other node's posteriors are watched:
+I[v -> u] = || O(X^(v))_u - O(X)_u ||_2 / delta, a pair's score max(I[a -> b], I[b -> a]) (engine.influence_scores: the differences are
+carried along the graph's support on the GPU, one source costs its L-hop neighbourhood, not a forward pass).  The victim answers from
+the graph it was trained and tested on, normalised (the perturbed graph under --dp_defense); --lt_graph raw queries the un-normalised
+graph of the priors instead, without self-loops, where a 2-layer victim's influence follows walks of exactly two steps and neighbours
+without a common neighbour score 0.  --arch gcn only.  For the outputs `log_posteriors` and `posteriors` and the sets attack, train and
+all: the AUC (engine.auc_delong's, of the unordered pairs) and, for the paper's density beliefs 1/4, 1/2, 1, 2 and 4, the precision,
+recall and F1 of the k = belief x (true edge count) best pairs (engine.topk_metrics); one `link teller <output>: auc_attack=...
+auc_train=... auc_all=...` line per output and one belief line per output and set.  --save_linkteller PATH: the whole graph's best pairs
+per output (as many as it has true edges, engine.top_pairs), the counts and the parameters as an .npz.  --ap and every report flag are
+refused in this mode.  --versus linkteller:posteriors|log_posteriors (--mode evaluate, with --ci or --ci_nodes, --arch gcn) takes that
+matrix (normalised graph, delta 1e-4) as the other side of the paired tests.
 Not provided (each exits with a message naming the reference line): --mode search/baseline/gaussian/gcn_attack.
 
 Several GPUs of one node -- one process per GPU, RCCL over xGMI:
@@ -132,6 +146,7 @@ class _Parser(argparse.ArgumentParser):
         args = super().parse_args(*a, **k)
         for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS:
             r.check(args, self.error)
+        reports.check_link_teller_args(args, self.error)
         return args
 
 
@@ -154,7 +169,7 @@ def build_parser():
     p.add_argument('--iter', type=int, default=1)
     p.add_argument('--max_eval', type=int, default=100)
     p.add_argument('--log_name', type=str, default="result.txt")
-    p.add_argument("--mode", type=str, default="evaluate", choices=["evaluate", "prepare", "notrain_test", "link_stealing"])
+    p.add_argument("--mode", type=str, default="evaluate", choices=["evaluate", "prepare", "notrain_test", "link_stealing", reports.LINKTELLER_MODE])
     p.add_argument("--measure", type=str, default="HSIC", choices=["HSIC", "MSELoss", "KL", "KDE", "CKA", "DP"])
     p.add_argument("--measure2", type=str, default="HSIC")
     p.add_argument("--nofeature", action='store_true')
@@ -204,6 +219,9 @@ def build_parser():
     p.add_argument('--dp_eps', type=float, default=argparse.SUPPRESS)          # with --dp_defense: the edge-level privacy budget
     p.add_argument('--dp_seed', type=int, default=argparse.SUPPRESS)           # with --dp_defense: the mechanism's seed (default: --seed)
     p.add_argument('--save_defense', type=str, default=argparse.SUPPRESS)      # with --dp_defense: the perturbed graph and what changed as an .npz
+    p.add_argument('--lt_graph', type=str, choices=list(reports.LINKTELLER_GRAPHS), default=argparse.SUPPRESS)   # --mode link_teller: the graph queried
+    p.add_argument('--lt_delta', type=float, default=argparse.SUPPRESS)        # --mode link_teller: the relative feature perturbation (1e-4)
+    p.add_argument('--save_linkteller', type=str, default=argparse.SUPPRESS)   # --mode link_teller: the best pairs, counts and parameters as an .npz
     return p
 
 
@@ -312,6 +330,19 @@ def link_stealing_lines(res, want_ap):
     return lines
 
 
+def link_teller_scores(victim_model, features, victim_graph, graph, delta, outputs=None):
+    """The LinkTeller pair scores of this run's victim: {output: n x n matrix} over `outputs` (default: engine.INFLUENCE_OUTPUTS)
+    and the info of the call.  graph "normalised": the victim is queried on utils.normalize_adj_tensor(victim_graph), what it was
+    trained and tested on; "raw": on victim_graph as it is, what the priors are computed from."""
+    query = victim_graph if graph == "raw" else utils.normalize_adj_tensor(victim_graph)
+    feats = features.to_dense() if features.is_sparse else features
+    matrices, info = {}, None
+    for output in outputs or engine.INFLUENCE_OUTPUTS:
+        matrices[output], info = engine.influence_scores(victim_model, feats, query, delta, output, "max")
+    return matrices, {"delta": info["delta"], "graph": graph, "nnz": info["nnz"], "reached": info["reached"],
+                      "max_reach": info["max_reach"]}
+
+
 def victim_tensors(m):
     """Every parameter of a victim: the registered ones and those of the layers it keeps in plain lists (models/gcn.py:44,
     graphsage.py:50, gat.py:47 -- as the reference's classes do)."""
@@ -396,6 +427,7 @@ def log_lines(res, ctx):
 def _run(args, rank, world):
     for r in reports.EVALUATE_REPORTS + reports.LATER_REPORTS:
         r.check(args, _exit)
+    reports.check_link_teller_args(args, _exit)
     device = torch.device(args.device)
     np.random.seed(args.seed); random.seed(args.seed); torch.manual_seed(args.seed)       # main.py:142-146
     data = Dataset(root=args.dataset_root, name=args.dataset, setting='GCN')
@@ -511,11 +543,30 @@ def _run(args, rank, world):
         if rank == 0:
             print("\n".join(link_stealing_lines(res["link_stealing"], want_ap)))
         return res
+    if args.mode == reports.LINKTELLER_MODE:                                               # no attack either
+        sets = {"attack": idx_attack, "train": idx_train, "all": None}
+        with torch.no_grad():
+            matrices, lt_info = link_teller_scores(victim_model, fd, vd, getattr(args, "lt_graph", reports.LINKTELLER_GRAPHS[0]),
+                                                   getattr(args, "lt_delta", reports.LINKTELLER_DELTA))
+        res = {"link_teller": {output: reports.link_teller_metrics(ad, S, sets) for output, S in matrices.items()},
+               "link_teller_info": lt_info}
+        if defense is not None:
+            res["defense"] = dict(defense["info"])
+        if rank == 0:
+            print("\n".join(reports.link_teller_lines(res["link_teller"])))
+            if getattr(args, "save_linkteller", None):
+                reports.save_linkteller(args.save_linkteller, ad, matrices, res["link_teller"], lt_info)
+        return res
     versus = getattr(args, "versus", None)
     other = None
     if versus is not None:  # refused before the attack runs, not after it
-        baseline = reports.versus_baseline(versus, _exit)
-        if baseline is not None:
+        influence = reports.versus_linkteller(versus, _exit)      # read ahead of versus_baseline, which keeps every other value
+        baseline = reports.versus_baseline(versus, _exit) if influence is None else None
+        if influence is not None:
+            with torch.no_grad():
+                other = link_teller_scores(victim_model, fd, vd, reports.LINKTELLER_GRAPHS[0], reports.LINKTELLER_DELTA,
+                                           (influence,))[0][influence]
+        elif baseline is not None:
             other = engine.pair_distance_scores(link_sources(Y_A, H_A2, features, device)[baseline[0]], baseline[1])
         else:
             other = feature_adj if versus == "features" else reports.load_versus(versus, adj.shape[0])

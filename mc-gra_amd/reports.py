@@ -196,13 +196,107 @@ def versus_baseline(versus, fail):
     return source, metric
 
 
+LINKTELLER_MODE = "link_teller"
+LINKTELLER_GRAPHS = ("normalised", "raw")       # --lt_graph: what the victim is queried on
+LINKTELLER_DELTA = 1e-4                         # --lt_delta's default, the paper's
+# the density beliefs of Wu et al. (IEEE S&P 2022, section VI): the attacker takes the k = belief x (true edge count) best pairs
+LINKTELLER_BELIEFS = (0.25, 0.5, 1.0, 2.0, 4.0)
+LINKTELLER_FLAGS = ("lt_graph", "lt_delta", "save_linkteller")
+
+
+def versus_linkteller(versus, fail):
+    """--versus linkteller:OUTPUT, the LinkTeller influence matrix of the run's own victim, as OUTPUT (one of
+    engine.INFLUENCE_OUTPUTS); None for any other value, which versus_baseline then reads as it always did."""
+    source, sep, output = (versus or "").partition(":")
+    if not sep or source != "linkteller":
+        return None
+    if output not in engine.INFLUENCE_OUTPUTS:
+        fail(f"--versus {versus}: output `{output}` is not one of {', '.join(engine.INFLUENCE_OUTPUTS)}")
+    return output
+
+
+def check_link_teller_args(args, fail):
+    """--mode link_teller and its flags, and --versus linkteller:OUTPUT: what can be refused from the command line alone."""
+    mode, arch = getattr(args, "mode", None), getattr(args, "arch", "gcn")
+    for flag in LINKTELLER_FLAGS:
+        if flag in vars(args) and mode != LINKTELLER_MODE:
+            fail(f"--{flag} needs --mode {LINKTELLER_MODE}")
+    if versus_linkteller(getattr(args, "versus", None), fail) is not None and arch != "gcn":
+        fail(f"--versus {args.versus} queries a GCN victim (engine.influence_scores): --arch gcn only, not --arch {arch}")
+    if mode != LINKTELLER_MODE:
+        return
+    if arch != "gcn":
+        fail(f"--mode {LINKTELLER_MODE} queries a GCN victim (engine.influence_scores): --arch gcn only, not --arch {arch}")
+    if getattr(args, "ap", False):
+        fail(f"--ap adds the average precision of a ranking that is sorted: --mode evaluate, notrain_test and link_stealing only, "
+             f"not --mode {mode}")
+    if getattr(args, "lt_graph", LINKTELLER_GRAPHS[0]) not in LINKTELLER_GRAPHS:
+        fail(f"--lt_graph takes one of {', '.join(LINKTELLER_GRAPHS)}, not {args.lt_graph!r}")
+    delta = getattr(args, "lt_delta", LINKTELLER_DELTA)
+    with np.errstate(over="ignore"):
+        d32 = float(np.float32(delta))
+    if not (np.isfinite(d32) and d32 != 0.0 and abs(d32) < 1.0):
+        fail(f"--lt_delta takes a perturbation whose float32 is finite, not 0 and below 1 in magnitude, not {delta!r}")
+    if getattr(args, "save_linkteller", None) == "":
+        fail("--save_linkteller takes the path of the .npz to write")
+
+
+def belief_k(belief, positives, pairs):
+    """k of a density belief: belief x the true edge count, rounded half up, clamped to the pair count."""
+    return min(int(Fraction(belief) * positives + Fraction(1, 2)), pairs)
+
+
+def link_teller_metrics(real, matrix, sets):
+    """One influence matrix scored against the true graph on every index set: {set: {"auc", "pairs", "positives" (engine.auc_delong's)
+    and "beliefs": {belief: {"k", "hits", "precision", "recall", "f1"}} over LINKTELLER_BELIEFS (engine.topk_metrics at belief_k)}}."""
+    out = {}
+    for name, ix in sets.items():
+        d = engine.auc_delong(real, matrix, ix)
+        beliefs = {}
+        for belief in LINKTELLER_BELIEFS:
+            k = belief_k(belief, d["positives"], d["pairs"])
+            if k > 0:
+                t = engine.topk_metrics(real, matrix, k, ix)
+                beliefs[belief] = {key: t[key] for key in ("k", "hits", "precision", "recall", "f1")}
+            else:       # (k = 0 would ask engine.topk_metrics for the true edge count)
+                none = float("nan") if d["positives"] == 0 else 0.0
+                beliefs[belief] = {"k": 0, "hits": 0, "precision": float("nan"), "recall": none, "f1": none}
+        out[name] = {"auc": d["auc"], "pairs": d["pairs"], "positives": d["positives"], "beliefs": beliefs}
+    return out
+
+
+def link_teller_lines(res):
+    """Per output of link_teller_metrics' results: the AUC line, then one belief line per index set."""
+    lines = []
+    for output, by_set in res.items():
+        lines.append(f"link teller {output}: " + " ".join(f"auc_{name}={d['auc']}" for name, d in by_set.items()))
+        for name, d in by_set.items():
+            lines.append(f"link teller {output} {name} beliefs: " + " ".join(
+                f"{belief}:k={b['k']},P={b['precision']},R={b['recall']},F1={b['f1']}" for belief, b in d["beliefs"].items()))
+    return lines
+
+
+def save_linkteller(path, real, matrices, res, info):
+    """--save_linkteller: per output the whole graph's P best pairs in ranking order, P its true edge count (engine.top_pairs:
+    pairs_<output> [P, 2] int64, scores_<output>, hits_<output>), the AUC of the whole graph, and the run's parameters and counts."""
+    arrays = {k: np.array(v) for k, v in info.items()}
+    for output, matrix in matrices.items():
+        d = res[output]["all"]
+        if d["positives"] > 0:
+            pairs, scores, hits = (t.cpu().numpy() for t in engine.top_pairs(matrix, d["positives"], None, real))
+        else:
+            pairs, scores, hits = np.zeros((0, 2), np.int64), np.zeros(0, np.float32), np.zeros(0, bool)
+        arrays.update({f"pairs_{output}": pairs, f"scores_{output}": scores, f"hits_{output}": hits, f"auc_{output}": np.float64(d["auc"])})
+    _save_npz(path, **arrays)
+
+
 def check_ci_args(args, fail):
     ci, versus, scores = getattr(args, "ci", False), getattr(args, "versus", None), getattr(args, "save_scores", None)
     if versus is not None and not ci and not getattr(args, "ci_nodes", False):
         fail("--versus needs --ci or --ci_nodes")
     if versus is not None and versus == "":
         fail("--versus takes `features` or the path of an .npy score matrix")
-    if versus is not None:
+    if versus is not None and versus_linkteller(versus, fail) is None:      # (read ahead of the SOURCE:METRIC shortcut)
         versus_baseline(versus, fail)
     if ci and args.mode != "evaluate":
         fail(f"--ci puts an interval on the AUC of the attack's modified_adj: --mode evaluate only, not --mode {args.mode}")
@@ -782,8 +876,8 @@ def check_defense_args(args, fail):
         fail(f"--dp_seed takes an integer in [0, 2^64), not {defense_seed(args)!r} (it defaults to --seed)")
     if getattr(args, "save_defense", None) == "":
         fail("--save_defense takes the path of the .npz to write")
-    if args.mode not in DEFENSE_MODES:
-        fail(f"--dp_defense perturbs the graph the victim is trained on: --mode {', '.join(DEFENSE_MODES)} only, "
+    if args.mode not in DEFENSE_MODES + (LINKTELLER_MODE,):      # (DEFENSE_MODES is pinned as it was before --mode link_teller)
+        fail(f"--dp_defense perturbs the graph the victim is trained on: --mode {', '.join(DEFENSE_MODES + (LINKTELLER_MODE,))} only, "
              f"not --mode {args.mode}")
 
 
